@@ -94,11 +94,51 @@ def parse_args():
     ap.add_argument("--path", default="rows", choices=["rows", "fields", "run1"],
                     help="rows: AoS xx_carr -> margins (the headline); fields: the fused SoA call, 27 MAPL fields -> "
                          "10**pred*OHscale; run1: OHXBoosterRun1Device, imports -> INTERNAL OH (both 1 GPU only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path handed its caller in the last step as "
+                         "DIR/<name>.npy (rank 0): rows -> margins (the gathered field with N > 1), fields -> oh, "
+                         "run1 -> oh, oh_boost (float32) and k_slab (float64).  At most 64 MB in all: a larger array is cut to a fixed "
+                         "seeded sample of its elements (dump_index), in index order")
     args = ap.parse_args()
     args.verify = not args.no_verify
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.path != "rows" and args.gpus != 1:
         ap.error(f"--path {args.path} is a single-GPU measurement")       # every rank, before any collective
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)           # the ranks of --gpus N start in ROOT
     return args
+
+
+DUMP_BYTES = 64 * 10**6        # --dump-outputs: all files together
+DUMP_SEED = 20240613
+
+
+def dump_index(n, k):
+    """The elements --dump-outputs keeps of an n-element output when only k fit: a fixed seeded sample, sorted, the
+    same for every run with the same n and k (None = all of them)."""
+    if k >= n:
+        return None
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+
+
+def dump_outputs(outdir, arrays):
+    """--dump-outputs: `arrays` (name -> device tensor or host array) as outdir/<name>.npy, float32 kept as it is and
+    anything else as float64, each cut to dump_index() when the files would exceed DUMP_BYTES together."""
+    os.makedirs(outdir, exist_ok=True)
+    share = (DUMP_BYTES - 4096 * len(arrays)) // len(arrays)          # 4 KiB: room for an .npy header
+    for name, a in arrays.items():
+        on_device = isinstance(a, torch.Tensor)
+        flat = a.reshape(-1) if on_device else np.asarray(a).reshape(-1)
+        dtype = np.float32 if flat.dtype == (torch.float32 if on_device else np.float32) else np.float64
+        pick = dump_index(flat.shape[0], share // np.dtype(dtype).itemsize)
+        if on_device:
+            if pick is not None:
+                flat = flat[torch.from_numpy(pick).to(flat.device)]
+            flat = flat.cpu().numpy()
+        elif pick is not None:
+            flat = flat[pick]
+        np.save(os.path.join(outdir, f"{name}.npy"), np.ascontiguousarray(flat, dtype=dtype))
 
 
 def cpu_model_name():
@@ -503,6 +543,8 @@ def bench_run1(args, grid, n_total, model, booster, dev, t_model):
     torch.cuda.synchronize()
     per_step = (time.perf_counter() - t0) / args.steps
     booster.check()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"oh": oh, "oh_boost": boost, "k_slab": [k1.value, k2.value]})
     nslab = plane * (k2.value - k1.value + 1)
     # ALGORITHMIC bytes of a Run1 tick: every import read once (3 edge fields, 28 layer fields - T, Q, TAUCLW, TAUCLI, seven
     # scattering coefficients, sixteen features used as they are, the default OH - and six 2-D fields), INTERNAL OH
@@ -628,6 +670,8 @@ def bench_fields(args, grid, n_total, model, booster, dev, t_model):
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     booster.check()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"oh": oh})
     info = booster.info()
     algo = 4 * (23 * n_total + 4 * plane + n_total) + info["node_bytes"]
     per_step = elapsed / args.steps
@@ -676,7 +720,9 @@ def launch_ranks(args):
     env.setdefault("OMP_NUM_THREADS", str(max(1, (os.cpu_count() or 8) // args.gpus)))
     for k in ("RANK", "LOCAL_RANK", "MASTER_PORT"):          # a stale one would send the ranks elsewhere
         env.pop(k, None)
-    cmd = launcher_argv(args.gpus, sys.argv[1:], free_port())
+    # the ranks start in ROOT: the last --dump-outputs wins, so name the caller's directory absolutely
+    argv = sys.argv[1:] + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])
+    cmd = launcher_argv(args.gpus, argv, free_port())
     print("bench: starting %d ranks: %s" % (args.gpus, " ".join(cmd)), file=sys.stderr, flush=True)
     proc = subprocess.Popen(cmd, env=env, stdout=subprocess.PIPE, text=True, cwd=ROOT)
     lines = 0
@@ -876,6 +922,8 @@ def main():
     fence()
     elapsed = time.perf_counter() - t0
     booster.check()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"margins": out_full})
     my_step_ms = elapsed / args.steps * 1e3
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)

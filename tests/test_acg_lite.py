@@ -1,5 +1,6 @@
 """tools/acg_lite.py - the stand-in for MAPL's code generator that oracle/Makefile uses to compile the reference's own
 parent grid component in place - and tests/golden/make_oh_specs.py, which pins the OH spec table with the same parser."""
+import importlib.util
 import json
 import os
 import subprocess
@@ -71,11 +72,18 @@ def test_acg_lite_reads_a_state_spec_table_and_writes_the_five_headers(tmp_path)
 
 
 def test_the_committed_oh_spec_table_is_what_the_reference_says_today(tmp_path):
-    """Where the reference is at hand (this container), tests/golden/oh_specs.json is regenerated and must be the
-    committed file: the golden cannot drift from the files it was read from."""
-    if not os.path.exists("/root/reference/OH_GridComp/OH_StateSpecs.rc"):
-        pytest.skip("no /root/reference here")
+    """tests/golden/oh_specs.json is a table, and where the reference is at hand (make_oh_specs.py's REF, set by
+    OHX_REFERENCE) it is regenerated and must be the committed file: the golden cannot drift from the files it was
+    read from."""
     committed = json.load(open(os.path.join(helpers.GOLDEN, "oh_specs.json")))
+    # it is a table, not text of the reference: names and flags only
+    assert set(committed) == {"made_by", "state_specs", "conditional_imports", "conditions", "data_instance", "mapl_defaults"}
+    assert len(committed["state_specs"]["EXPORT"]) == 32 and len(committed["conditional_imports"]["IMPORT_24"]) == 16
+    maker = importlib.util.spec_from_file_location("make_oh_specs", os.path.join(helpers.GOLDEN, "make_oh_specs.py"))
+    make_oh_specs = importlib.util.module_from_spec(maker)
+    maker.loader.exec_module(make_oh_specs)
+    if not (os.path.exists(make_oh_specs.RC) and os.path.exists(make_oh_specs.F90)):
+        pytest.skip(f"no reference at {make_oh_specs.REF} (OHX_REFERENCE) to regenerate the table from")
     src = open(os.path.join(helpers.GOLDEN, "make_oh_specs.py")).read()
     patched = tmp_path / "make_oh_specs.py"
     patched.write_text(src.replace('path = os.path.join(ROOT, "tests", "golden", "oh_specs.json")',
@@ -85,6 +93,3 @@ def test_the_committed_oh_spec_table_is_what_the_reference_says_today(tmp_path):
     r = subprocess.run([sys.executable, str(patched)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-2000:]
     assert json.load(open(tmp_path / "oh_specs.json")) == committed
-    # and it is a table, not text of the reference: names and flags only
-    assert set(committed) == {"made_by", "state_specs", "conditional_imports", "conditions", "data_instance", "mapl_defaults"}
-    assert len(committed["state_specs"]["EXPORT"]) == 32 and len(committed["conditional_imports"]["IMPORT_24"]) == 16

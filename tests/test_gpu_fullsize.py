@@ -272,6 +272,38 @@ def test_bench_over_rccl_with_one_rank():
         assert line["config"]["planner_prices"]["gather_bytes_per_s"] == 60e9 and ("predict_only" in ph) == (gather == "both")
 
 
+def test_bench_dumps_what_its_timed_steps_computed(tmp_path):
+    """bench.py --dump-outputs: the margins of the last timed step are the oracle's, row for row; they do not depend on
+    --steps, which the line reports back with ms_per_step; the fused path dumps its OH field."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    small = ["--grid", "C48", "--trees", "20", "--depth", "10", "--sample-log2", "15", "--cpu-seconds", "0", "--no-pcie"]
+
+    def bench(steps, out, *extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                            "--warmup", "1", "--dump-outputs", str(out), *small, *extra],
+                           capture_output=True, text=True, timeout=600, cwd=root)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
+        assert line["steps"] == steps and line["ms_per_step"] > 0
+        return line
+
+    bench(1, tmp_path / "one")
+    bench(3, tmp_path / "three")
+    assert os.listdir(tmp_path / "one") == ["margins.npy"]
+    got = np.load(tmp_path / "one" / "margins.npy")
+    assert got.dtype == np.float32 and got.shape == (48 * 288 * 72,)
+    assert np.array_equal(helpers.bits(got), helpers.bits(np.load(tmp_path / "three" / "margins.npy")))
+    model = synth.make_model(num_trees=20, max_depth=10, sample_log2=15)
+    want = helpers.oracle_predict(model.image, synth.rows_cpu(synth.GRIDS["C48"], 0, got.shape[0]), synth.XX_MISS)
+    assert np.array_equal(helpers.bits(got), helpers.bits(want))
+    bench(2, tmp_path / "fields", "--path", "fields")
+    oh = np.load(tmp_path / "fields" / "oh.npy")
+    assert oh.dtype == np.float32 and oh.shape == (48 * 288 * 72,) and np.all(oh > 0)
+
+
 def test_native_all_gather_entry_points_on_one_rank():
     """include/ohxgb.h part 4 with the one GPU of the box: RCCL is found and loaded by libohxgb.so itself, a
     communicator of one rank is built from a unique id, and OHXAllGatherOH puts the shard at its rows - out of place
