@@ -146,6 +146,9 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *   "ohx_brick" = "a,b,c", "ohx_brick_k_fastest", "ohx_prefetch", "ohx_coop_rows", "ohx_xcd_remap", "ohx_lds_pad", "ohx_overlap_group"
  *                     launch-shape knobs behind profiles/ *_sweeps.txt; the defaults are the measured best
  *   "ohx_top_levels", "ohx_line_slots", "ohx_min_chunk"  placement of the packed format
+ *   "ohx_contribs_split"  auto | off : OHXBoosterPredictContribs[Device]: a batch that leaves most of the chip's wave
+ *                     slots empty has its trees split over waves and the per-tree contributions summed in tree order by a
+ *                     second launch (auto), or one wave per 64 rows walks every tree (off); the same bits either way
  *   "ohx_device"      HIP device ordinal for this booster
  * None of them changes a prediction.
  * xgboost's own parameter names ("nthread", "predictor", ...) are accepted and
@@ -221,6 +224,41 @@ int OHXDMatrixInferGrid(DMatrixHandle handle, void* stream, int* found);
 int OHXBoosterPredictDevice(BoosterHandle handle, DMatrixHandle dmat, int option_mask, unsigned ntree_limit,
                             float* d_out, void* stream);
 int OHXBoosterCheck(BoosterHandle handle, void* stream);
+
+/* Per-feature contributions of each row, as xgboost 1.6.0's XGBoosterPredict with pred_contribs (approximate = 0:
+ * exact TreeSHAP, option_mask 4 there) or approx_contribs (approximate = 1, option_mask 8 there).  A separate entry
+ * point: XGBoosterPredict's option_mask is unchanged (and already departs from 1.6.0's bits: 16 = leaf indices here).
+ * Output: nrow x (F + 1) float32, row-major, F = the booster's num_feature; column F is the bias.  *out_len =
+ * nrow * (F + 1); *out_result is a host buffer owned by the booster, valid until its next contribs call or
+ * XGBoosterFree.  Both matrix forms; missing values as in the predict paths (NaN, the matrix's `missing`, columns
+ * the matrix does not have).  ntree_limit: 0 = all trees, else the first ntree_limit.
+ * Semantics, f = the margin XGBoosterPredict(option_mask = 1) returns; for each tree t of the range:
+ *   mean(n)  = the leaf value at a leaf, (mean(l) * cover(l) + mean(r) * cover(r)) / cover(n) at a split, in float in
+ *              this order (1.6.0 FillNodeMeanValues); cover = the node's sum_hess.
+ *   bias     = sum over trees of mean_t(root) in tree order from 0, then + the margin's base.
+ *   exact    = path-dependent TreeSHAP (Lundberg et al. 2020, Algorithm 2): at a split on feature j the row goes left
+ *              if x_j < cond, a missing value takes the default child; zero fraction cover(child) / cover(parent),
+ *              one fraction 1 if the row takes that child else 0; a feature that occurs again on a path has its
+ *              fractions multiplied into one element; phi_j goes to column j.
+ *   approximate = 1.6.0's CalculateContributionsApprox: along the row's path, mean(next) - mean(current) to the
+ *              split feature's slot, leaf - mean(last) to the last split's slot.
+ *   Each tree's contributions are accumulated on their own and added into the row's totals in tree order (1.6.0's
+ *   this_tree_contribs -> p_contribs).  Local accuracy: sum_j out[r][j] == f[r] up to rounding.  A row's bits do not
+ *   depend on the batch it is in, and the host and device forms agree bit for bit.  As everywhere in this library,
+ *   parity with libxgboost itself is not pinned (exact mode evaluates the same recurrences per leaf path in float32,
+ *   so its rounding differs from 1.6.0's recursive walk).
+ * Refused (-1, nothing enqueued): no model; an objective whose margin base is unknown (as option_mask 1); more
+ * columns than features; a split whose cover is not finite and > 0 (the model has no cover statistics - 1.6.0 would
+ * quietly produce NaN); a root-to-leaf path over more than 32 distinct features, or more than 128 features; d_out
+ * NULL; and, for the device form, a stream that is being captured: contributions are not capturable.
+ * Tables (node means, a path table per leaf - docs/12_contributions.md for their size) are built at the first call
+ * on a loaded model and kept until the model is replaced or XGBoosterFree; OHXReleaseScratch leaves them alone.
+ * Contributions use buffers of their own, never one of the predict, fields or Run1 paths.  The device form only
+ * enqueues on `stream`; +-inf in the rows is reported by the host form only. */
+int OHXBoosterPredictContribs(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
+                              bst_ulong* out_len, const float** out_result);
+int OHXBoosterPredictContribsDevice(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
+                                    float* d_out, void* stream);
 
 /* The whole of predict_OH_with_XGB's RUN section in one kernel
  * (OH_GridCompMod.F90:303-383): gathers the 27 MAPL fields in place (field f is

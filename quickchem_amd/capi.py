@@ -27,6 +27,7 @@ ABI_SYMBOLS = [
     "XGDMatrixSaveBinary", "XGDMatrixCreateFromFile", "XGBoosterCreate", "XGBoosterFree", "XGBoosterLoadModel",
     "XGBoosterSaveModel", "XGBoosterLoadModelFromBuffer", "XGBoosterPredict", "XGBoosterSetParam",
     "OHXDeviceCount", "OHXDMatrixCreateFromDevice", "OHXDMatrixSetGrid", "OHXDMatrixGetGrid", "OHXDMatrixInferGrid", "OHXBoosterPredictDevice", "OHXBoosterCheck",
+    "OHXBoosterPredictContribs", "OHXBoosterPredictContribsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
     "OHXJulianDay", "OHXSolarGeometry", "OHXSolarGeometryDevice", "OHXBoosterGetInfo", "OHXBoosterKernelSymbol", "OHXBoosterKernelSymbolRows",
     "OHXBoosterRingReruns", "OHXBoosterCopyEngineChoice", "OHXUnregisterHost", "OHXReleaseScratch",
@@ -109,6 +110,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.OHXDMatrixInferGrid.argtypes = [vp, vp, C.POINTER(i32)]
     lib.OHXBoosterPredictDevice.argtypes = [vp, vp, i32, C.c_uint, vp, vp]
     lib.OHXBoosterCheck.argtypes = [vp, vp]
+    lib.OHXBoosterPredictContribs.argtypes = [vp, vp, i32, C.c_uint, C.POINTER(u64), C.POINTER(C.POINTER(f32))]
+    lib.OHXBoosterPredictContribsDevice.argtypes = [vp, vp, i32, C.c_uint, vp, vp]
     lib.OHXBoosterPredictFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32,
                                             f32, i32, f32, vp, vp]
     lib.OHXBoosterPredictFieldsDevice.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32,
@@ -291,6 +294,24 @@ class Booster:
 
     def check(self, stream: int = 0) -> None:
         check(self.lib, self.lib.OHXBoosterCheck(self.handle, stream))
+
+    def predict_contribs(self, dmat: DMatrix, approximate: bool = False, ntree_limit: int = 0) -> np.ndarray:
+        """Per-feature contributions, (nrow, F + 1) float32, column F the bias (OHXBoosterPredictContribs): exact
+        TreeSHAP, or xgboost's approximate attribution with approximate=True."""
+        n = C.c_uint64()
+        ptr = C.POINTER(C.c_float)()
+        check(self.lib, self.lib.OHXBoosterPredictContribs(self.handle, dmat.handle, int(bool(approximate)), ntree_limit,
+                                                            C.byref(n), C.byref(ptr)))
+        nrow = dmat.num_row
+        if n.value == 0:
+            return np.empty((nrow, 0), dtype=np.float32)
+        return np.ctypeslib.as_array(ptr, shape=(n.value,)).reshape(nrow, n.value // nrow).copy()
+
+    def predict_contribs_device(self, dmat: DMatrix, out_ptr: int, approximate: bool = False, ntree_limit: int = 0,
+                                stream: int = 0) -> None:
+        """The same into device memory: out_ptr holds nrow * (F + 1) float32; only enqueues on `stream`."""
+        check(self.lib, self.lib.OHXBoosterPredictContribsDevice(self.handle, dmat.handle, int(bool(approximate)),
+                                                                  ntree_limit, out_ptr, stream))
 
     def predict_fields(self, fields: Sequence[np.ndarray], is2d: Sequence[bool], pl_feature: int, im: int, jm: int,
                        km: int, k1: int, k2: int, missing: float, oh_ml: np.ndarray, *, apply_pow10: bool = True,

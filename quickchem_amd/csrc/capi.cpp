@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/ohxgb.h"
+#include "contribs.hpp"
 #include "flatten.hpp"
 #include "forest.hpp"
 #include "kernels.hpp"
@@ -508,6 +509,42 @@ struct DMatrixObj {
   bool cluster_decided = false, cluster_on = false;
 };
 
+// Per-feature contributions (OHXBoosterPredictContribs): tables built at the first contribs call of each mode on the
+// loaded model, and buffers of their own - never one the predict, fields or Run1 paths use (a captured graph holds raw
+// pointers to those).  Dropped with the model (adopt_model) and with the booster, and the device part of it when the
+// booster has moved to another device ("ohx_device"); OHXReleaseScratch leaves them alone.
+struct ContribsState {
+  bool checked = false;              // feature count and cover checked, node means computed
+  std::string error;                 // why this model cannot have contributions at all (no cover, too many features)
+  std::string exact_error;           // why it cannot have exact ones (a path over too many distinct features)
+  std::vector<std::vector<float>> means;
+  int device = -1;                   // where the device part below lives
+  bool exact_ready = false, approx_ready = false;
+  DevBuf<PathHead> d_heads;          // exact mode: the path table
+  DevBuf<PathElem> d_elems;
+  DevBuf<uint32_t> d_class_start;
+  DevBuf<float> d_coef;
+  DevBuf<ContribNode> d_nodes;       // approximate mode
+  DevBuf<uint32_t> d_roots;
+  // the host form's output; the per-tree partials of split launches (sized by the largest split so far, at most
+  // 1 GiB - contribs.hip kPartBudgetBytes); the host form's inf flag
+  DevBuf<float> d_out, d_part;
+  DevBuf<uint32_t> d_flags;
+  PinnedBuf<float> h_out;
+  PinnedBuf<uint32_t> h_flags;
+  void release_device() {
+    for (DevBuf<float>* f : {&d_coef, &d_out, &d_part}) f->release();
+    d_heads.release();
+    d_elems.release();
+    d_class_start.release();
+    d_nodes.release();
+    d_roots.release();
+    d_flags.release();
+    exact_ready = approx_ready = false;
+    device = -1;
+  }
+};
+
 struct BoosterObj {
   ~BoosterObj() {
     for (hipEvent_t e : {run1_fork, run1_slab, run1_join, run1_clear})
@@ -618,6 +655,8 @@ struct BoosterObj {
   hipEvent_t cluster_done = nullptr;
   bool cluster_in_flight = false;
   std::vector<DevBuf<float>> d_run1_stage;
+  std::unique_ptr<ContribsState> contribs;
+  bool contribs_split = true;           // "ohx_contribs_split": small batches may have their trees split over waves
 };
 
 DMatrixObj* as_dmat(DMatrixHandle h) {
@@ -837,6 +876,7 @@ void adopt_model(BoosterObj& b, Forest&& f) {
   f.validate();
   for (const std::string& w : f.warnings) fprintf(stderr, "[libohxgb] warning: model file: %s\n", w.c_str());
   invalidate_device_state(b);
+  b.contribs.reset();
   b.forest = std::move(f);
   b.loaded = true;
   b.margin_error.clear();
@@ -927,7 +967,7 @@ struct LevelSizeCache {
 LevelSizeCache g_level_sizes;
 
 bool stream_capturing(hipStream_t stream);                 // defined with the deferred rows below
-[[noreturn]] void refuse_in_capture(const char* what);
+[[noreturn]] void refuse_in_capture(const char* what, const char* advice = nullptr);
 
 // Launches + one read-back on `stream`; waits for it (the rows must be there) - unless a matrix of this shape has
 // been searched before and `use_cache` allows taking its verdict.
@@ -1083,9 +1123,9 @@ bool stream_capturing(hipStream_t stream) {
   return st == hipStreamCaptureStatusActive;
 }
 
-[[noreturn]] void refuse_in_capture(const char* what) {
-  throw OhxError(std::string("inside a stream capture the library cannot ") + what +
-                 ": make one plain call of the same shape on this booster and matrix first, then capture");
+[[noreturn]] void refuse_in_capture(const char* what, const char* advice) {
+  throw OhxError(std::string("inside a stream capture the library cannot ") + what + ": " +
+                 (advice ? advice : "make one plain call of the same shape on this booster and matrix first, then capture"));
 }
 
 bool defer_prepare(BoosterObj& b, uint64_t nrow, LaunchTuning& tune, hipStream_t stream) {
@@ -1161,6 +1201,116 @@ void launch_predict_checked(BoosterObj& b, DMatrixObj& d, int option_mask, unsig
     HIP_CHECK(hipEventRecord(b.cluster_done, stream));
     b.cluster_in_flight = true;
   }
+}
+
+// Per-feature contributions: every refusal is decided here, before anything is enqueued.  What a mode needs is built at
+// its first call on the loaded model (contribs.hpp), on the booster's CURRENT device: the booster is uploaded first
+// (ensure_uploaded: it may just have been moved by "ohx_device"), and device tables left on another device are
+// released and built again here - so nothing a caller takes from the state or the booster afterwards (buffers,
+// b.dev, b.s_exec) is stale.  A model that cannot have contributions keeps its reason and is refused again at once.
+ContribsState& contribs_tables(BoosterObj& b, bool approximate) {
+  if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
+  if (!b.margin_error.empty()) throw OhxError(b.margin_error);
+  if (!b.contribs) b.contribs.reset(new ContribsState());
+  ContribsState& c = *b.contribs;
+  if (!c.error.empty()) throw OhxError(c.error);
+  if (!c.checked) {
+    try {
+      if (b.forest.num_feature > kMaxContribFeatures)
+        throw OhxError("feature contributions support boosters of at most " + std::to_string(kMaxContribFeatures) +
+                       " features (this one has " + std::to_string(b.forest.num_feature) + ")");
+      check_contrib_cover(b.forest);
+    } catch (const OhxError& e) {
+      c.error = e.what();
+      throw;
+    }
+    c.means.clear();
+    for (const Tree& t : b.forest.trees) c.means.push_back(node_means(t));
+    c.checked = true;
+  }
+  if (!approximate && !c.exact_error.empty()) throw OhxError(c.exact_error);
+  PathTable pt;
+  if (!approximate && !c.exact_ready) {      // host work first: a path that is too long is refused before any upload
+    try {
+      pt = build_path_table(b.forest);
+    } catch (const OhxError& e) {
+      c.exact_error = e.what();
+      throw;
+    }
+  }
+  ensure_uploaded(b);
+  if (c.device != b.dev.ordinal) {
+    if (c.device >= 0) {
+      HIP_CHECK(hipSetDevice(c.device));
+      c.release_device();
+      HIP_CHECK(hipSetDevice(b.dev.ordinal));
+      if (!approximate && pt.heads.empty() && !c.exact_ready) pt = build_path_table(b.forest);
+    }
+    c.device = b.dev.ordinal;
+    c.d_flags.ensure(1);
+    c.h_flags.ensure(1);
+    HIP_CHECK(hipMemset(c.d_flags.p, 0, sizeof(uint32_t)));
+  }
+  if (!approximate && !c.exact_ready) {
+    c.d_heads.upload(pt.heads);
+    c.d_elems.upload(pt.elems);
+    c.d_class_start.upload(pt.class_start);
+    c.d_coef.upload(unwind_coefficients());
+    c.exact_ready = true;
+  }
+  if (approximate && !c.approx_ready) {
+    std::vector<uint32_t> roots;
+    c.d_nodes.upload(emit_contrib_nodes(b.forest, c.means, &roots));
+    c.d_roots.upload(roots);
+    c.approx_ready = true;
+  }
+  return c;
+}
+
+// Checks, builds what the mode needs, then enqueues the launches: the host form (d_out null) on the library's stream
+// of the booster's device, into the state's own output buffer; the device form on `stream`.  Returns the state, which
+// nothing drops before the next contribs call on the booster.
+ContribsState& launch_contribs_checked(BoosterObj& b, DMatrixObj& d, int approximate, unsigned ntree_limit,
+                                       float* d_out, bool host_form, hipStream_t stream) {
+  if (approximate != 0 && approximate != 1) throw OhxError("approximate must be 0 (exact TreeSHAP) or 1");
+  if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
+  if (!host_form && d_out == nullptr && d.nrow != 0) throw OhxError("OHXBoosterPredictContribsDevice: d_out is NULL");
+  // before the tables are built: building them waits for the library's stream
+  if (!host_form && stream_capturing(stream))
+    refuse_in_capture("compute feature contributions",
+                      "OHXBoosterPredictContribsDevice is not capturable; call it outside the capture");
+  check_columns(b, d.ncol);
+  ContribsState& c = contribs_tables(b, approximate != 0);
+  if (d.device >= 0 && d.device != b.dev.ordinal)
+    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
+                   std::to_string(b.dev.ordinal));
+  const uint32_t F = b.forest.num_feature;
+  ContribsArgs a;
+  a.rows = d.d_data;
+  a.nrow = d.nrow;
+  a.ncol = (uint32_t)d.ncol;
+  a.missing = d.missing;
+  a.nfeat = F;
+  tree_range(b, ntree_limit, &a.tree_begin, &a.tree_end);
+  a.bias = contrib_bias(b.forest, c.means, a.tree_begin, a.tree_end, b.margin_base);
+  a.heads = c.d_heads.p;
+  a.elems = c.d_elems.p;
+  a.class_start = c.d_class_start.p;
+  a.coef = c.d_coef.p;
+  a.nodes = c.d_nodes.p;
+  a.roots = c.d_roots.p;
+  const ContribsPlan plan = plan_contribs(d.nrow, F, a.tree_end - a.tree_begin, b.contribs_split);
+  if (host_form) {
+    stream = b.s_exec;                       // taken after contribs_tables: the booster's current device
+    if (d.owned == nullptr) order_behind_caller(b.dev.ordinal, stream);
+    c.d_out.ensure((size_t)d.nrow * (F + 1));
+    d_out = c.d_out.p;
+    a.flags = c.d_flags.p;
+  }
+  a.out = d_out;
+  if (plan.split) c.d_part.ensure((size_t)plan.part_floats);
+  HIP_CHECK((hipError_t)launch_contribs(approximate != 0, a, plan, c.d_part.p, stream));
+  return c;
 }
 
 }  // namespace
@@ -1532,6 +1682,10 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
     const std::string v = value;
     if (v != "auto" && v != "on" && v != "off") throw OhxError("ohx_tree_tops must be auto, on or off");
     b->tune.tree_tops = v == "auto" ? -1 : (v == "on" ? 1 : 0);
+  } else if (n == "ohx_contribs_split") {
+    const std::string v = value;
+    if (v != "auto" && v != "off") throw OhxError("ohx_contribs_split must be auto or off");
+    b->contribs_split = v == "auto";
   } else if (n == "ohx_device") {
     int k = atoi(value);
     if (k != b->device_pref) invalidate_device_state(*b);
@@ -1573,6 +1727,40 @@ int OHXBoosterPredictDevice(BoosterHandle handle, DMatrixHandle dmat, int option
   if (d_out == nullptr && d->nrow != 0) throw OhxError("OHXBoosterPredictDevice: d_out is NULL");
   d->used_async = true;
   launch_predict_checked(*b, *d, option_mask, ntree_limit, d_out, static_cast<hipStream_t>(stream));
+  API_END();
+}
+
+int OHXBoosterPredictContribs(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
+                              bst_ulong* out_len, const float** out_result) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  DMatrixObj* d = as_dmat(dmat);
+  if (out_len == nullptr || out_result == nullptr) throw OhxError("OHXBoosterPredictContribs: NULL output argument");
+  // the state, the booster's device and its stream are taken only once the call has settled them
+  ContribsState& c = launch_contribs_checked(*b, *d, approximate, ntree_limit, nullptr, true, nullptr);
+  hipStream_t s = b->s_exec;
+  const size_t count = (size_t)d->nrow * (b->forest.num_feature + 1);
+  c.h_out.ensure(count);
+  if (count) HIP_CHECK(hipMemcpyAsync(c.h_out.p, c.d_out.p, count * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(c.h_flags.p, c.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (c.h_flags.p[0] != 0) {
+    HIP_CHECK(hipMemsetAsync(c.d_flags.p, 0, sizeof(uint32_t), s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    throw OhxError("Input data contains `inf` or `nan`");
+  }
+  *out_len = count;
+  *out_result = c.h_out.p;
+  API_END();
+}
+
+int OHXBoosterPredictContribsDevice(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
+                                    float* d_out, void* stream) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  DMatrixObj* d = as_dmat(dmat);
+  launch_contribs_checked(*b, *d, approximate, ntree_limit, d_out, false, static_cast<hipStream_t>(stream));
+  d->used_async = true;
   API_END();
 }
 

@@ -1,0 +1,121 @@
+// Host preparation of per-feature contributions (include/ohxgb.h, OHXBoosterPredictContribs): the tables the
+// contribs.hip kernels read, and the float node means both the kernels and the test-support CPU restatement
+// (contribs_host.cpp) start from.  Built once per booster and mode, at the first contribs call of that mode.
+//
+// Node means (xgboost 1.6.0 FillNodeMeanValues, in float, in this order):
+//   mean(leaf) = leaf value;  mean(n) = (mean(l) * cover(l) + mean(r) * cover(r)) / cover(n),  cover = sum_hess.
+//
+// Approximate mode walks ContribNode, the wide node's shape with the node's mean where the wide format keeps the
+// original node id: one 16-byte load per step holds the split and both means the step needs.
+//
+// Exact mode (path-dependent TreeSHAP) walks a path table: every leaf is one path, from the root down, its
+// elements the DISTINCT features split on along the way.  An element carries
+//   feature | miss << 31   miss = 1 when a missing value takes this path at EVERY occurrence of the feature
+//   [lo, hi)               the interval x must lie in to take this path at every occurrence (NaN = unbounded)
+//   z                      the product over occurrences of cover(child) / cover(parent)
+// so the one fraction of a row is  missing(x) ? miss : !(x < lo) && !(x >= hi).  Element 0 of the algorithm, the bias
+// element (z = o = 1), is implicit.  Within a tree the paths are sorted by length class (kPathClassMax) so the kernel
+// can run each class through a body unrolled to its maximum length; class_start[t * (kPathClasses + 1) + c] is where
+// class c of tree t starts.  Leaves reached without a split (a tree that is one leaf) have no features and are
+// not in the table: they only add to the bias column.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+
+#include "forest.hpp"
+
+namespace ohx {
+
+constexpr int kPathClasses = 7;
+constexpr int kPathClassMax[kPathClasses] = {4, 8, 12, 16, 20, 24, 32};
+constexpr int kMaxPathLen = 32;         // distinct features on one root-to-leaf path
+constexpr uint32_t kMaxContribFeatures = 128;   // two [feature][64] float tiles per wave must fit a block's 64 KiB of LDS
+
+struct ContribNode {   // 16 bytes
+  float value;         // split condition, or the leaf value
+  uint32_t left;       // absolute index of the left child (right = left + 1), 0 => leaf
+  uint32_t feat_dl;    // feature | default_left << 31
+  float mean;          // node mean
+};
+
+struct PathElem {      // 16 bytes
+  uint32_t feat;       // feature | miss << 31
+  float lo, hi;        // NaN = unbounded
+  float z;
+};
+
+struct PathHead {      // 16 bytes
+  uint32_t first;      // index of the path's first element
+  uint32_t len;        // distinct features, 1 .. kMaxPathLen
+  float leaf;
+  uint32_t pad;
+};
+
+struct PathTable {
+  std::vector<PathHead> heads;
+  std::vector<PathElem> elems;
+  std::vector<uint32_t> class_start;   // [tree][kPathClasses + 1]
+  uint64_t sum_sq = 0;                 // sum over paths of (len + 1)^2: the element steps of the recurrences
+  uint32_t max_len = 0;
+  uint64_t bytes() const {
+    return heads.size() * sizeof(PathHead) + elems.size() * sizeof(PathElem) + class_start.size() * sizeof(uint32_t);
+  }
+};
+
+// Throws OhxError unless every internal node reachable from a root has a finite cover > 0.
+void check_contrib_cover(const Forest& f);
+// mean of every node of tree t, indexed like the tree's arrays (unreachable nodes: 0)
+std::vector<float> node_means(const Tree& t);
+// bias column: sum of the root means of trees [t0, t1), in tree order from 0.0f, then + margin_base
+float contrib_bias(const Forest& f, const std::vector<std::vector<float>>& means, uint32_t t0, uint32_t t1,
+                   float margin_base);
+// file-order nodes of every tree, tree after tree; roots[t] = index of tree t's root
+std::vector<ContribNode> emit_contrib_nodes(const Forest& f, const std::vector<std::vector<float>>& means,
+                                            std::vector<uint32_t>* roots);
+// Throws OhxError when a path holds more than kMaxPathLen distinct features.
+PathTable build_path_table(const Forest& f);
+// the length class of a path of `len` distinct features
+int path_class(uint32_t len);
+
+// ---- the launches (contribs.hip) ----
+
+// unwound-sum coefficients per (len, i): {(len+1)/(i+1), (len-i)/(len+1), (len+1)/(len-i), 0}
+constexpr int kCoefStride = kMaxPathLen + 1;
+std::vector<float> unwind_coefficients();   // [kCoefStride][kCoefStride][4]
+
+struct ContribsArgs {
+  const float* rows = nullptr;   // [nrow][ncol], device
+  uint64_t nrow = 0;
+  uint32_t ncol = 0;
+  float missing = 0.0f;
+  uint32_t nfeat = 0;            // F: out is [nrow][F + 1]
+  uint32_t tree_begin = 0, tree_end = 0;
+  float bias = 0.0f;             // column F
+  float* out = nullptr;
+  uint32_t* flags = nullptr;     // bit 0: +-inf in the rows while `missing` is finite (may be null: not checked)
+  // exact mode
+  const PathHead* heads = nullptr;
+  const PathElem* elems = nullptr;
+  const uint32_t* class_start = nullptr;
+  const float* coef = nullptr;
+  // approximate mode
+  const ContribNode* nodes = nullptr;
+  const uint32_t* roots = nullptr;
+};
+
+// How a batch is cut: batches that leave most of the chip's wave slots empty have their trees split over waves,
+// every (tile, tree group) writing its trees' contributions to `part` one tree at a time, and a second launch sums
+// them in tree order.  Bigger batches: one wave per tile walks every tree.  Either way a row's bits are the same.
+struct ContribsPlan {
+  bool split = false;
+  uint32_t trees_per_group = 0, groups = 0;
+  uint64_t part_floats = 0;      // size of `part` the split needs
+};
+// allow_split = false ("ohx_contribs_split" = off): always direct
+ContribsPlan plan_contribs(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool allow_split);
+// Enqueues everything on `stream` (a hipStream_t).  `part` must hold plan.part_floats floats when plan.split.
+// Returns a hipError_t.
+int launch_contribs(bool approximate, const ContribsArgs& a, const ContribsPlan& plan, float* part, void* stream);
+
+}  // namespace ohx

@@ -45,6 +45,10 @@ inline void cell_of(uint64_t m, int im, int jm, int* i, int* j, int* k) {
 
 }  // namespace
 
+namespace ohx {
+void synth_set_error(const std::string& m) { g_err = m; }   // for contribs_host.cpp
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 

@@ -14,7 +14,7 @@ module ohx_bindings
 
    public :: XGDMatrixCreateFromMat, XGDMatrixFree, XGDMatrixNumRow, XGDMatrixNumCol
    public :: XGBoosterCreate, XGBoosterFree, XGBoosterLoadModel, XGBoosterSaveModel
-   public :: XGBoosterPredict, XGBoosterSetParam, OHXBoosterPredictFields, OHXDMatrixSetGrid
+   public :: XGBoosterPredict, XGBoosterSetParam, OHXBoosterPredictFields, OHXDMatrixSetGrid, OHXBoosterPredictContribs
    public :: OHXCommGetUniqueId, OHXCommInitRank, OHXCommFree, OHXCommInfo, OHXShardRows, OHXAllGatherOH, OHX_UNIQUE_ID_BYTES
    public :: ohx_last_error, ohx_c_string
 
@@ -118,6 +118,19 @@ module ohx_bindings
          real(c_float), value           :: ohscale
          type(c_ptr), value             :: oh_ml, margin
          integer(c_int)                 :: rc
+      end function
+
+      ! Per-feature contributions (ohxgb.h part 2): approximate = 0 exact TreeSHAP, 1 xgboost's approximate
+      ! attribution.  out_result points at nrow * (F + 1) floats owned by the booster (row-major: in Fortran a
+      ! (F + 1, nrow) array through c_f_pointer), column F + 1 the bias; valid until the next contribs call.
+      function OHXBoosterPredictContribs(handle, dmat, approximate, ntree_limit, out_len, out_result) &
+            bind(C, name="OHXBoosterPredictContribs") result(rc)
+         import :: c_int, c_ptr, c_int64_t
+         type(c_ptr), value         :: handle, dmat
+         integer(c_int), value      :: approximate, ntree_limit
+         integer(c_int64_t)         :: out_len
+         type(c_ptr)                :: out_result
+         integer(c_int)             :: rc
       end function
 
       ! Optional hint: the DMatrix rows are rows row0.. of the (im,jm,*) gather (ohxgb.h); speed only.

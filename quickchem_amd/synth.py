@@ -63,6 +63,9 @@ def _load():
                                           C.POINTER(C.c_uint64)]
         lib.ohx_super_walk_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float,
                                            C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.ohx_contribs_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int,
+                                         C.c_uint, C.c_void_p]
+        lib.ohx_contribs_table_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         _lib = lib
     return _lib
 
@@ -154,6 +157,30 @@ def super_walk_cpu(image, rows: np.ndarray, missing: float = XX_MISS):
         return None, None
     _check(rc)
     return out, {"super_nodes": int(info[0]), "phase1_trees": int(info[1]), "steps": int(info[2])}
+
+
+def contribs_cpu(image, rows: np.ndarray, num_feature: int, missing: float = XX_MISS, approximate: bool = False,
+                 ntree_limit: int = 0) -> np.ndarray:
+    """Host restatement of per-feature contributions (csrc/contribs_host.cpp: xgboost 1.6.0's recursive TreeShap or
+    CalculateContributionsApprox, in float): (nrow, num_feature + 1) float32, column num_feature the bias.  Test
+    support, the reference the GPU kernels are checked against."""
+    lib = _load()
+    src = np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else image
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    out = np.empty((rows.shape[0], num_feature + 1), dtype=np.float32)
+    _check(lib.ohx_contribs_cpu(src.ctypes.data, src.nbytes, rows.ctypes.data, rows.shape[0], rows.shape[1], missing,
+                                1 if approximate else 0, ntree_limit, out.ctypes.data))
+    return out
+
+
+def contribs_table_stats(image) -> Dict[str, int]:
+    """Size of the exact mode's path table as the library builds it (csrc/contribs.cpp build_path_table)."""
+    lib = _load()
+    src = np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else image
+    st = (C.c_uint64 * 5)()
+    _check(lib.ohx_contribs_table_stats(src.ctypes.data, src.nbytes, st))
+    return {"bytes": int(st[0]), "paths": int(st[1]), "elements": int(st[2]), "sum_len1_sq": int(st[3]),
+            "max_len": int(st[4])}
 
 
 # ---- device generators (torch tensors in HBM; libohx_synth_gpu.so, test support like the rest of this file) ----
