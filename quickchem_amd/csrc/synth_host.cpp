@@ -334,5 +334,26 @@ int ohx_super_walk_cpu(const uint8_t* model, uint64_t model_len, const float* ro
   }
 }
 
+// What emit_super made of every tree, for the CPU test-suite (which edge classes a test booster reaches): out[2 t] =
+// phase of tree t (1: the root is evaluated from the head record), out[2 t + 1] = its steps.  *ntrees = trees of the
+// booster; at most `cap` pairs are written (cap 0: ask for the count).  Returns 1 if the booster does not fit the format.
+int ohx_super_heads_cpu(const uint8_t* model, uint64_t model_len, uint32_t* out, uint64_t cap, uint64_t* ntrees) {
+  try {
+    Forest f = load_model_buffer(model, (size_t)model_len);
+    f.validate();
+    SuperForest sf;
+    if (!emit_super(f, &sf)) return 1;
+    *ntrees = sf.heads.size();
+    for (size_t t = 0; t < sf.heads.size() && t < cap; ++t) {
+      out[2 * t] = (sf.heads[t].root_meta >> 8) & 1u;
+      out[2 * t + 1] = sf.heads[t].steps;
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

@@ -63,6 +63,7 @@ def _load():
                                           C.POINTER(C.c_uint64)]
         lib.ohx_super_walk_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float,
                                            C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.ohx_super_heads_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_contribs_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int,
                                          C.c_uint, C.c_void_p]
         lib.ohx_contribs_table_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -157,6 +158,22 @@ def super_walk_cpu(image, rows: np.ndarray, missing: float = XX_MISS):
         return None, None
     _check(rc)
     return out, {"super_nodes": int(info[0]), "phase1_trees": int(info[1]), "steps": int(info[2])}
+
+
+def super_heads_cpu(image):
+    """Per tree, what emit_super (csrc/flatten.cpp) made of it: an (ntrees, 2) uint32 array of (phase, steps) - phase 1
+    when the root is evaluated from the head record, steps the walk's trip count.  Test support: which edge classes of
+    the kernels a booster reaches.  None if the booster does not fit the super-node format."""
+    lib = _load()
+    src = np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else image
+    n = C.c_uint64()
+    rc = lib.ohx_super_heads_cpu(src.ctypes.data, src.nbytes, None, 0, C.byref(n))
+    if rc == 1:
+        return None
+    _check(rc)
+    out = np.zeros((n.value, 2), dtype=np.uint32)
+    _check(lib.ohx_super_heads_cpu(src.ctypes.data, src.nbytes, out.ctypes.data, n.value, C.byref(n)))
+    return out
 
 
 def contribs_cpu(image, rows: np.ndarray, num_feature: int, missing: float = XX_MISS, approximate: bool = False,

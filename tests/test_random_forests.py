@@ -136,11 +136,14 @@ def test_gpu_kernels_on_random_boosters(ntree, nfeat, depth, p_leaf):
     model = O.load_model(js)
     for missing in (-999.0, float("nan")):
         want = O.predict(model, rows, missing=missing)
-        for kernel in ("auto", "wide", "packed1", "packed2", "packed4", "super1", "super2", "super4"):
-            b = capi.Booster(model_buffer=js)
-            b.set_param("ohx_kernel", kernel)
-            got = b.predict(capi.DMatrix(rows, missing=missing))
-            assert np.array_equal(helpers.bits(got), helpers.bits(want)), (kernel, missing)
+        for kernel in ("auto", "wide", "packed1", "packed2", "packed4", "super1", "super2", "super3", "super4", "ring"):
+            # the default launch (small batches of 8 or more trees: split over waves) and one wave per tile
+            for split in ("auto", "off"):
+                b = capi.Booster(model_buffer=js)
+                b.set_param("ohx_kernel", kernel)
+                b.set_param("ohx_tree_split", split)
+                got = b.predict(capi.DMatrix(rows, missing=missing))
+                assert np.array_equal(helpers.bits(got), helpers.bits(want)), (kernel, split, missing)
         # the clustering pass on trees of every shape (stumps, leaves at any depth, roots evaluated from the head or
         # not): a key from the top of up to four trees, any number of steps - same margins
         for trees, steps, z in ((1, 1, 0), (2, 7, 0), (4, 3, 1), (3, 16, 0)):

@@ -126,10 +126,13 @@ def test_scikit_learn_walks_like_the_oracle(sk_case):
 @pytest.mark.gpu
 def test_scikit_learn_walks_like_the_hip_path(sk_case):
     gbr, js, maps, test = sk_case
-    for kernel in ("auto", "wide", "packed2"):
+    for kernel, split in (("auto", "auto"), ("wide", "auto"), ("packed2", "auto"), ("ring", "off")):
         b = capi.Booster(model_buffer=js)
         b.set_param("ohx_kernel", kernel)
+        b.set_param("ohx_tree_split", split)
         d = capi.DMatrix(test, missing=float("nan"))
+        if kernel == "ring":
+            assert b.kernel_symbols_for(d).startswith("predict_rows_ring_kernel + ")
         margins = b.predict(d)
         leaves = b.predict(d, option_mask=16)
         check(leaves, margins, gbr, maps, test)
@@ -191,7 +194,10 @@ def test_missing_values_on_the_hip_path_against_scikit_learn(sk_missing_case):
     want = np.zeros(len(test), dtype=np.float32)
     for est in ests:
         want = (want + est.tree_.value[est.apply(test), 0, 0].astype(np.float32)).astype(np.float32)
-    for kernel in ("auto", "packed2", "wide"):
+    for kernel, split in (("auto", "auto"), ("packed2", "auto"), ("wide", "auto"), ("ring", "off")):
         b.set_param("ohx_kernel", kernel)
+        b.set_param("ohx_tree_split", split)
+        if kernel == "ring":
+            assert b.kernel_symbols_for(d).startswith("predict_rows_ring_kernel + ")
         assert np.array_equal(helpers.bits(b.predict(d)), helpers.bits(want)), kernel
     d.free()
