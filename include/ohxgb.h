@@ -249,12 +249,15 @@ int OHXBoosterCheck(BoosterHandle handle, void* stream);
  *   so its rounding differs from 1.6.0's recursive walk).
  * Refused (-1, nothing enqueued): no model; an objective whose margin base is unknown (as option_mask 1); more
  * columns than features; a split whose cover is not finite and > 0 (the model has no cover statistics - 1.6.0 would
- * quietly produce NaN); a root-to-leaf path over more than 32 distinct features, or more than 128 features; d_out
+ * quietly produce NaN; a LEAF of cover 0 is accepted: its zero fraction is 0, and both modes give the Shapley value /
+ * the Saabas walk, as 1.6.0's algorithm does); a root-to-leaf path over more than 32 distinct features, or more than 128 features; d_out
  * NULL; and, for the device form, a stream that is being captured: contributions are not capturable.
  * Tables (node means, a path table per leaf - docs/12_contributions.md for their size) are built at the first call
  * on a loaded model and kept until the model is replaced or XGBoosterFree; OHXReleaseScratch leaves them alone.
  * Contributions use buffers of their own, never one of the predict, fields or Run1 paths.  The device form only
- * enqueues on `stream`; +-inf in the rows is reported by the host form only. */
+ * enqueues on `stream`.  +-inf in the rows is reported by the host form only: there, as in predict, +-inf in ANY of a
+ * row's columns is an error unless `missing` is itself infinite, in both modes (not only in the columns the row's
+ * paths split on). */
 int OHXBoosterPredictContribs(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
                               bst_ulong* out_len, const float** out_result);
 int OHXBoosterPredictContribsDevice(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,

@@ -168,4 +168,20 @@ PathTable build_path_table(const Forest& f) {
   return pt;
 }
 
+ContribsPlan plan_contribs(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool allow_split) {
+  ContribsPlan p;
+  const uint64_t tiles = (nrow + kContribsTileRows - 1) / kContribsTileRows;
+  if (!allow_split || tiles == 0 || ntree < 2 || tiles * 2 > kWaveSlots) return p;
+  const uint64_t part = tiles * ntree * (uint64_t)nfeat * kContribsTileRows;
+  if (part * sizeof(float) > kPartBudgetBytes) return p;
+  uint64_t want = (kWaveSlots + tiles - 1) / tiles;   // tree groups that fill the chip's wave slots
+  if (want > ntree) want = ntree;
+  if (want < 2) return p;
+  p.trees_per_group = (uint32_t)((ntree + want - 1) / want);
+  p.groups = (ntree + p.trees_per_group - 1) / p.trees_per_group;
+  p.split = p.groups > 1;
+  p.part_floats = p.split ? part : 0;
+  return p;
+}
+
 }  // namespace ohx

@@ -30,10 +30,7 @@ namespace ohx {
 
 namespace {
 
-constexpr int kWave = 64;
-constexpr uint64_t kDirectTilesPerLaunch = 8192;     // exact mode: bounds the length of one launch
-constexpr uint64_t kPartBudgetBytes = 1ull << 30;     // largest `part` a split may ask for
-constexpr uint64_t kWaveSlots = 8192;                 // 256 CUs x 32 waves
+constexpr int kWave = (int)kContribsTileRows;
 
 __device__ __forceinline__ bool is_inf(float v) { return __builtin_isinf(v); }
 
@@ -122,12 +119,11 @@ __device__ __forceinline__ void exact_tree(const PathHead* __restrict__ heads, c
   shap_paths<32>(heads, elems, coef, cs[6], cs[7], xt, ct);
 }
 
-__device__ __forceinline__ bool approx_tree(const ContribsArgs& a, uint32_t t, const float* __restrict__ x,
+__device__ __forceinline__ void approx_tree(const ContribsArgs& a, uint32_t t, const float* __restrict__ x,
                                             bool missing_is_nan, float* __restrict__ ct) {
   const uint4* __restrict__ nodes = reinterpret_cast<const uint4*>(a.nodes);
   uint4 nd = nodes[a.roots[t]];
-  if (nd.y == 0u) return false;
-  bool any_inf = false;
+  if (nd.y == 0u) return;
   float cur = __uint_as_float(nd.w);
   uint32_t f = 0u;
   while (nd.y != 0u) {
@@ -135,7 +131,6 @@ __device__ __forceinline__ bool approx_tree(const ContribsArgs& a, uint32_t t, c
     bool miss = true, lt = false;
     if (f < a.ncol) {
       const float v = x[f];
-      any_inf |= is_inf(v);
       miss = (v != v) || (!missing_is_nan && v == a.missing);
       lt = v < __uint_as_float(nd.x);
     }
@@ -146,7 +141,6 @@ __device__ __forceinline__ bool approx_tree(const ContribsArgs& a, uint32_t t, c
     cur = next;
   }
   ct[f * kWave] += __uint_as_float(nd.x) - cur;
-  return any_inf;
 }
 
 // One block = one wave = one tile of 64 rows (direct) or one (tile, tree group) item (split).
@@ -185,14 +179,19 @@ __global__ __launch_bounds__(kWave) void contribs_kernel(ContribsArgs a, uint64_
       }
       ta[f * kWave] = v;
     }
-  } else if (!SPLIT) {
-    for (uint32_t f = 0; f < F; ++f) ta[f * kWave] = 0.0f;
+  } else {
+    if (!SPLIT)
+      for (uint32_t f = 0; f < F; ++f) ta[f * kWave] = 0.0f;
+    // +-inf anywhere in the row, as the exact row tile's fill and predict check - not only where the row's paths
+    // split; in the split form the first tree group of each tile looks
+    if (valid && a.flags && !is_inf(a.missing) && (!SPLIT || g == 0u))
+      for (uint32_t f = 0; f < a.ncol; ++f) any_inf |= is_inf(x[f]);
   }
   float* __restrict__ orow = out + (valid ? row : 0) * (uint64_t)(F + 1);
   for (uint32_t t = t0; t < t1; ++t) {
     for (uint32_t f = 0; f < F; ++f) ct[f * kWave] = 0.0f;
     if (APPROX) {
-      if (valid) any_inf |= approx_tree(a, t, x, missing_is_nan, ct);
+      if (valid) approx_tree(a, t, x, missing_is_nan, ct);
     } else {
       exact_tree(heads, elems, class_start, coef, t, ta, ct);
     }
@@ -260,22 +259,6 @@ hipError_t launch_mode(const ContribsArgs& a, const ContribsPlan& plan, float* p
 }
 
 }  // namespace
-
-ContribsPlan plan_contribs(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool allow_split) {
-  ContribsPlan p;
-  const uint64_t tiles = (nrow + kWave - 1) / kWave;
-  if (!allow_split || tiles == 0 || ntree < 2 || tiles * 2 > kWaveSlots) return p;
-  const uint64_t part = tiles * ntree * (uint64_t)nfeat * kWave;
-  if (part * sizeof(float) > kPartBudgetBytes) return p;
-  uint64_t want = (kWaveSlots + tiles - 1) / tiles;           // tree groups that fill the chip's wave slots
-  if (want > ntree) want = ntree;
-  if (want < 2) return p;
-  p.trees_per_group = (uint32_t)((ntree + want - 1) / want);
-  p.groups = (ntree + p.trees_per_group - 1) / p.trees_per_group;
-  p.split = p.groups > 1;
-  p.part_floats = p.split ? part : 0;
-  return p;
-}
 
 int launch_contribs(bool approximate, const ContribsArgs& a, const ContribsPlan& plan, float* part, void* stream) {
   if (a.nrow == 0) return (int)hipSuccess;

@@ -104,6 +104,11 @@ struct ContribsArgs {
   const uint32_t* roots = nullptr;
 };
 
+constexpr uint64_t kContribsTileRows = 64;            // rows of one tile: one wave, one row per lane
+constexpr uint64_t kWaveSlots = 8192;                 // 256 CUs x 32 waves
+constexpr uint64_t kPartBudgetBytes = 1ull << 30;     // largest `part` a split may ask for
+constexpr uint64_t kDirectTilesPerLaunch = 8192;      // exact mode, direct: tiles per launch (bounds a launch's length)
+
 // How a batch is cut: batches that leave most of the chip's wave slots empty have their trees split over waves,
 // every (tile, tree group) writing its trees' contributions to `part` one tree at a time, and a second launch sums
 // them in tree order.  Bigger batches: one wave per tile walks every tree.  Either way a row's bits are the same.
@@ -112,7 +117,7 @@ struct ContribsPlan {
   uint32_t trees_per_group = 0, groups = 0;
   uint64_t part_floats = 0;      // size of `part` the split needs
 };
-// allow_split = false ("ohx_contribs_split" = off): always direct
+// allow_split = false ("ohx_contribs_split" = off): always direct.  Host logic (contribs.cpp).
 ContribsPlan plan_contribs(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool allow_split);
 // Enqueues everything on `stream` (a hipStream_t).  `part` must hold plan.part_floats floats when plan.split.
 // Returns a hipError_t.

@@ -201,3 +201,17 @@ extern "C" __attribute__((visibility("default"))) int ohx_contribs_table_stats(c
     return -1;
   }
 }
+
+// The launch shape the library picks for a batch (contribs.cpp plan_contribs): plan[0] split (0 / 1), [1] tree groups,
+// [2] trees per group, [3] direct launches of exact mode (0 when split; approximate mode launches once below 2**24
+// tiles).
+extern "C" __attribute__((visibility("default"))) int ohx_contribs_plan(uint64_t nrow, uint32_t nfeat, uint32_t ntree,
+                                                                       int allow_split, uint64_t* plan) {
+  const ContribsPlan p = plan_contribs(nrow, nfeat, ntree, allow_split != 0);
+  const uint64_t tiles = (nrow + kContribsTileRows - 1) / kContribsTileRows;
+  plan[0] = p.split ? 1 : 0;
+  plan[1] = p.groups;
+  plan[2] = p.trees_per_group;
+  plan[3] = p.split ? 0 : (tiles + kDirectTilesPerLaunch - 1) / kDirectTilesPerLaunch;
+  return 0;
+}

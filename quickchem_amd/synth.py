@@ -67,6 +67,7 @@ def _load():
         lib.ohx_contribs_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int,
                                          C.c_uint, C.c_void_p]
         lib.ohx_contribs_table_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.ohx_contribs_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
         _lib = lib
     return _lib
 
@@ -198,6 +199,14 @@ def contribs_table_stats(image) -> Dict[str, int]:
     _check(lib.ohx_contribs_table_stats(src.ctypes.data, src.nbytes, st))
     return {"bytes": int(st[0]), "paths": int(st[1]), "elements": int(st[2]), "sum_len1_sq": int(st[3]),
             "max_len": int(st[4])}
+
+
+def contribs_plan(nrow: int, nfeat: int, ntree: int, allow_split: bool = True):
+    """The launch shape OHXBoosterPredictContribs picks for a batch (csrc/contribs.cpp plan_contribs): (split, groups,
+    trees_per_group, direct_launches) - direct_launches is exact mode's count of direct launches, 0 when split."""
+    p = (C.c_uint64 * 4)()
+    _check(_load().ohx_contribs_plan(nrow, nfeat, ntree, 1 if allow_split else 0, p))
+    return bool(p[0]), int(p[1]), int(p[2]), int(p[3])
 
 
 # ---- device generators (torch tensors in HBM; libohx_synth_gpu.so, test support like the rest of this file) ----

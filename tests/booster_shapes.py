@@ -303,3 +303,82 @@ def thresholds_by_feature(trees):
             if t.left[n] != -1:
                 out[t.feat[n]].add(float(np.float32(t.cond[n])))
     return out
+
+
+# ---- feature contributions: consistent covers and long paths with repeated features ----
+
+def _long_chain(rng, thresholds, distinct):
+    """A chain of depth 30 whose features are `distinct` features, each at least once, with repeats: for 27, a
+    permutation of all of them followed by 3 repeats; below 27, the distinct ones in random order with repeats
+    scattered between them.  Its deepest paths are `distinct` features long and split on some feature again."""
+    order = [int(f) for f in rng.permutation(NFEAT)[:distinct]]
+    if distinct == NFEAT:
+        seq = order + [int(f) for f in rng.choice(order, 30 - NFEAT)]
+    else:
+        seq = list(order)
+        for _ in range(30 - distinct):
+            k = int(rng.integers(1, len(seq)))
+            seq.insert(k, seq[int(rng.integers(0, k))])     # a feature already on the path above
+    t = Tree()
+    n = t.node()
+    for f in seq:
+        l, r = t.split(n)
+        t.feat[n], t.cond[n], t.dl[n] = f, float(thresholds(f)), int(rng.integers(0, 2))
+        n = l if rng.random() < 0.5 else r
+    for m in range(len(t.left)):
+        if t.left[m] == -1:
+            t.cond[m] = float(np.float32(rng.normal(0, 0.1)))
+    _force_phase(rng, t, int(rng.integers(0, 2)))
+    return t
+
+
+def _consistent_covers(rng, t, zero_cover_leaves):
+    """Leaves keep their 1 / 1000 covers (or get 0, never both children of one split), every split the sum of its
+    children's: zero fractions from about 1e-3 to 1, and mean(root) == v({})."""
+    if zero_cover_leaves:
+        for n in range(len(t.left)):
+            l, r = t.left[n], t.right[n]
+            if l == -1:
+                continue
+            for c, sib in ((l, r), (r, l)):
+                if t.left[c] == -1 and not (t.left[sib] == -1 and t.hess[sib] == 0.0) and rng.random() < 0.3:
+                    t.hess[c] = 0.0
+    for n in reversed(range(len(t.left))):          # children are always numbered after their parent
+        if t.left[n] != -1:
+            t.hess[n] = t.hess[t.left[n]] + t.hess[t.right[n]]
+
+
+def contribs_booster(seed, ntree, zero_cover_leaves=False):
+    """make_booster's shapes, thresholds and tie rows for feature contributions -> (JSON image, [Tree]).  Covers are
+    consistent (_consistent_covers).  The first chain of the plan takes all 27 features and then repeats (a path in
+    the 32-feature length class), the second 21 - 24 distinct features with repeats between them (the 24-feature
+    class); the rest draw features uniformly, as make_booster does (about 18 distinct on a depth-30 chain).
+    `zero_cover_leaves`: some leaves get cover 0 (a zero fraction of exactly 0; only leaves can - a split's cover
+    must be > 0)."""
+    rng = np.random.default_rng(seed)
+    thresholds = Thresholds(rng)
+    trees, chains = [], 0
+    for i, kind in enumerate(plan(rng, ntree)):
+        if kind == "chain" and chains < 2:
+            t = _long_chain(rng, thresholds, NFEAT if chains == 0 else int(rng.integers(21, 25)))
+            chains += 1
+        else:
+            t = make_tree(rng, kind, thresholds, i & 1 if kind in ("chain", "lopsided", "random", "small") else None)
+        _consistent_covers(rng, t, zero_cover_leaves)
+        trees.append(t)
+    return booster_json(trees, np.float32(rng.normal(0, 1))), trees
+
+
+def distinct_path_lengths(t):
+    """(distinct features, whether some feature repeats) of every root-to-leaf path of a Tree below a split."""
+    out = []
+
+    def walk(n, feats):
+        if t.left[n] == -1:
+            if feats:
+                out.append((len(set(feats)), len(set(feats)) < len(feats)))
+            return
+        walk(t.left[n], feats + [t.feat[n]])
+        walk(t.right[n], feats + [t.feat[n]])
+    walk(0, [])
+    return out
