@@ -148,7 +148,8 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *   "ohx_top_levels", "ohx_line_slots", "ohx_min_chunk"  placement of the packed format
  *   "ohx_contribs_split"  auto | off : OHXBoosterPredictContribs[Device]: a batch that leaves most of the chip's wave
  *                     slots empty has its trees split over waves and the per-tree contributions summed in tree order by a
- *                     second launch (auto), or one wave per 64 rows walks every tree (off); the same bits either way
+ *                     second launch (auto), or one wave per 64 rows walks every tree (off); the same bits either way;
+ *                     the same for OHXBoosterPredictInteractions[Device] (there a wave per 64 rows and feature)
  *   "ohx_device"      HIP device ordinal for this booster
  * None of them changes a prediction.
  * xgboost's own parameter names ("nthread", "predictor", ...) are accepted and
@@ -262,6 +263,41 @@ int OHXBoosterPredictContribs(BoosterHandle handle, DMatrixHandle dmat, int appr
                               bst_ulong* out_len, const float** out_result);
 int OHXBoosterPredictContribsDevice(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
                                     float* d_out, void* stream);
+
+/* SHAP interaction values of each row, as xgboost 1.6.0's XGBoosterPredict with pred_interactions
+ * (PredictInteractionContributions).  Output: nrow x (F + 1) x (F + 1) float32, row-major [row][i][k], F the
+ * booster's num_feature, index F the bias.  *out_len = nrow * (F + 1)^2; *out_result is a host buffer owned by the
+ * booster, valid until its next interactions call or XGBoosterFree.  Missing values, ntree_limit, the margin base and
+ * the matrix forms as in OHXBoosterPredictContribs.  With phi = what OHXBoosterPredictContribs returns for the same
+ * row, trees and `approximate` (bit for bit: the same launch fills it):
+ *   exact (approximate = 0), i != k, both < F:  Phi_ik = (phi_k | i on - phi_k | i off) / 2, 1.6.0's conditioning
+ *              inside path-dependent TreeSHAP: on a path that holds feature i (its element c, occurrences merged as in
+ *              contributions) "on" multiplies the path's weight by c's one fraction, "off" by its zero fraction, and c
+ *              leaves the permutation; phi_k is taken over the other elements.  Per path:
+ *              1/2 (o_c - z_c) (o_k - z_k) leaf W(path without c, k), W the unwound path sum.  Paths without i add
+ *              nothing to row i.  Each tree's row is accumulated on its own and added in tree order from 0.
+ *   diagonal   Phi_ii = phi_i - sum_{k != i} Phi_ik in 1.6.0's float order: from 0, for k = 0 .. F add phi_i at
+ *              k == i and subtract Phi_ik otherwise.
+ *   bias       row F and column F are 0 except Phi_FF = phi_F (conditioning on index F matches no split).
+ *   approximate = 1: 1.6.0's approximate walk ignores the condition, so every off-diagonal is 0 and the diagonal is
+ *              OHXBoosterPredictContribs(approximate = 1)'s vector, bit for bit.
+ *   A feature no tree of the range splits on has an all-zero row and column.  Mathematically Phi is symmetric, row i
+ *   sums to phi_i and the matrix to the margin of XGBoosterPredict(option_mask = 1), up to rounding.  A row's bits do
+ *   not depend on the batch, on "ohx_contribs_split", or on the form.  No float atomics.  Parity with libxgboost itself
+ *   is not pinned (the recurrences run per leaf path in float32, and 1.6.0 stores (on - off) / 2 from double).
+ * Refused (-1, nothing enqueued): everything OHXBoosterPredictContribs refuses (no model, unknown margin base, more
+ * columns than features, a split without cover, a path over 32 distinct features, more than 128 features, d_out or
+ * an output argument NULL, a stream being captured); +-inf in any column of a row in the host form unless `missing`
+ * is itself infinite; an output that cannot be allocated.  The tables are the contributions' (built once, at the
+ * first exact call of either entry point) plus, for exact mode, an index of the paths that hold each feature (one
+ * 4-byte entry per path element; docs/12_contributions.md section 12.6).  The buffers are the booster's contributions
+ * state's but none a contribs call uses, and never one of the predict, fields or Run1 paths; dropped with the model
+ * and at XGBoosterFree, rebuilt after an "ohx_device" move.  Exact mode costs about (path length) times what exact
+ * contributions cost per row: it is for subsets of rows.  The device form only enqueues on `stream`. */
+int OHXBoosterPredictInteractions(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
+                                  bst_ulong* out_len, const float** out_result);
+int OHXBoosterPredictInteractionsDevice(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
+                                        float* d_out, void* stream);
 
 /* The whole of predict_OH_with_XGB's RUN section in one kernel
  * (OH_GridCompMod.F90:303-383): gathers the 27 MAPL fields in place (field f is

@@ -28,6 +28,7 @@ ABI_SYMBOLS = [
     "XGBoosterSaveModel", "XGBoosterLoadModelFromBuffer", "XGBoosterPredict", "XGBoosterSetParam",
     "OHXDeviceCount", "OHXDMatrixCreateFromDevice", "OHXDMatrixSetGrid", "OHXDMatrixGetGrid", "OHXDMatrixInferGrid", "OHXBoosterPredictDevice", "OHXBoosterCheck",
     "OHXBoosterPredictContribs", "OHXBoosterPredictContribsDevice",
+    "OHXBoosterPredictInteractions", "OHXBoosterPredictInteractionsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
     "OHXJulianDay", "OHXSolarGeometry", "OHXSolarGeometryDevice", "OHXBoosterGetInfo", "OHXBoosterKernelSymbol", "OHXBoosterKernelSymbolRows",
     "OHXBoosterRingReruns", "OHXBoosterCopyEngineChoice", "OHXUnregisterHost", "OHXReleaseScratch",
@@ -112,6 +113,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.OHXBoosterCheck.argtypes = [vp, vp]
     lib.OHXBoosterPredictContribs.argtypes = [vp, vp, i32, C.c_uint, C.POINTER(u64), C.POINTER(C.POINTER(f32))]
     lib.OHXBoosterPredictContribsDevice.argtypes = [vp, vp, i32, C.c_uint, vp, vp]
+    lib.OHXBoosterPredictInteractions.argtypes = [vp, vp, i32, C.c_uint, C.POINTER(u64), C.POINTER(C.POINTER(f32))]
+    lib.OHXBoosterPredictInteractionsDevice.argtypes = [vp, vp, i32, C.c_uint, vp, vp]
     lib.OHXBoosterPredictFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32,
                                             f32, i32, f32, vp, vp]
     lib.OHXBoosterPredictFieldsDevice.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32,
@@ -312,6 +315,25 @@ class Booster:
         """The same into device memory: out_ptr holds nrow * (F + 1) float32; only enqueues on `stream`."""
         check(self.lib, self.lib.OHXBoosterPredictContribsDevice(self.handle, dmat.handle, int(bool(approximate)),
                                                                   ntree_limit, out_ptr, stream))
+
+    def predict_interactions(self, dmat: DMatrix, approximate: bool = False, ntree_limit: int = 0) -> np.ndarray:
+        """SHAP interaction values, (nrow, F + 1, F + 1) float32, index F the bias (OHXBoosterPredictInteractions):
+        exact, or with approximate=True the approximate contributions on the diagonal."""
+        n = C.c_uint64()
+        ptr = C.POINTER(C.c_float)()
+        check(self.lib, self.lib.OHXBoosterPredictInteractions(self.handle, dmat.handle, int(bool(approximate)),
+                                                                ntree_limit, C.byref(n), C.byref(ptr)))
+        nrow = dmat.num_row
+        if n.value == 0:
+            return np.empty((nrow, 0, 0), dtype=np.float32)
+        side = int(round((n.value // nrow) ** 0.5))
+        return np.ctypeslib.as_array(ptr, shape=(n.value,)).reshape(nrow, side, side).copy()
+
+    def predict_interactions_device(self, dmat: DMatrix, out_ptr: int, approximate: bool = False,
+                                    ntree_limit: int = 0, stream: int = 0) -> None:
+        """The same into device memory: out_ptr holds nrow * (F + 1)^2 float32; only enqueues on `stream`."""
+        check(self.lib, self.lib.OHXBoosterPredictInteractionsDevice(self.handle, dmat.handle, int(bool(approximate)),
+                                                                      ntree_limit, out_ptr, stream))
 
     def predict_fields(self, fields: Sequence[np.ndarray], is2d: Sequence[bool], pl_feature: int, im: int, jm: int,
                        km: int, k1: int, k2: int, missing: float, oh_ml: np.ndarray, *, apply_pow10: bool = True,

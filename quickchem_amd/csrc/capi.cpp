@@ -532,8 +532,18 @@ struct ContribsState {
   DevBuf<uint32_t> d_flags;
   PinnedBuf<float> h_out;
   PinnedBuf<uint32_t> h_flags;
+  // SHAP interaction values (OHXBoosterPredictInteractions) share the tables above and have buffers of their own: the
+  // feature-path index (exact mode, built at the first exact interactions call), the contributions phi, the partials
+  // of both split launches, the host form's output and its host copy
+  bool index_ready = false;
+  DevBuf<uint32_t> d_fpaths, d_fstart;
+  DevBuf<float> d_iphi, d_ipart, d_iout;
+  PinnedBuf<float> h_iout;
   void release_device() {
-    for (DevBuf<float>* f : {&d_coef, &d_out, &d_part}) f->release();
+    for (DevBuf<float>* f : {&d_coef, &d_out, &d_part, &d_iphi, &d_ipart, &d_iout}) f->release();
+    d_fpaths.release();
+    d_fstart.release();
+    index_ready = false;
     d_heads.release();
     d_elems.release();
     d_class_start.release();
@@ -1208,7 +1218,7 @@ void launch_predict_checked(BoosterObj& b, DMatrixObj& d, int option_mask, unsig
 // (ensure_uploaded: it may just have been moved by "ohx_device"), and device tables left on another device are
 // released and built again here - so nothing a caller takes from the state or the booster afterwards (buffers,
 // b.dev, b.s_exec) is stale.  A model that cannot have contributions keeps its reason and is refused again at once.
-ContribsState& contribs_tables(BoosterObj& b, bool approximate) {
+ContribsState& contribs_tables(BoosterObj& b, bool approximate, bool interactions = false) {
   if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
   if (!b.margin_error.empty()) throw OhxError(b.margin_error);
   if (!b.contribs) b.contribs.reset(new ContribsState());
@@ -1257,6 +1267,14 @@ ContribsState& contribs_tables(BoosterObj& b, bool approximate) {
     c.d_class_start.upload(pt.class_start);
     c.d_coef.upload(unwind_coefficients());
     c.exact_ready = true;
+  }
+  if (interactions && !approximate && !c.index_ready) {
+    // the path table's host copy is not kept once it is on the device: build it again for the index
+    if (pt.heads.empty()) pt = build_path_table(b.forest);
+    const FeaturePathIndex ix = build_feature_path_index(pt, (uint32_t)b.forest.trees.size(), b.forest.num_feature);
+    c.d_fpaths.upload(ix.paths);
+    c.d_fstart.upload(ix.start);
+    c.index_ready = true;
   }
   if (approximate && !c.approx_ready) {
     std::vector<uint32_t> roots;
@@ -1310,6 +1328,86 @@ ContribsState& launch_contribs_checked(BoosterObj& b, DMatrixObj& d, int approxi
   a.out = d_out;
   if (plan.split) c.d_part.ensure((size_t)plan.part_floats);
   HIP_CHECK((hipError_t)launch_contribs(approximate != 0, a, plan, c.d_part.p, stream));
+  return c;
+}
+
+// SHAP interaction values, as launch_contribs_checked: every refusal and every allocation before anything is
+// enqueued.  The contributions phi go to the state's own scratch (the contribs launch, same plan as a contribs call),
+// then the matrix is filled behind them on the same stream.
+ContribsState& launch_interactions_checked(BoosterObj& b, DMatrixObj& d, int approximate, unsigned ntree_limit,
+                                           float* d_out, bool host_form, hipStream_t stream) {
+  if (approximate != 0 && approximate != 1) throw OhxError("approximate must be 0 (exact TreeSHAP) or 1");
+  if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
+  if (!host_form && d_out == nullptr && d.nrow != 0)
+    throw OhxError("OHXBoosterPredictInteractionsDevice: d_out is NULL");
+  if (!host_form && stream_capturing(stream))
+    refuse_in_capture("compute SHAP interaction values",
+                      "OHXBoosterPredictInteractionsDevice is not capturable; call it outside the capture");
+  check_columns(b, d.ncol);
+  ContribsState& c = contribs_tables(b, approximate != 0, true);
+  if (d.device >= 0 && d.device != b.dev.ordinal)
+    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
+                   std::to_string(b.dev.ordinal));
+  const uint32_t F = b.forest.num_feature;
+  const uint64_t F1 = (uint64_t)F + 1;
+  if (d.nrow > (uint64_t)(SIZE_MAX / sizeof(float)) / (F1 * F1))
+    throw OhxError("SHAP interaction values: " + std::to_string(d.nrow) + " rows of " + std::to_string(F1 * F1) +
+                   " floats do not fit in memory");
+  ContribsArgs a;
+  a.rows = d.d_data;
+  a.nrow = d.nrow;
+  a.ncol = (uint32_t)d.ncol;
+  a.missing = d.missing;
+  a.nfeat = F;
+  tree_range(b, ntree_limit, &a.tree_begin, &a.tree_end);
+  a.bias = contrib_bias(b.forest, c.means, a.tree_begin, a.tree_end, b.margin_base);
+  a.heads = c.d_heads.p;
+  a.elems = c.d_elems.p;
+  a.class_start = c.d_class_start.p;
+  a.coef = c.d_coef.p;
+  a.nodes = c.d_nodes.p;
+  a.roots = c.d_roots.p;
+  const uint32_t ntree = a.tree_end - a.tree_begin;
+  const ContribsPlan cplan = plan_contribs(d.nrow, F, ntree, b.contribs_split);
+  const ContribsPlan iplan = approximate ? ContribsPlan{} : plan_interactions(d.nrow, F, ntree, b.contribs_split);
+  if (host_form) {
+    stream = b.s_exec;
+    if (d.owned == nullptr) order_behind_caller(b.dev.ordinal, stream);
+  }
+  try {
+    if (host_form) {
+      c.d_iout.ensure((size_t)(d.nrow * F1 * F1));
+      c.h_iout.ensure((size_t)(d.nrow * F1 * F1));
+    }
+    c.d_iphi.ensure((size_t)(d.nrow * F1));
+    const uint64_t part = std::max(cplan.part_floats, iplan.part_floats);
+    if (part) c.d_ipart.ensure((size_t)part);
+  } catch (const OhxError&) {
+    (void)hipGetLastError();   // a failed allocation must not surface again as the error of a later launch
+    throw;
+  }
+  if (host_form) {
+    d_out = c.d_iout.p;
+    a.flags = c.d_flags.p;
+  }
+  a.out = c.d_iphi.p;
+  HIP_CHECK((hipError_t)launch_contribs(approximate != 0, a, cplan, c.d_ipart.p, stream));
+  InteractionsArgs ia;
+  ia.rows = a.rows;
+  ia.nrow = a.nrow;
+  ia.ncol = a.ncol;
+  ia.missing = a.missing;
+  ia.nfeat = F;
+  ia.tree_begin = a.tree_begin;
+  ia.tree_end = a.tree_end;
+  ia.phi = c.d_iphi.p;
+  ia.out = d_out;
+  ia.heads = c.d_heads.p;
+  ia.elems = c.d_elems.p;
+  ia.fpaths = c.d_fpaths.p;
+  ia.fstart = c.d_fstart.p;
+  ia.coef = c.d_coef.p;
+  HIP_CHECK((hipError_t)launch_interactions(approximate != 0, ia, iplan, c.d_ipart.p, stream));
   return c;
 }
 
@@ -1760,6 +1858,40 @@ int OHXBoosterPredictContribsDevice(BoosterHandle handle, DMatrixHandle dmat, in
   BoosterObj* b = as_booster(handle);
   DMatrixObj* d = as_dmat(dmat);
   launch_contribs_checked(*b, *d, approximate, ntree_limit, d_out, false, static_cast<hipStream_t>(stream));
+  d->used_async = true;
+  API_END();
+}
+
+int OHXBoosterPredictInteractions(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
+                                  bst_ulong* out_len, const float** out_result) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  DMatrixObj* d = as_dmat(dmat);
+  if (out_len == nullptr || out_result == nullptr)
+    throw OhxError("OHXBoosterPredictInteractions: NULL output argument");
+  ContribsState& c = launch_interactions_checked(*b, *d, approximate, ntree_limit, nullptr, true, nullptr);
+  hipStream_t s = b->s_exec;
+  const size_t F1 = (size_t)b->forest.num_feature + 1;
+  const size_t count = (size_t)d->nrow * F1 * F1;
+  if (count) HIP_CHECK(hipMemcpyAsync(c.h_iout.p, c.d_iout.p, count * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(c.h_flags.p, c.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (c.h_flags.p[0] != 0) {
+    HIP_CHECK(hipMemsetAsync(c.d_flags.p, 0, sizeof(uint32_t), s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    throw OhxError("Input data contains `inf` or `nan`");
+  }
+  *out_len = count;
+  *out_result = c.h_iout.p;
+  API_END();
+}
+
+int OHXBoosterPredictInteractionsDevice(BoosterHandle handle, DMatrixHandle dmat, int approximate,
+                                        unsigned ntree_limit, float* d_out, void* stream) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  DMatrixObj* d = as_dmat(dmat);
+  launch_interactions_checked(*b, *d, approximate, ntree_limit, d_out, false, static_cast<hipStream_t>(stream));
   d->used_async = true;
   API_END();
 }

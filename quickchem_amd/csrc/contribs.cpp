@@ -184,4 +184,51 @@ ContribsPlan plan_contribs(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool a
   return p;
 }
 
+FeaturePathIndex build_feature_path_index(const PathTable& pt, uint32_t ntree, uint32_t nfeat) {
+  constexpr int K = kPathClasses;
+  FeaturePathIndex ix;
+  ix.start.assign((size_t)ntree * nfeat * (K + 1), 0u);
+  std::vector<uint32_t> count((size_t)ntree * nfeat * K, 0u);
+  for (uint32_t t = 0; t < ntree; ++t)
+    for (int c = 0; c < K; ++c)
+      for (uint32_t p = pt.class_start[(size_t)t * (K + 1) + c]; p < pt.class_start[(size_t)t * (K + 1) + c + 1]; ++p)
+        for (uint32_t k = 0; k < pt.heads[p].len; ++k)
+          ++count[((size_t)t * nfeat + (pt.elems[pt.heads[p].first + k].feat & 0x7FFFFFFFu)) * K + c];
+  uint32_t at = 0;
+  for (size_t tf = 0; tf < (size_t)ntree * nfeat; ++tf) {
+    for (int c = 0; c < K; ++c) {
+      ix.start[tf * (K + 1) + c] = at;
+      at += count[tf * K + c];
+    }
+    ix.start[tf * (K + 1) + K] = at;
+  }
+  ix.paths.resize(at);
+  std::vector<uint32_t> cursor(count.size());
+  for (size_t tf = 0; tf < (size_t)ntree * nfeat; ++tf)
+    for (int c = 0; c < K; ++c) cursor[tf * K + c] = ix.start[tf * (K + 1) + c];
+  for (uint32_t t = 0; t < ntree; ++t)
+    for (int c = 0; c < K; ++c)
+      for (uint32_t p = pt.class_start[(size_t)t * (K + 1) + c]; p < pt.class_start[(size_t)t * (K + 1) + c + 1]; ++p)
+        for (uint32_t k = 0; k < pt.heads[p].len; ++k)
+          ix.paths[cursor[((size_t)t * nfeat + (pt.elems[pt.heads[p].first + k].feat & 0x7FFFFFFFu)) * K + c]++] = p;
+  return ix;
+}
+
+ContribsPlan plan_interactions(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool allow_split) {
+  ContribsPlan p;
+  const uint64_t tiles = (nrow + kContribsTileRows - 1) / kContribsTileRows;
+  const uint64_t units = tiles * nfeat;   // the direct shape's waves: one per (tile, conditioning feature)
+  if (!allow_split || units == 0 || ntree < 2 || units * 2 > kWaveSlots) return p;
+  const uint64_t part = units * ntree * (uint64_t)nfeat * kContribsTileRows;
+  if (part * sizeof(float) > kPartBudgetBytes) return p;
+  uint64_t want = (kWaveSlots + units - 1) / units;
+  if (want > ntree) want = ntree;
+  if (want < 2) return p;
+  p.trees_per_group = (uint32_t)((ntree + want - 1) / want);
+  p.groups = (ntree + p.trees_per_group - 1) / p.trees_per_group;
+  p.split = p.groups > 1;
+  p.part_floats = p.split ? part : 0;
+  return p;
+}
+
 }  // namespace ohx

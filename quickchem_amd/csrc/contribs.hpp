@@ -123,4 +123,47 @@ ContribsPlan plan_contribs(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool a
 // Returns a hipError_t.
 int launch_contribs(bool approximate, const ContribsArgs& a, const ContribsPlan& plan, float* part, void* stream);
 
+// ---- SHAP interaction values (interactions.hip; include/ohxgb.h OHXBoosterPredictInteractions) ----
+//
+// Exact mode conditions on one feature i at a time: a wave owns one (64-row tile, feature i, tree group) and walks,
+// tree by tree, only the paths that hold i.  The feature-path index lists them: for tree t and feature f,
+// paths[start[(t * nfeat + f) * (kPathClasses + 1) + c] ..] are the table's paths of length class c that hold f, in
+// table order.  One entry per path element: as many entries as the table has elements (4 bytes each).
+struct FeaturePathIndex {
+  std::vector<uint32_t> paths;
+  std::vector<uint32_t> start;   // [tree][nfeat][kPathClasses + 1]
+  uint64_t bytes() const { return (paths.size() + start.size()) * sizeof(uint32_t); }
+};
+FeaturePathIndex build_feature_path_index(const PathTable& pt, uint32_t ntree, uint32_t nfeat);
+
+struct InteractionsArgs {
+  const float* rows = nullptr;   // [nrow][ncol], device
+  uint64_t nrow = 0;
+  uint32_t ncol = 0;
+  float missing = 0.0f;
+  uint32_t nfeat = 0;            // F: out is [nrow][F + 1][F + 1]
+  uint32_t tree_begin = 0, tree_end = 0;
+  const float* phi = nullptr;    // [nrow][F + 1]: the same rows' contributions over the same trees, same mode
+  float* out = nullptr;
+  // exact mode
+  const PathHead* heads = nullptr;
+  const PathElem* elems = nullptr;
+  const uint32_t* fpaths = nullptr;   // FeaturePathIndex
+  const uint32_t* fstart = nullptr;
+  const float* coef = nullptr;
+};
+
+// Exact mode's launch shape.  A direct wave is one (tile, feature); a batch whose direct waves leave most of the
+// chip's wave slots empty has its trees split over waves, every (tile, feature, tree group) wave storing each tree's
+// matrix row in `part` (tiles x nfeat x ntree x nfeat x 64 floats, at most kPartBudgetBytes), summed in tree order by
+// a second launch.  Direct launches hold at most kDirectTilesPerLaunch waves.  Host logic (contribs.cpp).
+ContribsPlan plan_interactions(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool allow_split);
+inline uint64_t interactions_tiles_per_launch(uint32_t nfeat) {
+  return nfeat == 0 || nfeat >= kDirectTilesPerLaunch ? 1 : kDirectTilesPerLaunch / nfeat;
+}
+// Enqueues on `stream`, after the launch that filled a.phi: exact mode's off-diagonals (plan, `part`), then the
+// diagonal and the bias row and column.  Approximate mode: the diagonal only, off-diagonals 0.  Returns a hipError_t.
+int launch_interactions(bool approximate, const InteractionsArgs& a, const ContribsPlan& plan, float* part,
+                        void* stream);
+
 }  // namespace ohx

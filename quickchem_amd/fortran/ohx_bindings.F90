@@ -15,6 +15,7 @@ module ohx_bindings
    public :: XGDMatrixCreateFromMat, XGDMatrixFree, XGDMatrixNumRow, XGDMatrixNumCol
    public :: XGBoosterCreate, XGBoosterFree, XGBoosterLoadModel, XGBoosterSaveModel
    public :: XGBoosterPredict, XGBoosterSetParam, OHXBoosterPredictFields, OHXDMatrixSetGrid, OHXBoosterPredictContribs
+   public :: OHXBoosterPredictInteractions
    public :: OHXCommGetUniqueId, OHXCommInitRank, OHXCommFree, OHXCommInfo, OHXShardRows, OHXAllGatherOH, OHX_UNIQUE_ID_BYTES
    public :: ohx_last_error, ohx_c_string
 
@@ -125,6 +126,19 @@ module ohx_bindings
       ! (F + 1, nrow) array through c_f_pointer), column F + 1 the bias; valid until the next contribs call.
       function OHXBoosterPredictContribs(handle, dmat, approximate, ntree_limit, out_len, out_result) &
             bind(C, name="OHXBoosterPredictContribs") result(rc)
+         import :: c_int, c_ptr, c_int64_t
+         type(c_ptr), value         :: handle, dmat
+         integer(c_int), value      :: approximate, ntree_limit
+         integer(c_int64_t)         :: out_len
+         type(c_ptr)                :: out_result
+         integer(c_int)             :: rc
+      end function
+
+      ! SHAP interaction values (ohxgb.h part 2): out_result points at nrow * (F + 1)**2 floats owned by the booster
+      ! (row-major [row][i][k]: in Fortran an (F + 1, F + 1, nrow) array through c_f_pointer, index F + 1 the bias);
+      ! valid until the next interactions call.
+      function OHXBoosterPredictInteractions(handle, dmat, approximate, ntree_limit, out_len, out_result) &
+            bind(C, name="OHXBoosterPredictInteractions") result(rc)
          import :: c_int, c_ptr, c_int64_t
          type(c_ptr), value         :: handle, dmat
          integer(c_int), value      :: approximate, ntree_limit

@@ -68,6 +68,10 @@ def _load():
                                          C.c_uint, C.c_void_p]
         lib.ohx_contribs_table_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_contribs_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
+        lib.ohx_interactions_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float,
+                                             C.c_int, C.c_uint, C.c_void_p]
+        lib.ohx_interactions_table_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.ohx_interactions_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
         _lib = lib
     return _lib
 
@@ -207,6 +211,38 @@ def contribs_plan(nrow: int, nfeat: int, ntree: int, allow_split: bool = True):
     p = (C.c_uint64 * 4)()
     _check(_load().ohx_contribs_plan(nrow, nfeat, ntree, 1 if allow_split else 0, p))
     return bool(p[0]), int(p[1]), int(p[2]), int(p[3])
+
+
+def interactions_cpu(image, rows: np.ndarray, num_feature: int, missing: float = XX_MISS, approximate: bool = False,
+                     ntree_limit: int = 0) -> np.ndarray:
+    """Host restatement of SHAP interaction values (csrc/contribs_host.cpp: xgboost 1.6.0's
+    PredictInteractionContributions, in float): (nrow, num_feature + 1, num_feature + 1) float32, index num_feature
+    the bias.  2 * num_feature + 3 TreeSHAP passes per row.  Test support."""
+    lib = _load()
+    src = np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else image
+    rows = np.ascontiguousarray(rows, dtype=np.float32)
+    out = np.empty((rows.shape[0], num_feature + 1, num_feature + 1), dtype=np.float32)
+    _check(lib.ohx_interactions_cpu(src.ctypes.data, src.nbytes, rows.ctypes.data, rows.shape[0], rows.shape[1],
+                                    missing, 1 if approximate else 0, ntree_limit, out.ctypes.data))
+    return out
+
+
+def interactions_table_stats(image) -> Dict[str, int]:
+    """Exact interactions' feature-path index size and the path sums (d = distinct features of a path)."""
+    lib = _load()
+    src = np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else image
+    st = (C.c_uint64 * 5)()
+    _check(lib.ohx_interactions_table_stats(src.ctypes.data, src.nbytes, st))
+    return {"index_bytes": int(st[0]), "paths": int(st[1]), "sum_d": int(st[2]), "sum_d2": int(st[3]),
+            "sum_d3": int(st[4])}
+
+
+def interactions_plan(nrow: int, nfeat: int, ntree: int, allow_split: bool = True):
+    """The launch shape OHXBoosterPredictInteractions picks for exact mode (csrc/contribs.cpp plan_interactions):
+    (split, groups, trees_per_group, direct_launches, part_floats) - direct_launches 0 when split."""
+    p = (C.c_uint64 * 5)()
+    _check(_load().ohx_interactions_plan(nrow, nfeat, ntree, 1 if allow_split else 0, p))
+    return bool(p[0]), int(p[1]), int(p[2]), int(p[3]), int(p[4])
 
 
 # ---- device generators (torch tensors in HBM; libohx_synth_gpu.so, test support like the rest of this file) ----
