@@ -299,6 +299,35 @@ int OHXBoosterPredictInteractions(BoosterHandle handle, DMatrixHandle dmat, int 
 int OHXBoosterPredictInteractionsDevice(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
                                         float* d_out, void* stream);
 
+/* Per-feature contributions from the MAPL fields, one 3-D array per feature: OHXBoosterPredictContribs without the
+ * row matrix.  Inputs as OHXBoosterPredictFields, gather included: fields[f] is (im,jm,km) Fortran order, or (im,jm)
+ * when is2d[f] != 0 (broadcast over the levels); field pl_feature is divided by 100 as a float32 division (-1: none);
+ * a value equal to `missing`, or NaN, is missing; features at or past nfield (nfield <= num_feature) are missing.
+ * Gridcell m = i + im*(j + jm*(k-k1)) for k = k1..k2 (1-based, inclusive).
+ * Output: out[0..F], F the booster's num_feature; out[f] an (im,jm,km) Fortran-order array, out[F] the bias.  For
+ * k1 <= k <= k2, out[f](i,j,k) is, bit for bit, what OHXBoosterPredictContribs returns at [m][f] (same `approximate`
+ * and ntree_limit) for the row the fields kernels walk for gridcell m.  Levels outside k1..k2 are left untouched.  A
+ * NULL out[f] is not computed into anything nor copied back; all NULL is refused.  k2 == k1 - 1 does nothing and
+ * succeeds.  A gridcell's bits depend on neither the launch shape ("ohx_contribs_split" applies), the form, nor the
+ * slab it is in.
+ * Host form: host pointers; the slab (3-D fields: levels k1..k2 only) and the requested outputs are staged in buffers
+ * of the booster's contributions state (never one of the predict, fields or Run1 paths; dropped with the model and at
+ * XGBoosterFree, rebuilt after an "ohx_device" move), and the call returns when every requested out[f] is written.
+ * +-inf in a gathered value of the slab (after the PL division) is an error unless `missing` is itself infinite, in
+ * both modes.  Device form: device pointers, work enqueued on `stream`; +-inf is not checked (as in
+ * OHXBoosterPredictContribsDevice); not capturable.
+ * Refused (-1, nothing enqueued): what OHXBoosterPredictContribs refuses (no model, unknown margin base, a split
+ * without cover, a path over 32 distinct features in exact mode, approximate not 0 or 1); what the fields forms
+ * refuse, with their messages (nfield over num_feature or 32, a booster over 32 features, im, jm or km not positive, a
+ * bad k range, NULL fields, is2d, out or field); every out[f] NULL; for the device form, a stream being captured. */
+int OHXBoosterPredictContribsFields(BoosterHandle handle, const float* const fields[], const int32_t is2d[],
+                                    int nfield, int pl_feature, int im, int jm, int km, int k1, int k2,
+                                    float missing, int approximate, unsigned ntree_limit, float* const out[]);
+int OHXBoosterPredictContribsFieldsDevice(BoosterHandle handle, const float* const d_fields[], const int32_t is2d[],
+                                          int nfield, int pl_feature, int im, int jm, int km, int k1, int k2,
+                                          float missing, int approximate, unsigned ntree_limit,
+                                          float* const d_out[], void* stream);
+
 /* The whole of predict_OH_with_XGB's RUN section in one kernel
  * (OH_GridCompMod.F90:303-383): gathers the 27 MAPL fields in place (field f is
  * (im,jm,km) Fortran order, or (im,jm) when is2d[f] != 0; feature order of

@@ -29,6 +29,7 @@ ABI_SYMBOLS = [
     "OHXDeviceCount", "OHXDMatrixCreateFromDevice", "OHXDMatrixSetGrid", "OHXDMatrixGetGrid", "OHXDMatrixInferGrid", "OHXBoosterPredictDevice", "OHXBoosterCheck",
     "OHXBoosterPredictContribs", "OHXBoosterPredictContribsDevice",
     "OHXBoosterPredictInteractions", "OHXBoosterPredictInteractionsDevice",
+    "OHXBoosterPredictContribsFields", "OHXBoosterPredictContribsFieldsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
     "OHXJulianDay", "OHXSolarGeometry", "OHXSolarGeometryDevice", "OHXBoosterGetInfo", "OHXBoosterKernelSymbol", "OHXBoosterKernelSymbolRows",
     "OHXBoosterRingReruns", "OHXBoosterCopyEngineChoice", "OHXUnregisterHost", "OHXReleaseScratch",
@@ -115,6 +116,10 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.OHXBoosterPredictContribsDevice.argtypes = [vp, vp, i32, C.c_uint, vp, vp]
     lib.OHXBoosterPredictInteractions.argtypes = [vp, vp, i32, C.c_uint, C.POINTER(u64), C.POINTER(C.POINTER(f32))]
     lib.OHXBoosterPredictInteractionsDevice.argtypes = [vp, vp, i32, C.c_uint, vp, vp]
+    lib.OHXBoosterPredictContribsFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32,
+                                                    i32, i32, f32, i32, C.c_uint, C.POINTER(vp)]
+    lib.OHXBoosterPredictContribsFieldsDevice.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32,
+                                                          i32, i32, i32, f32, i32, C.c_uint, C.POINTER(vp), vp]
     lib.OHXBoosterPredictFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32,
                                             f32, i32, f32, vp, vp]
     lib.OHXBoosterPredictFieldsDevice.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32,
@@ -356,6 +361,40 @@ class Booster:
         check(self.lib, self.lib.OHXBoosterPredictFieldsDevice(
             self.handle, ptrs, flags, nf, pl_feature, im, jm, km, k1, k2, missing, 1 if apply_pow10 else 0, ohscale,
             oh_ml_ptr, margin_ptr or None, stream or None))
+
+    def predict_contribs_fields(self, fields: Sequence[np.ndarray], is2d: Sequence[bool], pl_feature: int, im: int,
+                                jm: int, km: int, k1: int, k2: int, missing: float,
+                                out: Sequence[Optional[np.ndarray]], *, approximate: bool = False,
+                                ntree_limit: int = 0) -> None:
+        """Per-feature contributions of the slab k1..k2 (1-based) from the fields, as predict_fields gathers them
+        (OHXBoosterPredictContribsFields).  `out` holds F + 1 entries, F the booster's feature count: writable
+        Fortran-order float32 host arrays of im * jm * km elements (out[F] the bias), or None for one not wanted."""
+        nf = len(fields)
+        for a in out:
+            if a is not None and (not isinstance(a, np.ndarray) or a.dtype != np.float32 or
+                                  not a.flags["F_CONTIGUOUS"] or not a.flags["WRITEABLE"] or a.size < im * jm * km):
+                raise ValueError("out: writable Fortran-order float32 arrays of at least im * jm * km elements, or None")
+        ptrs = (C.c_void_p * nf)(*[f.ctypes.data for f in fields])
+        flags = (C.c_int32 * nf)(*[1 if b else 0 for b in is2d])
+        # padded with NULLs to the most entries the library reads (F + 1, F <= 32 for the fields forms)
+        outs = (C.c_void_p * max(len(out), 33))(*[a.ctypes.data if a is not None else None for a in out])
+        check(self.lib, self.lib.OHXBoosterPredictContribsFields(
+            self.handle, ptrs, flags, nf, pl_feature, im, jm, km, k1, k2, missing, int(bool(approximate)), ntree_limit,
+            outs))
+
+    def predict_contribs_fields_device(self, field_ptrs: Sequence[int], is2d: Sequence[bool], pl_feature: int,
+                                       im: int, jm: int, km: int, k1: int, k2: int, missing: float,
+                                       out_ptrs: Sequence[int], *, approximate: bool = False, ntree_limit: int = 0,
+                                       stream: int = 0) -> None:
+        """The same on device pointers (out_ptrs: F + 1 device addresses, 0 for one not wanted); only enqueues on
+        `stream`."""
+        nf = len(field_ptrs)
+        ptrs = (C.c_void_p * nf)(*field_ptrs)
+        flags = (C.c_int32 * nf)(*[1 if b else 0 for b in is2d])
+        outs = (C.c_void_p * max(len(out_ptrs), 33))(*[p or None for p in out_ptrs])
+        check(self.lib, self.lib.OHXBoosterPredictContribsFieldsDevice(
+            self.handle, ptrs, flags, nf, pl_feature, im, jm, km, k1, k2, missing, int(bool(approximate)), ntree_limit,
+            outs, stream or None))
 
     def run1_prepare(self, state: dict, *, dynamic_k_range: bool, tropp_min: float = 4000.0, ohscale: float = 0.85,
                      missing: float = -999.0, avogad: float = 6.023e26, runiv: float = 8314.47,

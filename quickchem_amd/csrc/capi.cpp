@@ -167,10 +167,29 @@ hipStream_t exec_stream() {
   return lib_streams(cur).exec;
 }
 
+// Owns its allocation: movable (a std::vector of them may reallocate), never copied - a copy would free the same
+// pointer twice and leave the survivor pointing at freed memory.
 template <class T>
 struct DevBuf {
   T* p = nullptr;
   size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept : p(o.p), n(o.n) {
+    o.p = nullptr;
+    o.n = 0;
+  }
+  DevBuf& operator=(DevBuf&& o) noexcept {
+    if (this != &o) {
+      release();
+      p = o.p;
+      n = o.n;
+      o.p = nullptr;
+      o.n = 0;
+    }
+    return *this;
+  }
   ~DevBuf() { release(); }
   void release() {
     if (p) (void)hipFree(p);
@@ -196,6 +215,9 @@ template <class T>
 struct PinnedBuf {
   T* p = nullptr;
   size_t n = 0;
+  PinnedBuf() = default;
+  PinnedBuf(const PinnedBuf&) = delete;             // owns its allocation, as DevBuf
+  PinnedBuf& operator=(const PinnedBuf&) = delete;
   ~PinnedBuf() {
     if (p) (void)hipHostFree(p);
   }
@@ -539,8 +561,13 @@ struct ContribsState {
   DevBuf<uint32_t> d_fpaths, d_fstart;
   DevBuf<float> d_iphi, d_ipart, d_iout;
   PinnedBuf<float> h_iout;
+  // the fields form's host form (OHXBoosterPredictContribsFields): the staged slab, one buffer per field, and the
+  // requested outputs, one slab of gridcells each (its split launches use d_part above)
+  std::vector<DevBuf<float>> d_fstage;
+  DevBuf<float> d_fout;
   void release_device() {
-    for (DevBuf<float>* f : {&d_coef, &d_out, &d_part, &d_iphi, &d_ipart, &d_iout}) f->release();
+    for (DevBuf<float>* f : {&d_coef, &d_out, &d_part, &d_iphi, &d_ipart, &d_iout, &d_fout}) f->release();
+    d_fstage.clear();
     d_fpaths.release();
     d_fstart.release();
     index_ready = false;
@@ -1904,8 +1931,8 @@ int OHXBoosterCheck(BoosterHandle handle, void* stream) {
   API_END();
 }
 
-static void fields_common(BoosterObj& b, FieldsArgs& a, const int32_t is2d[], int nfield, int pl_feature, int im,
-                          int jm, int km, int k1, int k2, float missing, int apply_pow10, float ohscale) {
+// the fields forms' checks of the grid and the field count (predict and contributions)
+static void check_fields_shape(const BoosterObj& b, int nfield, int im, int jm, int km, int k1, int k2) {
   if (nfield < 0 || nfield > 32) throw OhxError("predict_fields: nfield must be 0..32");
   if ((uint32_t)nfield > b.forest.num_feature)
     throw OhxError("Number of columns does not match number of features in booster (" + std::to_string(nfield) +
@@ -1913,6 +1940,11 @@ static void fields_common(BoosterObj& b, FieldsArgs& a, const int32_t is2d[], in
   if (b.forest.num_feature > 32) throw OhxError("predict_fields supports boosters with at most 32 features");
   if (im <= 0 || jm <= 0 || km <= 0) throw OhxError("predict_fields: im, jm, km must be positive");
   if (k1 < 1 || k2 > km || k2 < k1 - 1) throw OhxError("predict_fields: need 1 <= k1, k2 <= km, k2 >= k1 - 1");
+}
+
+static void fields_common(BoosterObj& b, FieldsArgs& a, const int32_t is2d[], int nfield, int pl_feature, int im,
+                          int jm, int km, int k1, int k2, float missing, int apply_pow10, float ohscale) {
+  check_fields_shape(b, nfield, im, jm, km, k1, k2);
   if (!objective_is_identity(b.forest.objective))
     throw OhxError("objective '" + b.forest.objective + "' is not supported by predict_fields");
   a.is2d_mask = 0;
@@ -2060,6 +2092,116 @@ int OHXBoosterPredictFields(BoosterHandle handle, const float* const fields[], c
   HIP_CHECK(hipStreamSynchronize(b->s_exec));
   for (hipEvent_t ev : events) (void)hipEventDestroy(ev);
   raise_flag_errors(*b, b->s_exec);
+  API_END();
+}
+
+// Contributions from the fields, both forms: the fields forms' checks and the contribs forms', in
+// launch_contribs_checked's order (the booster is settled on its device before the state and the stream are taken),
+// every allocation before anything is enqueued.  The host form (host_form, `fields` and `out` host pointers) stages
+// the slab and the requested outputs in the contribs state's own buffers and copies each requested output's slab back.
+static void contribs_fields_call(BoosterObj& b, const float* const fields[], const int32_t is2d[], int nfield,
+                                 int pl_feature, int im, int jm, int km, int k1, int k2, float missing, int approximate,
+                                 unsigned ntree_limit, float* const out[], bool host_form, hipStream_t stream) {
+  if (fields == nullptr || is2d == nullptr || out == nullptr) throw OhxError("predict_fields: NULL argument");
+  if (approximate != 0 && approximate != 1) throw OhxError("approximate must be 0 (exact TreeSHAP) or 1");
+  if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
+  if (!host_form && stream_capturing(stream))
+    refuse_in_capture("compute feature contributions",
+                      "OHXBoosterPredictContribsFieldsDevice is not capturable; call it outside the capture");
+  check_fields_shape(b, nfield, im, jm, km, k1, k2);
+  for (int f = 0; f < nfield; ++f)
+    if (fields[f] == nullptr) throw OhxError("predict_fields: field " + std::to_string(f) + " is NULL");
+  const uint32_t F = b.forest.num_feature;
+  uint32_t nout = 0;
+  for (uint32_t f = 0; f <= F; ++f) nout += out[f] != nullptr ? 1u : 0u;
+  if (nout == 0) throw OhxError("feature contributions from fields: every entry of out is NULL");
+  ContribsState& c = contribs_tables(b, approximate != 0);
+  if (k2 < k1) return;
+  const uint64_t plane = (uint64_t)im * (uint64_t)jm;
+  const uint64_t nrow = plane * (uint64_t)(k2 - k1 + 1);
+  const uint64_t slab = plane * (uint64_t)(k1 - 1);
+  ContribsArgs a;
+  a.nfeat = F;
+  a.missing = missing;
+  tree_range(b, ntree_limit, &a.tree_begin, &a.tree_end);
+  a.bias = contrib_bias(b.forest, c.means, a.tree_begin, a.tree_end, b.margin_base);
+  a.heads = c.d_heads.p;
+  a.elems = c.d_elems.p;
+  a.class_start = c.d_class_start.p;
+  a.coef = c.d_coef.p;
+  a.nodes = c.d_nodes.p;
+  a.roots = c.d_roots.p;
+  FieldsContribsArgs fa;
+  for (int f = 0; f < nfield; ++f)
+    if (is2d[f]) fa.is2d_mask |= 1u << f;
+  fa.pl_feature = pl_feature < 0 ? 0xFFFFFFFFu : (uint32_t)pl_feature;
+  fa.nfield = (uint32_t)nfield;
+  fa.missing = missing;
+  fa.plane = plane;
+  fa.nrow = nrow;
+  const ContribsPlan plan = plan_contribs(nrow, F, a.tree_end - a.tree_begin, b.contribs_split);
+  if (host_form) stream = b.s_exec;            // taken after contribs_tables: the booster's current device
+  try {
+    if (host_form) {
+      if (c.d_fstage.size() < (size_t)nfield) c.d_fstage.resize((size_t)nfield);
+      for (int f = 0; f < nfield; ++f) c.d_fstage[(size_t)f].ensure(is2d[f] ? plane : nrow);
+      c.d_fout.ensure((size_t)(nout * nrow));
+    }
+    if (plan.split) c.d_part.ensure((size_t)plan.part_floats);
+  } catch (const OhxError&) {
+    (void)hipGetLastError();   // a failed allocation must not surface again as the error of a later launch
+    throw;
+  }
+  if (host_form) {
+    // 3-D fields: the slab's levels only, as the fields predict stages them
+    for (int f = 0; f < nfield; ++f) {
+      float* dst = c.d_fstage[(size_t)f].p;
+      if (is2d[f]) HIP_CHECK(hipMemcpyAsync(dst, fields[f], plane * sizeof(float), hipMemcpyHostToDevice, stream));
+      else HIP_CHECK(hipMemcpyAsync(dst, fields[f] + slab, nrow * sizeof(float), hipMemcpyHostToDevice, stream));
+      fa.field[f] = dst;
+    }
+    uint32_t s = 0;
+    for (uint32_t f = 0; f <= F; ++f)
+      if (out[f] != nullptr) fa.out[f] = c.d_fout.p + (size_t)(s++) * nrow;
+    fa.flags = c.d_flags.p;
+  } else {
+    for (int f = 0; f < nfield; ++f) fa.field[f] = fields[f];
+    for (uint32_t f = 0; f <= F; ++f) fa.out[f] = out[f];
+    fa.src_off = slab;
+    fa.out_off = slab;
+  }
+  HIP_CHECK((hipError_t)launch_contribs_fields(approximate != 0, a, fa, plan, c.d_part.p, stream));
+  if (!host_form) return;
+  for (uint32_t f = 0; f <= F; ++f)
+    if (out[f] != nullptr)
+      HIP_CHECK(hipMemcpyAsync(out[f] + slab, fa.out[f], nrow * sizeof(float), hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipMemcpyAsync(c.h_flags.p, c.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  if (c.h_flags.p[0] != 0) {
+    HIP_CHECK(hipMemsetAsync(c.d_flags.p, 0, sizeof(uint32_t), stream));
+    HIP_CHECK(hipStreamSynchronize(stream));
+    throw OhxError("Input data contains `inf` or `nan`");
+  }
+}
+
+int OHXBoosterPredictContribsFields(BoosterHandle handle, const float* const fields[], const int32_t is2d[],
+                                    int nfield, int pl_feature, int im, int jm, int km, int k1, int k2, float missing,
+                                    int approximate, unsigned ntree_limit, float* const out[]) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  contribs_fields_call(*b, fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, approximate, ntree_limit,
+                       out, true, nullptr);
+  API_END();
+}
+
+int OHXBoosterPredictContribsFieldsDevice(BoosterHandle handle, const float* const d_fields[], const int32_t is2d[],
+                                          int nfield, int pl_feature, int im, int jm, int km, int k1, int k2,
+                                          float missing, int approximate, unsigned ntree_limit, float* const d_out[],
+                                          void* stream) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  contribs_fields_call(*b, d_fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, approximate, ntree_limit,
+                       d_out, false, static_cast<hipStream_t>(stream));
   API_END();
 }
 

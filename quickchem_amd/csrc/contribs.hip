@@ -119,8 +119,11 @@ __device__ __forceinline__ void exact_tree(const PathHead* __restrict__ heads, c
   shap_paths<32>(heads, elems, coef, cs[6], cs[7], xt, ct);
 }
 
+// The row's value of feature f is x[f * STRIDE]: a global row (STRIDE 1) or this lane's column of a row tile in LDS
+// (STRIDE kWave, `missing` already NaN there).  Features at or past `ncol` are missing.
+template <uint32_t STRIDE>
 __device__ __forceinline__ void approx_tree(const ContribsArgs& a, uint32_t t, const float* __restrict__ x,
-                                            bool missing_is_nan, float* __restrict__ ct) {
+                                            uint32_t ncol, bool missing_is_nan, float* __restrict__ ct) {
   const uint4* __restrict__ nodes = reinterpret_cast<const uint4*>(a.nodes);
   uint4 nd = nodes[a.roots[t]];
   if (nd.y == 0u) return;
@@ -129,8 +132,8 @@ __device__ __forceinline__ void approx_tree(const ContribsArgs& a, uint32_t t, c
   while (nd.y != 0u) {
     f = nd.z & 0x7FFFFFFFu;
     bool miss = true, lt = false;
-    if (f < a.ncol) {
-      const float v = x[f];
+    if (f < ncol) {
+      const float v = x[f * STRIDE];
       miss = (v != v) || (!missing_is_nan && v == a.missing);
       lt = v < __uint_as_float(nd.x);
     }
@@ -191,7 +194,7 @@ __global__ __launch_bounds__(kWave) void contribs_kernel(ContribsArgs a, uint64_
   for (uint32_t t = t0; t < t1; ++t) {
     for (uint32_t f = 0; f < F; ++f) ct[f * kWave] = 0.0f;
     if (APPROX) {
-      if (valid) approx_tree(a, t, x, missing_is_nan, ct);
+      if (valid) approx_tree<1>(a, t, x, a.ncol, missing_is_nan, ct);
     } else {
       exact_tree(heads, elems, class_start, coef, t, ta, ct);
     }
@@ -233,6 +236,131 @@ __global__ __launch_bounds__(kWave) void contribs_combine_kernel(ContribsArgs a,
   orow[F] = a.bias;
 }
 
+// ---- the fields form (OHXBoosterPredictContribsFields) ----
+//
+// A tile is 64 consecutive gridcells m of the slab, so each field's load is coalesced.  The gather is the fields
+// predict's (kernels.hip fill_tile_fields, restated here so that translation unit stays as tuned): 3-D fields at
+// src_off + m, 2-D ones at m % (im * jm), PL / 100 as a float32 division, +-inf noted after it, `missing` -> NaN,
+// fields past nfield NaN, a lane without a gridcell 0.  The row tile then feeds the same per-tree arithmetic as the
+// rows form (exact_tree, approx_tree), and each tree's vector is added into the totals in tree order from 0.0f, so a
+// gridcell's bits are those of its gathered row in OHXBoosterPredictContribs.
+// LDS: direct, three [nfeat][64] float tiles (row, tree, totals); split, two (row, tree).  Stores are feature-major:
+// per feature 64 consecutive floats of out[f]; a null out[f] is skipped (wave-uniform).
+template <bool APPROX, bool SPLIT>
+__global__ __launch_bounds__(kWave) void contribs_fields_kernel(ContribsArgs a, FieldsContribsArgs fa, uint64_t tile0,
+                                                                uint32_t trees_per_group, uint32_t groups,
+                                                                const PathHead* __restrict__ heads,
+                                                                const PathElem* __restrict__ elems,
+                                                                const uint32_t* __restrict__ class_start,
+                                                                const float4* __restrict__ coef,
+                                                                float* __restrict__ part) {
+  extern __shared__ float lds[];
+  const uint32_t lane = threadIdx.x;
+  const uint32_t F = a.nfeat;
+  const uint64_t item = blockIdx.x;
+  const uint64_t tile = tile0 + (SPLIT ? item / groups : item);
+  const uint32_t g = SPLIT ? (uint32_t)(item % groups) : 0u;
+  const uint64_t m = tile * kWave + lane;
+  const bool valid = m < fa.nrow;
+  float* __restrict__ xt = lds + lane;                            // row tile
+  float* __restrict__ ct = lds + (size_t)F * kWave + lane;        // this tree's contributions
+  float* __restrict__ tot = lds + (size_t)2 * F * kWave + lane;   // totals (direct)
+  const uint32_t t0 = a.tree_begin + g * trees_per_group;
+  const uint32_t t1 = SPLIT ? min(t0 + trees_per_group, a.tree_end) : a.tree_end;
+  const uint32_t ntree = a.tree_end - a.tree_begin;
+  const bool missing_is_nan = fa.missing != fa.missing;
+  const float qnan = __builtin_nanf("");
+  const uint64_t at3 = fa.src_off + (valid ? m : 0);
+  const uint64_t at2 = valid ? m % fa.plane : 0;
+  bool any_inf = false;
+  for (uint32_t f = 0; f < F; ++f) {
+    float v = 0.0f;
+    if (valid) {
+      v = qnan;
+      if (f < fa.nfield) {
+        const float* src = fa.field[f];
+        v = ((fa.is2d_mask >> f) & 1u) ? src[at2] : src[at3];
+        if (f == fa.pl_feature) v = v / 100.0f;
+        any_inf |= is_inf(v);
+        if (!missing_is_nan && v == fa.missing) v = qnan;
+      }
+    }
+    xt[f * kWave] = v;
+  }
+  if (!SPLIT)
+    for (uint32_t f = 0; f < F; ++f) tot[f * kWave] = 0.0f;
+  for (uint32_t t = t0; t < t1; ++t) {
+    for (uint32_t f = 0; f < F; ++f) ct[f * kWave] = 0.0f;
+    if (APPROX) {
+      if (valid) approx_tree<kWave>(a, t, xt, F, true, ct);
+    } else {
+      exact_tree(heads, elems, class_start, coef, t, xt, ct);
+    }
+    if (SPLIT) {
+      float* __restrict__ dst = part + ((tile * ntree + (t - a.tree_begin)) * F) * kWave + lane;
+      for (uint32_t f = 0; f < F; ++f) dst[(size_t)f * kWave] = ct[f * kWave];
+    } else {
+      for (uint32_t f = 0; f < F; ++f) tot[f * kWave] += ct[f * kWave];
+    }
+  }
+  if (!SPLIT && valid) {
+    const uint64_t at = fa.out_off + m;
+    for (uint32_t f = 0; f < F; ++f)
+      if (fa.out[f] != nullptr) fa.out[f][at] = tot[f * kWave];
+    if (fa.out[F] != nullptr) fa.out[F][at] = a.bias;
+  }
+  if (any_inf && fa.flags && !is_inf(fa.missing)) atomicOr(fa.flags, 1u);
+}
+
+// The second launch of a split, as contribs_combine_kernel but feature-major: one wave per tile,
+// out[f][out_off + m] = ((0 + part[t0][f]) + part[t0 + 1][f]) + ...
+__global__ __launch_bounds__(kWave) void contribs_fields_combine_kernel(ContribsArgs a, FieldsContribsArgs fa,
+                                                                        const float* __restrict__ part) {
+  const uint32_t lane = threadIdx.x;
+  const uint32_t F = a.nfeat;
+  const uint64_t tile = blockIdx.x;
+  const uint64_t m = tile * kWave + lane;
+  if (m >= fa.nrow) return;
+  const uint32_t ntree = a.tree_end - a.tree_begin;
+  const float* __restrict__ src = part + tile * ntree * F * kWave + lane;
+  const uint64_t at = fa.out_off + m;
+  for (uint32_t f = 0; f < F; ++f) {
+    if (fa.out[f] == nullptr) continue;
+    float acc = 0.0f;
+    for (uint32_t t = 0; t < ntree; ++t) acc += src[((size_t)t * F + f) * kWave];
+    fa.out[f][at] = acc;
+  }
+  if (fa.out[F] != nullptr) fa.out[F][at] = a.bias;
+}
+
+template <bool APPROX>
+hipError_t launch_fields_mode(const ContribsArgs& a, const FieldsContribsArgs& fa, const ContribsPlan& plan,
+                              float* part, hipStream_t stream) {
+  const uint64_t tiles = (fa.nrow + kWave - 1) / kWave;
+  const float4* coef = reinterpret_cast<const float4*>(a.coef);
+  if (plan.split) {
+    const size_t lds = (size_t)2 * a.nfeat * kWave * sizeof(float);
+    const uint64_t items = tiles * plan.groups;
+    hipLaunchKernelGGL((contribs_fields_kernel<APPROX, true>), dim3((unsigned)items), dim3(kWave), lds, stream, a, fa,
+                       (uint64_t)0, plan.trees_per_group, plan.groups, a.heads, a.elems, a.class_start, coef, part);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(contribs_fields_combine_kernel, dim3((unsigned)tiles), dim3(kWave), 0, stream, a, fa,
+                       (const float*)part);
+    return hipGetLastError();
+  }
+  const size_t lds = (size_t)3 * a.nfeat * kWave * sizeof(float);
+  const uint64_t chunk = APPROX ? (1ull << 24) : kDirectTilesPerLaunch;
+  for (uint64_t t = 0; t < tiles; t += chunk) {
+    const uint64_t n = tiles - t < chunk ? tiles - t : chunk;
+    hipLaunchKernelGGL((contribs_fields_kernel<APPROX, false>), dim3((unsigned)n), dim3(kWave), lds, stream, a, fa, t,
+                       0u, 1u, a.heads, a.elems, a.class_start, coef, (float*)nullptr);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+  }
+  return hipSuccess;
+}
+
 template <bool APPROX>
 hipError_t launch_mode(const ContribsArgs& a, const ContribsPlan& plan, float* part, hipStream_t stream) {
   const uint64_t tiles = (a.nrow + kWave - 1) / kWave;
@@ -264,6 +392,14 @@ int launch_contribs(bool approximate, const ContribsArgs& a, const ContribsPlan&
   if (a.nrow == 0) return (int)hipSuccess;
   hipStream_t s = static_cast<hipStream_t>(stream);
   return (int)(approximate ? launch_mode<true>(a, plan, part, s) : launch_mode<false>(a, plan, part, s));
+}
+
+int launch_contribs_fields(bool approximate, const ContribsArgs& a, const FieldsContribsArgs& f,
+                           const ContribsPlan& plan, float* part, void* stream) {
+  if (f.nrow == 0) return (int)hipSuccess;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return (int)(approximate ? launch_fields_mode<true>(a, f, plan, part, s)
+                           : launch_fields_mode<false>(a, f, plan, part, s));
 }
 
 }  // namespace ohx

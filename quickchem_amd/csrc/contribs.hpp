@@ -123,6 +123,30 @@ ContribsPlan plan_contribs(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool a
 // Returns a hipError_t.
 int launch_contribs(bool approximate, const ContribsArgs& a, const ContribsPlan& plan, float* part, void* stream);
 
+// ---- contributions from the fields (contribs.hip; include/ohxgb.h OHXBoosterPredictContribsFields) ----
+//
+// The rows are the slab's gridcells m = i + im * (j + jm * k'), gathered in place as the fields predict does (PL / 100,
+// 2-D fields broadcast over the levels, `missing` -> NaN, fields past nfield missing), into the row tile of the
+// contribs kernels' arithmetic.  Output feature-major: out[f][out_off + m], one array per feature and the bias.
+constexpr uint32_t kMaxFieldsFeatures = 32;
+struct FieldsContribsArgs {
+  const float* field[kMaxFieldsFeatures];      // device; field f is (im,jm) when bit f of is2d_mask is set
+  uint32_t is2d_mask = 0;
+  uint32_t pl_feature = 0xFFFFFFFFu;           // divided by 100 (0xFFFFFFFF: none)
+  uint32_t nfield = 0;
+  float missing = 0.0f;
+  uint64_t plane = 0;                          // im * jm
+  uint64_t nrow = 0;                           // gridcells of the slab
+  uint64_t src_off = 0;                        // floats from a 3-D field's pointer to the slab's first level
+  uint64_t out_off = 0;                        // the same in the outputs
+  float* out[kMaxFieldsFeatures + 1] = {};     // [0, nfeat]: device, nullptr = not stored
+  uint32_t* flags = nullptr;                   // bit 0: +-inf in the slab while `missing` is finite (null: not checked)
+};
+// `a` carries the trees, the bias and the mode's tables (a.rows, a.out unused); plan = plan_contribs(f.nrow, ...).
+// Enqueues on `stream`; returns a hipError_t.
+int launch_contribs_fields(bool approximate, const ContribsArgs& a, const FieldsContribsArgs& f,
+                           const ContribsPlan& plan, float* part, void* stream);
+
 // ---- SHAP interaction values (interactions.hip; include/ohxgb.h OHXBoosterPredictInteractions) ----
 //
 // Exact mode conditions on one feature i at a time: a wave owns one (64-row tile, feature i, tree group) and walks,

@@ -15,7 +15,7 @@ module ohx_bindings
    public :: XGDMatrixCreateFromMat, XGDMatrixFree, XGDMatrixNumRow, XGDMatrixNumCol
    public :: XGBoosterCreate, XGBoosterFree, XGBoosterLoadModel, XGBoosterSaveModel
    public :: XGBoosterPredict, XGBoosterSetParam, OHXBoosterPredictFields, OHXDMatrixSetGrid, OHXBoosterPredictContribs
-   public :: OHXBoosterPredictInteractions
+   public :: OHXBoosterPredictInteractions, OHXBoosterPredictContribsFields, OHXBoosterPredictContribsFieldsDevice
    public :: OHXCommGetUniqueId, OHXCommInitRank, OHXCommFree, OHXCommInfo, OHXShardRows, OHXAllGatherOH, OHX_UNIQUE_ID_BYTES
    public :: ohx_last_error, ohx_c_string
 
@@ -145,6 +145,39 @@ module ohx_bindings
          integer(c_int64_t)         :: out_len
          type(c_ptr)                :: out_result
          integer(c_int)             :: rc
+      end function
+
+      ! Per-feature contributions from the fields (ohxgb.h part 2): fields / is2d / ... as OHXBoosterPredictFields;
+      ! out(f) = c_loc of an (im,jm,km) real(c_float) array for f = 1 .. F + 1 (F + 1 the bias), or c_null_ptr for one
+      ! not wanted.  Levels k1..k2 are written.  Declarations only: nothing the oracle drivers link calls these.
+      function OHXBoosterPredictContribsFields(handle, fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, &
+                                               approximate, ntree_limit, out) &
+            bind(C, name="OHXBoosterPredictContribsFields") result(rc)
+         import :: c_int, c_ptr, c_float, c_int32_t
+         type(c_ptr), value             :: handle
+         type(c_ptr), intent(in)        :: fields(*)
+         integer(c_int32_t), intent(in) :: is2d(*)
+         integer(c_int), value          :: nfield, pl_feature, im, jm, km, k1, k2
+         real(c_float), value           :: missing
+         integer(c_int), value          :: approximate, ntree_limit
+         type(c_ptr), intent(in)        :: out(*)
+         integer(c_int)                 :: rc
+      end function
+
+      ! The same on device addresses, enqueued on `stream` (a hipStream_t; c_null_ptr = the default stream).
+      function OHXBoosterPredictContribsFieldsDevice(handle, d_fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, &
+                                                     missing, approximate, ntree_limit, d_out, stream) &
+            bind(C, name="OHXBoosterPredictContribsFieldsDevice") result(rc)
+         import :: c_int, c_ptr, c_float, c_int32_t
+         type(c_ptr), value             :: handle
+         type(c_ptr), intent(in)        :: d_fields(*)
+         integer(c_int32_t), intent(in) :: is2d(*)
+         integer(c_int), value          :: nfield, pl_feature, im, jm, km, k1, k2
+         real(c_float), value           :: missing
+         integer(c_int), value          :: approximate, ntree_limit
+         type(c_ptr), intent(in)        :: d_out(*)
+         type(c_ptr), value             :: stream
+         integer(c_int)                 :: rc
       end function
 
       ! Optional hint: the DMatrix rows are rows row0.. of the (im,jm,*) gather (ohxgb.h); speed only.
