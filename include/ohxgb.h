@@ -411,6 +411,9 @@ typedef struct OHXRun1Args {
   float *diag_aodup, *diag_aoddn, *diag_aod, *diag_strato3;
 } OHXRun1Args;
 
+/* Levels: 1 <= km <= 640 (the column sums hold one column of km levels per lane in a CU's 160 KiB of LDS); more is
+ * refused before anything is staged or enqueued, with an error that names the limit.  GEOS's L72, L91, L132, L137
+ * and L181 are all within it. */
 int OHXBoosterRun1(BoosterHandle handle, const OHXRun1Args* args);
 int OHXBoosterRun1Device(BoosterHandle handle, const OHXRun1Args* args, void* stream);
 

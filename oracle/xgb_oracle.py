@@ -335,11 +335,10 @@ def predict_OH_with_XGB(model: OracleModel, pl: np.ndarray, tropp: np.ndarray, f
 
 # --------------------------------------------------------------------- OH Run1, either side of the call
 
-def run1(model: OracleModel, st: dict, dynamic_k_range: bool, tropp_min: float = 4000.0, ohscale: float = 0.85,
-         avogad: float = 6.023e26, runiv: float = 8314.47, epsilon: float = 18.015 / 28.965):
-    """OH Run1 from the imports to INTERNAL OH (OH_GridCompMod.F90:1240-1257, 1444-1478, 1488,
-    1557-1595).  `st` maps the names of include/ohxgb.h's OHXRun1Args to [i,j(,k)] float32 arrays.
-    Every SUM is accumulated from zero, ascending in the level index, one float add at a time."""
+def run1_features(st: dict) -> dict:
+    """The feature half of OH Run1 (OH_GridCompMod.F90:1247, 1444-1478, 1488): PL_MOD and the booster's 27 fields in
+    the order of :313-339, plus the engineered ones under the names of OHXRun1Args' DIAG dumps.  Every SUM is
+    accumulated from zero, ascending in the level index, one float add at a time."""
     f32 = np.float32
     km = st["t_mod"].shape[2]
     ple_mod, ple_bst, zle = (np.asarray(st[k], dtype=f32) for k in ("ple_mod", "ple_bst", "zle_bst"))
@@ -370,11 +369,24 @@ def run1(model: OracleModel, st: dict, dynamic_k_range: bool, tropp_min: float =
         return out
 
     tauclw, taucli = np.asarray(st["tauclw"], dtype=f32), np.asarray(st["taucli"], dtype=f32)
+    diag = {"diag_pl_bst": pl_bst, "diag_tauclwdn": sum_dn(tauclw), "diag_tauclidn": sum_dn(taucli),
+            "diag_taucliup": sum_up(taucli), "diag_tauclwup": sum_up(tauclw), "diag_aodup": sum_up(aod),
+            "diag_aoddn": sum_dn(aod), "diag_aod": aod, "diag_strato3": strato3}
     fields = [st["lat_deg"], pl_bst, st["t_bst"], st["no2"], st["o3"], st["ch4"], st["co"], st["isop"], st["acet"],
-              st["c2h6"], st["c3h8"], st["prpe"], st["alk4"], st["mp"], st["h2o2"], sum_dn(tauclw), sum_dn(taucli),
-              sum_up(taucli), sum_up(tauclw), st["cloud"], st["qv"], strato3, st["albuv"], sum_up(aod), sum_dn(aod),
-              st["ch2o"], st["sza"]]                                                        # :313-339
-    fields = [np.asarray(a, dtype=f32) for a in fields]
+              st["c2h6"], st["c3h8"], st["prpe"], st["alk4"], st["mp"], st["h2o2"], diag["diag_tauclwdn"],
+              diag["diag_tauclidn"], diag["diag_taucliup"], diag["diag_tauclwup"], st["cloud"], st["qv"], strato3,
+              st["albuv"], diag["diag_aodup"], diag["diag_aoddn"], st["ch2o"], st["sza"]]           # :313-339
+    return dict(diag, pl_mod=pl_mod, fields=[np.asarray(a, dtype=f32) for a in fields])
+
+
+def run1(model: OracleModel, st: dict, dynamic_k_range: bool, tropp_min: float = 4000.0, ohscale: float = 0.85,
+         avogad: float = 6.023e26, runiv: float = 8314.47, epsilon: float = 18.015 / 28.965):
+    """OH Run1 from the imports to INTERNAL OH (OH_GridCompMod.F90:1240-1257, 1444-1478, 1488,
+    1557-1595).  `st` maps the names of include/ohxgb.h's OHXRun1Args to [i,j(,k)] float32 arrays.
+    The features are run1_features'."""
+    f32 = np.float32
+    feat = run1_features(st)
+    pl_mod, fields = feat["pl_mod"], feat["fields"]
     oh_ml, margin, k1, k2 = predict_OH_with_XGB(model, pl_mod, np.asarray(st["tropp_mod"], dtype=f32), fields,
                                                 dynamic_k_range, tropp_min)
     oh_ml = (oh_ml * f32(ohscale)).astype(f32)                                              # :1569

@@ -2247,8 +2247,15 @@ struct Run1Feed {
 };
 }  // namespace
 
-static void run1_device(BoosterObj& b, const OHXRun1Args& r, hipStream_t stream, Run1Feed* feed = nullptr) {
+// (both forms, before anything is staged or enqueued)
+static void check_run1_shape(const OHXRun1Args& r) {
   if (r.im <= 0 || r.jm <= 0 || r.km <= 0) throw OhxError("OHXBoosterRun1: im, jm, km must be positive");
+  if (r.km > kRun1MaxKm)
+    throw OhxError("OHXBoosterRun1: km = " + std::to_string(r.km) + " levels; the limit is " + std::to_string(kRun1MaxKm));
+}
+
+static void run1_device(BoosterObj& b, const OHXRun1Args& r, hipStream_t stream, Run1Feed* feed = nullptr) {
+  check_run1_shape(r);
   if (b.forest.num_feature != 27) throw OhxError("OHXBoosterRun1 needs the 27-feature OH booster");
   const void* need[] = {r.ple_mod, r.t_mod, r.q_mod, r.tropp_mod, r.ple_bst, r.zle_bst, r.tauclw, r.taucli,
                         r.gmito3, r.gmitto3, r.lat_deg, r.t_bst, r.no2, r.o3, r.ch4, r.co, r.isop, r.acet,
@@ -2637,7 +2644,7 @@ int OHXBoosterRun1(BoosterHandle handle, const OHXRun1Args* args) {
     throw OhxError("objective '" + b->forest.objective + "' is not supported by OHXBoosterRun1");
   ensure_uploaded(*b);
   const OHXRun1Args& h = *args;
-  if (h.im <= 0 || h.jm <= 0 || h.km <= 0) throw OhxError("OHXBoosterRun1: im, jm, km must be positive");
+  check_run1_shape(h);
   const size_t plane = (size_t)h.im * (size_t)h.jm, vol = plane * (size_t)h.km, edge = plane * (size_t)(h.km + 1);
   OHXRun1Args d = h;
   // Every input goes to HBM once, in the order the tick needs it (Run1Feed): stage 0 = what the slab count reads,

@@ -1762,7 +1762,8 @@ __global__ __launch_bounds__(kBlock) void feature_pointwise_kernel(PrepArgs a, f
   }
 }
 
-// blockIdx.y selects the field: 0 TAUCLW, 1 TAUCLI, 2 aod
+// blockIdx.y selects the field: 0 TAUCLW, 1 TAUCLI, 2 aod.  A block is one to four waves (launch_feature_prep: as many
+// as the LDS holds columns of km levels), each with 64 columns of its own
 __global__ __launch_bounds__(kBlock) void feature_column_sums_kernel(PrepArgs a, const float* __restrict__ aod) {
 #pragma clang fp contract(off)
   extern __shared__ float lds[];
@@ -1770,7 +1771,7 @@ __global__ __launch_bounds__(kBlock) void feature_column_sums_kernel(PrepArgs a,
   const int wave = threadIdx.x / kWave;
   const uint64_t plane = (uint64_t)a.im * (uint64_t)a.jm;
   const uint64_t ncols = a.ncols ? a.ncols : plane;
-  const uint64_t col = ((uint64_t)blockIdx.x * kWavesPerBlock + wave) * kWave + lane;
+  const uint64_t col = ((uint64_t)blockIdx.x * (blockDim.x / kWave) + wave) * kWave + lane;
   const bool valid = col < ncols;
   const uint64_t c = a.col0 + (valid ? col : ncols - 1);
   const float* src = blockIdx.y == 0 ? a.tauclw : (blockIdx.y == 1 ? a.taucli : aod);
@@ -2592,7 +2593,7 @@ static dim3 level_grid(uint64_t ncols, int km) {
 hipError_t launch_feature_prep(const PrepArgs& a, float* aod_scratch, hipStream_t stream) {
   const uint64_t plane = (uint64_t)a.im * (uint64_t)a.jm;
   if (plane == 0 || a.km <= 0) return hipSuccess;
-  if (a.col0 + a.ncols > plane || a.km > 65535) return hipErrorInvalidValue;
+  if (a.col0 + a.ncols > plane || a.km > kRun1MaxKm) return hipErrorInvalidValue;
   const uint64_t ncols = a.ncols ? a.ncols : plane;
   hipLaunchKernelGGL(feature_pointwise_kernel, level_grid(ncols, a.km), dim3(kBlock), 0, stream, a, aod_scratch);
   // a rank's block: a wave per column.  Also for a piece whose features are computed beside another piece's walk: the
@@ -2607,13 +2608,17 @@ hipError_t launch_feature_prep(const PrepArgs& a, float* aod_scratch, hipStream_
                        stream, a, (const float*)aod_scratch);
     return hipGetLastError();
   }
-  const size_t lds = (size_t)kWavesPerBlock * a.km * kWave * sizeof(float);
+  // the column in LDS: four waves a block up to 160 levels; above, as many as 160 KiB hold (one from 321 levels on)
+  const size_t wave_lds = (size_t)a.km * kWave * sizeof(float);
+  int waves = kWavesPerBlock;
+  while (waves > 1 && (size_t)waves * wave_lds > 160 * 1024) --waves;
+  const size_t lds = (size_t)waves * wave_lds;
   if (lds > 160 * 1024) return hipErrorInvalidValue;
   hipError_t e = ensure_lds(feature_column_sums_kernel, lds);
   if (e != hipSuccess) return e;
-  const uint64_t cols_per_block = (uint64_t)kWavesPerBlock * kWave;
+  const uint64_t cols_per_block = (uint64_t)waves * kWave;
   hipLaunchKernelGGL(feature_column_sums_kernel, dim3((unsigned)((ncols + cols_per_block - 1) / cols_per_block), 3),
-                     dim3(kBlock), lds, stream, a, (const float*)aod_scratch);
+                     dim3(waves * kWave), lds, stream, a, (const float*)aod_scratch);
   return hipGetLastError();
 }
 

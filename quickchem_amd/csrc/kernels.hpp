@@ -289,6 +289,9 @@ struct SolarArgs {
 };
 hipError_t launch_solar_geometry(const SolarArgs& a, hipStream_t stream);
 
+// The most levels launch_feature_prep takes: a column of the LDS column-sum kernel is km x 64 floats of LDS per wave,
+// and one wave's columns (256 B a level) must fit in a CU's 160 KiB.  OHXBoosterRun1 refuses more (include/ohxgb.h).
+constexpr int kRun1MaxKm = 640;
 hipError_t launch_feature_prep(const PrepArgs& a, float* aod_scratch, hipStream_t stream);  // aod_scratch: (im,jm,km)
 hipError_t launch_k_slab(const SlabArgs& a, hipStream_t stream);
 hipError_t launch_post_process(const PostArgs& a, hipStream_t stream);

@@ -303,6 +303,20 @@ def test_product_shell_on_the_gpu_against_the_reference_child(tmp_path, small_mo
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("km", [137, 181])
+def test_product_shell_on_the_gpu_against_the_reference_child_off_72_levels(tmp_path, small_model, km):
+    """GEOS's L137 and L181 columns: the feature kernels' paths away from 72 levels (the LDS column-sum kernel, at 181
+    levels with fewer waves per block) against the reference's own SUMs, on a small block over four hourly ticks with a
+    dynamic k range - two Boost ticks.  The tolerances of the other shell cases."""
+    kw = dict(grid=(6, 5, km), source="ONLINE_INST", nticks=4, seed=11, once_per_day=False, spinup=False, run_dt=1800,
+              oh_dt=3600, avg24_tick=-1, ohscale=1.0, ref_time="000000", beg="20240131 220000")
+    out, *_ = run_both(tmp_path, small_model, REF_ORACLE, tg.DRIVER_HIP, **kw)
+    (ref, _), (prod, _) = out["reference"], out["product"]
+    assert compare(ref, prod, tolerance=POW10) == 2
+    assert ref[-1]["OH"]["DIAG_TAUCLWDN"].shape[2] == km and ref[-1]["OH"]["DIAG_AODUP"].max() > 0
+
+
+@pytest.mark.gpu
 def test_reference_child_and_product_shell_on_a_block_the_ring_kernels_take(tmp_path, deep_model):
     """The same comparison at a size where the big-batch kernels do the work: a 96 x 72 x 72 block (497 664 gridcells; the
     slab ~350 000 rows), the OH booster's shape (100 trees of depth 18).  The reference's child reaches the MI355X through
