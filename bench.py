@@ -11,15 +11,21 @@ every GPU — that is part of the step.
 
 Prints ONE JSON line (rank 0).  `roofline` prices the predict kernel against the
 HBM roofline with the ALGORITHMIC bytes of SURVEY.md §8(d): 112 B per gridcell plus
-the node bytes once per step.  `cpu_baseline` is the reference's CPU path as far as it
-can be had here ("port"): the Fortran host (predict_OH_with_XGB: SoA->AoS gather,
-XGDMatrixCreateFromMat, XGBoosterPredict, 10**pred; OH_GridCompMod.F90:308-374)
-linked against the CPU oracle, timed on this node's host cores at one thread (how a
-GEOS rank runs it) and at all of them, on the first levels of the same batch.
+the node bytes once per step.
 
-After the timed steps every rank predicts its rows once more with a kernel of different
-design (`wide` nodes, no LDS tile, no grid hint: 64 consecutive rows per wave) and
-compares bit for bit: `config.verified`.
+A plain run does what the headline needs and no more: it sets up, warms up, times the
+steps, writes --dump-outputs and prints the line.  Everything else runs with --full:
+
+- `config.verified`: after the timed steps every rank predicts its rows once more with a
+  kernel of different design (`wide` nodes, no LDS tile, no grid hint: 64 consecutive
+  rows per wave) and compares bit for bit (also with --verify alone).
+- `cpu_baseline`: the reference's CPU path as far as it can be had here ("port"): the
+  Fortran host (predict_OH_with_XGB: SoA->AoS gather, XGDMatrixCreateFromMat,
+  XGBoosterPredict, 10**pred; OH_GridCompMod.F90:308-374) linked against the CPU
+  oracle, timed on this node's host cores at one thread (how a GEOS rank runs it) and
+  at all of them, on the first levels of the same batch; with it the timed margins are
+  compared with the oracle, bit for bit.
+- `pcie_inclusive`, `run1_host` and `rank_ticks`: the host-memory and GEOS-rank figures.
 """
 from __future__ import annotations
 
@@ -55,19 +61,24 @@ def parse_args():
     ap.add_argument("--param", action="append", default=[], help="extra XGBoosterSetParam name=value (repeatable)")
     ap.add_argument("--missing-ppm", type=int, default=0, help="inject -999.0/NaN at this rate per million entries")
     ap.add_argument("--cpu-seconds", type=float, default=15.0,
-                    help="cpu_baseline leg: 0 = skip, < 10 = a one-level sample, else the fixed sample (8 levels, 3 ticks)")
-    ap.add_argument("--no-pcie", action="store_true", help="skip the pcie_inclusive measurement (host-pointer entry points)")
+                    help="--full: the cpu_baseline leg: 0 = skip, < 10 = a one-level sample, else the fixed sample (8 levels, 3 ticks)")
+    ap.add_argument("--no-pcie", action="store_true", help="--full: skip the pcie_inclusive and run1_host measurements (host-pointer entry points)")
     ap.add_argument("--no-full-oracle", action="store_true",
-                    help="skip the comparison of EVERY timed margin with the CPU oracle (the first 2^20 rows and 2^20 drawn rows stay)")
+                    help="--full: skip the comparison of EVERY timed margin with the CPU oracle (the first 2^20 rows and 2^20 drawn rows stay)")
     ap.add_argument("--no-rank-ticks", action="store_true",
-                    help="skip the GEOS-rank tick measurement (the shell's Boost tick and skip tick as child processes)")
+                    help="--full: skip the GEOS-rank tick measurement (the shell's Boost tick and skip tick as child processes)")
     ap.add_argument("--shuffle", action="store_true", help="permute the rows (destroys spatial coherence)")
     ap.add_argument("--infer-grid", action="store_true",
                     help="rows path: no hint either, but let the library look for the level size in the rows "
                          "(OHXDMatrixInferGrid), as XGDMatrixCreateFromMat does unasked for host matrices")
-    ap.add_argument("--verify", action="store_true", help="(default; kept for older command lines)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run what a plain run leaves out: the cross-check against the `wide` "
+                         "kernel (config.verified), the CPU baseline and the oracle comparisons (cpu_baseline), "
+                         "pcie_inclusive, run1_host and rank_ticks")
+    ap.add_argument("--verify", action="store_true",
+                    help="the whole-batch cross-check against the `wide` kernel after the timed steps, without --full")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the whole-batch cross-check against the `wide` kernel after the timed steps")
+                    help="--full: skip the whole-batch cross-check against the `wide` kernel after the timed steps")
     ap.add_argument("--no-grid", action="store_true",
                     help="rows path: say nothing about the rows (no OHXDMatrixSetGrid, no OHXDMatrixInferGrid): what a "
                          "device-resident caller gets who knows nothing of the extensions; the first predict looks "
@@ -100,7 +111,7 @@ def parse_args():
                          "run1 -> oh, oh_boost (float32) and k_slab (float64).  At most 64 MB in all: a larger array is cut to a fixed "
                          "seeded sample of its elements (dump_index), in index order")
     args = ap.parse_args()
-    args.verify = not args.no_verify
+    args.verify = (args.full or args.verify) and not args.no_verify
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.path != "rows" and args.gpus != 1:
@@ -747,9 +758,9 @@ def main():
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world} (start `python bench.py --gpus N` plainly, or under "
                          f"python -m torch.distributed.run --nproc-per-node N)")
-    # the GEOS-rank ticks run as child processes and must be over before this process opens the GPU
+    # (--full) the GEOS-rank ticks run as child processes and must be over before this process opens the GPU
     shell_ticks = None
-    if (world == 1 and args.path == "rows" and not args.no_rank_ticks and not args.no_pcie and args.cpu_seconds > 0
+    if (args.full and world == 1 and args.path == "rows" and not args.no_rank_ticks and not args.no_pcie and args.cpu_seconds > 0
             and not args.shuffle and not args.missing_ppm and not args.rows and not args.param
             and (args.trees, args.depth, args.grid) == (100, 18, "C360")):
         shell_ticks = rank_ticks()
@@ -929,7 +940,7 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # ---- parity of the timed output, on every rank: the same rows through a kernel of different design ----
+    # ---- (--full) parity of the timed output, on every rank: the same rows through a kernel of different design ----
     verified = None
     if args.verify:
         other = capi.Booster(model_buffer=model.image)
@@ -983,11 +994,11 @@ def main():
     algo_bytes = BYTES_PER_CELL * n_local + info["node_bytes"]
     achieved = algo_bytes / kernel_s / 1e9
 
-    # ---- CPU baseline (rank 0, N = 1): Fortran host + oracle on the first levels of the same batch; it also
+    # ---- (--full) CPU baseline (rank 0, N = 1): Fortran host + oracle on the first levels of the same batch; it also
     #      checks the timed GPU output against the checker (10**margin within 2 ulp) ----
     cpu = None
     plain = (not args.shuffle and not args.missing_ppm and args.trees == 100 and args.depth == 18)
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and plain:
+    if args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and plain:
         cpu = cpu_baseline(model.image, grid, booster, out_local, args.cpu_seconds)
         # and bit for bit on the raw margins, oracle through ctypes, first 2**20 rows
         lib = capi.declare_xgb_api(C.CDLL(os.path.join(ROOT, "oracle", "lib", "liboracle_xgb.so")))
@@ -1027,7 +1038,7 @@ def main():
             cpu["whole_batch_oracle_s"] = round(time.perf_counter() - t_full, 2)
 
     pcie = host_tick = None
-    if rank == 0 and world == 1 and plain and not args.no_pcie and args.cpu_seconds > 0 and use_grid:
+    if args.full and rank == 0 and world == 1 and plain and not args.no_pcie and args.cpu_seconds > 0 and use_grid:
         pcie = pcie_inclusive(grid, booster, dev)
         host_tick = run1_host(booster)
     if rank == 0:

@@ -216,7 +216,7 @@ def test_two_ranks_share_the_gpu_and_agree_with_one(tmp_path):
     for extra in ([], ["--gather-chunks", "1"]):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"),
                             "--gpus", "2", "--grid", "C90", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
-                            "--verify"] + extra, capture_output=True, text=True, env=plain, timeout=900, cwd=root)
+                            "--full"] + extra, capture_output=True, text=True, env=plain, timeout=900, cwd=root)
         assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
         assert len([ln for ln in r.stdout.splitlines() if ln.startswith("{")]) == 1
         line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -236,7 +236,7 @@ def test_two_ranks_share_the_gpu_and_agree_with_one(tmp_path):
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                             "--master-addr", "127.0.0.1", "--master-port", "29578", os.path.join(root, "bench.py"),
                             "--gpus", "2", "--grid", "C48", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
-                            "--verify"] + extra, capture_output=True, text=True, env=env, timeout=900, cwd=root)
+                            "--full"] + extra, capture_output=True, text=True, env=env, timeout=900, cwd=root)
         assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
         line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
         assert line["config"]["verified"] is True and line["n_gpus"] == 2
@@ -258,7 +258,7 @@ def test_bench_over_rccl_with_one_rank():
     env = dict(os.environ, OHX_BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT="29581")
     for gather in ("both", "torch", "native", "none"):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--grid", "C90", "--steps", "2",
-                            "--warmup", "1", "--cpu-seconds", "0", "--gather", gather, "--gather-gbps", "60"],
+                            "--warmup", "1", "--cpu-seconds", "0", "--full", "--gather", gather, "--gather-gbps", "60"],
                            capture_output=True, text=True, env=env, timeout=900, cwd=root)
         assert r.returncode == 0, (gather, r.stdout[-1500:], r.stderr[-3000:])
         line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -228,6 +228,23 @@ def test_bench_reads_the_cpu_share_a_cgroup_grants(tmp_path):
     assert bench.cpu_quota(tree({})) is None
 
 
+def test_bench_leaves_all_but_the_headline_to_full(monkeypatch):
+    """A plain `bench.py --gpus 1 --steps N --warmup W` times the steps and prints the line; the cross-check against the
+    `wide` kernel (and the CPU baseline, pcie_inclusive, run1_host, rank_ticks, all gated on args.full) run with --full.
+    --verify asks for the cross-check alone, --no-verify leaves it out of --full."""
+    import sys
+    import bench
+
+    def parsed(*argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1", *argv])
+        return bench.parse_args()
+    plain = parsed()
+    assert (plain.full, plain.verify, plain.steps, plain.warmup) == (False, False, 3, 1)
+    assert (parsed("--full").full, parsed("--full").verify) == (True, True)
+    assert parsed("--full", "--no-verify").verify is False
+    assert (parsed("--verify").full, parsed("--verify").verify) == (False, True)
+
+
 def test_rank_tick_tool_sorts_ticks_into_boost_and_skip():
     """(r6) tools/rank_tick_end_to_end.py: the driver's TICK_US lines -> (tick, us, nhms); quantiles of a list."""
     import sys

@@ -8,7 +8,7 @@ rm -rf /tmp/st && mkdir -p /tmp/st && cp -r bench.py BASELINE.json quickchem_amd
 cp tools/bin/variants/sticky/*.so /tmp/st/quickchem_amd/lib/ || exit 1
 (cd /tmp/st && timeout -k 10 600 python -m pytest tests/test_random_forests.py tests/test_gpu_parity.py -m gpu -x -q > $O/tests.log 2>&1) || { tail -30 $O/tests.log; exit 1; }
 tail -3 $O/tests.log
-(cd /tmp/st && timeout -k 10 400 python bench.py --steps 5 --warmup 2 --no-pcie --no-rank-ticks --cpu-seconds 3 > $O/bench_verified.json 2> $O/bench_verified.err) || { tail -20 $O/bench_verified.err; exit 1; }
+(cd /tmp/st && timeout -k 10 400 python bench.py --full --steps 5 --warmup 2 --no-pcie --no-rank-ticks --cpu-seconds 3 > $O/bench_verified.json 2> $O/bench_verified.err) || { tail -20 $O/bench_verified.err; exit 1; }
 python - <<PY
 import json
 d = json.loads([l for l in open("$O/bench_verified.json") if l.startswith('{"metric"')][0])

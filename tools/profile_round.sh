@@ -1,7 +1,7 @@
 #!/bin/bash
 # usage: tools/profile_round.sh <round tag>   (run on the GPU box through gpurun)
 # Produces, under gpurun_out/profile_<tag>/, what profiles/ keeps for the round:
-#   kernel_stats.csv        rocprofv3 --kernel-trace --stats of the default `python3 bench.py`
+#   kernel_stats.csv        rocprofv3 --kernel-trace --stats of `python3 bench.py --full`
 #   bench.json              the JSON line of that same command;  bench_plain.json the same without the profiler
 #   pmc_summary.txt         per-step means of the predict kernel's counters (separate --pmc passes, tools/pmc.sh)
 #   calib_fetch_write.txt   FETCH_SIZE calibration on an almost pure streaming run (1 tree of depth 0)
@@ -12,10 +12,10 @@
 tag=$1
 cd /tmp && export TMPDIR=/tmp && R=$GRAFT_REPO_ROOT && O=$R/gpurun_out/profile_$tag && mkdir -p $O && cd $R
 if [ "${PHASE:-1}" = "1" ]; then
-timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py > $O/bench_under_rocprof.log 2>&1
+timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace -- python3 bench.py --full > $O/bench_under_rocprof.log 2>&1
 grep "^{\"metric\"" $O/bench_under_rocprof.log | tail -1 > $O/bench.json
 cp $O/trace/*/*_kernel_stats.csv $O/kernel_stats.csv 2>/dev/null
-timeout -k 10 600 python3 bench.py > $O/bench_plain.log 2>&1
+timeout -k 10 600 python3 bench.py --full > $O/bench_plain.log 2>&1
 grep "^{\"metric\"" $O/bench_plain.log | tail -1 > $O/bench_plain.json
 # the same with nothing but the timed region launching the walk kernel (no pcie_inclusive leg, no CPU leg)
 timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/trace2 -- python3 bench.py --no-pcie --cpu-seconds 0 > $O/bench_under_rocprof_timed_only.log 2>&1
@@ -46,7 +46,7 @@ PY
 python3 tools/make_traffic_json.py $O/pmc_summary.txt $O/calib_fetch_write.txt $O/bench_plain.json > $O/traffic.json
 # the default line once more, now that the measurement of these very kernels exists: it carries roofline.traffic
 cp $O/traffic.json profiles/${tag}_traffic.json
-timeout -k 10 600 python3 bench.py > $O/bench_plain.log 2>&1
+timeout -k 10 600 python3 bench.py --full > $O/bench_plain.log 2>&1
 grep "^{\"metric\"" $O/bench_plain.log | tail -1 > $O/bench_plain.json
 fi
 rm -rf $O/trace $O/trace2 $O/calib_FETCH_SIZE $O/calib_WRITE_SIZE
