@@ -88,7 +88,28 @@ int XGBoosterLoadModelFromBuffer(BoosterHandle handle, const void* buf, bst_ulon
  *   ntree_limit: 0 = all trees.
  * *out_result points at a host buffer owned by the booster, valid until the
  * next predict on that booster or XGBoosterFree (the reference never frees
- * it, :362,381).  *out_len = nrow (asserted at :359). */
+ * it, :362,381).  *out_len = nrow (asserted at :359).
+ *
+ * Boosters with several output groups (G = max(num_class, num_target) >= 2:
+ * multi:softprob, multi:softmax, 1.6.0's multi-target regression;
+ * OHXBoosterGetNumGroups), as xgboost 1.6.0 lays them out, row-major:
+ *   option_mask 1                         [nrow][G] margins
+ *   option_mask 0, identity objective     [nrow][G] margins
+ *   option_mask 0, multi:softprob         [nrow][G] softmax of the row's margins
+ *   option_mask 0, multi:softmax          [nrow]    index of the row's first maximal margin, as float
+ *   option_mask 0, any other objective    refused, as for one group
+ *   option_mask 16                        [nrow][L] leaf ids, trees in FILE order
+ * Group g's margin is the base margin plus the leaves of the trees with
+ * tree_info == g, added in file order; a group without trees has the base
+ * margin.  ntree_limit = k > 0 means the first k rounds: file trees
+ * [0, L = min(T, k * G)) (1.6.0's GetIterationFromTreeLimit, num_parallel_tree
+ * 1; unpinned against libxgboost, as everything here).  *out_len = nrow * G
+ * (nrow for multi:softmax, nrow * L for leaf ids).  Fortran callers: size the
+ * c_f_pointer of out_result by out_len, not by the number of rows.
+ * OHXBoosterPredictDevice writes the same into d_out (sized accordingly) and
+ * is not capturable for such a booster: -1 inside a stream capture, nothing
+ * enqueued.  The fields forms, OHXBoosterPredictContribsFields[Device] and
+ * OHXBoosterRun1[Device] are single-output and refuse such a booster. */
 int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, unsigned ntree_limit, int training,
                      bst_ulong* out_len, const float** out_result);
 
@@ -259,6 +280,9 @@ int OHXBoosterCheck(BoosterHandle handle, void* stream);
  * enqueues on `stream`.  +-inf in the rows is reported by the host form only: there, as in predict, +-inf in ANY of a
  * row's columns is an error unless `missing` is itself infinite, in both modes (not only in the columns the row's
  * paths split on). */
+/* Several output groups (G >= 2, XGBoosterPredict): [nrow][G][F+1], each group's block computed over the group's
+ * trees (ntree_limit as in XGBoosterPredict), its bias the base margin plus the group's trees' root means in file
+ * order; *out_len = nrow * G * (F+1), and the device form's d_out holds as many floats. */
 int OHXBoosterPredictContribs(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
                               bst_ulong* out_len, const float** out_result);
 int OHXBoosterPredictContribsDevice(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
@@ -294,6 +318,7 @@ int OHXBoosterPredictContribsDevice(BoosterHandle handle, DMatrixHandle dmat, in
  * state's but none a contribs call uses, and never one of the predict, fields or Run1 paths; dropped with the model
  * and at XGBoosterFree, rebuilt after an "ohx_device" move.  Exact mode costs about (path length) times what exact
  * contributions cost per row: it is for subsets of rows.  The device form only enqueues on `stream`. */
+/* Several output groups: [nrow][G][F+1][F+1], each group's block as OHXBoosterPredictContribs's. */
 int OHXBoosterPredictInteractions(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
                                   bst_ulong* out_len, const float** out_result);
 int OHXBoosterPredictInteractionsDevice(BoosterHandle handle, DMatrixHandle dmat, int approximate, unsigned ntree_limit,
@@ -448,6 +473,10 @@ int OHXSolarGeometryDevice(int jday, const float* d_lats, const float* d_lons, i
  * [4] max depth, [5] features, [6] node format in use (0 wide, 1 packed, 2 super-nodes),
  * [7] vector-memory instructions one wavefront issues to walk the whole forest once (super-nodes). */
 int OHXBoosterGetInfo(BoosterHandle handle, bst_ulong info[8]);
+/* Output groups of the loaded model: xgboost 1.6.0's num_output_group, max(num_class, num_target, 1).  1 for the OH
+ * booster; G >= 2 changes the shapes XGBoosterPredict, OHXBoosterPredictContribs and OHXBoosterPredictInteractions
+ * return (their comments).  -1 when the booster holds no model. */
+int OHXBoosterGetNumGroups(BoosterHandle handle, bst_ulong* out);
 /* Name of the GPU kernel XGBoosterPredict / OHXBoosterPredictDevice launch for rows of `ncol` columns with the
  * booster's current parameters, as a profiler prints it (without namespaces and arguments), e.g.
  * "predict_rows_tile_kernel<2,2,true,true>".  *out stays valid until the next call on this handle. */

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "OHXBoosterPredictInteractions", "OHXBoosterPredictInteractionsDevice",
     "OHXBoosterPredictContribsFields", "OHXBoosterPredictContribsFieldsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
-    "OHXJulianDay", "OHXSolarGeometry", "OHXSolarGeometryDevice", "OHXBoosterGetInfo", "OHXBoosterKernelSymbol", "OHXBoosterKernelSymbolRows",
+    "OHXJulianDay", "OHXSolarGeometry", "OHXSolarGeometryDevice", "OHXBoosterGetInfo", "OHXBoosterGetNumGroups", "OHXBoosterKernelSymbol", "OHXBoosterKernelSymbolRows",
     "OHXBoosterRingReruns", "OHXBoosterCopyEngineChoice", "OHXUnregisterHost", "OHXReleaseScratch",
     "OHXCommGetUniqueId", "OHXCommInitRank", "OHXCommFree", "OHXCommInfo", "OHXShardRows", "OHXAllGatherOH",
 ]
@@ -132,6 +132,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.OHXSolarGeometry.argtypes = [i32, vp, vp, i32, i32, f32, f32, vp, vp]
     lib.OHXSolarGeometryDevice.argtypes = [i32, vp, vp, i32, i32, f32, f32, vp, vp, vp]
     lib.OHXBoosterGetInfo.argtypes = [vp, C.POINTER(u64)]
+    lib.OHXBoosterGetNumGroups.argtypes = [vp, C.POINTER(u64)]
     lib.OHXBoosterKernelSymbol.argtypes = [vp, u64, C.POINTER(C.c_char_p)]
     lib.OHXBoosterKernelSymbolRows.argtypes = [vp, vp, C.POINTER(C.c_char_p)]
     lib.OHXBoosterRingReruns.argtypes = [vp, vp, C.POINTER(u64)]
@@ -282,10 +283,23 @@ class Booster:
     def set_param(self, name: str, value) -> None:
         check(self.lib, self.lib.XGBoosterSetParam(self.handle, name.encode(), str(value).encode()))
 
+    @property
+    def num_groups(self) -> int:
+        """Output groups of the loaded model (OHXBoosterGetNumGroups): max(num_class, num_target, 1)."""
+        out = C.c_uint64()
+        check(self.lib, self.lib.OHXBoosterGetNumGroups(self.handle, C.byref(out)))
+        return int(out.value)
+
+    def _groups(self) -> int:
+        # a library that only serves single-group boosters (the CPU oracle) has no OHXBoosterGetNumGroups
+        return self.num_groups if hasattr(self.lib, "OHXBoosterGetNumGroups") else 1
+
     def predict(self, dmat: DMatrix, option_mask: int = 0, ntree_limit: int = 0, training: int = 0,
                 copy: bool = True) -> np.ndarray:
         """Host result, float32: a copy of the booster-owned buffer, or (copy=False) a view of it that is valid until
-        the booster's next predict - what the reference's Fortran reads through its c_f_pointer (OH_GridCompMod.F90:362)."""
+        the booster's next predict - what the reference's Fortran reads through its c_f_pointer (OH_GridCompMod.F90:362).
+        One output group: 1-D, as ever.  Several (num_groups >= 2): (nrow, G) margins or probabilities, (nrow, L) leaf
+        ids in file tree order, and 1-D (nrow,) class indices for multi:softmax (include/ohxgb.h)."""
         n = C.c_uint64()
         ptr = C.POINTER(C.c_float)()
         check(self.lib, self.lib.XGBoosterPredict(self.handle, dmat.handle, option_mask, ntree_limit, training,
@@ -293,6 +307,9 @@ class Booster:
         if n.value == 0:
             return np.empty(0, dtype=np.float32)
         view = np.ctypeslib.as_array(ptr, shape=(n.value,))
+        nrow = dmat.num_row
+        if nrow and (n.value != nrow or option_mask == 16) and self._groups() >= 2:
+            view = view.reshape(nrow, n.value // nrow)
         return view.copy() if copy else view
 
     def predict_device(self, dmat: DMatrix, out_ptr: int, option_mask: int = 0, ntree_limit: int = 0,
@@ -305,7 +322,7 @@ class Booster:
 
     def predict_contribs(self, dmat: DMatrix, approximate: bool = False, ntree_limit: int = 0) -> np.ndarray:
         """Per-feature contributions, (nrow, F + 1) float32, column F the bias (OHXBoosterPredictContribs): exact
-        TreeSHAP, or xgboost's approximate attribution with approximate=True."""
+        TreeSHAP, or xgboost's approximate attribution with approximate=True.  Several output groups: (nrow, G, F + 1)."""
         n = C.c_uint64()
         ptr = C.POINTER(C.c_float)()
         check(self.lib, self.lib.OHXBoosterPredictContribs(self.handle, dmat.handle, int(bool(approximate)), ntree_limit,
@@ -313,7 +330,9 @@ class Booster:
         nrow = dmat.num_row
         if n.value == 0:
             return np.empty((nrow, 0), dtype=np.float32)
-        return np.ctypeslib.as_array(ptr, shape=(n.value,)).reshape(nrow, n.value // nrow).copy()
+        G = self._groups()
+        out = np.ctypeslib.as_array(ptr, shape=(n.value,)).reshape(nrow, n.value // nrow).copy()
+        return out.reshape(nrow, G, n.value // nrow // G) if G >= 2 else out
 
     def predict_contribs_device(self, dmat: DMatrix, out_ptr: int, approximate: bool = False, ntree_limit: int = 0,
                                 stream: int = 0) -> None:
@@ -323,7 +342,8 @@ class Booster:
 
     def predict_interactions(self, dmat: DMatrix, approximate: bool = False, ntree_limit: int = 0) -> np.ndarray:
         """SHAP interaction values, (nrow, F + 1, F + 1) float32, index F the bias (OHXBoosterPredictInteractions):
-        exact, or with approximate=True the approximate contributions on the diagonal."""
+        exact, or with approximate=True the approximate contributions on the diagonal.  Several output groups:
+        (nrow, G, F + 1, F + 1)."""
         n = C.c_uint64()
         ptr = C.POINTER(C.c_float)()
         check(self.lib, self.lib.OHXBoosterPredictInteractions(self.handle, dmat.handle, int(bool(approximate)),
@@ -331,8 +351,10 @@ class Booster:
         nrow = dmat.num_row
         if n.value == 0:
             return np.empty((nrow, 0, 0), dtype=np.float32)
-        side = int(round((n.value // nrow) ** 0.5))
-        return np.ctypeslib.as_array(ptr, shape=(n.value,)).reshape(nrow, side, side).copy()
+        G = self._groups()
+        side = int(round((n.value // nrow // G) ** 0.5))
+        out = np.ctypeslib.as_array(ptr, shape=(n.value,))
+        return (out.reshape(nrow, G, side, side) if G >= 2 else out.reshape(nrow, side, side)).copy()
 
     def predict_interactions_device(self, dmat: DMatrix, out_ptr: int, approximate: bool = False,
                                     ntree_limit: int = 0, stream: int = 0) -> None:

@@ -27,6 +27,7 @@
 #include "contribs.hpp"
 #include "flatten.hpp"
 #include "forest.hpp"
+#include "groups.hpp"
 #include "kernels.hpp"
 
 using namespace ohx;
@@ -565,8 +566,10 @@ struct ContribsState {
   // requested outputs, one slab of gridcells each (its split launches use d_part above)
   std::vector<DevBuf<float>> d_fstage;
   DevBuf<float> d_fout;
+  // several output groups: one group's block, [nrow][F+1] or [nrow][F+1][F+1], before it is scattered into the output
+  DevBuf<float> d_gblock;
   void release_device() {
-    for (DevBuf<float>* f : {&d_coef, &d_out, &d_part, &d_iphi, &d_ipart, &d_iout, &d_fout}) f->release();
+    for (DevBuf<float>* f : {&d_coef, &d_out, &d_part, &d_iphi, &d_ipart, &d_iout, &d_fout, &d_gblock}) f->release();
     d_fstage.clear();
     d_fpaths.release();
     d_fstart.release();
@@ -596,7 +599,16 @@ struct BoosterObj {
     if (defer_seen) (void)hipEventDestroy(defer_seen);
   }
   TrainStreams train;              // second stream of the launch train (kernels.hpp): made when ohx_overlap_group asks for it
-  Forest forest;
+  Forest forest;                   // file order: what XGBoosterSaveModel writes
+  // Several output groups (Forest::num_groups() >= 2, multi-class / multi-target): every device form is built from
+  // `grouped`, the same trees ordered group by group (flatten.hpp group_major), so that group g is the tree range
+  // [group_begin[g], group_begin[g+1]) of every walk and every contributions table.  A single-group booster has no copy:
+  // flat() is `forest` itself, and its device forms are what they always were.
+  uint32_t num_groups = 1;
+  Forest grouped;
+  std::vector<uint32_t> group_begin;     // G + 1 entries
+  std::vector<uint32_t> flat_file_index; // file position of each tree of `grouped`
+  const Forest& flat() const { return num_groups >= 2 ? grouped : forest; }
   bool loaded = false;
   float margin_base = 0.0f;        // Forest::margin_base() of the loaded model
   std::string margin_error;        // why it is unknown (objective this library cannot start a margin for)
@@ -633,6 +645,11 @@ struct BoosterObj {
   bool defer_too_many = false;
   DevBuf<float> d_pred;
   PinnedBuf<float> h_pred;
+  // several output groups: the [G][nrow] margin planes the walks write and group_finish reads, and the [nrow][T] leaf
+  // ids of a walk of all trees in group-major order with the map that puts them back in file order - buffers of the
+  // booster's own, never a fields or Run1 one
+  DevBuf<float> d_planes, d_gleaf;
+  DevBuf<uint32_t> d_flat_of_file;
   // the library's two streams on the booster's device (lib_streams; not the booster's to destroy).  Host forms of the
   // fused calls: PCIe copies on s_copy beside the kernels on s_exec.  OH Run1's device form: the slab count, and the
   // streaming kernels of the pieces that are not being walked, on s_copy beside the caller's stream
@@ -769,11 +786,12 @@ void invalidate_device_state(BoosterObj& b) {
   b.d_super_heads.release();
   b.super_ok = false;
   b.d_roots.release();
+  b.d_flat_of_file.release();
 }
 
 void ensure_wide(BoosterObj& b) {
   if (b.d_wide.p) return;
-  std::vector<WideNode> wide = emit_wide(b.forest, b.placement);
+  std::vector<WideNode> wide = emit_wide(b.flat(), b.placement);
   b.d_wide.upload(wide);
 }
 
@@ -786,12 +804,13 @@ void ensure_uploaded(BoosterObj& b) {
     return;
   }
   b.dev = use_device(b.device_pref);
-  b.placement = place_forest(b.forest, b.layout);
-  b.packed_ok = packed_format_fits(b.forest, b.placement);
+  const Forest& flat = b.flat();
+  b.placement = place_forest(flat, b.layout);
+  b.packed_ok = packed_format_fits(flat, b.placement);
   b.d_roots.upload(b.placement.roots);
   if (wants_super(b.kernel_name)) {
     SuperForest sf;
-    b.super_ok = emit_super(b.forest, &sf) && sf.nodes.size() * sizeof(SuperNode) < 0xFFFFFFF0ull;
+    b.super_ok = emit_super(flat, &sf) && sf.nodes.size() * sizeof(SuperNode) < 0xFFFFFFF0ull;
     if (b.super_ok) {
       b.super_slots = sf.nodes.size();
       b.super_gathers[0] = count_super_gathers(sf, 0);
@@ -803,7 +822,7 @@ void ensure_uploaded(BoosterObj& b) {
     }
   }
   if (b.packed_ok && !(b.super_ok && wants_super(b.kernel_name))) {
-    std::vector<PackedNode> packed = emit_packed(b.forest, b.placement, nullptr);
+    std::vector<PackedNode> packed = emit_packed(flat, b.placement, nullptr);
     b.d_packed.upload(packed);
   }
   if (pick_kernel(b) == KernelKind::Wide) ensure_wide(b);
@@ -855,10 +874,18 @@ void tree_range(const BoosterObj& b, unsigned ntree_limit, uint32_t* t0, uint32_
   *t1 = (ntree_limit == 0 || ntree_limit > T) ? T : ntree_limit;
 }
 
-void check_predict_options(const BoosterObj& b, int option_mask, bool* pred_leaf) {
+// `finish`: what group_finish makes of the margins of a booster with several output groups (groups.hpp)
+void check_predict_options(const BoosterObj& b, int option_mask, bool* pred_leaf, int* finish = nullptr) {
   *pred_leaf = false;
+  if (finish) *finish = kGroupMargins;
   if (option_mask == 0 || option_mask == 1) {
     if (!b.margin_error.empty()) throw OhxError(b.margin_error);
+    // the two multi-class transforms, for boosters of several output groups (a single group keeps the refusal below)
+    if (option_mask == 0 && finish && b.num_groups >= 2 &&
+        (b.forest.objective == "multi:softprob" || b.forest.objective == "multi:softmax")) {
+      *finish = b.forest.objective == "multi:softprob" ? kGroupSoftprob : kGroupArgmax;
+      return;
+    }
     if (option_mask == 0 && !objective_is_identity(b.forest.objective))
       throw OhxError("objective '" + b.forest.objective +
                      "' needs a prediction transform this library does not implement; "
@@ -871,6 +898,33 @@ void check_predict_options(const BoosterObj& b, int option_mask, bool* pred_leaf
   }
   throw OhxError("XGBoosterPredict: option_mask " + std::to_string(option_mask) +
                  " is not supported (0 = value, 1 = margin, 16 = leaf index)");
+}
+
+// Several output groups.  ntree_limit = k > 0 means the first k rounds: file trees [0, min(T, k * G)) (xgboost 1.6.0's
+// GetIterationFromTreeLimit with num_parallel_tree = 1); 0 means all trees.
+uint32_t group_tree_limit(const BoosterObj& b, unsigned ntree_limit) {
+  const uint64_t T = b.forest.trees.size(), want = (uint64_t)ntree_limit * b.num_groups;
+  return (uint32_t)((ntree_limit == 0 || want > T) ? T : want);
+}
+// ... and each group's share of file trees [0, L): a prefix of the group's range in the group-major copy, whose trees
+// keep their file order
+std::vector<uint32_t> group_tree_counts(const BoosterObj& b, uint32_t L) {
+  std::vector<uint32_t> n(b.num_groups, 0u);
+  for (uint32_t t = 0; t < L; ++t) ++n[(size_t)b.forest.tree_info[t]];
+  return n;
+}
+// floats XGBoosterPredict returns for a booster of several output groups
+size_t group_predict_len(const BoosterObj& b, uint64_t nrow, int option_mask, unsigned ntree_limit) {
+  if (option_mask == 16) return (size_t)nrow * group_tree_limit(b, ntree_limit);
+  if (option_mask == 0 && b.forest.objective == "multi:softmax") return (size_t)nrow;
+  return (size_t)nrow * b.num_groups;
+}
+// The OH shell's forms (fields, contributions from the fields, Run1) are single-output
+void refuse_groups(const BoosterObj& b, const char* what) {
+  if (b.loaded && b.num_groups >= 2)
+    throw OhxError(std::string(what) + " is single-output: this booster has " + std::to_string(b.num_groups) +
+                   " output groups (multi-class or multi-target); predict it through XGBoosterPredict or "
+                   "OHXBoosterPredictDevice");
 }
 
 void check_columns(const BoosterObj& b, uint64_t ncol) {
@@ -915,6 +969,11 @@ void adopt_model(BoosterObj& b, Forest&& f) {
   invalidate_device_state(b);
   b.contribs.reset();
   b.forest = std::move(f);
+  b.num_groups = b.forest.num_groups();
+  b.grouped = Forest();
+  b.group_begin.clear();
+  b.flat_file_index.clear();
+  if (b.num_groups >= 2) b.grouped = group_major(b.forest, &b.group_begin, &b.flat_file_index);
   b.loaded = true;
   b.margin_error.clear();
   try {
@@ -1196,8 +1255,12 @@ void defer_look(BoosterObj& b, uint64_t nrow, hipStream_t stream) {
   b.defer_last_nrow = nrow;
 }
 
+void launch_predict_groups(BoosterObj& b, DMatrixObj& d, int option_mask, unsigned ntree_limit, float* d_out,
+                           hipStream_t stream);
+
 void launch_predict_checked(BoosterObj& b, DMatrixObj& d, int option_mask, unsigned ntree_limit, float* d_out,
                             hipStream_t stream) {
+  if (b.loaded && b.num_groups >= 2) return launch_predict_groups(b, d, option_mask, ntree_limit, d_out, stream);
   bool pred_leaf = false;
   check_predict_options(b, option_mask, &pred_leaf);
   check_columns(b, d.ncol);
@@ -1240,6 +1303,85 @@ void launch_predict_checked(BoosterObj& b, DMatrixObj& d, int option_mask, unsig
   }
 }
 
+// A booster of several output groups (docs/13_output_groups.md): each group's tree range is walked by the kernel the
+// booster would pick anyway - ring, tiles with trees split over waves, deferred rows, the clustering pass - into its
+// plane of [G][nrow] margins, exactly as a single-group booster of those trees is walked; a group without trees in the
+// range is not walked and its plane holds the base margin.  group_finish then writes the output from the planes.  Leaf
+// ids: all trees of the group-major copy are walked into [nrow][T] and gathered back to file order.  Not capturable:
+// refused before anything is enqueued.
+void launch_predict_groups(BoosterObj& b, DMatrixObj& d, int option_mask, unsigned ntree_limit, float* d_out,
+                           hipStream_t stream) {
+  bool pred_leaf = false;
+  int finish = kGroupMargins;
+  check_predict_options(b, option_mask, &pred_leaf, &finish);
+  check_columns(b, d.ncol);
+  if (stream_capturing(stream))
+    refuse_in_capture("predict a booster of several output groups",
+                      "its predict waits for the stream and fills the booster's own group planes; call it outside the capture");
+  ensure_uploaded(b);
+  if (d.device >= 0 && d.device != b.dev.ordinal)
+    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
+                   std::to_string(b.dev.ordinal));
+  const uint32_t G = b.num_groups, T = (uint32_t)b.forest.trees.size();
+  const uint32_t L = group_tree_limit(b, ntree_limit);
+  const uint64_t n = d.nrow;
+  KernelKind kind = pick_kernel(b);
+  if (!d.grid_looked && d.grid_im == 0 && !pred_leaf && kind != KernelKind::Wide) infer_level_size(d, stream, d.owned != nullptr);
+  if (pred_leaf || kind == KernelKind::Wide) ensure_wide(b);
+  PredictArgs a;
+  a.rows = d.d_data;
+  a.nrow = n;
+  a.ncol = (uint32_t)d.ncol;
+  a.missing = d.missing;
+  a.flags = b.d_flags.p;
+  LaunchTuning tune = b.tune;
+  tune.grid_im = d.grid_im;
+  tune.grid_jm = d.grid_jm;
+  tune.grid_row0 = d.grid_row0;
+  if (pred_leaf) {
+    if (b.d_flat_of_file.p == nullptr && T != 0) {
+      std::vector<uint32_t> flat_of_file(T);
+      for (uint32_t i = 0; i < T; ++i) flat_of_file[b.flat_file_index[i]] = i;
+      b.d_flat_of_file.upload(flat_of_file);
+    }
+    b.d_gleaf.ensure((size_t)n * T);
+    a.tree_begin = 0;
+    a.tree_end = T;
+    a.out = b.d_gleaf.p;
+    a.pred_leaf = true;
+    HIP_CHECK(launch_predict(kind, device_forest(b), a, b.dev.num_cus, stream, tune));
+    HIP_CHECK(launch_group_leaf_gather(b.d_gleaf.p, n, T, b.d_flat_of_file.p, L, d_out, stream));
+    return;
+  }
+  const std::vector<uint32_t> cnt = group_tree_counts(b, L);
+  b.d_planes.ensure((size_t)n * G);
+  a.perm = cluster_rows(b, d, a, false, kind, stream);           // the rows' order: one pass for all groups
+  // room for the leaves of the largest group's trees, made once: no buffer is replaced between the groups' launches
+  if (a.perm == nullptr) leaf_room(b, n, *std::max_element(cnt.begin(), cnt.end()), tune, tune.grid_im, tune.grid_jm, tune.grid_row0);
+  uint32_t base_bits = 0;
+  memcpy(&base_bits, &b.margin_base, sizeof base_bits);
+  for (uint32_t g = 0; g < G; ++g) {
+    float* plane = b.d_planes.p + (size_t)g * n;
+    if (cnt[g] == 0) {
+      if (n) HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(plane), (int)base_bits, (size_t)n, stream));
+      continue;
+    }
+    a.tree_begin = b.group_begin[g];
+    a.tree_end = a.tree_begin + cnt[g];
+    a.out = plane;
+    LaunchTuning gt = tune;
+    const bool deferring = a.perm == nullptr && d.ncol == 27 && defer_prepare(b, n, gt, stream);
+    HIP_CHECK(launch_predict(kind, device_forest(b), a, b.dev.num_cus, stream, gt));
+    if (deferring) defer_look(b, n, stream);
+  }
+  if (a.perm != nullptr) {
+    if (b.cluster_done == nullptr) HIP_CHECK(hipEventCreateWithFlags(&b.cluster_done, hipEventDisableTiming));
+    HIP_CHECK(hipEventRecord(b.cluster_done, stream));
+    b.cluster_in_flight = true;
+  }
+  HIP_CHECK(launch_group_finish(b.d_planes.p, n, G, finish, d_out, stream));
+}
+
 // Per-feature contributions: every refusal is decided here, before anything is enqueued.  What a mode needs is built at
 // its first call on the loaded model (contribs.hpp), on the booster's CURRENT device: the booster is uploaded first
 // (ensure_uploaded: it may just have been moved by "ohx_device"), and device tables left on another device are
@@ -1262,14 +1404,14 @@ ContribsState& contribs_tables(BoosterObj& b, bool approximate, bool interaction
       throw;
     }
     c.means.clear();
-    for (const Tree& t : b.forest.trees) c.means.push_back(node_means(t));
+    for (const Tree& t : b.flat().trees) c.means.push_back(node_means(t));
     c.checked = true;
   }
   if (!approximate && !c.exact_error.empty()) throw OhxError(c.exact_error);
   PathTable pt;
   if (!approximate && !c.exact_ready) {      // host work first: a path that is too long is refused before any upload
     try {
-      pt = build_path_table(b.forest);
+      pt = build_path_table(b.flat());
     } catch (const OhxError& e) {
       c.exact_error = e.what();
       throw;
@@ -1281,7 +1423,7 @@ ContribsState& contribs_tables(BoosterObj& b, bool approximate, bool interaction
       HIP_CHECK(hipSetDevice(c.device));
       c.release_device();
       HIP_CHECK(hipSetDevice(b.dev.ordinal));
-      if (!approximate && pt.heads.empty() && !c.exact_ready) pt = build_path_table(b.forest);
+      if (!approximate && pt.heads.empty() && !c.exact_ready) pt = build_path_table(b.flat());
     }
     c.device = b.dev.ordinal;
     c.d_flags.ensure(1);
@@ -1297,15 +1439,15 @@ ContribsState& contribs_tables(BoosterObj& b, bool approximate, bool interaction
   }
   if (interactions && !approximate && !c.index_ready) {
     // the path table's host copy is not kept once it is on the device: build it again for the index
-    if (pt.heads.empty()) pt = build_path_table(b.forest);
-    const FeaturePathIndex ix = build_feature_path_index(pt, (uint32_t)b.forest.trees.size(), b.forest.num_feature);
+    if (pt.heads.empty()) pt = build_path_table(b.flat());
+    const FeaturePathIndex ix = build_feature_path_index(pt, (uint32_t)b.flat().trees.size(), b.forest.num_feature);
     c.d_fpaths.upload(ix.paths);
     c.d_fstart.upload(ix.start);
     c.index_ready = true;
   }
   if (approximate && !c.approx_ready) {
     std::vector<uint32_t> roots;
-    c.d_nodes.upload(emit_contrib_nodes(b.forest, c.means, &roots));
+    c.d_nodes.upload(emit_contrib_nodes(b.flat(), c.means, &roots));
     c.d_roots.upload(roots);
     c.approx_ready = true;
   }
@@ -1337,13 +1479,41 @@ ContribsState& launch_contribs_checked(BoosterObj& b, DMatrixObj& d, int approxi
   a.missing = d.missing;
   a.nfeat = F;
   tree_range(b, ntree_limit, &a.tree_begin, &a.tree_end);
-  a.bias = contrib_bias(b.forest, c.means, a.tree_begin, a.tree_end, b.margin_base);
+  a.bias = contrib_bias(b.flat(), c.means, a.tree_begin, a.tree_end, b.margin_base);
   a.heads = c.d_heads.p;
   a.elems = c.d_elems.p;
   a.class_start = c.d_class_start.p;
   a.coef = c.d_coef.p;
   a.nodes = c.d_nodes.p;
   a.roots = c.d_roots.p;
+  if (b.num_groups >= 2) {
+    // several output groups: [nrow][G][F+1], each group's block the computation over its tree range, into the state's
+    // block buffer and from there to its place in the output
+    const uint32_t G = b.num_groups;
+    const uint64_t W = (uint64_t)F + 1;
+    const std::vector<uint32_t> cnt = group_tree_counts(b, group_tree_limit(b, ntree_limit));
+    uint64_t part = 0;
+    for (uint32_t g = 0; g < G; ++g) part = std::max(part, plan_contribs(d.nrow, F, cnt[g], b.contribs_split).part_floats);
+    if (host_form) {
+      stream = b.s_exec;
+      if (d.owned == nullptr) order_behind_caller(b.dev.ordinal, stream);
+      c.d_out.ensure((size_t)(d.nrow * G * W));
+      d_out = c.d_out.p;
+      a.flags = c.d_flags.p;
+    }
+    c.d_gblock.ensure((size_t)(d.nrow * W));
+    if (part) c.d_part.ensure((size_t)part);
+    for (uint32_t g = 0; g < G; ++g) {
+      a.tree_begin = b.group_begin[g];
+      a.tree_end = a.tree_begin + cnt[g];
+      a.bias = contrib_bias(b.flat(), c.means, a.tree_begin, a.tree_end, b.margin_base);
+      a.out = c.d_gblock.p;
+      const ContribsPlan gplan = plan_contribs(d.nrow, F, cnt[g], b.contribs_split);
+      HIP_CHECK((hipError_t)launch_contribs(approximate != 0, a, gplan, c.d_part.p, stream));
+      HIP_CHECK(launch_group_block_scatter(c.d_gblock.p, d.nrow, (uint32_t)W, G, g, d_out, stream));
+    }
+    return c;
+  }
   const ContribsPlan plan = plan_contribs(d.nrow, F, a.tree_end - a.tree_begin, b.contribs_split);
   if (host_form) {
     stream = b.s_exec;                       // taken after contribs_tables: the booster's current device
@@ -1355,6 +1525,70 @@ ContribsState& launch_contribs_checked(BoosterObj& b, DMatrixObj& d, int approxi
   a.out = d_out;
   if (plan.split) c.d_part.ensure((size_t)plan.part_floats);
   HIP_CHECK((hipError_t)launch_contribs(approximate != 0, a, plan, c.d_part.p, stream));
+  return c;
+}
+
+// SHAP interaction values of a booster of several output groups: [nrow][G][F+1][F+1], each group's block the
+// computation over its tree range (contributions into the state's phi, then the matrix into its block buffer, then the
+// block to its place in the output).  Allocations before anything is enqueued, as below.
+ContribsState& launch_interactions_groups(BoosterObj& b, DMatrixObj& d, ContribsState& c, ContribsArgs a,
+                                          int approximate, unsigned ntree_limit, float* d_out, bool host_form,
+                                          hipStream_t stream) {
+  const uint32_t G = b.num_groups, F = b.forest.num_feature;
+  const uint64_t F1 = (uint64_t)F + 1, W = F1 * F1;
+  if (d.nrow > (uint64_t)(SIZE_MAX / sizeof(float)) / (W * G))
+    throw OhxError("SHAP interaction values: " + std::to_string(d.nrow) + " rows of " + std::to_string(G) + " x " +
+                   std::to_string(W) + " floats do not fit in memory");
+  const std::vector<uint32_t> cnt = group_tree_counts(b, group_tree_limit(b, ntree_limit));
+  uint64_t part = 0;
+  for (uint32_t g = 0; g < G; ++g) {
+    part = std::max(part, plan_contribs(d.nrow, F, cnt[g], b.contribs_split).part_floats);
+    if (!approximate) part = std::max(part, plan_interactions(d.nrow, F, cnt[g], b.contribs_split).part_floats);
+  }
+  if (host_form) {
+    stream = b.s_exec;
+    if (d.owned == nullptr) order_behind_caller(b.dev.ordinal, stream);
+  }
+  try {
+    if (host_form) {
+      c.d_iout.ensure((size_t)(d.nrow * G * W));
+      c.h_iout.ensure((size_t)(d.nrow * G * W));
+    }
+    c.d_iphi.ensure((size_t)(d.nrow * F1));
+    c.d_gblock.ensure((size_t)(d.nrow * W));
+    if (part) c.d_ipart.ensure((size_t)part);
+  } catch (const OhxError&) {
+    (void)hipGetLastError();
+    throw;
+  }
+  if (host_form) {
+    d_out = c.d_iout.p;
+    a.flags = c.d_flags.p;
+  }
+  InteractionsArgs ia;
+  ia.rows = a.rows;
+  ia.nrow = a.nrow;
+  ia.ncol = a.ncol;
+  ia.missing = a.missing;
+  ia.nfeat = F;
+  ia.phi = c.d_iphi.p;
+  ia.out = c.d_gblock.p;
+  ia.heads = c.d_heads.p;
+  ia.elems = c.d_elems.p;
+  ia.fpaths = c.d_fpaths.p;
+  ia.fstart = c.d_fstart.p;
+  ia.coef = c.d_coef.p;
+  for (uint32_t g = 0; g < G; ++g) {
+    a.tree_begin = ia.tree_begin = b.group_begin[g];
+    a.tree_end = ia.tree_end = a.tree_begin + cnt[g];
+    a.bias = contrib_bias(b.flat(), c.means, a.tree_begin, a.tree_end, b.margin_base);
+    a.out = c.d_iphi.p;
+    const ContribsPlan cplan = plan_contribs(d.nrow, F, cnt[g], b.contribs_split);
+    const ContribsPlan iplan = approximate ? ContribsPlan{} : plan_interactions(d.nrow, F, cnt[g], b.contribs_split);
+    HIP_CHECK((hipError_t)launch_contribs(approximate != 0, a, cplan, c.d_ipart.p, stream));
+    HIP_CHECK((hipError_t)launch_interactions(approximate != 0, ia, iplan, c.d_ipart.p, stream));
+    HIP_CHECK(launch_group_block_scatter(c.d_gblock.p, d.nrow, (uint32_t)W, G, g, d_out, stream));
+  }
   return c;
 }
 
@@ -1387,13 +1621,14 @@ ContribsState& launch_interactions_checked(BoosterObj& b, DMatrixObj& d, int app
   a.missing = d.missing;
   a.nfeat = F;
   tree_range(b, ntree_limit, &a.tree_begin, &a.tree_end);
-  a.bias = contrib_bias(b.forest, c.means, a.tree_begin, a.tree_end, b.margin_base);
+  a.bias = contrib_bias(b.flat(), c.means, a.tree_begin, a.tree_end, b.margin_base);
   a.heads = c.d_heads.p;
   a.elems = c.d_elems.p;
   a.class_start = c.d_class_start.p;
   a.coef = c.d_coef.p;
   a.nodes = c.d_nodes.p;
   a.roots = c.d_roots.p;
+  if (b.num_groups >= 2) return launch_interactions_groups(b, d, c, a, approximate, ntree_limit, d_out, host_form, stream);
   const uint32_t ntree = a.tree_end - a.tree_begin;
   const ContribsPlan cplan = plan_contribs(d.nrow, F, ntree, b.contribs_split);
   const ContribsPlan iplan = approximate ? ContribsPlan{} : plan_interactions(d.nrow, F, ntree, b.contribs_split);
@@ -1831,7 +2066,7 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
   uint32_t t0, t1;
   tree_range(*b, ntree_limit, &t0, &t1);
   const size_t per_row = (option_mask == 16) ? (size_t)(t1 - t0) : 1;
-  const size_t count = (size_t)d->nrow * per_row;
+  const size_t count = b->num_groups >= 2 ? group_predict_len(*b, d->nrow, option_mask, ntree_limit) : (size_t)d->nrow * per_row;
   ensure_uploaded(*b);
   b->d_pred.ensure(count);
   b->h_pred.ensure(count);
@@ -1864,7 +2099,7 @@ int OHXBoosterPredictContribs(BoosterHandle handle, DMatrixHandle dmat, int appr
   // the state, the booster's device and its stream are taken only once the call has settled them
   ContribsState& c = launch_contribs_checked(*b, *d, approximate, ntree_limit, nullptr, true, nullptr);
   hipStream_t s = b->s_exec;
-  const size_t count = (size_t)d->nrow * (b->forest.num_feature + 1);
+  const size_t count = (size_t)d->nrow * b->num_groups * (b->forest.num_feature + 1);
   c.h_out.ensure(count);
   if (count) HIP_CHECK(hipMemcpyAsync(c.h_out.p, c.d_out.p, count * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(c.h_flags.p, c.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -1899,7 +2134,7 @@ int OHXBoosterPredictInteractions(BoosterHandle handle, DMatrixHandle dmat, int 
   ContribsState& c = launch_interactions_checked(*b, *d, approximate, ntree_limit, nullptr, true, nullptr);
   hipStream_t s = b->s_exec;
   const size_t F1 = (size_t)b->forest.num_feature + 1;
-  const size_t count = (size_t)d->nrow * F1 * F1;
+  const size_t count = (size_t)d->nrow * b->num_groups * F1 * F1;
   if (count) HIP_CHECK(hipMemcpyAsync(c.h_iout.p, c.d_iout.p, count * sizeof(float), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipMemcpyAsync(c.h_flags.p, c.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
@@ -1969,6 +2204,7 @@ int OHXBoosterPredictFieldsDevice(BoosterHandle handle, const float* const d_fie
                                   int apply_pow10, float ohscale, float* d_oh_ml, float* d_margin, void* stream) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
+  refuse_groups(*b, "OHXBoosterPredictFieldsDevice");
   if (d_fields == nullptr || is2d == nullptr || d_oh_ml == nullptr) throw OhxError("predict_fields: NULL argument");
   ensure_uploaded(*b);
   FieldsArgs a{};
@@ -1997,6 +2233,7 @@ int OHXBoosterPredictFields(BoosterHandle handle, const float* const fields[], c
                             float ohscale, float* oh_ml, float* margin) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
+  refuse_groups(*b, "OHXBoosterPredictFields");
   if (fields == nullptr || is2d == nullptr || oh_ml == nullptr) throw OhxError("predict_fields: NULL argument");
   ensure_uploaded(*b);
   FieldsArgs a{};
@@ -2124,7 +2361,7 @@ static void contribs_fields_call(BoosterObj& b, const float* const fields[], con
   a.nfeat = F;
   a.missing = missing;
   tree_range(b, ntree_limit, &a.tree_begin, &a.tree_end);
-  a.bias = contrib_bias(b.forest, c.means, a.tree_begin, a.tree_end, b.margin_base);
+  a.bias = contrib_bias(b.flat(), c.means, a.tree_begin, a.tree_end, b.margin_base);
   a.heads = c.d_heads.p;
   a.elems = c.d_elems.p;
   a.class_start = c.d_class_start.p;
@@ -2189,6 +2426,7 @@ int OHXBoosterPredictContribsFields(BoosterHandle handle, const float* const fie
                                     int approximate, unsigned ntree_limit, float* const out[]) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
+  refuse_groups(*b, "OHXBoosterPredictContribsFields");
   contribs_fields_call(*b, fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, approximate, ntree_limit,
                        out, true, nullptr);
   API_END();
@@ -2200,6 +2438,7 @@ int OHXBoosterPredictContribsFieldsDevice(BoosterHandle handle, const float* con
                                           void* stream) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
+  refuse_groups(*b, "OHXBoosterPredictContribsFieldsDevice");
   contribs_fields_call(*b, d_fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, approximate, ntree_limit,
                        d_out, false, static_cast<hipStream_t>(stream));
   API_END();
@@ -2499,6 +2738,7 @@ static void run1_device(BoosterObj& b, const OHXRun1Args& r, hipStream_t stream,
 int OHXBoosterRun1Device(BoosterHandle handle, const OHXRun1Args* args, void* stream) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
+  refuse_groups(*b, "OHXBoosterRun1Device");
   if (args == nullptr) throw OhxError("OHXBoosterRun1Device: args is NULL");
   if (!objective_is_identity(b->forest.objective))
     throw OhxError("objective '" + b->forest.objective + "' is not supported by OHXBoosterRun1");
@@ -2639,6 +2879,7 @@ int OHXSolarGeometry(int jday, const float* lats, const float* lons, int im, int
 int OHXBoosterRun1(BoosterHandle handle, const OHXRun1Args* args) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
+  refuse_groups(*b, "OHXBoosterRun1");
   if (args == nullptr) throw OhxError("OHXBoosterRun1: args is NULL");
   if (!objective_is_identity(b->forest.objective))
     throw OhxError("objective '" + b->forest.objective + "' is not supported by OHXBoosterRun1");
@@ -2912,6 +3153,15 @@ int OHXBoosterGetInfo(BoosterHandle handle, bst_ulong info[8]) {
   info[5] = b->forest.num_feature;
   info[6] = super_used ? 2 : (packed_used ? 1 : 0);
   info[7] = super_used ? super_gathers : 0;
+  API_END();
+}
+
+int OHXBoosterGetNumGroups(BoosterHandle handle, bst_ulong* out) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  if (out == nullptr) throw OhxError("OHXBoosterGetNumGroups: out is NULL");
+  if (!b->loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
+  *out = b->num_groups;
   API_END();
 }
 

@@ -248,6 +248,33 @@ bool emit_super(const Forest& f, SuperForest* out) {
   return true;
 }
 
+Forest group_major(const Forest& f, std::vector<uint32_t>* group_begin, std::vector<uint32_t>* file_index) {
+  const uint32_t G = f.num_groups();
+  group_begin->assign((size_t)G + 1, 0u);
+  for (int32_t g : f.tree_info) ++(*group_begin)[(size_t)g + 1];
+  for (uint32_t g = 0; g < G; ++g) (*group_begin)[g + 1] += (*group_begin)[g];
+  std::vector<uint32_t> next(group_begin->begin(), group_begin->end() - 1);
+  file_index->assign(f.trees.size(), 0u);
+  for (size_t t = 0; t < f.trees.size(); ++t) (*file_index)[next[(size_t)f.tree_info[t]]++] = (uint32_t)t;
+  Forest out;
+  out.base_score = f.base_score;
+  out.num_feature = f.num_feature;
+  out.num_class = f.num_class;
+  out.num_target = f.num_target;
+  out.major_version = f.major_version;
+  out.minor_version = f.minor_version;
+  out.objective = f.objective;
+  out.booster = f.booster;
+  out.legacy_binary = f.legacy_binary;
+  out.trees.reserve(f.trees.size());
+  out.tree_info.reserve(f.trees.size());
+  for (uint32_t t : *file_index) {
+    out.trees.push_back(f.trees[t]);
+    out.tree_info.push_back(f.tree_info[t]);
+  }
+  return out;
+}
+
 std::vector<WideNode> emit_wide(const Forest& f, const Placement& p) {
   std::vector<WideNode> out((size_t)p.num_slots, WideNode{0.0f, 0u, 0u, -1});
   for (size_t ti = 0; ti < f.trees.size(); ++ti) {

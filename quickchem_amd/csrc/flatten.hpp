@@ -118,6 +118,13 @@ struct SuperForest {
   std::vector<SuperTreeHead> heads;
 };
 
+// Several output groups (Forest::num_groups() >= 2): the device forms are built from a copy of the booster whose trees
+// are ordered group by group, each group's trees in file order, so that a group is one contiguous tree range for every
+// walk and every contributions table.  group_begin: G + 1 entries, group g is trees [group_begin[g], group_begin[g+1]);
+// file_index: the file position of each tree of the copy.  Only called for G >= 2: a single-group booster is used as
+// it is.
+Forest group_major(const Forest& f, std::vector<uint32_t>* group_begin, std::vector<uint32_t>* file_index);
+
 // Returns false (and leaves `out` empty) when the booster does not fit the format.
 bool emit_super(const Forest& f, SuperForest* out);
 

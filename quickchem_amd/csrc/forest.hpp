@@ -57,6 +57,9 @@ struct Forest {
 
   size_t total_nodes() const;
   int max_depth() const;
+  // xgboost 1.6.0's num_output_group: max(num_class, num_target, 1).  Tree t adds into group tree_info[t]; every group
+  // starts from margin_base().  1 for the OH model.
+  uint32_t num_groups() const;
   // Checks every invariant the traversal kernels rely on; throws OhxError.
   void validate() const;
   // The value a prediction starts from.  xgboost 1.6.0 keeps the user's base_score in the file and starts

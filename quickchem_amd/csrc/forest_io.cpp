@@ -64,6 +64,11 @@ int Forest::max_depth() const {
   return d;
 }
 
+uint32_t Forest::num_groups() const {
+  int64_t g = std::max<int64_t>((int64_t)num_class, (int64_t)num_target);
+  return g > 1 ? (uint32_t)g : 1u;
+}
+
 bool objective_is_identity(const std::string& name) {
   return name == "reg:squarederror" || name == "reg:linear" || name == "reg:squaredlogerror" ||
          name == "reg:pseudohubererror" || name == "reg:absoluteerror";
@@ -72,7 +77,9 @@ bool objective_is_identity(const std::string& name) {
 // src/objective/regression_obj.cu, regression_loss.h, aft_obj.cu, rank_obj.cu, hinge.cu of xgboost 1.6.0:
 // logistic losses return -log(1/p - 1), the log-link objectives log(p), everything else the value itself.
 bool prob_to_margin(const std::string& o, float base_score, float* margin) {
-  if (objective_is_identity(o) || o == "binary:hinge" || o == "rank:pairwise" || o == "rank:ndcg" || o == "rank:map") {
+  // multi:softprob / multi:softmax (softmax_multiclass_obj.cu): ProbToMargin is the identity
+  if (objective_is_identity(o) || o == "multi:softprob" || o == "multi:softmax" || o == "binary:hinge" ||
+      o == "rank:pairwise" || o == "rank:ndcg" || o == "rank:map") {
     *margin = base_score;
     return true;
   }
@@ -137,8 +144,14 @@ void Forest::validate() const {
     }
     (void)reached;
   }
-  for (int32_t g : tree_info)
-    if (g != 0) throw OhxError("multi-group (multi-class) boosters are not supported by the OH predictor");
+  // several output groups (multi-class, multi-target): every tree must name one of them; a group without trees is
+  // allowed (its margin is margin_base())
+  const uint32_t G = num_groups();
+  for (size_t ti = 0; ti < tree_info.size(); ++ti)
+    if (tree_info[ti] < 0 || (uint32_t)tree_info[ti] >= G)
+      throw OhxError("tree " + std::to_string(ti) + ": tree_info " + std::to_string(tree_info[ti]) +
+                     " is not an output group of this booster (num_class " + std::to_string(num_class) +
+                     ", num_target " + std::to_string(num_target) + ": groups 0 .. " + std::to_string(G - 1) + ")");
 }
 
 // ---------------------------------------------------------------- legacy binary
