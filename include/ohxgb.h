@@ -109,7 +109,32 @@ int XGBoosterLoadModelFromBuffer(BoosterHandle handle, const void* buf, bst_ulon
  * OHXBoosterPredictDevice writes the same into d_out (sized accordingly) and
  * is not capturable for such a booster: -1 inside a stream capture, nothing
  * enqueued.  The fields forms, OHXBoosterPredictContribsFields[Device] and
- * OHXBoosterRun1[Device] are single-output and refuse such a booster. */
+ * OHXBoosterRun1[Device] are single-output and refuse such a booster.
+ *
+ * Categorical splits (xgboost 1.6.0's JSON / UBJSON: split_type, categories, categories_nodes,
+ * categories_segments, categories_sizes; docs/14_categorical.md).  A node with split_type 1 on feature f holds a set S
+ * of categories, non-negative integers of at most OHX_MAX_CATEGORY.  With M = max(S) and
+ * Size = 32 * ceil((M + 1) / 32) - the bit capacity of 1.6.0's per-node bit field - a row with v = x[f] goes, the
+ * tests made in this order:
+ *   v missing (NaN, equal to the matrix's `missing`, a column the matrix lacks)   the default child, as at a
+ *                                                                                numeric split: tested FIRST
+ *   v < 0 or v >= Size (compared as floats)                                       left if default_left, else right
+ *   else, c = (int)v (truncation: 2.7 is category 2, -0.0 is 0), c in S           RIGHT
+ *   else                                                                          left
+ * Size is checked before the cast, so no float outside int range is cast.  Numeric nodes, the leaf sum (base plus
+ * the leaves in tree order, float32, per row), ntree_limit, the base margin and the +-inf rule of both matrix forms
+ * are unchanged.  This restates common::Decision / GetNextNode<has_missing, has_categorical> of xgboost 1.6.0 and is,
+ * as everything here, unpinned against a real libxgboost.
+ * Such a booster (one output group only: several are refused at load) predicts through XGBoosterPredict and
+ * OHXBoosterPredictDevice with option_mask 0 (identity objectives), 1 and 16, by kernels of its own (node format 3 of
+ * OHXBoosterGetInfo); "ohx_kernel" and the other launch knobs are accepted and do not select a kernel for it (a grid said
+ * with OHXDMatrixSetGrid and "ohx_brick" shape the tile kernel's waves as they do for every booster).  Bit
+ * for bit the same whatever the batch, the form or the kernel.  OHXBoosterPredictDevice is not capturable for it
+ * (-1 inside a stream capture, nothing enqueued).  XGBoosterSaveModel writes it as JSON or UBJSON; the legacy binary
+ * format is refused, as by 1.6.0.  Refused at the top of the call, with a message that says "categorical":
+ * OHXBoosterPredictFields[Device], OHXBoosterPredictContribs[Device], OHXBoosterPredictContribsFields[Device],
+ * OHXBoosterPredictInteractions[Device], OHXBoosterRun1[Device]. */
+#define OHX_MAX_CATEGORY 16777215 /* 2**24 - 1: larger integers are not exact in float32 */
 int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, unsigned ntree_limit, int training,
                      bst_ulong* out_len, const float** out_result);
 
@@ -171,6 +196,8 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *                     slots empty has its trees split over waves and the per-tree contributions summed in tree order by a
  *                     second launch (auto), or one wave per 64 rows walks every tree (off); the same bits either way;
  *                     the same for OHXBoosterPredictInteractions[Device] (there a wave per 64 rows and feature)
+ *   "ohx_cat_kernel"  auto | direct : boosters with categorical splits: direct = margins by the kernel without LDS
+ *                     too (auto: the tile kernel where a block's tiles fit a CU's LDS, up to 160 features)
  *   "ohx_device"      HIP device ordinal for this booster
  * None of them changes a prediction.
  * xgboost's own parameter names ("nthread", "predictor", ...) are accepted and
@@ -470,13 +497,17 @@ int OHXSolarGeometryDevice(int jday, const float* d_lats, const float* d_lons, i
 
 /* Model facts for roofline accounting: info[0] trees, [1] nodes in the model,
  * [2] node slots in HBM, [3] bytes of the node array the selected kernel reads,
- * [4] max depth, [5] features, [6] node format in use (0 wide, 1 packed, 2 super-nodes),
+ * [4] max depth, [5] features, [6] node format in use (0 wide, 1 packed, 2 super-nodes, 3 the 16-byte nodes of a
+ * booster with categorical splits: then [3] counts the nodes and the words of the sets kept beside them),
  * [7] vector-memory instructions one wavefront issues to walk the whole forest once (super-nodes). */
 int OHXBoosterGetInfo(BoosterHandle handle, bst_ulong info[8]);
 /* Output groups of the loaded model: xgboost 1.6.0's num_output_group, max(num_class, num_target, 1).  1 for the OH
  * booster; G >= 2 changes the shapes XGBoosterPredict, OHXBoosterPredictContribs and OHXBoosterPredictInteractions
  * return (their comments).  -1 when the booster holds no model. */
 int OHXBoosterGetNumGroups(BoosterHandle handle, bst_ulong* out);
+/* Nodes of the loaded model with a categorical split (split_type 1) over all trees.  0 for every booster without
+ * one: such a booster is flattened, launched and predicted exactly as before.  -1 when the booster holds no model. */
+int OHXBoosterGetNumCategoricalSplits(BoosterHandle handle, bst_ulong* out);
 /* Name of the GPU kernel XGBoosterPredict / OHXBoosterPredictDevice launch for rows of `ncol` columns with the
  * booster's current parameters, as a profiler prints it (without namespaces and arguments), e.g.
  * "predict_rows_tile_kernel<2,2,true,true>".  *out stays valid until the next call on this handle. */

@@ -31,7 +31,7 @@ ABI_SYMBOLS = [
     "OHXBoosterPredictInteractions", "OHXBoosterPredictInteractionsDevice",
     "OHXBoosterPredictContribsFields", "OHXBoosterPredictContribsFieldsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
-    "OHXJulianDay", "OHXSolarGeometry", "OHXSolarGeometryDevice", "OHXBoosterGetInfo", "OHXBoosterGetNumGroups", "OHXBoosterKernelSymbol", "OHXBoosterKernelSymbolRows",
+    "OHXJulianDay", "OHXSolarGeometry", "OHXSolarGeometryDevice", "OHXBoosterGetInfo", "OHXBoosterGetNumGroups", "OHXBoosterGetNumCategoricalSplits", "OHXBoosterKernelSymbol", "OHXBoosterKernelSymbolRows",
     "OHXBoosterRingReruns", "OHXBoosterCopyEngineChoice", "OHXUnregisterHost", "OHXReleaseScratch",
     "OHXCommGetUniqueId", "OHXCommInitRank", "OHXCommFree", "OHXCommInfo", "OHXShardRows", "OHXAllGatherOH",
 ]
@@ -133,6 +133,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.OHXSolarGeometryDevice.argtypes = [i32, vp, vp, i32, i32, f32, f32, vp, vp, vp]
     lib.OHXBoosterGetInfo.argtypes = [vp, C.POINTER(u64)]
     lib.OHXBoosterGetNumGroups.argtypes = [vp, C.POINTER(u64)]
+    lib.OHXBoosterGetNumCategoricalSplits.argtypes = [vp, C.POINTER(u64)]
     lib.OHXBoosterKernelSymbol.argtypes = [vp, u64, C.POINTER(C.c_char_p)]
     lib.OHXBoosterKernelSymbolRows.argtypes = [vp, vp, C.POINTER(C.c_char_p)]
     lib.OHXBoosterRingReruns.argtypes = [vp, vp, C.POINTER(u64)]
@@ -288,6 +289,13 @@ class Booster:
         """Output groups of the loaded model (OHXBoosterGetNumGroups): max(num_class, num_target, 1)."""
         out = C.c_uint64()
         check(self.lib, self.lib.OHXBoosterGetNumGroups(self.handle, C.byref(out)))
+        return int(out.value)
+
+    def num_categorical_splits(self) -> int:
+        """Nodes with a categorical split in the loaded model (OHXBoosterGetNumCategoricalSplits); 0 for a booster
+        without one."""
+        out = C.c_uint64()
+        check(self.lib, self.lib.OHXBoosterGetNumCategoricalSplits(self.handle, C.byref(out)))
         return int(out.value)
 
     def _groups(self) -> int:

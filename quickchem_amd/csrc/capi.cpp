@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/ohxgb.h"
+#include "categorical.hpp"
 #include "contribs.hpp"
 #include "flatten.hpp"
 #include "forest.hpp"
@@ -709,6 +710,15 @@ struct BoosterObj {
   hipEvent_t cluster_done = nullptr;
   bool cluster_in_flight = false;
   std::vector<DevBuf<float>> d_run1_stage;
+  // Categorical splits (docs/14_categorical.md): a booster that holds at least one is walked from a node format of
+  // its own (flatten.hpp CatNode) by the kernels of categorical.hip and has none of the device forms above but the
+  // roots; num_cat == 0 - every other booster - builds and launches exactly what it always did.
+  uint64_t num_cat = 0;
+  DevBuf<CatNode> d_cat_nodes;
+  DevBuf<uint32_t> d_cat_words;
+  DevBuf<int32_t> d_cat_orig;
+  uint64_t cat_word_count = 0, cat_inline_sets = 0, cat_word_sets = 0;
+  bool cat_force_direct = false;        // "ohx_cat_kernel" = direct: margins by the direct kernel too (same bits)
   std::unique_ptr<ContribsState> contribs;
   bool contribs_split = true;           // "ohx_contribs_split": small batches may have their trees split over waves
 };
@@ -787,6 +797,9 @@ void invalidate_device_state(BoosterObj& b) {
   b.super_ok = false;
   b.d_roots.release();
   b.d_flat_of_file.release();
+  b.d_cat_nodes.release();
+  b.d_cat_words.release();
+  b.d_cat_orig.release();
 }
 
 void ensure_wide(BoosterObj& b) {
@@ -808,7 +821,17 @@ void ensure_uploaded(BoosterObj& b) {
   b.placement = place_forest(flat, b.layout);
   b.packed_ok = packed_format_fits(flat, b.placement);
   b.d_roots.upload(b.placement.roots);
-  if (wants_super(b.kernel_name)) {
+  if (b.num_cat != 0) {
+    // categorical splits: the one format the kernels of categorical.hip read, whatever ohx_kernel says
+    CatForest cf = emit_cat(flat, b.placement);
+    b.cat_word_count = cf.words.size();
+    b.cat_inline_sets = cf.inline_sets;
+    b.cat_word_sets = cf.word_sets;
+    if (cf.words.empty()) cf.words.push_back(0u);
+    b.d_cat_nodes.upload(cf.nodes);
+    b.d_cat_words.upload(cf.words);
+    b.d_cat_orig.upload(cf.orig_id);
+  } else if (wants_super(b.kernel_name)) {
     SuperForest sf;
     b.super_ok = emit_super(flat, &sf) && sf.nodes.size() * sizeof(SuperNode) < 0xFFFFFFF0ull;
     if (b.super_ok) {
@@ -821,11 +844,11 @@ void ensure_uploaded(BoosterObj& b) {
       b.d_super_heads.upload(sf.heads);
     }
   }
-  if (b.packed_ok && !(b.super_ok && wants_super(b.kernel_name))) {
+  if (b.num_cat == 0 && b.packed_ok && !(b.super_ok && wants_super(b.kernel_name))) {
     std::vector<PackedNode> packed = emit_packed(flat, b.placement, nullptr);
     b.d_packed.upload(packed);
   }
-  if (pick_kernel(b) == KernelKind::Wide) ensure_wide(b);
+  if (b.num_cat == 0 && pick_kernel(b) == KernelKind::Wide) ensure_wide(b);
   b.d_flags.ensure(3);      // [0] kFlag* bits, [1] ring re-runs counted on the device, [2] the train a block last gave up in
   {
     LibStreams& ls = lib_streams(b.dev.ordinal);
@@ -927,6 +950,27 @@ void refuse_groups(const BoosterObj& b, const char* what) {
                    "OHXBoosterPredictDevice");
 }
 
+// What a booster with categorical splits cannot do yet is refused at the top of the call, before an argument is read
+// or the device is touched (include/ohxgb.h part 5)
+void refuse_categorical(const BoosterObj& b, const char* what) {
+  if (b.loaded && b.num_cat != 0)
+    throw OhxError(std::string(what) + " does not take a booster with categorical splits (this one has " +
+                   std::to_string(b.num_cat) + "); predict it through XGBoosterPredict or OHXBoosterPredictDevice");
+}
+
+DeviceCatForest device_cat_forest(const BoosterObj& b) {
+  DeviceCatForest d;
+  d.nodes = b.d_cat_nodes.p;
+  d.node_bytes = (uint32_t)(b.d_cat_nodes.n * sizeof(CatNode));
+  d.words = b.d_cat_words.p;
+  d.orig_id = b.d_cat_orig.p;
+  d.roots = b.d_roots.p;
+  d.num_trees = (uint32_t)b.forest.trees.size();
+  d.num_feature = b.forest.num_feature;
+  d.base_score = b.margin_base;
+  return d;
+}
+
 void check_columns(const BoosterObj& b, uint64_t ncol) {
   if (ncol > b.forest.num_feature)
     throw OhxError("Number of columns does not match number of features in booster (" + std::to_string(ncol) +
@@ -970,6 +1014,7 @@ void adopt_model(BoosterObj& b, Forest&& f) {
   b.contribs.reset();
   b.forest = std::move(f);
   b.num_groups = b.forest.num_groups();
+  b.num_cat = b.forest.num_categorical_splits();
   b.grouped = Forest();
   b.group_begin.clear();
   b.flat_file_index.clear();
@@ -1264,10 +1309,32 @@ void launch_predict_checked(BoosterObj& b, DMatrixObj& d, int option_mask, unsig
   bool pred_leaf = false;
   check_predict_options(b, option_mask, &pred_leaf);
   check_columns(b, d.ncol);
+  if (b.loaded && b.num_cat != 0 && stream_capturing(stream))
+    refuse_in_capture("predict a booster with categorical splits",
+                      "its kernels are not among what a capture may hold yet; call it outside the capture");
   ensure_uploaded(b);
   if (d.device >= 0 && d.device != b.dev.ordinal)
     throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
                    std::to_string(b.dev.ordinal));
+  if (b.num_cat != 0) {
+    // the kernels of categorical.hip; of the launch knobs only the rows' grid and the brick shape apply (ohx_kernel, tree
+    // split, deferred rows, the clustering pass and the level-size search do not)
+    CatPredictArgs c;
+    c.rows = d.d_data;
+    c.nrow = d.nrow;
+    c.ncol = (uint32_t)d.ncol;
+    c.missing = d.missing;
+    tree_range(b, ntree_limit, &c.tree_begin, &c.tree_end);
+    c.out = d_out;
+    c.pred_leaf = pred_leaf;
+    c.flags = b.d_flags.p;
+    LaunchTuning tune = b.tune;
+    tune.grid_im = d.grid_im;
+    tune.grid_jm = d.grid_jm;
+    tune.grid_row0 = d.grid_row0;
+    HIP_CHECK(launch_predict_cat(device_cat_forest(b), c, b.dev.num_cus, b.cat_force_direct, stream, tune));
+    return;
+  }
   KernelKind kind = pick_kernel(b);
   // nobody has said which grid the rows come from: look once (work on `stream` enqueued so far is waited for)
   // (a matrix the library copied itself - the reference's create / predict / free per tick - takes the verdict of
@@ -2046,6 +2113,10 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
     const std::string v = value;
     if (v != "auto" && v != "off") throw OhxError("ohx_contribs_split must be auto or off");
     b->contribs_split = v == "auto";
+  } else if (n == "ohx_cat_kernel") {
+    // boosters with categorical splits: "direct" = margins by the direct kernel too (the same bits as the tile kernel's)
+    if (v != "auto" && v != "direct") throw OhxError("ohx_cat_kernel must be auto or direct");
+    b->cat_force_direct = v == "direct";
   } else if (n == "ohx_device") {
     int k = atoi(value);
     if (k != b->device_pref) invalidate_device_state(*b);
@@ -2094,6 +2165,7 @@ int OHXBoosterPredictContribs(BoosterHandle handle, DMatrixHandle dmat, int appr
                               bst_ulong* out_len, const float** out_result) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
+  refuse_categorical(*b, "OHXBoosterPredictContribs");
   DMatrixObj* d = as_dmat(dmat);
   if (out_len == nullptr || out_result == nullptr) throw OhxError("OHXBoosterPredictContribs: NULL output argument");
   // the state, the booster's device and its stream are taken only once the call has settled them
@@ -2118,6 +2190,7 @@ int OHXBoosterPredictContribsDevice(BoosterHandle handle, DMatrixHandle dmat, in
                                     float* d_out, void* stream) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
+  refuse_categorical(*b, "OHXBoosterPredictContribsDevice");
   DMatrixObj* d = as_dmat(dmat);
   launch_contribs_checked(*b, *d, approximate, ntree_limit, d_out, false, static_cast<hipStream_t>(stream));
   d->used_async = true;
@@ -2128,6 +2201,7 @@ int OHXBoosterPredictInteractions(BoosterHandle handle, DMatrixHandle dmat, int 
                                   bst_ulong* out_len, const float** out_result) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
+  refuse_categorical(*b, "OHXBoosterPredictInteractions");
   DMatrixObj* d = as_dmat(dmat);
   if (out_len == nullptr || out_result == nullptr)
     throw OhxError("OHXBoosterPredictInteractions: NULL output argument");
@@ -2152,6 +2226,7 @@ int OHXBoosterPredictInteractionsDevice(BoosterHandle handle, DMatrixHandle dmat
                                         unsigned ntree_limit, float* d_out, void* stream) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
+  refuse_categorical(*b, "OHXBoosterPredictInteractionsDevice");
   DMatrixObj* d = as_dmat(dmat);
   launch_interactions_checked(*b, *d, approximate, ntree_limit, d_out, false, static_cast<hipStream_t>(stream));
   d->used_async = true;
@@ -2205,6 +2280,7 @@ int OHXBoosterPredictFieldsDevice(BoosterHandle handle, const float* const d_fie
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   refuse_groups(*b, "OHXBoosterPredictFieldsDevice");
+  refuse_categorical(*b, "OHXBoosterPredictFieldsDevice");
   if (d_fields == nullptr || is2d == nullptr || d_oh_ml == nullptr) throw OhxError("predict_fields: NULL argument");
   ensure_uploaded(*b);
   FieldsArgs a{};
@@ -2234,6 +2310,7 @@ int OHXBoosterPredictFields(BoosterHandle handle, const float* const fields[], c
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   refuse_groups(*b, "OHXBoosterPredictFields");
+  refuse_categorical(*b, "OHXBoosterPredictFields");
   if (fields == nullptr || is2d == nullptr || oh_ml == nullptr) throw OhxError("predict_fields: NULL argument");
   ensure_uploaded(*b);
   FieldsArgs a{};
@@ -2427,6 +2504,7 @@ int OHXBoosterPredictContribsFields(BoosterHandle handle, const float* const fie
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   refuse_groups(*b, "OHXBoosterPredictContribsFields");
+  refuse_categorical(*b, "OHXBoosterPredictContribsFields");
   contribs_fields_call(*b, fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, approximate, ntree_limit,
                        out, true, nullptr);
   API_END();
@@ -2439,6 +2517,7 @@ int OHXBoosterPredictContribsFieldsDevice(BoosterHandle handle, const float* con
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   refuse_groups(*b, "OHXBoosterPredictContribsFieldsDevice");
+  refuse_categorical(*b, "OHXBoosterPredictContribsFieldsDevice");
   contribs_fields_call(*b, d_fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, approximate, ntree_limit,
                        d_out, false, static_cast<hipStream_t>(stream));
   API_END();
@@ -2739,6 +2818,7 @@ int OHXBoosterRun1Device(BoosterHandle handle, const OHXRun1Args* args, void* st
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   refuse_groups(*b, "OHXBoosterRun1Device");
+  refuse_categorical(*b, "OHXBoosterRun1Device");
   if (args == nullptr) throw OhxError("OHXBoosterRun1Device: args is NULL");
   if (!objective_is_identity(b->forest.objective))
     throw OhxError("objective '" + b->forest.objective + "' is not supported by OHXBoosterRun1");
@@ -2880,6 +2960,7 @@ int OHXBoosterRun1(BoosterHandle handle, const OHXRun1Args* args) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   refuse_groups(*b, "OHXBoosterRun1");
+  refuse_categorical(*b, "OHXBoosterRun1");
   if (args == nullptr) throw OhxError("OHXBoosterRun1: args is NULL");
   if (!objective_is_identity(b->forest.objective))
     throw OhxError("objective '" + b->forest.objective + "' is not supported by OHXBoosterRun1");
@@ -3115,6 +3196,22 @@ int OHXBoosterGetInfo(BoosterHandle handle, bst_ulong info[8]) {
   BoosterObj* b = as_booster(handle);
   if (info == nullptr) throw OhxError("OHXBoosterGetInfo: info is NULL");
   if (!b->loaded) throw OhxError("the booster holds no model");
+  if (b->num_cat != 0) {
+    // categorical splits: node format 3 (flatten.hpp CatNode); host-only like the rest
+    Placement lp = b->uploaded ? Placement() : place_forest(b->forest, b->layout);
+    const Placement& pl = b->uploaded ? b->placement : lp;
+    uint64_t words = b->cat_word_count;
+    if (!b->uploaded) words = emit_cat(b->forest, pl).words.size();
+    info[0] = b->forest.trees.size();
+    info[1] = pl.real_nodes;
+    info[2] = pl.num_slots;
+    info[3] = pl.num_slots * sizeof(CatNode) + words * sizeof(uint32_t);
+    info[4] = (bst_ulong)pl.max_depth;
+    info[5] = b->forest.num_feature;
+    info[6] = 3;
+    info[7] = 0;
+    return 0;
+  }
   // host-only: placement can be computed without a device
   Placement local;
   const Placement* p = &b->placement;
@@ -3165,11 +3262,25 @@ int OHXBoosterGetNumGroups(BoosterHandle handle, bst_ulong* out) {
   API_END();
 }
 
+int OHXBoosterGetNumCategoricalSplits(BoosterHandle handle, bst_ulong* out) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  if (out == nullptr) throw OhxError("OHXBoosterGetNumCategoricalSplits: out is NULL");
+  if (!b->loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
+  *out = b->num_cat;
+  API_END();
+}
+
 int OHXBoosterKernelSymbol(BoosterHandle handle, bst_ulong ncol, const char** out) {
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   if (out == nullptr) throw OhxError("OHXBoosterKernelSymbol: out is NULL");
   ensure_uploaded(*b);
+  if (b->num_cat != 0) {
+    b->symbol = cat_kernel_symbol(b->forest.num_feature, false, b->cat_force_direct);
+    *out = b->symbol.c_str();
+    return 0;
+  }
   b->symbol = predict_kernel_symbol(pick_kernel(*b), device_forest(*b), (uint32_t)ncol, b->tune);
   *out = b->symbol.c_str();
   API_END();
@@ -3182,6 +3293,11 @@ int OHXBoosterKernelSymbolRows(BoosterHandle handle, DMatrixHandle dmat, const c
   if (out == nullptr) throw OhxError("OHXBoosterKernelSymbolRows: out is NULL");
   check_columns(*b, d->ncol);
   ensure_uploaded(*b);
+  if (b->num_cat != 0) {
+    b->symbol = cat_kernel_symbol(b->forest.num_feature, false, b->cat_force_direct);
+    *out = b->symbol.c_str();
+    return 0;
+  }
   PredictArgs a;
   a.rows = d->d_data;
   a.nrow = d->nrow;

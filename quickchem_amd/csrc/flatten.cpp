@@ -300,4 +300,58 @@ std::vector<WideNode> emit_wide(const Forest& f, const Placement& p) {
   return out;
 }
 
+CatForest emit_cat(const Forest& f, const Placement& p) {
+  if (f.num_feature > kCatFeatureMask) throw OhxError("booster has too many features for the categorical node format");
+  if (p.num_slots * sizeof(CatNode) >= 0xFFFFFFF0ull) throw OhxError("booster too large for the categorical node format (4 GiB of nodes)");
+  CatForest out;
+  out.nodes.assign((size_t)p.num_slots, CatNode{0u, 0u, 0u, 0.0f});
+  out.orig_id.assign((size_t)p.num_slots, -1);
+  for (size_t ti = 0; ti < f.trees.size(); ++ti) {
+    const Tree& t = f.trees[ti];
+    const auto& slot = p.slot_of[ti];
+    for (size_t i = 0; i < t.size(); ++i) {
+      if (slot[i] == kNoSlot) continue;
+      CatNode nd{0u, 0u, 0u, 0.0f};
+      out.orig_id[slot[i]] = (int32_t)i;
+      if (t.left[i] == -1) {
+        memcpy(&nd.bits, &t.value[i], 4);
+      } else {
+        const uint32_t ls = slot[(size_t)t.left[i]], rs = slot[(size_t)t.right[i]];
+        if (rs != ls + 1) throw OhxError("internal error: placement broke sibling adjacency");
+        nd.left = ls;
+        nd.meta = t.feature[i] | ((uint32_t)(t.default_left[i] ? 1u : 0u) << 31);
+        if (!t.is_categorical(i)) {
+          memcpy(&nd.bits, &t.value[i], 4);
+        } else {
+          const int64_t* cats = nullptr;
+          size_t count = 0;
+          if (!t.category_set(i, &cats, &count) || count == 0)
+            throw OhxError("internal error: a categorical node without a set reached the flattening");
+          int64_t top = 0;
+          for (size_t c = 0; c < count; ++c) {
+            if (cats[c] < 0 || cats[c] > kMaxCategory) throw OhxError("internal error: category out of range in the flattening");
+            top = std::max(top, cats[c]);
+          }
+          const uint32_t nwords = (uint32_t)(top / 32 + 1);
+          nd.meta |= kCatFlag;
+          nd.size = (float)(32u * nwords);
+          if (nwords == 1) {
+            for (size_t c = 0; c < count; ++c) nd.bits |= 1u << (uint32_t)cats[c];
+            ++out.inline_sets;
+          } else {
+            if (out.words.size() + nwords >= 0xFFFFFFF0ull) throw OhxError("booster too large: more than 2**32 category words");
+            nd.meta |= kCatWords;
+            nd.bits = (uint32_t)out.words.size();
+            out.words.resize(out.words.size() + nwords, 0u);
+            for (size_t c = 0; c < count; ++c) out.words[nd.bits + (size_t)(cats[c] >> 5)] |= 1u << (uint32_t)(cats[c] & 31);
+            ++out.word_sets;
+          }
+        }
+      }
+      out.nodes[slot[i]] = nd;
+    }
+  }
+  return out;
+}
+
 }  // namespace ohx

@@ -125,6 +125,35 @@ struct SuperForest {
 // it is.
 Forest group_major(const Forest& f, std::vector<uint32_t>* group_begin, std::vector<uint32_t>* file_index);
 
+// Boosters with categorical splits (docs/14_categorical.md): a format of their own, built only for them, from the same
+// Placement as the wide format - 16 bytes a node, absolute child slots, right = left + 1, left == 0 => leaf.
+//   bits  numeric node: float bits of the split condition; leaf: of the leaf value;
+//         categorical node, inline set (largest category < 32): the set itself, bit c = category c;
+//         categorical node, larger set: index of the set's first word in CatForest::words
+//   meta  feature | kCatFlag (categorical) | kCatWords (the set lies in `words`) | default_left << 31
+//   size  categorical nodes: the set's capacity in bits, 32 * ceil((largest category + 1) / 32), as a float (exact: at
+//         most 2**24); a row's value v is a category only if 0 <= v < size, and then bit (int)v of the set decides:
+//         word (int)v >> 5, bit (int)v & 31, set => RIGHT.  0 elsewhere.
+// The node id of the model file (pred_leaf) is kept beside the nodes, one per slot: it is read once per tree.
+struct CatNode {
+  uint32_t bits;
+  uint32_t left;
+  uint32_t meta;
+  float size;
+};
+static_assert(sizeof(CatNode) == 16, "one 128-bit load per node");
+constexpr uint32_t kCatFlag = 1u << 30;
+constexpr uint32_t kCatWords = 1u << 29;
+constexpr uint32_t kCatFeatureMask = kCatWords - 1u;
+
+struct CatForest {
+  std::vector<CatNode> nodes;        // [num_slots]
+  std::vector<uint32_t> words;       // the sets that do not fit a node, one after the other
+  std::vector<int32_t> orig_id;      // [num_slots], -1 for a slot no node sits in
+  uint64_t inline_sets = 0, word_sets = 0;
+};
+CatForest emit_cat(const Forest& f, const Placement& p);
+
 // Returns false (and leaves `out` empty) when the booster does not fit the format.
 bool emit_super(const Forest& f, SuperForest* out);
 

@@ -12,6 +12,7 @@
 #include <cstring>
 #include <fstream>
 #include <sstream>
+#include <type_traits>
 
 #include "forest.hpp"
 #include "json_min.hpp"
@@ -32,6 +33,33 @@ void Tree::resize(size_t n) {
   sum_hess.assign(n, 0.0f);
   base_weight.assign(n, 0.0f);
   leaf_child_cnt.assign(n, 0);
+  split_type.assign(n, 0);
+  categories.clear();
+  categories_nodes.clear();
+  categories_segments.clear();
+  categories_sizes.clear();
+}
+
+size_t Tree::num_categorical_splits() const {
+  size_t n = 0;
+  for (uint8_t s : split_type) n += s != 0 ? 1 : 0;
+  return n;
+}
+
+bool Tree::category_set(size_t node, const int64_t** begin, size_t* count) const {
+  for (size_t k = 0; k < categories_nodes.size(); ++k) {
+    if ((size_t)categories_nodes[k] != node) continue;
+    *begin = categories.data() + categories_segments[k];
+    *count = (size_t)categories_sizes[k];
+    return true;
+  }
+  return false;
+}
+
+uint64_t Forest::num_categorical_splits() const {
+  uint64_t n = 0;
+  for (const auto& t : trees) n += t.num_categorical_splits();
+  return n;
 }
 
 size_t Forest::total_nodes() const {
@@ -143,7 +171,49 @@ void Forest::validate() const {
       stack.push_back(t.right[(size_t)i]);
     }
     (void)reached;
+    // categorical splits: the four arrays of the file must name every categorical node once, with a set that lies
+    // inside `categories`, is not empty and holds categories the device format can keep (forest.hpp kMaxCategory)
+    const std::string where = "tree " + std::to_string(ti) + ": ";
+    if (t.split_type.size() != n) throw OhxError(where + "split_type length does not match the number of nodes");
+    size_t ncat = 0;
+    for (size_t i = 0; i < n; ++i) {
+      if (t.split_type[i] > 1)
+        throw OhxError(where + "node " + std::to_string(i) + " has split_type " + std::to_string((int)t.split_type[i]) +
+                       " (0 = numeric and 1 = categorical are known)");
+      if (t.split_type[i] == 0) continue;
+      ++ncat;
+      if (t.deleted[i] || t.left[i] == -1)
+        throw OhxError(where + "categorical node " + std::to_string(i) + " is a leaf or a deleted slot");
+    }
+    if (t.categories_nodes.size() != t.categories_segments.size() || t.categories_nodes.size() != t.categories_sizes.size())
+      throw OhxError(where + "categories_nodes, categories_segments and categories_sizes differ in length");
+    std::vector<uint8_t> has_segment(n, 0);
+    for (size_t k = 0; k < t.categories_nodes.size(); ++k) {
+      const int64_t node = t.categories_nodes[k], seg = t.categories_segments[k], size = t.categories_sizes[k];
+      if (node < 0 || (size_t)node >= n)
+        throw OhxError(where + "categories_nodes entry " + std::to_string(node) + " is out of range");
+      if (has_segment[(size_t)node])
+        throw OhxError(where + "categories_nodes names node " + std::to_string(node) + " more than once (repeated)");
+      if (t.split_type[(size_t)node] != 1)
+        throw OhxError(where + "categories_nodes names node " + std::to_string(node) + ", which is a numeric node");
+      has_segment[(size_t)node] = 1;
+      if (size == 0) throw OhxError(where + "categorical node " + std::to_string(node) + " has a segment of size 0");
+      if (seg < 0 || size < 0 || (uint64_t)seg + (uint64_t)size > t.categories.size())
+        throw OhxError(where + "the segment of categorical node " + std::to_string(node) + " runs past categories");
+      for (int64_t c = seg; c < seg + size; ++c) {
+        if (t.categories[(size_t)c] < 0)
+          throw OhxError(where + "categorical node " + std::to_string(node) + " holds a negative category");
+        if (t.categories[(size_t)c] > kMaxCategory)
+          throw OhxError(where + "categorical node " + std::to_string(node) + " holds category " +
+                         std::to_string(t.categories[(size_t)c]) + ", above the limit of " + std::to_string(kMaxCategory));
+      }
+    }
+    for (size_t i = 0; i < n && ncat != 0; ++i)
+      if (t.split_type[i] == 1 && !has_segment[i])
+        throw OhxError(where + "categorical node " + std::to_string(i) + " has no segment in categories_nodes");
   }
+  if (num_groups() >= 2 && num_categorical_splits() != 0)
+    throw OhxError("categorical splits in a booster with several output groups (multi-class or multi-target) are not supported");
   // several output groups (multi-class, multi-target): every tree must name one of them; a group without trees is
   // allowed (its margin is margin_base())
   const uint32_t G = num_groups();
@@ -312,6 +382,10 @@ Forest parse_legacy_binary(const uint8_t* p, size_t len) {
 }
 
 std::vector<uint8_t> write_legacy_binary(const Forest& f) {
+  // as xgboost 1.6.0: the legacy format has no place for a category set
+  if (f.num_categorical_splits() != 0)
+    throw OhxError("a booster with categorical splits cannot be saved in the legacy binary format: use JSON/UBJ "
+                   "(a file name ending in .json or .ubj)");
   Writer w;
   size_t nodes = f.total_nodes();
   w.buf.reserve(4 + 136 + 64 + 160 + f.trees.size() * 152 + nodes * 36 + 64);
@@ -625,8 +699,16 @@ std::vector<uint8_t> write_ubjson_model(const Forest& f) {
   w.key("attributes"); w.out.push_back('{');
   for (auto& kv : f.attributes) w.kstr(kv.first, kv.second);
   w.out.push_back('}');
-  empty("feature_names");
-  empty("feature_types");
+  auto strings = [&](const std::string& k, const std::vector<std::string>& v) {
+    if (v.empty()) return empty(k);
+    w.key(k);
+    w.out.push_back('[');
+    for (const std::string& x : v) w.str(x);
+    w.out.push_back(']');
+  };
+  auto i32_or_empty = [&](const std::string& k, const std::vector<int32_t>& v) { if (v.empty()) empty(k); else i32(k, v); };
+  strings("feature_names", f.feature_names);
+  strings("feature_types", f.feature_types);
   w.key("gradient_booster"); w.out.push_back('{');
   w.key("model"); w.out.push_back('{');
   w.key("gbtree_model_param"); w.out.push_back('{');
@@ -640,7 +722,13 @@ std::vector<uint8_t> write_ubjson_model(const Forest& f) {
     const Tree& t = f.trees[ti];
     w.out.push_back('{');
     f32("base_weights", t.base_weight);
-    empty("categories"); empty("categories_nodes"); empty("categories_segments"); empty("categories_sizes");
+    {
+      std::vector<int32_t> cats(t.categories.begin(), t.categories.end());
+      i32_or_empty("categories", cats);
+    }
+    i32_or_empty("categories_nodes", t.categories_nodes);
+    i32_or_empty("categories_segments", t.categories_segments);
+    i32_or_empty("categories_sizes", t.categories_sizes);
     u8("default_left", t.default_left);
     w.key("id"); w.integer((int64_t)ti);
     i32("left_children", t.left);
@@ -655,6 +743,7 @@ std::vector<uint8_t> write_ubjson_model(const Forest& f) {
     for (size_t i = 0; i < t.size(); ++i) sidx[i] = (int32_t)t.feature[i];
     i32("split_indices", sidx);
     std::vector<uint8_t> stype(t.size(), 0);
+    for (size_t i = 0; i < t.size(); ++i) stype[i] = t.is_categorical(i) ? t.split_type[i] : 0;
     u8("split_type", stype);
     f32("sum_hessian", t.sum_hess);
     w.key("tree_param"); w.out.push_back('{');
@@ -730,8 +819,25 @@ static Forest forest_from_document(const json::Value& doc) {
     auto& dl = nums_of(jt.at("default_left"), "default_left", n);
     const std::vector<json::Num>* st = nullptr;
     if (const json::Value* v = jt.find("split_type")) st = &nums_of(*v, "split_type", n);
-    if (const json::Value* cn = jt.find("categories_nodes"))
-      if (cn->array_size() != 0) throw OhxError("JSON model: categorical splits are not supported");
+    // the category sets, as the file gives them (Forest::validate judges them)
+    auto ints_of = [&](const char* key, auto& dst) {
+      const json::Value* v = jt.find(key);
+      if (v == nullptr) return;
+      if (v->type != json::Value::NumArray) {
+        if (v->array_size() != 0) throw OhxError(std::string("JSON model: '") + key + "' is not a numeric array");
+        return;
+      }
+      dst.reserve(v->nums.size());
+      for (const json::Num& x : v->nums) {
+        // far outside what validate() accepts is kept as "too large" / "negative", never cast out of range
+        const double d = x.d != x.d ? -1.0 : std::min(std::max(x.d, -2147483648.0), 2147483647.0);
+        dst.push_back((typename std::remove_reference<decltype(dst)>::type::value_type)d);
+      }
+    };
+    ints_of("categories", t.categories);
+    ints_of("categories_nodes", t.categories_nodes);
+    ints_of("categories_segments", t.categories_segments);
+    ints_of("categories_sizes", t.categories_sizes);
     const std::vector<json::Num>* lch = nullptr;
     const std::vector<json::Num>* sh = nullptr;
     const std::vector<json::Num>* bw = nullptr;
@@ -747,7 +853,10 @@ static Forest forest_from_document(const json::Value& doc) {
       t.feature[i] = (uint32_t)si[i].d;
       t.value[i] = sc[i].f;
       t.default_left[i] = dl[i].d != 0.0 ? 1 : 0;
-      if (st && (*st)[i].d != 0.0) throw OhxError("JSON model: categorical splits are not supported");
+      if (st) {
+        const double k = (*st)[i].d;
+        t.split_type[i] = (k >= 0.0 && k <= 255.0) ? (uint8_t)k : (uint8_t)255;
+      }
       if (lch) t.loss_chg[i] = (*lch)[i].f;
       if (sh) t.sum_hess[i] = (*sh)[i].f;
       if (bw) t.base_weight[i] = (*bw)[i].f;
@@ -763,6 +872,15 @@ static Forest forest_from_document(const json::Value& doc) {
     // deleted slots in JSON: xgboost marks them with split index == max
     for (size_t i = 1; i < n; ++i)
       if (si[i].d >= 4294967295.0) { t.deleted[i] = 1; t.left[i] = t.right[i] = -1; t.feature[i] = 0; }
+  }
+  for (const char* key : {"feature_names", "feature_types"}) {
+    const json::Value* v = learner.find(key);
+    if (v == nullptr || v->type != json::Value::Array) continue;
+    std::vector<std::string>& dst = key[8] == 'n' ? f.feature_names : f.feature_types;
+    for (const json::Value& x : v->arr) {
+      if (x.type != json::Value::String) throw OhxError(std::string("JSON model: '") + key + "' holds something that is not a string");
+      dst.push_back(x.str);
+    }
   }
   auto& info = nums_of(model.at("tree_info"), "tree_info", num_trees);
   f.tree_info.resize(num_trees);
@@ -788,7 +906,23 @@ std::string write_json_model(const Forest& f) {
     if (i) o += ',';
     o += '"' + f.attributes[i].first + "\":\"" + f.attributes[i].second + '"';
   }
-  o += "},\"feature_names\":[],\"feature_types\":[],\"gradient_booster\":{\"model\":{";
+  auto strings = [&](const char* key, const std::vector<std::string>& v) {
+    o += std::string("\"") + key + "\":[";
+    for (size_t i = 0; i < v.size(); ++i) {
+      if (i) o += ',';
+      o += '"';
+      for (char c : v[i]) {
+        if (c == '"' || c == '\\') o += '\\';
+        o += c;
+      }
+      o += '"';
+    }
+    o += "],";
+  };
+  o += "},";
+  strings("feature_names", f.feature_names);
+  strings("feature_types", f.feature_types);
+  o += "\"gradient_booster\":{\"model\":{";
   o += "\"gbtree_model_param\":{\"num_parallel_tree\":\"1\",\"num_trees\":\"" + std::to_string(f.trees.size()) +
        "\",\"size_leaf_vector\":\"0\"},";
   put_array(o, "tree_info", f.tree_info, fi);
@@ -798,7 +932,10 @@ std::string write_json_model(const Forest& f) {
     if (ti) o += ',';
     o += '{';
     put_array(o, "base_weights", t.base_weight, ff);
-    o += "\"categories\":[],\"categories_nodes\":[],\"categories_segments\":[],\"categories_sizes\":[],";
+    put_array(o, "categories", t.categories, [](std::string& s, int64_t v) { s += std::to_string(v); });
+    put_array(o, "categories_nodes", t.categories_nodes, fi);
+    put_array(o, "categories_segments", t.categories_segments, fi);
+    put_array(o, "categories_sizes", t.categories_sizes, fi);
     put_array(o, "default_left", t.default_left, fb);
     o += "\"id\":" + std::to_string(ti) + ',';
     put_array(o, "left_children", t.left, fi);
@@ -813,7 +950,8 @@ std::string write_json_model(const Forest& f) {
     for (size_t i = 0; i < t.size(); ++i) sidx[i] = t.deleted[i] ? 0xFFFFFFFFu : t.feature[i];
     put_array(o, "split_indices", sidx, fu);
     std::vector<uint8_t> stype(t.size(), 0);
-    put_array(o, "split_type", stype, fb);
+    for (size_t i = 0; i < t.size(); ++i) stype[i] = t.is_categorical(i) ? t.split_type[i] : 0;
+    put_array(o, "split_type", stype, [](std::string& s, uint8_t v) { s += std::to_string((int)v); });
     put_array(o, "sum_hessian", t.sum_hess, ff);
     int32_t num_deleted = 0;
     for (size_t i = 1; i < t.size(); ++i) num_deleted += t.deleted[i] ? 1 : 0;

@@ -355,5 +355,35 @@ int ohx_super_heads_cpu(const uint8_t* model, uint64_t model_len, uint32_t* out,
   }
 }
 
+// What emit_cat (flatten.hpp) makes of a booster with categorical splits, for the CPU test-suite, which walks these
+// arrays in Python the way the kernels of categorical.hip do: nodes = four 32-bit words per slot {bits, left, meta, size
+// as float bits}, words = the sets kept beside the nodes, orig_id per slot, roots per tree.  info[0] = slots, [1] =
+// words, [2] = trees, [3] = inline sets, [4] = sets in `words`; every array is written up to its cap (all caps 0: ask
+// for the sizes).  Placement with the default layout, as a booster is uploaded.
+int ohx_cat_flatten_cpu(const uint8_t* model, uint64_t model_len, uint32_t* nodes, uint64_t cap_slots, uint32_t* words,
+                        uint64_t cap_words, int32_t* orig_id, uint32_t* roots, uint64_t cap_trees, uint64_t* info) {
+  try {
+    Forest f = load_model_buffer(model, (size_t)model_len);
+    f.validate();
+    const Placement p = place_forest(f, LayoutParams());
+    const CatForest cf = emit_cat(f, p);
+    info[0] = cf.nodes.size();
+    info[1] = cf.words.size();
+    info[2] = p.roots.size();
+    info[3] = cf.inline_sets;
+    info[4] = cf.word_sets;
+    for (size_t i = 0; i < cf.nodes.size() && i < cap_slots; ++i) {
+      memcpy(nodes + 4 * i, &cf.nodes[i], 16);
+      orig_id[i] = cf.orig_id[i];
+    }
+    for (size_t i = 0; i < cf.words.size() && i < cap_words; ++i) words[i] = cf.words[i];
+    for (size_t i = 0; i < p.roots.size() && i < cap_trees; ++i) roots[i] = p.roots[i];
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
 }  // extern "C"
 #pragma GCC visibility pop

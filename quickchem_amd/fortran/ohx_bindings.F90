@@ -17,6 +17,7 @@ module ohx_bindings
    public :: XGBoosterPredict, XGBoosterSetParam, OHXBoosterPredictFields, OHXDMatrixSetGrid, OHXBoosterPredictContribs
    public :: OHXBoosterPredictInteractions, OHXBoosterPredictContribsFields, OHXBoosterPredictContribsFieldsDevice
    public :: OHXCommGetUniqueId, OHXCommInitRank, OHXCommFree, OHXCommInfo, OHXShardRows, OHXAllGatherOH, OHX_UNIQUE_ID_BYTES
+   public :: OHXBoosterGetNumCategoricalSplits
    public :: ohx_last_error, ohx_c_string
 
    integer, parameter :: OHX_UNIQUE_ID_BYTES = 128
@@ -187,6 +188,15 @@ module ohx_bindings
          integer(c_int), value     :: im, jm
          integer(c_int64_t), value :: row0
          integer(c_int)            :: rc
+      end function
+
+      ! Nodes of the loaded model with a categorical split (ohxgb.h); 0 for a booster without one.  A booster that has
+      ! some predicts through XGBoosterPredict only: the fields, contributions and Run1 forms refuse it.
+      function OHXBoosterGetNumCategoricalSplits(handle, out) bind(C, name="OHXBoosterGetNumCategoricalSplits") result(rc)
+         import :: c_int, c_ptr, c_int64_t
+         type(c_ptr), value              :: handle
+         integer(c_int64_t), intent(out) :: out
+         integer(c_int)                  :: rc
       end function
 
       ! ---- part 4 of ohxgb.h: the OH field reassembled on every GPU of a node, for a host that has MPI but no

@@ -72,6 +72,8 @@ def _load():
                                              C.c_int, C.c_uint, C.c_void_p]
         lib.ohx_interactions_table_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_interactions_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
+        lib.ohx_cat_flatten_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
+                                            C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         _lib = lib
     return _lib
 
@@ -146,6 +148,25 @@ def convert_model(image, fmt: str) -> np.ndarray:
     code = {"binary": 0, "json": 1, "ubj": 2}[fmt]
     _check(lib.ohx_model_convert(src.ctypes.data, src.nbytes, code, C.byref(out), C.byref(n)))
     return _take(out, n.value)
+
+
+def cat_flatten_cpu(image):
+    """What the flattening makes of a booster with categorical splits (csrc/flatten.hpp emit_cat), for tests that walk
+    it on the host: dict of nodes uint32 [slots][4] = {bits, left, meta, size as float bits}, words uint32, orig_id
+    int32 [slots], roots uint32 [trees], inline_sets, word_sets."""
+    lib = _load()
+    src = np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else image
+    info = (C.c_uint64 * 5)()
+    _check(lib.ohx_cat_flatten_cpu(src.ctypes.data, src.nbytes, None, 0, None, 0, None, None, 0, info))
+    slots, nwords, ntrees = int(info[0]), int(info[1]), int(info[2])
+    nodes = np.zeros((slots, 4), dtype=np.uint32)
+    words = np.zeros(max(nwords, 1), dtype=np.uint32)
+    orig_id = np.zeros(slots, dtype=np.int32)
+    roots = np.zeros(ntrees, dtype=np.uint32)
+    _check(lib.ohx_cat_flatten_cpu(src.ctypes.data, src.nbytes, nodes.ctypes.data, slots, words.ctypes.data, nwords,
+                                   orig_id.ctypes.data, roots.ctypes.data, ntrees, info))
+    return {"nodes": nodes, "words": words[:nwords], "orig_id": orig_id, "roots": roots,
+            "inline_sets": int(info[3]), "word_sets": int(info[4])}
 
 
 def super_walk_cpu(image, rows: np.ndarray, missing: float = XX_MISS):
