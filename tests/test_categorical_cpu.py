@@ -1,7 +1,9 @@
 """Boosters with categorical splits, what needs no GPU (docs/14_categorical.md): they load from JSON and UBJSON and save
 back to both, a booster without such a split is written byte for byte as before, everything Forest::validate refuses has
 its message, what such a booster cannot do yet is refused at the top of the call, the flattening walked in Python agrees
-with the restatement of the routing table, and categorical.hip cross-compiles to the code its design asks for."""
+with the restatement of the routing table, and categorical.hip cross-compiles to the code its design asks for.  The
+adversarial builder of tests/categorical_support.py covers what it promises, its sparse restatement is the dense one,
+its tie rows sit on the edges they name, and its boosters (the category 2**24 - 1 included) round-trip and flatten."""
 import ctypes as C
 import json
 import os
@@ -326,6 +328,184 @@ def test_the_flat_arrays_walked_in_python_agree_with_the_restatement(booster, mi
         got = walk_flat(flat, CS.base_of(js), X[:, :ncol], missing)
         assert np.array_equal(helpers.bits(got), helpers.bits(margins))
         assert np.array_equal(walk_flat(flat, CS.base_of(js), X[:, :ncol], missing, pred_leaf=True), leaves)
+
+
+# ---------------------------------------------------------------- the adversarial builder (tests/categorical_support.py)
+
+@pytest.fixture(scope="module")
+def adversarial():
+    return CS.make_adversarial(5150, 33, maxcat=True)
+
+
+def path_to(t, n):
+    par = {c: m for m in range(len(t.left)) if t.left[m] != -1 for c in (t.left[m], t.right[m])}
+    out = []
+    while n in par:
+        n = par[n]
+        out.append(n)
+    return out[::-1]
+
+
+def test_the_adversarial_builder_covers_what_it_promises(adversarial):
+    _, trees, cat_max = adversarial
+    assert {t.kind for t in trees} == set(CS.KINDS) | {"maxcat"}
+    assert {k for t in trees for k in t.setkind.values()} == set(CS.SET_KINDS) | {"maxcat"}
+    assert max(t.depth() for t in trees) == 30
+    for t in trees:
+        assert (t.kind == "leaf") == (len(t.left) == 1)
+        assert set(t.setkind) == set(t.cats)
+    # a root leaf in both positions of a pair, a depth-30 chain beside it
+    assert (trees[0].kind, trees[1].depth()) == ("leaf", 30) and (trees[2].depth(), trees[3].kind) == (30, "leaf")
+    for ntree, first, second in ((2, 0, 30), (3, 30, 0)):
+        _, small, _ = CS.make_adversarial(1, ntree)
+        assert (small[0].depth(), small[1].depth()) == (first, second)
+    _, one, _ = CS.make_adversarial(1, 1)
+    assert len(one) == 1 and one[0].depth() == 30
+    assert {len(CS.make_adversarial(1, n)[1]) & 1 for n in (1, 2, 3, 5, 10, 33)} == {0, 1}
+    # the set kinds are what their names say
+    for t in trees:
+        for n, kind in t.setkind.items():
+            c = t.cats[n]
+            if kind == "zero":
+                assert c == [0]
+            elif kind == "top":
+                assert len(c) == 1
+            elif kind == "full":
+                assert sorted(c) == list(range(max(c) + 1))
+            elif kind == "edges":
+                assert set(c) <= set(CS.WORD_EDGES)
+            elif kind == "repeated":
+                assert len(set(c)) < len(c)
+            elif kind == "maxcat":
+                assert max(c) == 2 ** 24 - 1 == CS.MAX_CATEGORY and len(c) > 1 and min(c) < 32
+    assert {t.cats[n][0] for t in trees for n, k in t.setkind.items() if k == "top"} >= {31, 32, 64, 1000}
+    assert any(t.cats[n] != sorted(t.cats[n]) for t in trees for n, k in t.setkind.items() if k == "repeated")
+    assert any(set(t.cats[n]) == set(CS.WORD_EDGES) for t in trees for n, k in t.setkind.items() if k == "edges")
+    # a chain alternates numeric and categorical splits of ONE feature, its thresholds integers or their neighbours
+    for t in trees:
+        if t.kind != "chain":
+            continue
+        inner = [n for n in range(len(t.left)) if t.left[n] != -1]
+        assert len({t.feat[n] for n in inner}) == 1 and {t.stype[n] for n in inner} == {0, 1}
+        for n in inner:
+            if t.stype[n] == 0:
+                c = np.float32(t.cond[n])
+                k = np.float32(np.round(c))
+                assert c in (k, np.nextafter(k, np.float32(np.inf)), np.nextafter(k, np.float32(-np.inf)))
+    assert {np.float32(t.cond[n]) == np.round(np.float32(t.cond[n])) for t in trees if t.kind == "chain"
+            for n in range(len(t.left)) if t.left[n] != -1 and t.stype[n] == 0} == {True, False}
+    # mixed capacity: on ONE path, one feature with a one-word set above a larger one and the reverse
+    orders = set()
+    for t in trees:
+        if t.kind != "mixed_capacity":
+            continue
+        deepest = max((n for n in range(len(t.left)) if t.left[n] != -1), key=lambda n: len(path_to(t, n)))
+        spine = path_to(t, deepest) + [deepest]
+        assert len({t.feat[n] for n in spine}) == 1 and all(t.stype[n] == 1 for n in spine)
+        caps = [CS.capacity(max(t.cats[n])) for n in spine]
+        assert len(set(caps)) >= 4
+        for a, b in zip(caps, caps[1:]):
+            if a != b:
+                orders.add((a == 32, b == 32))
+    assert {(True, False), (False, True)} <= orders
+    assert {t.dl[n] for t in trees for n in t.cats} == {0, 1}
+
+
+def test_category_tie_rows_sit_on_the_edges_they_name(adversarial):
+    _, trees, cat_max = adversarial
+    X = CS.category_tie_rows(np.random.default_rng(8), trees, 1500, cat_max)
+    assert X.dtype == np.float32 and not np.isnan(X).any() and not np.isinf(X).any()
+    cat_cols = X[:, sorted(cat_max)]
+    assert np.any((cat_cols == 0) & np.signbit(cat_cols))                           # -0.0
+    assert np.any(cat_cols == CS.DENORMAL) and np.any(cat_cols == -CS.DENORMAL)
+    frac = cat_cols[(cat_cols > 1) & (cat_cols != np.trunc(cat_cols))]
+    assert np.any(np.nextafter(frac, np.float32(np.inf)) == np.trunc(frac) + 1)     # just below an integer
+    sizes = {np.float32(CS.capacity(max(c))) for t in trees for c in t.cats.values()}
+    assert sizes >= {32.0, 64.0, 96.0, 1024.0, 2.0 ** 24}
+    for s in (np.float32(32), np.float32(64)):
+        assert np.any(cat_cols == s) and np.any(cat_cols == np.nextafter(s, np.float32(0))) and np.any(cat_cols == s - 1)
+
+
+def test_category_tie_rows_reach_the_last_level_of_every_spine():
+    """The rows the GPU tests use: the deepest node of each depth-30 chain and of each mixed-capacity spine is reached
+    by some row, both children of every stump, and at least a quarter of every tree's leaves."""
+    _, trees, cat_max = CS.make_adversarial(710, 10)
+    X = np.concatenate([CS.rows(10, 1200, cat_max, missing=-999.0),
+                        CS.category_tie_rows(np.random.default_rng(10), trees, 700, cat_max)])
+    _, leaves = CS.predict(trees, 0.0, X, walker=CS.walk_sparse)
+    for ti, t in enumerate(trees):
+        depth_of = {0: 0}
+        for n in range(len(t.left)):
+            if t.left[n] != -1:
+                depth_of[t.left[n]] = depth_of[t.right[n]] = depth_of[n] + 1
+        reached = np.unique(leaves[:, ti]).astype(int)
+        nleaf = sum(1 for n in range(len(t.left)) if t.left[n] == -1)
+        print("tree %d (%s, depth %d): %d of %d leaves reached" % (ti, t.kind, t.depth(), len(reached), nleaf))
+        if t.kind in ("chain", "mixed_capacity", "cat_stump"):
+            assert max(depth_of[n] for n in reached) == t.depth()
+        if t.kind == "cat_stump":
+            assert len(reached) == 2
+        assert 4 * len(reached) >= nleaf
+
+
+def test_the_sparse_restatement_is_the_dense_one(booster):
+    """walk_sparse keeps `walk`'s tests in their order and looks membership up in sorted keys: the same leaves on the
+    first builder's boosters (and on an adversarial one without the 2**24 - 1 node, whose dense table does not exist)."""
+    cases = [booster, CS.make_booster(2024, 12), CS.make_booster(31, 10, suffix=True), CS.make_adversarial(3, 10)]
+    for js, trees, cat_max in cases:
+        for missing in (np.nan, -999.0):
+            X = np.concatenate([CS.rows(21, 400, cat_max, missing=missing), CS.edge_rows(22, cat_max, missing=missing)])
+            for ncol in (CS.NFEAT, 9):
+                for t in trees:
+                    assert np.array_equal(CS.walk(t, X[:, :ncol], missing), CS.walk_sparse(t, X[:, :ncol], missing))
+            a = CS.predict(trees, CS.base_of(js), X, missing, 5)
+            b = CS.predict(trees, CS.base_of(js), X, missing, 5, walker=CS.walk_sparse)
+            assert np.array_equal(helpers.bits(a[0]), helpers.bits(b[0])) and np.array_equal(a[1], b[1])
+
+
+@pytest.mark.parametrize("missing", [np.nan, -999.0])
+def test_the_flat_arrays_walked_in_python_agree_on_the_adversarial_booster(adversarial, missing):
+    js, trees, cat_max = adversarial
+    flat = synth.cat_flatten_cpu(js)
+    assert flat["inline_sets"] + flat["word_sets"] == count_splits(trees)
+    want_words = sum(CS.capacity(max(c)) // 32 for t in trees for c in t.cats.values() if max(c) >= 32)
+    assert len(flat["words"]) == want_words >= 2 ** 19                               # the 2**24 - 1 node alone: 524 288
+    ties = CS.category_tie_rows(np.random.default_rng(4), trees, 400, cat_max)
+    X = np.concatenate([CS.rows(21, 150, cat_max, missing=missing), ties, CS.edge_rows(22, cat_max, missing=missing)])
+    X[:6, 1] = np.array([16777215, 16777214, 16777216, 8388607.5, 3e9, np.nan], dtype=np.float32)
+    for ncol in (CS.NFEAT, 9):
+        margins, leaves = CS.predict(trees, CS.base_of(js), X[:, :ncol], missing, walker=CS.walk_sparse)
+        got = walk_flat(flat, CS.base_of(js), X[:, :ncol], missing)
+        assert np.array_equal(helpers.bits(got), helpers.bits(margins))
+        assert np.array_equal(walk_flat(flat, CS.base_of(js), X[:, :ncol], missing, pred_leaf=True), leaves)
+
+
+def test_load_save_load_of_the_adversarial_booster(adversarial, tmp_path):
+    """JSON and UBJSON, the node with category 2**24 - 1 included; a list with repeated members comes back as the file
+    gave it (the writer writes what the reader read, not the set)."""
+    js, trees, cat_max = adversarial
+    want = document(js)["learner"]["gradient_booster"]["model"]["trees"]
+    assert any(2 ** 24 - 1 in t["categories"] for t in want)
+    assert any(len(set(c)) < len(c) for t in trees for c in t.cats.values())
+    images = {"json": synth.convert_model(js, "json"), "ubj": synth.convert_model(js, "ubj")}
+    first = document(images["json"])
+    for key in ("categories", "categories_nodes", "categories_segments", "categories_sizes", "split_type", "split_indices",
+                "default_left", "left_children", "right_children"):
+        for a, b in zip(first["learner"]["gradient_booster"]["model"]["trees"], want):
+            assert a[key] == b[key], key
+    for src in ("json", "ubj"):
+        for dst, suffix in (("json", ".json"), ("ubj", ".ubj")):
+            b = load(images[src])
+            assert b.num_categorical_splits() == count_splits(trees)
+            path = str(tmp_path / ("adv_" + src + suffix))
+            b.save_model(path)
+            saved = np.fromfile(path, dtype=np.uint8)
+            assert bytes(saved) == bytes(images[dst]), (src, dst)
+            back = capi.Booster(path)
+            assert back.num_categorical_splits() == count_splits(trees)
+            assert document(synth.convert_model(saved, "json")) == first
+            b.free()
+            back.free()
 
 
 def test_the_suffix_twin_is_a_numeric_model_that_routes_alike():
