@@ -784,8 +784,20 @@ bool use_tree_tops(const LaunchTuning& tune, double mean_steps) {
   return tune.tree_tops < 0 ? mean_steps >= kTreeTopsMinMeanSteps : tune.tree_tops != 0;
 }
 
+// the kind an "ohx_kernel" name stands for ("auto" is none: pick_kernel decides by the booster)
+bool kind_of_name(const std::string& k, KernelKind* out) {
+  for (KernelKind c : {KernelKind::Wide, KernelKind::Packed1, KernelKind::Packed2, KernelKind::Packed4, KernelKind::Super1,
+                       KernelKind::Super2, KernelKind::Super3, KernelKind::Super4, KernelKind::Ring})
+    if (k == kernel_kind_name(c)) {
+      *out = c;
+      return true;
+    }
+  return false;
+}
+
 bool wants_super(const std::string& k) {
-  return k == "auto" || k == "ring" || (k.size() == 6 && k.compare(0, 5, "super") == 0);
+  KernelKind kind;
+  return k == "auto" || (kind_of_name(k, &kind) && kind_is_super(kind));
 }
 
 void invalidate_device_state(BoosterObj& b) {
@@ -989,7 +1001,7 @@ void raise_flag_errors(BoosterObj& b, hipStream_t stream) {
 // `flags` = the first two words of d_flags as read back behind the work on `stream`, which the caller has waited for
 void judge_flags(BoosterObj& b, const uint32_t flags[2], hipStream_t stream) {
   // a ring block that timed out is not an error: its rows were walked again by the tile kernel on the stream, behind
-  // the train (kernels.hip launch_rows_ring); worth a line on stderr the first time, and a counter from then on
+  // the train (kernels.hip launch_ring_rerun); worth a line on stderr the first time, and a counter from then on
   if (flags[1] != b.ring_reruns_seen) {
     if (b.ring_reruns_seen == 0)
       fprintf(stderr, "[libohxgb] warning: a block of the ring kernel gave up waiting for another; the batch was predicted "
@@ -1220,14 +1232,8 @@ float* const kPlannedBuffer = reinterpret_cast<float*>((uintptr_t)256);
 void leaf_room(BoosterObj& b, uint64_t nrow, uint32_t ntree, LaunchTuning& tune, int im, int jm, uint64_t row0,
                bool plan_only = false) {
   if (tune.tree_split == 0 || !b.super_ok || nrow == 0 || nrow > (uint64_t)b.dev.num_cus * 10u * 64u + 4096u) return;
-  size_t tiles = (size_t)((nrow + 63) / 64);
-  if (im > 0 && jm > 0) {
-    TileShape probe;
-    if (tune.brick_li < 0) probe.set_grid_auto((uint32_t)im, (uint32_t)jm, row0, nrow);
-    else if (tune.brick_li + tune.brick_lj + tune.brick_lk == 6)
-      probe.set_grid((uint32_t)im, (uint32_t)jm, row0, nrow, (uint32_t)tune.brick_li, (uint32_t)tune.brick_lj, (uint32_t)tune.brick_lk);
-    if (probe.im != 0 && probe.ntiles(nrow) > tiles) tiles = (size_t)probe.ntiles(nrow);
-  }
+  // the launcher's shape (kernels.hpp pick_shape), or the consecutive rows it falls back to, whichever makes more tiles
+  const size_t tiles = (size_t)std::max(TileShape().ntiles(nrow), pick_shape(tune, im, jm, row0, nrow).ntiles(nrow));
   if (plan_only) {
     tune.leaf_buf = b.d_leaves.p != nullptr ? b.d_leaves.p : kPlannedBuffer;
     tune.leaf_words = std::max(b.d_leaves.n, tiles * 64 * (size_t)ntree);
@@ -1241,9 +1247,9 @@ void leaf_room(BoosterObj& b, uint64_t nrow, uint32_t ntree, LaunchTuning& tune,
 // What defer_prepare would say and hand out for this batch, touching nothing: not the pending read-back, not
 // defer_too_many, no allocation, no memset on any stream (the query used to do all four, the memset on NULL).
 bool defer_plan(const BoosterObj& b, uint64_t nrow, LaunchTuning& tune) {
-  if (tune.defer_missing == 0 || !(tune.defer_missing > 0 || nrow >= (1u << 18))) return false;
+  if (!DeferRule::wanted(tune, nrow)) return false;
   tune.defer_buf = b.d_defer.p != nullptr ? b.d_defer.p : reinterpret_cast<uint32_t*>(kPlannedBuffer);
-  tune.defer_words = std::max(b.d_defer.n, (size_t)(nrow / 32 + 1024 + 1));
+  tune.defer_words = std::max(b.d_defer.n, (size_t)DeferRule::defer_capacity(nrow) + 1);
   tune.defer_count_only = (b.defer_too_many && tune.defer_missing < 0) ? 1 : 0;
   return true;
 }
@@ -1270,15 +1276,16 @@ bool stream_capturing(hipStream_t stream) {
 }
 
 bool defer_prepare(BoosterObj& b, uint64_t nrow, LaunchTuning& tune, hipStream_t stream) {
-  if (tune.defer_missing == 0 || !(tune.defer_missing > 0 || nrow >= (1u << 18))) return false;
+  if (!DeferRule::wanted(tune, nrow)) return false;
+  const size_t words = (size_t)DeferRule::defer_capacity(nrow) + 1;      // the count, then the list
   const bool capturing = stream_capturing(stream);
   if (!capturing && b.defer_pending && hipEventQuery(b.defer_seen) == hipSuccess) {
     b.defer_pending = false;
     b.defer_too_many = (uint64_t)b.h_defer_count.p[0] * 50u > b.defer_last_nrow;        // more than 2 % of the rows
   }
   const uint32_t* before = b.d_defer.p;
-  if (capturing && b.d_defer.n < (size_t)(nrow / 32 + 1024 + 1)) refuse_in_capture("allocate the list of rows left to the second launch");
-  b.d_defer.ensure((size_t)(nrow / 32 + 1024 + 1));
+  if (capturing && b.d_defer.n < words) refuse_in_capture("allocate the list of rows left to the second launch");
+  b.d_defer.ensure(words);
   // the launchers zero the count only when they really defer (kernels.hip launch_predict: prefetch kernel, no split
   // ...); defer_look reads it back regardless, so a buffer fresh from hipMalloc must not hold garbage
   // on the stream the launches and defer_look's read-back run on: those streams are non-blocking, a NULL-stream memset
@@ -1298,6 +1305,26 @@ void defer_look(BoosterObj& b, uint64_t nrow, hipStream_t stream) {
   HIP_CHECK(hipEventRecord(b.defer_seen, stream));
   b.defer_pending = true;
   b.defer_last_nrow = nrow;
+}
+
+// A walk with what the booster lends it: room for the leaves of a small batch (`room`) and the list of the rows left to a
+// second launch (`may_defer`), then `launch(tune)`, then the look at how many rows were listed.  `im`, `jm`, `row0`: as leaf_room.
+template <class Launch>
+void walk_with_buffers(BoosterObj& b, uint64_t nrow, uint32_t ntree, LaunchTuning tune, int im, int jm, uint64_t row0, bool room,
+                       bool may_defer, hipStream_t stream, Launch launch) {
+  if (room) leaf_room(b, nrow, ntree, tune, im, jm, row0);
+  const bool deferring = may_defer && defer_prepare(b, nrow, tune, stream);
+  HIP_CHECK(launch(tune));
+  if (deferring) defer_look(b, nrow, stream);
+}
+
+// the booster's knobs and the grid the matrix's rows come from (kernels.hpp LaunchTuning::grid_im)
+LaunchTuning tune_for(const BoosterObj& b, const DMatrixObj& d) {
+  LaunchTuning tune = b.tune;
+  tune.grid_im = d.grid_im;
+  tune.grid_jm = d.grid_jm;
+  tune.grid_row0 = d.grid_row0;
+  return tune;
 }
 
 void launch_predict_groups(BoosterObj& b, DMatrixObj& d, int option_mask, unsigned ntree_limit, float* d_out,
@@ -1328,11 +1355,7 @@ void launch_predict_checked(BoosterObj& b, DMatrixObj& d, int option_mask, unsig
     c.out = d_out;
     c.pred_leaf = pred_leaf;
     c.flags = b.d_flags.p;
-    LaunchTuning tune = b.tune;
-    tune.grid_im = d.grid_im;
-    tune.grid_jm = d.grid_jm;
-    tune.grid_row0 = d.grid_row0;
-    HIP_CHECK(launch_predict_cat(device_cat_forest(b), c, b.dev.num_cus, b.cat_force_direct, stream, tune));
+    HIP_CHECK(launch_predict_cat(device_cat_forest(b), c, b.dev.num_cus, b.cat_force_direct, stream, tune_for(b, d)));
     return;
   }
   KernelKind kind = pick_kernel(b);
@@ -1353,16 +1376,13 @@ void launch_predict_checked(BoosterObj& b, DMatrixObj& d, int option_mask, unsig
   a.out = d_out;
   a.pred_leaf = pred_leaf;
   a.flags = b.d_flags.p;
-  LaunchTuning tune = b.tune;
-  tune.grid_im = d.grid_im;
-  tune.grid_jm = d.grid_jm;
-  tune.grid_row0 = d.grid_row0;
   a.perm = cluster_rows(b, d, a, pred_leaf, kind, stream);
-  if (!pred_leaf && a.perm == nullptr) leaf_room(b, d.nrow, a.tree_end - a.tree_begin, tune, tune.grid_im, tune.grid_jm, tune.grid_row0);
   // rows with missing values leave for a second, small launch instead of slowing their whole wave down (big batches)
-  const bool deferring = a.perm == nullptr && !pred_leaf && d.ncol == 27 && defer_prepare(b, d.nrow, tune, stream);
-  HIP_CHECK(launch_predict(kind, device_forest(b), a, b.dev.num_cus, stream, tune));
-  if (deferring) defer_look(b, d.nrow, stream);
+  const bool own_order = !pred_leaf && a.perm == nullptr;
+  walk_with_buffers(b, d.nrow, a.tree_end - a.tree_begin, tune_for(b, d), d.grid_im, d.grid_jm, d.grid_row0, own_order,
+                    own_order && d.ncol == 27, stream, [&](const LaunchTuning& tune) {
+                      return launch_predict(kind, device_forest(b), a, b.dev.num_cus, stream, tune);
+                    });
   if (a.perm != nullptr) {
     if (b.cluster_done == nullptr) HIP_CHECK(hipEventCreateWithFlags(&b.cluster_done, hipEventDisableTiming));
     HIP_CHECK(hipEventRecord(b.cluster_done, stream));
@@ -1401,10 +1421,7 @@ void launch_predict_groups(BoosterObj& b, DMatrixObj& d, int option_mask, unsign
   a.ncol = (uint32_t)d.ncol;
   a.missing = d.missing;
   a.flags = b.d_flags.p;
-  LaunchTuning tune = b.tune;
-  tune.grid_im = d.grid_im;
-  tune.grid_jm = d.grid_jm;
-  tune.grid_row0 = d.grid_row0;
+  LaunchTuning tune = tune_for(b, d);
   if (pred_leaf) {
     if (b.d_flat_of_file.p == nullptr && T != 0) {
       std::vector<uint32_t> flat_of_file(T);
@@ -1436,7 +1453,7 @@ void launch_predict_groups(BoosterObj& b, DMatrixObj& d, int option_mask, unsign
     a.tree_begin = b.group_begin[g];
     a.tree_end = a.tree_begin + cnt[g];
     a.out = plane;
-    LaunchTuning gt = tune;
+    LaunchTuning gt = tune;      // (not walk_with_buffers: the room above serves every group, the list is prepared per group)
     const bool deferring = a.perm == nullptr && d.ncol == 27 && defer_prepare(b, n, gt, stream);
     HIP_CHECK(launch_predict(kind, device_forest(b), a, b.dev.num_cus, stream, gt));
     if (deferring) defer_look(b, n, stream);
@@ -2002,8 +2019,8 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
   }
   BoosterObj* b = as_booster(handle);
   if (n == "ohx_kernel") {
-    if (v != "auto" && v != "wide" && v != "packed1" && v != "packed2" && v != "packed4" && v != "super1" &&
-        v != "super2" && v != "super3" && v != "super4" && v != "ring")
+    KernelKind named;
+    if (v != "auto" && !kind_of_name(v, &named))
       throw OhxError("ohx_kernel must be one of auto, wide, packed1, packed2, packed4, super1 .. super4, ring");
     if (v != b->kernel_name) invalidate_device_state(*b);
     b->kernel_name = v;
@@ -2294,12 +2311,10 @@ int OHXBoosterPredictFieldsDevice(BoosterHandle handle, const float* const d_fie
   if (pick_kernel(*b) == KernelKind::Wide) ensure_wide(*b);
   if (a.k2 >= a.k1) {
     const uint64_t nrow = (uint64_t)im * (uint64_t)jm * (uint64_t)(a.k2 - a.k1 + 1);
-    LaunchTuning tune = b->tune;
-    leaf_room(*b, nrow, a.tree_end - a.tree_begin, tune, im, jm, 0);
-    const bool deferring = nfield == 27 && defer_prepare(*b, nrow, tune, static_cast<hipStream_t>(stream));
-    HIP_CHECK(launch_predict_fields(pick_kernel(*b), device_forest(*b), a, b->dev.num_cus,
-                                    static_cast<hipStream_t>(stream), tune));
-    if (deferring) defer_look(*b, nrow, static_cast<hipStream_t>(stream));
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    walk_with_buffers(*b, nrow, a.tree_end - a.tree_begin, b->tune, im, jm, 0, true, nfield == 27, s, [&](const LaunchTuning& tune) {
+      return launch_predict_fields(pick_kernel(*b), device_forest(*b), a, b->dev.num_cus, s, tune);
+    });
   }
   API_END();
 }
@@ -2381,12 +2396,10 @@ int OHXBoosterPredictFields(BoosterHandle handle, const float* const fields[], c
     piece.k2 = a.k1 + (int)l1 - 1;
     // rows of this piece start at plane * l0 of the slab-ordered margin buffer
     piece.margin_out = margin_base ? const_cast<float*>(margin_base) + plane * l0 : nullptr;
-    LaunchTuning tune = b->tune;
-    const uint64_t piece_rows = plane * (l1 - l0);
-    leaf_room(*b, piece_rows, piece.tree_end - piece.tree_begin, tune, im, jm, 0);
-    const bool deferring = nfield == 27 && defer_prepare(*b, piece_rows, tune, b->s_exec);
-    HIP_CHECK(launch_predict_fields(pick_kernel(*b), device_forest(*b), piece, b->dev.num_cus, b->s_exec, tune));
-    if (deferring) defer_look(*b, piece_rows, b->s_exec);
+    walk_with_buffers(*b, plane * (l1 - l0), piece.tree_end - piece.tree_begin, b->tune, im, jm, 0, true, nfield == 27, b->s_exec,
+                      [&](const LaunchTuning& tune) {
+                        return launch_predict_fields(pick_kernel(*b), device_forest(*b), piece, b->dev.num_cus, b->s_exec, tune);
+                      });
   }
   if (one_launch) {
     HostMover back(b->s_exec, false);
@@ -2781,6 +2794,8 @@ static void run1_device(BoosterObj& b, const OHXRun1Args& r, hipStream_t stream,
       fa.out = oh_ml + first;
       fa.flags = b.d_flags.p;
       const uint64_t slab_rows = (uint64_t)r.im * (uint64_t)jq * (uint64_t)(k2 - k1 + 1);
+      // (not walk_with_buffers: the gated wait for the walk's inputs sits between the list's set-up and the launch, and only
+      // the last piece's count is looked at)
       LaunchTuning tune = b.tune;
       leaf_room(b, slab_rows, fa.tree_end - fa.tree_begin, tune, r.im, jq, 0);
       const bool deferring = defer_prepare(b, slab_rows, tune, stream);
@@ -3304,10 +3319,7 @@ int OHXBoosterKernelSymbolRows(BoosterHandle handle, DMatrixHandle dmat, const c
   a.ncol = (uint32_t)d->ncol;
   a.missing = d->missing;
   tree_range(*b, 0, &a.tree_begin, &a.tree_end);
-  LaunchTuning tune = b->tune;
-  tune.grid_im = d->grid_im;
-  tune.grid_jm = d->grid_jm;
-  tune.grid_row0 = d->grid_row0;
+  LaunchTuning tune = tune_for(*b, *d);
   leaf_room(*b, d->nrow, a.tree_end - a.tree_begin, tune, tune.grid_im, tune.grid_jm, tune.grid_row0, /*plan_only=*/true);
   if (d->ncol == 27) (void)defer_plan(*b, d->nrow, tune);
   b->symbol = predict_kernel_symbols_rows(pick_kernel(*b), device_forest(*b), a, b->dev.num_cus, tune);

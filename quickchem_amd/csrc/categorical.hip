@@ -226,16 +226,9 @@ hipError_t launch_predict_cat(const DeviceCatForest& fr, const CatPredictArgs& a
                               hipStream_t stream, const LaunchTuning& tune) {
   CatPredictArgs a = args;
   // which rows a wave takes: bricks when the caller named the grid the rows come from, as the walk kernels do
-  // (kernels.hip shape_rows); not when most bricks would hold no row, or were too many to number in 32 bits
-  a.shape = TileShape();
-  if (tune.grid_im > 0 && tune.grid_jm > 0 && a.nrow > 0 &&
-      (tune.brick_li < 0 || tune.brick_li + tune.brick_lj + tune.brick_lk == 6)) {
-    if (tune.brick_li < 0) a.shape.set_grid_auto((uint32_t)tune.grid_im, (uint32_t)tune.grid_jm, tune.grid_row0, a.nrow);
-    else a.shape.set_grid((uint32_t)tune.grid_im, (uint32_t)tune.grid_jm, tune.grid_row0, a.nrow, (uint32_t)tune.brick_li,
-                          (uint32_t)tune.brick_lj, (uint32_t)tune.brick_lk);
-    a.shape.k_fastest = (uint32_t)tune.brick_k_fastest;
-    if (a.shape.ntiles(a.nrow) >= 0xFFFFFFFFull || a.shape.live_tiles() * 2 < a.shape.ntiles(a.nrow)) a.shape = TileShape();
-  }
+  // (kernels.hpp pick_shape); not when most bricks would hold no row
+  a.shape = pick_shape(tune, tune.grid_im, tune.grid_jm, tune.grid_row0, a.nrow);
+  if (a.shape.im != 0 && a.shape.live_tiles() * 2 < a.shape.ntiles(a.nrow)) a.shape = TileShape();
   a.ntiles = a.shape.ntiles(a.nrow);
   if (a.nrow == 0 || (a.pred_leaf && a.tree_end == a.tree_begin)) return hipSuccess;
   if (a.tree_end < a.tree_begin || a.tree_end > fr.num_trees || a.ncol > fr.num_feature) return hipErrorInvalidValue;

@@ -800,7 +800,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CHAINS >
   // noalias: with the margins' stores provably elsewhere, the wave-uniform head records stay scalar
   // loads (as members of the by-value structs they turn into one more vector load per walk)
   extern __shared__ float lds[];
-  // the launch behind a ring train (launch_rows_ring): nothing to do unless a block of that train gave up
+  // the launch behind a ring train (launch_ring_rerun): nothing to do unless a block of that train gave up
   if (a.only_if_train != 0u) {
     if (__hip_atomic_load(a.flags + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != a.only_if_train) return;
     if (blockIdx.x == 0 && threadIdx.x == 0) atomicAdd(a.flags + 1, 1u);
@@ -2037,82 +2037,96 @@ struct TrainCursor {
   }
 };
 
-// which rows a wave takes: bricks when the caller named the grid the rows come from
-void shape_rows(PredictArgs& a, const LaunchTuning& tune) {
-  if (a.perm == nullptr && tune.grid_im > 0 && tune.grid_jm > 0 && a.nrow > 0 &&
-      (tune.brick_li < 0 || tune.brick_li + tune.brick_lj + tune.brick_lk == 6)) {
-    if (tune.brick_li < 0) a.shape.set_grid_auto((uint32_t)tune.grid_im, (uint32_t)tune.grid_jm, tune.grid_row0, a.nrow);
-    else a.shape.set_grid((uint32_t)tune.grid_im, (uint32_t)tune.grid_jm, tune.grid_row0, a.nrow, (uint32_t)tune.brick_li,
-                          (uint32_t)tune.brick_lj, (uint32_t)tune.brick_lk);
-    a.shape.k_fastest = (uint32_t)tune.brick_k_fastest;
-  }
-  if (a.shape.ntiles(a.nrow) >= 0xFFFFFFFFull) a.shape = TileShape();   // tile_row numbers bricks in 32 bits
+// ------------------------------------------------------------------ launch pieces
+// What a walk launches is decided once, in plan_rows / plan_fields below; the launchers and the symbol functions read
+// the WalkPlan and decide nothing themselves (docs/05_kernels.md has the table).  The pieces a plan is launched with
+// are written once for both families: the argument structs name the members they use identically.
+
+using RowsKernel = void (*)(DeviceForest, PredictArgs, const SuperTreeHead*, float*);
+using FieldsKernel = void (*)(DeviceForest, FieldsArgs, const SuperTreeHead*, float*, float*);
+
+// `heads` and the outputs are kernel arguments of their own (noalias: predict_rows_tile_kernel)
+void launch_walk(RowsKernel kernel, uint64_t grid, unsigned threads, size_t lds, hipStream_t stream, const DeviceForest& fr,
+                 const PredictArgs& a) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, stream, fr, a, fr.super_heads, a.out);
+}
+void launch_walk(FieldsKernel kernel, uint64_t grid, unsigned threads, size_t lds, hipStream_t stream, const DeviceForest& fr,
+                 const FieldsArgs& a) {
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(threads), lds, stream, fr, a, fr.super_heads, a.out, a.margin_out);
+}
+void launch_combine(unsigned grid, hipStream_t stream, const DeviceForest& fr, const PredictArgs& a) {
+  hipLaunchKernelGGL(combine_leaves_kernel, dim3(grid), dim3(kBlock), 0, stream, a, fr.base_score, a.out);
+}
+void launch_combine(unsigned grid, hipStream_t stream, const DeviceForest& fr, const FieldsArgs& a) {
+  hipLaunchKernelGGL(combine_leaves_fields_kernel, dim3(grid), dim3(kBlock), 0, stream, a, fr.base_score, a.out, a.margin_out);
 }
 
-// A small batch: the trees in `split` runs, a wave per (run, tile), then the launch that sums the leaves in tree order.
-template <class K>
-hipError_t launch_rows_split(K kernel, size_t lds, const DeviceForest& fr, PredictArgs a, int num_cus, hipStream_t stream,
-                             const LaunchTuning& tune, uint32_t split) {
-  hipError_t e = ensure_lds(kernel, lds);
-  if (e != hipSuccess) return e;
-  a.xcd_remap = tune.xcd_remap;
-  a.run_log = 0;
-  a.run_lo_bits = 0;
-  a.tile_begin = 0;
-  a.tile_end = a.shape.ntiles(a.nrow);
-  a.leaf_buf = tune.leaf_buf;
-  a.tree_split = split;
-  const int grid = tile_grid(kernel, lds, a.tile_end * split, num_cus);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, stream, fr, a, fr.super_heads, a.out);
-  const uint64_t blocks = (a.tile_end + kWavesPerBlock - 1) / kWavesPerBlock;
-  hipLaunchKernelGGL(combine_leaves_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, stream, a,
-                     fr.base_score, a.out);
-  return hipGetLastError();
-}
-
-// One launch, or a train of launches of one residency (grid x 4 tiles) each.
-template <class K>
-hipError_t launch_rows_tiled(K kernel, size_t lds, const DeviceForest& fr, PredictArgs a, int num_cus,
-                             hipStream_t stream, const LaunchTuning& tune) {
-  lds += (size_t)tune.lds_pad;
-  hipError_t e = ensure_lds(kernel, lds);
-  if (e != hipSuccess) return e;
-  shape_rows(a, tune);
-  const uint64_t ntiles = a.shape.ntiles(a.nrow);
-  const int grid = tile_grid(kernel, lds, ntiles, num_cus);
-  a.xcd_remap = tune.xcd_remap;
-  // runs of consecutive rows inside a tile (load_pieces): a brick's cells along i, or all 64 rows without a grid
-  a.run_log = 0;
-  a.run_lo_bits = 0;
-  if (tune.coop_rows && a.perm == nullptr && a.ncol == 27) {
-    if (a.shape.im == 0) {
-      a.run_log = 6;
-    } else if (a.shape.li >= 2) {
-      a.run_log = a.shape.li;
-      a.run_lo_bits = a.shape.k_fastest ? a.shape.lk : 0u;
-    }
-  }
-  if (tune.launches_per_residency <= 0) {
-    a.tile_begin = 0;
-    a.tile_end = ntiles;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, stream, fr, a, fr.super_heads, a.out);
-    return hipGetLastError();
-  }
-  const uint64_t per_launch = (uint64_t)grid * kWavesPerBlock * (uint64_t)tune.launches_per_residency;
+// One launch (per_launch >= ntiles), or a train of launches of `per_launch` tiles each: `grid` blocks of `threads` at most.
+template <class K, class Args>
+hipError_t launch_train(K kernel, unsigned threads, size_t lds, uint64_t grid, uint64_t ntiles, uint64_t per_launch,
+                        hipStream_t stream, const LaunchTuning& tune, const DeviceForest& fr, Args a) {
+  const uint64_t waves = threads / kWave;
   TrainCursor train(stream, tune);
   for (uint64_t t0 = 0; t0 < ntiles; t0 += per_launch) {
     a.tile_begin = t0;
     a.tile_end = t0 + per_launch < ntiles ? t0 + per_launch : ntiles;
-    const uint64_t blocks = (a.tile_end - a.tile_begin + kWavesPerBlock - 1) / kWavesPerBlock;
+    const uint64_t blocks = (a.tile_end - a.tile_begin + waves - 1) / waves;
     hipStream_t s;
-    e = train.next(&s);
+    hipError_t e = train.next(&s);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks < (uint64_t)grid ? blocks : (uint64_t)grid)), dim3(kBlock), lds,
-                       s, fr, a, fr.super_heads, a.out);
+    launch_walk(kernel, blocks < grid ? blocks : grid, threads, lds, s, fr, a);
   }
-  e = train.meet();
+  return train.meet();
+}
+
+// A ring block that gave up waiting has not written its rows, and says so by writing this train's id to flags[2].
+// Behind the train: the tile kernel `again` over ALL of the train's rows, every block of which leaves at once unless it
+// finds that id there (5 us per step when it does not), missing-aware and without deferring; its first block counts the
+// event.  Stream-ordered, so the device forms need no host in the loop (include/ohxgb.h: OHXBoosterRingReruns).
+template <class K, class Args>
+hipError_t launch_ring_rerun(K again, size_t lds, const DeviceForest& fr, Args b, uint64_t ntiles, int num_cus, hipStream_t stream) {
+  hipError_t e = ensure_lds(again, lds);
   if (e != hipSuccess) return e;
-  return hipGetLastError();
+  b.only_if_train = b.train_id;
+  b.defer_list = nullptr;
+  b.defer_count = nullptr;
+  b.defer_cap = 0;
+  b.tile_begin = 0;
+  b.tile_end = ntiles;
+  launch_walk(again, tile_grid(again, lds, ntiles, num_cus), kBlock, lds, stream, fr, b);
+  return hipSuccess;
+}
+
+// The second launch of a deferred-rows call: the rows of the list, 64 per wave, each lane its own row, missing-aware.
+template <class K, class Args>
+hipError_t launch_deferred(K kernel, size_t lds, const DeviceForest& fr, Args a, int num_cus, hipStream_t stream) {
+  hipError_t e = ensure_lds(kernel, lds);
+  if (e != hipSuccess) return e;
+  a.perm = a.defer_list;
+  a.perm_count = a.defer_count;
+  a.perm_slots = a.defer_cap;
+  a.defer_list = nullptr;
+  a.defer_count = nullptr;
+  a.tile_begin = 0;
+  a.tile_end = ((uint64_t)a.defer_cap + kWave - 1) / kWave;
+  launch_walk(kernel, tile_grid(kernel, lds, a.tile_end, num_cus), kBlock, lds, stream, fr, a);
+  return hipSuccess;
+}
+
+// A small batch or slab: the trees in `split` runs, a wave per (run, tile), then the launch that sums the leaves in tree order.
+template <class K, class Args>
+hipError_t launch_split(K kernel, size_t lds, const DeviceForest& fr, Args a, uint64_t ntiles, int num_cus, hipStream_t stream,
+                        const LaunchTuning& tune, uint32_t split) {
+  hipError_t e = ensure_lds(kernel, lds);
+  if (e != hipSuccess) return e;
+  a.tile_begin = 0;
+  a.tile_end = ntiles;
+  a.leaf_buf = tune.leaf_buf;
+  a.tree_split = split;
+  launch_walk(kernel, tile_grid(kernel, lds, ntiles * split, num_cus), kBlock, lds, stream, fr, a);
+  const uint64_t blocks = (ntiles + kWavesPerBlock - 1) / kWavesPerBlock;
+  launch_combine((unsigned)(blocks < 8192 ? blocks : 8192), stream, fr, a);
+  return hipSuccess;
 }
 
 // ids of ring launch trains, process-wide, never 0 (PredictArgs::train_id)
@@ -2123,93 +2137,266 @@ uint32_t next_train_id() {
   return id;
 }
 
-// The train of launches of predict_rows_ring_kernel: one 1 024-thread block per CU, `ring_rounds` tiles per wave
-// and launch (the waves of a block walk the same trees by construction; what a launch boundary still buys is that the
-// blocks of an XCD start on tree 0 together).
-hipError_t launch_rows_ring(const DeviceForest& fr, PredictArgs a, int num_cus, hipStream_t stream, const LaunchTuning& tune) {
-  hipError_t e = ensure_lds(predict_rows_ring_kernel, kRingLdsBytes);
-  if (e != hipSuccess) return e;
-  shape_rows(a, tune);
-  const uint64_t ntiles = a.shape.ntiles(a.nrow);
-  uint64_t grid = (ntiles + kRingWaves - 1) / kRingWaves;
-  const uint64_t cus = tune.reserve_cus > 0 && tune.reserve_cus < num_cus ? (uint64_t)(num_cus - tune.reserve_cus) : (uint64_t)num_cus;
-  if (grid > cus) grid = cus;
+// ------------------------------------------------------------------ the plan
+
+// runs of consecutive rows inside a tile that a wave fetches together (load_pieces; 27-column rows only): a brick's
+// cells along i, or all 64 rows without a grid
+struct CoopRuns {
+  uint32_t run_log = 0, run_lo_bits = 0;
+};
+CoopRuns coop_runs(const TileShape& shape, const LaunchTuning& tune, bool permuted, uint32_t ncol) {
+  CoopRuns r;
+  if (!tune.coop_rows || permuted || ncol != 27) return r;
+  if (shape.im == 0) {
+    r.run_log = 6;
+  } else if (shape.li >= 2) {
+    r.run_log = shape.li;
+    r.run_lo_bits = shape.k_fastest ? shape.lk : 0u;
+  }
+  return r;
+}
+void set_runs(PredictArgs& a, const CoopRuns& r) {
+  a.run_log = r.run_log;
+  a.run_lo_bits = r.run_lo_bits;
+}
+void set_runs(FieldsArgs&, const CoopRuns&) {}      // (the fields kernels gather cell by cell)
+
+// A small batch or slab leaves most of the chip's wave slots empty and takes as long as one tile's walk of ALL trees
+// (165 us for the OH booster whatever N, profiles/r03_latency_rows.json): its trees are cut into runs walked by
+// different waves.  Decided on the live tiles of `*shape` against the chip's 20 wave slots per CU: at most 10 runs, of
+// at least 4 trees each, and only with room for every leaf in the booster's leaf buffer.  Returns the runs, 0 = no split.
+// `rows_if_sparse` is what the rows form does and the fields form does not: bricks laid over a level of which the batch
+// holds a small part are mostly empty, and *shape becomes 64 consecutive rows per wave when the trees are split (a
+// slab of fields is whole levels, every brick of which is live).
+uint32_t tree_split_for(const LaunchTuning& tune, uint64_t nrow, uint32_t ntree, int num_cus, bool rows_if_sparse, TileShape* shape) {
+  if (tune.tree_split == 0 || tune.leaf_buf == nullptr || ntree < 8) return 0;
+  TileShape sh = *shape;
+  if (rows_if_sparse && sh.im != 0 && sh.live_tiles() * 2 < sh.ntiles(nrow)) sh = TileShape();
+  const uint64_t ntiles = sh.ntiles(nrow);
+  const uint64_t live = sh.im != 0 && sh.live_tiles() < ntiles ? sh.live_tiles() : ntiles;
+  const uint64_t slots = (uint64_t)num_cus * 20u;
+  uint64_t want = tune.tree_split > 1 ? (uint64_t)tune.tree_split : (live * 2 <= slots ? slots / (live ? live : 1) : 0);
+  if (want > 10) want = 10;
+  if (want * 4 > ntree) want = ntree / 4;
+  if (want < 2 || ntiles * ntree * kWave > tune.leaf_words) return 0;
+  *shape = sh;
+  return (uint32_t)want;
+}
+
+// ring kernels: one block per CU, less the CUs left free for a collective's kernels (LaunchTuning::reserve_cus)
+uint64_t ring_cus(const LaunchTuning& tune, int num_cus) {
+  return tune.reserve_cus > 0 && tune.reserve_cus < num_cus ? (uint64_t)(num_cus - tune.reserve_cus) : (uint64_t)num_cus;
+}
+
+struct WalkPlan {
+  enum How { Direct, Tile, Split, Ring };
+  bool ok = true;           // false: the forest has no array this kind of kernel could read
+  How how = Tile;           // predict_rows_direct_kernel (wide nodes, no LDS; rows only) / a tile kernel / a tile kernel over
+                            // runs of trees and the combine kernel / a ring kernel
+  // Tile, Split: the tile kernel's template arguments (pf = PREFETCH27: 27-column rows, the next tile's in flight during
+  // a walk; rows only).  The deferred rows' launch takes the same kernel without pf.  The ring kernels have no
+  // arguments, and the tile kernels of the launches behind a ring train are fixed (rows_ring_rerun_kernel,
+  // rows_ring_deferred_kernel, fields_ring_later_kernel).
+  int fmt = 2, chains = 2;
+  bool tops = false, pf = false;
+  size_t lds = 0;           // of the first launch or train
+  size_t lds_tile = 0;      // of a tile kernel behind it (tile_lds_bytes)
+  TileShape shape;
+  CoopRuns runs;
+  uint32_t split = 0;       // Split: runs of trees
+  bool defer = false, listing = false;      // rows with missing values counted / left to a second launch
+  uint32_t defer_cap = 0;
+  int rounds = 0;           // Tile, Ring: tiles per wave and launch of the train (<= 0: one launch)
+  uint64_t cus = 0;         // Ring: blocks at most
+};
+
+// rows with missing values are left to a second launch (PredictArgs::defer_list) where the form allows it
+void plan_defer(WalkPlan& p, bool allowed, const LaunchTuning& tune, uint64_t nrow) {
+  p.defer = allowed && tune.defer_buf != nullptr && tune.defer_words >= 2 && nrow < 0xFFFFFFF0ull && DeferRule::wanted(tune, nrow);
+  p.listing = p.defer && !tune.defer_count_only;
+  const uint64_t want = DeferRule::defer_capacity(nrow);
+  p.defer_cap = p.listing ? (uint32_t)(want < tune.defer_words - 1 ? want : tune.defer_words - 1) : 0u;
+}
+
+void plan_kind(WalkPlan& p, KernelKind kind, const DeviceForest& fr) {
+  const bool is_super = kind_is_super(kind);
+  p.fmt = is_super ? 2 : 1;
+  p.chains = kind_chains(kind);
+  p.tops = is_super && fr.tree_tops;
+  p.lds = p.lds_tile = tile_lds_bytes(fr.num_feature, is_super);
+  if (is_super && fr.super == nullptr) p.ok = false;
+}
+
+WalkPlan plan_rows(KernelKind kind, const DeviceForest& fr, const PredictArgs& a, int num_cus, const LaunchTuning& tune) {
+  WalkPlan p;
+  plan_kind(p, kind, fr);
+  const bool tile_ok = fr.num_feature >= 1 && p.lds <= 160 * 1024 && a.ncol <= fr.num_feature;
+  if (a.pred_leaf || kind == KernelKind::Wide || !tile_ok || (p.fmt == 1 && fr.packed == nullptr)) {
+    p.how = WalkPlan::Direct;
+    return p;
+  }
+  // every wave gets more than one tile per launch and the rows are the OH shape: prefetch
+  p.pf = a.ncol == 27 && fr.num_feature == 27 && tune.launches_per_residency != 1 && tune.prefetch;
+  plan_defer(p, p.pf && a.perm == nullptr, tune, a.nrow);
+  // bricks when the caller named the grid the rows come from; rows grouped by the clustering pass come as they are listed
+  if (a.perm == nullptr) p.shape = pick_shape(tune, tune.grid_im, tune.grid_jm, tune.grid_row0, a.nrow);
+  if (p.fmt == 2 && a.perm == nullptr)
+    p.split = tree_split_for(tune, a.nrow, a.tree_end - a.tree_begin, num_cus, /*rows_if_sparse=*/true, &p.shape);
+  if (p.split) {      // (the list is still set up, as it has been; nothing is listed and no second launch follows)
+    p.how = WalkPlan::Split;
+    p.pf = false;
+    return p;
+  }
+  p.runs = coop_runs(p.shape, tune, a.perm != nullptr, a.ncol);
+  // the ring kernel takes the OH shape with the next rows in flight (a big batch); everything else of a booster
+  // that asked for it - small batches with their trees split over waves, other column counts, the second launch of
+  // the deferred rows - goes the super2 way
+  if (kind == KernelKind::Ring && p.pf && a.tree_end > a.tree_begin) {
+    p.how = WalkPlan::Ring;
+    p.lds = kRingLdsBytes;
+    p.cus = ring_cus(tune, num_cus);
+    // rows that are not known to be neighbours on a grid (no hint and no level size found, or rows that come through the
+    // clustering pass's permutation) keep the short launches: what their lanes ask for has little in common, the XCD's L2
+    // is all they share, and it only holds while the blocks walk the same trees - shuffled C360 rows 47.2 ms at 16 rounds,
+    // 50.3 at 64 (without the clustering pass 84 against 125); rows on a grid 24.28 / 24.13 (profiles/r04_sweeps.txt)
+    // (through the permutation: 47.4 ms at 16, 45.9 at 4; 64 consecutive rows per wave: 34.05 at 16, 34.5 at 4)
+    p.rounds = tune.ring_rounds;
+    const int no_grid = a.perm != nullptr ? kRingRoundsPermuted : kRingRoundsNoGrid;
+    if (p.shape.im == 0 && (p.rounds <= 0 || p.rounds > no_grid)) p.rounds = no_grid;      // (0 = one launch: for rows on a grid only)
+    return p;
+  }
+  p.lds += (size_t)tune.lds_pad;
+  p.rounds = tune.launches_per_residency;
+  return p;
+}
+
+WalkPlan plan_fields(KernelKind kind, const DeviceForest& fr, const FieldsArgs& a, uint64_t nrow, int num_cus, const LaunchTuning& tune) {
+  WalkPlan p;
+  plan_kind(p, kind, fr);
+  if (fr.num_feature < 1 || p.lds > 160 * 1024) p.ok = false;
+  if (kind == KernelKind::Wide || (p.fmt == 1 && fr.packed == nullptr)) {
+    p.fmt = 0;
+    p.chains = 1;
+    if (fr.wide == nullptr) p.ok = false;
+  }
+  if (!p.ok) return p;
+  p.shape = pick_shape(tune, a.im, a.jm, 0, nrow);
+  p.rounds = tune.launches_per_residency;
+  // A small slab - a GEOS rank's block: as small row batches
+  if (p.fmt == 2) p.split = tree_split_for(tune, nrow, a.tree_end - a.tree_begin, num_cus, /*rows_if_sparse=*/false, &p.shape);
+  if (p.split) {
+    // (as it has been: super1 and super4 walk without tree tops here, and every other kind walks 2 chains)
+    p.how = WalkPlan::Split;
+    if (kind == KernelKind::Super1 || kind == KernelKind::Super4) p.tops = false;
+    else p.chains = 2;
+    return p;
+  }
+  plan_defer(p, fr.num_feature == 27, tune, nrow);
+  // the ring kernel for slabs that fill the chip at least twice; smaller ones (a rank-sized block) the super2 way:
+  // a block of the ring kernel is 16 tiles that wait for each other's trees
+  if (kind == KernelKind::Ring && fr.num_feature == 27 && a.tree_end > a.tree_begin &&
+      nrow >= (uint64_t)num_cus * kRingWaves * kWave * 2u) {
+    p.how = WalkPlan::Ring;
+    p.lds = kRingLdsBytes;
+    p.cus = ring_cus(tune, num_cus);
+    p.rounds = tune.ring_rounds;
+  }
+  return p;
+}
+
+// ------------------------------------------------------------------ the kernels of a plan
+// One list per family from (FMT, CHAINS, TOPS) to the kernel.  The lists, and the functions around them, stand in the
+// order in which the code object has held its kernels so far: it holds them in the order in which this file first
+// names them, and two builds' device code can only be compared text for text while that order stays.
+
+RowsKernel rows_ring_rerun_kernel() { return predict_rows_tile_kernel<2, 2, true, true>; }
+
+hipError_t launch_rows_direct(const DeviceForest& fr, const PredictArgs& a, int num_cus, hipStream_t stream) {
+  if (fr.wide == nullptr) return hipErrorInvalidValue;
+  const int grid = grid_for(a.nrow, num_cus, 8);
+  if (a.pred_leaf) hipLaunchKernelGGL(predict_rows_direct_kernel<true>, dim3(grid), dim3(kBlock), 0, stream, fr, a);
+  else hipLaunchKernelGGL(predict_rows_direct_kernel<false>, dim3(grid), dim3(kBlock), 0, stream, fr, a);
+  return hipGetLastError();
+}
+
+RowsKernel rows_ring_deferred_kernel() { return predict_rows_tile_kernel<2, 2, false, true>; }
+
+RowsKernel rows_tile_kernel(int fmt, int chains, bool tops, bool pf) {
+#define OHX_WALK(FMT, CH, TOPS)                                           \
+  if (fmt == FMT && chains == CH && tops == TOPS) {                       \
+    if (!pf) return predict_rows_tile_kernel<FMT, CH, false, TOPS>;       \
+    return predict_rows_tile_kernel<FMT, CH, true, TOPS>;                 \
+  }
+  OHX_WALK(1, 1, false) OHX_WALK(1, 2, false) OHX_WALK(1, 4, false)
+  OHX_WALK(2, 1, true) OHX_WALK(2, 1, false) OHX_WALK(2, 3, true) OHX_WALK(2, 3, false)
+  OHX_WALK(2, 4, true) OHX_WALK(2, 4, false) OHX_WALK(2, 2, true) OHX_WALK(2, 2, false)
+#undef OHX_WALK
+  return nullptr;      // no such walk: an error at the launch
+}
+
+FieldsKernel fields_tile_kernel(int fmt, int chains, bool tops) {
+#define OHX_WALK(FMT, CH, TOPS) \
+  if (fmt == FMT && chains == CH && tops == TOPS) return predict_fields_kernel<FMT, CH, TOPS>;
+  OHX_WALK(0, 1, false) OHX_WALK(2, 1, false) OHX_WALK(2, 4, false) OHX_WALK(2, 2, true) OHX_WALK(2, 2, false)
+  OHX_WALK(1, 1, false) OHX_WALK(1, 2, false) OHX_WALK(1, 4, false)
+  OHX_WALK(2, 1, true) OHX_WALK(2, 3, true) OHX_WALK(2, 3, false) OHX_WALK(2, 4, true)
+#undef OHX_WALK
+  return nullptr;
+}
+
+// behind a ring train of fields, both the launch after a time-out and the deferred rows' launch
+FieldsKernel fields_ring_later_kernel() { return predict_fields_kernel<2, 2, true>; }
+
+// ------------------------------------------------------------------ a plan's launches
+
+// `first`: the plan's tile or ring kernel; `rerun`: the launch behind a ring train (launch_ring_rerun); `second`: the
+// deferred rows' launch.  `a` comes with everything but what the plan decides.
+template <class K, class Args>
+hipError_t launch_plan(const WalkPlan& p, K first, K rerun, K second, const DeviceForest& fr, Args a, uint64_t nrow, int num_cus,
+                       hipStream_t stream, const LaunchTuning& tune) {
+  if (first == nullptr || rerun == nullptr || second == nullptr) return hipErrorInvalidValue;
+  a.shape = p.shape;
   a.xcd_remap = tune.xcd_remap;
-  a.run_log = 0;
-  a.run_lo_bits = 0;
-  if (tune.coop_rows && a.perm == nullptr && a.ncol == 27) {
-    if (a.shape.im == 0) {
-      a.run_log = 6;
-    } else if (a.shape.li >= 2) {
-      a.run_log = a.shape.li;
-      a.run_lo_bits = a.shape.k_fastest ? a.shape.lk : 0u;
-    }
-  }
-  // rows that are not known to be neighbours on a grid (no hint and no level size found, or rows that come through the
-  // clustering pass's permutation) keep the short launches: what their lanes ask for has little in common, the XCD's L2
-  // is all they share, and it only holds while the blocks walk the same trees - shuffled C360 rows 47.2 ms at 16 rounds,
-  // 50.3 at 64 (without the clustering pass 84 against 125); rows on a grid 24.28 / 24.13 (profiles/r04_sweeps.txt)
-  // (through the permutation: 47.4 ms at 16, 45.9 at 4; 64 consecutive rows per wave: 34.05 at 16, 34.5 at 4)
-  int rounds = tune.ring_rounds;
-  const int no_grid = a.perm != nullptr ? kRingRoundsPermuted : kRingRoundsNoGrid;
-  if (a.shape.im == 0 && (rounds <= 0 || rounds > no_grid)) rounds = no_grid;      // (0 = one launch: for rows on a grid only)
-  const uint64_t per_launch = rounds <= 0 ? ntiles : grid * kRingWaves * (uint64_t)rounds;
-  a.train_id = next_train_id();
-  TrainCursor train(stream, tune);
-  for (uint64_t t0 = 0; t0 < ntiles; t0 += per_launch) {
-    a.tile_begin = t0;
-    a.tile_end = t0 + per_launch < ntiles ? t0 + per_launch : ntiles;
-    const uint64_t blocks = (a.tile_end - a.tile_begin + kRingWaves - 1) / kRingWaves;
-    hipStream_t s;
-    e = train.next(&s);
+  const uint64_t ntiles = p.shape.ntiles(nrow);
+  if (p.defer) {
+    a.defer_cap = p.defer_cap;
+    a.defer_count = tune.defer_buf;
+    a.defer_list = tune.defer_buf + 1;
+    hipError_t e = hipMemsetAsync(a.defer_count, 0, sizeof(uint32_t), stream);
+    if (e == hipSuccess && p.listing) e = hipMemsetAsync(a.defer_list, 0xFF, (size_t)a.defer_cap * sizeof(uint32_t), stream);
     if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(predict_rows_ring_kernel, dim3((unsigned)(blocks < grid ? blocks : grid)), dim3(kRingBlock),
-                       kRingLdsBytes, s, fr, a, fr.super_heads, a.out);
   }
-  e = train.meet();
+  if (p.how == WalkPlan::Split) {
+    hipError_t e = launch_split(first, p.lds, fr, a, ntiles, num_cus, stream, tune, p.split);
+    return e != hipSuccess ? e : hipGetLastError();
+  }
+  hipError_t e = ensure_lds(first, p.lds);
   if (e != hipSuccess) return e;
-  // A ring block that gave up waiting has not written its rows, and says so by writing this train's id to flags[2].
-  // Behind the train: the tile kernel over ALL of the train's rows, every block of which leaves at once unless it finds
-  // that id there (5 us per step when it does not), missing-aware and without deferring; its first block counts the
-  // event.  Stream-ordered, so the device forms need no host in the loop (include/ohxgb.h: OHXBoosterRingReruns).
-  if (a.flags != nullptr) {
-    auto again = predict_rows_tile_kernel<2, 2, true, true>;
-    const size_t lds2 = tile_lds_bytes(fr.num_feature, true);
-    e = ensure_lds(again, lds2);
-    if (e != hipSuccess) return e;
-    PredictArgs b = a;
-    b.only_if_train = a.train_id;
-    b.defer_list = nullptr;
-    b.defer_count = nullptr;
-    b.defer_cap = 0;
-    b.tile_begin = 0;
-    b.tile_end = ntiles;
-    hipLaunchKernelGGL(again, dim3(tile_grid(again, lds2, ntiles, num_cus)), dim3(kBlock), lds2, stream, fr, b, fr.super_heads,
-                       b.out);
+  set_runs(a, p.runs);
+  const bool ring = p.how == WalkPlan::Ring;
+  const unsigned threads = ring ? kRingBlock : kBlock;
+  const uint64_t waves = threads / kWave;
+  uint64_t grid = (ntiles + waves - 1) / waves;
+  if (ring) {
+    if (grid > p.cus) grid = p.cus;
+    a.train_id = next_train_id();
+  } else {
+    grid = (uint64_t)tile_grid(first, p.lds, ntiles, num_cus);
   }
-  return hipGetLastError();
+  e = launch_train(first, threads, p.lds, grid, ntiles, p.rounds <= 0 ? ntiles : grid * waves * (uint64_t)p.rounds, stream, tune, fr, a);
+  if (e == hipSuccess && ring && a.flags != nullptr) e = launch_ring_rerun(rerun, p.lds_tile, fr, a, ntiles, num_cus, stream);
+  if (e == hipSuccess && p.listing) {
+    set_runs(a, CoopRuns());      // every lane fetches its own row, whichever the list gives it
+    a.shape = TileShape();
+    e = launch_deferred(second, p.lds_tile, fr, a, num_cus, stream);
+  }
+  return e != hipSuccess ? e : hipGetLastError();
 }
 
-// The second launch of a deferred-rows predict: the rows of the list, 64 per wave, each lane its own row, missing-aware.
-template <class K>
-hipError_t launch_deferred(K kernel, size_t lds, const DeviceForest& fr, PredictArgs a, int num_cus, hipStream_t stream) {
-  hipError_t e = ensure_lds(kernel, lds);
-  if (e != hipSuccess) return e;
-  a.perm = a.defer_list;
-  a.perm_count = a.defer_count;
-  a.perm_slots = a.defer_cap;
-  a.defer_list = nullptr;
-  a.defer_count = nullptr;
-  a.shape = TileShape();
-  a.run_log = 0;
-  a.run_lo_bits = 0;
-  a.tile_begin = 0;
-  a.tile_end = ((uint64_t)a.defer_cap + kWave - 1) / kWave;
-  const int grid = tile_grid(kernel, lds, a.tile_end, num_cus);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, stream, fr, a, fr.super_heads, a.out);
-  return hipGetLastError();
+std::string rows_tile_symbol(const WalkPlan& p, bool pf) {
+  return "predict_rows_tile_kernel<" + std::to_string(p.fmt) + "," + std::to_string(p.chains) + (pf ? ",true," : ",false,") +
+         (p.tops ? "true>" : "false>");
 }
-
 
 }  // namespace
 
@@ -2228,332 +2415,58 @@ const char* kernel_kind_name(KernelKind k) {
   return "?";
 }
 
-// What launch_predict does with a batch, decided in one place so that OHXBoosterKernelSymbolRows can say it too.
-struct RowsPlan {
-  bool ok = true;          // false: the forest has no array this kind of kernel could read
-  bool is_super = false;
-  bool direct = false;     // predict_rows_direct_kernel (wide nodes, no LDS)
-  bool pf = false;         // 27-column rows, the next tile's in flight during a walk
-  bool defer = false, listing = false;      // rows with missing values counted / left to a second launch
-  bool ring = false;       // predict_rows_ring_kernel
-  uint32_t split = 0;      // > 0: a small batch, its trees in this many runs over waves
-  TileShape split_shape;
-  size_t lds = 0;
-};
-
-RowsPlan plan_rows(KernelKind kind, const DeviceForest& fr, const PredictArgs& a, int num_cus, const LaunchTuning& tune) {
-  RowsPlan p;
-  p.is_super = kind == KernelKind::Super1 || kind == KernelKind::Super2 || kind == KernelKind::Super3 ||
-               kind == KernelKind::Super4 || kind == KernelKind::Ring;
-  p.lds = tile_lds_bytes(fr.num_feature, p.is_super);
-  const bool tile_ok = fr.num_feature >= 1 && p.lds <= 160 * 1024 && a.ncol <= fr.num_feature;
-  if (p.is_super && fr.super == nullptr) p.ok = false;
-  if (a.pred_leaf || kind == KernelKind::Wide || !tile_ok || (!p.is_super && fr.packed == nullptr)) {
-    p.direct = true;
-    return p;
-  }
-  // every wave gets more than one tile per launch and the rows are the OH shape: prefetch
-  p.pf = a.ncol == 27 && fr.num_feature == 27 && tune.launches_per_residency != 1 && tune.prefetch;
-  // rows with missing values are left to a second launch (PredictArgs::defer_list)
-  constexpr uint64_t kDeferMinRows = 1u << 18;
-  p.defer = p.pf && a.perm == nullptr && tune.defer_buf != nullptr && tune.defer_words >= 2 && a.nrow < 0xFFFFFFF0ull &&
-            (tune.defer_missing > 0 || (tune.defer_missing < 0 && a.nrow >= kDeferMinRows));
-  p.listing = p.defer && !tune.defer_count_only;
-  // A small batch leaves most of the chip's wave slots empty and takes as long as one tile's walk of ALL trees
-  // (165 us for the OH booster whatever N, profiles/r03_latency_rows.json): cut the trees into runs walked by
-  // different waves.  Decided on the live tiles of the batch against the chip's 20 waves per CU.
-  if (p.is_super && a.perm == nullptr && tune.tree_split != 0 && tune.leaf_buf != nullptr && a.tree_end - a.tree_begin >= 8) {
-    PredictArgs probe = a;
-    shape_rows(probe, tune);
-    // bricks laid over a level of which the batch holds a small part are mostly empty: 64 consecutive rows per wave then
-    if (probe.shape.im != 0 && probe.shape.live_tiles() * 2 < probe.shape.ntiles(a.nrow)) probe.shape = TileShape();
-    const uint64_t ntiles = probe.shape.ntiles(a.nrow);
-    const uint64_t live = probe.shape.im != 0 && probe.shape.live_tiles() < ntiles ? probe.shape.live_tiles() : ntiles;
-    const uint64_t slots = (uint64_t)num_cus * 20u;
-    const uint32_t ntree = a.tree_end - a.tree_begin;
-    uint64_t want = tune.tree_split > 1 ? (uint64_t)tune.tree_split : (live * 2 <= slots ? slots / (live ? live : 1) : 0);
-    if (want > 10) want = 10;
-    if (want * 4 > ntree) want = ntree / 4;
-    if (want >= 2 && ntiles * ntree * kWave <= tune.leaf_words) {
-      p.split = (uint32_t)want;
-      p.split_shape = probe.shape;
-    }
-  }
-  // the ring kernel takes the OH shape with the next rows in flight (a big batch); everything else of a booster
-  // that asked for it - small batches with their trees split over waves, other column counts, the second launch of
-  // the deferred rows - goes the super2 way
-  p.ring = kind == KernelKind::Ring && p.pf && !p.split && a.tree_end > a.tree_begin;
-  return p;
-}
-
-hipError_t launch_predict(KernelKind kind, const DeviceForest& fr, const PredictArgs& a_in, int num_cus,
-                          hipStream_t stream, const LaunchTuning& tune) {
-  if (a_in.nrow == 0) return hipSuccess;
-  PredictArgs a = a_in;
-  const RowsPlan plan = plan_rows(kind, fr, a, num_cus, tune);
-  if (!plan.ok) return hipErrorInvalidValue;
-  const size_t lds = plan.lds;
-  if (plan.direct) {
-    if (fr.wide == nullptr) return hipErrorInvalidValue;
-    const int grid = grid_for(a.nrow, num_cus, 8);
-    if (a.pred_leaf) hipLaunchKernelGGL(predict_rows_direct_kernel<true>, dim3(grid), dim3(kBlock), 0, stream, fr, a);
-    else hipLaunchKernelGGL(predict_rows_direct_kernel<false>, dim3(grid), dim3(kBlock), 0, stream, fr, a);
-    return hipGetLastError();
-  }
-  const bool pf = plan.pf, listing = plan.listing;
-  if (plan.defer) {
-    const uint64_t want = a.nrow / 32 + 1024;                                   // room for ~3 % of the rows
-    a.defer_cap = listing ? (uint32_t)(want < tune.defer_words - 1 ? want : tune.defer_words - 1) : 0u;
-    a.defer_count = tune.defer_buf;
-    a.defer_list = tune.defer_buf + 1;
-    hipError_t e = hipMemsetAsync(a.defer_count, 0, sizeof(uint32_t), stream);
-    if (e == hipSuccess && listing) e = hipMemsetAsync(a.defer_list, 0xFF, (size_t)a.defer_cap * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-  }
-  const uint32_t split = plan.split;
-  if (split) a.shape = plan.split_shape;
-#define OHX_ROWS_T(FMT, CH, TOPS)                                                                                  \
-  {                                                                                                                \
-    if (split) return launch_rows_split(predict_rows_tile_kernel<FMT, CH, false, TOPS>, lds, fr, a, num_cus, stream, tune, split); \
-    hipError_t e_ = pf ? launch_rows_tiled(predict_rows_tile_kernel<FMT, CH, true, TOPS>, lds, fr, a, num_cus, stream, tune)   \
-                       : launch_rows_tiled(predict_rows_tile_kernel<FMT, CH, false, TOPS>, lds, fr, a, num_cus, stream, tune); \
-    if (e_ == hipSuccess && listing)                                                                               \
-      e_ = launch_deferred(predict_rows_tile_kernel<FMT, CH, false, TOPS>, lds, fr, a, num_cus, stream);           \
-    return e_;                                                                                                     \
-  }
-#define OHX_ROWS(FMT, CH)                    \
-  if (fr.tree_tops) OHX_ROWS_T(FMT, CH, true); \
-  OHX_ROWS_T(FMT, CH, false)
-  if (plan.ring) {
-    hipError_t e_ = launch_rows_ring(fr, a, num_cus, stream, tune);
-    if (e_ == hipSuccess && listing)
-      e_ = launch_deferred(predict_rows_tile_kernel<2, 2, false, true>, lds, fr, a, num_cus, stream);
-    return e_;
-  }
-  switch (kind) {
-    case KernelKind::Packed1: OHX_ROWS_T(1, 1, false);
-    case KernelKind::Packed2: OHX_ROWS_T(1, 2, false);
-    case KernelKind::Packed4: OHX_ROWS_T(1, 4, false);
-    case KernelKind::Super1: OHX_ROWS(2, 1);
-    case KernelKind::Super3: OHX_ROWS(2, 3);
-    case KernelKind::Super4: OHX_ROWS(2, 4);
-    default: OHX_ROWS(2, 2);
-  }
-#undef OHX_ROWS
-#undef OHX_ROWS_T
-}
-
-std::string predict_kernel_symbol(KernelKind kind, const DeviceForest& fr, uint32_t ncol, const LaunchTuning& tune) {
-  const bool is_super = kind == KernelKind::Super1 || kind == KernelKind::Super2 || kind == KernelKind::Super3 ||
-                        kind == KernelKind::Super4 || kind == KernelKind::Ring;
-  const size_t lds = tile_lds_bytes(fr.num_feature, is_super);
-  const bool tile_ok = fr.num_feature >= 1 && lds <= 160 * 1024 && ncol <= fr.num_feature;
-  if (kind == KernelKind::Wide || !tile_ok || (!is_super && fr.packed == nullptr)) return "predict_rows_direct_kernel<false>";
-  const bool pf = ncol == 27 && fr.num_feature == 27 && tune.launches_per_residency != 1 && tune.prefetch;
-  if (kind == KernelKind::Ring && pf) return "predict_rows_ring_kernel";
-  int chains = 2;
-  if (kind == KernelKind::Packed1 || kind == KernelKind::Super1) chains = 1;
-  if (kind == KernelKind::Super3) chains = 3;
-  if (kind == KernelKind::Packed4 || kind == KernelKind::Super4) chains = 4;
-  return std::string("predict_rows_tile_kernel<") + (is_super ? "2," : "1,") + std::to_string(chains) +
-         (pf ? ",true," : ",false,") + (is_super && fr.tree_tops ? "true>" : "false>");
-}
-
-// Every __global__ a predict on this batch launches, in order, joined by " + " (OHXBoosterKernelSymbolRows).
-std::string predict_kernel_symbols_rows(KernelKind kind, const DeviceForest& fr, const PredictArgs& a, int num_cus,
-                                        const LaunchTuning& tune) {
-  const RowsPlan p = plan_rows(kind, fr, a, num_cus, tune);
-  if (a.nrow == 0 || !p.ok) return "";
-  if (p.direct) return a.pred_leaf ? "predict_rows_direct_kernel<true>" : "predict_rows_direct_kernel<false>";
-  int chains = 2;
-  if (kind == KernelKind::Packed1 || kind == KernelKind::Super1) chains = 1;
-  if (kind == KernelKind::Super3) chains = 3;
-  if (kind == KernelKind::Packed4 || kind == KernelKind::Super4) chains = 4;
-  const bool tops = p.is_super && fr.tree_tops;
-  auto tile = [&](bool prefetch) {
-    return std::string("predict_rows_tile_kernel<") + (p.is_super ? "2," : "1,") + std::to_string(chains) +
-           (prefetch ? ",true," : ",false,") + (tops ? "true>" : "false>");
-  };
-  if (p.split) return tile(false) + " + combine_leaves_kernel";
-  std::string out;
-  if (p.ring) {
-    out = "predict_rows_ring_kernel + predict_rows_tile_kernel<2,2,true,true> (only after a ring time-out)";
-    if (p.listing) out += " + predict_rows_tile_kernel<2,2,false,true> (rows with missing values)";
-    return out;
-  }
-  out = tile(p.pf);
-  if (p.listing) out += " + " + tile(false) + " (rows with missing values)";
-  return out;
-}
-
-// Same train of launches as the row kernels: a launch per `launches_per_residency` residencies
-// keeps the waves of an XCD on the same few trees.
-template <class K>
-hipError_t launch_fields_tiled(K kernel, size_t lds, const DeviceForest& fr, FieldsArgs a, uint64_t nrow, int num_cus,
-                               hipStream_t stream, const LaunchTuning& tune, int waves_per_block = kWavesPerBlock,
-                               int rounds = -1) {
-  if (rounds < 0) rounds = tune.launches_per_residency;
-  const bool ring = waves_per_block != kWavesPerBlock;
-  const unsigned threads = (unsigned)waves_per_block * kWave;
-  hipError_t e = ensure_lds(kernel, lds);
-  if (e != hipSuccess) return e;
-  if (tune.brick_li < 0) a.shape.set_grid_auto((uint32_t)a.im, (uint32_t)a.jm, 0, nrow);
-  else if (tune.brick_li + tune.brick_lj + tune.brick_lk == 6)
-    a.shape.set_grid((uint32_t)a.im, (uint32_t)a.jm, 0, nrow, (uint32_t)tune.brick_li, (uint32_t)tune.brick_lj,
-                     (uint32_t)tune.brick_lk);
-  a.shape.k_fastest = (uint32_t)tune.brick_k_fastest;
-  a.xcd_remap = tune.xcd_remap;
-  if (a.shape.ntiles(nrow) >= 0xFFFFFFFFull) a.shape = TileShape();
-  const uint64_t ntiles = a.shape.ntiles(nrow);
-  int grid = tile_grid(kernel, lds, ntiles, num_cus);
-  if (ring) {        // one block per CU, less the CUs left free for a collective's kernels (LaunchTuning::reserve_cus)
-    const uint64_t blocks = (ntiles + waves_per_block - 1) / waves_per_block;
-    const uint64_t cus = tune.reserve_cus > 0 && tune.reserve_cus < num_cus ? (uint64_t)(num_cus - tune.reserve_cus) : (uint64_t)num_cus;
-    grid = (int)(blocks < cus ? blocks : cus);
-  }
-  // rows with missing values are left to a second launch (PredictArgs::defer_list)
-  constexpr uint64_t kDeferMinRows = 1u << 18;
-  if (tune.defer_buf != nullptr && tune.defer_words >= 2 && nrow < 0xFFFFFFF0ull && fr.num_feature == 27 &&
-      (tune.defer_missing > 0 || (tune.defer_missing < 0 && nrow >= kDeferMinRows))) {
-    const uint64_t want = nrow / 32 + 1024;
-    a.defer_cap = tune.defer_count_only ? 0u : (uint32_t)(want < tune.defer_words - 1 ? want : tune.defer_words - 1);
-    a.defer_count = tune.defer_buf;
-    a.defer_list = tune.defer_buf + 1;
-    e = hipMemsetAsync(a.defer_count, 0, sizeof(uint32_t), stream);
-    if (e == hipSuccess && a.defer_cap) e = hipMemsetAsync(a.defer_list, 0xFF, (size_t)a.defer_cap * sizeof(uint32_t), stream);
-    if (e != hipSuccess) return e;
-  }
-  const uint64_t per_launch = rounds <= 0 ? ntiles : (uint64_t)grid * waves_per_block * (uint64_t)rounds;
-  if (ring) a.train_id = next_train_id();
-  TrainCursor train(stream, tune);
-  for (uint64_t t0 = 0; t0 < ntiles; t0 += per_launch) {
-    a.tile_begin = t0;
-    a.tile_end = t0 + per_launch < ntiles ? t0 + per_launch : ntiles;
-    const uint64_t blocks = (a.tile_end - a.tile_begin + waves_per_block - 1) / waves_per_block;
-    hipStream_t s;
-    e = train.next(&s);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)(blocks < (uint64_t)grid ? blocks : (uint64_t)grid)), dim3(threads), lds,
-                       s, fr, a, fr.super_heads, a.out, a.margin_out);
-  }
-  e = train.meet();
-  if (e != hipSuccess) return e;
-  if (ring && a.flags != nullptr) {
-    // as launch_rows_ring: the tile kernel over all of the slab, predicated on this train's id in flags[2]
-    auto again = predict_fields_kernel<2, 2, true>;
-    const size_t lds2 = tile_lds_bytes(fr.num_feature, true);
-    e = ensure_lds(again, lds2);
-    if (e != hipSuccess) return e;
-    FieldsArgs b = a;
-    b.only_if_train = a.train_id;
-    b.defer_list = nullptr;
-    b.defer_count = nullptr;
-    b.defer_cap = 0;
-    b.tile_begin = 0;
-    b.tile_end = ntiles;
-    hipLaunchKernelGGL(again, dim3(tile_grid(again, lds2, ntiles, num_cus)), dim3(kBlock), lds2, stream, fr, b, fr.super_heads,
-                       b.out, b.margin_out);
-  }
-  if (a.defer_list != nullptr && a.defer_cap != 0u) {
-    // the second launch: the listed rows, 64 per wave, every lane gathering its own row from the fields
-    a.perm = a.defer_list;
-    a.perm_count = a.defer_count;
-    a.perm_slots = a.defer_cap;
-    a.defer_list = nullptr;
-    a.defer_count = nullptr;
-    a.tile_begin = 0;
-    a.tile_end = ((uint64_t)a.defer_cap + kWave - 1) / kWave;
-    if (ring) {      // the listed rows go through the tile kernel (a lane per row, missing-aware)
-      auto second = predict_fields_kernel<2, 2, true>;
-      const size_t lds2 = tile_lds_bytes(fr.num_feature, true);
-      e = ensure_lds(second, lds2);
-      if (e != hipSuccess) return e;
-      const int grid2 = tile_grid(second, lds2, a.tile_end, num_cus);
-      hipLaunchKernelGGL(second, dim3(grid2), dim3(kBlock), lds2, stream, fr, a, fr.super_heads, a.out, a.margin_out);
-    } else {
-      const int grid2 = tile_grid(kernel, lds, a.tile_end, num_cus);
-      hipLaunchKernelGGL(kernel, dim3(grid2), dim3(kBlock), lds, stream, fr, a, fr.super_heads, a.out, a.margin_out);
-    }
-  }
-  return hipGetLastError();
-}
-
-// A small slab: the trees in `split` runs, a wave per (run, tile), then the launch that sums the leaves in tree order
-template <class K>
-hipError_t launch_fields_split(K kernel, size_t lds, const DeviceForest& fr, FieldsArgs a, int num_cus, hipStream_t stream,
-                               const LaunchTuning& tune, uint32_t split) {
-  hipError_t e = ensure_lds(kernel, lds);
-  if (e != hipSuccess) return e;
-  a.xcd_remap = tune.xcd_remap;
-  a.tile_begin = 0;
-  a.tile_end = a.shape.ntiles((uint64_t)a.im * a.jm * (uint64_t)(a.k2 - a.k1 + 1));
-  a.leaf_buf = tune.leaf_buf;
-  a.tree_split = split;
-  const int grid = tile_grid(kernel, lds, a.tile_end * split, num_cus);
-  hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, stream, fr, a, fr.super_heads, a.out, a.margin_out);
-  const uint64_t blocks = (a.tile_end + kWavesPerBlock - 1) / kWavesPerBlock;
-  hipLaunchKernelGGL(combine_leaves_fields_kernel, dim3((unsigned)(blocks < 8192 ? blocks : 8192)), dim3(kBlock), 0, stream, a,
-                     fr.base_score, a.out, a.margin_out);
-  return hipGetLastError();
+hipError_t launch_predict(KernelKind kind, const DeviceForest& fr, const PredictArgs& a, int num_cus, hipStream_t stream,
+                          const LaunchTuning& tune) {
+  if (a.nrow == 0) return hipSuccess;
+  const WalkPlan p = plan_rows(kind, fr, a, num_cus, tune);
+  if (!p.ok) return hipErrorInvalidValue;
+  if (p.how == WalkPlan::Direct) return launch_rows_direct(fr, a, num_cus, stream);
+  const bool ring = p.how == WalkPlan::Ring;
+  return launch_plan(p, ring ? predict_rows_ring_kernel : rows_tile_kernel(p.fmt, p.chains, p.tops, p.pf), rows_ring_rerun_kernel(),
+                     ring ? rows_ring_deferred_kernel() : rows_tile_kernel(p.fmt, p.chains, p.tops, false), fr, a, a.nrow,
+                     num_cus, stream, tune);
 }
 
 hipError_t launch_predict_fields(KernelKind kind, const DeviceForest& fr, const FieldsArgs& a, int num_cus,
                                  hipStream_t stream, const LaunchTuning& tune) {
   if (a.k2 < a.k1 || a.im <= 0 || a.jm <= 0) return hipSuccess;
   const uint64_t nrow = (uint64_t)a.im * (uint64_t)a.jm * (uint64_t)(a.k2 - a.k1 + 1);
-  const bool is_super = kind == KernelKind::Super1 || kind == KernelKind::Super2 || kind == KernelKind::Super3 ||
-                        kind == KernelKind::Super4 || kind == KernelKind::Ring;
-  const size_t lds = tile_lds_bytes(fr.num_feature, is_super);
-  if (fr.num_feature < 1 || lds > 160 * 1024) return hipErrorInvalidValue;
-  if (is_super && fr.super == nullptr) return hipErrorInvalidValue;
-  const bool use_wide = kind == KernelKind::Wide || (!is_super && fr.packed == nullptr);
-  if (use_wide && fr.wide == nullptr) return hipErrorInvalidValue;
-#define OHX_LAUNCH_FIELDS_T(FMT, CH, TOPS) \
-  return launch_fields_tiled(predict_fields_kernel<FMT, CH, TOPS>, lds, fr, a, nrow, num_cus, stream, tune)
-#define OHX_LAUNCH_FIELDS(FMT, CH)                    \
-  if (fr.tree_tops) OHX_LAUNCH_FIELDS_T(FMT, CH, true); \
-  OHX_LAUNCH_FIELDS_T(FMT, CH, false)
-  if (use_wide) OHX_LAUNCH_FIELDS_T(0, 1, false);
-  // A small slab - a GEOS rank's block - leaves most of the chip's wave slots empty and takes as long as one tile's walk
-  // of ALL trees: its trees are cut into runs walked by different waves, as launch_predict does for small row batches
-  if (is_super && tune.tree_split != 0 && tune.leaf_buf != nullptr && a.tree_end - a.tree_begin >= 8) {
-    FieldsArgs probe = a;
-    if (tune.brick_li < 0) probe.shape.set_grid_auto((uint32_t)a.im, (uint32_t)a.jm, 0, nrow);
-    else if (tune.brick_li + tune.brick_lj + tune.brick_lk == 6)
-      probe.shape.set_grid((uint32_t)a.im, (uint32_t)a.jm, 0, nrow, (uint32_t)tune.brick_li, (uint32_t)tune.brick_lj,
-                           (uint32_t)tune.brick_lk);
-    probe.shape.k_fastest = (uint32_t)tune.brick_k_fastest;
-    const uint64_t ntiles = probe.shape.ntiles(nrow);
-    const uint64_t live = probe.shape.im != 0 && probe.shape.live_tiles() < ntiles ? probe.shape.live_tiles() : ntiles;
-    const uint64_t slots = (uint64_t)num_cus * 20u;
-    const uint32_t ntree = a.tree_end - a.tree_begin;
-    uint64_t want = tune.tree_split > 1 ? (uint64_t)tune.tree_split : (live * 2 <= slots ? slots / (live ? live : 1) : 0);
-    if (want > 10) want = 10;
-    if (want * 4 > ntree) want = ntree / 4;
-    if (want >= 2 && ntiles < 0xFFFFFFFFull && ntiles * ntree * kWave <= tune.leaf_words) {
-      if (kind == KernelKind::Super1) return launch_fields_split(predict_fields_kernel<2, 1, false>, lds, fr, probe, num_cus, stream, tune, (uint32_t)want);
-      if (kind == KernelKind::Super4) return launch_fields_split(predict_fields_kernel<2, 4, false>, lds, fr, probe, num_cus, stream, tune, (uint32_t)want);
-      if (fr.tree_tops) return launch_fields_split(predict_fields_kernel<2, 2, true>, lds, fr, probe, num_cus, stream, tune, (uint32_t)want);
-      return launch_fields_split(predict_fields_kernel<2, 2, false>, lds, fr, probe, num_cus, stream, tune, (uint32_t)want);
-    }
+  const WalkPlan p = plan_fields(kind, fr, a, nrow, num_cus, tune);
+  if (!p.ok) return hipErrorInvalidValue;
+  const bool ring = p.how == WalkPlan::Ring;
+  const FieldsKernel tile = fields_tile_kernel(p.fmt, p.chains, p.tops);
+  return launch_plan(p, ring ? predict_fields_ring_kernel : tile, fields_ring_later_kernel(),
+                     ring ? fields_ring_later_kernel() : tile, fr, a, nrow, num_cus, stream, tune);
+}
+
+// Every __global__ a predict on this batch launches, in order, joined by " + " (OHXBoosterKernelSymbolRows).
+std::string predict_kernel_symbols_rows(KernelKind kind, const DeviceForest& fr, const PredictArgs& a, int num_cus,
+                                        const LaunchTuning& tune) {
+  const WalkPlan p = plan_rows(kind, fr, a, num_cus, tune);
+  if (a.nrow == 0 || !p.ok) return "";
+  switch (p.how) {
+    case WalkPlan::Direct: return a.pred_leaf ? "predict_rows_direct_kernel<true>" : "predict_rows_direct_kernel<false>";
+    case WalkPlan::Split: return rows_tile_symbol(p, false) + " + combine_leaves_kernel";
+    case WalkPlan::Ring:
+      return std::string("predict_rows_ring_kernel + predict_rows_tile_kernel<2,2,true,true> (only after a ring time-out)") +
+             (p.listing ? " + predict_rows_tile_kernel<2,2,false,true> (rows with missing values)" : "");
+    case WalkPlan::Tile: break;
   }
-  // the ring kernel for slabs that fill the chip at least twice; smaller ones (a rank-sized block) the super2 way:
-  // a block of the ring kernel is 16 tiles that wait for each other's trees
-  if (kind == KernelKind::Ring && fr.num_feature == 27 && a.tree_end > a.tree_begin &&
-      nrow >= (uint64_t)num_cus * kRingWaves * kWave * 2u)
-    return launch_fields_tiled(predict_fields_ring_kernel, kRingLdsBytes, fr, a, nrow, num_cus, stream, tune, kRingWaves,
-                               tune.ring_rounds);
-  switch (kind) {
-    case KernelKind::Packed1: OHX_LAUNCH_FIELDS_T(1, 1, false);
-    case KernelKind::Packed2: OHX_LAUNCH_FIELDS_T(1, 2, false);
-    case KernelKind::Packed4: OHX_LAUNCH_FIELDS_T(1, 4, false);
-    case KernelKind::Super1: OHX_LAUNCH_FIELDS(2, 1);
-    case KernelKind::Super3: OHX_LAUNCH_FIELDS(2, 3);
-    case KernelKind::Super4: OHX_LAUNCH_FIELDS(2, 4);
-    default: OHX_LAUNCH_FIELDS(2, 2);
-  }
-#undef OHX_LAUNCH_FIELDS
-#undef OHX_LAUNCH_FIELDS_T
+  return rows_tile_symbol(p, p.pf) + (p.listing ? " + " + rows_tile_symbol(p, false) + " (rows with missing values)" : "");
+}
+
+// The first kernel of the plan of a notional big batch: more rows than any small-batch rule takes, all trees, no grid
+// named.  `tune` is the booster's own: it carries none of the per-call buffers (leaf_buf, defer_buf), so the plan
+// neither splits trees over waves nor defers rows, and the number of CUs (1 here) decides nothing in it.  A forest
+// without trees is named its tile kernel, as launch_predict would launch it (the ring takes at least one tree).
+std::string predict_kernel_symbol(KernelKind kind, const DeviceForest& fr, uint32_t ncol, const LaunchTuning& tune) {
+  PredictArgs a;
+  a.nrow = 1u << 24;
+  a.ncol = ncol;
+  a.tree_end = fr.num_trees;
+  const WalkPlan p = plan_rows(kind, fr, a, 1, tune);
+  if (p.how == WalkPlan::Direct) return "predict_rows_direct_kernel<false>";
+  return p.how == WalkPlan::Ring ? "predict_rows_ring_kernel" : rows_tile_symbol(p, p.pf);
 }
 
 uint32_t cluster_key_bits(const ClusterArgs& a) { return a.ntrees * (1u + 2u * a.nsteps); }

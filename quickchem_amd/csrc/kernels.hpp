@@ -157,7 +157,7 @@ struct TrainStreams {
 };
 
 // ring kernels: tiles per wave and launch at most, for rows not known to lie on a grid, and for rows that come through
-// the clustering pass's permutation (launch_rows_ring)
+// the clustering pass's permutation (kernels.hip plan_rows)
 constexpr int kRingRoundsNoGrid = 16;
 constexpr int kRingRoundsPermuted = 4;
 
@@ -320,8 +320,49 @@ hipError_t sort_pairs_u32(void* temp, size_t* temp_bytes, uint32_t* keys_a, uint
 // predict_fields_ring_kernel); falls back to Super2 for what those kernels do not take (small batches, other shapes)
 enum class KernelKind { Wide, Packed1, Packed2, Packed4, Super1, Super2, Super3, Super4, Ring };
 
+// super-node records (the ring kernels walk them too), against packed or wide nodes
+constexpr bool kind_is_super(KernelKind k) {
+  return k == KernelKind::Super1 || k == KernelKind::Super2 || k == KernelKind::Super3 || k == KernelKind::Super4 ||
+         k == KernelKind::Ring;
+}
+// trees a lane walks at a time
+constexpr int kind_chains(KernelKind k) {
+  switch (k) {
+    case KernelKind::Packed1: case KernelKind::Super1: return 1;
+    case KernelKind::Super3: return 3;
+    case KernelKind::Packed4: case KernelKind::Super4: return 4;
+    default: return 2;
+  }
+}
+
+// Which 64 rows a wave takes of rows [row0, row0 + nrow) gathered from an im x jm grid (0 = unknown: 64 consecutive
+// rows): the brick chosen per call or the one the knobs name, or consecutive rows where the knobs name none or the
+// bricks were too many for tile_row, which numbers them in 32 bits.  Every launcher, and whoever sizes a buffer by
+// the tiles of a launch (capi.cpp leaf_room), asks here.
+inline TileShape pick_shape(const LaunchTuning& tune, int im, int jm, uint64_t row0, uint64_t nrow) {
+  TileShape s;
+  if (im > 0 && jm > 0 && nrow > 0) {
+    if (tune.brick_li < 0) s.set_grid_auto((uint32_t)im, (uint32_t)jm, row0, nrow);
+    else if (tune.brick_li + tune.brick_lj + tune.brick_lk == 6)
+      s.set_grid((uint32_t)im, (uint32_t)jm, row0, nrow, (uint32_t)tune.brick_li, (uint32_t)tune.brick_lj, (uint32_t)tune.brick_lk);
+    if (s.im != 0) s.k_fastest = (uint32_t)tune.brick_k_fastest;
+  }
+  if (s.ntiles(nrow) >= 0xFFFFFFFFull) s = TileShape();
+  return s;
+}
+
+// Rows with missing values left to a second launch (PredictArgs::defer_list): who asks for it and how long the list is.
+// The booster's buffer holds the count and then the list: defer_capacity(nrow) + 1 words.
+struct DeferRule {
+  static constexpr uint64_t kDeferMinRows = 1u << 18;
+  static constexpr uint64_t defer_capacity(uint64_t nrow) { return nrow / 32 + 1024; }      // room for ~3 % of the rows
+  static bool wanted(const LaunchTuning& tune, uint64_t nrow) {
+    return tune.defer_missing > 0 || (tune.defer_missing < 0 && nrow >= kDeferMinRows);
+  }
+};
+
 const char* kernel_kind_name(KernelKind k);
-// the __global__ launch_predict would launch for rows of `ncol` columns (for profiles and bench.py)
+// the first __global__ launch_predict would launch for a big batch of rows of `ncol` columns (for profiles and bench.py)
 std::string predict_kernel_symbol(KernelKind kind, const DeviceForest& forest, uint32_t ncol, const LaunchTuning& tune);
 // ... and every kernel a predict on the batch `a` launches, in order, joined by " + "
 std::string predict_kernel_symbols_rows(KernelKind kind, const DeviceForest& fr, const PredictArgs& a, int num_cus,
