@@ -380,6 +380,60 @@ int OHXBoosterPredictContribsFieldsDevice(BoosterHandle handle, const float* con
                                           float missing, int approximate, unsigned ntree_limit,
                                           float* const d_out[], void* stream);
 
+/* Selected gridcells: choose cells of an (im,jm,km) block on the device, gather their rows from the fields into a
+ * device row matrix for the rows forms (OHXDMatrixCreateFromDevice, then OHXBoosterPredictDevice, ...ContribsDevice,
+ * ...InteractionsDevice: the expensive answers, for a column or a few thousand cells), scatter per-cell results back
+ * into (im,jm,km) arrays.  None of the six calls takes a booster (docs/15_selected_cells.md).
+ * A cell index is c = (i-1) + im*((j-1) + jm*(k-1)) for 1-based i, j, k: an int64 in [0, im*jm*km), the offset of the
+ * cell in any (im,jm,km) Fortran-order array, whatever the slab.
+ * Host forms take host pointers, stage through buffers of their own call (never a booster's; of 3-D arrays only the
+ * levels that are needed cross PCIe) and return when the outputs are complete.  Device forms take device pointers,
+ * only enqueue on `stream` (NULL = the default stream) and never wait; the first selection or scatter on a stream
+ * allocates a 32 KiB table for that stream (so: one plain call before capturing).
+ * d_status (device forms, may be NULL) is a word the kernels OR bits into and never clear:
+ *   OHX_CELLS_OUT_OF_RANGE      a cell index outside [0, im*jm*km).  It is never dereferenced: the gather writes NaN
+ *                               into every column of that row, the scatter skips the entry.
+ *   OHX_CELLS_NOT_ASCENDING     the scatter's cells are not strictly ascending
+ *   OHX_CELLS_OVER_CAP          the selection found more cells than cap
+ * The host forms do all of the above and then return -1 with a message that names the first bad position.
+ *
+ * OHXSelectCells: the cells of the box i1..i2, j1..j2, k1..k2 (1-based, inclusive; i2 == i1 - 1 and the like: an empty
+ * box, nothing selected, success) with a(i,j[,k]) > b(i,j[,k]), compared as float32, in strictly ascending order;
+ * *count = how many.  a_is2d / b_is2d != 0: an (im,jm) array, the same for every level.  b == NULL: the scalar b0.
+ * a == NULL: every cell of the box (b, b0 unused).  NaN on either side selects nothing.  So: a box or a column (a
+ * NULL), a mask (a = mask, b0 = 0), the troposphere of OH Run1 (a = PL_MOD, b = TROPP 2-D).  When more than cap cells
+ * are selected the first cap are written, the full count is reported and OHX_CELLS_OVER_CAP raised.  The order comes
+ * from a scan of per-block counts, never from an atomic counter: the same array every run.  The device form writes
+ * *d_count (an int64 on the device).
+ *
+ * OHXGatherCells: rows[ncell][nfield] float32, row-major; row n holds, for cell cells[n], what the fields forms put
+ * in their tile for that gridcell before missing is canonicalised: fields[f] at the cell - at its (i,j) when is2d[f]
+ * - and field pl_feature divided by 100 as a float32 division (-1: none).  Values equal to a missing marker stay as
+ * they are: the DMatrix made over `rows` says what is missing, and features past nfield are columns it does not have.
+ * Any order and duplicates are allowed in cells; ncell == 0 does nothing.  Refused: nfield < 1 or > 32, im, jm or km
+ * not positive, NULL arrays (the fields forms' messages).
+ *
+ * OHXScatterCells: out3d[cells[n]] = values[n * stride + col]; every other cell is left untouched.  cells must be
+ * strictly ascending.  An entry that is not above EVERY entry in front of it (so: one that is <= its predecessor) is
+ * skipped and OHX_CELLS_NOT_ASCENDING raised, hence no cell is written twice and the result does not depend on
+ * scheduling, whatever the list holds.  One call per output column. */
+#define OHX_CELLS_OUT_OF_RANGE 1u
+#define OHX_CELLS_NOT_ASCENDING 2u
+#define OHX_CELLS_OVER_CAP 4u
+int OHXSelectCells(int im, int jm, int km, int i1, int i2, int j1, int j2, int k1, int k2, const float* a, int a_is2d,
+                   const float* b, int b_is2d, float b0, int64_t* cells, int64_t cap, int64_t* count);
+int OHXSelectCellsDevice(int im, int jm, int km, int i1, int i2, int j1, int j2, int k1, int k2, const float* d_a,
+                         int a_is2d, const float* d_b, int b_is2d, float b0, int64_t* d_cells, int64_t cap,
+                         int64_t* d_count, uint32_t* d_status, void* stream);
+int OHXGatherCells(const float* const fields[], const int32_t is2d[], int nfield, int pl_feature, int im, int jm, int km,
+                   const int64_t* cells, int64_t ncell, float* rows);
+int OHXGatherCellsDevice(const float* const d_fields[], const int32_t is2d[], int nfield, int pl_feature, int im, int jm,
+                         int km, const int64_t* d_cells, int64_t ncell, float* d_rows, uint32_t* d_status, void* stream);
+int OHXScatterCells(const float* values, int64_t stride, int64_t col, const int64_t* cells, int64_t ncell, float* out3d,
+                    int im, int jm, int km);
+int OHXScatterCellsDevice(const float* d_values, int64_t stride, int64_t col, const int64_t* d_cells, int64_t ncell,
+                          float* d_out3d, int im, int jm, int km, uint32_t* d_status, void* stream);
+
 /* The whole of predict_OH_with_XGB's RUN section in one kernel
  * (OH_GridCompMod.F90:303-383): gathers the 27 MAPL fields in place (field f is
  * (im,jm,km) Fortran order, or (im,jm) when is2d[f] != 0; feature order of

@@ -30,6 +30,8 @@ ABI_SYMBOLS = [
     "OHXBoosterPredictContribs", "OHXBoosterPredictContribsDevice",
     "OHXBoosterPredictInteractions", "OHXBoosterPredictInteractionsDevice",
     "OHXBoosterPredictContribsFields", "OHXBoosterPredictContribsFieldsDevice",
+    "OHXSelectCells", "OHXSelectCellsDevice", "OHXGatherCells", "OHXGatherCellsDevice",
+    "OHXScatterCells", "OHXScatterCellsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
     "OHXJulianDay", "OHXSolarGeometry", "OHXSolarGeometryDevice", "OHXBoosterGetInfo", "OHXBoosterGetNumGroups", "OHXBoosterGetNumCategoricalSplits", "OHXBoosterKernelSymbol", "OHXBoosterKernelSymbolRows",
     "OHXBoosterRingReruns", "OHXBoosterCopyEngineChoice", "OHXUnregisterHost", "OHXReleaseScratch",
@@ -122,6 +124,13 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                                           i32, i32, i32, f32, i32, C.c_uint, C.POINTER(vp), vp]
     lib.OHXBoosterPredictFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32,
                                             f32, i32, f32, vp, vp]
+    i64 = C.c_int64
+    lib.OHXSelectCells.argtypes = [i32] * 9 + [vp, i32, vp, i32, f32, vp, i64, C.POINTER(i64)]
+    lib.OHXSelectCellsDevice.argtypes = [i32] * 9 + [vp, i32, vp, i32, f32, vp, i64, vp, vp, vp]
+    lib.OHXGatherCells.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, vp, i64, vp]
+    lib.OHXGatherCellsDevice.argtypes = [C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, vp, i64, vp, vp, vp]
+    lib.OHXScatterCells.argtypes = [vp, i64, i64, vp, i64, vp, i32, i32, i32]
+    lib.OHXScatterCellsDevice.argtypes = [vp, i64, i64, vp, i64, vp, i32, i32, i32, vp, vp]
     lib.OHXBoosterPredictFieldsDevice.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32,
                                                   i32, i32, f32, i32, f32, vp, vp, vp]
     lib.OHXBoosterRun1.argtypes = [vp, C.POINTER(OHXRun1Args)]
@@ -426,6 +435,59 @@ class Booster:
             self.handle, ptrs, flags, nf, pl_feature, im, jm, km, k1, k2, missing, int(bool(approximate)), ntree_limit,
             outs, stream or None))
 
+    def explain_cells(self, fields, is2d: Sequence[bool], pl_feature: int, im: int, jm: int, km: int, missing: float, *,
+                      box=None, a=None, b=None, b0: float = 0.0, cells=None, what: str = "contribs",
+                      approximate: bool = False, ntree_limit: int = 0, scatter: bool = True,
+                      fill: float = float("nan")):
+        """Contributions (what="contribs") or SHAP interaction values (what="interactions") of selected gridcells,
+        from device fields, on torch's current stream: select_cells_device (unless `cells`, an int64 device tensor, is
+        given) -> gather_cells_device -> OHXDMatrixCreateFromDevice -> OHXBoosterPredictContribsDevice / ...InteractionsDevice
+        -> scatter_cells_device, one call per output column.  `fields`, `a`, `b`: torch float32 device tensors, a field
+        (im,jm,km) or (im,jm) in Fortran order; `a` / `b` count as 2-D when they hold im * jm elements.  Waits once,
+        for the count of the selection.  Returns (cells, out): `out` a (columns, im*jm*km) tensor, row c the
+        Fortran-order array of output column c (F + 1 columns, (F + 1)^2 for interactions, times the booster's
+        groups), `fill` where no cell was selected; with scatter=False the per-cell tensor (ncell, columns)."""
+        import torch
+        if what not in ("contribs", "interactions"):
+            raise ValueError("what: 'contribs' or 'interactions'")
+        dev = fields[0].device
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        total = im * jm * km
+        if cells is None:
+            i1, i2, j1, j2, k1, k2 = box or (1, im, 1, jm, 1, km)
+            cap = max(0, (i2 - i1 + 1) * (j2 - j1 + 1) * (k2 - k1 + 1))
+            cells = torch.empty(max(cap, 1), dtype=torch.int64, device=dev)
+            count = torch.zeros(1, dtype=torch.int64, device=dev)
+            select_cells_device(im, jm, km, (i1, i2, j1, j2, k1, k2), a.data_ptr() if a is not None else 0,
+                                a is not None and a.numel() == im * jm, b.data_ptr() if b is not None else 0,
+                                b is not None and b.numel() == im * jm, b0, cells.data_ptr(), cap, count.data_ptr(),
+                                stream=stream, lib=self.lib)
+            cells = cells[:int(count.item())]
+        ncell = int(cells.numel())
+        nf = len(fields)
+        F = self.info()["num_feature"]
+        ncol = self._groups() * ((F + 1) if what == "contribs" else (F + 1) * (F + 1))
+        rows = torch.empty((max(ncell, 1), nf), dtype=torch.float32, device=dev)
+        vals = torch.empty((max(ncell, 1), ncol), dtype=torch.float32, device=dev)
+        gather_cells_device([f.data_ptr() for f in fields], is2d, pl_feature, im, jm, km, cells.data_ptr(), ncell,
+                            rows.data_ptr(), stream=stream, lib=self.lib)
+        if ncell:
+            dmat = DMatrix(device_ptr=rows.data_ptr(), nrow=ncell, ncol=nf, missing=missing, lib=self.lib)
+            try:
+                if what == "contribs":
+                    self.predict_contribs_device(dmat, vals.data_ptr(), approximate, ntree_limit, stream)
+                else:
+                    self.predict_interactions_device(dmat, vals.data_ptr(), approximate, ntree_limit, stream)
+            finally:
+                dmat.free()
+        if not scatter:
+            return cells, vals[:ncell]
+        out = torch.full((ncol, total), fill, dtype=torch.float32, device=dev)
+        for c in range(ncol):
+            scatter_cells_device(vals.data_ptr(), ncol, c, cells.data_ptr(), ncell, out[c].data_ptr(), im, jm, km,
+                                 stream=stream, lib=self.lib)
+        return cells, out
+
     def run1_prepare(self, state: dict, *, dynamic_k_range: bool, tropp_min: float = 4000.0, ohscale: float = 0.85,
                      missing: float = -999.0, avogad: float = 6.023e26, runiv: float = 8314.47,
                      epsilon: float = 18.015 / 28.965, want_boost: bool = True, want_ndwet: bool = True,
@@ -551,6 +613,113 @@ def oh_post_process(ple_mod, t_mod, q_mod, tropp_mod, default_oh, oh_ml, *, avog
     check(lib, lib.OHXOHPostProcess(im, jm, km, avogad, runiv, epsilon, *[a.ctypes.data for a in flat], oh.ctypes.data,
                                     ndwet.ctypes.data))
     return oh.reshape(km, jm, im).transpose(2, 1, 0), ndwet.reshape(km, jm, im).transpose(2, 1, 0)
+
+
+# ---- selected gridcells (include/ohxgb.h part 2: OHXSelectCells, OHXGatherCells, OHXScatterCells) ----
+# bits of the device forms' status word
+CELLS_OUT_OF_RANGE, CELLS_NOT_ASCENDING, CELLS_OVER_CAP = 1, 2, 4
+
+
+def _flat_field(a) -> np.ndarray:
+    """A field as the C ABI reads it: float32, Fortran order.  1-D arrays are taken as already flattened that way,
+    [i,j(,k)]-indexed ones are flattened."""
+    a = np.asarray(a, dtype=np.float32)
+    return np.ascontiguousarray(a) if a.ndim == 1 else np.ascontiguousarray(a.ravel(order="F"))
+
+
+def select_cells(im: int, jm: int, km: int, box=None, a=None, b=None, b0: float = 0.0, cap: Optional[int] = None,
+                 out: Optional[np.ndarray] = None, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    """OHXSelectCells on host arrays: the cell indices c = (i-1) + im*((j-1) + jm*(k-1)) of the box (i1, i2, j1, j2, k1,
+    k2; 1-based, inclusive; default the whole block) with a > b, ascending, as an int64 array.  `a`, `b`: fields of
+    im*jm*km elements, or of im*jm (2-D, the same on every level); b None: the scalar b0; a None: every cell of the
+    box.  cap: most cells wanted (default: the box).  When more are selected the call raises OhxError, whose `count`
+    attribute is the full count; `out`, an int64 array of at least cap entries, then holds the first cap."""
+    lib = lib or load_library()
+    i1, i2, j1, j2, k1, k2 = box or (1, im, 1, jm, 1, km)
+    if cap is None:
+        cap = max(0, i2 - i1 + 1) * max(0, j2 - j1 + 1) * max(0, k2 - k1 + 1)
+    if out is None:
+        out = np.empty(max(cap, 1), dtype=np.int64)
+    elif out.dtype != np.int64 or not out.flags["C_CONTIGUOUS"] or out.size < cap:
+        raise ValueError("out: a contiguous int64 array of at least cap entries")
+    fa = _flat_field(a) if a is not None else None
+    fb = _flat_field(b) if b is not None else None
+    count = C.c_int64(0)
+    rc = lib.OHXSelectCells(im, jm, km, i1, i2, j1, j2, k1, k2, fa.ctypes.data if fa is not None else None,
+                            int(fa is not None and fa.size == im * jm), fb.ctypes.data if fb is not None else None,
+                            int(fb is not None and fb.size == im * jm), b0, out.ctypes.data, cap, C.byref(count))
+    if rc != 0:
+        err = OhxError(lib.XGBGetLastError().decode("utf-8", "replace"))
+        err.count = count.value
+        raise err
+    return out[:count.value].copy()
+
+
+def select_cells_device(im: int, jm: int, km: int, box, a_ptr: int, a_is2d: bool, b_ptr: int, b_is2d: bool, b0: float,
+                        cells_ptr: int, cap: int, count_ptr: int, status_ptr: int = 0, stream: int = 0,
+                        lib: Optional[C.CDLL] = None) -> None:
+    """OHXSelectCellsDevice: device addresses (a_ptr / b_ptr 0 for none; cells int64[cap], count int64[1], status
+    uint32[1] or 0); only enqueues on `stream`."""
+    lib = lib or load_library()
+    i1, i2, j1, j2, k1, k2 = box or (1, im, 1, jm, 1, km)
+    check(lib, lib.OHXSelectCellsDevice(im, jm, km, i1, i2, j1, j2, k1, k2, a_ptr or None, int(bool(a_is2d)),
+                                        b_ptr or None, int(bool(b_is2d)), b0, cells_ptr or None, cap, count_ptr or None,
+                                        status_ptr or None, stream or None))
+
+
+def gather_cells(fields: Sequence[np.ndarray], is2d: Sequence[bool], pl_feature: int, im: int, jm: int, km: int, cells,
+                 rows: Optional[np.ndarray] = None, lib: Optional[C.CDLL] = None) -> np.ndarray:
+    """OHXGatherCells on host arrays -> (ncell, nfield) float32: row n is what the fields forms gather for cell
+    cells[n] (field pl_feature divided by 100; -1: none).  `rows`, when given, is filled even when the call raises
+    (a cell out of range: its row is NaN)."""
+    lib = lib or load_library()
+    nf = len(fields)
+    flat = [_flat_field(f) for f in fields]
+    cells = np.ascontiguousarray(cells, dtype=np.int64)
+    if rows is None:
+        rows = np.empty((cells.size, nf), dtype=np.float32)
+    elif rows.dtype != np.float32 or not rows.flags["C_CONTIGUOUS"] or rows.size < cells.size * nf:
+        raise ValueError("rows: a contiguous float32 array of ncell * nfield elements")
+    ptrs = (C.c_void_p * max(nf, 1))(*[f.ctypes.data for f in flat])
+    flags = (C.c_int32 * max(nf, 1))(*[1 if t else 0 for t in is2d])
+    check(lib, lib.OHXGatherCells(ptrs, flags, nf, pl_feature, im, jm, km, cells.ctypes.data, cells.size,
+                                  rows.ctypes.data))
+    return rows
+
+
+def gather_cells_device(field_ptrs: Sequence[int], is2d: Sequence[bool], pl_feature: int, im: int, jm: int, km: int,
+                        cells_ptr: int, ncell: int, rows_ptr: int, status_ptr: int = 0, stream: int = 0,
+                        lib: Optional[C.CDLL] = None) -> None:
+    """OHXGatherCellsDevice: device addresses; rows float32[ncell][nfield]; only enqueues on `stream`."""
+    lib = lib or load_library()
+    nf = len(field_ptrs)
+    ptrs = (C.c_void_p * max(nf, 1))(*field_ptrs)
+    flags = (C.c_int32 * max(nf, 1))(*[1 if t else 0 for t in is2d])
+    check(lib, lib.OHXGatherCellsDevice(ptrs, flags, nf, pl_feature, im, jm, km, cells_ptr or None, ncell,
+                                        rows_ptr or None, status_ptr or None, stream or None))
+
+
+def scatter_cells(values, col: int, cells, out3d: np.ndarray, im: int, jm: int, km: int,
+                  lib: Optional[C.CDLL] = None) -> None:
+    """OHXScatterCells on host arrays: out3d[cells[n]] = values[n, col] (values 1-D: col 0).  out3d: a writable float32
+    array of im*jm*km elements in Fortran order (1-D, or F-contiguous 3-D); other cells keep what they hold."""
+    lib = lib or load_library()
+    values = np.ascontiguousarray(values, dtype=np.float32)
+    cells = np.ascontiguousarray(cells, dtype=np.int64)
+    stride = 1 if values.ndim == 1 else values.shape[1]
+    if (out3d.dtype != np.float32 or not out3d.flags["WRITEABLE"] or out3d.size < im * jm * km or
+            not (out3d.flags["F_CONTIGUOUS"] or out3d.ndim == 1)):
+        raise ValueError("out3d: a writable Fortran-order float32 array of im * jm * km elements")
+    check(lib, lib.OHXScatterCells(values.ctypes.data, stride, col, cells.ctypes.data, cells.size, out3d.ctypes.data,
+                                   im, jm, km))
+
+
+def scatter_cells_device(values_ptr: int, stride: int, col: int, cells_ptr: int, ncell: int, out_ptr: int, im: int,
+                         jm: int, km: int, status_ptr: int = 0, stream: int = 0, lib: Optional[C.CDLL] = None) -> None:
+    """OHXScatterCellsDevice: device addresses; only enqueues on `stream`."""
+    lib = lib or load_library()
+    check(lib, lib.OHXScatterCellsDevice(values_ptr or None, stride, col, cells_ptr or None, ncell, out_ptr or None,
+                                         im, jm, km, status_ptr or None, stream or None))
 
 
 UNIQUE_ID_BYTES = 128

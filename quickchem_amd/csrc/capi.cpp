@@ -13,6 +13,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <map>
 #include <memory>
 #include <atomic>
 #include <chrono>
@@ -25,6 +26,7 @@
 
 #include "../../include/ohxgb.h"
 #include "categorical.hpp"
+#include "cells.hpp"
 #include "contribs.hpp"
 #include "flatten.hpp"
 #include "forest.hpp"
@@ -2258,6 +2260,11 @@ int OHXBoosterCheck(BoosterHandle handle, void* stream) {
   API_END();
 }
 
+// (shared with the selected-gridcells calls, which take no booster)
+static void check_grid_positive(int im, int jm, int km) {
+  if (im <= 0 || jm <= 0 || km <= 0) throw OhxError("predict_fields: im, jm, km must be positive");
+}
+
 // the fields forms' checks of the grid and the field count (predict and contributions)
 static void check_fields_shape(const BoosterObj& b, int nfield, int im, int jm, int km, int k1, int k2) {
   if (nfield < 0 || nfield > 32) throw OhxError("predict_fields: nfield must be 0..32");
@@ -2265,7 +2272,7 @@ static void check_fields_shape(const BoosterObj& b, int nfield, int im, int jm, 
     throw OhxError("Number of columns does not match number of features in booster (" + std::to_string(nfield) +
                    " vs. " + std::to_string(b.forest.num_feature) + ")");
   if (b.forest.num_feature > 32) throw OhxError("predict_fields supports boosters with at most 32 features");
-  if (im <= 0 || jm <= 0 || km <= 0) throw OhxError("predict_fields: im, jm, km must be positive");
+  check_grid_positive(im, jm, km);
   if (k1 < 1 || k2 > km || k2 < k1 - 1) throw OhxError("predict_fields: need 1 <= k1, k2 <= km, k2 >= k1 - 1");
 }
 
@@ -2533,6 +2540,295 @@ int OHXBoosterPredictContribsFieldsDevice(BoosterHandle handle, const float* con
   refuse_categorical(*b, "OHXBoosterPredictContribsFieldsDevice");
   contribs_fields_call(*b, d_fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, approximate, ntree_limit,
                        d_out, false, static_cast<hipStream_t>(stream));
+  API_END();
+}
+
+// ---- selected gridcells (include/ohxgb.h part 2b; cells.hip) ----
+//
+// No booster: the device forms enqueue on the caller's stream with the current device, the host forms stage through
+// buffers of their own call on the library's stream.  The ordered passes (selection, scatter) keep one number per
+// block in a table: the device forms' is one per (device, stream), made at the first call on that stream and kept for
+// the life of the process - calls on one stream run one after the other, so they may share it - and both launches of
+// a call are enqueued under the mutex, so two threads on one stream cannot interleave theirs.
+extern "C++" {
+namespace {
+struct CellsTables {
+  std::mutex mu;
+  std::map<std::pair<int, hipStream_t>, uint64_t*> by_stream;
+};
+static CellsTables g_cells_tables;
+
+// with g_cells_tables.mu held
+uint64_t* cells_table(int device, hipStream_t stream) {
+  uint64_t*& t = g_cells_tables.by_stream[{device, stream}];
+  if (t == nullptr) {
+    if (stream_capturing(stream))
+      refuse_in_capture("allocate the per-block table of a selection or a scatter",
+                        "make one plain call on this stream first, then capture");
+    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&t), kCellsMaxBlocks * sizeof(uint64_t)));
+  }
+  return t;
+}
+
+SelectCellsArgs select_args(int im, int jm, int km, int i1, int i2, int j1, int j2, int k1, int k2, const float* a,
+                            int a_is2d, const float* b, int b_is2d, float b0, const int64_t* cells, int64_t cap,
+                            const int64_t* count) {
+  check_grid_positive(im, jm, km);
+  if (i1 < 1 || i2 > im || i2 < i1 - 1 || j1 < 1 || j2 > jm || j2 < j1 - 1 || k1 < 1 || k2 > km || k2 < k1 - 1)
+    throw OhxError("select_cells: need 1 <= i1, i2 <= im, i2 >= i1 - 1, and the same for j and k");
+  if (cap < 0) throw OhxError("select_cells: cap must not be negative");
+  if (count == nullptr || (cells == nullptr && cap > 0)) throw OhxError("select_cells: NULL argument");
+  SelectCellsArgs s;
+  s.im = im;
+  s.jm = jm;
+  s.i0 = i1 - 1;
+  s.j0 = j1 - 1;
+  s.k0 = k1 - 1;
+  s.wi = i2 - i1 + 1;
+  s.wj = j2 - j1 + 1;
+  s.wk = k2 - k1 + 1;
+  s.a = a;
+  s.b = a != nullptr ? b : nullptr;
+  s.a_is2d = a_is2d != 0;
+  s.b_is2d = b_is2d != 0;
+  s.b0 = b0;
+  s.cap = cap;
+  return s;
+}
+
+GatherCellsArgs gather_args(const float* const fields[], const int32_t is2d[], int nfield, int pl_feature, int im,
+                            int jm, int km, const int64_t* cells, int64_t ncell, const float* rows) {
+  if (nfield < 1 || nfield > (int)kCellsMaxFields) throw OhxError("gather_cells: nfield must be 1..32");
+  check_grid_positive(im, jm, km);
+  if (ncell < 0) throw OhxError("gather_cells: ncell must not be negative");
+  if (fields == nullptr || is2d == nullptr || (ncell > 0 && (cells == nullptr || rows == nullptr)))
+    throw OhxError("predict_fields: NULL argument");
+  GatherCellsArgs g{};
+  for (int f = 0; f < nfield; ++f) {
+    if (fields[f] == nullptr) throw OhxError("predict_fields: field " + std::to_string(f) + " is NULL");
+    g.field[f] = fields[f];
+    if (is2d[f]) g.is2d_mask |= 1u << f;
+  }
+  g.pl_feature = pl_feature < 0 ? 0xFFFFFFFFu : (uint32_t)pl_feature;
+  g.nfield = (uint32_t)nfield;
+  g.plane = (int64_t)im * jm;
+  g.ncells_total = g.plane * km;
+  return g;
+}
+
+void scatter_check(const float* values, int64_t stride, int64_t col, const int64_t* cells, int64_t ncell,
+                   const float* out3d, int im, int jm, int km) {
+  check_grid_positive(im, jm, km);
+  if (ncell < 0) throw OhxError("scatter_cells: ncell must not be negative");
+  if (stride < 1 || col < 0 || col >= stride) throw OhxError("scatter_cells: need stride >= 1 and 0 <= col < stride");
+  if (out3d == nullptr || (ncell > 0 && (values == nullptr || cells == nullptr)))
+    throw OhxError("scatter_cells: NULL argument");
+}
+
+// the levels (0-based, inclusive) the in-range entries of a host list touch; false when there is none
+bool cells_level_range(const int64_t* cells, int64_t ncell, int64_t plane, int64_t total, int64_t* lev0, int64_t* lev1) {
+  int64_t lo = total, hi = -1;
+  for (int64_t n = 0; n < ncell; ++n) {
+    const int64_t c = cells[n];
+    if (c < 0 || c >= total) continue;
+    lo = std::min(lo, c);
+    hi = std::max(hi, c);
+  }
+  if (hi < 0) return false;
+  *lev0 = lo / plane;
+  *lev1 = hi / plane;
+  return true;
+}
+
+// a device pointer moved back by `off` floats: what the kernels index with whole-block cell indices when only a slab
+// from element `off` on is staged (nothing in front of the slab is ever addressed)
+float* slab_base(float* staged, int64_t off) {
+  return reinterpret_cast<float*>(reinterpret_cast<uintptr_t>(staged) - (uintptr_t)off * sizeof(float));
+}
+}  // namespace
+}  // extern "C++"
+
+int OHXSelectCellsDevice(int im, int jm, int km, int i1, int i2, int j1, int j2, int k1, int k2, const float* d_a,
+                         int a_is2d, const float* d_b, int b_is2d, float b0, int64_t* d_cells, int64_t cap,
+                         int64_t* d_count, uint32_t* d_status, void* stream) {
+  API_BEGIN();
+  SelectCellsArgs s = select_args(im, jm, km, i1, i2, j1, j2, k1, k2, d_a, a_is2d, d_b, b_is2d, b0, d_cells, cap, d_count);
+  const DeviceInfo dev = use_device(-1);
+  s.cells = d_cells;
+  s.count = d_count;
+  s.status = d_status;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> g(g_cells_tables.mu);
+  HIP_CHECK((hipError_t)launch_select_cells(s, cells_table(dev.ordinal, st), st));
+  API_END();
+}
+
+int OHXSelectCells(int im, int jm, int km, int i1, int i2, int j1, int j2, int k1, int k2, const float* a, int a_is2d,
+                   const float* b, int b_is2d, float b0, int64_t* cells, int64_t cap, int64_t* count) {
+  API_BEGIN();
+  SelectCellsArgs s = select_args(im, jm, km, i1, i2, j1, j2, k1, k2, a, a_is2d, b, b_is2d, b0, cells, cap, count);
+  const int64_t nbox = s.wi * s.wj * s.wk;
+  if (nbox == 0) {
+    *count = 0;
+    return 0;
+  }
+  const DeviceInfo dev = use_device(-1);
+  hipStream_t st = lib_streams(dev.ordinal).exec;
+  const int64_t plane = (int64_t)im * jm, off = plane * s.k0, slab = plane * s.wk;
+  DevBuf<float> d_a, d_b;
+  DevBuf<int64_t> d_cells, d_count;
+  DevBuf<uint64_t> d_table;
+  DevBuf<uint32_t> d_status;
+  const int64_t keep = std::min(cap, nbox);
+  d_cells.ensure((size_t)keep);
+  d_count.ensure(1);
+  d_table.ensure(kCellsMaxBlocks);
+  d_status.ensure(1);
+  // 3-D arrays: the box's levels only
+  auto stage = [&](DevBuf<float>& d, const float* h, bool two_d) -> const float* {
+    d.ensure((size_t)(two_d ? plane : slab));
+    HIP_CHECK(hipMemcpyAsync(d.p, two_d ? h : h + off, (size_t)(two_d ? plane : slab) * sizeof(float),
+                             hipMemcpyHostToDevice, st));
+    return two_d ? d.p : slab_base(d.p, off);
+  };
+  if (s.a != nullptr) s.a = stage(d_a, a, s.a_is2d != 0);
+  if (s.b != nullptr) s.b = stage(d_b, b, s.b_is2d != 0);
+  s.cells = d_cells.p;
+  s.count = d_count.p;
+  s.status = d_status.p;
+  HIP_CHECK(hipMemsetAsync(d_status.p, 0, sizeof(uint32_t), st));
+  HIP_CHECK((hipError_t)launch_select_cells(s, d_table.p, st));
+  int64_t found = 0;
+  uint32_t status = 0;
+  HIP_CHECK(hipMemcpyAsync(&found, d_count.p, sizeof(int64_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(&status, d_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  const int64_t written = std::min(found, cap);
+  if (written > 0) {
+    HIP_CHECK(hipMemcpyAsync(cells, d_cells.p, (size_t)written * sizeof(int64_t), hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+  }
+  *count = found;
+  if ((status & kCellsOverCap) != 0 || found > cap)
+    throw OhxError("select_cells: " + std::to_string(found) + " cells are selected and cap is " + std::to_string(cap) +
+                   ": the first " + std::to_string(cap) + " were written");
+  API_END();
+}
+
+int OHXGatherCellsDevice(const float* const d_fields[], const int32_t is2d[], int nfield, int pl_feature, int im, int jm,
+                         int km, const int64_t* d_cells, int64_t ncell, float* d_rows, uint32_t* d_status, void* stream) {
+  API_BEGIN();
+  const GatherCellsArgs g = gather_args(d_fields, is2d, nfield, pl_feature, im, jm, km, d_cells, ncell, d_rows);
+  if (ncell == 0) return 0;
+  (void)use_device(-1);
+  HIP_CHECK((hipError_t)launch_gather_cells(g, d_cells, ncell, d_rows, d_status, static_cast<hipStream_t>(stream)));
+  API_END();
+}
+
+int OHXGatherCells(const float* const fields[], const int32_t is2d[], int nfield, int pl_feature, int im, int jm, int km,
+                   const int64_t* cells, int64_t ncell, float* rows) {
+  API_BEGIN();
+  GatherCellsArgs g = gather_args(fields, is2d, nfield, pl_feature, im, jm, km, cells, ncell, rows);
+  if (ncell == 0) return 0;
+  const DeviceInfo dev = use_device(-1);
+  hipStream_t st = lib_streams(dev.ordinal).exec;
+  // 3-D fields: only the levels the list's cells lie on cross PCIe
+  int64_t lev0 = 0, lev1 = 0;
+  const bool any = cells_level_range(cells, ncell, g.plane, g.ncells_total, &lev0, &lev1);
+  const int64_t slab = any ? g.plane * (lev1 - lev0 + 1) : 0;
+  const int64_t off3 = g.plane * lev0;
+  std::vector<DevBuf<float>> d_field((size_t)nfield);
+  DevBuf<int64_t> d_cells;
+  DevBuf<float> d_rows;
+  DevBuf<uint32_t> d_status;
+  d_cells.ensure((size_t)ncell);
+  d_rows.ensure((size_t)ncell * (size_t)nfield);
+  d_status.ensure(1);
+  for (int f = 0; f < nfield; ++f) {
+    const int64_t n = !any ? 0 : (is2d[f] ? g.plane : slab);
+    d_field[(size_t)f].ensure((size_t)n);
+    if (n > 0)
+      HIP_CHECK(hipMemcpyAsync(d_field[(size_t)f].p, is2d[f] ? fields[f] : fields[f] + off3, (size_t)n * sizeof(float),
+                               hipMemcpyHostToDevice, st));
+    g.field[f] = is2d[f] ? d_field[(size_t)f].p : slab_base(d_field[(size_t)f].p, off3);
+  }
+  HIP_CHECK(hipMemcpyAsync(d_cells.p, cells, (size_t)ncell * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemsetAsync(d_status.p, 0, sizeof(uint32_t), st));
+  HIP_CHECK((hipError_t)launch_gather_cells(g, d_cells.p, ncell, d_rows.p, d_status.p, st));
+  uint32_t status = 0;
+  HIP_CHECK(hipMemcpyAsync(rows, d_rows.p, (size_t)ncell * (size_t)nfield * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(&status, d_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  if ((status & kCellsOutOfRange) != 0) {
+    int64_t at = 0;
+    while (at < ncell && cells[at] >= 0 && cells[at] < g.ncells_total) ++at;
+    throw OhxError("gather_cells: cell index out of range at position " + std::to_string(at) + " (" +
+                   std::to_string(at < ncell ? cells[at] : 0) + ", the block has " + std::to_string(g.ncells_total) +
+                   " cells): that row is NaN");
+  }
+  API_END();
+}
+
+int OHXScatterCellsDevice(const float* d_values, int64_t stride, int64_t col, const int64_t* d_cells, int64_t ncell,
+                          float* d_out3d, int im, int jm, int km, uint32_t* d_status, void* stream) {
+  API_BEGIN();
+  scatter_check(d_values, stride, col, d_cells, ncell, d_out3d, im, jm, km);
+  if (ncell == 0) return 0;
+  const DeviceInfo dev = use_device(-1);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  std::lock_guard<std::mutex> g(g_cells_tables.mu);
+  HIP_CHECK((hipError_t)launch_scatter_cells(d_values, stride, col, d_cells, ncell, d_out3d, (int64_t)im * jm * km,
+                                             d_status, cells_table(dev.ordinal, st), st));
+  API_END();
+}
+
+int OHXScatterCells(const float* values, int64_t stride, int64_t col, const int64_t* cells, int64_t ncell, float* out3d,
+                    int im, int jm, int km) {
+  API_BEGIN();
+  scatter_check(values, stride, col, cells, ncell, out3d, im, jm, km);
+  if (ncell == 0) return 0;
+  const DeviceInfo dev = use_device(-1);
+  hipStream_t st = lib_streams(dev.ordinal).exec;
+  const int64_t plane = (int64_t)im * jm, total = plane * km;
+  // the column alone goes up, and of out3d only the levels the list's cells lie on go up and come back
+  int64_t lev0 = 0, lev1 = 0;
+  const bool any = cells_level_range(cells, ncell, plane, total, &lev0, &lev1);
+  const int64_t off = plane * lev0, slab = any ? plane * (lev1 - lev0 + 1) : 0;
+  std::vector<float> column((size_t)ncell);
+  for (int64_t n = 0; n < ncell; ++n) column[(size_t)n] = values[n * stride + col];
+  DevBuf<float> d_values, d_out;
+  DevBuf<int64_t> d_cells;
+  DevBuf<uint64_t> d_table;
+  DevBuf<uint32_t> d_status;
+  d_values.ensure((size_t)ncell);
+  d_cells.ensure((size_t)ncell);
+  d_out.ensure((size_t)slab);
+  d_table.ensure(kCellsMaxBlocks);
+  d_status.ensure(1);
+  HIP_CHECK(hipMemcpyAsync(d_values.p, column.data(), (size_t)ncell * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemcpyAsync(d_cells.p, cells, (size_t)ncell * sizeof(int64_t), hipMemcpyHostToDevice, st));
+  if (any) HIP_CHECK(hipMemcpyAsync(d_out.p, out3d + off, (size_t)slab * sizeof(float), hipMemcpyHostToDevice, st));
+  HIP_CHECK(hipMemsetAsync(d_status.p, 0, sizeof(uint32_t), st));
+  HIP_CHECK((hipError_t)launch_scatter_cells(d_values.p, 1, 0, d_cells.p, ncell, slab_base(d_out.p, off), total,
+                                             d_status.p, d_table.p, st));
+  uint32_t status = 0;
+  if (any) HIP_CHECK(hipMemcpyAsync(out3d + off, d_out.p, (size_t)slab * sizeof(float), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipMemcpyAsync(&status, d_status.p, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  if (status != 0) {
+    int64_t top = INT64_MIN;
+    for (int64_t n = 0; n < ncell; ++n) {
+      const int64_t c = cells[n];
+      if (c < 0 || c >= total)
+        throw OhxError("scatter_cells: cell index out of range at position " + std::to_string(n) + " (" +
+                       std::to_string(c) + ", the block has " + std::to_string(total) + " cells): skipped");
+      if (c <= top)
+        throw OhxError("scatter_cells: cells must be strictly ascending: position " + std::to_string(n) + " holds " +
+                       std::to_string(c) + " after " + std::to_string(top) + ": skipped");
+      top = c;
+    }
+    throw OhxError("scatter_cells: the kernel reported status " + std::to_string(status));
+  }
   API_END();
 }
 

@@ -19,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "cells.hpp"
 #include "flatten.hpp"
 #include "forest.hpp"
 #include "synth_common.h"
@@ -383,6 +384,18 @@ int ohx_cat_flatten_cpu(const uint8_t* model, uint64_t model_len, uint32_t* node
     g_err = e.what();
     return -1;
   }
+}
+
+// The launch shapes of the selected-gridcells calls (cells.hpp): plan[0], plan[1] = blocks and items per block of an
+// ordered pass over n items (the selection's box cells, the scatter's entries); plan[2] = floats between two lanes'
+// rows in the gather's LDS tile; plan[3] = waves (blocks) of a gather of n cells.
+int ohx_cells_plan(uint64_t n, uint32_t nfield, uint64_t* plan) {
+  const CellsPassPlan p = plan_cells_pass(n);
+  plan[0] = p.blocks;
+  plan[1] = p.chunk;
+  plan[2] = cells_gather_lds_stride(nfield);
+  plan[3] = (n + kCellsWave - 1) / kCellsWave;
+  return 0;
 }
 
 }  // extern "C"

@@ -18,6 +18,8 @@ module ohx_bindings
    public :: OHXBoosterPredictInteractions, OHXBoosterPredictContribsFields, OHXBoosterPredictContribsFieldsDevice
    public :: OHXCommGetUniqueId, OHXCommInitRank, OHXCommFree, OHXCommInfo, OHXShardRows, OHXAllGatherOH, OHX_UNIQUE_ID_BYTES
    public :: OHXBoosterGetNumCategoricalSplits
+   public :: OHXSelectCells, OHXSelectCellsDevice, OHXGatherCells, OHXGatherCellsDevice
+   public :: OHXScatterCells, OHXScatterCellsDevice
    public :: ohx_last_error, ohx_c_string
 
    integer, parameter :: OHX_UNIQUE_ID_BYTES = 128
@@ -178,6 +180,88 @@ module ohx_bindings
          integer(c_int), value          :: approximate, ntree_limit
          type(c_ptr), intent(in)        :: d_out(*)
          type(c_ptr), value             :: stream
+         integer(c_int)                 :: rc
+      end function
+
+      ! Selected gridcells (ohxgb.h part 2): a cell index is c = (i-1) + im*((j-1) + jm*(k-1)), integer(c_int64_t).
+      ! Declarations only, as above.  a, b: c_loc of an (im,jm,km) array, or of an (im,jm) one with a_is2d / b_is2d
+      ! /= 0; c_null_ptr for none (b: the scalar b0; a: every cell of the box).  cells holds cap entries.
+      function OHXSelectCells(im, jm, km, i1, i2, j1, j2, k1, k2, a, a_is2d, b, b_is2d, b0, cells, cap, count) &
+            bind(C, name="OHXSelectCells") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         integer(c_int), value          :: im, jm, km, i1, i2, j1, j2, k1, k2
+         type(c_ptr), value             :: a, b
+         integer(c_int), value          :: a_is2d, b_is2d
+         real(c_float), value           :: b0
+         integer(c_int64_t)             :: cells(*)
+         integer(c_int64_t), value      :: cap
+         integer(c_int64_t), intent(out) :: count
+         integer(c_int)                 :: rc
+      end function
+
+      ! The same on device addresses: d_cells, d_count (one int64) and d_status (one int32 of bits, or c_null_ptr) are
+      ! device pointers; enqueued on `stream`.
+      function OHXSelectCellsDevice(im, jm, km, i1, i2, j1, j2, k1, k2, d_a, a_is2d, d_b, b_is2d, b0, d_cells, cap, &
+                                    d_count, d_status, stream) bind(C, name="OHXSelectCellsDevice") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         integer(c_int), value          :: im, jm, km, i1, i2, j1, j2, k1, k2
+         type(c_ptr), value             :: d_a, d_b
+         integer(c_int), value          :: a_is2d, b_is2d
+         real(c_float), value           :: b0
+         type(c_ptr), value             :: d_cells
+         integer(c_int64_t), value      :: cap
+         type(c_ptr), value             :: d_count, d_status, stream
+         integer(c_int)                 :: rc
+      end function
+
+      ! rows(nfield, ncell): column n is the row of cell cells(n); fields / is2d / pl_feature as OHXBoosterPredictFields.
+      function OHXGatherCells(fields, is2d, nfield, pl_feature, im, jm, km, cells, ncell, rows) &
+            bind(C, name="OHXGatherCells") result(rc)
+         import :: c_int, c_ptr, c_float, c_int32_t, c_int64_t
+         type(c_ptr), intent(in)        :: fields(*)
+         integer(c_int32_t), intent(in) :: is2d(*)
+         integer(c_int), value          :: nfield, pl_feature, im, jm, km
+         integer(c_int64_t), intent(in) :: cells(*)
+         integer(c_int64_t), value      :: ncell
+         real(c_float)                  :: rows(*)
+         integer(c_int)                 :: rc
+      end function
+
+      function OHXGatherCellsDevice(d_fields, is2d, nfield, pl_feature, im, jm, km, d_cells, ncell, d_rows, d_status, &
+                                    stream) bind(C, name="OHXGatherCellsDevice") result(rc)
+         import :: c_int, c_ptr, c_int32_t, c_int64_t
+         type(c_ptr), intent(in)        :: d_fields(*)
+         integer(c_int32_t), intent(in) :: is2d(*)
+         integer(c_int), value          :: nfield, pl_feature, im, jm, km
+         type(c_ptr), value             :: d_cells
+         integer(c_int64_t), value      :: ncell
+         type(c_ptr), value             :: d_rows, d_status, stream
+         integer(c_int)                 :: rc
+      end function
+
+      ! out3d(cells(n)) = values(col + 1, n) for values(stride, ncell); cells strictly ascending.
+      function OHXScatterCells(values, stride, col, cells, ncell, out3d, im, jm, km) &
+            bind(C, name="OHXScatterCells") result(rc)
+         import :: c_int, c_float, c_int64_t
+         real(c_float), intent(in)      :: values(*)
+         integer(c_int64_t), value      :: stride, col
+         integer(c_int64_t), intent(in) :: cells(*)
+         integer(c_int64_t), value      :: ncell
+         real(c_float)                  :: out3d(*)
+         integer(c_int), value          :: im, jm, km
+         integer(c_int)                 :: rc
+      end function
+
+      function OHXScatterCellsDevice(d_values, stride, col, d_cells, ncell, d_out3d, im, jm, km, d_status, stream) &
+            bind(C, name="OHXScatterCellsDevice") result(rc)
+         import :: c_int, c_ptr, c_int64_t
+         type(c_ptr), value             :: d_values
+         integer(c_int64_t), value      :: stride, col
+         type(c_ptr), value             :: d_cells
+         integer(c_int64_t), value      :: ncell
+         type(c_ptr), value             :: d_out3d
+         integer(c_int), value          :: im, jm, km
+         type(c_ptr), value             :: d_status, stream
          integer(c_int)                 :: rc
       end function
 

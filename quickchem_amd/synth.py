@@ -68,6 +68,7 @@ def _load():
                                          C.c_uint, C.c_void_p]
         lib.ohx_contribs_table_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_contribs_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
+        lib.ohx_cells_plan.argtypes = [C.c_uint64, C.c_uint32, C.POINTER(C.c_uint64)]
         lib.ohx_interactions_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float,
                                              C.c_int, C.c_uint, C.c_void_p]
         lib.ohx_interactions_table_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -232,6 +233,15 @@ def contribs_plan(nrow: int, nfeat: int, ntree: int, allow_split: bool = True):
     p = (C.c_uint64 * 4)()
     _check(_load().ohx_contribs_plan(nrow, nfeat, ntree, 1 if allow_split else 0, p))
     return bool(p[0]), int(p[1]), int(p[2]), int(p[3])
+
+
+def cells_plan(n: int, nfield: int = 27):
+    """The launch shapes of the selected-gridcells calls (csrc/cells.hpp): (blocks, items_per_block) of an ordered pass
+    over `n` items - the selection's box cells, the scatter's list entries - then the gather's LDS lane stride in
+    floats for `nfield` fields and its waves for `n` cells."""
+    p = (C.c_uint64 * 4)()
+    _check(_load().ohx_cells_plan(n, nfield, p))
+    return int(p[0]), int(p[1]), int(p[2]), int(p[3])
 
 
 def interactions_cpu(image, rows: np.ndarray, num_feature: int, missing: float = XX_MISS, approximate: bool = False,
