@@ -203,7 +203,12 @@ struct DevBuf {
   void ensure(size_t count) {
     if (count <= n) return;
     release();
-    HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)));
+    try {
+      HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T)));
+    } catch (const OhxError&) {
+      (void)hipGetLastError();   // forgotten here: left with the runtime, it would surface again as the error of the next launch
+      throw;
+    }
     n = count;
   }
   void upload(const std::vector<T>& h) {
@@ -230,7 +235,12 @@ struct PinnedBuf {
     if (p) (void)hipHostFree(p);
     p = nullptr;
     n = 0;
-    HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+    try {
+      HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&p), std::max<size_t>(count, 1) * sizeof(T), hipHostMallocDefault));
+    } catch (const OhxError&) {
+      (void)hipGetLastError();   // as DevBuf::ensure
+      throw;
+    }
     n = count;
   }
 };
@@ -1468,7 +1478,7 @@ void launch_predict_groups(BoosterObj& b, DMatrixObj& d, int option_mask, unsign
   HIP_CHECK(launch_group_finish(b.d_planes.p, n, G, finish, d_out, stream));
 }
 
-// Per-feature contributions: every refusal is decided here, before anything is enqueued.  What a mode needs is built at
+// The tables of an explanation call, and the refusals that come with them.  What a mode needs is built at
 // its first call on the loaded model (contribs.hpp), on the booster's CURRENT device: the booster is uploaded first
 // (ensure_uploaded: it may just have been moved by "ohx_device"), and device tables left on another device are
 // released and built again here - so nothing a caller takes from the state or the booster afterwards (buffers,
@@ -1540,223 +1550,283 @@ ContribsState& contribs_tables(BoosterObj& b, bool approximate, bool interaction
   return c;
 }
 
-// Checks, builds what the mode needs, then enqueues the launches: the host form (d_out null) on the library's stream
-// of the booster's device, into the state's own output buffer; the device form on `stream`.  Returns the state, which
-// nothing drops before the next contribs call on the booster.
-ContribsState& launch_contribs_checked(BoosterObj& b, DMatrixObj& d, int approximate, unsigned ntree_limit,
-                                       float* d_out, bool host_form, hipStream_t stream) {
-  if (approximate != 0 && approximate != 1) throw OhxError("approximate must be 0 (exact TreeSHAP) or 1");
+// (shared with the selected-gridcells calls, which take no booster)
+void check_grid_positive(int im, int jm, int km) {
+  if (im <= 0 || jm <= 0 || km <= 0) throw OhxError("predict_fields: im, jm, km must be positive");
+}
+
+// the fields forms' checks of the grid and the field count (predict and contributions)
+void check_fields_shape(const BoosterObj& b, int nfield, int im, int jm, int km, int k1, int k2) {
+  if (nfield < 0 || nfield > 32) throw OhxError("predict_fields: nfield must be 0..32");
+  if ((uint32_t)nfield > b.forest.num_feature)
+    throw OhxError("Number of columns does not match number of features in booster (" + std::to_string(nfield) +
+                   " vs. " + std::to_string(b.forest.num_feature) + ")");
+  if (b.forest.num_feature > 32) throw OhxError("predict_fields supports boosters with at most 32 features");
+  check_grid_positive(im, jm, km);
+  if (k1 < 1 || k2 > km || k2 < k1 - 1) throw OhxError("predict_fields: need 1 <= k1, k2 <= km, k2 >= k1 - 1");
+}
+
+// The fields forms' preamble, into any of their argument structs (FieldsArgs, FieldsContribsArgs, GatherCellsArgs): which
+// fields are (im,jm), the feature divided by 100 or none, the field count - and no field NULL (`fields` null: the caller
+// looks at its fields itself, as it stages them).
+template <class Args>
+void fields_preamble(Args& a, const float* const fields[], const int32_t is2d[], int nfield, int pl_feature) {
+  a.is2d_mask = 0;
+  for (int f = 0; f < nfield; ++f) {
+    if (fields != nullptr && fields[f] == nullptr) throw OhxError("predict_fields: field " + std::to_string(f) + " is NULL");
+    if (is2d[f]) a.is2d_mask |= 1u << f;
+  }
+  a.pl_feature = pl_feature < 0 ? 0xFFFFFFFFu : (uint32_t)pl_feature;
+  a.nfield = (uint32_t)nfield;
+}
+
+// ---- explanations: feature contributions and SHAP interaction values (docs/12_contributions.md, "The call path") ----
+//
+// One path for all eight ABI functions, each step once: explain_refusals, explain_args / interactions_args, then in
+// explain() the room, the enqueue and, for a host form, finish_host_form.  Every refusal and every allocation comes
+// before anything is enqueued.
+
+// the fields forms' arguments, as the ABI takes them (host or device pointers, by the form)
+struct FieldsSource {
+  const float* const* fields;
+  const int32_t* is2d;
+  int nfield, pl_feature, im, jm, km, k1, k2;
+  float missing;
+  float* const* out;               // [F + 1], NULL = not stored
+};
+
+// What one call asks for.  The source is a DMatrix (rows forms) or the fields arguments (fields forms).
+struct ExplainCall {
+  const char* name = "";           // the ABI function, for the messages
+  bool interactions = false;       // SHAP interaction values, else feature contributions
+  int approximate = 0;             // as given: refused unless 0 or 1
+  unsigned ntree_limit = 0;
+  bool host_form = false;          // on the library's stream, through the state's buffers; else enqueued on `stream`
+  hipStream_t stream = nullptr;
+  DMatrixObj* d = nullptr;         // rows forms
+  float* d_out = nullptr;          // rows forms, device form
+  const FieldsSource* fs = nullptr;
+};
+struct ExplainResult {
+  size_t count = 0;                // floats of a rows form's output
+  float* host = nullptr;           // the host form's copy of it
+};
+
+// Every refusal, in the order the forms have always had, building on the way what the mode needs (contribs_tables:
+// after it the booster is settled on its device, so its stream and the state's buffers may be taken).  A fields form's
+// preamble goes to `fa`.
+ContribsState& explain_refusals(BoosterObj& b, const ExplainCall& q, FieldsContribsArgs& fa) {
+  const FieldsSource* fs = q.fs;
+  if (fs != nullptr && (fs->fields == nullptr || fs->is2d == nullptr || fs->out == nullptr))
+    throw OhxError("predict_fields: NULL argument");
+  if (q.approximate != 0 && q.approximate != 1) throw OhxError("approximate must be 0 (exact TreeSHAP) or 1");
   if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
-  if (!host_form && d_out == nullptr && d.nrow != 0) throw OhxError("OHXBoosterPredictContribsDevice: d_out is NULL");
+  if (fs == nullptr && !q.host_form && q.d_out == nullptr && q.d->nrow != 0)
+    throw OhxError(std::string(q.name) + ": d_out is NULL");
   // before the tables are built: building them waits for the library's stream
-  if (!host_form && stream_capturing(stream))
-    refuse_in_capture("compute feature contributions",
-                      "OHXBoosterPredictContribsDevice is not capturable; call it outside the capture");
-  check_columns(b, d.ncol);
-  ContribsState& c = contribs_tables(b, approximate != 0);
+  if (!q.host_form && stream_capturing(q.stream))
+    refuse_in_capture(q.interactions ? "compute SHAP interaction values" : "compute feature contributions",
+                      (std::string(q.name) + " is not capturable; call it outside the capture").c_str());
+  if (fs != nullptr) {
+    check_fields_shape(b, fs->nfield, fs->im, fs->jm, fs->km, fs->k1, fs->k2);
+    fields_preamble(fa, fs->fields, fs->is2d, fs->nfield, fs->pl_feature);
+    bool any_out = false;
+    for (uint32_t f = 0; f <= b.forest.num_feature; ++f) any_out |= fs->out[f] != nullptr;
+    if (!any_out) throw OhxError("feature contributions from fields: every entry of out is NULL");
+  } else {
+    check_columns(b, q.d->ncol);
+  }
+  ContribsState& c = contribs_tables(b, q.approximate != 0, q.interactions);
+  if (fs != nullptr) return c;
+  const DMatrixObj& d = *q.d;
   if (d.device >= 0 && d.device != b.dev.ordinal)
     throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
                    std::to_string(b.dev.ordinal));
-  const uint32_t F = b.forest.num_feature;
+  if (q.interactions) {
+    const uint64_t F1 = (uint64_t)b.forest.num_feature + 1, W = F1 * F1, G = b.num_groups;
+    if (d.nrow > (uint64_t)(SIZE_MAX / sizeof(float)) / (W * G))
+      throw OhxError("SHAP interaction values: " + std::to_string(d.nrow) + " rows of " +
+                     (G >= 2 ? std::to_string(G) + " x " : std::string()) + std::to_string(W) +
+                     " floats do not fit in memory");
+  }
+  return c;
+}
+
+// The one place a ContribsArgs gets its trees, its bias and the mode's tables; the caller adds the rows and the output.
+ContribsArgs explain_args(const BoosterObj& b, const ContribsState& c, uint32_t t0, uint32_t t1) {
   ContribsArgs a;
-  a.rows = d.d_data;
-  a.nrow = d.nrow;
-  a.ncol = (uint32_t)d.ncol;
-  a.missing = d.missing;
-  a.nfeat = F;
-  tree_range(b, ntree_limit, &a.tree_begin, &a.tree_end);
-  a.bias = contrib_bias(b.flat(), c.means, a.tree_begin, a.tree_end, b.margin_base);
+  a.nfeat = b.forest.num_feature;
+  a.tree_begin = t0;
+  a.tree_end = t1;
+  a.bias = contrib_bias(b.flat(), c.means, t0, t1, b.margin_base);
   a.heads = c.d_heads.p;
   a.elems = c.d_elems.p;
   a.class_start = c.d_class_start.p;
   a.coef = c.d_coef.p;
   a.nodes = c.d_nodes.p;
   a.roots = c.d_roots.p;
-  if (b.num_groups >= 2) {
-    // several output groups: [nrow][G][F+1], each group's block the computation over its tree range, into the state's
-    // block buffer and from there to its place in the output
-    const uint32_t G = b.num_groups;
-    const uint64_t W = (uint64_t)F + 1;
-    const std::vector<uint32_t> cnt = group_tree_counts(b, group_tree_limit(b, ntree_limit));
-    uint64_t part = 0;
-    for (uint32_t g = 0; g < G; ++g) part = std::max(part, plan_contribs(d.nrow, F, cnt[g], b.contribs_split).part_floats);
-    if (host_form) {
-      stream = b.s_exec;
-      if (d.owned == nullptr) order_behind_caller(b.dev.ordinal, stream);
-      c.d_out.ensure((size_t)(d.nrow * G * W));
-      d_out = c.d_out.p;
-      a.flags = c.d_flags.p;
-    }
-    c.d_gblock.ensure((size_t)(d.nrow * W));
-    if (part) c.d_part.ensure((size_t)part);
-    for (uint32_t g = 0; g < G; ++g) {
-      a.tree_begin = b.group_begin[g];
-      a.tree_end = a.tree_begin + cnt[g];
-      a.bias = contrib_bias(b.flat(), c.means, a.tree_begin, a.tree_end, b.margin_base);
-      a.out = c.d_gblock.p;
-      const ContribsPlan gplan = plan_contribs(d.nrow, F, cnt[g], b.contribs_split);
-      HIP_CHECK((hipError_t)launch_contribs(approximate != 0, a, gplan, c.d_part.p, stream));
-      HIP_CHECK(launch_group_block_scatter(c.d_gblock.p, d.nrow, (uint32_t)W, G, g, d_out, stream));
-    }
-    return c;
-  }
-  const ContribsPlan plan = plan_contribs(d.nrow, F, a.tree_end - a.tree_begin, b.contribs_split);
-  if (host_form) {
-    stream = b.s_exec;                       // taken after contribs_tables: the booster's current device
-    if (d.owned == nullptr) order_behind_caller(b.dev.ordinal, stream);
-    c.d_out.ensure((size_t)d.nrow * (F + 1));
-    d_out = c.d_out.p;
-    a.flags = c.d_flags.p;
-  }
-  a.out = d_out;
-  if (plan.split) c.d_part.ensure((size_t)plan.part_floats);
-  HIP_CHECK((hipError_t)launch_contribs(approximate != 0, a, plan, c.d_part.p, stream));
-  return c;
+  return a;
 }
 
-// SHAP interaction values of a booster of several output groups: [nrow][G][F+1][F+1], each group's block the
-// computation over its tree range (contributions into the state's phi, then the matrix into its block buffer, then the
-// block to its place in the output).  Allocations before anything is enqueued, as below.
-ContribsState& launch_interactions_groups(BoosterObj& b, DMatrixObj& d, ContribsState& c, ContribsArgs a,
-                                          int approximate, unsigned ntree_limit, float* d_out, bool host_form,
-                                          hipStream_t stream) {
-  const uint32_t G = b.num_groups, F = b.forest.num_feature;
-  const uint64_t F1 = (uint64_t)F + 1, W = F1 * F1;
-  if (d.nrow > (uint64_t)(SIZE_MAX / sizeof(float)) / (W * G))
-    throw OhxError("SHAP interaction values: " + std::to_string(d.nrow) + " rows of " + std::to_string(G) + " x " +
-                   std::to_string(W) + " floats do not fit in memory");
-  const std::vector<uint32_t> cnt = group_tree_counts(b, group_tree_limit(b, ntree_limit));
-  uint64_t part = 0;
-  for (uint32_t g = 0; g < G; ++g) {
-    part = std::max(part, plan_contribs(d.nrow, F, cnt[g], b.contribs_split).part_floats);
-    if (!approximate) part = std::max(part, plan_interactions(d.nrow, F, cnt[g], b.contribs_split).part_floats);
-  }
-  if (host_form) {
-    stream = b.s_exec;
-    if (d.owned == nullptr) order_behind_caller(b.dev.ordinal, stream);
-  }
-  try {
-    if (host_form) {
-      c.d_iout.ensure((size_t)(d.nrow * G * W));
-      c.h_iout.ensure((size_t)(d.nrow * G * W));
-    }
-    c.d_iphi.ensure((size_t)(d.nrow * F1));
-    c.d_gblock.ensure((size_t)(d.nrow * W));
-    if (part) c.d_ipart.ensure((size_t)part);
-  } catch (const OhxError&) {
-    (void)hipGetLastError();
-    throw;
-  }
-  if (host_form) {
-    d_out = c.d_iout.p;
-    a.flags = c.d_flags.p;
-  }
+// ... and an InteractionsArgs: the rows and trees of `a`, whose output is the phi this one reads.
+InteractionsArgs interactions_args(const ContribsArgs& a, const ContribsState& c, float* out) {
   InteractionsArgs ia;
   ia.rows = a.rows;
   ia.nrow = a.nrow;
   ia.ncol = a.ncol;
   ia.missing = a.missing;
-  ia.nfeat = F;
-  ia.phi = c.d_iphi.p;
-  ia.out = c.d_gblock.p;
-  ia.heads = c.d_heads.p;
-  ia.elems = c.d_elems.p;
-  ia.fpaths = c.d_fpaths.p;
-  ia.fstart = c.d_fstart.p;
-  ia.coef = c.d_coef.p;
-  for (uint32_t g = 0; g < G; ++g) {
-    a.tree_begin = ia.tree_begin = b.group_begin[g];
-    a.tree_end = ia.tree_end = a.tree_begin + cnt[g];
-    a.bias = contrib_bias(b.flat(), c.means, a.tree_begin, a.tree_end, b.margin_base);
-    a.out = c.d_iphi.p;
-    const ContribsPlan cplan = plan_contribs(d.nrow, F, cnt[g], b.contribs_split);
-    const ContribsPlan iplan = approximate ? ContribsPlan{} : plan_interactions(d.nrow, F, cnt[g], b.contribs_split);
-    HIP_CHECK((hipError_t)launch_contribs(approximate != 0, a, cplan, c.d_ipart.p, stream));
-    HIP_CHECK((hipError_t)launch_interactions(approximate != 0, ia, iplan, c.d_ipart.p, stream));
-    HIP_CHECK(launch_group_block_scatter(c.d_gblock.p, d.nrow, (uint32_t)W, G, g, d_out, stream));
-  }
-  return c;
-}
-
-// SHAP interaction values, as launch_contribs_checked: every refusal and every allocation before anything is
-// enqueued.  The contributions phi go to the state's own scratch (the contribs launch, same plan as a contribs call),
-// then the matrix is filled behind them on the same stream.
-ContribsState& launch_interactions_checked(BoosterObj& b, DMatrixObj& d, int approximate, unsigned ntree_limit,
-                                           float* d_out, bool host_form, hipStream_t stream) {
-  if (approximate != 0 && approximate != 1) throw OhxError("approximate must be 0 (exact TreeSHAP) or 1");
-  if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
-  if (!host_form && d_out == nullptr && d.nrow != 0)
-    throw OhxError("OHXBoosterPredictInteractionsDevice: d_out is NULL");
-  if (!host_form && stream_capturing(stream))
-    refuse_in_capture("compute SHAP interaction values",
-                      "OHXBoosterPredictInteractionsDevice is not capturable; call it outside the capture");
-  check_columns(b, d.ncol);
-  ContribsState& c = contribs_tables(b, approximate != 0, true);
-  if (d.device >= 0 && d.device != b.dev.ordinal)
-    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
-                   std::to_string(b.dev.ordinal));
-  const uint32_t F = b.forest.num_feature;
-  const uint64_t F1 = (uint64_t)F + 1;
-  if (d.nrow > (uint64_t)(SIZE_MAX / sizeof(float)) / (F1 * F1))
-    throw OhxError("SHAP interaction values: " + std::to_string(d.nrow) + " rows of " + std::to_string(F1 * F1) +
-                   " floats do not fit in memory");
-  ContribsArgs a;
-  a.rows = d.d_data;
-  a.nrow = d.nrow;
-  a.ncol = (uint32_t)d.ncol;
-  a.missing = d.missing;
-  a.nfeat = F;
-  tree_range(b, ntree_limit, &a.tree_begin, &a.tree_end);
-  a.bias = contrib_bias(b.flat(), c.means, a.tree_begin, a.tree_end, b.margin_base);
-  a.heads = c.d_heads.p;
-  a.elems = c.d_elems.p;
-  a.class_start = c.d_class_start.p;
-  a.coef = c.d_coef.p;
-  a.nodes = c.d_nodes.p;
-  a.roots = c.d_roots.p;
-  if (b.num_groups >= 2) return launch_interactions_groups(b, d, c, a, approximate, ntree_limit, d_out, host_form, stream);
-  const uint32_t ntree = a.tree_end - a.tree_begin;
-  const ContribsPlan cplan = plan_contribs(d.nrow, F, ntree, b.contribs_split);
-  const ContribsPlan iplan = approximate ? ContribsPlan{} : plan_interactions(d.nrow, F, ntree, b.contribs_split);
-  if (host_form) {
-    stream = b.s_exec;
-    if (d.owned == nullptr) order_behind_caller(b.dev.ordinal, stream);
-  }
-  try {
-    if (host_form) {
-      c.d_iout.ensure((size_t)(d.nrow * F1 * F1));
-      c.h_iout.ensure((size_t)(d.nrow * F1 * F1));
-    }
-    c.d_iphi.ensure((size_t)(d.nrow * F1));
-    const uint64_t part = std::max(cplan.part_floats, iplan.part_floats);
-    if (part) c.d_ipart.ensure((size_t)part);
-  } catch (const OhxError&) {
-    (void)hipGetLastError();   // a failed allocation must not surface again as the error of a later launch
-    throw;
-  }
-  if (host_form) {
-    d_out = c.d_iout.p;
-    a.flags = c.d_flags.p;
-  }
-  a.out = c.d_iphi.p;
-  HIP_CHECK((hipError_t)launch_contribs(approximate != 0, a, cplan, c.d_ipart.p, stream));
-  InteractionsArgs ia;
-  ia.rows = a.rows;
-  ia.nrow = a.nrow;
-  ia.ncol = a.ncol;
-  ia.missing = a.missing;
-  ia.nfeat = F;
+  ia.nfeat = a.nfeat;
   ia.tree_begin = a.tree_begin;
   ia.tree_end = a.tree_end;
-  ia.phi = c.d_iphi.p;
-  ia.out = d_out;
+  ia.phi = a.out;
+  ia.out = out;
   ia.heads = c.d_heads.p;
   ia.elems = c.d_elems.p;
   ia.fpaths = c.d_fpaths.p;
   ia.fstart = c.d_fstart.p;
   ia.coef = c.d_coef.p;
-  HIP_CHECK((hipError_t)launch_interactions(approximate != 0, ia, iplan, c.d_ipart.p, stream));
-  return c;
+  return ia;
+}
+
+// The end of a host form: the output (or each requested output's slab) and the inf flag come back, and a set flag is
+// cleared for the next call and refused.
+struct CopyBack {
+  float* dst;
+  const float* src;
+  size_t count;
+};
+void finish_host_form(ContribsState& c, hipStream_t s, const std::vector<CopyBack>& copies) {
+  for (const CopyBack& k : copies)
+    if (k.count) HIP_CHECK(hipMemcpyAsync(k.dst, k.src, k.count * sizeof(float), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipMemcpyAsync(c.h_flags.p, c.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HIP_CHECK(hipStreamSynchronize(s));
+  if (c.h_flags.p[0] != 0) {
+    HIP_CHECK(hipMemsetAsync(c.d_flags.p, 0, sizeof(uint32_t), s));
+    HIP_CHECK(hipStreamSynchronize(s));
+    throw OhxError("Input data contains `inf` or `nan`");
+  }
+}
+
+// The call.  A single-group booster is one tree range written straight to the output; several output groups are one
+// range each - [nrow][G][W], W = F+1 or (F+1)^2 - computed into the state's block buffer and scattered from there to
+// the group's place.  Contributions keep d_out / h_out / d_part and interactions d_iout / h_iout / d_ipart: a result
+// stays valid until the next call of its own kind (include/ohxgb.h).  Returns what a rows host form hands back; the
+// state is dropped by nothing before the next explanation call on the booster.
+ExplainResult explain(BoosterObj& b, const ExplainCall& q) {
+  FieldsContribsArgs fa;
+  ContribsState& c = explain_refusals(b, q, fa);
+  const FieldsSource* fs = q.fs;
+  if (fs != nullptr && fs->k2 < fs->k1) return {};
+  const bool approx = q.approximate != 0;
+  const uint32_t F = b.forest.num_feature, G = b.num_groups;
+  const uint64_t F1 = (uint64_t)F + 1, W = q.interactions ? F1 * F1 : F1;
+  const uint64_t plane = fs ? (uint64_t)fs->im * (uint64_t)fs->jm : 0;
+  const uint64_t nrow = fs ? plane * (uint64_t)(fs->k2 - fs->k1 + 1) : q.d->nrow;
+  const uint64_t slab = fs ? plane * (uint64_t)(fs->k1 - 1) : 0;     // floats from a 3-D array's start to level k1
+
+  // the tree ranges and their launch shapes
+  struct Range {
+    uint32_t t0, t1;
+    ContribsPlan cplan, iplan;
+  };
+  std::vector<Range> ranges(G >= 2 ? G : 1);
+  if (G >= 2) {
+    const std::vector<uint32_t> cnt = group_tree_counts(b, group_tree_limit(b, q.ntree_limit));
+    for (uint32_t g = 0; g < G; ++g) {
+      ranges[g].t0 = b.group_begin[g];
+      ranges[g].t1 = ranges[g].t0 + cnt[g];
+    }
+  } else {
+    tree_range(b, q.ntree_limit, &ranges[0].t0, &ranges[0].t1);
+  }
+  uint64_t part = 0;
+  for (Range& r : ranges) {
+    r.cplan = plan_contribs(nrow, F, r.t1 - r.t0, b.contribs_split);
+    if (q.interactions && !approx) r.iplan = plan_interactions(nrow, F, r.t1 - r.t0, b.contribs_split);
+    part = std::max({part, r.cplan.part_floats, r.iplan.part_floats});
+  }
+
+  // room: every buffer of the call, before the first enqueue
+  DevBuf<float>& d_part = q.interactions ? c.d_ipart : c.d_part;
+  ExplainResult res;
+  float* out = q.d_out;
+  if (fs != nullptr) {
+    if (q.host_form) {
+      uint32_t nout = 0;
+      for (uint32_t f = 0; f <= F; ++f) nout += fs->out[f] != nullptr ? 1u : 0u;
+      if (c.d_fstage.size() < (size_t)fs->nfield) c.d_fstage.resize((size_t)fs->nfield);
+      for (int f = 0; f < fs->nfield; ++f) c.d_fstage[(size_t)f].ensure(fs->is2d[f] ? plane : nrow);
+      c.d_fout.ensure((size_t)(nout * nrow));
+    }
+  } else {
+    res.count = (size_t)(nrow * G * W);
+    if (q.host_form) {
+      DevBuf<float>& d_res = q.interactions ? c.d_iout : c.d_out;
+      PinnedBuf<float>& h_res = q.interactions ? c.h_iout : c.h_out;
+      d_res.ensure(res.count);
+      h_res.ensure(res.count);
+      out = d_res.p;
+      res.host = h_res.p;
+    }
+    if (q.interactions) c.d_iphi.ensure((size_t)(nrow * F1));
+    if (G >= 2) c.d_gblock.ensure((size_t)(nrow * W));
+  }
+  if (part) d_part.ensure((size_t)part);
+
+  // enqueue: a host form on the library's stream of the booster's device, behind what the caller's default stream
+  // holds for a matrix that borrows the caller's rows
+  hipStream_t stream = q.host_form ? b.s_exec : q.stream;
+  std::vector<CopyBack> back;
+  if (fs != nullptr) {
+    fa.missing = fs->missing;
+    fa.plane = plane;
+    fa.nrow = nrow;
+    if (q.host_form) {
+      // 3-D fields: the slab's levels only, as the fields predict stages them
+      for (int f = 0; f < fs->nfield; ++f) {
+        float* dst = c.d_fstage[(size_t)f].p;
+        const bool flat = fs->is2d[f] != 0;
+        HIP_CHECK(hipMemcpyAsync(dst, fs->fields[f] + (flat ? 0 : slab), (flat ? plane : nrow) * sizeof(float),
+                                 hipMemcpyHostToDevice, stream));
+        fa.field[f] = dst;
+      }
+      for (uint32_t f = 0; f <= F; ++f) {
+        if (fs->out[f] == nullptr) continue;
+        fa.out[f] = c.d_fout.p + back.size() * (size_t)nrow;
+        back.push_back({fs->out[f] + slab, fa.out[f], (size_t)nrow});
+      }
+      fa.flags = c.d_flags.p;
+    } else {
+      for (int f = 0; f < fs->nfield; ++f) fa.field[f] = fs->fields[f];
+      for (uint32_t f = 0; f <= F; ++f) fa.out[f] = fs->out[f];
+      fa.src_off = fa.out_off = slab;
+    }
+  } else if (q.host_form) {
+    if (q.d->owned == nullptr) order_behind_caller(b.dev.ordinal, stream);
+    back.push_back({res.host, out, res.count});
+  }
+  for (uint32_t g = 0; g < (uint32_t)ranges.size(); ++g) {
+    const Range& r = ranges[g];
+    ContribsArgs a = explain_args(b, c, r.t0, r.t1);
+    float* target = G >= 2 ? c.d_gblock.p : out;
+    if (fs != nullptr) {
+      a.missing = fs->missing;
+      HIP_CHECK((hipError_t)launch_contribs_fields(approx, a, fa, r.cplan, d_part.p, stream));
+      continue;
+    }
+    a.rows = q.d->d_data;
+    a.nrow = nrow;
+    a.ncol = (uint32_t)q.d->ncol;
+    a.missing = q.d->missing;
+    if (q.host_form) a.flags = c.d_flags.p;
+    a.out = q.interactions ? c.d_iphi.p : target;
+    HIP_CHECK((hipError_t)launch_contribs(approx, a, r.cplan, d_part.p, stream));
+    if (q.interactions)   // the matrix, behind the phi it reads on the same stream
+      HIP_CHECK((hipError_t)launch_interactions(approx, interactions_args(a, c, target), r.iplan, d_part.p, stream));
+    if (G >= 2) HIP_CHECK(launch_group_block_scatter(c.d_gblock.p, nrow, (uint32_t)W, G, g, out, stream));
+  }
+  if (q.host_form) finish_host_form(c, stream, back);
+  return res;
 }
 
 }  // namespace
@@ -2185,23 +2255,16 @@ int OHXBoosterPredictContribs(BoosterHandle handle, DMatrixHandle dmat, int appr
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   refuse_categorical(*b, "OHXBoosterPredictContribs");
-  DMatrixObj* d = as_dmat(dmat);
+  ExplainCall q;
+  q.name = "OHXBoosterPredictContribs";
+  q.d = as_dmat(dmat);
   if (out_len == nullptr || out_result == nullptr) throw OhxError("OHXBoosterPredictContribs: NULL output argument");
-  // the state, the booster's device and its stream are taken only once the call has settled them
-  ContribsState& c = launch_contribs_checked(*b, *d, approximate, ntree_limit, nullptr, true, nullptr);
-  hipStream_t s = b->s_exec;
-  const size_t count = (size_t)d->nrow * b->num_groups * (b->forest.num_feature + 1);
-  c.h_out.ensure(count);
-  if (count) HIP_CHECK(hipMemcpyAsync(c.h_out.p, c.d_out.p, count * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(c.h_flags.p, c.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  if (c.h_flags.p[0] != 0) {
-    HIP_CHECK(hipMemsetAsync(c.d_flags.p, 0, sizeof(uint32_t), s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    throw OhxError("Input data contains `inf` or `nan`");
-  }
-  *out_len = count;
-  *out_result = c.h_out.p;
+  q.approximate = approximate;
+  q.ntree_limit = ntree_limit;
+  q.host_form = true;
+  const ExplainResult r = explain(*b, q);
+  *out_len = r.count;
+  *out_result = r.host;
   API_END();
 }
 
@@ -2210,9 +2273,15 @@ int OHXBoosterPredictContribsDevice(BoosterHandle handle, DMatrixHandle dmat, in
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   refuse_categorical(*b, "OHXBoosterPredictContribsDevice");
-  DMatrixObj* d = as_dmat(dmat);
-  launch_contribs_checked(*b, *d, approximate, ntree_limit, d_out, false, static_cast<hipStream_t>(stream));
-  d->used_async = true;
+  ExplainCall q;
+  q.name = "OHXBoosterPredictContribsDevice";
+  q.d = as_dmat(dmat);
+  q.approximate = approximate;
+  q.ntree_limit = ntree_limit;
+  q.d_out = d_out;
+  q.stream = static_cast<hipStream_t>(stream);
+  explain(*b, q);
+  q.d->used_async = true;
   API_END();
 }
 
@@ -2221,23 +2290,18 @@ int OHXBoosterPredictInteractions(BoosterHandle handle, DMatrixHandle dmat, int 
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   refuse_categorical(*b, "OHXBoosterPredictInteractions");
-  DMatrixObj* d = as_dmat(dmat);
+  ExplainCall q;
+  q.name = "OHXBoosterPredictInteractions";
+  q.interactions = true;
+  q.d = as_dmat(dmat);
   if (out_len == nullptr || out_result == nullptr)
     throw OhxError("OHXBoosterPredictInteractions: NULL output argument");
-  ContribsState& c = launch_interactions_checked(*b, *d, approximate, ntree_limit, nullptr, true, nullptr);
-  hipStream_t s = b->s_exec;
-  const size_t F1 = (size_t)b->forest.num_feature + 1;
-  const size_t count = (size_t)d->nrow * b->num_groups * F1 * F1;
-  if (count) HIP_CHECK(hipMemcpyAsync(c.h_iout.p, c.d_iout.p, count * sizeof(float), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipMemcpyAsync(c.h_flags.p, c.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-  HIP_CHECK(hipStreamSynchronize(s));
-  if (c.h_flags.p[0] != 0) {
-    HIP_CHECK(hipMemsetAsync(c.d_flags.p, 0, sizeof(uint32_t), s));
-    HIP_CHECK(hipStreamSynchronize(s));
-    throw OhxError("Input data contains `inf` or `nan`");
-  }
-  *out_len = count;
-  *out_result = c.h_iout.p;
+  q.approximate = approximate;
+  q.ntree_limit = ntree_limit;
+  q.host_form = true;
+  const ExplainResult r = explain(*b, q);
+  *out_len = r.count;
+  *out_result = r.host;
   API_END();
 }
 
@@ -2246,9 +2310,16 @@ int OHXBoosterPredictInteractionsDevice(BoosterHandle handle, DMatrixHandle dmat
   API_BEGIN();
   BoosterObj* b = as_booster(handle);
   refuse_categorical(*b, "OHXBoosterPredictInteractionsDevice");
-  DMatrixObj* d = as_dmat(dmat);
-  launch_interactions_checked(*b, *d, approximate, ntree_limit, d_out, false, static_cast<hipStream_t>(stream));
-  d->used_async = true;
+  ExplainCall q;
+  q.name = "OHXBoosterPredictInteractionsDevice";
+  q.interactions = true;
+  q.d = as_dmat(dmat);
+  q.approximate = approximate;
+  q.ntree_limit = ntree_limit;
+  q.d_out = d_out;
+  q.stream = static_cast<hipStream_t>(stream);
+  explain(*b, q);
+  q.d->used_async = true;
   API_END();
 }
 
@@ -2260,32 +2331,15 @@ int OHXBoosterCheck(BoosterHandle handle, void* stream) {
   API_END();
 }
 
-// (shared with the selected-gridcells calls, which take no booster)
-static void check_grid_positive(int im, int jm, int km) {
-  if (im <= 0 || jm <= 0 || km <= 0) throw OhxError("predict_fields: im, jm, km must be positive");
-}
-
-// the fields forms' checks of the grid and the field count (predict and contributions)
-static void check_fields_shape(const BoosterObj& b, int nfield, int im, int jm, int km, int k1, int k2) {
-  if (nfield < 0 || nfield > 32) throw OhxError("predict_fields: nfield must be 0..32");
-  if ((uint32_t)nfield > b.forest.num_feature)
-    throw OhxError("Number of columns does not match number of features in booster (" + std::to_string(nfield) +
-                   " vs. " + std::to_string(b.forest.num_feature) + ")");
-  if (b.forest.num_feature > 32) throw OhxError("predict_fields supports boosters with at most 32 features");
-  check_grid_positive(im, jm, km);
-  if (k1 < 1 || k2 > km || k2 < k1 - 1) throw OhxError("predict_fields: need 1 <= k1, k2 <= km, k2 >= k1 - 1");
-}
-
-static void fields_common(BoosterObj& b, FieldsArgs& a, const int32_t is2d[], int nfield, int pl_feature, int im,
-                          int jm, int km, int k1, int k2, float missing, int apply_pow10, float ohscale) {
+// `fields`: the device form's, checked and taken here; the host form (nullptr) checks its own as it stages them
+static void fields_common(BoosterObj& b, FieldsArgs& a, const float* const fields[], const int32_t is2d[], int nfield,
+                          int pl_feature, int im, int jm, int km, int k1, int k2, float missing, int apply_pow10,
+                          float ohscale) {
   check_fields_shape(b, nfield, im, jm, km, k1, k2);
   if (!objective_is_identity(b.forest.objective))
     throw OhxError("objective '" + b.forest.objective + "' is not supported by predict_fields");
-  a.is2d_mask = 0;
-  for (int f = 0; f < nfield; ++f)
-    if (is2d[f]) a.is2d_mask |= (1u << f);
-  a.pl_feature = pl_feature < 0 ? 0xFFFFFFFFu : (uint32_t)pl_feature;
-  a.nfield = (uint32_t)nfield;
+  fields_preamble(a, fields, is2d, nfield, pl_feature);
+  for (int f = 0; fields != nullptr && f < nfield; ++f) a.field[f] = fields[f];
   a.im = im;
   a.jm = jm;
   a.km = km;
@@ -2308,11 +2362,7 @@ int OHXBoosterPredictFieldsDevice(BoosterHandle handle, const float* const d_fie
   if (d_fields == nullptr || is2d == nullptr || d_oh_ml == nullptr) throw OhxError("predict_fields: NULL argument");
   ensure_uploaded(*b);
   FieldsArgs a{};
-  fields_common(*b, a, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, apply_pow10, ohscale);
-  for (int f = 0; f < nfield; ++f) {
-    if (d_fields[f] == nullptr) throw OhxError("predict_fields: field " + std::to_string(f) + " is NULL");
-    a.field[f] = d_fields[f];
-  }
+  fields_common(*b, a, d_fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, apply_pow10, ohscale);
   a.out = d_oh_ml;
   a.margin_out = d_margin;
   if (pick_kernel(*b) == KernelKind::Wide) ensure_wide(*b);
@@ -2336,7 +2386,7 @@ int OHXBoosterPredictFields(BoosterHandle handle, const float* const fields[], c
   if (fields == nullptr || is2d == nullptr || oh_ml == nullptr) throw OhxError("predict_fields: NULL argument");
   ensure_uploaded(*b);
   FieldsArgs a{};
-  fields_common(*b, a, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, apply_pow10, ohscale);
+  fields_common(*b, a, nullptr, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, apply_pow10, ohscale);
   if (a.k2 < a.k1) return 0;
   const size_t plane = (size_t)im * (size_t)jm;
   const size_t nlev = (size_t)(a.k2 - a.k1 + 1);
@@ -2429,95 +2479,7 @@ int OHXBoosterPredictFields(BoosterHandle handle, const float* const fields[], c
   API_END();
 }
 
-// Contributions from the fields, both forms: the fields forms' checks and the contribs forms', in
-// launch_contribs_checked's order (the booster is settled on its device before the state and the stream are taken),
-// every allocation before anything is enqueued.  The host form (host_form, `fields` and `out` host pointers) stages
-// the slab and the requested outputs in the contribs state's own buffers and copies each requested output's slab back.
-static void contribs_fields_call(BoosterObj& b, const float* const fields[], const int32_t is2d[], int nfield,
-                                 int pl_feature, int im, int jm, int km, int k1, int k2, float missing, int approximate,
-                                 unsigned ntree_limit, float* const out[], bool host_form, hipStream_t stream) {
-  if (fields == nullptr || is2d == nullptr || out == nullptr) throw OhxError("predict_fields: NULL argument");
-  if (approximate != 0 && approximate != 1) throw OhxError("approximate must be 0 (exact TreeSHAP) or 1");
-  if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
-  if (!host_form && stream_capturing(stream))
-    refuse_in_capture("compute feature contributions",
-                      "OHXBoosterPredictContribsFieldsDevice is not capturable; call it outside the capture");
-  check_fields_shape(b, nfield, im, jm, km, k1, k2);
-  for (int f = 0; f < nfield; ++f)
-    if (fields[f] == nullptr) throw OhxError("predict_fields: field " + std::to_string(f) + " is NULL");
-  const uint32_t F = b.forest.num_feature;
-  uint32_t nout = 0;
-  for (uint32_t f = 0; f <= F; ++f) nout += out[f] != nullptr ? 1u : 0u;
-  if (nout == 0) throw OhxError("feature contributions from fields: every entry of out is NULL");
-  ContribsState& c = contribs_tables(b, approximate != 0);
-  if (k2 < k1) return;
-  const uint64_t plane = (uint64_t)im * (uint64_t)jm;
-  const uint64_t nrow = plane * (uint64_t)(k2 - k1 + 1);
-  const uint64_t slab = plane * (uint64_t)(k1 - 1);
-  ContribsArgs a;
-  a.nfeat = F;
-  a.missing = missing;
-  tree_range(b, ntree_limit, &a.tree_begin, &a.tree_end);
-  a.bias = contrib_bias(b.flat(), c.means, a.tree_begin, a.tree_end, b.margin_base);
-  a.heads = c.d_heads.p;
-  a.elems = c.d_elems.p;
-  a.class_start = c.d_class_start.p;
-  a.coef = c.d_coef.p;
-  a.nodes = c.d_nodes.p;
-  a.roots = c.d_roots.p;
-  FieldsContribsArgs fa;
-  for (int f = 0; f < nfield; ++f)
-    if (is2d[f]) fa.is2d_mask |= 1u << f;
-  fa.pl_feature = pl_feature < 0 ? 0xFFFFFFFFu : (uint32_t)pl_feature;
-  fa.nfield = (uint32_t)nfield;
-  fa.missing = missing;
-  fa.plane = plane;
-  fa.nrow = nrow;
-  const ContribsPlan plan = plan_contribs(nrow, F, a.tree_end - a.tree_begin, b.contribs_split);
-  if (host_form) stream = b.s_exec;            // taken after contribs_tables: the booster's current device
-  try {
-    if (host_form) {
-      if (c.d_fstage.size() < (size_t)nfield) c.d_fstage.resize((size_t)nfield);
-      for (int f = 0; f < nfield; ++f) c.d_fstage[(size_t)f].ensure(is2d[f] ? plane : nrow);
-      c.d_fout.ensure((size_t)(nout * nrow));
-    }
-    if (plan.split) c.d_part.ensure((size_t)plan.part_floats);
-  } catch (const OhxError&) {
-    (void)hipGetLastError();   // a failed allocation must not surface again as the error of a later launch
-    throw;
-  }
-  if (host_form) {
-    // 3-D fields: the slab's levels only, as the fields predict stages them
-    for (int f = 0; f < nfield; ++f) {
-      float* dst = c.d_fstage[(size_t)f].p;
-      if (is2d[f]) HIP_CHECK(hipMemcpyAsync(dst, fields[f], plane * sizeof(float), hipMemcpyHostToDevice, stream));
-      else HIP_CHECK(hipMemcpyAsync(dst, fields[f] + slab, nrow * sizeof(float), hipMemcpyHostToDevice, stream));
-      fa.field[f] = dst;
-    }
-    uint32_t s = 0;
-    for (uint32_t f = 0; f <= F; ++f)
-      if (out[f] != nullptr) fa.out[f] = c.d_fout.p + (size_t)(s++) * nrow;
-    fa.flags = c.d_flags.p;
-  } else {
-    for (int f = 0; f < nfield; ++f) fa.field[f] = fields[f];
-    for (uint32_t f = 0; f <= F; ++f) fa.out[f] = out[f];
-    fa.src_off = slab;
-    fa.out_off = slab;
-  }
-  HIP_CHECK((hipError_t)launch_contribs_fields(approximate != 0, a, fa, plan, c.d_part.p, stream));
-  if (!host_form) return;
-  for (uint32_t f = 0; f <= F; ++f)
-    if (out[f] != nullptr)
-      HIP_CHECK(hipMemcpyAsync(out[f] + slab, fa.out[f], nrow * sizeof(float), hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipMemcpyAsync(c.h_flags.p, c.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
-  HIP_CHECK(hipStreamSynchronize(stream));
-  if (c.h_flags.p[0] != 0) {
-    HIP_CHECK(hipMemsetAsync(c.d_flags.p, 0, sizeof(uint32_t), stream));
-    HIP_CHECK(hipStreamSynchronize(stream));
-    throw OhxError("Input data contains `inf` or `nan`");
-  }
-}
-
+// Contributions from the fields: the explanation call (explain, above) with the fields as its source.
 int OHXBoosterPredictContribsFields(BoosterHandle handle, const float* const fields[], const int32_t is2d[],
                                     int nfield, int pl_feature, int im, int jm, int km, int k1, int k2, float missing,
                                     int approximate, unsigned ntree_limit, float* const out[]) {
@@ -2525,8 +2487,14 @@ int OHXBoosterPredictContribsFields(BoosterHandle handle, const float* const fie
   BoosterObj* b = as_booster(handle);
   refuse_groups(*b, "OHXBoosterPredictContribsFields");
   refuse_categorical(*b, "OHXBoosterPredictContribsFields");
-  contribs_fields_call(*b, fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, approximate, ntree_limit,
-                       out, true, nullptr);
+  const FieldsSource fs{fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, out};
+  ExplainCall q;
+  q.name = "OHXBoosterPredictContribsFields";
+  q.fs = &fs;
+  q.approximate = approximate;
+  q.ntree_limit = ntree_limit;
+  q.host_form = true;
+  explain(*b, q);
   API_END();
 }
 
@@ -2538,8 +2506,14 @@ int OHXBoosterPredictContribsFieldsDevice(BoosterHandle handle, const float* con
   BoosterObj* b = as_booster(handle);
   refuse_groups(*b, "OHXBoosterPredictContribsFieldsDevice");
   refuse_categorical(*b, "OHXBoosterPredictContribsFieldsDevice");
-  contribs_fields_call(*b, d_fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, approximate, ntree_limit,
-                       d_out, false, static_cast<hipStream_t>(stream));
+  const FieldsSource fs{d_fields, is2d, nfield, pl_feature, im, jm, km, k1, k2, missing, d_out};
+  ExplainCall q;
+  q.name = "OHXBoosterPredictContribsFieldsDevice";
+  q.fs = &fs;
+  q.approximate = approximate;
+  q.ntree_limit = ntree_limit;
+  q.stream = static_cast<hipStream_t>(stream);
+  explain(*b, q);
   API_END();
 }
 
@@ -2604,13 +2578,8 @@ GatherCellsArgs gather_args(const float* const fields[], const int32_t is2d[], i
   if (fields == nullptr || is2d == nullptr || (ncell > 0 && (cells == nullptr || rows == nullptr)))
     throw OhxError("predict_fields: NULL argument");
   GatherCellsArgs g{};
-  for (int f = 0; f < nfield; ++f) {
-    if (fields[f] == nullptr) throw OhxError("predict_fields: field " + std::to_string(f) + " is NULL");
-    g.field[f] = fields[f];
-    if (is2d[f]) g.is2d_mask |= 1u << f;
-  }
-  g.pl_feature = pl_feature < 0 ? 0xFFFFFFFFu : (uint32_t)pl_feature;
-  g.nfield = (uint32_t)nfield;
+  fields_preamble(g, fields, is2d, nfield, pl_feature);
+  for (int f = 0; f < nfield; ++f) g.field[f] = fields[f];
   g.plane = (int64_t)im * jm;
   g.ncells_total = g.plane * km;
   return g;

@@ -168,13 +168,15 @@ PathTable build_path_table(const Forest& f) {
   return pt;
 }
 
-ContribsPlan plan_contribs(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool allow_split) {
+// The split rule of both explanation launches.  `units` = the direct shape's waves; a batch whose direct waves leave
+// most of the chip's wave slots empty has its trees split over as many tree groups as fill them, each wave keeping
+// nfeat x 64 floats of `part` per tree.
+static ContribsPlan plan_split(uint64_t units, uint32_t nfeat, uint32_t ntree, bool allow_split) {
   ContribsPlan p;
-  const uint64_t tiles = (nrow + kContribsTileRows - 1) / kContribsTileRows;
-  if (!allow_split || tiles == 0 || ntree < 2 || tiles * 2 > kWaveSlots) return p;
-  const uint64_t part = tiles * ntree * (uint64_t)nfeat * kContribsTileRows;
+  if (!allow_split || units == 0 || ntree < 2 || units * 2 > kWaveSlots) return p;
+  const uint64_t part = units * ntree * (uint64_t)nfeat * kContribsTileRows;
   if (part * sizeof(float) > kPartBudgetBytes) return p;
-  uint64_t want = (kWaveSlots + tiles - 1) / tiles;   // tree groups that fill the chip's wave slots
+  uint64_t want = (kWaveSlots + units - 1) / units;   // tree groups that fill the chip's wave slots
   if (want > ntree) want = ntree;
   if (want < 2) return p;
   p.trees_per_group = (uint32_t)((ntree + want - 1) / want);
@@ -182,6 +184,13 @@ ContribsPlan plan_contribs(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool a
   p.split = p.groups > 1;
   p.part_floats = p.split ? part : 0;
   return p;
+}
+
+static uint64_t tiles_of(uint64_t nrow) { return (nrow + kContribsTileRows - 1) / kContribsTileRows; }
+
+// contributions: one direct wave per tile
+ContribsPlan plan_contribs(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool allow_split) {
+  return plan_split(tiles_of(nrow), nfeat, ntree, allow_split);
 }
 
 FeaturePathIndex build_feature_path_index(const PathTable& pt, uint32_t ntree, uint32_t nfeat) {
@@ -214,21 +223,9 @@ FeaturePathIndex build_feature_path_index(const PathTable& pt, uint32_t ntree, u
   return ix;
 }
 
+// interactions: one direct wave per (tile, conditioning feature)
 ContribsPlan plan_interactions(uint64_t nrow, uint32_t nfeat, uint32_t ntree, bool allow_split) {
-  ContribsPlan p;
-  const uint64_t tiles = (nrow + kContribsTileRows - 1) / kContribsTileRows;
-  const uint64_t units = tiles * nfeat;   // the direct shape's waves: one per (tile, conditioning feature)
-  if (!allow_split || units == 0 || ntree < 2 || units * 2 > kWaveSlots) return p;
-  const uint64_t part = units * ntree * (uint64_t)nfeat * kContribsTileRows;
-  if (part * sizeof(float) > kPartBudgetBytes) return p;
-  uint64_t want = (kWaveSlots + units - 1) / units;
-  if (want > ntree) want = ntree;
-  if (want < 2) return p;
-  p.trees_per_group = (uint32_t)((ntree + want - 1) / want);
-  p.groups = (ntree + p.trees_per_group - 1) / p.trees_per_group;
-  p.split = p.groups > 1;
-  p.part_floats = p.split ? part : 0;
-  return p;
+  return plan_split(tiles_of(nrow) * nfeat, nfeat, ntree, allow_split);
 }
 
 }  // namespace ohx

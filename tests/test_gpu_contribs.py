@@ -222,6 +222,32 @@ def test_refusals(torch_cuda):
     assert np.array_equal(helpers.bits(out.cpu().numpy()), helpers.bits(b.predict_contribs(d)))
 
 
+@pytest.mark.parametrize("approximate", [False, True])
+def test_a_failed_allocation_leaves_no_error_behind(torch_cuda, approximate):
+    """An output that cannot be allocated (2**40 borrowed rows) is refused with a message before anything is launched,
+    and the failure is forgotten with it: the next host call and the next device call on the caller's stream give the
+    bits of the call before."""
+    torch = torch_cuda
+    rng = np.random.default_rng(33)
+    js, _, _ = cs.random_booster(rng, 3, 4, 4, 0.1)
+    rows = cs.random_rows(rng, 64, 4)
+    b = capi.Booster(model_buffer=js)
+    d = capi.DMatrix(rows, missing=-999.0)
+    before = b.predict_contribs(d, approximate=approximate)
+    t = torch.from_numpy(rows).cuda()
+    huge = capi.DMatrix(device_ptr=t.data_ptr(), nrow=1 << 40, ncol=4, missing=-999.0)
+    with pytest.raises(capi.OhxError):
+        b.predict_contribs(huge, approximate=approximate)
+    assert np.array_equal(helpers.bits(b.predict_contribs(d, approximate=approximate)), helpers.bits(before))
+    out = torch.zeros((64, 5), dtype=torch.float32, device="cuda")
+    dd = capi.DMatrix(device_ptr=t.data_ptr(), nrow=64, ncol=4, missing=-999.0)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        b.predict_contribs_device(dd, out.data_ptr(), approximate=approximate, stream=s.cuda_stream)
+    s.synchronize()
+    assert np.array_equal(helpers.bits(out.cpu().numpy()), helpers.bits(before))
+
+
 def test_buffers_stay_apart_from_a_captured_predict(torch_cuda, deep_model):
     """A predict captured into a hipGraph holds raw pointers to the booster's buffers: a contribs call on a bigger batch
     in between must not move them - the replay still matches the oracle bit for bit."""

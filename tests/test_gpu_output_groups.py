@@ -302,6 +302,35 @@ def test_contributions_device_form_is_the_host_form(torch_cuda, contribs_case):
     assert np.array_equal(helpers.bits(out.cpu().numpy().reshape(300, 4, 28)), helpers.bits(host))
 
 
+@pytest.mark.parametrize("approximate", [False, True])
+def test_a_failed_allocation_leaves_no_error_behind(torch_cuda, approximate):
+    """Three output groups: an output (and a block buffer) that cannot be allocated, 2**40 borrowed rows, is refused
+    with a message before anything is launched, and the failure is forgotten with it - the next host call and the next
+    device call on the caller's stream give the bits of the call before."""
+    from tests import contribs_support as cs
+    torch = torch_cuda
+    rng = np.random.default_rng(34)
+    js, _, _ = cs.random_booster(rng, 3, 4, 4, 0.1)
+    image = OG.multi_json(js, [0, 1, 2], 3)
+    rows = cs.random_rows(rng, 64, 4)
+    b = booster(image)
+    d = capi.DMatrix(rows, missing=-999.0)
+    before = b.predict_contribs(d, approximate=approximate)
+    assert before.shape == (64, 3, 5)
+    t = torch.from_numpy(rows).cuda()
+    huge = capi.DMatrix(device_ptr=t.data_ptr(), nrow=1 << 40, ncol=4, missing=-999.0)
+    with pytest.raises(capi.OhxError):
+        b.predict_contribs(huge, approximate=approximate)
+    assert np.array_equal(helpers.bits(b.predict_contribs(d, approximate=approximate)), helpers.bits(before))
+    out = torch.zeros((64, 3, 5), dtype=torch.float32, device="cuda")
+    dd = capi.DMatrix(device_ptr=t.data_ptr(), nrow=64, ncol=4, missing=-999.0)
+    s = torch.cuda.Stream()
+    with torch.cuda.stream(s):
+        b.predict_contribs_device(dd, out.data_ptr(), approximate=approximate, stream=s.cuda_stream)
+    s.synchronize()
+    assert np.array_equal(helpers.bits(out.cpu().numpy()), helpers.bits(before))
+
+
 # ---- outside cross-check: scikit-learn's multi-class gradient boosting ----
 
 def test_sklearn_three_class_gradient_boosting():
