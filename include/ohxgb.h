@@ -192,6 +192,9 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *   "ohx_brick" = "a,b,c", "ohx_brick_k_fastest", "ohx_prefetch", "ohx_coop_rows", "ohx_xcd_remap", "ohx_lds_pad", "ohx_overlap_group"
  *                     launch-shape knobs behind profiles/ *_sweeps.txt; the defaults are the measured best
  *   "ohx_top_levels", "ohx_line_slots", "ohx_min_chunk"  placement of the packed format
+ *   "ohx_super_pack"  0..3 : which super-node groups of a tree share a 128-byte line below the records of a walk's first
+ *                     four steps (0 = breadth first, 1 = trees on 128-byte bases, 2 = + sibling pairs in one line, 3 = +
+ *                     families in two lines; docs/03_hbm_layout.md); the margins are the same bits whatever the value
  *   "ohx_contribs_split"  auto | off : OHXBoosterPredictContribs[Device]: a batch that leaves most of the chip's wave
  *                     slots empty has its trees split over waves and the per-tree contributions summed in tree order by a
  *                     second launch (auto), or one wave per 64 rows walks every tree (off); the same bits either way;

@@ -857,7 +857,7 @@ void ensure_uploaded(BoosterObj& b) {
     b.d_cat_orig.upload(cf.orig_id);
   } else if (wants_super(b.kernel_name)) {
     SuperForest sf;
-    b.super_ok = emit_super(flat, &sf) && sf.nodes.size() * sizeof(SuperNode) < 0xFFFFFFF0ull;
+    b.super_ok = emit_super(flat, &sf, b.layout.super_pack) && sf.nodes.size() * sizeof(SuperNode) < 0xFFFFFFF0ull;
     if (b.super_ok) {
       b.super_slots = sf.nodes.size();
       b.super_gathers[0] = count_super_gathers(sf, 0);
@@ -865,6 +865,8 @@ void ensure_uploaded(BoosterObj& b) {
       b.super_gathers[2] = count_super_gathers(sf, 2);
       b.super_mean_steps = mean_super_steps(sf);
       b.d_super.upload(sf.nodes);
+      // groups 2k and 2k + 1 of a tree are one cache line (flatten.hpp kSuperPack*) only in an array that starts on one
+      if (((uintptr_t)b.d_super.p & 127u) != 0) throw OhxError("internal error: the super-node array is not 128-byte aligned");
       b.d_super_heads.upload(sf.heads);
     }
   }
@@ -2111,6 +2113,11 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
     if (k < 2 || k > 1024) throw OhxError("ohx_min_chunk must be in 2..1024");
     if (k != b->layout.min_chunk) invalidate_device_state(*b);
     b->layout.min_chunk = k;
+  } else if (n == "ohx_super_pack") {
+    int k = atoi(value);
+    if (k < kSuperPackNone || k > kSuperPackFamilies) throw OhxError("ohx_super_pack must be in 0..3");
+    if (k != b->layout.super_pack) invalidate_device_state(*b);
+    b->layout.super_pack = k;
   } else if (n == "ohx_launches_per_residency") {
     int k = atoi(value);
     if (k < 0 || k > 1000000) throw OhxError("ohx_launches_per_residency must be >= 0");
@@ -3516,7 +3523,7 @@ int OHXBoosterGetInfo(BoosterHandle handle, bst_ulong info[8]) {
       super_used = b->super_ok;
     } else {
       SuperForest sf;
-      super_used = emit_super(b->forest, &sf);
+      super_used = emit_super(b->forest, &sf, b->layout.super_pack);
       super_slots = sf.nodes.size();
       super_gathers = count_super_gathers(sf, walk_mode(mean_super_steps(sf)));
     }

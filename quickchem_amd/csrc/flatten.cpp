@@ -158,10 +158,57 @@ int choose_super_phase(const Tree& t) {
 
 }  // namespace
 
-bool emit_super(const Forest& f, SuperForest* out) {
-  out->nodes.clear();
-  out->heads.clear();
-  if (f.num_feature > kSuperLeaf) return false;
+namespace {
+
+// Numbers for the child groups below level 3, by line (flatten.hpp kSuperPack*): whole lines (two groups) and whole
+// 256-byte stretches come from the end of the tree, and what an alignment or a single leaves free is handed out again
+// before anything new - to the next single, the next pair.
+struct GroupNumbers {
+  uint32_t next = 2;                        // groups 0 and 1 are the fillers and the start
+  std::vector<uint32_t> free_pairs, free_singles;
+  bool by_line = false;
+  void begin_lines() {
+    if (by_line) return;
+    by_line = true;
+    if (next & 1u) free_singles.push_back(next++);
+  }
+  uint32_t pair() {
+    begin_lines();
+    uint32_t g;
+    if (!free_pairs.empty()) {
+      g = free_pairs.back();
+      free_pairs.pop_back();
+    } else {
+      g = next;
+      next += 2;
+    }
+    return g;
+  }
+  uint32_t single() {
+    begin_lines();
+    if (!free_singles.empty()) {
+      const uint32_t g = free_singles.back();
+      free_singles.pop_back();
+      return g;
+    }
+    const uint32_t g = pair();
+    free_singles.push_back(g + 1);
+    return g;
+  }
+  uint32_t quad() {
+    begin_lines();
+    if (next & 2u) {
+      free_pairs.push_back(next);
+      next += 2;
+    }
+    const uint32_t g = next;
+    next += 4;
+    return g;
+  }
+};
+
+// One tree's records, relative to its base, and its head (base not set).  False: more than kSuperMaxGroups groups.
+bool emit_super_tree(const Tree& t, int pack, std::vector<SuperNode>* records, SuperTreeHead* head_out) {
   // a filler looks like an internal node that sends everything - numbers below its +inf thresholds, NaN by its
   // default-left bits - to slot 0 of group 0, i.e. to a filler; none of its codes says "leaf" (flatten.hpp)
   const float inf = std::numeric_limits<float>::infinity();
@@ -171,75 +218,151 @@ bool emit_super(const Forest& f, SuperForest* out) {
     int32_t node;
     uint32_t slot;   // relative to the tree base
     uint32_t level;  // super-nodes above this one on its path
+    uint32_t group;  // its child group where that was numbered ahead, by line; 0: none yet
   };
   std::vector<Item> queue;
-  for (const Tree& t : f.trees) {
-    const uint32_t base = (uint32_t)out->nodes.size();
-    SuperTreeHead head{base, 0u, 0.0f, 0u};
-    std::vector<SuperNode> sn(8, unused);  // group 0: four fillers; group 1: where the walk starts
-    uint32_t next_group = 2;
-    queue.clear();
-    const bool root_is_leaf = t.left[0] == -1;
-    const int phase = root_is_leaf ? 0 : choose_super_phase(t);
-    if (phase == 1) {
-      // the root is evaluated from the head record; its children start the super-nodes
-      head.root_meta = (t.feature[0] & 31u) | ((uint32_t)(t.default_left[0] ? 1u : 0u) << 5) | (1u << 8);
-      head.root_thr = t.value[0];
-      queue.push_back({t.left[0], 4u, 0u});
-      queue.push_back({t.right[0], 5u, 0u});
-    } else {
-      queue.push_back({0, 4u, 0u});
-    }
-    for (size_t qi = 0; qi < queue.size(); ++qi) {
-      const Item it = queue[qi];
-      const size_t n = (size_t)it.node;
-      SuperNode s = unused;
-      if (t.left[n] == -1) {
-        // a leaf on top: its value in all three slots, all three feature codes 31, so that whichever
-        // child slot the walk looks at says "leaf" and holds the value; group 0: fillers from here on
-        s.thr0 = s.thrL = s.thrR = t.value[n];
-        s.meta = leaf_meta;
+  SuperTreeHead head{0u, 0u, 0.0f, 0u};
+  std::vector<SuperNode>& sn = *records;
+  sn.assign(8, unused);  // group 0: four fillers; group 1: where the walk starts
+  GroupNumbers numbers;
+  const bool root_is_leaf = t.left[0] == -1;
+  const int phase = root_is_leaf ? 0 : choose_super_phase(t);
+  if (phase == 1) {
+    // the root is evaluated from the head record; its children start the super-nodes
+    head.root_meta = (t.feature[0] & 31u) | ((uint32_t)(t.default_left[0] ? 1u : 0u) << 5) | (1u << 8);
+    head.root_thr = t.value[0];
+    queue.push_back({t.left[0], 4u, 0u, 0u});
+    queue.push_back({t.right[0], 5u, 0u, 0u});
+  } else {
+    queue.push_back({0, 4u, 0u, 0u});
+  }
+  // does the record on top of node n name a child group?
+  auto has_group = [&](int32_t node) {
+    const size_t n = (size_t)node;
+    if (t.left[n] == -1) return false;
+    return t.left[(size_t)t.left[n]] != -1 || t.left[(size_t)t.right[n]] != -1;
+  };
+  size_t numbered_to = 0;   // queue entries whose group's child groups have their numbers
+  for (size_t qi = 0; qi < queue.size(); ++qi) {
+    if (pack >= kSuperPackPairs && queue[qi].level >= 3 && qi >= numbered_to) {
+      // the records of one group follow each other in the queue (their parent pushed them): number their child groups
+      // together.  q[s]: the queue entry in slot s of the group if it names a child group
+      size_t qe = qi;
+      size_t q[4];
+      bool has[4] = {false, false, false, false};
+      int count = 0;
+      for (; qe < queue.size() && (queue[qe].slot >> 2) == (queue[qi].slot >> 2); ++qe)
+        if (has_group(queue[qe].node)) {
+          q[queue[qe].slot & 3u] = qe;
+          has[queue[qe].slot & 3u] = true;
+          ++count;
+        }
+      numbered_to = qe;
+      if (pack >= kSuperPackFamilies && count >= 3) {
+        const uint32_t g = numbers.quad();
+        for (int s = 0; s < 4; ++s) {
+          if (has[s]) queue[q[s]].group = g + (uint32_t)s;
+          else numbers.free_singles.push_back(g + (uint32_t)s);
+        }
       } else {
-        const size_t l = (size_t)t.left[n], r = (size_t)t.right[n];
-        const bool l_int = t.left[l] != -1, r_int = t.left[r] != -1;
-        s.thr0 = t.value[n];
-        s.thrL = t.value[l];
-        s.thrR = t.value[r];
-        uint32_t meta = super_meta(t.feature[n], l_int ? t.feature[l] : kSuperLeaf, r_int ? t.feature[r] : kSuperLeaf,
-                                   t.default_left[n] ? 1u : 0u, (l_int && t.default_left[l]) ? 1u : 0u,
-                                   (r_int && t.default_left[r]) ? 1u : 0u, 0u);
-        if (l_int || r_int) {
-          const uint32_t grp = next_group++;
-          if (grp >= kSuperMaxGroups) {
-            out->nodes.clear();
-            out->heads.clear();
-            return false;
-          }
-          meta |= grp << 18;
-          sn.resize((size_t)next_group * 4, unused);
-          if (l_int) {
-            queue.push_back({t.left[l], grp * 4 + 0, it.level + 1});
-            queue.push_back({t.right[l], grp * 4 + 1, it.level + 1});
-          }
-          if (r_int) {
-            queue.push_back({t.left[r], grp * 4 + 2, it.level + 1});
-            queue.push_back({t.right[r], grp * 4 + 3, it.level + 1});
+        size_t lone[2];
+        int nlone = 0;
+        for (int s = 0; s < 4; s += 2) {
+          if (has[s] && has[s + 1]) {
+            const uint32_t g = numbers.pair();
+            queue[q[s]].group = g;
+            queue[q[s + 1]].group = g + 1;
+          } else if (has[s] || has[s + 1]) {
+            lone[nlone++] = q[has[s] ? s : s + 1];
           }
         }
-        s.meta = meta;
+        if (nlone == 2) {
+          const uint32_t g = numbers.pair();
+          queue[lone[0]].group = g;
+          queue[lone[1]].group = g + 1;
+        } else if (nlone == 1) {
+          queue[lone[0]].group = numbers.single();
+        }
       }
-      // breadth first: the super-nodes of a walk's first three steps (levels 0-2: at most 2 + 8 + 32) and the
-      // fillers of group 0 lie in the tree's first kSuperTopSlots records - what walk_super's one coalesced
-      // "tree top" load per tree relies on
-      if (it.level <= 2 && it.slot >= kSuperTopSlots) throw OhxError("internal error: tree top outside its first records");
-      if (it.level <= 3 && it.slot >= kSuperRingSlots) throw OhxError("internal error: a record of the first four steps outside the tree's first 176");
-      // (below level 3 the order is free - a record names its child group by number - and was tried group by group depth
-      // first, a subtree one stretch of the array, child group a median 368 B from its parent instead of 60 KB: the C360
-      // step 24.39 against 24.16 ms, +1.0 %; profiles/r06_not_kept_dfs_order.patch, r06_sweeps.txt)
-      sn[it.slot] = s;
-      if (it.level + 1 > head.steps) head.steps = it.level + 1;
+      if (numbers.next > kSuperMaxGroups) return false;
     }
+    const Item it = queue[qi];
+    const size_t n = (size_t)it.node;
+    SuperNode s = unused;
+    if (t.left[n] == -1) {
+      // a leaf on top: its value in all three slots, all three feature codes 31, so that whichever
+      // child slot the walk looks at says "leaf" and holds the value; group 0: fillers from here on
+      s.thr0 = s.thrL = s.thrR = t.value[n];
+      s.meta = leaf_meta;
+    } else {
+      const size_t l = (size_t)t.left[n], r = (size_t)t.right[n];
+      const bool l_int = t.left[l] != -1, r_int = t.left[r] != -1;
+      s.thr0 = t.value[n];
+      s.thrL = t.value[l];
+      s.thrR = t.value[r];
+      uint32_t meta = super_meta(t.feature[n], l_int ? t.feature[l] : kSuperLeaf, r_int ? t.feature[r] : kSuperLeaf,
+                                 t.default_left[n] ? 1u : 0u, (l_int && t.default_left[l]) ? 1u : 0u,
+                                 (r_int && t.default_left[r]) ? 1u : 0u, 0u);
+      if (l_int || r_int) {
+        const uint32_t grp = it.group ? it.group : numbers.next++;
+        if (numbers.next > kSuperMaxGroups) return false;
+        meta |= grp << 18;
+        if (sn.size() < (size_t)numbers.next * 4) sn.resize((size_t)numbers.next * 4, unused);
+        if (l_int) {
+          queue.push_back({t.left[l], grp * 4 + 0, it.level + 1, 0u});
+          queue.push_back({t.right[l], grp * 4 + 1, it.level + 1, 0u});
+        }
+        if (r_int) {
+          queue.push_back({t.left[r], grp * 4 + 2, it.level + 1, 0u});
+          queue.push_back({t.right[r], grp * 4 + 3, it.level + 1, 0u});
+        }
+      }
+      s.meta = meta;
+    }
+    // breadth first: the super-nodes of a walk's first three steps (levels 0-2: at most 2 + 8 + 32) and the
+    // fillers of group 0 lie in the tree's first kSuperTopSlots records - what walk_super's one coalesced
+    // "tree top" load per tree relies on
+    if (it.level <= 2 && it.slot >= kSuperTopSlots) throw OhxError("internal error: tree top outside its first records");
+    if (it.level <= 3 && it.slot >= kSuperRingSlots) throw OhxError("internal error: a record of the first four steps outside the tree's first 176");
+    // (below level 3 the order is free - a record names its child group by number - and was tried group by group depth
+    // first, a subtree one stretch of the array, child group a median 368 B from its parent instead of 60 KB: the C360
+    // step 24.39 against 24.16 ms, +1.0 %; profiles/r06_not_kept_dfs_order.patch, r06_sweeps.txt.  What is chosen
+    // there now is which groups share a line: flatten.hpp kSuperPack*)
+    sn[it.slot] = s;
+    if (it.level + 1 > head.steps) head.steps = it.level + 1;
+  }
+  *head_out = head;
+  return true;
+}
+
+}  // namespace
+
+bool emit_super(const Forest& f, SuperForest* out, int super_pack) {
+  out->nodes.clear();
+  out->heads.clear();
+  out->packed.clear();
+  if (f.num_feature > kSuperLeaf) return false;
+  const float inf = std::numeric_limits<float>::infinity();
+  const SuperNode unused{inf, inf, inf, super_meta(0, 0, 0, 1, 1, 1, 0)};
+  std::vector<SuperNode> sn;
+  for (const Tree& t : f.trees) {
+    // groups 2k and 2k + 1 of a tree are one 128-byte line only if the tree starts on one
+    if (super_pack >= kSuperPackBases && (out->nodes.size() & 7u) != 0) out->nodes.insert(out->nodes.end(), 4, unused);
+    SuperTreeHead head;
+    bool by_line = super_pack >= kSuperPackPairs;
+    if (!by_line || !emit_super_tree(t, super_pack, &sn, &head)) {
+      // the group index has 14 bits: a tree that fits them only without the groups the lines skip keeps the old numbers
+      by_line = false;
+      if (!emit_super_tree(t, kSuperPackNone, &sn, &head)) {
+        out->nodes.clear();
+        out->heads.clear();
+        out->packed.clear();
+        return false;
+      }
+    }
+    head.base = (uint32_t)out->nodes.size();
     out->heads.push_back(head);
+    out->packed.push_back(by_line ? 1u : 0u);
     out->nodes.insert(out->nodes.end(), sn.begin(), sn.end());
     if (out->nodes.size() >= 0xFFFFFFF0ull) throw OhxError("booster too large for the super-node format");
   }

@@ -32,6 +32,9 @@ struct LayoutParams {
   int top_levels = 9;    // levels stored breadth-first per tree (root = level 0)
   int line_slots = 16;   // slots per packed line below the top; 0 => breadth-first all the way
   int min_chunk = 6;     // do not start a new subtree in a line with fewer free slots than this
+  // super-node format: which groups of a tree share a 128-byte line below the records of a walk's first four steps
+  // (kSuperPack*, emit_super); "ohx_super_pack"
+  int super_pack = 2;
 };
 
 struct PackedNode {  // 8 bytes
@@ -95,7 +98,7 @@ constexpr uint32_t super_meta(uint32_t f0, uint32_t fl, uint32_t fr, uint32_t dl
   return (fl & 31u) | (dl0 << 5) | (dll << 6) | (dlr << 7) | ((f0 & 31u) << 8) | ((fr & 31u) << 13) | (group << 18);
 }
 constexpr uint32_t kSuperMaxGroups = 1u << 14;
-// Groups are numbered breadth first, so the records a walk can stand on during its first three steps are among
+// Groups are numbered breadth first down to level 3 (kSuperPack*), so the records a walk can stand on during its first three steps are among
 // the tree's first 48 (groups 0-11): the kernels fetch them with one coalesced load per tree and wave (one record
 // per lane) and hand them from lane to lane.  emit_super pads the array by this much behind the last tree.
 constexpr uint32_t kSuperTopSlots = 48;
@@ -116,7 +119,25 @@ struct SuperTreeHead {
 struct SuperForest {
   std::vector<SuperNode> nodes;
   std::vector<SuperTreeHead> heads;
+  std::vector<uint8_t> packed;   // per tree: 1 = its deep groups were numbered by line (kSuperPackPairs and up)
 };
+
+// Which groups share a 128-byte line (two groups; the array is 128-byte aligned on the device).  A deep gather costs
+// the texture path by the distinct lines its 64 lanes name (docs/04_tree_walk_cost.md §4.13), and where the lanes of a
+// quad or a brick part company is a step's SECOND decision: onto the records LL / LR (or RL / RR) of one group, whose
+// child groups the next gather reads.  The records of a walk's first four steps - levels 0 to 3, the tree's first
+// kSuperRingSlots at most - are numbered breadth first whatever the value; the variants are cumulative:
+//   kSuperPackNone      breadth first all the way, a tree wherever the last one ended (until round 11)
+//   kSuperPackBases     + every tree starts on a 128-byte line: one filler group in front of a tree that would start on
+//                       an odd group, so that groups 2k and 2k + 1 of every tree are one line
+//   kSuperPackPairs     + below level 3 the child groups of the records in slots 0 / 1 of a group are numbered 2k and
+//                       2k + 1, and so are those of slots 2 / 3; where only one of the two has a child group it takes
+//                       the half line the last such single left open (the other pair's of the same group first), or
+//                       opens a line - no group number is left out but a tree's last odd one
+//   kSuperPackFamilies  + three or four child groups of one group's records lie in one 256-byte aligned stretch, pairs
+//                       as above inside it; the groups this skips are handed to later pairs and singles
+// A tree whose numbering would pass kSuperMaxGroups with the skipped groups is numbered breadth first instead.
+constexpr int kSuperPackNone = 0, kSuperPackBases = 1, kSuperPackPairs = 2, kSuperPackFamilies = 3;
 
 // Several output groups (Forest::num_groups() >= 2): the device forms are built from a copy of the booster whose trees
 // are ordered group by group, each group's trees in file order, so that a group is one contiguous tree range for every
@@ -155,7 +176,7 @@ struct CatForest {
 CatForest emit_cat(const Forest& f, const Placement& p);
 
 // Returns false (and leaves `out` empty) when the booster does not fit the format.
-bool emit_super(const Forest& f, SuperForest* out);
+bool emit_super(const Forest& f, SuperForest* out, int super_pack = LayoutParams().super_pack);
 
 Placement place_forest(const Forest& f, const LayoutParams& lp);
 bool packed_format_fits(const Forest& f, const Placement& p);

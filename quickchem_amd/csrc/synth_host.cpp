@@ -22,6 +22,7 @@
 #include "cells.hpp"
 #include "flatten.hpp"
 #include "forest.hpp"
+#include "super_walk.hpp"
 #include "synth_common.h"
 
 using namespace ohx;
@@ -271,13 +272,21 @@ int ohx_model_convert(const uint8_t* in_buf, uint64_t in_len, int format, uint8_
 // layout bug shows without a GPU.  Not a prediction path: scalar, test support only.
 // out[nrow] margins; info[0] = super-nodes, info[1] = trees that start below the root (phase 1),
 // info[2] = total steps.  Returns 1 if the booster does not fit the format.
+int ohx_super_walk_pack_cpu(const uint8_t* model, uint64_t model_len, int super_pack, const float* rows, uint64_t nrow,
+                             uint32_t ncol, float missing, float* out, uint64_t* info);
 int ohx_super_walk_cpu(const uint8_t* model, uint64_t model_len, const float* rows, uint64_t nrow, uint32_t ncol,
                        float missing, float* out, uint64_t* info) {
+  return ohx_super_walk_pack_cpu(model, model_len, LayoutParams().super_pack, rows, nrow, ncol, missing, out, info);
+}
+
+// ... with the groups placed as `super_pack` says (flatten.hpp kSuperPack*), the default being what a booster uploads
+int ohx_super_walk_pack_cpu(const uint8_t* model, uint64_t model_len, int super_pack, const float* rows, uint64_t nrow,
+                             uint32_t ncol, float missing, float* out, uint64_t* info) {
   try {
     Forest f = load_model_buffer(model, (size_t)model_len);
     f.validate();
     SuperForest sf;
-    if (!emit_super(f, &sf)) return 1;
+    if (!emit_super(f, &sf, super_pack)) return 1;
     uint64_t phase1 = 0, steps = 0;
     for (const SuperTreeHead& h : sf.heads) {
       phase1 += (h.root_meta >> 8) & 1u;
@@ -288,45 +297,79 @@ int ohx_super_walk_cpu(const uint8_t* model, uint64_t model_len, const float* ro
       info[1] = phase1;
       info[2] = steps;
     }
-    const bool missing_is_nan = missing != missing;
     std::vector<float> x(32, 0.0f);   // rows 27..31 "belong to nobody"
     for (uint64_t r = 0; r < nrow; ++r) {
-      for (uint32_t c = 0; c < 32; ++c) {
-        float v = c < ncol ? rows[r * ncol + c] : (c < f.num_feature ? NAN : 0.0f);
-        if (c < ncol && !missing_is_nan && v == missing) v = NAN;
-        x[c] = v;
-      }
+      super_walk_row(rows + r * ncol, ncol, f.num_feature, missing, x.data());
       float acc = f.base_score;
-      for (const SuperTreeHead& h : sf.heads) {
-        auto left = [](float xv, float thr, bool dl) { return xv != xv ? dl : xv < thr; };
-        uint32_t rel = 4u;
-        if (h.root_meta & 0x100u) rel += left(x[h.root_meta & 31u], h.root_thr, (h.root_meta & 32u) != 0) ? 0u : 1u;
-        uint32_t leaf_bits = 0, taken = 0;
-        // as walk_super does: the records of the first three steps among the tree's first kSuperTopSlots
-        // (its one "top" load); two more steps than the tree has, as when it shares a group of chains with a
-        // deeper tree (a walk past its leaf only meets fillers)
-        const uint32_t nsteps = h.steps + 2u;
-        for (uint32_t step = 0; step < nsteps; ++step) {
-          if (step < 3 && rel >= kSuperTopSlots) throw OhxError("tree top outside the first records of its tree");
-          if ((size_t)h.base + rel >= sf.nodes.size()) throw OhxError("walk left the super-node array");
-          const SuperNode& s = sf.nodes[h.base + rel];
-          const uint32_t w = s.meta;
-          const bool l0 = left(x[(w >> 8) & 31u], s.thr0, ((w >> 5) & 1u) != 0);
-          const float thr1 = l0 ? s.thrL : s.thrR;
-          const uint32_t f1 = (w >> (l0 ? 0u : 13u)) & 31u;
-          if (f1 == 31u) {
-            memcpy(&leaf_bits, &thr1, 4);
-            ++taken;
-          }
-          const bool l1 = left(x[f1], thr1, ((w >> (l0 ? 6u : 7u)) & 1u) != 0);
-          rel = ((w >> 18) << 2) + (l0 ? 0u : 2u) + (l1 ? 0u : 1u);
-        }
-        if (taken != 1) throw OhxError("a walk must meet exactly one leaf code, met " + std::to_string(taken));
-        float leaf;
-        memcpy(&leaf, &leaf_bits, 4);
-        acc += leaf;
-      }
+      // two more steps than the tree has, as when it shares a group of chains with a deeper tree (a walk past its
+      // leaf only meets fillers)
+      for (const SuperTreeHead& h : sf.heads) acc += super_walk_tree(sf, h, x.data(), h.steps + 2u, nullptr);
       out[r] = acc;
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
+// emit_super's arrays themselves, for the CPU test-suite's checks of what flatten.hpp promises: nodes = four 32-bit
+// words per record {thr0, thrL, thrR as float bits, meta}, heads = four words per tree {base, root_meta, root_thr
+// bits, steps}, packed = per tree 1 if its deep groups were numbered by line.  info[0] = records, info[1] = trees;
+// every array is written up to its cap (caps 0: ask for the sizes).  Returns 1 if the booster does not fit the format.
+int ohx_super_records_cpu(const uint8_t* model, uint64_t model_len, int super_pack, uint32_t* nodes, uint64_t cap_nodes,
+                          uint32_t* heads, uint8_t* packed, uint64_t cap_trees, uint64_t* info) {
+  try {
+    Forest f = load_model_buffer(model, (size_t)model_len);
+    f.validate();
+    SuperForest sf;
+    if (!emit_super(f, &sf, super_pack)) return 1;
+    info[0] = sf.nodes.size();
+    info[1] = sf.heads.size();
+    static_assert(sizeof(SuperNode) == 16 && sizeof(SuperTreeHead) == 16, "four words each");
+    if (cap_nodes) memcpy(nodes, sf.nodes.data(), std::min<size_t>(cap_nodes, sf.nodes.size()) * 16);
+    if (cap_trees) {
+      memcpy(heads, sf.heads.data(), std::min<size_t>(cap_trees, sf.heads.size()) * 16);
+      memcpy(packed, sf.packed.data(), std::min<size_t>(cap_trees, sf.packed.size()));
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    g_err = e.what();
+    return -1;
+  }
+}
+
+// Distinct cache lines per deep gather (line_count.cpp count_super_lines, which says what rows and shape mean; shape =
+// {li, lj, lk, k_fastest}, NULL or all 0: 64 consecutive rows a wave).  table: six doubles per step for steps 0 ..
+// 31 - wave-gathers, then the sums of distinct records, of look-ups, of 128-byte lines, then blocks of 16 tiles and the
+// sum of their distinct lines.  info[0] = records of the forest, info[1] = fillers among them, info[2] = trees
+// numbered by line.  Returns 1 if the booster does not fit the format.
+int ohx_super_line_count(const uint8_t* model, uint64_t model_len, int super_pack, const float* rows, uint64_t ntile,
+                         uint32_t ncol, float missing, const uint32_t* shape, uint32_t first_step, double* table,
+                         uint64_t* info) {
+  try {
+    Forest f = load_model_buffer(model, (size_t)model_len);
+    f.validate();
+    SuperForest sf;
+    if (!emit_super(f, &sf, super_pack)) return 1;
+    LineCountShape sh;
+    if (shape) sh.li = shape[0], sh.lj = shape[1], sh.lk = shape[2], sh.k_fastest = shape[3];
+    if (sh.li + sh.lj + sh.lk != 6 && sh.li + sh.lj + sh.lk != 0) throw OhxError("ohx_super_line_count: a brick is 64 gridcells");
+    std::vector<LineCountStep> steps(kLineCountMaxSteps);
+    count_super_lines(sf, f.num_feature, rows, ntile, ncol, missing, sh, first_step, steps.data());
+    for (uint32_t s = 0; s < kLineCountMaxSteps; ++s) {
+      const LineCountStep& st = steps[s];
+      const double row[6] = {st.gathers, st.records, st.lookups, st.lines, st.block_gathers, st.block_lines};
+      memcpy(table + 6 * s, row, sizeof row);
+    }
+    if (info) {
+      uint64_t fillers = 0, by_line = 0;
+      const uint32_t filler_meta = super_meta(0, 0, 0, 1, 1, 1, 0);
+      for (const SuperNode& n : sf.nodes) fillers += n.meta == filler_meta && std::isinf(n.thr0);
+      for (uint8_t p : sf.packed) by_line += p;
+      info[0] = sf.nodes.size();
+      info[1] = fillers;
+      info[2] = by_line;
     }
     return 0;
   } catch (const std::exception& e) {

@@ -64,6 +64,12 @@ def _load():
         lib.ohx_super_walk_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float,
                                            C.c_void_p, C.POINTER(C.c_uint64)]
         lib.ohx_super_heads_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.ohx_super_walk_pack_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32,
+                                                C.c_float, C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.ohx_super_records_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_void_p,
+                                              C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.ohx_super_line_count.argtypes = [C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_uint64, C.c_uint32,
+                                             C.c_float, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_uint64)]
         lib.ohx_contribs_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int,
                                          C.c_uint, C.c_void_p]
         lib.ohx_contribs_table_stats.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -170,21 +176,78 @@ def cat_flatten_cpu(image):
             "inline_sets": int(info[3]), "word_sets": int(info[4])}
 
 
-def super_walk_cpu(image, rows: np.ndarray, missing: float = XX_MISS):
+SUPER_PACKS = (0, 1, 2, 3)   # csrc/flatten.hpp kSuperPack*: breadth first, + 128-byte tree bases, + sibling pairs, + families
+
+
+def super_walk_cpu(image, rows: np.ndarray, missing: float = XX_MISS, super_pack=None):
     """Host check of the super-node layout the kernels read (csrc/flatten.hpp): emit_super's arrays walked
     the kernels' way - fixed trip count per tree, no finished state, fillers - by a scalar loop.  Test
-    support, not a prediction path.  Returns (margins, info) or (None, None) if the booster does not fit."""
+    support, not a prediction path.  super_pack: the placement of the groups ("ohx_super_pack"; None = what a booster
+    uploads by default).  Returns (margins, info) or (None, None) if the booster does not fit."""
     lib = _load()
     src = np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else image
     rows = np.ascontiguousarray(rows, dtype=np.float32)
     out = np.empty(rows.shape[0], dtype=np.float32)
     info = (C.c_uint64 * 4)()
-    rc = lib.ohx_super_walk_cpu(src.ctypes.data, src.nbytes, rows.ctypes.data, rows.shape[0], rows.shape[1], missing,
-                                out.ctypes.data, info)
+    if super_pack is None:
+        rc = lib.ohx_super_walk_cpu(src.ctypes.data, src.nbytes, rows.ctypes.data, rows.shape[0], rows.shape[1], missing,
+                                    out.ctypes.data, info)
+    else:
+        rc = lib.ohx_super_walk_pack_cpu(src.ctypes.data, src.nbytes, int(super_pack), rows.ctypes.data, rows.shape[0],
+                                         rows.shape[1], missing, out.ctypes.data, info)
     if rc == 1:
         return None, None
     _check(rc)
     return out, {"super_nodes": int(info[0]), "phase1_trees": int(info[1]), "steps": int(info[2])}
+
+
+def super_records_cpu(image, super_pack: int):
+    """emit_super's arrays (csrc/flatten.hpp) for `super_pack`: dict of nodes uint32 [records][4] = {thr0, thrL, thrR as
+    float bits, meta}, heads uint32 [trees][4] = {base, root_meta, root_thr bits, steps}, packed uint8 [trees] = the
+    tree's deep groups were numbered by line.  None if the booster does not fit the super-node format."""
+    lib = _load()
+    src = np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else image
+    info = (C.c_uint64 * 2)()
+    rc = lib.ohx_super_records_cpu(src.ctypes.data, src.nbytes, int(super_pack), None, 0, None, None, 0, info)
+    if rc == 1:
+        return None
+    _check(rc)
+    nodes = np.zeros((int(info[0]), 4), dtype=np.uint32)
+    heads = np.zeros((int(info[1]), 4), dtype=np.uint32)
+    packed = np.zeros(int(info[1]), dtype=np.uint8)
+    _check(lib.ohx_super_records_cpu(src.ctypes.data, src.nbytes, int(super_pack), nodes.ctypes.data, nodes.shape[0],
+                                     heads.ctypes.data, packed.ctypes.data, heads.shape[0], info))
+    return {"nodes": nodes, "heads": heads, "packed": packed}
+
+
+def super_line_count(image, tiles: np.ndarray, super_pack: int, brick=None, k_fastest: bool = True,
+                     first_step: int = 4, missing: float = XX_MISS):
+    """Distinct cache lines per deep gather of the super-node walk, counted on the host (csrc/line_count.cpp).  tiles:
+    (ntile, 64, ncol) rows, a tile's 64 gridcells in grid order (i fastest, then j, then k inside the brick), 16
+    consecutive tiles one block's; brick = (li, lj, lk) log2 extents of the brick a wave takes (None: 64 consecutive
+    rows) and k_fastest its lane order, as the launch picks them.  Returns (table, info): table[step] = dict of means
+    per wave-gather for the 0-based steps from first_step on that any tree has - records, lookups (64-byte blocks per
+    quad, summed over the quads), lines (128 bytes), block_lines (128-byte lines per block of 16 tiles) - and the
+    gathers counted; info = records of the forest, fillers among them, trees numbered by line."""
+    lib = _load()
+    src = np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else image
+    tiles = np.ascontiguousarray(tiles, dtype=np.float32)
+    assert tiles.ndim == 3 and tiles.shape[1] == 64
+    shape = np.array(list(brick) + [1 if k_fastest else 0] if brick else [0, 0, 0, 0], dtype=np.uint32)
+    raw = np.zeros((32, 6), dtype=np.float64)
+    info = (C.c_uint64 * 3)()
+    rc = lib.ohx_super_line_count(src.ctypes.data, src.nbytes, int(super_pack), tiles.ctypes.data, tiles.shape[0],
+                                  tiles.shape[2], missing, shape.ctypes.data, first_step, raw.ctypes.data, info)
+    if rc == 1:
+        return None, None
+    _check(rc)
+    table = {}
+    for s in range(32):
+        g, rec, look, lines, bg, bl = raw[s]
+        if g > 0:
+            table[s] = {"gathers": int(g), "records": rec / g, "lookups": look / g, "lines": lines / g,
+                        "block_lines": bl / bg if bg > 0 else float("nan")}
+    return table, {"records": int(info[0]), "fillers": int(info[1]), "packed_trees": int(info[2])}
 
 
 def super_heads_cpu(image):
