@@ -437,6 +437,51 @@ int OHXScatterCells(const float* values, int64_t stride, int64_t col, const int6
 int OHXScatterCellsDevice(const float* d_values, int64_t stride, int64_t col, const int64_t* d_cells, int64_t ncell,
                           float* d_out3d, int im, int jm, int km, uint32_t* d_status, void* stream);
 
+/* Node visit counts, and the covers refreshed from them (docs/16_visit_counts.md).  Every contribution the library
+ * computes is weighted by sum_hess, the cover the training run left in the model file: it answers "relative to the
+ * training set".  These calls count how many rows of the CALLER's data pass every node, and make those counts the
+ * covers, so that contributions answer "relative to this data" - xgboost's process_type = update, updater = refresh,
+ * refresh_leaf = 0 on data whose hessian is 1 a row (reg:squarederror); parity with libxgboost is not pinned.
+ * Counting.  OHXBoosterCountVisits walks every row of the matrix down EVERY tree exactly as a margin predict does (a
+ * value that is NaN or equal to the matrix's `missing` takes the default child; a column the matrix lacks is missing;
+ * x < cond goes left; +-inf is compared as the float it is - XGDMatrixCreateFromMat has already refused it for host
+ * data, and the count calls raise no flag) and adds one to the counter of the leaf it reaches.  Both matrix forms.
+ * Counts ACCUMULATE over calls until OHXBoosterResetVisitCounts, a model load or XGBoosterFree; an "ohx_device" move
+ * resets them too.  The host form returns when the rows are added; the device form only enqueues on `stream` and is
+ * not capturable.  Counts are integers (64-bit counters, integer atomics only, no float atomics): they do not depend
+ * on the batch split, the launch shape, OHXDMatrixSetGrid, a knob, or the form.  Knobs, for tests and measurements:
+ * "ohx_visits_kernel" = auto | global | lds (global: one 64-bit global add per distinct leaf and wave; lds: a tree
+ * whose leaf histogram fits keeps it in LDS and flushes it once per block; auto = global, the faster of the two on the
+ * C360 L72 batch, docs/16_visit_counts.md 16.4), "ohx_visits_lds_leaves" = n (with lds: a tree of more than n leaves
+ * is counted the global way; auto or 0 = what fits a CU).
+ * Reading.  OHXBoosterGetVisitCounts waits for `stream`, copies the leaf counters back and sums them up each tree on
+ * the host.  *ntree = the trees; tree_offsets has *ntree + 1 entries; counts[tree_offsets[t] + n] is the number of
+ * counted rows that passed node n of file tree t, in the file's node numbering; *rows_seen = the rows counted.  A
+ * tree's root equals *rows_seen, a split equals the sum of its two children, unreachable and deleted slots are 0.  The
+ * buffers are the booster's and stay valid until the next visits call on it.  Before any count: all zeros.
+ * Refresh.  OHXBoosterRefreshCover waits for `stream` and stores, for every node reachable from a root,
+ *   sum_hess := (float)count + prior_weight * sum_hess_old
+ * in float32, the product rounded and then the sum (no fused multiply-add).  prior_weight = 0 is xgboost's refresh on
+ * hessian-1 data; prior_weight > 0 blends the training cover in, so that subtrees no counted row reached keep a
+ * positive cover.  All or nothing.  Refused with the forest untouched: nothing counted yet; prior_weight negative or
+ * not finite; any SPLIT whose new cover would not be finite and > 0 (the message names the first such tree and node and
+ * says how many of the splits there are; a LEAF of cover 0 stays legal, as in OHXBoosterPredictContribs).  On success
+ * the contributions state is dropped exactly as a model load drops it (its tables are rebuilt at the next call), the
+ * counters are kept, XGBoosterSaveModel writes the new sum_hess in all three formats, unreachable nodes keep their old
+ * value, and every prediction is unchanged bit for bit: no walk reads cover.
+ * Refused at the top of every one of the five calls: no model; a booster with categorical splits; several output
+ * groups; NULL output arguments; and, for the count calls, more columns than features, no usable HIP device, and (the
+ * device form) a stream that is being captured.  The visit state - the walk's own node format, the counters, the
+ * result buffers - is built at first use and never shares a buffer with the predict, fields, Run1 or contributions
+ * paths (a graph captured earlier still replays); dropped when a model is loaded and at XGBoosterFree;
+ * OHXReleaseScratch leaves it alone.  Calls on ONE booster must not run concurrently (OHXBoosterPredictDevice). */
+int OHXBoosterCountVisits(BoosterHandle handle, DMatrixHandle dmat);
+int OHXBoosterCountVisitsDevice(BoosterHandle handle, DMatrixHandle dmat, void* stream);
+int OHXBoosterGetVisitCounts(BoosterHandle handle, void* stream, bst_ulong* ntree, const bst_ulong** tree_offsets,
+                             const uint64_t** counts, uint64_t* rows_seen);
+int OHXBoosterResetVisitCounts(BoosterHandle handle);
+int OHXBoosterRefreshCover(BoosterHandle handle, void* stream, float prior_weight);
+
 /* The whole of predict_OH_with_XGB's RUN section in one kernel
  * (OH_GridCompMod.F90:303-383): gathers the 27 MAPL fields in place (field f is
  * (im,jm,km) Fortran order, or (im,jm) when is2d[f] != 0; feature order of

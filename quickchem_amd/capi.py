@@ -20,6 +20,11 @@ LIB_PATH = os.path.join(_HERE, "lib", "libohxgb.so")
 RING_ROUNDS_DEFAULT = 64
 RING_ROUNDS_NO_GRID = 16      # kRingRoundsNoGrid: at most, for rows not known to lie on a grid
 RING_ROUNDS_PERMUTED = 4      # kRingRoundsPermuted: at most, for rows that come through the clustering pass
+# visit counts (csrc/visits.hpp): a block is 4 waves of 64 rows and strides over the tiles; blocks of one launch per CU at
+# most - the LDS kernel's per tree - so one trip of a kernel's loop is CUs x this x 256 rows
+VISITS_BLOCK_ROWS = 256
+VISITS_LDS_BLOCKS_PER_CU = 1
+VISITS_GLOBAL_BLOCKS_PER_CU = 4
 
 # every symbol include/ohxgb.h declares
 ABI_SYMBOLS = [
@@ -30,6 +35,8 @@ ABI_SYMBOLS = [
     "OHXBoosterPredictContribs", "OHXBoosterPredictContribsDevice",
     "OHXBoosterPredictInteractions", "OHXBoosterPredictInteractionsDevice",
     "OHXBoosterPredictContribsFields", "OHXBoosterPredictContribsFieldsDevice",
+    "OHXBoosterCountVisits", "OHXBoosterCountVisitsDevice", "OHXBoosterGetVisitCounts", "OHXBoosterResetVisitCounts",
+    "OHXBoosterRefreshCover",
     "OHXSelectCells", "OHXSelectCellsDevice", "OHXGatherCells", "OHXGatherCellsDevice",
     "OHXScatterCells", "OHXScatterCellsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
@@ -122,6 +129,12 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                                     i32, i32, f32, i32, C.c_uint, C.POINTER(vp)]
     lib.OHXBoosterPredictContribsFieldsDevice.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32,
                                                           i32, i32, i32, f32, i32, C.c_uint, C.POINTER(vp), vp]
+    lib.OHXBoosterCountVisits.argtypes = [vp, vp]
+    lib.OHXBoosterCountVisitsDevice.argtypes = [vp, vp, vp]
+    lib.OHXBoosterGetVisitCounts.argtypes = [vp, vp, C.POINTER(u64), C.POINTER(C.POINTER(u64)), C.POINTER(C.POINTER(u64)),
+                                             C.POINTER(u64)]
+    lib.OHXBoosterResetVisitCounts.argtypes = [vp]
+    lib.OHXBoosterRefreshCover.argtypes = [vp, vp, f32]
     lib.OHXBoosterPredictFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32,
                                             f32, i32, f32, vp, vp]
     i64 = C.c_int64
@@ -378,6 +391,37 @@ class Booster:
         """The same into device memory: out_ptr holds nrow * (F + 1)^2 float32; only enqueues on `stream`."""
         check(self.lib, self.lib.OHXBoosterPredictInteractionsDevice(self.handle, dmat.handle, int(bool(approximate)),
                                                                       ntree_limit, out_ptr, stream))
+
+    def count_visits(self, dmat: DMatrix) -> None:
+        """OHXBoosterCountVisits: every row of `dmat` walks every tree as a margin predict does and adds one to the
+        counter of the leaf it reaches; counts accumulate until reset_visit_counts or a model load.  Returns when the
+        rows are added."""
+        check(self.lib, self.lib.OHXBoosterCountVisits(self.handle, dmat.handle))
+
+    def count_visits_device(self, dmat: DMatrix, stream: int = 0) -> None:
+        """The same, only enqueued on `stream` (not capturable)."""
+        check(self.lib, self.lib.OHXBoosterCountVisitsDevice(self.handle, dmat.handle, stream or None))
+
+    def visit_counts(self, stream: int = 0):
+        """OHXBoosterGetVisitCounts -> (counts, rows_seen): counts[t][n] = the counted rows that passed node n of file
+        tree t (np.uint64, file node numbering; copies).  Waits for `stream`."""
+        ntree, seen = C.c_uint64(), C.c_uint64()
+        offs, cnt = C.POINTER(C.c_uint64)(), C.POINTER(C.c_uint64)()
+        check(self.lib, self.lib.OHXBoosterGetVisitCounts(self.handle, stream or None, C.byref(ntree), C.byref(offs),
+                                                           C.byref(cnt), C.byref(seen)))
+        if ntree.value == 0:
+            return [], int(seen.value)
+        o = [int(offs[t]) for t in range(ntree.value + 1)]
+        flat = np.ctypeslib.as_array(cnt, shape=(max(o[-1], 1),))
+        return [flat[o[t]:o[t + 1]].astype(np.uint64) for t in range(ntree.value)], int(seen.value)
+
+    def reset_visit_counts(self) -> None:
+        check(self.lib, self.lib.OHXBoosterResetVisitCounts(self.handle))
+
+    def refresh_cover(self, prior_weight: float = 0.0, stream: int = 0) -> None:
+        """OHXBoosterRefreshCover: sum_hess := float32(count) + prior_weight * sum_hess for every reachable node, all or
+        nothing; contributions computed afterwards are weighted by the counted data's covers."""
+        check(self.lib, self.lib.OHXBoosterRefreshCover(self.handle, stream or None, prior_weight))
 
     def predict_fields(self, fields: Sequence[np.ndarray], is2d: Sequence[bool], pl_feature: int, im: int, jm: int,
                        km: int, k1: int, k2: int, missing: float, oh_ml: np.ndarray, *, apply_pow10: bool = True,

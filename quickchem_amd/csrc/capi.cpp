@@ -32,6 +32,7 @@
 #include "forest.hpp"
 #include "groups.hpp"
 #include "kernels.hpp"
+#include "visits.hpp"
 
 using namespace ohx;
 
@@ -598,6 +599,26 @@ struct ContribsState {
   }
 };
 
+// Node visit counts (OHXBoosterCountVisits; visits.hpp): the walk's own node format, the leaf counters and the buffers
+// the results come back in.  Built at the first visits call on the loaded model - the host part (no device needed) by any
+// of the five calls, the device part by the first count - and never sharing a buffer with the predict, fields, Run1 or
+// contributions paths.  Dropped with the model (adopt_model), with the booster and by an "ohx_device" move;
+// OHXReleaseScratch leaves it alone.
+struct VisitState {
+  VisitForest vf;                     // nodes, roots, leaf maps (host)
+  VisitPlan plan;                     // which trees take the LDS path, for the knobs below
+  uint32_t plan_lds_leaves = 0;
+  bool plan_use_lds = false, plan_uploaded = false;
+  int device = -1;                    // where the device part lives; -1 = not built yet
+  int num_cus = 0;
+  DevBuf<VisitNode> d_nodes;
+  DevBuf<uint32_t> d_roots, d_leaf_offset, d_lds_trees, d_global_trees;
+  DevBuf<unsigned long long> d_counts;
+  PinnedBuf<unsigned long long> h_leaf;
+  std::vector<uint64_t> node_counts;  // what OHXBoosterGetVisitCounts hands out
+  uint64_t rows_seen = 0;
+};
+
 struct BoosterObj {
   ~BoosterObj() {
     for (hipEvent_t e : {run1_fork, run1_slab, run1_join, run1_clear})
@@ -733,6 +754,10 @@ struct BoosterObj {
   bool cat_force_direct = false;        // "ohx_cat_kernel" = direct: margins by the direct kernel too (same bits)
   std::unique_ptr<ContribsState> contribs;
   bool contribs_split = true;           // "ohx_contribs_split": small batches may have their trees split over waves
+  std::unique_ptr<VisitState> visits;
+  bool visits_use_lds = false;          // "ohx_visits_kernel" = lds: trees whose leaf histogram fits in LDS keep it there
+                                        // (auto and global: every tree the global way - the faster at C360; same integers)
+  uint32_t visits_lds_leaves = 0;       // "ohx_visits_lds_leaves": leaves a block's LDS histogram may hold (0 = what fits)
 };
 
 DMatrixObj* as_dmat(DMatrixHandle h) {
@@ -1038,6 +1063,7 @@ void adopt_model(BoosterObj& b, Forest&& f) {
   for (const std::string& w : f.warnings) fprintf(stderr, "[libohxgb] warning: model file: %s\n", w.c_str());
   invalidate_device_state(b);
   b.contribs.reset();
+  b.visits.reset();
   b.forest = std::move(f);
   b.num_groups = b.forest.num_groups();
   b.num_cat = b.forest.num_categorical_splits();
@@ -1831,6 +1857,107 @@ ExplainResult explain(BoosterObj& b, const ExplainCall& q) {
   return res;
 }
 
+// ---- node visit counts (visits.hpp) ----
+
+// What every one of the five calls refuses first, then the state's host part (built at first use; no device needed)
+VisitState& visits_begin(BoosterObj& b, const char* what) {
+  if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
+  refuse_categorical(b, what);
+  refuse_groups(b, what);
+  if (!b.visits) {
+    auto v = std::make_unique<VisitState>();
+    v->vf = emit_visits(b.forest, place_forest(b.forest, b.layout));
+    v->node_counts.assign((size_t)v->vf.tree_offsets.back(), 0);
+    b.visits = std::move(v);
+  }
+  return *b.visits;
+}
+
+// The device part, and the plan's tree lists for the knobs as they stand.  Waits for the library's stream: never called
+// inside a capture.
+void visits_on_device(BoosterObj& b, VisitState& v) {
+  // the booster's device (where it has one already), without building any of the predict path's device forms; throws
+  // where there is no usable HIP device
+  const DeviceInfo dev = use_device(b.uploaded ? b.dev.ordinal : b.device_pref);
+  hipStream_t exec = lib_streams(dev.ordinal).exec;
+  if (v.device != dev.ordinal) {
+    v.d_nodes.upload(v.vf.nodes);
+    v.d_roots.upload(v.vf.roots);
+    v.d_leaf_offset.upload(v.vf.leaf_offset);
+    const size_t leaves = v.vf.leaf_offset.back();
+    v.d_counts.ensure(leaves);
+    v.h_leaf.ensure(leaves);
+    HIP_CHECK(hipMemsetAsync(v.d_counts.p, 0, std::max<size_t>(leaves, 1) * sizeof(unsigned long long), exec));
+    HIP_CHECK(hipStreamSynchronize(exec));
+    v.rows_seen = 0;
+    v.plan_uploaded = false;
+    v.device = dev.ordinal;
+    v.num_cus = dev.num_cus;
+  }
+  if (!v.plan_uploaded || v.plan_lds_leaves != b.visits_lds_leaves || v.plan_use_lds != b.visits_use_lds) {
+    // (a count enqueued earlier may still read the lists: the upload below waits for the library's stream only)
+    if (v.plan_uploaded) HIP_CHECK(hipDeviceSynchronize());
+    v.plan = plan_visits(v.vf, b.forest.num_feature, b.visits_lds_leaves, /*force_global=*/!b.visits_use_lds);
+    v.d_lds_trees.upload(v.plan.lds_trees);
+    v.d_global_trees.upload(v.plan.global_trees);
+    HIP_CHECK((hipError_t)prepare_count_visits(v.plan));      // once per plan: the kernels' dynamic LDS limits
+    v.plan_lds_leaves = b.visits_lds_leaves;
+    v.plan_use_lds = b.visits_use_lds;
+    v.plan_uploaded = true;
+  }
+}
+
+// The booster's refusals come before the matrix handle is looked at.
+void count_visits(BoosterObj& b, DMatrixHandle dmat, bool host_form, hipStream_t caller, const char* what) {
+  VisitState& v = visits_begin(b, what);
+  DMatrixObj& d = *as_dmat(dmat);
+  check_columns(b, d.ncol);
+  // before the device part is built: building it waits for the library's stream
+  if (!host_form && stream_capturing(caller))
+    refuse_in_capture("count node visits", (std::string(what) + " is not capturable; call it outside the capture").c_str());
+  visits_on_device(b, v);
+  if (d.device >= 0 && d.device != v.device)
+    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
+                   std::to_string(v.device));
+  hipStream_t stream = host_form ? lib_streams(v.device).exec : caller;
+  if (host_form && d.owned == nullptr) order_behind_caller(v.device, stream);
+  DeviceVisitForest fr;
+  fr.nodes = v.d_nodes.p;
+  fr.node_bytes = (uint32_t)(v.vf.nodes.size() * sizeof(VisitNode));
+  fr.roots = v.d_roots.p;
+  fr.leaf_offset = v.d_leaf_offset.p;
+  fr.lds_trees = v.d_lds_trees.p;
+  fr.global_trees = v.d_global_trees.p;
+  fr.num_trees = (uint32_t)b.forest.trees.size();
+  fr.num_feature = b.forest.num_feature;
+  fr.total_leaves = v.vf.leaf_offset.back();
+  VisitArgs a;
+  a.rows = d.d_data;
+  a.nrow = d.nrow;
+  a.ncol = (uint32_t)d.ncol;
+  a.missing = d.missing;
+  a.counts = v.d_counts.p;
+  HIP_CHECK((hipError_t)launch_count_visits(fr, a, v.plan, v.num_cus, tune_for(b, d), stream));
+  v.rows_seen += d.nrow;
+  if (host_form) HIP_CHECK(hipStreamSynchronize(stream));
+  else d.used_async = true;
+}
+
+// Waits for `stream`, brings the leaf counters back and sums them up each tree (v.node_counts).  A state that has never
+// counted has no device part: all zeros.
+void read_visit_counts(BoosterObj& b, VisitState& v, hipStream_t stream) {
+  const size_t leaves = v.vf.leaf_offset.back();
+  if (v.device < 0) {
+    std::fill(v.node_counts.begin(), v.node_counts.end(), 0);
+    return;
+  }
+  HIP_CHECK(hipSetDevice(v.device));
+  if (leaves) HIP_CHECK(hipMemcpyAsync(v.h_leaf.p, v.d_counts.p, leaves * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
+  HIP_CHECK(hipStreamSynchronize(stream));
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are uint64");
+  visit_node_sums(b.forest, v.vf, reinterpret_cast<const uint64_t*>(v.h_leaf.p), v.node_counts.data());
+}
+
 }  // namespace
 
 // =================================================================== C ABI
@@ -2213,9 +2340,29 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
     // boosters with categorical splits: "direct" = margins by the direct kernel too (the same bits as the tile kernel's)
     if (v != "auto" && v != "direct") throw OhxError("ohx_cat_kernel must be auto or direct");
     b->cat_force_direct = v == "direct";
+  } else if (n == "ohx_visits_kernel") {
+    // visit counts: "lds" = a tree whose leaf histogram fits keeps it in LDS; "global" = one global add per distinct leaf
+    // and wave for every tree.  The same integers; auto is global, the faster of the two where it was measured
+    // (docs/16_visit_counts.md 16.4)
+    if (v != "auto" && v != "global" && v != "lds") throw OhxError("ohx_visits_kernel must be auto, global or lds");
+    b->visits_use_lds = v == "lds";
+  } else if (n == "ohx_visits_lds_leaves") {
+    // visit counts, "ohx_visits_kernel" = lds: the most leaves a tree may have to keep its histogram in LDS ("auto" or
+    // 0 = what fits a CU)
+    long k = 0;
+    if (v != "auto") {
+      char* end = nullptr;
+      k = strtol(value, &end, 10);
+      if (v.empty() || end == value || *end != '\0' || k < 0 || k > 0x7FFFFFFFl)
+        throw OhxError("ohx_visits_lds_leaves must be auto or a whole number >= 0");
+    }
+    b->visits_lds_leaves = (uint32_t)k;
   } else if (n == "ohx_device") {
     int k = atoi(value);
-    if (k != b->device_pref) invalidate_device_state(*b);
+    if (k != b->device_pref) {
+      invalidate_device_state(*b);
+      b->visits.reset();               // the visit counts live on the device they were counted on
+    }
     b->device_pref = k;
   }
   // any other name is an xgboost training/runtime parameter with no meaning here
@@ -2327,6 +2474,70 @@ int OHXBoosterPredictInteractionsDevice(BoosterHandle handle, DMatrixHandle dmat
   q.stream = static_cast<hipStream_t>(stream);
   explain(*b, q);
   q.d->used_async = true;
+  API_END();
+}
+
+int OHXBoosterCountVisits(BoosterHandle handle, DMatrixHandle dmat) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  count_visits(*b, dmat, true, nullptr, "OHXBoosterCountVisits");
+  API_END();
+}
+
+int OHXBoosterCountVisitsDevice(BoosterHandle handle, DMatrixHandle dmat, void* stream) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  count_visits(*b, dmat, false, static_cast<hipStream_t>(stream), "OHXBoosterCountVisitsDevice");
+  API_END();
+}
+
+int OHXBoosterGetVisitCounts(BoosterHandle handle, void* stream, bst_ulong* ntree, const bst_ulong** tree_offsets,
+                             const uint64_t** counts, uint64_t* rows_seen) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  VisitState& v = visits_begin(*b, "OHXBoosterGetVisitCounts");
+  if (ntree == nullptr || tree_offsets == nullptr || counts == nullptr || rows_seen == nullptr)
+    throw OhxError("OHXBoosterGetVisitCounts: NULL output argument");
+  read_visit_counts(*b, v, static_cast<hipStream_t>(stream));
+  static_assert(sizeof(bst_ulong) == sizeof(uint64_t), "tree_offsets are handed out as bst_ulong");
+  *ntree = b->forest.trees.size();
+  *tree_offsets = reinterpret_cast<const bst_ulong*>(v.vf.tree_offsets.data());
+  *counts = v.node_counts.data();
+  *rows_seen = v.rows_seen;
+  API_END();
+}
+
+int OHXBoosterResetVisitCounts(BoosterHandle handle) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  VisitState& v = visits_begin(*b, "OHXBoosterResetVisitCounts");
+  if (v.device >= 0) {
+    // behind every count, whatever stream it was enqueued on
+    HIP_CHECK(hipSetDevice(v.device));
+    HIP_CHECK(hipDeviceSynchronize());
+    hipStream_t s = lib_streams(v.device).exec;
+    HIP_CHECK(hipMemsetAsync(v.d_counts.p, 0, std::max<size_t>(v.vf.leaf_offset.back(), 1) * sizeof(unsigned long long), s));
+    HIP_CHECK(hipStreamSynchronize(s));
+  }
+  std::fill(v.node_counts.begin(), v.node_counts.end(), 0);
+  v.rows_seen = 0;
+  API_END();
+}
+
+int OHXBoosterRefreshCover(BoosterHandle handle, void* stream, float prior_weight) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  VisitState& v = visits_begin(*b, "OHXBoosterRefreshCover");
+  if (!(std::isfinite(prior_weight) && prior_weight >= 0.0f))
+    throw OhxError("OHXBoosterRefreshCover: prior_weight must be finite and >= 0");
+  if (v.rows_seen == 0)
+    throw OhxError("OHXBoosterRefreshCover: no row has been counted yet (OHXBoosterCountVisits); the covers are unchanged");
+  read_visit_counts(*b, v, static_cast<hipStream_t>(stream));
+  // all or nothing: every new cover is computed (and every split's judged) before the first one is stored
+  std::vector<std::vector<float>> covers = refreshed_covers(b->forest, v.vf, v.node_counts.data(), prior_weight);
+  for (size_t t = 0; t < covers.size(); ++t) b->forest.trees[t].sum_hess = std::move(covers[t]);
+  // the contributions' tables hold the old covers: dropped exactly as a model load drops them, rebuilt at the next call
+  b->contribs.reset();
   API_END();
 }
 

@@ -283,6 +283,43 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
+      !  Node visit counts and the covers refreshed from them (include/ohxgb.h; docs/16_visit_counts.md).
+      !  Interface blocks only: nothing the oracle-linked drivers link calls them.
+      function OHXBoosterCountVisits(handle, dmat) bind(C, name="OHXBoosterCountVisits") result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: handle, dmat
+         integer(c_int)     :: rc
+      end function
+
+      function OHXBoosterCountVisitsDevice(handle, dmat, stream) bind(C, name="OHXBoosterCountVisitsDevice") result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: handle, dmat, stream
+         integer(c_int)     :: rc
+      end function
+
+      !  tree_offsets: c_ptr to ntree + 1 integer(c_int64_t); counts: c_ptr to tree_offsets(ntree + 1) integer(c_int64_t)
+      function OHXBoosterGetVisitCounts(handle, stream, ntree, tree_offsets, counts, rows_seen) &
+            bind(C, name="OHXBoosterGetVisitCounts") result(rc)
+         import :: c_int, c_ptr, c_int64_t
+         type(c_ptr), value              :: handle, stream
+         integer(c_int64_t), intent(out) :: ntree, rows_seen
+         type(c_ptr), intent(out)        :: tree_offsets, counts
+         integer(c_int)                  :: rc
+      end function
+
+      function OHXBoosterResetVisitCounts(handle) bind(C, name="OHXBoosterResetVisitCounts") result(rc)
+         import :: c_int, c_ptr
+         type(c_ptr), value :: handle
+         integer(c_int)     :: rc
+      end function
+
+      function OHXBoosterRefreshCover(handle, stream, prior_weight) bind(C, name="OHXBoosterRefreshCover") result(rc)
+         import :: c_int, c_ptr, c_float
+         type(c_ptr), value   :: handle, stream
+         real(c_float), value :: prior_weight
+         integer(c_int)       :: rc
+      end function
+
       ! ---- part 4 of ohxgb.h: the OH field reassembled on every GPU of a node, for a host that has MPI but no
       !      torch.distributed.  Rank 0 gets the id, MPI_Bcast carries its OHX_UNIQUE_ID_BYTES bytes, every rank
       !      (hipSetDevice done) inits; d_shard / d_full are DEVICE addresses, stream a hipStream_t (c_null_ptr = default)

@@ -81,6 +81,12 @@ def _load():
         lib.ohx_interactions_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_int, C.POINTER(C.c_uint64)]
         lib.ohx_cat_flatten_cpu.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64,
                                             C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.ohx_visits_layout.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.POINTER(C.c_uint64), C.c_void_p,
+                                          C.c_void_p, C.c_void_p]
+        lib.ohx_visits_node_sums.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64]
+        lib.ohx_visits_refresh.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]
+        lib.ohx_visits_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_void_p,
+                                        C.POINTER(C.c_uint64)]
         _lib = lib
     return _lib
 
@@ -296,6 +302,61 @@ def contribs_plan(nrow: int, nfeat: int, ntree: int, allow_split: bool = True):
     p = (C.c_uint64 * 4)()
     _check(_load().ohx_contribs_plan(nrow, nfeat, ntree, 1 if allow_split else 0, p))
     return bool(p[0]), int(p[1]), int(p[2]), int(p[3])
+
+
+def _image(image) -> np.ndarray:
+    return np.frombuffer(bytes(image), dtype=np.uint8) if not isinstance(image, np.ndarray) else image
+
+
+def visits_layout(image, max_trees: int = 1 << 16, max_leaves: int = 1 << 24):
+    """The visit counts' maps of a booster (csrc/visits.hpp VisitForest) -> (tree_offsets[T + 1] uint64, leaf_offset[T + 1]
+    uint32, leaf_node uint32): counter leaf_offset[t] + l belongs to file node leaf_node[leaf_offset[t] + l] of tree t."""
+    img = _image(image)
+    ntree = C.c_uint64()
+    offs = np.zeros(max_trees + 1, dtype=np.uint64)
+    loff = np.zeros(max_trees + 1, dtype=np.uint32)
+    lnode = np.zeros(max_leaves, dtype=np.uint32)
+    _check(_load().ohx_visits_layout(img.ctypes.data, img.nbytes, max_trees, max_leaves, C.byref(ntree), offs.ctypes.data,
+                                     loff.ctypes.data, lnode.ctypes.data))
+    T = ntree.value
+    return offs[:T + 1].copy(), loff[:T + 1].copy(), lnode[:int(loff[T])].copy()
+
+
+def visits_node_sums(image, leaf_counts) -> np.ndarray:
+    """Leaf counters -> node counts in file numbering, tree after tree (what OHXBoosterGetVisitCounts does on the host)."""
+    img = _image(image)
+    offs, _, lnode = visits_layout(img)
+    leaf_counts = np.ascontiguousarray(leaf_counts, dtype=np.uint64)
+    out = np.full(int(offs[-1]), 0xDEADBEEF, dtype=np.uint64)
+    _check(_load().ohx_visits_node_sums(img.ctypes.data, img.nbytes, leaf_counts.ctypes.data, leaf_counts.size,
+                                        out.ctypes.data, out.size))
+    return out
+
+
+def visits_refresh(image, node_counts, prior_weight: float):
+    """The covers OHXBoosterRefreshCover would store for these node counts -> (sum_hess float32 tree after tree, error):
+    error is None, or the refusal's message - and sum_hess then the forest's covers as they are afterwards."""
+    img = _image(image)
+    node_counts = np.ascontiguousarray(node_counts, dtype=np.uint64)
+    out = np.zeros(node_counts.size, dtype=np.float32)
+    lib = _load()
+    rc = lib.ohx_visits_refresh(img.ctypes.data, img.nbytes, node_counts.ctypes.data, node_counts.size, prior_weight,
+                                out.ctypes.data)
+    return out, (None if rc == 0 else lib.ohx_synth_last_error().decode())
+
+
+def visits_plan(image, lds_leaves: int = 0, force_global: bool = False, num_cus: int = 256, ntiles: int = 1 << 20):
+    """csrc/visits.hpp plan_visits for a booster -> dict: takes_lds (per tree), stage, hist_leaves, the two kernels'
+    dynamic LDS bytes, capacity (leaves), and their blocks for `ntiles` tiles on `num_cus` CUs."""
+    img = _image(image)
+    T = len(visits_layout(img)[0]) - 1
+    takes = np.zeros(max(T, 1), dtype=np.uint8)
+    info = (C.c_uint64 * 8)()
+    _check(_load().ohx_visits_plan(img.ctypes.data, img.nbytes, lds_leaves, int(force_global), num_cus, ntiles,
+                                   takes.ctypes.data, info))
+    return {"takes_lds": takes[:T].astype(bool), "stage": bool(info[0]), "hist_leaves": int(info[1]),
+            "lds_bytes_lds": int(info[2]), "lds_bytes_global": int(info[3]), "capacity": int(info[4]),
+            "lds_blocks": int(info[5]), "global_blocks": int(info[6]), "lds_trees": int(info[7])}
 
 
 def cells_plan(n: int, nfield: int = 27):
