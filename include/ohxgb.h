@@ -482,6 +482,51 @@ int OHXBoosterGetVisitCounts(BoosterHandle handle, void* stream, bst_ulong* ntre
 int OHXBoosterResetVisitCounts(BoosterHandle handle);
 int OHXBoosterRefreshCover(BoosterHandle handle, void* stream, float prior_weight);
 
+/* Leaf refit (docs/17_leaf_refit.md): every tree keeps its structure and every leaf value is estimated again from the
+ * CALLER's rows and labels - the other half of xgboost's process_type = update, updater = refresh: refresh_leaf = 1,
+ * for reg:squarederror (gradient pred - label, hessian 1 a row).  The semantics restate xgboost 1.6.0 (TreeRefresher in
+ * updater_refresh.cc, CalcWeight in param.h); parity with libxgboost is not pinned.
+ * With T trees in file order, `base` the margin every prediction starts from and y the labels, for t = 0 .. T-1:
+ *  1. pred_t[r] = base + new_leaf_0(r) + ... + new_leaf_{t-1}(r), float32, added in tree order per row: the sum a
+ *     margin predict of the refit model makes.
+ *  2. Row r reaches leaf l_t(r) of tree t exactly as a margin predict does - the walk of OHXBoosterCountVisits: NaN, the
+ *     matrix's `missing` or a column the matrix lacks takes the default child; x < cond goes left; +-inf is compared as
+ *     the float it is.  The walk does not read leaf values.
+ *  3. g = pred_t[r] - y[r], one float32 subtraction; q = (int64) rint(g * 2^24): the product is exact in float32, the
+ *     rounding is to nearest even.
+ *  4. G_l = the sum of q over the leaf's rows, an int64; H_l = the number of those rows.  Integer adds only (no float
+ *     atomics): the sums depend on neither the order of the rows, the launch shape, the form, nor
+ *     OHXDMatrixSetGrid.
+ *  5. w = (float)( -((double)G_l * 2^-24) / ((double)H_l + (double)lambda) ).
+ *  6. new_leaf = w * eta, one float32 multiply (no fused multiply-add).  This is CalcWeight with reg_alpha = 0,
+ *     max_delta_step = 0 and min_child_weight <= 1, times learning_rate.  The leaf's base_weight becomes w.
+ *  7. A leaf no row reaches (H_l == 0): unvisited = 0 keeps its value and base_weight - a stated departure from
+ *     xgboost: no row says anything about such a leaf; unvisited = 1 stores +0.0f in both, as xgboost does.
+ * *leaves_refit (may be NULL) receives the number of leaves with H_l > 0 over all trees.
+ * All or nothing: the forest is replaced only after every tree is done and the device's error word has been read back
+ * clean.  Refused, with the forest untouched: no model; categorical splits; several output groups; an objective that
+ * is not identity / squared error; NULL labels; eta not finite; lambda not finite or negative; unvisited not 0 or 1;
+ * nlabel != the matrix's rows, or no rows; more than 2^31 rows; more columns than features; a stream that is being
+ * captured (nothing is enqueued); no usable HIP device (no CPU fallback); a leaf-id buffer that cannot be allocated
+ * (the message says how many bytes T * nrow * 4 is); and any row at any tree whose g is not finite or has
+ * |g| >= 256 - the kernels raise a flag and the message says "label" (|q| < 2^32 and at most 2^31 rows is what keeps G
+ * inside an int64).
+ * On success leaf value and base_weight are replaced and every other array of the forest is untouched - sum_hess
+ * included, which remains OHXBoosterRefreshCover's job.  Everything built from leaf values is dropped as a model load
+ * drops it: the flattened device forests and the contributions state; a graph captured earlier is as stale as after
+ * XGBoosterLoadModel.  The visit state holds no leaf value and is kept with its counters.  XGBoosterSaveModel writes
+ * the new leaves in all three formats.
+ * Both forms wait.  The host form stages the labels and returns when the forest is replaced.  The device form takes
+ * d_labels in HBM (nlabel floats, ready on `stream`), enqueues on `stream` and waits for it once at the end, to read the
+ * leaves and the error word back - as OHXBoosterRefreshCover waits.  The refit state (the walk's node format, T x nrow
+ * leaf ids, the running prediction, the sums, the leaf tables, the staged labels) is the booster's own and never a
+ * buffer of the predict, fields, Run1, contributions or visit paths; dropped when a model is loaded, by an
+ * "ohx_device" move and at XGBoosterFree.  Calls on ONE booster must not run concurrently. */
+int OHXBoosterRefitLeaves(BoosterHandle handle, DMatrixHandle dmat, const float* labels, bst_ulong nlabel, float eta,
+                          float lambda, int unvisited, bst_ulong* leaves_refit);
+int OHXBoosterRefitLeavesDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels, bst_ulong nlabel,
+                                float eta, float lambda, int unvisited, bst_ulong* leaves_refit, void* stream);
+
 /* The whole of predict_OH_with_XGB's RUN section in one kernel
  * (OH_GridCompMod.F90:303-383): gathers the 27 MAPL fields in place (field f is
  * (im,jm,km) Fortran order, or (im,jm) when is2d[f] != 0; feature order of

@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "OHXBoosterPredictInteractions", "OHXBoosterPredictInteractionsDevice",
     "OHXBoosterPredictContribsFields", "OHXBoosterPredictContribsFieldsDevice",
     "OHXBoosterCountVisits", "OHXBoosterCountVisitsDevice", "OHXBoosterGetVisitCounts", "OHXBoosterResetVisitCounts",
-    "OHXBoosterRefreshCover",
+    "OHXBoosterRefreshCover", "OHXBoosterRefitLeaves", "OHXBoosterRefitLeavesDevice",
     "OHXSelectCells", "OHXSelectCellsDevice", "OHXGatherCells", "OHXGatherCellsDevice",
     "OHXScatterCells", "OHXScatterCellsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
@@ -135,6 +135,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                                              C.POINTER(u64)]
     lib.OHXBoosterResetVisitCounts.argtypes = [vp]
     lib.OHXBoosterRefreshCover.argtypes = [vp, vp, f32]
+    lib.OHXBoosterRefitLeaves.argtypes = [vp, vp, vp, u64, f32, f32, i32, C.POINTER(u64)]
+    lib.OHXBoosterRefitLeavesDevice.argtypes = [vp, vp, vp, u64, f32, f32, i32, C.POINTER(u64), vp]
     lib.OHXBoosterPredictFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32,
                                             f32, i32, f32, vp, vp]
     i64 = C.c_int64
@@ -422,6 +424,30 @@ class Booster:
         """OHXBoosterRefreshCover: sum_hess := float32(count) + prior_weight * sum_hess for every reachable node, all or
         nothing; contributions computed afterwards are weighted by the counted data's covers."""
         check(self.lib, self.lib.OHXBoosterRefreshCover(self.handle, stream or None, prior_weight))
+
+    REFIT_UNVISITED = {"keep": 0, "zero": 1}
+
+    def refit_leaves(self, dmat: DMatrix, labels, eta: float = 1.0, reg_lambda: float = 1.0,
+                     unvisited: str = "keep") -> int:
+        """OHXBoosterRefitLeaves: every tree keeps its structure, every leaf value is estimated again from the rows of
+        `dmat` and `labels` (squared error: w = -G / (H + reg_lambda), leaf = w * eta, tree after tree).  A leaf no row
+        reaches keeps its value (unvisited="keep") or becomes 0 ("zero", as xgboost).  All or nothing; returns the
+        number of leaves that were refit."""
+        y = np.ascontiguousarray(labels, dtype=np.float32).reshape(-1)
+        n = C.c_uint64()
+        check(self.lib, self.lib.OHXBoosterRefitLeaves(self.handle, dmat.handle, y.ctypes.data, y.size, eta, reg_lambda,
+                                                        self.REFIT_UNVISITED[unvisited], C.byref(n)))
+        return int(n.value)
+
+    def refit_leaves_device(self, dmat: DMatrix, labels_ptr: int, nlabel: int, eta: float = 1.0,
+                            reg_lambda: float = 1.0, unvisited: str = "keep", stream: int = 0) -> int:
+        """The same with the labels in device memory (labels_ptr: a torch data_ptr() of nlabel float32, ready on
+        `stream`); enqueues on `stream` and waits for it once at the end (not capturable)."""
+        n = C.c_uint64()
+        check(self.lib, self.lib.OHXBoosterRefitLeavesDevice(self.handle, dmat.handle, labels_ptr, nlabel, eta,
+                                                              reg_lambda, self.REFIT_UNVISITED[unvisited], C.byref(n),
+                                                              stream or None))
+        return int(n.value)
 
     def predict_fields(self, fields: Sequence[np.ndarray], is2d: Sequence[bool], pl_feature: int, im: int, jm: int,
                        km: int, k1: int, k2: int, missing: float, oh_ml: np.ndarray, *, apply_pow10: bool = True,

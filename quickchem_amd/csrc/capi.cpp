@@ -33,6 +33,7 @@
 #include "groups.hpp"
 #include "kernels.hpp"
 #include "visits.hpp"
+#include "refit.hpp"
 
 using namespace ohx;
 
@@ -619,6 +620,25 @@ struct VisitState {
   uint64_t rows_seen = 0;
 };
 
+// Leaf refit (OHXBoosterRefitLeaves; refit.hpp): the walk's node format (emit_visits, a copy of the refit's own), the
+// leaf-id planes, the running prediction, the per-leaf sums, the leaf tables and the staged labels.  Built at the first
+// refit on the loaded model and never a buffer of the predict, fields, Run1, contributions or visit paths.  It holds no
+// leaf value between calls, so it outlives a refit; dropped with the model (adopt_model), with the booster and by an
+// "ohx_device" move.
+struct RefitState {
+  VisitForest vf;
+  int device = -1;
+  int num_cus = 0;
+  bool prepared = false;
+  DevBuf<VisitNode> d_nodes;
+  DevBuf<uint32_t> d_roots, d_leaf_offset, d_ids, d_error;
+  DevBuf<float> d_pred, d_leaf, d_weight, d_labels;
+  DevBuf<unsigned long long> d_G, d_H;
+  PinnedBuf<float> h_leaf, h_weight;      // the old tables on the way in, the new ones on the way back
+  PinnedBuf<unsigned long long> h_H;
+  PinnedBuf<uint32_t> h_error;
+};
+
 struct BoosterObj {
   ~BoosterObj() {
     for (hipEvent_t e : {run1_fork, run1_slab, run1_join, run1_clear})
@@ -758,6 +778,7 @@ struct BoosterObj {
   bool visits_use_lds = false;          // "ohx_visits_kernel" = lds: trees whose leaf histogram fits in LDS keep it there
                                         // (auto and global: every tree the global way - the faster at C360; same integers)
   uint32_t visits_lds_leaves = 0;       // "ohx_visits_lds_leaves": leaves a block's LDS histogram may hold (0 = what fits)
+  std::unique_ptr<RefitState> refit;
 };
 
 DMatrixObj* as_dmat(DMatrixHandle h) {
@@ -1064,6 +1085,7 @@ void adopt_model(BoosterObj& b, Forest&& f) {
   invalidate_device_state(b);
   b.contribs.reset();
   b.visits.reset();
+  b.refit.reset();
   b.forest = std::move(f);
   b.num_groups = b.forest.num_groups();
   b.num_cat = b.forest.num_categorical_splits();
@@ -1885,8 +1907,8 @@ void visits_on_device(BoosterObj& b, VisitState& v) {
     v.d_roots.upload(v.vf.roots);
     v.d_leaf_offset.upload(v.vf.leaf_offset);
     const size_t leaves = v.vf.leaf_offset.back();
-    v.d_counts.ensure(leaves);
-    v.h_leaf.ensure(leaves);
+    v.d_counts.ensure(std::max<size_t>(leaves, 1));      // (a forest without trees: the memset below writes one word)
+    v.h_leaf.ensure(std::max<size_t>(leaves, 1));
     HIP_CHECK(hipMemsetAsync(v.d_counts.p, 0, std::max<size_t>(leaves, 1) * sizeof(unsigned long long), exec));
     HIP_CHECK(hipStreamSynchronize(exec));
     v.rows_seen = 0;
@@ -1956,6 +1978,143 @@ void read_visit_counts(BoosterObj& b, VisitState& v, hipStream_t stream) {
   HIP_CHECK(hipStreamSynchronize(stream));
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are uint64");
   visit_node_sums(b.forest, v.vf, reinterpret_cast<const uint64_t*>(v.h_leaf.p), v.node_counts.data());
+}
+
+// ---- leaf refit (refit.hpp) ----
+
+// Both forms of OHXBoosterRefitLeaves.  The refusals that need neither a matrix nor a device come first, in the
+// header's order; nothing is enqueued before the last of them.
+void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulong nlabel, float eta, float lambda,
+                  int unvisited, bst_ulong* leaves_refit, bool host_form, hipStream_t caller, const char* what) {
+  if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
+  refuse_categorical(b, what);
+  refuse_groups(b, what);
+  if (!objective_is_identity(b.forest.objective))
+    throw OhxError(std::string(what) + " refits squared-error leaves (gradient pred - label, hessian 1): the objective " +
+                   b.forest.objective + " is not reg:squarederror");
+  if (labels == nullptr) throw OhxError(std::string(what) + ": labels is NULL");
+  if (!std::isfinite(eta)) throw OhxError(std::string(what) + ": eta must be finite");
+  if (!(std::isfinite(lambda) && lambda >= 0.0f)) throw OhxError(std::string(what) + ": lambda must be finite and >= 0");
+  if (unvisited != 0 && unvisited != 1) throw OhxError(std::string(what) + ": unvisited must be 0 (keep) or 1 (zero)");
+  DMatrixObj& d = *as_dmat(dmat);
+  if (d.nrow == 0) throw OhxError(std::string(what) + ": the matrix has no rows");
+  if (nlabel != d.nrow)
+    throw OhxError(std::string(what) + ": " + std::to_string(nlabel) + " labels for " + std::to_string(d.nrow) + " rows");
+  if (d.nrow > kRefitMaxRows)
+    throw OhxError(std::string(what) + ": at most 2^31 rows per refit (" + std::to_string(d.nrow) + " given)");
+  check_columns(b, d.ncol);
+  // before anything is built or enqueued: building the state waits for the library's stream
+  if (!host_form && stream_capturing(caller))
+    refuse_in_capture("refit leaf values", (std::string(what) + " is not capturable; call it outside the capture").c_str());
+  const DeviceInfo dev = use_device(b.uploaded ? b.dev.ordinal : b.device_pref);   // throws where there is no device
+  if (d.device >= 0 && d.device != dev.ordinal)
+    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
+                   std::to_string(dev.ordinal));
+  if (!b.refit) {
+    auto r = std::make_unique<RefitState>();
+    r->vf = emit_visits(b.forest, place_forest(b.forest, b.layout));
+    b.refit = std::move(r);
+  }
+  RefitState& r = *b.refit;
+  const size_t T = b.forest.trees.size();
+  const size_t leaves = r.vf.leaf_offset.back();
+  const RefitPlan plan = plan_refit(d.nrow, b.forest.num_feature, T, dev.num_cus);
+  if (r.device != dev.ordinal) {
+    r.d_nodes.upload(r.vf.nodes);
+    r.d_roots.upload(r.vf.roots);
+    r.d_leaf_offset.upload(r.vf.leaf_offset);
+    // (a forest without trees has no leaf: one word each, so that the memsets below have somewhere to go)
+    const size_t room = std::max<size_t>(leaves, 1);
+    r.d_G.ensure(room);
+    r.d_H.ensure(room);
+    r.d_leaf.ensure(room);
+    r.d_weight.ensure(room);
+    r.d_error.ensure(1);
+    r.h_leaf.ensure(room);
+    r.h_weight.ensure(room);
+    r.h_H.ensure(room);
+    r.h_error.ensure(1);
+    r.device = dev.ordinal;
+    r.num_cus = dev.num_cus;
+    r.prepared = false;
+  }
+  if (!r.prepared) {
+    HIP_CHECK((hipError_t)prepare_refit(plan));
+    r.prepared = true;
+  }
+  try {
+    r.d_ids.ensure((size_t)T * d.nrow);
+  } catch (const OhxError& e) {
+    throw OhxError(std::string(what) + ": the leaf-id buffer of " + std::to_string(T) + " trees x " + std::to_string(d.nrow) +
+                   " rows x 4 = " + std::to_string(plan.ids_bytes) + " bytes cannot be allocated (" + e.what() + ")");
+  }
+  r.d_pred.ensure(d.nrow);
+  if (host_form) r.d_labels.ensure(d.nrow);
+  hipStream_t stream = host_form ? lib_streams(dev.ordinal).exec : caller;
+  if (host_form && d.owned == nullptr) order_behind_caller(dev.ordinal, stream);
+  // every earlier refit has been waited for, so the buffers are free; the old leaf tables go in, for the leaves no row
+  // reaches
+  refit_gather_leaves(b.forest, r.vf, r.h_leaf.p, r.h_weight.p);
+  const size_t nl = std::max<size_t>(leaves, 1);
+  HIP_CHECK(hipMemsetAsync(r.d_G.p, 0, nl * sizeof(unsigned long long), stream));
+  HIP_CHECK(hipMemsetAsync(r.d_H.p, 0, nl * sizeof(unsigned long long), stream));
+  HIP_CHECK(hipMemsetAsync(r.d_error.p, 0, sizeof(uint32_t), stream));
+  if (leaves) {
+    HIP_CHECK(hipMemcpyAsync(r.d_leaf.p, r.h_leaf.p, leaves * sizeof(float), hipMemcpyHostToDevice, stream));
+    HIP_CHECK(hipMemcpyAsync(r.d_weight.p, r.h_weight.p, leaves * sizeof(float), hipMemcpyHostToDevice, stream));
+  }
+  if (host_form) HIP_CHECK(hipMemcpyAsync(r.d_labels.p, labels, d.nrow * sizeof(float), hipMemcpyHostToDevice, stream));
+  RefitArgs a;
+  a.nodes = r.d_nodes.p;
+  a.node_bytes = (uint32_t)(r.vf.nodes.size() * sizeof(VisitNode));
+  a.roots = r.d_roots.p;
+  a.leaf_offset = r.d_leaf_offset.p;
+  a.num_trees = (uint32_t)T;
+  a.num_feature = b.forest.num_feature;
+  a.total_leaves = (uint32_t)leaves;
+  a.rows = d.d_data;
+  a.nrow = d.nrow;
+  a.ncol = (uint32_t)d.ncol;
+  a.missing = d.missing;
+  a.labels = host_form ? r.d_labels.p : labels;
+  a.ids = r.d_ids.p;
+  a.pred = r.d_pred.p;
+  a.G = r.d_G.p;
+  a.H = r.d_H.p;
+  a.leaf = r.d_leaf.p;
+  a.weight = r.d_weight.p;
+  a.error = r.d_error.p;
+  a.base = b.margin_base;
+  a.eta = eta;
+  a.lambda = lambda;
+  a.unvisited = unvisited;
+  hipError_t launched = (hipError_t)launch_refit(a, plan, r.vf.leaf_offset.data(), stream);
+  if (launched == hipSuccess && leaves) {
+    launched = hipMemcpyAsync(r.h_leaf.p, r.d_leaf.p, leaves * sizeof(float), hipMemcpyDeviceToHost, stream);
+    if (launched == hipSuccess) launched = hipMemcpyAsync(r.h_weight.p, r.d_weight.p, leaves * sizeof(float), hipMemcpyDeviceToHost, stream);
+    if (launched == hipSuccess) launched = hipMemcpyAsync(r.h_H.p, r.d_H.p, leaves * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
+  }
+  if (launched == hipSuccess) launched = hipMemcpyAsync(r.h_error.p, r.d_error.p, sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+  // both forms wait, whatever was enqueued: the labels and the tables are read from the caller's and the state's memory
+  const hipError_t waited = hipStreamSynchronize(stream);
+  if (!host_form) d.used_async = true;
+  HIP_CHECK(launched);
+  HIP_CHECK(waited);
+  const uint32_t flags = r.h_error.p[0];
+  if (flags & kRefitFlagLabel)
+    throw OhxError(std::string(what) + ": a gradient pred - label is not finite or reaches 256 in size at some row and tree: "
+                   "look for a label that is NaN, infinite or far from the model's range; the forest is unchanged");
+  if (flags != 0) throw OhxError(std::string(what) + ": the refit kernels reported error flags " + std::to_string(flags));
+  // all or nothing: every tree is done and the error word is clean
+  refit_write_back(b.forest, r.vf, r.h_leaf.p, r.h_weight.p);
+  // everything built from leaf values is dropped as a model load drops it; the visit state holds none
+  invalidate_device_state(b);
+  b.contribs.reset();
+  if (leaves_refit != nullptr) {
+    bst_ulong n = 0;
+    for (size_t l = 0; l < leaves; ++l) n += r.h_H.p[l] != 0ull ? 1u : 0u;
+    *leaves_refit = n;
+  }
 }
 
 }  // namespace
@@ -2362,6 +2521,7 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
     if (k != b->device_pref) {
       invalidate_device_state(*b);
       b->visits.reset();               // the visit counts live on the device they were counted on
+      b->refit.reset();
     }
     b->device_pref = k;
   }
@@ -2538,6 +2698,23 @@ int OHXBoosterRefreshCover(BoosterHandle handle, void* stream, float prior_weigh
   for (size_t t = 0; t < covers.size(); ++t) b->forest.trees[t].sum_hess = std::move(covers[t]);
   // the contributions' tables hold the old covers: dropped exactly as a model load drops them, rebuilt at the next call
   b->contribs.reset();
+  API_END();
+}
+
+int OHXBoosterRefitLeaves(BoosterHandle handle, DMatrixHandle dmat, const float* labels, bst_ulong nlabel, float eta,
+                          float lambda, int unvisited, bst_ulong* leaves_refit) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  refit_leaves(*b, dmat, labels, nlabel, eta, lambda, unvisited, leaves_refit, true, nullptr, "OHXBoosterRefitLeaves");
+  API_END();
+}
+
+int OHXBoosterRefitLeavesDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels, bst_ulong nlabel,
+                                float eta, float lambda, int unvisited, bst_ulong* leaves_refit, void* stream) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  refit_leaves(*b, dmat, d_labels, nlabel, eta, lambda, unvisited, leaves_refit, false, static_cast<hipStream_t>(stream),
+               "OHXBoosterRefitLeavesDevice");
   API_END();
 }
 

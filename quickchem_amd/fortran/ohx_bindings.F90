@@ -320,6 +320,32 @@ module ohx_bindings
          integer(c_int)       :: rc
       end function
 
+      !  Leaf refit (include/ohxgb.h; docs/17_leaf_refit.md).  Interface blocks only: nothing the oracle-linked drivers
+      !  link calls them.  labels: nlabel real(c_float) on the host; d_labels: their DEVICE address (c_ptr).
+      !  leaves_refit: c_loc of an integer(c_int64_t), or c_null_ptr - the header allows NULL
+      function OHXBoosterRefitLeaves(handle, dmat, labels, nlabel, eta, lambda, unvisited, leaves_refit) &
+            bind(C, name="OHXBoosterRefitLeaves") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat
+         real(c_float), intent(in)       :: labels(*)
+         integer(c_int64_t), value       :: nlabel
+         real(c_float), value            :: eta, lambda
+         integer(c_int), value           :: unvisited
+         type(c_ptr), value              :: leaves_refit
+         integer(c_int)                  :: rc
+      end function
+
+      function OHXBoosterRefitLeavesDevice(handle, dmat, d_labels, nlabel, eta, lambda, unvisited, leaves_refit, stream) &
+            bind(C, name="OHXBoosterRefitLeavesDevice") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat, d_labels, stream
+         integer(c_int64_t), value       :: nlabel
+         real(c_float), value            :: eta, lambda
+         integer(c_int), value           :: unvisited
+         type(c_ptr), value              :: leaves_refit
+         integer(c_int)                  :: rc
+      end function
+
       ! ---- part 4 of ohxgb.h: the OH field reassembled on every GPU of a node, for a host that has MPI but no
       !      torch.distributed.  Rank 0 gets the id, MPI_Bcast carries its OHX_UNIQUE_ID_BYTES bytes, every rank
       !      (hipSetDevice done) inits; d_shard / d_full are DEVICE addresses, stream a hipStream_t (c_null_ptr = default)

@@ -87,6 +87,11 @@ def _load():
         lib.ohx_visits_refresh.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p]
         lib.ohx_visits_plan.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32, C.c_int, C.c_int, C.c_uint64, C.c_void_p,
                                         C.POINTER(C.c_uint64)]
+        lib.ohx_refit_solve.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_float, C.c_int, C.c_void_p,
+                                        C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.ohx_refit_write_back.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        lib.ohx_refit_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
         _lib = lib
     return _lib
 
@@ -357,6 +362,47 @@ def visits_plan(image, lds_leaves: int = 0, force_global: bool = False, num_cus:
     return {"takes_lds": takes[:T].astype(bool), "stage": bool(info[0]), "hist_leaves": int(info[1]),
             "lds_bytes_lds": int(info[2]), "lds_bytes_global": int(info[3]), "capacity": int(info[4]),
             "lds_blocks": int(info[5]), "global_blocks": int(info[6]), "lds_trees": int(info[7])}
+
+
+def refit_solve(G, H, eta: float, reg_lambda: float, unvisited: int, value, base_weight):
+    """csrc/refit.cpp refit_solve on injected sums: G int64 and H uint64 per leaf, the old leaf tables ->
+    (value, base_weight, leaves with H > 0) as OHXBoosterRefitLeaves would store them."""
+    G = np.ascontiguousarray(G, dtype=np.int64)
+    H = np.ascontiguousarray(H, dtype=np.uint64)
+    v = np.array(value, dtype=np.float32)
+    w = np.array(base_weight, dtype=np.float32)
+    assert G.shape == H.shape == v.shape == w.shape and G.ndim == 1
+    n = C.c_uint64()
+    _check(_load().ohx_refit_solve(G.ctypes.data, H.ctypes.data, G.size, eta, reg_lambda, unvisited, v.ctypes.data,
+                                   w.ctypes.data, C.byref(n)))
+    return v, w, int(n.value)
+
+
+def refit_write_back(image, value, base_weight):
+    """csrc/refit.cpp refit_gather_leaves and refit_write_back on a booster: leaf tables in the dense numbering of
+    visits_layout -> (old value table, old base_weight table, node values, node base_weights): the forest's arrays tree
+    after tree in file numbering once the tables are written back."""
+    img = _image(image)
+    offs, loff, _ = visits_layout(img)
+    value = np.ascontiguousarray(value, dtype=np.float32)
+    base_weight = np.ascontiguousarray(base_weight, dtype=np.float32)
+    nleaf, nnode = int(loff[-1]), int(offs[-1])
+    assert value.size == nleaf and base_weight.size == nleaf
+    ov, ob = np.zeros(max(nleaf, 1), dtype=np.float32), np.zeros(max(nleaf, 1), dtype=np.float32)
+    nv, nb = np.zeros(max(nnode, 1), dtype=np.float32), np.zeros(max(nnode, 1), dtype=np.float32)
+    _check(_load().ohx_refit_write_back(img.ctypes.data, img.nbytes, value.ctypes.data, base_weight.ctypes.data, nleaf,
+                                        ov.ctypes.data, ob.ctypes.data, nv.ctypes.data, nb.ctypes.data, nnode))
+    return ov[:nleaf], ob[:nleaf], nv[:nnode], nb[:nnode]
+
+
+def refit_plan(nrow: int, num_feature: int = NFEAT, ntree: int = 1, num_cus: int = 256):
+    """csrc/refit.hpp plan_refit -> dict: stage, lds_bytes, ids_blocks, accum_blocks, ids_bytes, block_rows (rows a
+    block takes per trip of either kernel's loop), and the two kernels' block caps per CU."""
+    info = (C.c_uint64 * 8)()
+    _check(_load().ohx_refit_plan(nrow, num_feature, ntree, num_cus, info))
+    return {"stage": bool(info[0]), "lds_bytes": int(info[1]), "ids_blocks": int(info[2]), "accum_blocks": int(info[3]),
+            "ids_bytes": int(info[4]), "block_rows": int(info[5]), "ids_blocks_per_cu": int(info[6]),
+            "accum_blocks_per_cu": int(info[7])}
 
 
 def cells_plan(n: int, nfield: int = 27):
