@@ -600,38 +600,43 @@ struct ContribsState {
   }
 };
 
-// Node visit counts (OHXBoosterCountVisits; visits.hpp): the walk's own node format, the leaf counters and the buffers
-// the results come back in.  Built at the first visits call on the loaded model - the host part (no device needed) by any
-// of the five calls, the device part by the first count - and never sharing a buffer with the predict, fields, Run1 or
-// contributions paths.  Dropped with the model (adopt_model), with the booster and by an "ohx_device" move;
-// OHXReleaseScratch leaves it alone.
-struct VisitState {
+// The forest as the walk to dense leaf indices reads it (visits.hpp VisitForest, DeviceLeafWalk): ONE per booster, read by
+// the visit counts and by the leaf refit.  The host part is built by the first call of either on the loaded model and
+// needs no device; the device part by the first count or refit.  Never a buffer of the predict, fields, Run1 or
+// contributions paths, and read-only to every kernel: a device-form count still in flight and a later refit on the same
+// device may read it together.  It holds no leaf value, so it outlives a refit; dropped - with the two states below -
+// with the model (adopt_model), with the booster and by an "ohx_device" move; OHXReleaseScratch leaves all three alone.
+// A booster without a device of its own follows the caller's current device: the walk is then freed and built again
+// where it is asked for (hipFree waits for what still reads it), and each state below does the same with its own
+// buffers when it next finds the walk elsewhere (`device`) - until then a count made on the old device stays readable.
+struct LeafWalkState {
   VisitForest vf;                     // nodes, roots, leaf maps (host)
-  VisitPlan plan;                     // which trees take the LDS path, for the knobs below
-  uint32_t plan_lds_leaves = 0;
-  bool plan_use_lds = false, plan_uploaded = false;
   int device = -1;                    // where the device part lives; -1 = not built yet
   int num_cus = 0;
   DevBuf<VisitNode> d_nodes;
-  DevBuf<uint32_t> d_roots, d_leaf_offset, d_lds_trees, d_global_trees;
+  DevBuf<uint32_t> d_roots, d_leaf_offset;
+};
+
+// Node visit counts (OHXBoosterCountVisits): the plan's tree lists, the leaf counters and the buffers the results come
+// back in.
+struct VisitState {
+  VisitPlan plan;                     // which trees take the LDS path, for the knobs below
+  uint32_t plan_lds_leaves = 0;
+  bool plan_use_lds = false, plan_uploaded = false;
+  int device = -1;                    // the walk's device when the counters were made; -1 = not built yet
+  DevBuf<uint32_t> d_lds_trees, d_global_trees;
   DevBuf<unsigned long long> d_counts;
   PinnedBuf<unsigned long long> h_leaf;
   std::vector<uint64_t> node_counts;  // what OHXBoosterGetVisitCounts hands out
   uint64_t rows_seen = 0;
 };
 
-// Leaf refit (OHXBoosterRefitLeaves; refit.hpp): the walk's node format (emit_visits, a copy of the refit's own), the
-// leaf-id planes, the running prediction, the per-leaf sums, the leaf tables and the staged labels.  Built at the first
-// refit on the loaded model and never a buffer of the predict, fields, Run1, contributions or visit paths.  It holds no
-// leaf value between calls, so it outlives a refit; dropped with the model (adopt_model), with the booster and by an
-// "ohx_device" move.
+// Leaf refit (OHXBoosterRefitLeaves; refit.hpp): the leaf-id planes, the running prediction, the per-leaf sums, the leaf
+// tables and the staged labels.  Built at the first refit on the loaded model.
 struct RefitState {
-  VisitForest vf;
-  int device = -1;
-  int num_cus = 0;
+  int device = -1;                    // as VisitState's
   bool prepared = false;
-  DevBuf<VisitNode> d_nodes;
-  DevBuf<uint32_t> d_roots, d_leaf_offset, d_ids, d_error;
+  DevBuf<uint32_t> d_ids, d_error;
   DevBuf<float> d_pred, d_leaf, d_weight, d_labels;
   DevBuf<unsigned long long> d_G, d_H;
   PinnedBuf<float> h_leaf, h_weight;      // the old tables on the way in, the new ones on the way back
@@ -774,6 +779,7 @@ struct BoosterObj {
   bool cat_force_direct = false;        // "ohx_cat_kernel" = direct: margins by the direct kernel too (same bits)
   std::unique_ptr<ContribsState> contribs;
   bool contribs_split = true;           // "ohx_contribs_split": small batches may have their trees split over waves
+  std::unique_ptr<LeafWalkState> leaf_walk;   // shared by the two below; dropped only together with them
   std::unique_ptr<VisitState> visits;
   bool visits_use_lds = false;          // "ohx_visits_kernel" = lds: trees whose leaf histogram fits in LDS keep it there
                                         // (auto and global: every tree the global way - the faster at C360; same integers)
@@ -781,9 +787,23 @@ struct BoosterObj {
   std::unique_ptr<RefitState> refit;
 };
 
+// the leaf walk with both states that refer to it
+void drop_leaf_walk(BoosterObj& b) {
+  b.visits.reset();
+  b.refit.reset();
+  b.leaf_walk.reset();
+}
+
 DMatrixObj* as_dmat(DMatrixHandle h) {
   if (h == nullptr || !g_dmats.has(h)) throw OhxError("DMatrix handle is invalid or has been freed");
   return static_cast<DMatrixObj*>(h);
+}
+
+// a matrix that names its device is walked by a booster on that device only
+void check_same_device(const DMatrixObj& d, int ordinal) {
+  if (d.device >= 0 && d.device != ordinal)
+    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
+                   std::to_string(ordinal));
 }
 
 BoosterObj* as_booster(BoosterHandle h) {
@@ -1084,8 +1104,7 @@ void adopt_model(BoosterObj& b, Forest&& f) {
   for (const std::string& w : f.warnings) fprintf(stderr, "[libohxgb] warning: model file: %s\n", w.c_str());
   invalidate_device_state(b);
   b.contribs.reset();
-  b.visits.reset();
-  b.refit.reset();
+  drop_leaf_walk(b);
   b.forest = std::move(f);
   b.num_groups = b.forest.num_groups();
   b.num_cat = b.forest.num_categorical_splits();
@@ -1392,6 +1411,13 @@ LaunchTuning tune_for(const BoosterObj& b, const DMatrixObj& d) {
 void launch_predict_groups(BoosterObj& b, DMatrixObj& d, int option_mask, unsigned ntree_limit, float* d_out,
                            hipStream_t stream);
 
+// behind a walk that reads cluster_rows' permutation: what the next clustering pass on this booster waits for
+void mark_cluster_in_flight(BoosterObj& b, hipStream_t stream) {
+  if (b.cluster_done == nullptr) HIP_CHECK(hipEventCreateWithFlags(&b.cluster_done, hipEventDisableTiming));
+  HIP_CHECK(hipEventRecord(b.cluster_done, stream));
+  b.cluster_in_flight = true;
+}
+
 void launch_predict_checked(BoosterObj& b, DMatrixObj& d, int option_mask, unsigned ntree_limit, float* d_out,
                             hipStream_t stream) {
   if (b.loaded && b.num_groups >= 2) return launch_predict_groups(b, d, option_mask, ntree_limit, d_out, stream);
@@ -1402,9 +1428,7 @@ void launch_predict_checked(BoosterObj& b, DMatrixObj& d, int option_mask, unsig
     refuse_in_capture("predict a booster with categorical splits",
                       "its kernels are not among what a capture may hold yet; call it outside the capture");
   ensure_uploaded(b);
-  if (d.device >= 0 && d.device != b.dev.ordinal)
-    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
-                   std::to_string(b.dev.ordinal));
+  check_same_device(d, b.dev.ordinal);
   if (b.num_cat != 0) {
     // the kernels of categorical.hip; of the launch knobs only the rows' grid and the brick shape apply (ohx_kernel, tree
     // split, deferred rows, the clustering pass and the level-size search do not)
@@ -1445,11 +1469,7 @@ void launch_predict_checked(BoosterObj& b, DMatrixObj& d, int option_mask, unsig
                     own_order && d.ncol == 27, stream, [&](const LaunchTuning& tune) {
                       return launch_predict(kind, device_forest(b), a, b.dev.num_cus, stream, tune);
                     });
-  if (a.perm != nullptr) {
-    if (b.cluster_done == nullptr) HIP_CHECK(hipEventCreateWithFlags(&b.cluster_done, hipEventDisableTiming));
-    HIP_CHECK(hipEventRecord(b.cluster_done, stream));
-    b.cluster_in_flight = true;
-  }
+  if (a.perm != nullptr) mark_cluster_in_flight(b, stream);
 }
 
 // A booster of several output groups (docs/13_output_groups.md): each group's tree range is walked by the kernel the
@@ -1468,9 +1488,7 @@ void launch_predict_groups(BoosterObj& b, DMatrixObj& d, int option_mask, unsign
     refuse_in_capture("predict a booster of several output groups",
                       "its predict waits for the stream and fills the booster's own group planes; call it outside the capture");
   ensure_uploaded(b);
-  if (d.device >= 0 && d.device != b.dev.ordinal)
-    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
-                   std::to_string(b.dev.ordinal));
+  check_same_device(d, b.dev.ordinal);
   const uint32_t G = b.num_groups, T = (uint32_t)b.forest.trees.size();
   const uint32_t L = group_tree_limit(b, ntree_limit);
   const uint64_t n = d.nrow;
@@ -1520,11 +1538,7 @@ void launch_predict_groups(BoosterObj& b, DMatrixObj& d, int option_mask, unsign
     HIP_CHECK(launch_predict(kind, device_forest(b), a, b.dev.num_cus, stream, gt));
     if (deferring) defer_look(b, n, stream);
   }
-  if (a.perm != nullptr) {
-    if (b.cluster_done == nullptr) HIP_CHECK(hipEventCreateWithFlags(&b.cluster_done, hipEventDisableTiming));
-    HIP_CHECK(hipEventRecord(b.cluster_done, stream));
-    b.cluster_in_flight = true;
-  }
+  if (a.perm != nullptr) mark_cluster_in_flight(b, stream);
   HIP_CHECK(launch_group_finish(b.d_planes.p, n, G, finish, d_out, stream));
 }
 
@@ -1689,9 +1703,7 @@ ContribsState& explain_refusals(BoosterObj& b, const ExplainCall& q, FieldsContr
   ContribsState& c = contribs_tables(b, q.approximate != 0, q.interactions);
   if (fs != nullptr) return c;
   const DMatrixObj& d = *q.d;
-  if (d.device >= 0 && d.device != b.dev.ordinal)
-    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
-                   std::to_string(b.dev.ordinal));
+  check_same_device(d, b.dev.ordinal);
   if (q.interactions) {
     const uint64_t F1 = (uint64_t)b.forest.num_feature + 1, W = F1 * F1, G = b.num_groups;
     if (d.nrow > (uint64_t)(SIZE_MAX / sizeof(float)) / (W * G))
@@ -1879,47 +1891,81 @@ ExplainResult explain(BoosterObj& b, const ExplainCall& q) {
   return res;
 }
 
+// ---- the leaf walk the visit counts and the refit share ----
+
+// the host part, built at first use on the loaded model; no device needed
+LeafWalkState& leaf_walk_host(BoosterObj& b) {
+  if (!b.leaf_walk) {
+    auto w = std::make_unique<LeafWalkState>();
+    w->vf = emit_visits(b.forest, place_forest(b.forest, b.layout));
+    b.leaf_walk = std::move(w);
+  }
+  return *b.leaf_walk;
+}
+
+// The booster's device (where it has one already), without building any of the predict path's device forms; throws
+// where there is no usable HIP device.
+DeviceInfo leaf_walk_device(const BoosterObj& b) { return use_device(b.uploaded ? b.dev.ordinal : b.device_pref); }
+
+// Builds the walk on `dev` (leaf_walk_device); one left on another device is freed first, so that no buffer stays
+// behind there.  Waits for the library's stream: never called inside a capture.
+LeafWalkState& leaf_walk_on_device(BoosterObj& b, const DeviceInfo& dev) {
+  LeafWalkState& w = leaf_walk_host(b);
+  if (w.device != dev.ordinal) {
+    w.d_nodes.release();
+    w.d_roots.release();
+    w.d_leaf_offset.release();
+    w.d_nodes.upload(w.vf.nodes);
+    w.d_roots.upload(w.vf.roots);
+    w.d_leaf_offset.upload(w.vf.leaf_offset);
+    w.device = dev.ordinal;
+    w.num_cus = dev.num_cus;
+  }
+  return w;
+}
+
+DeviceLeafWalk device_leaf_walk(const BoosterObj& b, const LeafWalkState& w) {
+  // nodes, node_bytes, roots, leaf_offset, num_trees, num_feature, total_leaves
+  return {w.d_nodes.p, (uint32_t)(w.vf.nodes.size() * sizeof(VisitNode)), w.d_roots.p, w.d_leaf_offset.p,
+          (uint32_t)b.forest.trees.size(), b.forest.num_feature, w.vf.leaf_offset.back()};
+}
+
 // ---- node visit counts (visits.hpp) ----
 
-// What every one of the five calls refuses first, then the state's host part (built at first use; no device needed)
+// What every one of the five calls refuses first, then the host parts (built at first use; no device needed)
 VisitState& visits_begin(BoosterObj& b, const char* what) {
   if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
   refuse_categorical(b, what);
   refuse_groups(b, what);
+  const LeafWalkState& w = leaf_walk_host(b);
   if (!b.visits) {
-    auto v = std::make_unique<VisitState>();
-    v->vf = emit_visits(b.forest, place_forest(b.forest, b.layout));
-    v->node_counts.assign((size_t)v->vf.tree_offsets.back(), 0);
-    b.visits = std::move(v);
+    b.visits = std::make_unique<VisitState>();
+    b.visits->node_counts.assign((size_t)w.vf.tree_offsets.back(), 0);
   }
   return *b.visits;
 }
 
 // The device part, and the plan's tree lists for the knobs as they stand.  Waits for the library's stream: never called
 // inside a capture.
-void visits_on_device(BoosterObj& b, VisitState& v) {
-  // the booster's device (where it has one already), without building any of the predict path's device forms; throws
-  // where there is no usable HIP device
-  const DeviceInfo dev = use_device(b.uploaded ? b.dev.ordinal : b.device_pref);
-  hipStream_t exec = lib_streams(dev.ordinal).exec;
-  if (v.device != dev.ordinal) {
-    v.d_nodes.upload(v.vf.nodes);
-    v.d_roots.upload(v.vf.roots);
-    v.d_leaf_offset.upload(v.vf.leaf_offset);
-    const size_t leaves = v.vf.leaf_offset.back();
+LeafWalkState& visits_on_device(BoosterObj& b, VisitState& v) {
+  LeafWalkState& w = leaf_walk_on_device(b, leaf_walk_device(b));
+  if (v.device != w.device) {
+    hipStream_t exec = lib_streams(w.device).exec;
+    const size_t leaves = w.vf.leaf_offset.back();
+    v.d_counts.release();                                // (counters left on another device go with it)
+    for (DevBuf<uint32_t>* buf : {&v.d_lds_trees, &v.d_global_trees}) buf->release();
     v.d_counts.ensure(std::max<size_t>(leaves, 1));      // (a forest without trees: the memset below writes one word)
     v.h_leaf.ensure(std::max<size_t>(leaves, 1));
     HIP_CHECK(hipMemsetAsync(v.d_counts.p, 0, std::max<size_t>(leaves, 1) * sizeof(unsigned long long), exec));
     HIP_CHECK(hipStreamSynchronize(exec));
     v.rows_seen = 0;
     v.plan_uploaded = false;
-    v.device = dev.ordinal;
-    v.num_cus = dev.num_cus;
+    v.device = w.device;
   }
   if (!v.plan_uploaded || v.plan_lds_leaves != b.visits_lds_leaves || v.plan_use_lds != b.visits_use_lds) {
     // (a count enqueued earlier may still read the lists: the upload below waits for the library's stream only)
     if (v.plan_uploaded) HIP_CHECK(hipDeviceSynchronize());
-    v.plan = plan_visits(v.vf, b.forest.num_feature, b.visits_lds_leaves, /*force_global=*/!b.visits_use_lds);
+    v.plan = plan_visits(w.vf, b.forest.num_feature, b.visits_lds_leaves, /*force_global=*/!b.visits_use_lds);
     v.d_lds_trees.upload(v.plan.lds_trees);
     v.d_global_trees.upload(v.plan.global_trees);
     HIP_CHECK((hipError_t)prepare_count_visits(v.plan));      // once per plan: the kernels' dynamic LDS limits
@@ -1927,6 +1973,7 @@ void visits_on_device(BoosterObj& b, VisitState& v) {
     v.plan_use_lds = b.visits_use_lds;
     v.plan_uploaded = true;
   }
+  return w;
 }
 
 // The booster's refusals come before the matrix handle is looked at.
@@ -1937,29 +1984,21 @@ void count_visits(BoosterObj& b, DMatrixHandle dmat, bool host_form, hipStream_t
   // before the device part is built: building it waits for the library's stream
   if (!host_form && stream_capturing(caller))
     refuse_in_capture("count node visits", (std::string(what) + " is not capturable; call it outside the capture").c_str());
-  visits_on_device(b, v);
-  if (d.device >= 0 && d.device != v.device)
-    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
-                   std::to_string(v.device));
-  hipStream_t stream = host_form ? lib_streams(v.device).exec : caller;
-  if (host_form && d.owned == nullptr) order_behind_caller(v.device, stream);
+  const LeafWalkState& w = visits_on_device(b, v);
+  check_same_device(d, w.device);
+  hipStream_t stream = host_form ? lib_streams(w.device).exec : caller;
+  if (host_form && d.owned == nullptr) order_behind_caller(w.device, stream);
   DeviceVisitForest fr;
-  fr.nodes = v.d_nodes.p;
-  fr.node_bytes = (uint32_t)(v.vf.nodes.size() * sizeof(VisitNode));
-  fr.roots = v.d_roots.p;
-  fr.leaf_offset = v.d_leaf_offset.p;
+  fr.walk = device_leaf_walk(b, w);
   fr.lds_trees = v.d_lds_trees.p;
   fr.global_trees = v.d_global_trees.p;
-  fr.num_trees = (uint32_t)b.forest.trees.size();
-  fr.num_feature = b.forest.num_feature;
-  fr.total_leaves = v.vf.leaf_offset.back();
   VisitArgs a;
   a.rows = d.d_data;
   a.nrow = d.nrow;
   a.ncol = (uint32_t)d.ncol;
   a.missing = d.missing;
   a.counts = v.d_counts.p;
-  HIP_CHECK((hipError_t)launch_count_visits(fr, a, v.plan, v.num_cus, tune_for(b, d), stream));
+  HIP_CHECK((hipError_t)launch_count_visits(fr, a, v.plan, w.num_cus, tune_for(b, d), stream));
   v.rows_seen += d.nrow;
   if (host_form) HIP_CHECK(hipStreamSynchronize(stream));
   else d.used_async = true;
@@ -1968,7 +2007,8 @@ void count_visits(BoosterObj& b, DMatrixHandle dmat, bool host_form, hipStream_t
 // Waits for `stream`, brings the leaf counters back and sums them up each tree (v.node_counts).  A state that has never
 // counted has no device part: all zeros.
 void read_visit_counts(BoosterObj& b, VisitState& v, hipStream_t stream) {
-  const size_t leaves = v.vf.leaf_offset.back();
+  const LeafWalkState& w = leaf_walk_host(b);
+  const size_t leaves = w.vf.leaf_offset.back();
   if (v.device < 0) {
     std::fill(v.node_counts.begin(), v.node_counts.end(), 0);
     return;
@@ -1977,7 +2017,7 @@ void read_visit_counts(BoosterObj& b, VisitState& v, hipStream_t stream) {
   if (leaves) HIP_CHECK(hipMemcpyAsync(v.h_leaf.p, v.d_counts.p, leaves * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream));
   HIP_CHECK(hipStreamSynchronize(stream));
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the counters are uint64");
-  visit_node_sums(b.forest, v.vf, reinterpret_cast<const uint64_t*>(v.h_leaf.p), v.node_counts.data());
+  visit_node_sums(b.forest, w.vf, reinterpret_cast<const uint64_t*>(v.h_leaf.p), v.node_counts.data());
 }
 
 // ---- leaf refit (refit.hpp) ----
@@ -2006,23 +2046,18 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
   // before anything is built or enqueued: building the state waits for the library's stream
   if (!host_form && stream_capturing(caller))
     refuse_in_capture("refit leaf values", (std::string(what) + " is not capturable; call it outside the capture").c_str());
-  const DeviceInfo dev = use_device(b.uploaded ? b.dev.ordinal : b.device_pref);   // throws where there is no device
-  if (d.device >= 0 && d.device != dev.ordinal)
-    throw OhxError("the DMatrix lives on HIP device " + std::to_string(d.device) + " but the booster on device " +
-                   std::to_string(dev.ordinal));
-  if (!b.refit) {
-    auto r = std::make_unique<RefitState>();
-    r->vf = emit_visits(b.forest, place_forest(b.forest, b.layout));
-    b.refit = std::move(r);
-  }
+  const DeviceInfo dev = leaf_walk_device(b);   // throws where there is no device
+  check_same_device(d, dev.ordinal);
+  if (!b.refit) b.refit = std::make_unique<RefitState>();
   RefitState& r = *b.refit;
+  const LeafWalkState& w = leaf_walk_on_device(b, dev);
   const size_t T = b.forest.trees.size();
-  const size_t leaves = r.vf.leaf_offset.back();
+  const size_t leaves = w.vf.leaf_offset.back();
   const RefitPlan plan = plan_refit(d.nrow, b.forest.num_feature, T, dev.num_cus);
-  if (r.device != dev.ordinal) {
-    r.d_nodes.upload(r.vf.nodes);
-    r.d_roots.upload(r.vf.roots);
-    r.d_leaf_offset.upload(r.vf.leaf_offset);
+  if (r.device != w.device) {
+    for (DevBuf<uint32_t>* buf : {&r.d_ids, &r.d_error}) buf->release();      // (what was left on another device)
+    for (DevBuf<float>* buf : {&r.d_pred, &r.d_leaf, &r.d_weight, &r.d_labels}) buf->release();
+    for (DevBuf<unsigned long long>* buf : {&r.d_G, &r.d_H}) buf->release();
     // (a forest without trees has no leaf: one word each, so that the memsets below have somewhere to go)
     const size_t room = std::max<size_t>(leaves, 1);
     r.d_G.ensure(room);
@@ -2034,8 +2069,7 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
     r.h_weight.ensure(room);
     r.h_H.ensure(room);
     r.h_error.ensure(1);
-    r.device = dev.ordinal;
-    r.num_cus = dev.num_cus;
+    r.device = w.device;
     r.prepared = false;
   }
   if (!r.prepared) {
@@ -2054,7 +2088,7 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
   if (host_form && d.owned == nullptr) order_behind_caller(dev.ordinal, stream);
   // every earlier refit has been waited for, so the buffers are free; the old leaf tables go in, for the leaves no row
   // reaches
-  refit_gather_leaves(b.forest, r.vf, r.h_leaf.p, r.h_weight.p);
+  refit_gather_leaves(b.forest, w.vf, r.h_leaf.p, r.h_weight.p);
   const size_t nl = std::max<size_t>(leaves, 1);
   HIP_CHECK(hipMemsetAsync(r.d_G.p, 0, nl * sizeof(unsigned long long), stream));
   HIP_CHECK(hipMemsetAsync(r.d_H.p, 0, nl * sizeof(unsigned long long), stream));
@@ -2065,13 +2099,7 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
   }
   if (host_form) HIP_CHECK(hipMemcpyAsync(r.d_labels.p, labels, d.nrow * sizeof(float), hipMemcpyHostToDevice, stream));
   RefitArgs a;
-  a.nodes = r.d_nodes.p;
-  a.node_bytes = (uint32_t)(r.vf.nodes.size() * sizeof(VisitNode));
-  a.roots = r.d_roots.p;
-  a.leaf_offset = r.d_leaf_offset.p;
-  a.num_trees = (uint32_t)T;
-  a.num_feature = b.forest.num_feature;
-  a.total_leaves = (uint32_t)leaves;
+  a.walk = device_leaf_walk(b, w);
   a.rows = d.d_data;
   a.nrow = d.nrow;
   a.ncol = (uint32_t)d.ncol;
@@ -2088,7 +2116,7 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
   a.eta = eta;
   a.lambda = lambda;
   a.unvisited = unvisited;
-  hipError_t launched = (hipError_t)launch_refit(a, plan, r.vf.leaf_offset.data(), stream);
+  hipError_t launched = (hipError_t)launch_refit(a, plan, w.vf.leaf_offset.data(), stream);
   if (launched == hipSuccess && leaves) {
     launched = hipMemcpyAsync(r.h_leaf.p, r.d_leaf.p, leaves * sizeof(float), hipMemcpyDeviceToHost, stream);
     if (launched == hipSuccess) launched = hipMemcpyAsync(r.h_weight.p, r.d_weight.p, leaves * sizeof(float), hipMemcpyDeviceToHost, stream);
@@ -2106,7 +2134,7 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
                    "look for a label that is NaN, infinite or far from the model's range; the forest is unchanged");
   if (flags != 0) throw OhxError(std::string(what) + ": the refit kernels reported error flags " + std::to_string(flags));
   // all or nothing: every tree is done and the error word is clean
-  refit_write_back(b.forest, r.vf, r.h_leaf.p, r.h_weight.p);
+  refit_write_back(b.forest, w.vf, r.h_leaf.p, r.h_weight.p);
   // everything built from leaf values is dropped as a model load drops it; the visit state holds none
   invalidate_device_state(b);
   b.contribs.reset();
@@ -2520,8 +2548,7 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
     int k = atoi(value);
     if (k != b->device_pref) {
       invalidate_device_state(*b);
-      b->visits.reset();               // the visit counts live on the device they were counted on
-      b->refit.reset();
+      drop_leaf_walk(*b);              // the visit counts live on the device they were counted on
     }
     b->device_pref = k;
   }
@@ -2661,7 +2688,7 @@ int OHXBoosterGetVisitCounts(BoosterHandle handle, void* stream, bst_ulong* ntre
   read_visit_counts(*b, v, static_cast<hipStream_t>(stream));
   static_assert(sizeof(bst_ulong) == sizeof(uint64_t), "tree_offsets are handed out as bst_ulong");
   *ntree = b->forest.trees.size();
-  *tree_offsets = reinterpret_cast<const bst_ulong*>(v.vf.tree_offsets.data());
+  *tree_offsets = reinterpret_cast<const bst_ulong*>(b->leaf_walk->vf.tree_offsets.data());
   *counts = v.node_counts.data();
   *rows_seen = v.rows_seen;
   API_END();
@@ -2676,7 +2703,7 @@ int OHXBoosterResetVisitCounts(BoosterHandle handle) {
     HIP_CHECK(hipSetDevice(v.device));
     HIP_CHECK(hipDeviceSynchronize());
     hipStream_t s = lib_streams(v.device).exec;
-    HIP_CHECK(hipMemsetAsync(v.d_counts.p, 0, std::max<size_t>(v.vf.leaf_offset.back(), 1) * sizeof(unsigned long long), s));
+    HIP_CHECK(hipMemsetAsync(v.d_counts.p, 0, v.d_counts.n * sizeof(unsigned long long), s));
     HIP_CHECK(hipStreamSynchronize(s));
   }
   std::fill(v.node_counts.begin(), v.node_counts.end(), 0);
@@ -2694,7 +2721,7 @@ int OHXBoosterRefreshCover(BoosterHandle handle, void* stream, float prior_weigh
     throw OhxError("OHXBoosterRefreshCover: no row has been counted yet (OHXBoosterCountVisits); the covers are unchanged");
   read_visit_counts(*b, v, static_cast<hipStream_t>(stream));
   // all or nothing: every new cover is computed (and every split's judged) before the first one is stored
-  std::vector<std::vector<float>> covers = refreshed_covers(b->forest, v.vf, v.node_counts.data(), prior_weight);
+  std::vector<std::vector<float>> covers = refreshed_covers(b->forest, b->leaf_walk->vf, v.node_counts.data(), prior_weight);
   for (size_t t = 0; t < covers.size(); ++t) b->forest.trees[t].sum_hess = std::move(covers[t]);
   // the contributions' tables hold the old covers: dropped exactly as a model load drops them, rebuilt at the next call
   b->contribs.reset();

@@ -19,12 +19,12 @@
 
 #include "categorical.hpp"
 #include "kernels.hpp"
+#include "walk_device.hpp"
 
 namespace ohx {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kBlock = 256;
 constexpr int kWavesPerBlock = kBlock / kWave;
 constexpr size_t kCuLdsBytes = 160 * 1024;
@@ -33,56 +33,6 @@ constexpr size_t kCuLdsBytes = 160 * 1024;
 #define OHX_CAT_CHAINS 2
 #endif
 constexpr int kChains = OHX_CAT_CHAINS;
-
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// The nodes are read through a buffer descriptor: one 128-bit load per node that the compiler cannot split into
-// narrower loads (it does split a plain uint4 load whose words are used at different points, which multiplies the
-// gathers), a 32-bit offset instead of a 64-bit address, and a hardware range check that turns a stray slot into a
-// read of zeros - a leaf of value 0 - instead of a fault.  emit_cat keeps the array under 4 GiB.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t node_rsrc(const DeviceCatForest& fr) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<CatNode*>(fr.nodes), 0, (int)fr.node_bytes, 0x00020000);
-}
-__device__ __forceinline__ uint4 load_node(__amdgpu_buffer_rsrc_t r, uint32_t slot) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(slot << 4), 0, 0);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-__device__ __forceinline__ bool is_inf(float v) { return __builtin_isinf(v); }
-
-// Row of this lane in tile `tile_id` (kernels.hpp TileShape; the walk kernels' own rule, kernels.hip tile_row): without
-// a grid tile t is rows 64 t .. 64 t + 63, with one it is a brick of 2^li x 2^lj x 2^lk neighbouring gridcells, whose
-// rows share more tree nodes than 64 cells of one latitude line do.  Every row of [0, nrow) lies in exactly one tile.
-__device__ __forceinline__ uint64_t tile_row(const TileShape& sh, uint64_t tile_id, int lane, uint64_t nrow, bool* valid) {
-  if (sh.im == 0) {
-    const uint64_t row = tile_id * kWave + lane;
-    *valid = row < nrow;
-    return row;
-  }
-  uint32_t t = (uint32_t)tile_id;
-  const uint32_t bi = t % sh.nbi;
-  t /= sh.nbi;
-  const uint32_t bj = t % sh.nbj;
-  const uint32_t bk = t / sh.nbj;
-  const uint32_t l = (uint32_t)lane;
-  uint32_t di, dj, dk;
-  if (sh.k_fastest) {
-    dk = l & ((1u << sh.lk) - 1u);
-    di = (l >> sh.lk) & ((1u << sh.li) - 1u);
-    dj = l >> (sh.lk + sh.li);
-  } else {
-    di = l & ((1u << sh.li) - 1u);
-    dj = (l >> sh.li) & ((1u << sh.lj) - 1u);
-    dk = l >> (sh.li + sh.lj);
-  }
-  const uint32_t i = (bi << sh.li) + di;
-  const uint32_t j = (bj << sh.lj) + dj;
-  const uint32_t k = sh.k_first + (bk << sh.lk) + dk;
-  const uint64_t m = (uint64_t)i + (uint64_t)sh.im * ((uint64_t)j + (uint64_t)sh.jm * (uint64_t)k);
-  *valid = i < sh.im && j < sh.jm && m >= sh.row0 && m - sh.row0 < sh.nrow && m - sh.row0 < nrow;
-  return m - sh.row0;
-}
 
 // The child a row with value v (NaN = missing) takes at node nd: 0 = left, 1 = right.
 __device__ __forceinline__ uint32_t step_right(const uint4& nd, float v, const uint32_t* __restrict__ words) {
@@ -107,56 +57,28 @@ __global__ __launch_bounds__(kBlock) void predict_cat_tile_kernel(DeviceCatFores
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
   float* tile = cat_lds + (size_t)wave * fr.num_feature * kWave + lane;
-  const __amdgpu_buffer_rsrc_t nodes = node_rsrc(fr);
+  const __amdgpu_buffer_rsrc_t nodes = make_rsrc(fr.nodes, fr.node_bytes);
   const uint32_t* __restrict__ words = fr.words;
   const bool missing_is_nan = a.missing != a.missing;
-  const float qnan = __builtin_nanf("");
   const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
   for (uint64_t t64 = (uint64_t)blockIdx.x * kWavesPerBlock + wave; t64 < a.ntiles; t64 += nwaves) {
     bool valid;
     const uint64_t row = tile_row(a.shape, t64, lane, a.nrow, &valid);
     if (!__any(valid)) continue;                 // a brick that overhangs the rows altogether
-    // ---- fill: `missing` -> NaN, columns the matrix does not have -> NaN, a lane without a row -> zeros
-    {
-      const float* p = a.rows + (valid ? row : 0) * (uint64_t)a.ncol;
-      bool any_inf = false;
-      uint32_t f = 0;
-      if (valid) {
-        for (; f + 4 <= a.ncol; f += 4) {
-          const f4u v = __builtin_nontemporal_load(reinterpret_cast<const f4u*>(p + f));
-#pragma unroll
-          for (int c = 0; c < 4; ++c) {
-            float x = v[c];
-            any_inf |= is_inf(x);
-            if (!missing_is_nan && x == a.missing) x = qnan;
-            tile[(f + c) * kWave] = x;
-          }
-        }
-        for (; f < a.ncol; ++f) {
-          float x = __builtin_nontemporal_load(p + f);
-          any_inf |= is_inf(x);
-          if (!missing_is_nan && x == a.missing) x = qnan;
-          tile[f * kWave] = x;
-        }
-        for (; f < fr.num_feature; ++f) tile[f * kWave] = qnan;
-        if (any_inf && !is_inf(a.missing) && a.flags) atomicOr(a.flags, kFlagInfInput);
-      } else {
-        for (; f < fr.num_feature; ++f) tile[f * kWave] = 0.0f;
-      }
-    }
+    (void)stage_rows<true>(tile, a.rows, row, valid, a.ncol, fr.num_feature, a.missing, missing_is_nan, a.flags);
     // (a wave reads only its own tile, each lane only its own column: no barrier)
     float acc = fr.base_score;
     uint32_t t = a.tree_begin;
     for (; t + kChains <= a.tree_end; t += kChains) {
       uint4 n[kChains];
 #pragma unroll
-      for (int c = 0; c < kChains; ++c) n[c] = load_node(nodes, fr.roots[t + c]);
+      for (int c = 0; c < kChains; ++c) n[c] = load_node16(nodes, fr.roots[t + c]);
       bool walking = true;
       while (walking) {
         walking = false;
 #pragma unroll
         for (int c = 0; c < kChains; ++c) {
-          if (n[c].y != 0u) n[c] = load_node(nodes, n[c].y + step_right(n[c], tile[(n[c].z & kCatFeatureMask) * kWave], words));
+          if (n[c].y != 0u) n[c] = load_node16(nodes, n[c].y + step_right(n[c], tile[(n[c].z & kCatFeatureMask) * kWave], words));
           walking |= n[c].y != 0u;
         }
       }
@@ -164,8 +86,8 @@ __global__ __launch_bounds__(kBlock) void predict_cat_tile_kernel(DeviceCatFores
       for (int c = 0; c < kChains; ++c) acc += __uint_as_float(n[c].x);      // in tree order
     }
     for (; t < a.tree_end; ++t) {
-      uint4 n0 = load_node(nodes, fr.roots[t]);
-      while (n0.y != 0u) n0 = load_node(nodes, n0.y + step_right(n0, tile[(n0.z & kCatFeatureMask) * kWave], words));
+      uint4 n0 = load_node16(nodes, fr.roots[t]);
+      while (n0.y != 0u) n0 = load_node16(nodes, n0.y + step_right(n0, tile[(n0.z & kCatFeatureMask) * kWave], words));
       acc += __uint_as_float(n0.x);
     }
     if (valid) a.out[row] = acc;
@@ -176,7 +98,7 @@ __global__ __launch_bounds__(kBlock) void predict_cat_tile_kernel(DeviceCatFores
 // of every tree's leaf as a float, [nrow][ntree].
 template <bool PRED_LEAF>
 __global__ __launch_bounds__(kBlock) void predict_cat_direct_kernel(DeviceCatForest fr, CatPredictArgs a) {
-  const __amdgpu_buffer_rsrc_t nodes = node_rsrc(fr);
+  const __amdgpu_buffer_rsrc_t nodes = make_rsrc(fr.nodes, fr.node_bytes);
   const uint32_t* __restrict__ words = fr.words;
   const bool missing_is_nan = a.missing != a.missing;
   const float qnan = __builtin_nanf("");
@@ -191,7 +113,7 @@ __global__ __launch_bounds__(kBlock) void predict_cat_direct_kernel(DeviceCatFor
     float acc = fr.base_score;
     for (uint32_t t = a.tree_begin; t < a.tree_end; ++t) {
       uint32_t slot = fr.roots[t];
-      uint4 nd = load_node(nodes, slot);
+      uint4 nd = load_node16(nodes, slot);
       while (nd.y != 0u) {
         const uint32_t f = nd.z & kCatFeatureMask;
         float v = qnan;
@@ -200,7 +122,7 @@ __global__ __launch_bounds__(kBlock) void predict_cat_direct_kernel(DeviceCatFor
           if (!missing_is_nan && v == a.missing) v = qnan;
         }
         slot = nd.y + step_right(nd, v, words);
-        nd = load_node(nodes, slot);
+        nd = load_node16(nodes, slot);
       }
       if (PRED_LEAF) a.out[row * (uint64_t)ntree + (t - a.tree_begin)] = (float)fr.orig_id[slot];
       else acc += __uint_as_float(nd.x);
@@ -225,20 +147,14 @@ const char* cat_kernel_symbol(uint32_t num_feature, bool pred_leaf, bool force_d
 hipError_t launch_predict_cat(const DeviceCatForest& fr, const CatPredictArgs& args, int num_cus, bool force_direct,
                               hipStream_t stream, const LaunchTuning& tune) {
   CatPredictArgs a = args;
-  // which rows a wave takes: bricks when the caller named the grid the rows come from, as the walk kernels do
-  // (kernels.hpp pick_shape); not when most bricks would hold no row
-  a.shape = pick_shape(tune, tune.grid_im, tune.grid_jm, tune.grid_row0, a.nrow);
-  if (a.shape.im != 0 && a.shape.live_tiles() * 2 < a.shape.ntiles(a.nrow)) a.shape = TileShape();
+  a.shape = pick_shape_dense(tune, a.nrow);
   a.ntiles = a.shape.ntiles(a.nrow);
   if (a.nrow == 0 || (a.pred_leaf && a.tree_end == a.tree_begin)) return hipSuccess;
   if (a.tree_end < a.tree_begin || a.tree_end > fr.num_trees || a.ncol > fr.num_feature) return hipErrorInvalidValue;
   if (cat_uses_tile(fr.num_feature, a.pred_leaf, force_direct)) {
     const size_t lds = cat_tile_lds_bytes(fr.num_feature);
-    if (lds > 64 * 1024) {
-      hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(predict_cat_tile_kernel),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      if (e != hipSuccess) return e;
-    }
+    const hipError_t e = raise_lds_limit(predict_cat_tile_kernel, lds);
+    if (e != hipSuccess) return e;
     int per_cu = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, predict_cat_tile_kernel, kBlock, lds) != hipSuccess || per_cu < 1)
       per_cu = 1;

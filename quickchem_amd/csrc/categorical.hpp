@@ -1,6 +1,7 @@
 // Launchers of the gfx950 kernels that predict boosters with categorical splits (definitions in categorical.hip;
 // semantics in include/ohxgb.h and docs/14_categorical.md).  Such a booster is walked from a node format of its own
 // (flatten.hpp CatNode) and by these kernels only: nothing here is reached by a booster without a categorical split.
+// Which rows a wave takes, the fill of its LDS tile and the node load are the walk kernels' (walk_device.hpp).
 #pragma once
 #include <hip/hip_runtime_api.h>
 

@@ -22,18 +22,15 @@
 #include <cstdint>
 
 #include "kernels.hpp"
+#include "walk_device.hpp"
 
 namespace ohx {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kBlock = 256;                  // 4 waves
 constexpr int kWavesPerBlock = kBlock / kWave;
 
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 // a pointer that is KNOWN to point into LDS: loads through it are ds_read, never flat_load (a generic pointer
 // into LDS whose origin the compiler loses track of goes through the texture addresser like a global load)
 typedef const __attribute__((address_space(3))) char* lds_cptr;
@@ -41,55 +38,9 @@ typedef const __attribute__((address_space(3))) u32x4* lds_u32x4_ptr;
 typedef __attribute__((address_space(3))) uint32_t* lds_u32_ptr;
 typedef __attribute__((address_space(3))) void* lds_void_ptr;
 
-// The packed 8-byte nodes are read through a buffer descriptor: one 64-bit load per node that the
-// compiler cannot split into dword loads (it does split a plain uint2 load when only one half
-// is needed early, which doubles the gathers), a 32-bit offset instead of a 64-bit address,
-// and a hardware range check.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, uint32_t bytes) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, (int)bytes, 0x00020000);
-}
-__device__ __forceinline__ uint2 load_node8(__amdgpu_buffer_rsrc_t r, uint32_t slot) {
-  const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(r, (int)(slot << 3), 0, 0);
-  return make_uint2(v.x, v.y);
-}
-__device__ __forceinline__ bool is_inf(float v) { return __builtin_isinf(v); }
-
 // ------------------------------------------------------------------ lanes -> rows
 
-// Row of this lane in tile `tile_id` (TileShape, kernels.hpp).  Tiles are numbered brick-i
-// fastest, so the waves of a block and the blocks of a launch walk neighbouring bricks.
-__device__ __forceinline__ uint64_t tile_row(const TileShape& sh, uint64_t tile_id, int lane, uint64_t nrow,
-                                             bool* valid) {
-  if (sh.im == 0) {
-    const uint64_t row = tile_id * kWave + lane;
-    *valid = row < nrow;
-    return row;
-  }
-  uint32_t t = (uint32_t)tile_id;
-  const uint32_t bi = t % sh.nbi;
-  t /= sh.nbi;
-  const uint32_t bj = t % sh.nbj;
-  const uint32_t bk = t / sh.nbj;
-  const uint32_t l = (uint32_t)lane;
-  uint32_t di, dj, dk;
-  if (sh.k_fastest) {
-    dk = l & ((1u << sh.lk) - 1u);
-    di = (l >> sh.lk) & ((1u << sh.li) - 1u);
-    dj = l >> (sh.lk + sh.li);
-  } else {
-    di = l & ((1u << sh.li) - 1u);
-    dj = (l >> sh.li) & ((1u << sh.lj) - 1u);
-    dk = l >> (sh.li + sh.lj);
-  }
-  const uint32_t i = (bi << sh.li) + di;
-  const uint32_t j = (bj << sh.lj) + dj;
-  const uint32_t k = sh.k_first + (bk << sh.lk) + dk;
-  const uint64_t m = (uint64_t)i + (uint64_t)sh.im * ((uint64_t)j + (uint64_t)sh.jm * (uint64_t)k);
-  *valid = i < sh.im && j < sh.jm && m >= sh.row0 && m - sh.row0 < sh.nrow;
-  return m - sh.row0;
-}
-
-// the same for a launch: rows grouped by the clustering pass come through the permutation
+// tile_row (walk_device.hpp) for a launch: rows grouped by the clustering pass come through the permutation
 __device__ __forceinline__ uint64_t launch_row(const PredictArgs& a, uint64_t tile_id, int lane, bool* valid,
                                                uint64_t perm_slots = ~0ull) {
   if (a.perm != nullptr) {
@@ -104,46 +55,7 @@ __device__ __forceinline__ uint64_t launch_row(const PredictArgs& a, uint64_t ti
 
 // ------------------------------------------------------------------ tile fill
 
-// Row-major rows -> LDS tile[f * 64 + lane].  `missing` values become NaN so the
-// walk has one notion of missing.  Returns true if this lane's row has any NaN.
-__device__ __forceinline__ bool fill_tile_rows(float* __restrict__ tile, const float* __restrict__ rows,
-                                               uint64_t row, bool valid, uint32_t ncol, uint32_t nfeat,
-                                               float missing, bool missing_is_nan, uint32_t* flags) {
-  bool any_nan = false;
-  bool any_inf = false;
-  const float qnan = __builtin_nanf("");
-  const float* p = rows + row * (uint64_t)ncol;
-  uint32_t f = 0;
-  if (valid) {
-    for (; f + 4 <= ncol; f += 4) {
-      f4u v = __builtin_nontemporal_load(reinterpret_cast<const f4u*>(p + f));
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float x = v[c];
-        any_inf |= is_inf(x);
-        if (!missing_is_nan && x == missing) x = qnan;
-        any_nan |= (x != x);
-        tile[(f + c) * kWave] = x;
-      }
-    }
-    for (; f < ncol; ++f) {
-      float x = __builtin_nontemporal_load(p + f);
-      any_inf |= is_inf(x);
-      if (!missing_is_nan && x == missing) x = qnan;
-      any_nan |= (x != x);
-      tile[f * kWave] = x;
-    }
-    // a booster with more features than the matrix has columns sees them as missing
-    for (; f < nfeat; ++f) {
-      tile[f * kWave] = qnan;
-      any_nan = true;
-    }
-    if (any_inf && !is_inf(missing) && flags) atomicOr(flags, kFlagInfInput);
-  } else {
-    for (; f < nfeat; ++f) tile[f * kWave] = 0.0f;
-  }
-  return any_nan;
-}
+// (rows of a matrix: stage_rows, walk_device.hpp)
 
 // One lane's row of the fused path into its column of the wave's tile: field after field (the reference's gather,
 // OH_GridCompMod.F90:308-345, PL / 100 at :314), `missing` -> NaN.  The fields come one after the other, each load
@@ -912,8 +824,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CHAINS >
         bool valid;
         const uint64_t row = launch_row(a, tile_id, lane, &valid);
         if (!__any(valid) || t0 >= t1) continue;
-        const bool lane_nan = fill_tile_rows(tile, a.rows, row, valid, a.ncol, fr.num_feature, a.missing,
-                                             missing_is_nan, a.flags);
+        const bool lane_nan = stage_rows<true>(tile, a.rows, row, valid, a.ncol, fr.num_feature, a.missing,
+                                               missing_is_nan, a.flags);
         float* leaves = a.leaf_buf + ((size_t)(tile_id - a.tile_begin) * ntree - a.tree_begin) * kWave + lane;
         (void)walk_tile<FMT, CHAINS, TOPS>(fr, heads, t0, t1, tile, __any(lane_nan), first, nfirst, leaves);
       }
@@ -932,8 +844,8 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(CHAINS >
     bool valid;
     const uint64_t row = launch_row(a, tile_id, lane, &valid, slots);
     if (!__any(valid)) continue;                      // nothing of the matrix in this tile
-    const bool lane_nan = fill_tile_rows(tile, a.rows, row, valid, a.ncol, fr.num_feature, a.missing,
-                                         missing_is_nan, a.flags);
+    const bool lane_nan = stage_rows<true>(tile, a.rows, row, valid, a.ncol, fr.num_feature, a.missing,
+                                           missing_is_nan, a.flags);
     const bool wave_nan = __any(lane_nan);
     // the tile is private to this wave: its own LDS writes are ordered before its reads
     const float acc = walk_tile<FMT, CHAINS, TOPS>(fr, heads, a.tree_begin, a.tree_end, tile, wave_nan, first, nfirst);
@@ -1988,14 +1900,6 @@ int tile_grid(K kernel, size_t lds_bytes, uint64_t ntiles, int num_cus) {
   return (int)blocks;
 }
 
-template <class K>
-hipError_t ensure_lds(K kernel, size_t lds_bytes) {
-  if (lds_bytes > 64 * 1024)
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)lds_bytes);
-  return hipSuccess;
-}
-
 // Which stream the k-th launch of a train goes to (TrainStreams, kernels.hpp).  Inside a group the launches
 // alternate between the caller's stream and the side stream; at a group's end both streams meet.  Order between
 // launches never matters for the results (disjoint rows); it only shapes how the chip is filled.
@@ -2085,7 +1989,7 @@ hipError_t launch_train(K kernel, unsigned threads, size_t lds, uint64_t grid, u
 // event.  Stream-ordered, so the device forms need no host in the loop (include/ohxgb.h: OHXBoosterRingReruns).
 template <class K, class Args>
 hipError_t launch_ring_rerun(K again, size_t lds, const DeviceForest& fr, Args b, uint64_t ntiles, int num_cus, hipStream_t stream) {
-  hipError_t e = ensure_lds(again, lds);
+  hipError_t e = raise_lds_limit(again, lds);
   if (e != hipSuccess) return e;
   b.only_if_train = b.train_id;
   b.defer_list = nullptr;
@@ -2100,7 +2004,7 @@ hipError_t launch_ring_rerun(K again, size_t lds, const DeviceForest& fr, Args b
 // The second launch of a deferred-rows call: the rows of the list, 64 per wave, each lane its own row, missing-aware.
 template <class K, class Args>
 hipError_t launch_deferred(K kernel, size_t lds, const DeviceForest& fr, Args a, int num_cus, hipStream_t stream) {
-  hipError_t e = ensure_lds(kernel, lds);
+  hipError_t e = raise_lds_limit(kernel, lds);
   if (e != hipSuccess) return e;
   a.perm = a.defer_list;
   a.perm_count = a.defer_count;
@@ -2117,7 +2021,7 @@ hipError_t launch_deferred(K kernel, size_t lds, const DeviceForest& fr, Args a,
 template <class K, class Args>
 hipError_t launch_split(K kernel, size_t lds, const DeviceForest& fr, Args a, uint64_t ntiles, int num_cus, hipStream_t stream,
                         const LaunchTuning& tune, uint32_t split) {
-  hipError_t e = ensure_lds(kernel, lds);
+  hipError_t e = raise_lds_limit(kernel, lds);
   if (e != hipSuccess) return e;
   a.tile_begin = 0;
   a.tile_end = ntiles;
@@ -2370,7 +2274,7 @@ hipError_t launch_plan(const WalkPlan& p, K first, K rerun, K second, const Devi
     hipError_t e = launch_split(first, p.lds, fr, a, ntiles, num_cus, stream, tune, p.split);
     return e != hipSuccess ? e : hipGetLastError();
   }
-  hipError_t e = ensure_lds(first, p.lds);
+  hipError_t e = raise_lds_limit(first, p.lds);
   if (e != hipSuccess) return e;
   set_runs(a, p.runs);
   const bool ring = p.how == WalkPlan::Ring;
@@ -2473,7 +2377,7 @@ uint32_t cluster_key_bits(const ClusterArgs& a) { return a.ntrees * (1u + 2u * a
 
 template <int NT>
 hipError_t launch_cluster_keys_nt(const DeviceForest& fr, const ClusterArgs& a, size_t lds, int num_cus, hipStream_t stream) {
-  hipError_t e = ensure_lds(cluster_keys_kernel<NT>, lds);
+  hipError_t e = raise_lds_limit(cluster_keys_kernel<NT>, lds);
   if (e != hipSuccess) return e;
   const int grid = tile_grid(cluster_keys_kernel<NT>, lds, (a.nrow + kWave - 1) / kWave, num_cus);
   hipLaunchKernelGGL(cluster_keys_kernel<NT>, dim3(grid), dim3(kBlock), lds, stream, fr, a);
@@ -2527,7 +2431,7 @@ hipError_t launch_feature_prep(const PrepArgs& a, float* aod_scratch, hipStream_
   while (waves > 1 && (size_t)waves * wave_lds > 160 * 1024) --waves;
   const size_t lds = (size_t)waves * wave_lds;
   if (lds > 160 * 1024) return hipErrorInvalidValue;
-  hipError_t e = ensure_lds(feature_column_sums_kernel, lds);
+  hipError_t e = raise_lds_limit(feature_column_sums_kernel, lds);
   if (e != hipSuccess) return e;
   const uint64_t cols_per_block = (uint64_t)waves * kWave;
   hipLaunchKernelGGL(feature_column_sums_kernel, dim3((unsigned)((ncols + cols_per_block - 1) / cols_per_block), 3),

@@ -351,6 +351,13 @@ inline TileShape pick_shape(const LaunchTuning& tune, int im, int jm, uint64_t r
   return s;
 }
 
+// The same for a launcher whose waves gain nothing from an empty brick (categorical.hip, visits.hip): bricks of the grid
+// the caller named for the rows (tune.grid_*), unless most bricks would hold no row; then 64 consecutive rows.
+inline TileShape pick_shape_dense(const LaunchTuning& tune, uint64_t nrow) {
+  const TileShape s = pick_shape(tune, tune.grid_im, tune.grid_jm, tune.grid_row0, nrow);
+  return s.im != 0 && s.live_tiles() * 2 < s.ntiles(nrow) ? TileShape() : s;
+}
+
 // Rows with missing values left to a second launch (PredictArgs::defer_list): who asks for it and how long the list is.
 // The booster's buffer holds the count and then the list: defer_capacity(nrow) + 1 words.
 struct DeferRule {

@@ -2,7 +2,7 @@
 // A gather costs the texture path by the tag look-ups of its quads and by the lines that miss the L1; both are decided
 // by where emit_super put the groups (flatten.hpp kSuperPack*) and by which rows share a wave, and neither needs a GPU
 // to be counted.  The rows go through the trees with the host walk of the layout tests (super_walk.hpp) and to the
-// lanes as the ring kernels send them (kernels.hip tile_row).
+// lanes as the ring kernels send them (walk_device.hpp tile_row).
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -13,7 +13,7 @@ namespace ohx {
 
 namespace {
 
-// lane -> gridcell of its brick, in grid order: what tile_row (kernels.hip) does with a lane
+// lane -> gridcell of its brick, in grid order: what tile_row (walk_device.hpp) does with a lane
 inline uint32_t lane_cell(const LineCountShape& sh, uint32_t l) {
   if (sh.li + sh.lj + sh.lk != 6) return l;
   uint32_t di, dj, dk;

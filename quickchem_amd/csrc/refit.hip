@@ -15,84 +15,14 @@
 #include <cstdint>
 
 #include "refit.hpp"
+#include "walk_device.hpp"
 
 namespace ohx {
 
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kBlock = (int)kRefitBlock;
 constexpr int kWavesPerBlock = kBlock / kWave;
-
-typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-// the node loads of visits.hip: one 128-bit load through a buffer descriptor, range-checked by the hardware (a stray
-// slot reads zeros: a leaf of index 0)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t node_rsrc(const RefitArgs& a) {
-  return __builtin_amdgcn_make_buffer_rsrc(const_cast<VisitNode*>(a.nodes), 0, (int)a.node_bytes, 0x00020000);
-}
-__device__ __forceinline__ uint4 load_node(__amdgpu_buffer_rsrc_t r, uint32_t slot) {
-  const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r, (int)(slot << 4), 0, 0);
-  return make_uint4(v.x, v.y, v.z, v.w);
-}
-
-// The wave's rows into LDS as tile[feature * 64 + lane]: `missing` -> NaN, columns the matrix does not have -> NaN, a
-// lane without a row -> zeros (it walks and stores nothing).  The launch reads every row once: nontemporal loads.
-__device__ __forceinline__ void stage_rows(float* tile, const RefitArgs& a, uint64_t row, bool valid) {
-  const bool missing_is_nan = a.missing != a.missing;
-  const float qnan = __builtin_nanf("");
-  uint32_t f = 0;
-  if (valid) {
-    const float* p = a.rows + row * (uint64_t)a.ncol;
-    for (; f + 4 <= a.ncol; f += 4) {
-      const f4u v = __builtin_nontemporal_load(reinterpret_cast<const f4u*>(p + f));
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        float x = v[c];
-        if (!missing_is_nan && x == a.missing) x = qnan;
-        tile[(f + c) * kWave] = x;
-      }
-    }
-    for (; f < a.ncol; ++f) {
-      float x = __builtin_nontemporal_load(p + f);
-      if (!missing_is_nan && x == a.missing) x = qnan;
-      tile[f * kWave] = x;
-    }
-    for (; f < a.num_feature; ++f) tile[f * kWave] = qnan;
-  } else {
-    for (; f < a.num_feature; ++f) tile[f * kWave] = 0.0f;
-  }
-}
-
-// The dense leaf index the row reaches in the tree rooted at `root` (visits.hip walk_to_leaf): NaN takes the default
-// child, x < cond goes left, +-inf is compared as the float it is.
-template <bool STAGE>
-__device__ __forceinline__ uint32_t walk_to_leaf(__amdgpu_buffer_rsrc_t nodes, uint32_t root, const float* tile,
-                                                 const float* x, const RefitArgs& a) {
-  const bool missing_is_nan = a.missing != a.missing;
-  const float qnan = __builtin_nanf("");
-  uint4 nd = load_node(nodes, root);
-  while (nd.y != 0u) {
-    const uint32_t f = nd.z & 0x7FFFFFFFu;
-    float v;
-    if (STAGE) {
-      v = tile[f * kWave];
-    } else {
-      v = 0.0f;
-      if (x != nullptr) {
-        v = qnan;
-        if (f < a.ncol) {
-          v = x[f];
-          if (!missing_is_nan && v == a.missing) v = qnan;
-        }
-      }
-    }
-    const bool left = (v != v) ? (nd.z >> 31) != 0u : (v < __uint_as_float(nd.x));
-    nd = load_node(nodes, nd.y + (left ? 0u : 1u));
-  }
-  return nd.w;
-}
 
 // grid (blocks); dynamic LDS: the four tiles (STAGE)
 template <bool STAGE>
@@ -100,31 +30,26 @@ __global__ __launch_bounds__(kBlock) void refit_leaf_ids_kernel(RefitArgs a) {
   extern __shared__ float refit_lds[];
   const int lane = threadIdx.x & (kWave - 1);
   const int wave = threadIdx.x / kWave;
-  float* tile = refit_lds + (size_t)wave * a.num_feature * kWave + lane;
-  const __amdgpu_buffer_rsrc_t nodes = node_rsrc(a);
+  const DeviceLeafWalk& w = a.walk;
+  float* tile = refit_lds + (size_t)wave * w.num_feature * kWave + lane;
+  const bool missing_is_nan = a.missing != a.missing;
+  const __amdgpu_buffer_rsrc_t nodes = make_rsrc(w.nodes, w.node_bytes);
   const uint64_t ntiles = (a.nrow + kWave - 1) / kWave;
   const uint64_t nwaves = (uint64_t)gridDim.x * kWavesPerBlock;
   for (uint64_t t64 = (uint64_t)blockIdx.x * kWavesPerBlock + wave; t64 < ntiles; t64 += nwaves) {
     const uint64_t row = t64 * kWave + lane;
     const bool valid = row < a.nrow;
-    if (STAGE) stage_rows(tile, a, row, valid);
+    // the launch reads every row once: nontemporal loads
+    if (STAGE) (void)stage_rows<true>(tile, a.rows, row, valid, a.ncol, w.num_feature, a.missing, missing_is_nan, nullptr);
     // (a wave reads only its own tile, each lane only its own column: no barrier)
     const float* x = valid ? a.rows + row * (uint64_t)a.ncol : nullptr;
-    for (uint32_t tree = 0; tree < a.num_trees; ++tree) {
-      const uint32_t leaf = walk_to_leaf<STAGE>(nodes, a.roots[tree], tile, x, a);
-      const uint32_t key = a.leaf_offset[tree] + leaf;
+    for (uint32_t tree = 0; tree < w.num_trees; ++tree) {
+      const uint32_t leaf = walk_to_leaf<STAGE>(nodes, w.roots[tree], tile, x, a.ncol, a.missing);
+      const uint32_t key = w.leaf_offset[tree] + leaf;
       // tree-major planes: the wave's 64 ids are 256 contiguous bytes
       if (valid) __builtin_nontemporal_store(leaf, a.ids + (uint64_t)tree * a.nrow + row);
-      // the rows per leaf: the first lane still to do names its leaf, everyone on it is counted with one add
-      const bool counted = valid && key < a.total_leaves;
-      uint64_t todo = __ballot(counted);
-      while (todo != 0ull) {
-        const int leader = __ffsll((unsigned long long)todo) - 1;
-        const uint32_t k = (uint32_t)__builtin_amdgcn_readlane((int)key, leader);
-        const uint64_t same = __ballot(counted && key == k);
-        if (lane == leader) atomicAdd(&a.H[k], (unsigned long long)__popcll(same));
-        todo &= ~same;
-      }
+      // the rows per leaf
+      add_per_leaf(a.H, key, valid && key < w.total_leaves, lane);
     }
   }
 }
@@ -132,11 +57,11 @@ __global__ __launch_bounds__(kBlock) void refit_leaf_ids_kernel(RefitArgs a) {
 // grid (blocks); tree = the tree whose sums are made.  pred is written here for the first time at tree 0.
 __global__ __launch_bounds__(kBlock) void refit_accumulate_kernel(RefitArgs a, uint32_t tree) {
   const int lane = threadIdx.x & (kWave - 1);
-  const uint32_t leaf0 = a.leaf_offset[tree];
-  const uint32_t nleaf = a.leaf_offset[tree + 1] - leaf0;
+  const uint32_t leaf0 = a.walk.leaf_offset[tree];
+  const uint32_t nleaf = a.walk.leaf_offset[tree + 1] - leaf0;
   uint32_t prev0 = 0, nprev = 0;
   if (tree != 0) {
-    prev0 = a.leaf_offset[tree - 1];
+    prev0 = a.walk.leaf_offset[tree - 1];
     nprev = leaf0 - prev0;
   }
   const uint32_t* ids = a.ids + (uint64_t)tree * a.nrow;
@@ -190,8 +115,8 @@ __global__ __launch_bounds__(kBlock) void refit_accumulate_kernel(RefitArgs a, u
 
 // grid (blocks over the tree's leaves)
 __global__ __launch_bounds__(kBlock) void refit_solve_kernel(RefitArgs a, uint32_t tree) {
-  const uint32_t leaf0 = a.leaf_offset[tree];
-  const uint32_t nleaf = a.leaf_offset[tree + 1] - leaf0;
+  const uint32_t leaf0 = a.walk.leaf_offset[tree];
+  const uint32_t nleaf = a.walk.leaf_offset[tree + 1] - leaf0;
   const uint32_t l = blockIdx.x * kBlock + threadIdx.x;
   if (l >= nleaf) return;
   const uint32_t k = leaf0 + l;
@@ -209,22 +134,20 @@ __global__ __launch_bounds__(kBlock) void refit_solve_kernel(RefitArgs a, uint32
 }  // namespace
 
 int prepare_refit(const RefitPlan& plan) {
-  if (!plan.stage || plan.lds_bytes <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(refit_leaf_ids_kernel<true>),
-                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)plan.lds_bytes);
+  return plan.stage ? raise_lds_limit(refit_leaf_ids_kernel<true>, plan.lds_bytes) : hipSuccess;
 }
 
 int launch_refit(const RefitArgs& a, const RefitPlan& plan, const uint32_t* leaf_offset, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (a.nrow == 0 || a.num_trees == 0) return hipSuccess;
-  if (a.nrow > kRefitMaxRows || a.ncol > a.num_feature || plan.lds_bytes > kVisitStageMaxBytes || plan.ids_blocks == 0 ||
-      plan.accum_blocks == 0 || plan.stage != visit_stages(a.num_feature))
+  if (a.nrow == 0 || a.walk.num_trees == 0) return hipSuccess;
+  if (a.nrow > kRefitMaxRows || a.ncol > a.walk.num_feature || plan.lds_bytes > kVisitStageMaxBytes || plan.ids_blocks == 0 ||
+      plan.accum_blocks == 0 || plan.stage != visit_stages(a.walk.num_feature))
     return hipErrorInvalidValue;
   hipError_t e = hipSuccess;
   if (plan.stage) hipLaunchKernelGGL(refit_leaf_ids_kernel<true>, dim3(plan.ids_blocks), dim3(kBlock), plan.lds_bytes, stream, a);
   else hipLaunchKernelGGL(refit_leaf_ids_kernel<false>, dim3(plan.ids_blocks), dim3(kBlock), 0, stream, a);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  for (uint32_t t = 0; t < a.num_trees; ++t) {
+  for (uint32_t t = 0; t < a.walk.num_trees; ++t) {
     hipLaunchKernelGGL(refit_accumulate_kernel, dim3(plan.accum_blocks), dim3(kBlock), 0, stream, a, t);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     const uint32_t leaves = leaf_offset[t + 1] - leaf_offset[t];

@@ -4,7 +4,8 @@
 //
 // Tree t's gradient depends on the refit leaves of trees 0 .. t-1, so the device makes one pass over the rows per tree.
 // What does not depend on leaf values - which leaf a row reaches - is computed once, for all trees, by one walk that
-// stores dense leaf ids (visits.hpp VisitForest numbering) tree-major.  The per-leaf sums are integers: the gradient in
+// stores dense leaf ids (visits.hpp VisitForest numbering) tree-major.  The walk reads the booster's one DeviceLeafWalk,
+// which the visit counts read too, with the routines of walk_device.hpp.  The per-leaf sums are integers: the gradient in
 // fixed point (2^-24) as int64, the hessian a count of rows.  No float atomics, and the same sums whatever the order of
 // the rows or the launch shape.
 #pragma once
@@ -67,12 +68,7 @@ inline uint32_t refit_solve_blocks(uint32_t leaves) { return (leaves + kRefitBlo
 
 #ifdef __HIPCC__
 struct RefitArgs {
-  // the walk: the VisitForest on the device
-  const VisitNode* nodes = nullptr;
-  uint32_t node_bytes = 0;
-  const uint32_t* roots = nullptr;
-  const uint32_t* leaf_offset = nullptr;   // T + 1
-  uint32_t num_trees = 0, num_feature = 0, total_leaves = 0;
+  DeviceLeafWalk walk;                     // the VisitForest on the device (visits.hpp)
   // the rows
   const float* rows = nullptr;             // [nrow][ncol]
   uint64_t nrow = 0;
@@ -94,7 +90,7 @@ struct RefitArgs {
 int prepare_refit(const RefitPlan& plan);
 // Enqueues on `stream` (a hipStream_t) the leaf-id walk and then, tree after tree, the accumulate pass and the solve:
 // 2T + 1 launches, nothing in between.  G, H and the error word must be zero; leaf_offset is the host's copy of
-// a.leaf_offset (a solve launch is sized by its tree's leaves).  Returns a hipError_t.
+// a.walk.leaf_offset (a solve launch is sized by its tree's leaves).  Returns a hipError_t.
 int launch_refit(const RefitArgs& a, const RefitPlan& plan, const uint32_t* leaf_offset, void* stream);
 #endif  // __HIPCC__
 

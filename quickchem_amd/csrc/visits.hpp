@@ -5,7 +5,7 @@
 // leaf it ends on.  The host sums the leaf counters up each tree, so a split's count is the sum of its children's by
 // construction.  Everything is an integer: no float atomics, and the same numbers whatever the launch shape.
 //
-// The walk reads a 16-byte node of its own, VisitNode: the wide node's shape and placement (flatten.hpp WideNode,
+// The walk (walk_device.hpp walk_to_leaf) reads a 16-byte node of its own, VisitNode: the wide node's shape and placement (flatten.hpp WideNode,
 // place_forest) with the tree's DENSE LEAF INDEX where the wide format keeps the file's node id.  Leaves are numbered
 // 0 .. leaf_count[t] - 1 per tree in file node order; leaf_offset[t] is where tree t's counters start in the one
 // uint64 array of the booster.
@@ -93,15 +93,21 @@ inline uint32_t visit_global_blocks(uint64_t ntiles, int num_cus) {
 }
 
 #ifdef __HIPCC__
-struct DeviceVisitForest {
+// The VisitForest on the device: what a walk to dense leaf indices reads (walk_device.hpp walk_to_leaf).  One per
+// booster, shared by the visit counts and the leaf refit; no kernel writes to it.
+struct DeviceLeafWalk {
   const VisitNode* nodes = nullptr;
-  uint32_t node_bytes = 0;
+  uint32_t node_bytes = 0;                  // of `nodes` (< 4 GiB: read through a buffer descriptor)
   const uint32_t* roots = nullptr;
-  const uint32_t* leaf_offset = nullptr;
-  const uint32_t* lds_trees = nullptr;      // the plan's lists
-  const uint32_t* global_trees = nullptr;
+  const uint32_t* leaf_offset = nullptr;    // T + 1
   uint32_t num_trees = 0, num_feature = 0;
   uint32_t total_leaves = 0;                // leaf_offset[num_trees]: the counters
+};
+
+struct DeviceVisitForest {
+  DeviceLeafWalk walk;
+  const uint32_t* lds_trees = nullptr;      // the plan's lists
+  const uint32_t* global_trees = nullptr;
 };
 
 struct VisitArgs {

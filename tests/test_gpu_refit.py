@@ -295,6 +295,128 @@ def test_after_a_refit_everything_equals_a_booster_loaded_with_the_expected_leav
     d.free()
 
 
+# ---- the walk the refit shares with the visit counts ----
+
+SHARED_MISSING = -999.0
+
+
+@functools.lru_cache(maxsize=None)
+def shared_walk(ntree=3, depth=4):
+    """The smallest case that still takes every path of the shared walk: 5 features (the 4-wide row loads have a tail),
+    130 rows (two full tiles and one of 2), missing = -999 in the rows, and a matrix of 4 columns (feature 4 is absent).
+    -> (image, rows, labels, the restatement's refit, the expected counts from a fresh booster's leaf ids)."""
+    js = V.random_booster(8300 + ntree, ntree, 5, max_depth=depth, p_leaf=0.1)
+    rng = np.random.default_rng(ntree)
+    x = random_rows(rng, 130, 5)
+    x[rng.random(x.shape) < 0.1] = SHARED_MISSING
+    x = np.ascontiguousarray(x[:, :4])
+    y = labels_for(ntree, 130)
+    want = R.refit(js, x, SHARED_MISSING, y, 0.5, 1.0, 0)
+    trees = V.doc_trees(js)
+    fresh = capi.Booster(model_buffer=js)
+    d = capi.DMatrix(x, missing=SHARED_MISSING)
+    counts = V.expected_counts(trees, fresh.predict(d, option_mask=16).reshape(len(x), len(trees)))
+    d.free()
+    fresh.free()
+    V.check_invariants(trees, counts, len(x))
+    return js, x, y, want, counts
+
+
+def count(b, d):
+    b.count_visits(d)
+    return b.visit_counts()
+
+
+def refit_is_the_restatement(b, d, y, want, tmp_path, what):
+    assert b.refit_leaves(d, y, eta=0.5) == want["leaves_refit"], what
+    same_leaves(held(b, tmp_path)[0], (want["value"], want["base_weight"]), what)
+
+
+def test_counting_and_refitting_in_either_order_share_one_walk(torch_cuda, tmp_path):
+    js, x, y, want, counts = shared_walk()
+    d = capi.DMatrix(x, missing=SHARED_MISSING)
+    b = capi.Booster(model_buffer=js)
+    before, seen = count(b, d)                              # the count builds the walk
+    assert seen == 130
+    V.assert_same_counts(before, counts, "count first")
+    refit_is_the_restatement(b, d, y, want, tmp_path, "refit after a count")
+    after, seen = b.visit_counts()
+    assert seen == 130
+    V.assert_same_counts(after, before, "the refit moved a counter")
+    b.reset_visit_counts()
+    again, seen = count(b, d)                               # the structure is unchanged: so are the counts
+    assert seen == 130
+    V.assert_same_counts(again, counts, "count after the refit")
+    b.free()
+    b = capi.Booster(model_buffer=js)
+    refit_is_the_restatement(b, d, y, want, tmp_path, "refit first")      # the refit builds the walk
+    got, seen = count(b, d)
+    assert seen == 130
+    V.assert_same_counts(got, counts, "count after a refit that built the walk")
+    b.free()
+    d.free()
+
+
+def test_a_visits_knob_between_a_count_and_a_refit(torch_cuda, tmp_path):
+    """The plan's tree lists are uploaded again; the walk they index is not."""
+    js, x, y, want, counts = shared_walk()
+    d = capi.DMatrix(x, missing=SHARED_MISSING)
+    b = capi.Booster(model_buffer=js)
+    count(b, d)
+    b.set_param("ohx_visits_kernel", "lds")
+    refit_is_the_restatement(b, d, y, want, tmp_path, "refit after the knob")
+    got, seen = count(b, d)
+    assert seen == 260
+    V.assert_same_counts(got, [c * np.uint64(2) for c in counts], "two counts, the knob between them")
+    b.free()
+    d.free()
+
+
+def test_a_model_load_drops_the_shared_walk(torch_cuda, tmp_path):
+    js, x, y, want, counts = shared_walk()
+    js2, x2, y2, want2, counts2 = shared_walk(5, 3)
+    assert len(V.doc_trees(js2)) != len(V.doc_trees(js))
+    assert sum(len(v) for v in want2["value"]) != sum(len(v) for v in want["value"])
+    d = capi.DMatrix(x, missing=SHARED_MISSING)
+    b = capi.Booster(model_buffer=js)
+    count(b, d)
+    refit_is_the_restatement(b, d, y, want, tmp_path, "the first model")
+    d.free()
+    b.load_model_buffer(js2)
+    d = capi.DMatrix(x2, missing=SHARED_MISSING)
+    refit_is_the_restatement(b, d, y2, want2, tmp_path, "the second model")
+    got, seen = count(b, d)
+    assert seen == 130
+    V.assert_same_counts(got, counts2, "the second model")
+    b.free()
+    d.free()
+
+
+def test_a_device_move_rebuilds_the_walk_and_both_states(torch_cuda, tmp_path):
+    torch = torch_cuda
+    if capi.device_count() < 2:
+        pytest.skip("one HIP device: nowhere to move the booster")
+    js, x, y, want, counts = shared_walk()
+    twice = R.refit(R.with_leaves(js, want["value"], want["base_weight"]), x, SHARED_MISSING, y, 0.5, 1.0, 0)
+    d = capi.DMatrix(x, missing=SHARED_MISSING)
+    b = capi.Booster(model_buffer=js)
+    count(b, d)
+    refit_is_the_restatement(b, d, y, want, tmp_path, "device 0")
+    d.free()
+    b.set_param("ohx_device", 1)
+    try:
+        torch.cuda.set_device(1)                            # a matrix is copied to the current device
+        d = capi.DMatrix(x, missing=SHARED_MISSING)
+        got, seen = count(b, d)                             # the counters did not move with it
+        assert seen == 130
+        V.assert_same_counts(got, counts, "device 1")
+        refit_is_the_restatement(b, d, y, twice, tmp_path, "device 1")
+    finally:
+        d.free()
+        b.free()
+        torch.cuda.set_device(0)
+
+
 # ---- all or nothing ----
 
 def test_bad_labels_are_refused_with_the_forest_untouched_and_the_next_refit_succeeds(torch_cuda, tmp_path):

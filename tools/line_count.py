@@ -7,7 +7,7 @@ gridcells spread over the lower 52 levels of the C360 batch (tests/analysis/quad
 file predicted 39.1 tag look-ups per gather for the shipped lane order against 38.4 measured
 (TCP_TOTAL_CACHE_ACCESSES per vector-memory instruction); the look-ups this counter reports for super_pack 0 on the same
 bricks are its calibration.  The lines of a BLOCK need neighbours, so every brick is also counted together with the 15
-tiles that share its block of 16 in launch order (tiles are numbered brick-i fastest, kernels.hip tile_row).
+tiles that share its block of 16 in launch order (tiles are numbered brick-i fastest, walk_device.hpp tile_row).
 
 The counting is native (csrc/line_count.cpp) and walks with the host walk of the layout tests (csrc/super_walk.hpp).
 usage: python3 tools/line_count.py [--bricks 300] [--trees 100] [--depth 18]      (CPU only, about a minute)"""
