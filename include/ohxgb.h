@@ -527,6 +527,75 @@ int OHXBoosterRefitLeaves(BoosterHandle handle, DMatrixHandle dmat, const float*
 int OHXBoosterRefitLeavesDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels, bst_ulong nlabel,
                                 float eta, float lambda, int unvisited, bst_ulong* leaves_refit, void* stream);
 
+/* Boosting new trees (docs/18_boost_trees.md): `rounds` depth-limited regression trees are fitted, one after another, to
+ * the squared-error gradient of the CALLER's rows and labels with a histogram method on the GPU, and appended to the
+ * forest - what a user with labels does after OHXBoosterRefitLeaves has taken the frozen structure as far as it goes.
+ * Parity with libxgboost's hist updater is NOT claimed: the formulas restate xgboost 1.6.0's CalcGain and CalcWeight
+ * (param.h) with reg_alpha = 0 and max_delta_step = 0; the candidate set and the tie rules are this library's own and
+ * are stated here.  Every bit of the result is defined by integer sums and by double arithmetic in a stated order.
+ * Cuts.  Feature f has ncut_f = cut_ptr[f+1] - cut_ptr[f] cut values c_0 < c_1 < ..., 0 <= ncut_f <= 254, finite and
+ * strictly ascending; cut_ptr has F + 1 entries (F = the booster's num_feature, 1 <= F <= 128) and starts at 0.  A
+ * row's bin for f is b = #{j : c_j <= x}, compared as float32: +inf gives ncut_f, -inf gives 0; NaN, the matrix's
+ * `missing` or a column the matrix lacks gives the missing bin, 255.  Hence x < c_j exactly when b <= j: the float walk
+ * of every predict path partitions rows exactly as the bins do.
+ * OHXQuantileCuts (host only: no device, no booster) makes cuts from a row-major host sample [nrow][ncol] and max_bins
+ * in 2..255.  Per column: (1) the values that are not missing (NaN or == missing) and are finite, sorted ascending,
+ * s_0..s_{n-1}, with distinct values u_0 < ... < u_{m-1}; (2) m <= 1: no cuts; (3) m <= max_bins: the cuts are
+ * u_1..u_{m-1}; (4) otherwise the candidates s[floor(j * n / max_bins)] for j = 1..max_bins-1, deduplicated, with any
+ * equal to u_0 dropped.  (5) It writes cut_ptr (ncol + 1 entries), *needed = the number of cut values, and the values
+ * into cut_values; if more than `cap` are needed it refuses (rc -1) with *needed still set.
+ * Per new tree t, with pred the float32 margin of the forest so far - initially, bit for bit, what
+ * XGBoosterPredict(option_mask = 1) returns:
+ *  1. g = pred - y; q = (int64) rint(g * 2^24): both exactly as steps 3-4 of the refit above, with the same refusal for
+ *     a gradient that is not finite or has |g| >= 256.  At most 2^31 rows.
+ *  2. Nodes are numbered in allocation order: the root is 0; levels d = 0 .. max_depth-1 are processed in turn; within
+ *     a level the open nodes are taken in ascending id; a node that splits gets the next two ids, left = n,
+ *     right = n + 1.
+ *  3. Histograms.  For an open node p, feature f and bin b, Ghist[p][f][b] is the int64 sum of q over the node's rows in
+ *     that bin and Hhist[p][f][b] the count of those rows, the missing bin included.  Integer adds only (no float
+ *     atomics): the sums depend on neither the order of the rows, the launch shape, the form, nor OHXDMatrixSetGrid.
+ *  4. Split choice.  Candidates are (f, j, dl) with j < ncut_f and dl in {0, 1}.
+ *     GL = sum_{b<=j} Ghist[b] + (dl ? Ghist[missing] : 0), HL likewise, GR = Gp - GL, HR = Hp - HL, in integers.  A
+ *     candidate is valid when HL >= min_child_rows and HR >= min_child_rows (min_child_rows >= 1).  In double, with
+ *     Gd = (double)G * 2^-24: gain(G, H) = (Gd * Gd) / ((double)H + (double)lambda) and
+ *     loss_chg = (gain(L) + gain(R)) - gain(P); no fused multiply-add.  The best candidate is the largest loss_chg,
+ *     compared as doubles; exact ties go to the lexicographically smallest (f, j, dl) - so the default is right whenever
+ *     the node holds no missing value of f.  The node splits when a valid candidate exists and best > (double)gamma
+ *     (gamma >= 0).
+ *  5. Node records.  A split stores feature = f, value = c_j, default_left = dl, loss_chg = (float)best.  Every node
+ *     stores sum_hess = (float)Hp and base_weight = w = (float)( -((double)Gp * 2^-24) / ((double)Hp + (double)lambda) ),
+ *     the refit's step 5.  A leaf stores value = w * eta (one float32 multiply), loss_chg = 0, feature = 0 and
+ *     default_left = 0.  parent holds the file's left-child bit (bit 31; the root is -1); leaf_child_cnt is 0, deleted is
+ *     0, and there are no categorical arrays.  A node with Hp < 2 * min_child_rows, or one at max_depth, is a leaf
+ *     without evaluation.
+ *  6. pred += leaf(row), one float32 add per row.  tree_info gets 0.
+ * *nodes_added (may be NULL) receives the total number of nodes over the new trees.
+ * All or nothing: the forest is extended only after every round is done and the device's error word has been read back
+ * clean.  On success everything built from the forest is dropped as a model load drops it: the flattened device
+ * forests, the contributions state, the refit state, and the visit state WITH its counters (the leaf numbering has
+ * changed); a graph captured earlier is stale.  XGBoosterSaveModel writes the longer forest in all three formats, and
+ * contributions work at once: the new trees carry covers.
+ * Refused, with the forest untouched: no model (a loaded model with 0 trees is accepted); categorical splits; several
+ * output groups; an objective that is not identity / squared error; NULL labels or cuts; no feature, or more than 128
+ * features; rounds < 1; max_depth outside 1..8; eta not finite; lambda or gamma not finite or negative;
+ * min_child_rows < 1; cuts that are not finite or not strictly ascending, or more than 254 for a feature; nlabel != the
+ * matrix's rows, or no rows; more than 2^31 rows; more columns than features; a stream that is being captured (nothing
+ * is enqueued); no usable HIP device (no CPU fallback); a buffer that cannot be allocated (the message says the
+ * bytes); and a gradient out of range at any round (the message says "label").
+ * Both forms wait once, at the end.  The host form stages the labels; the device form takes d_labels in HBM (nlabel
+ * floats, ready on `stream`) and enqueues on `stream`.  The cut arrays are HOST pointers in both forms.  The grow state
+ * (bin planes of F * nrow bytes, row positions, the running margin, the level's histograms, the node records, the
+ * staged labels and cuts) is the booster's own and never a buffer of another path; dropped when a model is loaded, by
+ * an "ohx_device" move and at XGBoosterFree.  Calls on ONE booster must not run concurrently. */
+int OHXBoosterBoostTrees(BoosterHandle handle, DMatrixHandle dmat, const float* labels, bst_ulong nlabel,
+                         const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
+                         float lambda, float gamma, bst_ulong min_child_rows, bst_ulong* nodes_added);
+int OHXBoosterBoostTreesDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels, bst_ulong nlabel,
+                               const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
+                               float lambda, float gamma, bst_ulong min_child_rows, bst_ulong* nodes_added, void* stream);
+int OHXQuantileCuts(const float* data, bst_ulong nrow, bst_ulong ncol, float missing, int max_bins, bst_ulong* cut_ptr,
+                    float* cut_values, bst_ulong cap, bst_ulong* needed);
+
 /* The whole of predict_OH_with_XGB's RUN section in one kernel
  * (OH_GridCompMod.F90:303-383): gathers the 27 MAPL fields in place (field f is
  * (im,jm,km) Fortran order, or (im,jm) when is2d[f] != 0; feature order of

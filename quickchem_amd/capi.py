@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "OHXBoosterPredictContribsFields", "OHXBoosterPredictContribsFieldsDevice",
     "OHXBoosterCountVisits", "OHXBoosterCountVisitsDevice", "OHXBoosterGetVisitCounts", "OHXBoosterResetVisitCounts",
     "OHXBoosterRefreshCover", "OHXBoosterRefitLeaves", "OHXBoosterRefitLeavesDevice",
+    "OHXBoosterBoostTrees", "OHXBoosterBoostTreesDevice", "OHXQuantileCuts",
     "OHXSelectCells", "OHXSelectCellsDevice", "OHXGatherCells", "OHXGatherCellsDevice",
     "OHXScatterCells", "OHXScatterCellsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
@@ -137,6 +138,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.OHXBoosterRefreshCover.argtypes = [vp, vp, f32]
     lib.OHXBoosterRefitLeaves.argtypes = [vp, vp, vp, u64, f32, f32, i32, C.POINTER(u64)]
     lib.OHXBoosterRefitLeavesDevice.argtypes = [vp, vp, vp, u64, f32, f32, i32, C.POINTER(u64), vp]
+    lib.OHXBoosterBoostTrees.argtypes = [vp, vp, vp, u64, vp, vp, i32, i32, f32, f32, f32, u64, C.POINTER(u64)]
+    lib.OHXBoosterBoostTreesDevice.argtypes = [vp, vp, vp, u64, vp, vp, i32, i32, f32, f32, f32, u64, C.POINTER(u64), vp]
+    lib.OHXQuantileCuts.argtypes = [vp, u64, u64, f32, i32, vp, vp, u64, C.POINTER(u64)]
     lib.OHXBoosterPredictFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32,
                                             f32, i32, f32, vp, vp]
     i64 = C.c_int64
@@ -447,6 +451,41 @@ class Booster:
         check(self.lib, self.lib.OHXBoosterRefitLeavesDevice(self.handle, dmat.handle, labels_ptr, nlabel, eta,
                                                               reg_lambda, self.REFIT_UNVISITED[unvisited], C.byref(n),
                                                               stream or None))
+        return int(n.value)
+
+    @staticmethod
+    def _cuts(cuts):
+        cut_ptr, cut_values = cuts
+        cut_ptr = np.ascontiguousarray(cut_ptr, dtype=np.uint64).reshape(-1)
+        cut_values = np.ascontiguousarray(cut_values, dtype=np.float32).reshape(-1)
+        if cut_values.size == 0:
+            cut_values = np.zeros(1, dtype=np.float32)      # (a pointer that is not NULL)
+        return cut_ptr, cut_values
+
+    def boost_trees(self, dmat: DMatrix, labels, cuts, rounds: int = 1, max_depth: int = 6, eta: float = 0.3,
+                    reg_lambda: float = 1.0, gamma: float = 0.0, min_child_rows: int = 1) -> int:
+        """OHXBoosterBoostTrees: `rounds` trees of depth <= max_depth are fitted on the GPU to the squared-error gradient
+        of the rows of `dmat` and `labels`, from histograms over `cuts` = (cut_ptr, cut_values) (quantile_cuts makes
+        them), and appended to the forest.  All or nothing; returns the number of nodes added."""
+        y = np.ascontiguousarray(labels, dtype=np.float32).reshape(-1)
+        cut_ptr, cut_values = self._cuts(cuts)
+        n = C.c_uint64()
+        check(self.lib, self.lib.OHXBoosterBoostTrees(self.handle, dmat.handle, y.ctypes.data, y.size, cut_ptr.ctypes.data,
+                                                       cut_values.ctypes.data, rounds, max_depth, eta, reg_lambda, gamma,
+                                                       min_child_rows, C.byref(n)))
+        return int(n.value)
+
+    def boost_trees_device(self, dmat: DMatrix, labels_ptr: int, nlabel: int, cuts, rounds: int = 1, max_depth: int = 6,
+                           eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0, min_child_rows: int = 1,
+                           stream: int = 0) -> int:
+        """The same with the labels in device memory (labels_ptr: a torch data_ptr() of nlabel float32, ready on
+        `stream`; the cuts stay host arrays); enqueues on `stream` and waits for it once at the end (not capturable)."""
+        cut_ptr, cut_values = self._cuts(cuts)
+        n = C.c_uint64()
+        check(self.lib, self.lib.OHXBoosterBoostTreesDevice(self.handle, dmat.handle, labels_ptr, nlabel,
+                                                             cut_ptr.ctypes.data, cut_values.ctypes.data, rounds,
+                                                             max_depth, eta, reg_lambda, gamma, min_child_rows,
+                                                             C.byref(n), stream or None))
         return int(n.value)
 
     def predict_fields(self, fields: Sequence[np.ndarray], is2d: Sequence[bool], pl_feature: int, im: int, jm: int,
@@ -793,6 +832,22 @@ def scatter_cells_device(values_ptr: int, stride: int, col: int, cells_ptr: int,
 
 
 UNIQUE_ID_BYTES = 128
+
+
+def quantile_cuts(x, missing: float = float("nan"), max_bins: int = 255, lib: Optional[C.CDLL] = None):
+    """OHXQuantileCuts (host only) -> (cut_ptr uint64 [ncol + 1], cut_values float32): per column of the row-major
+    sample `x` at most max_bins - 1 ascending cut values, what Booster.boost_trees takes as `cuts`."""
+    lib = lib or load_library()
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    assert x.ndim == 2
+    nrow, ncol = x.shape
+    cut_ptr = np.zeros(ncol + 1, dtype=np.uint64)
+    cap = ncol * (max_bins - 1) if 2 <= max_bins <= 255 else 0
+    values = np.zeros(max(cap, 1), dtype=np.float32)
+    needed = C.c_uint64()
+    check(lib, lib.OHXQuantileCuts(x.ctypes.data, nrow, ncol, missing, max_bins, cut_ptr.ctypes.data, values.ctypes.data,
+                                   cap, C.byref(needed)))
+    return cut_ptr, values[:needed.value].copy()
 
 
 def shard_rows(n_total: int, nranks: int, rank: int, lib: Optional[C.CDLL] = None):

@@ -34,6 +34,7 @@
 #include "kernels.hpp"
 #include "visits.hpp"
 #include "refit.hpp"
+#include "grow.hpp"
 
 using namespace ohx;
 
@@ -644,6 +645,38 @@ struct RefitState {
   PinnedBuf<uint32_t> h_error;
 };
 
+// Boosting new trees (OHXBoosterBoostTrees; grow.hpp): the bin planes, the node a row stands on, the running margin, the
+// level's histograms and candidates, the node records of every round and the staged labels and cuts.  Built at the
+// first call on the loaded model; never a buffer of another path.
+struct GrowState {
+  int device = -1;
+  bool prepared = false;
+  DevBuf<uint8_t> d_bins;
+  DevBuf<uint16_t> d_pos;
+  DevBuf<float> d_pred, d_labels, d_cuts;
+  DevBuf<uint32_t> d_cut_ptr, d_tree_nodes, d_saved_flag;
+  DevBuf<unsigned long long> d_Ghist, d_Hhist;
+  DevBuf<GrowCand> d_best;
+  DevBuf<GrowNode> d_nodes;
+  DevBuf<GrowLevelState> d_state;
+  PinnedBuf<GrowNode> h_nodes;
+  PinnedBuf<uint32_t> h_tree_nodes, h_cut_ptr;
+  PinnedBuf<float> h_cuts;
+  PinnedBuf<GrowLevelState> h_state;
+  void release_device() {
+    d_bins.release();
+    d_pos.release();
+    for (DevBuf<float>* f : {&d_pred, &d_labels, &d_cuts}) f->release();
+    for (DevBuf<uint32_t>* f : {&d_cut_ptr, &d_tree_nodes, &d_saved_flag}) f->release();
+    d_Ghist.release();
+    d_Hhist.release();
+    d_best.release();
+    d_nodes.release();
+    d_state.release();
+    prepared = false;
+  }
+};
+
 struct BoosterObj {
   ~BoosterObj() {
     for (hipEvent_t e : {run1_fork, run1_slab, run1_join, run1_clear})
@@ -785,6 +818,7 @@ struct BoosterObj {
                                         // (auto and global: every tree the global way - the faster at C360; same integers)
   uint32_t visits_lds_leaves = 0;       // "ohx_visits_lds_leaves": leaves a block's LDS histogram may hold (0 = what fits)
   std::unique_ptr<RefitState> refit;
+  std::unique_ptr<GrowState> grow;
 };
 
 // the leaf walk with both states that refer to it
@@ -1105,6 +1139,7 @@ void adopt_model(BoosterObj& b, Forest&& f) {
   invalidate_device_state(b);
   b.contribs.reset();
   drop_leaf_walk(b);
+  b.grow.reset();
   b.forest = std::move(f);
   b.num_groups = b.forest.num_groups();
   b.num_cat = b.forest.num_categorical_splits();
@@ -2145,6 +2180,170 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
   }
 }
 
+// ---- boosting new trees (grow.hpp) ----
+
+// Both forms of OHXBoosterBoostTrees.  The refusals that need neither a matrix nor a device come first, in the header's
+// order; nothing is enqueued before the last of them.
+void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulong nlabel, const bst_ulong* cut_ptr,
+                 const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
+                 bst_ulong min_child_rows, bst_ulong* nodes_added, bool host_form, hipStream_t caller, const char* what) {
+  const std::string w0(what);
+  if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
+  refuse_categorical(b, what);
+  refuse_groups(b, what);
+  if (!objective_is_identity(b.forest.objective))
+    throw OhxError(w0 + " fits squared-error trees (gradient pred - label, hessian 1): the objective " + b.forest.objective +
+                   " is not reg:squarederror");
+  if (!b.margin_error.empty()) throw OhxError(b.margin_error);
+  if (labels == nullptr) throw OhxError(w0 + ": labels is NULL");
+  if (cut_ptr == nullptr || cut_values == nullptr) throw OhxError(w0 + ": the cuts are NULL");
+  const uint32_t F = b.forest.num_feature;
+  if (F == 0 || F > kGrowMaxFeatures)
+    throw OhxError(w0 + ": the booster has " + std::to_string(F) + " features; 1 to 128 are binned (their cuts are staged in LDS)");
+  if (rounds < 1) throw OhxError(w0 + ": rounds must be >= 1");
+  if (max_depth < 1 || max_depth > kGrowMaxDepth) throw OhxError(w0 + ": max_depth must be in 1..8");
+  if (!std::isfinite(eta)) throw OhxError(w0 + ": eta must be finite");
+  if (!(std::isfinite(lambda) && lambda >= 0.0f)) throw OhxError(w0 + ": lambda must be finite and >= 0");
+  if (!(std::isfinite(gamma) && gamma >= 0.0f)) throw OhxError(w0 + ": gamma must be finite and >= 0");
+  if (min_child_rows < 1) throw OhxError(w0 + ": min_child_rows must be >= 1");
+  grow_check_cuts(cut_ptr, cut_values, F, what);
+  DMatrixObj& d = *as_dmat(dmat);
+  if (d.nrow == 0) throw OhxError(w0 + ": the matrix has no rows");
+  if (nlabel != d.nrow) throw OhxError(w0 + ": " + std::to_string(nlabel) + " labels for " + std::to_string(d.nrow) + " rows");
+  if (d.nrow > kRefitMaxRows) throw OhxError(w0 + ": at most 2^31 rows per call (" + std::to_string(d.nrow) + " given)");
+  check_columns(b, d.ncol);
+  // before anything is built or enqueued: building the state waits for the library's stream
+  if (!host_form && stream_capturing(caller))
+    refuse_in_capture("grow trees", (w0 + " is not capturable; call it outside the capture").c_str());
+  ensure_uploaded(b);                      // throws where there is no device; the initial margin is a margin predict
+  const DeviceInfo dev = b.dev;
+  check_same_device(d, dev.ordinal);
+  if (!b.grow) b.grow = std::make_unique<GrowState>();
+  GrowState& g = *b.grow;
+  if (g.device != dev.ordinal) {
+    g.release_device();                    // (what was left on another device)
+    g.device = dev.ordinal;
+  }
+  if (!g.prepared) {
+    HIP_CHECK((hipError_t)prepare_grow());
+    g.prepared = true;
+  }
+  const uint64_t n = d.nrow, ncuts = cut_ptr[F];
+  const size_t R = (size_t)rounds;
+  const GrowPlan plan = plan_grow(n, F, ncuts, max_depth, dev.num_cus);
+  auto room = [&](auto& buf, size_t count, size_t elem, const char* name) {
+    try {
+      buf.ensure(count);
+    } catch (const OhxError& e) {
+      throw OhxError(w0 + ": " + name + " of " + std::to_string((uint64_t)count * elem) + " bytes cannot be allocated (" + e.what() + ")");
+    }
+  };
+  room(g.d_bins, (size_t)plan.bins_bytes, 1, "the bin planes (features x rows)");
+  room(g.d_pos, n, 2, "the row positions");
+  room(g.d_pred, n, 4, "the running margin");
+  if (host_form) room(g.d_labels, n, 4, "the staged labels");
+  room(g.d_Ghist, (size_t)(plan.hist_bytes / 16), 8, "the gradient histograms");
+  room(g.d_Hhist, (size_t)(plan.hist_bytes / 16), 8, "the count histograms");
+  room(g.d_best, (size_t)(1u << (max_depth - 1)) * F, sizeof(GrowCand), "the split candidates");
+  room(g.d_nodes, R * kGrowMaxNodes, sizeof(GrowNode), "the node records");
+  g.d_tree_nodes.ensure(R);
+  g.d_cuts.ensure(std::max<size_t>(ncuts, 1));
+  g.d_cut_ptr.ensure(F + 1);
+  g.d_state.ensure(1);
+  g.d_saved_flag.ensure(1);
+  g.h_nodes.ensure(R * kGrowMaxNodes);
+  g.h_tree_nodes.ensure(R);
+  g.h_cuts.ensure(std::max<size_t>(ncuts, 1));
+  g.h_cut_ptr.ensure(F + 1);
+  g.h_state.ensure(1);
+  for (uint32_t f = 0; f <= F; ++f) g.h_cut_ptr.p[f] = (uint32_t)cut_ptr[f];
+  if (ncuts) memcpy(g.h_cuts.p, cut_values, ncuts * sizeof(float));
+  hipStream_t stream = host_form ? lib_streams(dev.ordinal).exec : caller;
+  if (host_form && d.owned == nullptr) order_behind_caller(dev.ordinal, stream);
+  // every earlier call has been waited for, so the buffers are free
+  HIP_CHECK(hipMemcpyAsync(g.d_cut_ptr.p, g.h_cut_ptr.p, (F + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+  if (ncuts) HIP_CHECK(hipMemcpyAsync(g.d_cuts.p, g.h_cuts.p, ncuts * sizeof(float), hipMemcpyHostToDevice, stream));
+  HIP_CHECK(hipMemsetAsync(g.d_state.p, 0, sizeof(GrowLevelState), stream));
+  HIP_CHECK(hipMemsetAsync(g.d_tree_nodes.p, 0, R * sizeof(uint32_t), stream));
+  HIP_CHECK(hipMemsetAsync(g.d_pos.p, 0, n * sizeof(uint16_t), stream));
+  if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_labels.p, labels, n * sizeof(float), hipMemcpyHostToDevice, stream));
+  // The margin of the forest so far, by the predict path.  Its kernels raise the booster's sticky inf flag for +-inf in
+  // a device matrix; bins take +-inf as the floats they are, so the flag word is put back as it was.
+  if (b.forest.trees.empty()) {
+    uint32_t base_bits = 0;
+    memcpy(&base_bits, &b.margin_base, sizeof base_bits);
+    HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g.d_pred.p), (int)base_bits, (size_t)n, stream));
+  } else {
+    HIP_CHECK(hipMemcpyAsync(g.d_saved_flag.p, b.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    launch_predict_checked(b, d, 1, 0, g.d_pred.p, stream);
+    HIP_CHECK(hipMemcpyAsync(b.d_flags.p, g.d_saved_flag.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+  }
+  GrowArgs a;
+  a.rows = d.d_data;
+  a.nrow = n;
+  a.ncol = (uint32_t)d.ncol;
+  a.num_feature = F;
+  a.missing = d.missing;
+  a.labels = host_form ? g.d_labels.p : labels;
+  a.cut_ptr = g.d_cut_ptr.p;
+  a.cuts = g.d_cuts.p;
+  a.ncuts = (uint32_t)ncuts;
+  a.bins = g.d_bins.p;
+  a.pos = g.d_pos.p;
+  a.pred = g.d_pred.p;
+  a.Ghist = g.d_Ghist.p;
+  a.Hhist = g.d_Hhist.p;
+  a.best = g.d_best.p;
+  a.nodes = g.d_nodes.p;
+  a.tree_nodes = g.d_tree_nodes.p;
+  a.state = g.d_state.p;
+  a.max_depth = max_depth;
+  a.eta = eta;
+  a.lambda = lambda;
+  a.gamma = gamma;
+  a.min_child_rows = min_child_rows;
+  hipError_t launched = (hipError_t)launch_grow_bin(a, plan, stream);
+  for (uint32_t r = 0; launched == hipSuccess && r < (uint32_t)rounds; ++r) launched = (hipError_t)launch_grow_tree(a, plan, r, stream);
+  if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_nodes.p, g.d_nodes.p, R * kGrowMaxNodes * sizeof(GrowNode), hipMemcpyDeviceToHost, stream);
+  if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_tree_nodes.p, g.d_tree_nodes.p, R * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
+  if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_state.p, g.d_state.p, sizeof(GrowLevelState), hipMemcpyDeviceToHost, stream);
+  // both forms wait, whatever was enqueued: the labels and the records are read from the caller's and the state's memory
+  const hipError_t waited = hipStreamSynchronize(stream);
+  if (!host_form) d.used_async = true;
+  HIP_CHECK(launched);
+  HIP_CHECK(waited);
+  const uint32_t flags = g.h_state.p->error;
+  if (flags & kGrowFlagLabel)
+    throw OhxError(w0 + ": a gradient pred - label is not finite or reaches 256 in size at some row and round: look for a "
+                   "label that is NaN, infinite or far from the model's range; the forest is unchanged");
+  if (flags != 0) throw OhxError(w0 + ": the grow kernels reported error flags " + std::to_string(flags));
+  // all or nothing: every round is done and the error word is clean
+  std::vector<Tree> grown;
+  bst_ulong added = 0;
+  for (size_t r = 0; r < R; ++r) {
+    grown.push_back(grow_assemble_tree(g.h_nodes.p + r * kGrowMaxNodes, g.h_tree_nodes.p[r], F));
+    added += g.h_tree_nodes.p[r];
+  }
+  const size_t T0 = b.forest.trees.size();
+  for (Tree& t : grown) {
+    b.forest.trees.push_back(std::move(t));
+    b.forest.tree_info.push_back(0);
+  }
+  try {
+    b.forest.validate();
+  } catch (...) {
+    b.forest.trees.resize(T0);
+    b.forest.tree_info.resize(T0);
+    throw;
+  }
+  // everything built from the forest is dropped as a model load drops it; the leaf numbering has changed, so the visit
+  // state goes with its counters
+  invalidate_device_state(b);
+  b.contribs.reset();
+  drop_leaf_walk(b);
+  if (nodes_added != nullptr) *nodes_added = added;
+}
+
 }  // namespace
 
 // =================================================================== C ABI
@@ -2549,6 +2748,7 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
     if (k != b->device_pref) {
       invalidate_device_state(*b);
       drop_leaf_walk(*b);              // the visit counts live on the device they were counted on
+      b->grow.reset();
     }
     b->device_pref = k;
   }
@@ -2742,6 +2942,41 @@ int OHXBoosterRefitLeavesDevice(BoosterHandle handle, DMatrixHandle dmat, const 
   BoosterObj* b = as_booster(handle);
   refit_leaves(*b, dmat, d_labels, nlabel, eta, lambda, unvisited, leaves_refit, false, static_cast<hipStream_t>(stream),
                "OHXBoosterRefitLeavesDevice");
+  API_END();
+}
+
+int OHXBoosterBoostTrees(BoosterHandle handle, DMatrixHandle dmat, const float* labels, bst_ulong nlabel,
+                         const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
+                         float lambda, float gamma, bst_ulong min_child_rows, bst_ulong* nodes_added) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  boost_trees(*b, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows,
+              nodes_added, true, nullptr, "OHXBoosterBoostTrees");
+  API_END();
+}
+
+int OHXBoosterBoostTreesDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels, bst_ulong nlabel,
+                               const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
+                               float lambda, float gamma, bst_ulong min_child_rows, bst_ulong* nodes_added, void* stream) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows,
+              nodes_added, false, static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesDevice");
+  API_END();
+}
+
+int OHXQuantileCuts(const float* data, bst_ulong nrow, bst_ulong ncol, float missing, int max_bins, bst_ulong* cut_ptr,
+                    float* cut_values, bst_ulong cap, bst_ulong* needed) {
+  API_BEGIN();
+  if (cut_ptr == nullptr || needed == nullptr) throw OhxError("OHXQuantileCuts: NULL output argument");
+  if (data == nullptr && nrow * ncol != 0) throw OhxError("OHXQuantileCuts: data is NULL");
+  if (cut_values == nullptr && cap != 0) throw OhxError("OHXQuantileCuts: cut_values is NULL");
+  if (max_bins < 2 || max_bins > 255) throw OhxError("OHXQuantileCuts: max_bins must be in 2..255");
+  static_assert(sizeof(bst_ulong) == sizeof(uint64_t), "bst_ulong is uint64");
+  *needed = quantile_cuts(data, nrow, ncol, missing, max_bins, reinterpret_cast<uint64_t*>(cut_ptr), cut_values, cap);
+  if (*needed > cap)
+    throw OhxError("OHXQuantileCuts: " + std::to_string(*needed) + " cut values are needed and cut_values holds " +
+                   std::to_string(cap));
   API_END();
 }
 

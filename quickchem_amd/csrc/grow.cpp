@@ -1,0 +1,144 @@
+// Host side of the tree grower (grow.hpp): the quantile cuts, the cut checks, the split choice of one node over its
+// features, the assembly of a Tree from the device's node records and the launch plan.  No device code: libohx_synth.so
+// links it too, for the tests that need no GPU.
+#include "grow.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <string>
+
+namespace ohx {
+
+uint64_t quantile_cuts(const float* data, uint64_t nrow, uint64_t ncol, float missing, int max_bins, uint64_t* cut_ptr,
+                       float* cut_values, uint64_t cap) {
+  const bool missing_is_nan = missing != missing;
+  uint64_t total = 0;
+  std::vector<float> s, cuts;
+  cut_ptr[0] = 0;
+  for (uint64_t c = 0; c < ncol; ++c) {
+    s.clear();
+    for (uint64_t r = 0; r < nrow; ++r) {
+      const float v = data[r * ncol + c];
+      if (v != v || (!missing_is_nan && v == missing) || !std::isfinite(v)) continue;
+      s.push_back(v);
+    }
+    std::sort(s.begin(), s.end());
+    cuts.clear();
+    const uint64_t n = s.size();
+    uint64_t m = 0;
+    for (uint64_t i = 0; i < n; ++i)
+      if (i == 0 || s[i] != s[i - 1]) ++m;
+    if (m >= 2 && m <= (uint64_t)max_bins) {
+      for (uint64_t i = 1; i < n; ++i)
+        if (s[i] != s[i - 1]) cuts.push_back(s[i]);
+    } else if (m > (uint64_t)max_bins) {
+      for (uint64_t j = 1; j < (uint64_t)max_bins; ++j) {
+        const float v = s[(size_t)(j * n / (uint64_t)max_bins)];
+        if (v == s[0] || (!cuts.empty() && v == cuts.back())) continue;
+        cuts.push_back(v);
+      }
+    }
+    for (size_t i = 0; i < cuts.size(); ++i)
+      if (total + i < cap) cut_values[total + i] = cuts[i];
+    total += cuts.size();
+    cut_ptr[c + 1] = total;
+  }
+  return total;
+}
+
+void grow_check_cuts(const uint64_t* cut_ptr, const float* cut_values, uint32_t num_feature, const char* what) {
+  if (cut_ptr[0] != 0) throw OhxError(std::string(what) + ": cut_ptr[0] must be 0");
+  for (uint32_t f = 0; f < num_feature; ++f) {
+    if (cut_ptr[f + 1] < cut_ptr[f]) throw OhxError(std::string(what) + ": cut_ptr must not descend (feature " + std::to_string(f) + ")");
+    const uint64_t n = cut_ptr[f + 1] - cut_ptr[f];
+    if (n > kGrowMaxCuts)
+      throw OhxError(std::string(what) + ": feature " + std::to_string(f) + " has " + std::to_string(n) +
+                     " cuts; at most 254 fit the uint8 bins");
+    for (uint64_t j = cut_ptr[f]; j < cut_ptr[f + 1]; ++j) {
+      if (!std::isfinite(cut_values[j]))
+        throw OhxError(std::string(what) + ": the cuts of feature " + std::to_string(f) + " are not all finite");
+      if (j > cut_ptr[f] && !(cut_values[j - 1] < cut_values[j]))
+        throw OhxError(std::string(what) + ": the cuts of feature " + std::to_string(f) + " are not strictly ascending");
+    }
+  }
+}
+
+GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr, int64_t Gp,
+                         uint64_t Hp, float lambda, uint64_t min_child_rows) {
+  GrowCand best;
+  for (uint32_t f = 0; f < num_feature; ++f) {
+    const int64_t* g = G + (size_t)f * kGrowBins;
+    const uint64_t* h = H + (size_t)f * kGrowBins;
+    const uint32_t ncut = (uint32_t)(cut_ptr[f + 1] - cut_ptr[f]);
+    const GrowCand c = grow_best_split(g, h, f, 0, ncut, ncut, 0, 0, g[kGrowMissingBin], h[kGrowMissingBin], Gp, Hp,
+                                       (double)lambda, min_child_rows);
+    if (grow_better(c, best)) best = c;
+  }
+  return best;
+}
+
+Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature) {
+  if (n == 0 || n > kGrowMaxNodes || n % 2 == 0) throw OhxError("grown tree: " + std::to_string(n) + " nodes is not a tree");
+  Tree t;
+  t.resize(n);
+  t.num_feature = (int32_t)num_feature;
+  uint32_t next = 1;
+  for (uint32_t i = 0; i < n; ++i) {
+    const GrowNode& r = nodes[i];
+    if (r.left >= 0) {
+      // allocation order: a split takes the next two ids
+      if ((uint32_t)r.left != next || r.right != r.left + 1 || (uint32_t)r.right >= n || r.feature >= num_feature)
+        throw OhxError("grown tree: node " + std::to_string(i) + " is out of allocation order");
+      if (nodes[r.left].parent != (int32_t)(i | 0x80000000u) || nodes[r.right].parent != (int32_t)i)
+        throw OhxError("grown tree: the children of node " + std::to_string(i) + " do not name it");
+      next += 2;
+    } else if (r.right != -1) {
+      throw OhxError("grown tree: node " + std::to_string(i) + " has one child");
+    }
+    t.left[i] = r.left;
+    t.right[i] = r.right;
+    t.parent[i] = i == 0 ? -1 : r.parent;
+    t.feature[i] = r.left >= 0 ? r.feature : 0u;
+    t.default_left[i] = r.left >= 0 ? (uint8_t)(r.default_left != 0) : (uint8_t)0;
+    t.value[i] = r.value;
+    t.deleted[i] = 0;
+    t.loss_chg[i] = r.left >= 0 ? r.loss_chg : 0.0f;
+    t.sum_hess[i] = r.sum_hess;
+    t.base_weight[i] = r.base_weight;
+    t.leaf_child_cnt[i] = 0;
+  }
+  if (next != n) throw OhxError("grown tree: " + std::to_string(n) + " records hold " + std::to_string(next) + " nodes");
+  return t;
+}
+
+GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus) {
+  GrowPlan p;
+  const uint64_t cus = num_cus > 0 ? (uint64_t)num_cus : 1;
+  const uint64_t want = (nrow + kGrowBlock - 1) / kGrowBlock, cap = cus * kGrowRowBlocksPerCu;
+  p.row_blocks = (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
+  p.bin_lds_bytes = (uint32_t)(ncuts * sizeof(float));
+  p.bins_bytes = (uint64_t)num_feature * nrow;
+  const uint32_t F = std::max<uint32_t>(num_feature, 1);
+  for (int d = 0; d < max_depth; ++d) {
+    GrowLevelPlan l;
+    l.slots = 1u << d;
+    // all of a level's nodes in one block where they fit, then as many features as LDS still holds: a block reads pos,
+    // pred and the label of every row once per group, and the bins of its own features only
+    l.node_group = std::min(l.slots, kGrowMaxPairs);
+    l.feat_group = std::max(1u, std::min(F, kGrowMaxPairs / l.node_group));
+    l.node_groups = (l.slots + l.node_group - 1) / l.node_group;
+    l.feat_groups = (F + l.feat_group - 1) / l.feat_group;
+    l.feat_group = (F + l.feat_groups - 1) / l.feat_groups;     // the same number of groups, evenly filled
+    l.lds_bytes = l.node_group * l.feat_group * kGrowPairBytes;
+    const uint64_t groups = (uint64_t)l.node_groups * l.feat_groups;
+    const uint64_t hwant = (nrow + kGrowHistBlock - 1) / kGrowHistBlock;
+    const uint64_t hcap = std::max<uint64_t>(1, cus * kGrowHistBlocksPerCu / groups);
+    // (one block's trips stay below kGrowMaxTrips at 2^31 rows whatever the cap: 2^31 / 1024 = 2^21)
+    l.hist_blocks = (uint32_t)std::max<uint64_t>(1, std::min(hwant, hcap));
+    p.levels.push_back(l);
+    p.hist_bytes = (uint64_t)l.slots * F * kGrowBins * 16;
+  }
+  return p;
+}
+
+}  // namespace ohx

@@ -1,0 +1,186 @@
+// Boosting new trees (include/ohxgb.h OHXBoosterBoostTrees; design in docs/18_boost_trees.md): `rounds` depth-limited
+// regression trees are fitted, level by level, to the squared-error gradient of the caller's rows and labels and
+// appended to the forest.  The rows are binned once against the caller's cuts (uint8, feature-major planes); a level's
+// gradient histograms are integer sums kept in LDS and flushed with 64-bit global adds; a split is chosen from the
+// histograms by a total order (largest loss_chg, then the smallest (feature, cut, default-left)), so that the result
+// depends on neither the order of the rows nor the launch shape.  The gradient is the refit's 2^-24 fixed point and the
+// leaf solve is refit_solve_leaf itself (refit.hpp).
+//
+// What host and device share is in this header: the gain, the comparison of two candidates, the scan of one feature's
+// bins, and the launch plan.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "refit.hpp"
+
+#define OHX_GROW_HD OHX_REFIT_HD
+
+namespace ohx {
+
+constexpr uint32_t kGrowBins = 256;            // bins per (node, feature): 0 .. ncut, and the missing bin
+constexpr uint32_t kGrowMissingBin = 255;
+constexpr uint32_t kGrowMaxCuts = 254;         // per feature
+constexpr uint32_t kGrowMaxFeatures = 128;     // the cuts of all features fit LDS: 128 x 254 floats
+constexpr int kGrowMaxDepth = 8;
+constexpr uint32_t kGrowMaxNodes = 512;        // node records kept per tree (a tree of depth 8 has at most 511)
+constexpr uint32_t kGrowFlagLabel = 1u;        // the error word: a gradient out of range (refit.hpp kRefitFlagLabel)
+constexpr uint32_t kGrowFlagState = 2u;        // a node id or a bin outside its table (never, from sound buffers)
+
+// gain(G, H) of the header: CalcGain of xgboost 1.6.0 with reg_alpha = 0 and max_delta_step = 0, on the fixed-point sum
+OHX_GROW_HD inline double grow_gain(int64_t G, uint64_t H, double lambda) {
+  const double Gd = (double)G * (1.0 / 16777216.0);
+  return (Gd * Gd) / ((double)H + lambda);
+}
+
+// One candidate.  key orders the candidates of a node: (feature << 9) | (j << 1) | dl
+struct GrowCand {
+  double loss_chg = 0.0;
+  int64_t GL = 0;
+  uint64_t HL = 0;
+  uint32_t key = 0;
+  uint32_t valid = 0;
+};
+OHX_GROW_HD inline uint32_t grow_key(uint32_t f, uint32_t j, uint32_t dl) { return (f << 9) | (j << 1) | dl; }
+
+// The header's total order: a is taken over b when it is valid and b is not, when its loss_chg is larger (compared as
+// doubles), or when they are equal and its key is smaller.  Associative and commutative as a reduction: the winner does
+// not depend on who arrives first.
+OHX_GROW_HD inline bool grow_better(const GrowCand& a, const GrowCand& b) {
+  if (!a.valid) return false;
+  if (!b.valid) return true;
+  if (a.loss_chg > b.loss_chg) return true;
+  if (a.loss_chg < b.loss_chg) return false;
+  return a.key < b.key;
+}
+
+// The best candidate among cuts j0 .. j0 + n - 1 (those below ncut) of feature f.  G / H point at bin j0; GLb / HLb
+// are the sums over the bins below j0; Gm / Hm the missing bin; Gp / Hp the node.  Candidates are visited in ascending
+// (j, dl) and replaced only by a strictly better one.  The host calls it with j0 = 0, n = ncut; a lane of
+// grow_split_kernel with its four bins.
+OHX_GROW_HD inline GrowCand grow_best_split(const int64_t* G, const uint64_t* H, uint32_t f, uint32_t j0, uint32_t n,
+                                            uint32_t ncut, int64_t GLb, uint64_t HLb, int64_t Gm, uint64_t Hm, int64_t Gp,
+                                            uint64_t Hp, double lambda, uint64_t min_child_rows) {
+  GrowCand best;
+  const double parent = grow_gain(Gp, Hp, lambda);
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t j = j0 + k;
+    GLb += G[k];
+    HLb += H[k];
+    if (j >= ncut) continue;
+    for (uint32_t dl = 0; dl < 2; ++dl) {
+      GrowCand c;
+      c.GL = dl ? GLb + Gm : GLb;
+      c.HL = dl ? HLb + Hm : HLb;
+      const int64_t GR = Gp - c.GL;
+      const uint64_t HR = Hp - c.HL;
+      if (c.HL < min_child_rows || HR < min_child_rows) continue;
+      c.loss_chg = (grow_gain(c.GL, c.HL, lambda) + grow_gain(GR, HR, lambda)) - parent;
+      c.key = grow_key(f, j, dl);
+      c.valid = 1;
+      if (grow_better(c, best)) best = c;
+    }
+  }
+  return best;
+}
+
+// A node as the device leaves it.  Children are written as leaves when their parent splits and overwritten if they
+// split in turn, so every record is complete whenever the level loop stops.
+struct GrowNode {
+  int64_t G;            // the node's sums
+  uint64_t H;
+  int32_t left, right;  // -1: a leaf
+  int32_t parent;       // the file's form: bit 31 = left child, root = -1
+  uint32_t feature;
+  uint32_t cut;         // j of the split (device only: the partition compares bins with it)
+  uint32_t default_left;
+  float value;          // c_j, or the leaf value
+  float loss_chg, sum_hess, base_weight;
+};
+
+// ---- the host side (grow.cpp) ----
+
+// OHXQuantileCuts of the header.  Returns the number of cut values needed; writes cut_ptr (ncol + 1) always and
+// cut_values when they fit `cap`.
+uint64_t quantile_cuts(const float* data, uint64_t nrow, uint64_t ncol, float missing, int max_bins, uint64_t* cut_ptr,
+                       float* cut_values, uint64_t cap);
+// Throws OhxError(what + ...) unless cut_ptr starts at 0, ascends, holds at most 254 cuts per feature, and the values
+// are finite and strictly ascending within a feature.
+void grow_check_cuts(const uint64_t* cut_ptr, const float* cut_values, uint32_t num_feature, const char* what);
+// The best split of one node over all features from its histograms G / H [num_feature][256] (grow_best_split per
+// feature, ascending, replaced by a strictly better one only).
+GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr, int64_t Gp,
+                         uint64_t Hp, float lambda, uint64_t min_child_rows);
+// A Tree of the forest from n node records; throws on a record that is not a tree in allocation order.
+Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature);
+
+// ---- the launch plan ----
+
+constexpr uint32_t kGrowBlock = 256;           // bin, split, partition and leaf kernels: a row per lane
+constexpr uint32_t kGrowHistBlock = 1024;      // the histogram kernel: sixteen waves share a block's LDS histogram
+constexpr uint32_t kGrowRowBlocksPerCu = 8;    // the streaming kernels
+constexpr uint32_t kGrowHistBlocksPerCu = 2;   // over all of gridDim.y
+constexpr uint32_t kGrowLdsBytes = 160 * 1024; // a CU's LDS
+constexpr uint32_t kGrowPairBytes = kGrowBins * (8 + 4);          // one (node, feature) histogram in LDS
+constexpr uint32_t kGrowMaxPairs = kGrowLdsBytes / kGrowPairBytes; // 53
+// a block's 32-bit LDS count of a bin cannot overflow: trips x 1024 rows stay below 2^32
+constexpr uint64_t kGrowMaxTrips = (1ull << 22) - 1;
+
+struct GrowLevelPlan {
+  uint32_t slots = 0;         // node slots of the level: 2^d
+  uint32_t node_group = 0;    // node slots per block
+  uint32_t feat_group = 0;    // features per block
+  uint32_t node_groups = 0, feat_groups = 0;   // gridDim.y = node_groups x feat_groups
+  uint32_t hist_blocks = 0;   // gridDim.x: blocks over the rows
+  uint32_t lds_bytes = 0;     // node_group x feat_group x 256 x 12
+};
+struct GrowPlan {
+  uint32_t row_blocks = 0;    // bin, partition and leaf kernels; one trip is row_blocks x 256 rows
+  uint32_t bin_lds_bytes = 0; // the staged cuts
+  std::vector<GrowLevelPlan> levels;   // max_depth entries
+  uint64_t bins_bytes = 0;    // num_feature x nrow
+  uint64_t hist_bytes = 0;    // the deepest level's global histograms: slots x num_feature x 256 x 16
+};
+GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus);
+
+#ifdef __HIPCC__
+struct GrowLevelState {   // one per call, on the device
+  uint32_t begin, end;    // the open nodes of the level at hand: ids [begin, end)
+  uint32_t next;          // the next id to allocate = the tree's nodes so far
+  uint32_t error;         // kGrowFlag*
+};
+struct GrowArgs {
+  // the rows
+  const float* rows = nullptr;     // [nrow][ncol]
+  uint64_t nrow = 0;
+  uint32_t ncol = 0, num_feature = 0;
+  float missing = 0.0f;
+  const float* labels = nullptr;   // [nrow]
+  // the cuts
+  const uint32_t* cut_ptr = nullptr;   // [num_feature + 1]
+  const float* cuts = nullptr;
+  uint32_t ncuts = 0;
+  // the grower's own buffers
+  uint8_t* bins = nullptr;         // [num_feature][nrow]
+  uint16_t* pos = nullptr;         // [nrow] the node a row stands on
+  float* pred = nullptr;           // [nrow] the margin of the forest so far
+  unsigned long long* Ghist = nullptr;   // [slots][num_feature][256] int64 as two's complement
+  unsigned long long* Hhist = nullptr;   // [slots][num_feature][256]
+  GrowCand* best = nullptr;        // [slots][num_feature]
+  GrowNode* nodes = nullptr;       // [rounds][kGrowMaxNodes]
+  uint32_t* tree_nodes = nullptr;  // [rounds] nodes of each tree
+  GrowLevelState* state = nullptr;
+  int max_depth = 0;
+  float eta = 0.0f, lambda = 0.0f, gamma = 0.0f;
+  uint64_t min_child_rows = 1;
+};
+// Once per device before the first launch: the dynamic LDS limits.  Returns a hipError_t.
+int prepare_grow();
+// Enqueues the binning.  bins must be sized by the plan.  Returns a hipError_t.
+int launch_grow_bin(const GrowArgs& a, const GrowPlan& plan, void* stream);
+// Enqueues one tree, round `round`: per level the histogram memsets, the histogram, split and partition kernels, then
+// the leaf kernel (pred += leaf, pos = 0).  pos must be zero and pred the margin so far.  Returns a hipError_t.
+int launch_grow_tree(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
+#endif  // __HIPCC__
+
+}  // namespace ohx

@@ -1,0 +1,118 @@
+// Test support (libohx_synth.so): the host pieces of the tree grower (grow.hpp) without a GPU - the split choice on
+// injected histograms (the shared grow_best_split the split kernel runs per lane), the assembly of a tree from node
+// records appended to a booster and written in a file format, and the launch plan.  The product library runs the same
+// functions of grow.cpp behind OHXBoosterBoostTrees.
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "grow.hpp"
+
+namespace ohx {
+void synth_set_error(const std::string& m);   // synth_host.cpp
+}
+
+using namespace ohx;
+
+// G / H: [num_feature][256].  out: [0] valid, [1] feature, [2] j, [3] default_left, [4] splits (valid and
+// loss_chg > gamma); sums: [0] GL, [1] HL
+extern "C" __attribute__((visibility("default"))) int ohx_grow_node_split(const int64_t* G, const uint64_t* H,
+                                                                         uint32_t num_feature, const uint64_t* cut_ptr,
+                                                                         int64_t Gp, uint64_t Hp, float lambda, float gamma,
+                                                                         uint64_t min_child_rows, double* loss_chg,
+                                                                         uint32_t out[5], int64_t sums[2]) {
+  try {
+    const GrowCand c = grow_node_split(G, H, num_feature, cut_ptr, Gp, Hp, lambda, min_child_rows);
+    *loss_chg = c.loss_chg;
+    out[0] = c.valid;
+    out[1] = c.key >> 9;
+    out[2] = (c.key >> 1) & 255u;
+    out[3] = c.key & 1u;
+    out[4] = c.valid && c.loss_chg > (double)gamma ? 1u : 0u;
+    sums[0] = c.GL;
+    sums[1] = (int64_t)c.HL;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// One tree of n node records, given as arrays, is assembled (grow_assemble_tree) and appended to the booster of
+// `model`; the longer forest comes back in `format` (0 legacy binary, 1 JSON, 2 UBJSON; free with ohx_synth_free).
+extern "C" __attribute__((visibility("default"))) int ohx_grow_append(const void* model, uint64_t len, uint32_t n,
+                                                                     const int32_t* left, const int32_t* right,
+                                                                     const int32_t* parent, const uint32_t* feature,
+                                                                     const uint32_t* default_left, const float* value,
+                                                                     const float* loss_chg, const float* sum_hess,
+                                                                     const float* base_weight, int format, uint8_t** out_buf,
+                                                                     uint64_t* out_len) {
+  try {
+    Forest f = load_model_buffer(model, (size_t)len);
+    f.validate();
+    std::vector<GrowNode> nodes(n);
+    for (uint32_t i = 0; i < n; ++i) {
+      GrowNode& r = nodes[i];
+      r.G = 0;
+      r.H = 0;
+      r.left = left[i];
+      r.right = right[i];
+      r.parent = parent[i];
+      r.feature = feature[i];
+      r.cut = 0;
+      r.default_left = default_left[i];
+      r.value = value[i];
+      r.loss_chg = loss_chg[i];
+      r.sum_hess = sum_hess[i];
+      r.base_weight = base_weight[i];
+    }
+    f.trees.push_back(grow_assemble_tree(nodes.data(), n, f.num_feature));
+    f.tree_info.push_back(0);
+    f.validate();
+    std::vector<uint8_t> b;
+    if (format == 1) {
+      const std::string s = write_json_model(f);
+      b.assign(s.begin(), s.end());
+    } else {
+      b = format == 2 ? write_ubjson_model(f) : write_legacy_binary(f);
+    }
+    *out_buf = (uint8_t*)malloc(b.size() ? b.size() : 1);
+    memcpy(*out_buf, b.data(), b.size());
+    *out_len = b.size();
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// info: [0] blocks of the bin, partition and leaf kernels, [1] rows such a block takes per trip, [2] LDS bytes of the
+// staged cuts, [3] bytes of the bin planes, [4] bytes of the deepest level's global histograms, [5] rows a histogram
+// block takes per trip, [6] (node, feature) histograms a block's LDS holds at most, [7] LDS bytes of one of them.
+// levels: max_depth x 7 = slots, node_group, feat_group, node_groups, feat_groups, hist_blocks, lds_bytes
+extern "C" __attribute__((visibility("default"))) int ohx_grow_plan(uint64_t nrow, uint32_t num_feature, uint64_t ncuts,
+                                                                   int max_depth, int num_cus, uint64_t info[8],
+                                                                   uint64_t* levels) {
+  try {
+    if (max_depth < 1 || max_depth > kGrowMaxDepth) throw OhxError("ohx_grow_plan: max_depth must be in 1..8");
+    const GrowPlan p = plan_grow(nrow, num_feature, ncuts, max_depth, num_cus);
+    info[0] = p.row_blocks;
+    info[1] = kGrowBlock;
+    info[2] = p.bin_lds_bytes;
+    info[3] = p.bins_bytes;
+    info[4] = p.hist_bytes;
+    info[5] = kGrowHistBlock;
+    info[6] = kGrowMaxPairs;
+    info[7] = kGrowPairBytes;
+    for (size_t d = 0; d < p.levels.size(); ++d) {
+      const GrowLevelPlan& l = p.levels[d];
+      const uint64_t v[7] = {l.slots, l.node_group, l.feat_group, l.node_groups, l.feat_groups, l.hist_blocks, l.lds_bytes};
+      memcpy(levels + d * 7, v, sizeof v);
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}

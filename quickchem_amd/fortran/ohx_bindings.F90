@@ -346,6 +346,53 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
+      !  Boosting new trees (include/ohxgb.h; docs/18_boost_trees.md).  Interface blocks only.  labels: nlabel
+      !  real(c_float) on the host; d_labels: their DEVICE address (c_ptr); cut_ptr / cut_values: HOST arrays in both
+      !  forms.  nodes_added: c_loc of an integer(c_int64_t), or c_null_ptr
+      function OHXBoosterBoostTrees(handle, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, &
+            gamma, min_child_rows, nodes_added) bind(C, name="OHXBoosterBoostTrees") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat
+         real(c_float), intent(in)       :: labels(*)
+         integer(c_int64_t), value       :: nlabel
+         integer(c_int64_t), intent(in)  :: cut_ptr(*)
+         real(c_float), intent(in)       :: cut_values(*)
+         integer(c_int), value           :: rounds, max_depth
+         real(c_float), value            :: eta, lambda, gamma
+         integer(c_int64_t), value       :: min_child_rows
+         type(c_ptr), value              :: nodes_added
+         integer(c_int)                  :: rc
+      end function
+
+      function OHXBoosterBoostTreesDevice(handle, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, &
+            lambda, gamma, min_child_rows, nodes_added, stream) bind(C, name="OHXBoosterBoostTreesDevice") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat, d_labels, stream
+         integer(c_int64_t), value       :: nlabel
+         integer(c_int64_t), intent(in)  :: cut_ptr(*)
+         real(c_float), intent(in)       :: cut_values(*)
+         integer(c_int), value           :: rounds, max_depth
+         real(c_float), value            :: eta, lambda, gamma
+         integer(c_int64_t), value       :: min_child_rows
+         type(c_ptr), value              :: nodes_added
+         integer(c_int)                  :: rc
+      end function
+
+      !  data: a row-major host sample (nrow x ncol); cut_ptr: ncol + 1 entries out; needed: the cut values in all
+      function OHXQuantileCuts(data, nrow, ncol, missing, max_bins, cut_ptr, cut_values, cap, needed) &
+            bind(C, name="OHXQuantileCuts") result(rc)
+         import :: c_int, c_float, c_int64_t
+         real(c_float), intent(in)       :: data(*)
+         integer(c_int64_t), value       :: nrow, ncol
+         real(c_float), value            :: missing
+         integer(c_int), value           :: max_bins
+         integer(c_int64_t), intent(out) :: cut_ptr(*)
+         real(c_float), intent(out)      :: cut_values(*)
+         integer(c_int64_t), value       :: cap
+         integer(c_int64_t), intent(out) :: needed
+         integer(c_int)                  :: rc
+      end function
+
       ! ---- part 4 of ohxgb.h: the OH field reassembled on every GPU of a node, for a host that has MPI but no
       !      torch.distributed.  Rank 0 gets the id, MPI_Bcast carries its OHX_UNIQUE_ID_BYTES bytes, every rank
       !      (hipSetDevice done) inits; d_shard / d_full are DEVICE addresses, stream a hipStream_t (c_null_ptr = default)

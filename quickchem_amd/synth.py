@@ -92,6 +92,12 @@ def _load():
         lib.ohx_refit_write_back.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                              C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         lib.ohx_refit_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+        lib.ohx_grow_node_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint64, C.c_float,
+                                            C.c_float, C.c_uint64, C.POINTER(C.c_double), C.c_void_p, C.c_void_p]
+        lib.ohx_grow_append.argtypes = [C.c_void_p, C.c_uint64, C.c_uint32] + [C.c_void_p] * 9 + [
+            C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
+        lib.ohx_grow_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64),
+                                      C.c_void_p]
         _lib = lib
     return _lib
 
@@ -403,6 +409,52 @@ def refit_plan(nrow: int, num_feature: int = NFEAT, ntree: int = 1, num_cus: int
     return {"stage": bool(info[0]), "lds_bytes": int(info[1]), "ids_blocks": int(info[2]), "accum_blocks": int(info[3]),
             "ids_bytes": int(info[4]), "block_rows": int(info[5]), "ids_blocks_per_cu": int(info[6]),
             "accum_blocks_per_cu": int(info[7])}
+
+
+def grow_node_split(G, H, cut_ptr, Gp: int, Hp: int, reg_lambda: float, gamma: float, min_child_rows: int):
+    """csrc/grow.cpp grow_node_split (the shared grow_best_split per feature) on injected histograms G int64 / H uint64
+    [num_feature][256] -> dict: valid, feature, j, default_left, splits, loss_chg (float64), GL, HL."""
+    G = np.ascontiguousarray(G, dtype=np.int64)
+    H = np.ascontiguousarray(H, dtype=np.uint64)
+    cut_ptr = np.ascontiguousarray(cut_ptr, dtype=np.uint64)
+    assert G.shape == H.shape and G.ndim == 2 and G.shape[1] == 256 and cut_ptr.size == G.shape[0] + 1
+    loss = C.c_double()
+    out, sums = np.zeros(5, dtype=np.uint32), np.zeros(2, dtype=np.int64)
+    _check(_load().ohx_grow_node_split(G.ctypes.data, H.ctypes.data, G.shape[0], cut_ptr.ctypes.data, Gp, Hp, reg_lambda,
+                                       gamma, min_child_rows, C.byref(loss), out.ctypes.data, sums.ctypes.data))
+    return {"valid": bool(out[0]), "feature": int(out[1]), "j": int(out[2]), "default_left": int(out[3]),
+            "splits": bool(out[4]), "loss_chg": float(loss.value), "GL": int(sums[0]), "HL": int(sums[1])}
+
+
+def grow_append(image, tree, fmt: str = "json") -> np.ndarray:
+    """csrc/grow.cpp grow_assemble_tree on node records (a dict of the nine arrays left, right, parent, feature,
+    default_left, value, loss_chg, sum_hess, base_weight), appended to the booster of `image`; the longer forest in
+    `fmt` ("binary", "json", "ubj")."""
+    img = _image(image)
+    n = len(tree["left"])
+    arrs = [np.ascontiguousarray(tree[k], dtype=t) for k, t in (
+        ("left", np.int32), ("right", np.int32), ("parent", np.int32), ("feature", np.uint32),
+        ("default_left", np.uint32), ("value", np.float32), ("loss_chg", np.float32), ("sum_hess", np.float32),
+        ("base_weight", np.float32))]
+    assert all(a.size == n for a in arrs)
+    out, m = C.c_void_p(), C.c_uint64()
+    _check(_load().ohx_grow_append(img.ctypes.data, img.nbytes, n, *[a.ctypes.data for a in arrs],
+                                   {"binary": 0, "json": 1, "ubj": 2}[fmt], C.byref(out), C.byref(m)))
+    return _take(out, m.value)
+
+
+def grow_plan(nrow: int, num_feature: int = NFEAT, ncuts: int = 0, max_depth: int = 6, num_cus: int = 256):
+    """csrc/grow.hpp plan_grow -> dict: row_blocks and block_rows (bin, partition and leaf kernels), bin_lds_bytes,
+    bins_bytes, hist_bytes, hist_block_rows, max_pairs, pair_bytes, and levels: per level a dict of slots, node_group,
+    feat_group, node_groups, feat_groups, hist_blocks, lds_bytes."""
+    info = (C.c_uint64 * 8)()
+    lev = np.zeros((max(max_depth, 1), 7), dtype=np.uint64)
+    _check(_load().ohx_grow_plan(nrow, num_feature, ncuts, max_depth, num_cus, info, lev.ctypes.data))
+    names = ("slots", "node_group", "feat_group", "node_groups", "feat_groups", "hist_blocks", "lds_bytes")
+    return {"row_blocks": int(info[0]), "block_rows": int(info[1]), "bin_lds_bytes": int(info[2]),
+            "bins_bytes": int(info[3]), "hist_bytes": int(info[4]), "hist_block_rows": int(info[5]),
+            "max_pairs": int(info[6]), "pair_bytes": int(info[7]),
+            "levels": [dict(zip(names, (int(v) for v in row))) for row in lev]}
 
 
 def cells_plan(n: int, nfield: int = 27):

@@ -1,0 +1,126 @@
+"""Timing of OHXBoosterBoostTreesDevice on the benchmark's synthetic OH booster (100 trees, depth <= 18, as bench.py
+builds it) and the C360 L72 rows resident in HBM.  Labels = the margins of a booster of the same recipe grown from
+another seed, as tools/refit_timing.py takes them.  Run by hand on an MI355X; writes one JSON document (default
+profiles/boost_timing.json).
+
+The cuts come from OHXQuantileCuts on a sample of `--sample` rows copied to the host.  The whole call is timed from the
+host (it waits at its end): a fresh booster's first call, which also allocates the state's buffers, and the second call
+of the same shape on one booster, which finds them, for 1 round and for `--rounds` rounds at `--max-depth`.  The one-off cost
+(binning, the initial margin, the allocations' reuse) is what a 1-round call takes beyond one round's share of the long
+call.  The RMSE against the labels is taken before the call, after a refit, and after the refit plus `--rounds` rounds.
+
+The kernels' own times - the binning, and per level the histogram, split and partition kernels - come from a second
+run of this script under a kernel trace with --reps 1 --rounds 1 (docs/18_boost_trees.md 18.4 says how)."""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from quickchem_amd import capi, synth  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "boost_timing.json"))
+    ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--grid", default="C360", help="a name of synth.GRIDS")
+    ap.add_argument("--label-seed", type=int, default=synth.MODEL_SEED + 1)
+    ap.add_argument("--rounds", type=int, default=10)
+    ap.add_argument("--max-depth", type=int, default=6)
+    ap.add_argument("--eta", type=float, default=0.3)
+    ap.add_argument("--reg-lambda", type=float, default=1.0)
+    ap.add_argument("--max-bins", type=int, default=255)
+    ap.add_argument("--sample", type=int, default=1 << 20)
+    ap.add_argument("--skip-rmse", action="store_true", help="time only (a run under a kernel trace)")
+    args = ap.parse_args()
+    assert torch.cuda.is_available(), "boost_timing needs the MI355X"
+    torch.cuda.set_device(0)
+    model = synth.make_model()
+    teacher = synth.make_model(model_seed=args.label_seed)
+    F = synth.NFEAT
+    grid = synth.GRIDS[args.grid]
+    n = grid[0] * grid[1] * grid[2]
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    rows = torch.empty((n, F), dtype=torch.float32, device="cuda")
+    synth.rows_device(grid, 0, n, rows)
+    stream = torch.cuda.current_stream().cuda_stream
+    d = capi.DMatrix(device_ptr=rows.data_ptr(), nrow=n, ncol=F, missing=synth.XX_MISS)
+    d.set_grid(grid[0], grid[1], 0)
+    # the cuts: quantiles of an evenly strided sample of the rows
+    step = max(1, n // args.sample)
+    t0 = time.perf_counter()
+    sample = rows[::step].cpu().numpy()
+    cuts = capi.quantile_cuts(sample, synth.XX_MISS, args.max_bins)
+    ncuts = int(cuts[0][-1])
+    res = {"model": {"trees": model.num_trees, "nodes": model.num_nodes, "max_depth": model.max_depth}, "rows": n,
+           "plan": synth.grow_plan(n, F, ncuts, args.max_depth, cus), "max_depth": args.max_depth, "eta": args.eta,
+           "reg_lambda": args.reg_lambda, "reps": args.reps, "sample_rows": int(len(sample)), "cut_values": ncuts,
+           "cuts_host_seconds": time.perf_counter() - t0}
+
+    def margins(b):
+        out = torch.empty(n, dtype=torch.float32, device="cuda")
+        b.predict_device(d, out.data_ptr(), stream=stream)
+        torch.cuda.synchronize()
+        b.check()
+        return out
+
+    tb = capi.Booster(model_buffer=teacher.image)
+    labels = margins(tb)
+    tb.free()
+
+    def rmse(b):
+        return float(torch.sqrt(torch.mean((margins(b).double() - labels.double()) ** 2)).item())
+
+    def boost(b, rounds):
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        nodes = b.boost_trees_device(d, labels.data_ptr(), n, cuts, rounds=rounds, max_depth=args.max_depth, eta=args.eta,
+                                     reg_lambda=args.reg_lambda, stream=stream)
+        return time.perf_counter() - t, nodes
+
+    for rounds in sorted({1, args.rounds}):
+        first, again, nodes = [], [], 0
+        for _ in range(args.reps):
+            b = capi.Booster(model_buffer=model.image)
+            dt, nodes = boost(b, rounds)
+            first.append(dt)
+            b.free()
+            # a call that finds its buffers: the second on one booster, continuing from the first
+            b = capi.Booster(model_buffer=model.image)
+            boost(b, rounds)
+            dt, _ = boost(b, rounds)
+            again.append(dt)
+            b.free()
+        res[f"rounds_{rounds}"] = {"first_call_median_s": float(np.median(first)), "median_s": float(np.median(again)),
+                                   "min_s": float(np.min(again)), "max_s": float(np.max(again)), "nodes_added": nodes}
+        print(f"rounds_{rounds}", json.dumps(res[f"rounds_{rounds}"]), flush=True)
+    if args.rounds > 1:
+        per_round = (res[f"rounds_{args.rounds}"]["median_s"] - res["rounds_1"]["median_s"]) / (args.rounds - 1)
+        res["per_round_s"] = per_round
+        res["one_off_s"] = res["rounds_1"]["median_s"] - per_round
+    if not args.skip_rmse:
+        b = capi.Booster(model_buffer=model.image)
+        res["rmse_before"] = rmse(b)
+        b.refit_leaves_device(d, labels.data_ptr(), n, eta=1.0, reg_lambda=1.0, stream=stream)
+        res["rmse_after_refit"] = rmse(b)
+        boost(b, args.rounds)
+        res[f"rmse_after_refit_and_{args.rounds}_rounds"] = rmse(b)
+        b.free()
+    d.free()
+    os.makedirs(os.path.dirname(args.out), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
