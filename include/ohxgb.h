@@ -595,6 +595,27 @@ int OHXBoosterBoostTreesDevice(BoosterHandle handle, DMatrixHandle dmat, const f
                                float lambda, float gamma, bst_ulong min_child_rows, bst_ulong* nodes_added, void* stream);
 int OHXQuantileCuts(const float* data, bst_ulong nrow, bst_ulong ncol, float missing, int max_bins, bst_ulong* cut_ptr,
                     float* cut_values, bst_ulong cap, bst_ulong* needed);
+/* OHXDMatrixQuantileCuts (docs/19_device_cuts.md) makes the same cuts from a DMatrix's rows where they lie, in HBM: no
+ * booster, either matrix form (XGDMatrixCreateFromMat or OHXDMatrixCreateFromDevice).  The result is what
+ * OHXQuantileCuts returns for the row-major sample made of rows 0, row_step, 2 * row_step, ... (< nrow) of the matrix,
+ * the matrix's own `missing`, and the same max_bins and cap: steps (1)-(5) above apply word for word, including the
+ * `cap` refusal with *needed still set.  One stated difference: a cut equal to zero is always +0.0f (the host form's
+ * sort leaves the sign of a zero unspecified; x < -0.0f and x < +0.0f are the same predicate, so no bin changes).
+ * No sort is made: an exact radix select over an order-preserving integer key finds every distinct value or order
+ * statistic from integer histograms in three passes over the sampled rows.  Integer adds only (no float atomics, no
+ * compare-and-swap loops): the result depends on neither the order of the sampled rows, the launch shape,
+ * OHXDMatrixSetGrid, nor the matrix form.
+ * cut_ptr (ncol + 1 entries, ncol the MATRIX's columns), cut_values and needed are HOST pointers.  A matrix of fewer
+ * columns than the booster has features yields ncol + 1 pointers; the caller repeats the last one for the columns the
+ * matrix lacks.  nrow == 0 succeeds with every pointer 0 and launches nothing.
+ * `stream` is the stream the rows are ready on: the call enqueues there and waits once, at the end.  It is not
+ * capturable.  Its scratch (ncol x 4096 and ncol x 255 x 1024 counters of 4 bytes, and a record per column) is the
+ * call's own: allocated on the matrix's device, freed before it returns, never a booster's buffer.
+ * Refused (rc -1, nothing enqueued, outputs other than *needed untouched): an invalid handle; NULL cut_ptr or needed;
+ * NULL cut_values with cap != 0; max_bins outside 2..255; row_step < 1; more than 2^31 rows; a stream that is being
+ * captured; no usable HIP device (no CPU fallback); a buffer that cannot be allocated (the message says the bytes). */
+int OHXDMatrixQuantileCuts(DMatrixHandle dmat, bst_ulong row_step, int max_bins, bst_ulong* cut_ptr, float* cut_values,
+                           bst_ulong cap, bst_ulong* needed, void* stream);
 
 /* The whole of predict_OH_with_XGB's RUN section in one kernel
  * (OH_GridCompMod.F90:303-383): gathers the 27 MAPL fields in place (field f is

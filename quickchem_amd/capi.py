@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "OHXBoosterPredictContribsFields", "OHXBoosterPredictContribsFieldsDevice",
     "OHXBoosterCountVisits", "OHXBoosterCountVisitsDevice", "OHXBoosterGetVisitCounts", "OHXBoosterResetVisitCounts",
     "OHXBoosterRefreshCover", "OHXBoosterRefitLeaves", "OHXBoosterRefitLeavesDevice",
-    "OHXBoosterBoostTrees", "OHXBoosterBoostTreesDevice", "OHXQuantileCuts",
+    "OHXBoosterBoostTrees", "OHXBoosterBoostTreesDevice", "OHXQuantileCuts", "OHXDMatrixQuantileCuts",
     "OHXSelectCells", "OHXSelectCellsDevice", "OHXGatherCells", "OHXGatherCellsDevice",
     "OHXScatterCells", "OHXScatterCellsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
@@ -141,6 +141,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.OHXBoosterBoostTrees.argtypes = [vp, vp, vp, u64, vp, vp, i32, i32, f32, f32, f32, u64, C.POINTER(u64)]
     lib.OHXBoosterBoostTreesDevice.argtypes = [vp, vp, vp, u64, vp, vp, i32, i32, f32, f32, f32, u64, C.POINTER(u64), vp]
     lib.OHXQuantileCuts.argtypes = [vp, u64, u64, f32, i32, vp, vp, u64, C.POINTER(u64)]
+    lib.OHXDMatrixQuantileCuts.argtypes = [vp, u64, i32, vp, vp, u64, C.POINTER(u64), vp]
     lib.OHXBoosterPredictFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32,
                                             f32, i32, f32, vp, vp]
     i64 = C.c_int64
@@ -257,6 +258,22 @@ class DMatrix:
         im, jm, r0, inf = C.c_int32(), C.c_int32(), C.c_uint64(), C.c_int32()
         check(self.lib, self.lib.OHXDMatrixGetGrid(self.handle, C.byref(im), C.byref(jm), C.byref(r0), C.byref(inf)))
         return im.value, jm.value, r0.value, bool(inf.value)
+
+    def quantile_cuts(self, row_step: int = 1, max_bins: int = 255, stream=None, pad_to: Optional[int] = None):
+        """OHXDMatrixQuantileCuts -> (cut_ptr uint64, cut_values float32): the cuts quantile_cuts makes from rows 0,
+        row_step, 2 * row_step, ... of this matrix, found on the GPU where the rows lie (`stream`: the stream they are
+        ready on; the call waits).  cut_ptr has num_col + 1 entries; pad_to=F repeats the last one up to F + 1 entries,
+        for a booster of F features that the matrix has fewer columns than."""
+        ncol = self.num_col
+        cut_ptr = np.zeros(ncol + 1, dtype=np.uint64)
+        cap = ncol * (max_bins - 1) if 2 <= max_bins <= 255 else 0
+        values = np.zeros(max(cap, 1), dtype=np.float32)
+        needed = C.c_uint64()
+        check(self.lib, self.lib.OHXDMatrixQuantileCuts(self.handle, row_step, max_bins, cut_ptr.ctypes.data,
+                                                        values.ctypes.data, cap, C.byref(needed), stream or None))
+        if pad_to is not None and pad_to > ncol:
+            cut_ptr = np.concatenate([cut_ptr, np.full(pad_to - ncol, cut_ptr[-1], dtype=np.uint64)])
+        return cut_ptr, values[:needed.value].copy()
 
     def save_binary(self, fname: str) -> None:
         check(self.lib, self.lib.XGDMatrixSaveBinary(self.handle, fname.encode(), 1))

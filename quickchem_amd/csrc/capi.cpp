@@ -35,6 +35,7 @@
 #include "visits.hpp"
 #include "refit.hpp"
 #include "grow.hpp"
+#include "cuts.hpp"
 
 using namespace ohx;
 
@@ -2344,6 +2345,67 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   if (nodes_added != nullptr) *nodes_added = added;
 }
 
+// ---- quantile cuts from rows in HBM (cuts.hpp) ----
+
+// OHXDMatrixQuantileCuts.  The refusals that need neither a matrix nor a device come first; nothing is enqueued before
+// the last refusal.  The scratch is this call's own: allocated on the matrix's device and freed before it returns.
+void dmatrix_quantile_cuts(DMatrixHandle dmat, bst_ulong row_step, int max_bins, bst_ulong* cut_ptr, float* cut_values,
+                           bst_ulong cap, bst_ulong* needed, hipStream_t stream) {
+  const std::string w0("OHXDMatrixQuantileCuts");
+  if (cut_ptr == nullptr || needed == nullptr) throw OhxError(w0 + ": NULL output argument");
+  if (cut_values == nullptr && cap != 0) throw OhxError(w0 + ": cut_values is NULL");
+  if (max_bins < 2 || max_bins > (int)kCutsMaxBins) throw OhxError(w0 + ": max_bins must be in 2..255");
+  if (row_step < 1) throw OhxError(w0 + ": row_step must be >= 1");
+  DMatrixObj& d = *as_dmat(dmat);
+  if (d.nrow > kCutsMaxRows) throw OhxError(w0 + ": at most 2^31 rows per call (" + std::to_string(d.nrow) + " given)");
+  static_assert(sizeof(bst_ulong) == sizeof(uint64_t), "bst_ulong is uint64");
+  uint64_t* ptr = reinterpret_cast<uint64_t*>(cut_ptr);
+  const uint64_t ncol = d.ncol;
+  if (d.nrow == 0 || ncol == 0) {        // nothing to look at: no cuts, and nothing is launched
+    for (uint64_t c = 0; c <= ncol; ++c) ptr[c] = 0;
+    *needed = 0;
+    return;
+  }
+  if (ncol > 0xFFFFFFFFull) throw OhxError(w0 + ": " + std::to_string(ncol) + " columns");
+  const DeviceInfo dev = use_device(d.device);       // throws where there is no device
+  if (stream_capturing(stream)) refuse_in_capture("make quantile cuts", (w0 + " is not capturable; call it outside the capture").c_str());
+  HIP_CHECK((hipError_t)prepare_cuts());
+  const CutsPlan plan = plan_cuts(d.nrow, row_step, ncol, dev.num_cus);
+  DevBuf<uint32_t> d_table1, d_table;
+  DevBuf<CutsCol> d_cols;
+  PinnedBuf<CutsCol> h_cols;
+  auto room = [&](auto& buf, size_t count, size_t elem, const char* name) {
+    try {
+      buf.ensure(count);
+    } catch (const OhxError& e) {
+      throw OhxError(w0 + ": " + name + " of " + std::to_string((uint64_t)count * elem) + " bytes cannot be allocated (" + e.what() + ")");
+    }
+  };
+  room(d_table1, (size_t)(plan.table1_bytes / 4), 4, "the first pass's counters (columns x 4096)");
+  room(d_table, (size_t)(plan.table_bytes / 4), 4, "the later passes' counters (columns x 255 x 1024)");
+  room(d_cols, (size_t)ncol, sizeof(CutsCol), "the column records");
+  room(h_cols, (size_t)ncol, sizeof(CutsCol), "the host copy of the column records");
+  CutsArgs a;
+  a.rows = d.d_data;
+  a.sampled = plan.sampled;
+  a.row_step = row_step;
+  a.ncol = (uint32_t)ncol;
+  a.missing = d.missing;
+  a.max_bins = (uint32_t)max_bins;
+  a.table1 = d_table1.p;
+  a.table = d_table.p;
+  a.cols = d_cols.p;
+  hipError_t launched = (hipError_t)launch_cuts(a, plan, stream);
+  if (launched == hipSuccess) launched = hipMemcpyAsync(h_cols.p, d_cols.p, (size_t)ncol * sizeof(CutsCol), hipMemcpyDeviceToHost, stream);
+  // the one wait, whatever was enqueued: the scratch is freed on return
+  const hipError_t waited = hipStreamSynchronize(stream);
+  HIP_CHECK(launched);
+  HIP_CHECK(waited);
+  *needed = cuts_write(h_cols.p, ncol, (uint32_t)max_bins, ptr, cut_values, cap);
+  if (*needed > cap)
+    throw OhxError(w0 + ": " + std::to_string(*needed) + " cut values are needed and cut_values holds " + std::to_string(cap));
+}
+
 }  // namespace
 
 // =================================================================== C ABI
@@ -2977,6 +3039,13 @@ int OHXQuantileCuts(const float* data, bst_ulong nrow, bst_ulong ncol, float mis
   if (*needed > cap)
     throw OhxError("OHXQuantileCuts: " + std::to_string(*needed) + " cut values are needed and cut_values holds " +
                    std::to_string(cap));
+  API_END();
+}
+
+int OHXDMatrixQuantileCuts(DMatrixHandle dmat, bst_ulong row_step, int max_bins, bst_ulong* cut_ptr, float* cut_values,
+                           bst_ulong cap, bst_ulong* needed, void* stream) {
+  API_BEGIN();
+  dmatrix_quantile_cuts(dmat, row_step, max_bins, cut_ptr, cut_values, cap, needed, static_cast<hipStream_t>(stream));
   API_END();
 }
 

@@ -393,6 +393,22 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
+      !  the same cuts from rows 0, row_step, 2 * row_step, ... of a DMatrix in HBM; cut_ptr (the matrix's ncol + 1
+      !  entries), cut_values and needed are host arrays; stream: a hipStream_t the rows are ready on (c_null_ptr = default)
+      function OHXDMatrixQuantileCuts(dmat, row_step, max_bins, cut_ptr, cut_values, cap, needed, stream) &
+            bind(C, name="OHXDMatrixQuantileCuts") result(rc)
+         import :: c_int, c_float, c_int64_t, c_ptr
+         type(c_ptr), value              :: dmat
+         integer(c_int64_t), value       :: row_step
+         integer(c_int), value           :: max_bins
+         integer(c_int64_t), intent(out) :: cut_ptr(*)
+         real(c_float), intent(out)      :: cut_values(*)
+         integer(c_int64_t), value       :: cap
+         integer(c_int64_t), intent(out) :: needed
+         type(c_ptr), value              :: stream
+         integer(c_int)                  :: rc
+      end function
+
       ! ---- part 4 of ohxgb.h: the OH field reassembled on every GPU of a node, for a host that has MPI but no
       !      torch.distributed.  Rank 0 gets the id, MPI_Bcast carries its OHX_UNIQUE_ID_BYTES bytes, every rank
       !      (hipSetDevice done) inits; d_shard / d_full are DEVICE addresses, stream a hipStream_t (c_null_ptr = default)

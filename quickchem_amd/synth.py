@@ -98,6 +98,10 @@ def _load():
             C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         lib.ohx_grow_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64),
                                       C.c_void_p]
+        lib.ohx_cuts_select.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int, C.c_uint64, C.c_void_p,
+                                        C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
+        lib.ohx_cuts_keys.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.ohx_cuts_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
         _lib = lib
     return _lib
 
@@ -455,6 +459,43 @@ def grow_plan(nrow: int, num_feature: int = NFEAT, ncuts: int = 0, max_depth: in
             "bins_bytes": int(info[3]), "hist_bytes": int(info[4]), "hist_block_rows": int(info[5]),
             "max_pairs": int(info[6]), "pair_bytes": int(info[7]),
             "levels": [dict(zip(names, (int(v) for v in row))) for row in lev]}
+
+
+def quantile_cuts_select(x, missing: float = float("nan"), max_bins: int = 255, row_step: int = 1, bits=(12, 10, 10)):
+    """csrc/cuts.cpp cuts_select_host: the radix select of OHXDMatrixQuantileCuts on the host, over rows 0, row_step, ...
+    of the row-major `x` - the counting is a plain loop, the step between passes and the final assembly are the code
+    the product library runs.  bits: the key bits each pass takes (they sum to 32).
+    -> (cut_ptr uint64 [ncol + 1], cut_values float32)."""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    assert x.ndim == 2
+    nrow, ncol = x.shape
+    b = np.ascontiguousarray(bits, dtype=np.uint32)
+    cut_ptr = np.zeros(ncol + 1, dtype=np.uint64)
+    cap = ncol * 254
+    values = np.zeros(max(cap, 1), dtype=np.float32)
+    needed = C.c_uint64()
+    _check(_load().ohx_cuts_select(x.ctypes.data, nrow, ncol, missing, max_bins, row_step, b.ctypes.data, b.size,
+                                   cut_ptr.ctypes.data, values.ctypes.data, cap, C.byref(needed)))
+    return cut_ptr, values[:needed.value].copy()
+
+
+def cuts_keys(bits):
+    """csrc/cuts.hpp cuts_key of float32 bit patterns (uint32) and cuts_unkey of the keys -> (keys, back)."""
+    u = np.ascontiguousarray(bits, dtype=np.uint32)
+    keys, back = np.zeros_like(u), np.zeros_like(u)
+    _check(_load().ohx_cuts_keys(u.ctypes.data, u.size, keys.ctypes.data, back.ctypes.data))
+    return keys, back
+
+
+def cuts_plan(nrow: int, row_step: int = 1, ncol: int = NFEAT, num_cus: int = 256):
+    """csrc/cuts.hpp plan_cuts -> dict: sampled (rows), block_rows, pass 1's blocks1, col_group1, col_groups1 and
+    lds1_bytes, passes 2 and 3's blocks, col_group, col_groups and lds_bytes (the staged prefixes), table1_bytes and
+    table_bytes."""
+    info = (C.c_uint64 * 12)()
+    _check(_load().ohx_cuts_plan(nrow, row_step, ncol, num_cus, info))
+    names = ("sampled", "blocks1", "col_group1", "col_groups1", "lds1_bytes", "blocks", "col_group", "col_groups",
+             "lds_bytes", "table1_bytes", "table_bytes", "block_rows")
+    return dict(zip(names, (int(v) for v in info)))
 
 
 def cells_plan(n: int, nfield: int = 27):

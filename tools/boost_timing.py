@@ -3,8 +3,11 @@ builds it) and the C360 L72 rows resident in HBM.  Labels = the margins of a boo
 another seed, as tools/refit_timing.py takes them.  Run by hand on an MI355X; writes one JSON document (default
 profiles/boost_timing.json).
 
-The cuts come from OHXQuantileCuts on a sample of `--sample` rows copied to the host.  The whole call is timed from the
-host (it waits at its end): a fresh booster's first call, which also allocates the state's buffers, and the second call
+The cuts come from OHXQuantileCuts on a sample of `--sample` rows copied to the host (`--cuts host`), from
+OHXDMatrixQuantileCuts on the same evenly strided rows where they lie (`--cuts device`), or from both, each timed and
+the two compared (`--cuts both`, the default); `--cuts-full` also times the device call on every row (row_step = 1).
+The trees are grown over the host's cuts where they were made, else over the device's.  The whole boost call is timed
+from the host (it waits at its end): a fresh booster's first call, which also allocates the state's buffers, and the second call
 of the same shape on one booster, which finds them, for 1 round and for `--rounds` rounds at `--max-depth`.  The one-off cost
 (binning, the initial margin, the allocations' reuse) is what a 1-round call takes beyond one round's share of the long
 call.  The RMSE against the labels is taken before the call, after a refit, and after the refit plus `--rounds` rounds.
@@ -40,6 +43,8 @@ def main():
     ap.add_argument("--reg-lambda", type=float, default=1.0)
     ap.add_argument("--max-bins", type=int, default=255)
     ap.add_argument("--sample", type=int, default=1 << 20)
+    ap.add_argument("--cuts", choices=("host", "device", "both"), default="both")
+    ap.add_argument("--cuts-full", action="store_true", help="also time the device cuts on every row (row_step = 1)")
     ap.add_argument("--skip-rmse", action="store_true", help="time only (a run under a kernel trace)")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "boost_timing needs the MI355X"
@@ -57,14 +62,45 @@ def main():
     d.set_grid(grid[0], grid[1], 0)
     # the cuts: quantiles of an evenly strided sample of the rows
     step = max(1, n // args.sample)
-    t0 = time.perf_counter()
-    sample = rows[::step].cpu().numpy()
-    cuts = capi.quantile_cuts(sample, synth.XX_MISS, args.max_bins)
-    ncuts = int(cuts[0][-1])
     res = {"model": {"trees": model.num_trees, "nodes": model.num_nodes, "max_depth": model.max_depth}, "rows": n,
-           "plan": synth.grow_plan(n, F, ncuts, args.max_depth, cus), "max_depth": args.max_depth, "eta": args.eta,
-           "reg_lambda": args.reg_lambda, "reps": args.reps, "sample_rows": int(len(sample)), "cut_values": ncuts,
-           "cuts_host_seconds": time.perf_counter() - t0}
+           "max_depth": args.max_depth, "eta": args.eta, "reg_lambda": args.reg_lambda, "reps": args.reps,
+           "row_step": step, "sample_rows": -(-n // step), "cuts_plan": synth.cuts_plan(n, step, F, cus)}
+    cuts = None
+    if args.cuts in ("host", "both"):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sample = rows[::step].cpu().numpy()
+        cuts = capi.quantile_cuts(sample, synth.XX_MISS, args.max_bins)
+        res["cuts_host_seconds"] = time.perf_counter() - t0
+
+    def device_cuts(row_step):
+        """-> (the cuts, the seconds of a first call and of the `--reps` calls after it)."""
+        times = []
+        for _ in range(args.reps + 1):
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            c = d.quantile_cuts(row_step, args.max_bins, stream=stream)
+            times.append(time.perf_counter() - t)
+        return c, times
+
+    if args.cuts in ("device", "both"):
+        dcuts, times = device_cuts(step)
+        res["cuts_device_first_call_seconds"] = times[0]
+        res["cuts_device_seconds"] = float(np.median(times[1:])) if args.reps else times[0]
+        if cuts is not None:
+            res["cuts_device_equal_host"] = bool(np.array_equal(cuts[0], dcuts[0]) and np.array_equal(cuts[1], dcuts[1]))
+        else:
+            cuts = dcuts
+    if args.cuts_full:
+        fcuts, times = device_cuts(1)
+        res["cuts_device_full_first_call_seconds"] = times[0]
+        res["cuts_device_full_seconds"] = float(np.median(times[1:])) if args.reps else times[0]
+        res["cuts_device_full_cut_values"] = int(fcuts[0][-1])
+        res["cuts_full_plan"] = synth.cuts_plan(n, 1, F, cus)
+    ncuts = int(cuts[0][-1])
+    res["cut_values"] = ncuts
+    res["plan"] = synth.grow_plan(n, F, ncuts, args.max_depth, cus)
+    print("cuts", json.dumps({k: v for k, v in res.items() if k.startswith("cuts_") and not k.endswith("plan")}), flush=True)
 
     def margins(b):
         out = torch.empty(n, dtype=torch.float32, device="cuda")
