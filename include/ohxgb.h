@@ -593,6 +593,58 @@ int OHXBoosterBoostTrees(BoosterHandle handle, DMatrixHandle dmat, const float* 
 int OHXBoosterBoostTreesDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels, bst_ulong nlabel,
                                const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
                                float lambda, float gamma, bst_ulong min_child_rows, bst_ulong* nodes_added, void* stream);
+/* Boosting with a held-out set (docs/20_boost_eval.md): the call above, with the RMSE of the training rows and of a
+ * second, held-out matrix after every round, and early stopping on the held-out error - without leaving the GPU between
+ * rounds.  Tree t (1-based) is exactly the tree OHXBoosterBoostTrees grows at round t from the same arguments: the
+ * held-out rows never influence a tree.
+ * The metric.  For a set of n rows with running float32 margin pred_t after t new trees (t = 0 is the forest as
+ * loaded; the held-out rows' initial margin is, bit for bit, what XGBoosterPredict(option_mask = 1) returns for them,
+ * and every new tree adds its leaf with one float32 add, a row stepping left exactly when x < c_j, NaN, the held-out
+ * matrix's own `missing` or a column it lacks taking the default): g = pred_t[r] - y[r], one float32 subtraction;
+ * q = (int64) rint(g * 2^24), exactly as step 1 above; S_t = sum_r q_r^2 is an exact integer.  |g| < 256 gives
+ * |q| <= 2^32 - 256, so q^2 < 2^64 fits a uint64; the device keeps S_t as two uint64 accumulators, one summing the high
+ * 32 bits of each q^2 and one the low 32 bits, and with at most 2^31 rows neither can overflow.  Integer adds only: the
+ * sums depend on neither the order of the rows, the launch shape, the form, nor OHXDMatrixSetGrid.
+ * train_rmse[t] and eval_rmse[t] are written for t = 0 .. *rounds_run (room for rounds + 1 doubles each; either may
+ * be NULL; later entries are untouched): sqrt( (double)S_t * 2^-48 / (double)n ), where (double)S_t is the exact
+ * integer rounded to nearest even, as an unsigned __int128 conversion rounds it, the scaling is exact, and the division
+ * and the square root are IEEE double.
+ * The stop rule is decided on the exact integers, never on the doubles.  best starts at 0; after tree t is grown,
+ * best = t if S_eval[t] < S_eval[best] - strictly: a tie is not an improvement.  If patience >= 1 and
+ * t - best >= patience the call stops and *rounds_run = t; otherwise *rounds_run = rounds.  *best_round = best.
+ * What is kept.  patience == 0: all `rounds` trees are appended; the forest, and XGBoosterSaveModel's bytes in all three
+ * formats, equal what OHXBoosterBoostTrees leaves.  patience >= 1: trees 1 .. best are appended and the later ones are
+ * discarded - a stated departure from xgboost, which keeps them and records best_iteration.  best == 0 is a success
+ * that appends nothing: the forest and everything built from it stay as they were.  *nodes_added (may be NULL) counts
+ * the kept trees' nodes.
+ * The held-out matrix.  eval_dmat == NULL means no held-out set: eval_labels must be NULL, eval_nlabel 0 and patience
+ * 0; only train_rmse is written and *best_round = *rounds_run.  Otherwise it is a matrix of either form, possibly the
+ * same handle as dmat, with its own `missing`, 1 to 2^31 rows, at most the booster's number of features (the columns it
+ * lacks fall in the missing bin), on the training matrix's device; eval_nlabel equals its row count.
+ * Refused, with the forest and every output untouched: everything OHXBoosterBoostTrees refuses, in the same order and
+ * with the same guarantees; in addition patience < 0; patience >= 1 without a held-out matrix; eval labels without a
+ * held-out matrix, or NULL with one; NULL rounds_run or best_round; a held-out handle that is stale; a held-out matrix
+ * with no rows, more than 2^31 rows, more columns than features, another device, or eval_nlabel != its rows.  Nothing
+ * is enqueued before the last argument check.  The range refusal covers every margin that is summed: a training
+ * residual that is not finite or has |g| >= 256 at t = 0 .. rounds_run (the message says "label"; the plain call never
+ * looks at the margin after its last tree, this one does), and a held-out one likewise (the message says
+ * "eval label"), also in a round whose tree would have been discarded.
+ * patience == 0 waits once, at the end: sums, records and the error word come back together.  patience >= 1 waits once
+ * a round for that round's held-out sums and the error word (a few tens of bytes), and enqueues nothing more once the
+ * rule says stop.  The device form takes d_labels and d_eval_labels in HBM, ready on `stream`.  Not capturable.  The
+ * held-out bin planes and margin, the staged eval labels and the sums are part of the grow state.  Everything else is
+ * as for OHXBoosterBoostTrees: all or nothing, what a success drops, no concurrent calls on ONE booster. */
+int OHXBoosterBoostTreesEval(BoosterHandle handle, DMatrixHandle dmat, const float* labels, bst_ulong nlabel,
+                             DMatrixHandle eval_dmat, const float* eval_labels, bst_ulong eval_nlabel,
+                             const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
+                             float lambda, float gamma, bst_ulong min_child_rows, int patience, double* train_rmse,
+                             double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added);
+int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels, bst_ulong nlabel,
+                                   DMatrixHandle eval_dmat, const float* d_eval_labels, bst_ulong eval_nlabel,
+                                   const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
+                                   float lambda, float gamma, bst_ulong min_child_rows, int patience, double* train_rmse,
+                                   double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added,
+                                   void* stream);
 int OHXQuantileCuts(const float* data, bst_ulong nrow, bst_ulong ncol, float missing, int max_bins, bst_ulong* cut_ptr,
                     float* cut_values, bst_ulong cap, bst_ulong* needed);
 /* OHXDMatrixQuantileCuts (docs/19_device_cuts.md) makes the same cuts from a DMatrix's rows where they lie, in HBM: no

@@ -37,7 +37,8 @@ ABI_SYMBOLS = [
     "OHXBoosterPredictContribsFields", "OHXBoosterPredictContribsFieldsDevice",
     "OHXBoosterCountVisits", "OHXBoosterCountVisitsDevice", "OHXBoosterGetVisitCounts", "OHXBoosterResetVisitCounts",
     "OHXBoosterRefreshCover", "OHXBoosterRefitLeaves", "OHXBoosterRefitLeavesDevice",
-    "OHXBoosterBoostTrees", "OHXBoosterBoostTreesDevice", "OHXQuantileCuts", "OHXDMatrixQuantileCuts",
+    "OHXBoosterBoostTrees", "OHXBoosterBoostTreesDevice", "OHXBoosterBoostTreesEval", "OHXBoosterBoostTreesEvalDevice",
+    "OHXQuantileCuts", "OHXDMatrixQuantileCuts",
     "OHXSelectCells", "OHXSelectCellsDevice", "OHXGatherCells", "OHXGatherCellsDevice",
     "OHXScatterCells", "OHXScatterCellsDevice",
     "OHXBoosterPredictFields", "OHXBoosterPredictFieldsDevice", "OHXBoosterRun1", "OHXBoosterRun1Device", "OHXOHPostProcess", "OHXOHPostProcessDevice",
@@ -140,6 +141,9 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.OHXBoosterRefitLeavesDevice.argtypes = [vp, vp, vp, u64, f32, f32, i32, C.POINTER(u64), vp]
     lib.OHXBoosterBoostTrees.argtypes = [vp, vp, vp, u64, vp, vp, i32, i32, f32, f32, f32, u64, C.POINTER(u64)]
     lib.OHXBoosterBoostTreesDevice.argtypes = [vp, vp, vp, u64, vp, vp, i32, i32, f32, f32, f32, u64, C.POINTER(u64), vp]
+    lib.OHXBoosterBoostTreesEval.argtypes = [vp, vp, vp, u64, vp, vp, u64, vp, vp, i32, i32, f32, f32, f32, u64, i32, vp, vp,
+                                             C.POINTER(i32), C.POINTER(i32), C.POINTER(u64)]
+    lib.OHXBoosterBoostTreesEvalDevice.argtypes = lib.OHXBoosterBoostTreesEval.argtypes + [vp]
     lib.OHXQuantileCuts.argtypes = [vp, u64, u64, f32, i32, vp, vp, u64, C.POINTER(u64)]
     lib.OHXDMatrixQuantileCuts.argtypes = [vp, u64, i32, vp, vp, u64, C.POINTER(u64), vp]
     lib.OHXBoosterPredictFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32,
@@ -504,6 +508,50 @@ class Booster:
                                                              max_depth, eta, reg_lambda, gamma, min_child_rows,
                                                              C.byref(n), stream or None))
         return int(n.value)
+
+    @staticmethod
+    def _eval_result(train, held, run, best, n, has_eval):
+        k = int(run.value) + 1
+        return {"train_rmse": train[:k].copy(), "eval_rmse": held[:k].copy() if has_eval else None,
+                "rounds_run": int(run.value), "best_round": int(best.value), "nodes_added": int(n.value)}
+
+    def boost_trees_eval(self, dmat: DMatrix, labels, cuts, eval_set=None, rounds: int = 1, max_depth: int = 6,
+                         eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0, min_child_rows: int = 1,
+                         patience: int = 0) -> dict:
+        """OHXBoosterBoostTreesEval: boost_trees with the RMSE of the training rows, and of the held-out
+        eval_set = (DMatrix, labels) where one is given, after every round - computed on the GPU from exact integer
+        sums.  patience >= 1 stops once the held-out error has not improved for that many rounds and keeps the trees up
+        to the best round only.  -> dict: train_rmse and eval_rmse (float64, entries 0 .. rounds_run; eval_rmse None
+        without an eval_set), rounds_run, best_round, nodes_added."""
+        y = np.ascontiguousarray(labels, dtype=np.float32).reshape(-1)
+        cut_ptr, cut_values = self._cuts(cuts)
+        ed, ey = (eval_set[0], np.ascontiguousarray(eval_set[1], dtype=np.float32).reshape(-1)) if eval_set is not None else (None, None)
+        k = max(int(rounds), 0) + 1
+        train, held = np.full(k, np.nan), np.full(k, np.nan)
+        run, best, n = C.c_int32(), C.c_int32(), C.c_uint64()
+        check(self.lib, self.lib.OHXBoosterBoostTreesEval(
+            self.handle, dmat.handle, y.ctypes.data, y.size, ed.handle if ed is not None else None,
+            ey.ctypes.data if ey is not None else None, ey.size if ey is not None else 0, cut_ptr.ctypes.data,
+            cut_values.ctypes.data, rounds, max_depth, eta, reg_lambda, gamma, min_child_rows, patience,
+            train.ctypes.data, held.ctypes.data, C.byref(run), C.byref(best), C.byref(n)))
+        return self._eval_result(train, held, run, best, n, ed is not None)
+
+    def boost_trees_eval_device(self, dmat: DMatrix, labels_ptr: int, nlabel: int, cuts, eval_set=None, rounds: int = 1,
+                                max_depth: int = 6, eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
+                                min_child_rows: int = 1, patience: int = 0, stream: int = 0) -> dict:
+        """The same with the labels in device memory: labels_ptr, and eval_set = (DMatrix, eval_labels_ptr,
+        eval_nlabel), are torch data_ptr()s of float32 ready on `stream`; the cuts stay host arrays.  Enqueues on
+        `stream`; waits once at the end, and with patience >= 1 once a round (not capturable)."""
+        cut_ptr, cut_values = self._cuts(cuts)
+        ed, eptr, en = eval_set if eval_set is not None else (None, None, 0)
+        k = max(int(rounds), 0) + 1
+        train, held = np.full(k, np.nan), np.full(k, np.nan)
+        run, best, n = C.c_int32(), C.c_int32(), C.c_uint64()
+        check(self.lib, self.lib.OHXBoosterBoostTreesEvalDevice(
+            self.handle, dmat.handle, labels_ptr, nlabel, ed.handle if ed is not None else None, eptr or None, en,
+            cut_ptr.ctypes.data, cut_values.ctypes.data, rounds, max_depth, eta, reg_lambda, gamma, min_child_rows,
+            patience, train.ctypes.data, held.ctypes.data, C.byref(run), C.byref(best), C.byref(n), stream or None))
+        return self._eval_result(train, held, run, best, n, ed is not None)
 
     def predict_fields(self, fields: Sequence[np.ndarray], is2d: Sequence[bool], pl_feature: int, im: int, jm: int,
                        km: int, k1: int, k2: int, missing: float, oh_ml: np.ndarray, *, apply_pow10: bool = True,

@@ -664,10 +664,18 @@ struct GrowState {
   PinnedBuf<uint32_t> h_tree_nodes, h_cut_ptr;
   PinnedBuf<float> h_cuts;
   PinnedBuf<GrowLevelState> h_state;
+  // the held-out metric (OHXBoosterBoostTreesEval): the held-out rows' bin planes, margin and staged labels, and the
+  // sums [rounds + 1][2 sets][hi, lo]
+  DevBuf<uint8_t> d_eval_bins;
+  DevBuf<float> d_eval_pred, d_eval_labels;
+  DevBuf<unsigned long long> d_sums;
+  PinnedBuf<unsigned long long> h_sums;
   void release_device() {
     d_bins.release();
     d_pos.release();
-    for (DevBuf<float>* f : {&d_pred, &d_labels, &d_cuts}) f->release();
+    d_eval_bins.release();
+    d_sums.release();
+    for (DevBuf<float>* f : {&d_pred, &d_labels, &d_cuts, &d_eval_pred, &d_eval_labels}) f->release();
     for (DevBuf<uint32_t>* f : {&d_cut_ptr, &d_tree_nodes, &d_saved_flag}) f->release();
     d_Ghist.release();
     d_Hhist.release();
@@ -2183,11 +2191,25 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
 
 // ---- boosting new trees (grow.hpp) ----
 
-// Both forms of OHXBoosterBoostTrees.  The refusals that need neither a matrix nor a device come first, in the header's
-// order; nothing is enqueued before the last of them.
+// What OHXBoosterBoostTreesEval adds to a boost call: the held-out set, the patience and where the results go.
+struct BoostEval {
+  DMatrixHandle dmat = nullptr;      // NULL: no held-out set
+  const float* labels = nullptr;
+  bst_ulong nlabel = 0;
+  int patience = 0;
+  double* train_rmse = nullptr;
+  double* eval_rmse = nullptr;
+  int* rounds_run = nullptr;
+  int* best_round = nullptr;
+};
+
+// Both forms of OHXBoosterBoostTrees, and of OHXBoosterBoostTreesEval where `ev` is given.  The refusals that need
+// neither a matrix nor a device come first, in the header's order; nothing is enqueued before the last of them.
+// Without `ev` nothing of the metric is allocated or enqueued.
 void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulong nlabel, const bst_ulong* cut_ptr,
                  const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
-                 bst_ulong min_child_rows, bst_ulong* nodes_added, bool host_form, hipStream_t caller, const char* what) {
+                 bst_ulong min_child_rows, bst_ulong* nodes_added, bool host_form, hipStream_t caller, const char* what,
+                 const BoostEval* ev = nullptr) {
   const std::string w0(what);
   if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
   refuse_categorical(b, what);
@@ -2208,17 +2230,43 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   if (!(std::isfinite(gamma) && gamma >= 0.0f)) throw OhxError(w0 + ": gamma must be finite and >= 0");
   if (min_child_rows < 1) throw OhxError(w0 + ": min_child_rows must be >= 1");
   grow_check_cuts(cut_ptr, cut_values, F, what);
+  if (ev != nullptr) {
+    if (ev->patience < 0) throw OhxError(w0 + ": patience must be >= 0");
+    if (ev->rounds_run == nullptr || ev->best_round == nullptr) throw OhxError(w0 + ": rounds_run or best_round is NULL");
+    if (ev->dmat == nullptr) {
+      if (ev->patience >= 1)
+        throw OhxError(w0 + ": patience " + std::to_string(ev->patience) + " needs a held-out matrix to stop on (eval_dmat is NULL)");
+      if (ev->labels != nullptr || ev->nlabel != 0)
+        throw OhxError(w0 + ": eval labels are given without a held-out matrix (eval_dmat is NULL)");
+    } else if (ev->labels == nullptr) {
+      throw OhxError(w0 + ": eval labels is NULL");
+    }
+  }
   DMatrixObj& d = *as_dmat(dmat);
   if (d.nrow == 0) throw OhxError(w0 + ": the matrix has no rows");
   if (nlabel != d.nrow) throw OhxError(w0 + ": " + std::to_string(nlabel) + " labels for " + std::to_string(d.nrow) + " rows");
   if (d.nrow > kRefitMaxRows) throw OhxError(w0 + ": at most 2^31 rows per call (" + std::to_string(d.nrow) + " given)");
   check_columns(b, d.ncol);
+  DMatrixObj* e = nullptr;           // the held-out matrix
+  if (ev != nullptr && ev->dmat != nullptr) {
+    if (ev->dmat != dmat && !g_dmats.has(ev->dmat)) throw OhxError(w0 + ": the held-out DMatrix handle is invalid or has been freed");
+    e = static_cast<DMatrixObj*>(ev->dmat);
+    if (e->nrow == 0) throw OhxError(w0 + ": the held-out matrix has no rows");
+    if (ev->nlabel != e->nrow)
+      throw OhxError(w0 + ": " + std::to_string(ev->nlabel) + " eval labels for " + std::to_string(e->nrow) + " held-out rows");
+    if (e->nrow > kRefitMaxRows) throw OhxError(w0 + ": at most 2^31 held-out rows per call (" + std::to_string(e->nrow) + " given)");
+    check_columns(b, e->ncol);
+    if (e->device >= 0 && d.device >= 0 && e->device != d.device)
+      throw OhxError(w0 + ": the held-out DMatrix lives on HIP device " + std::to_string(e->device) + " but the training matrix on device " +
+                     std::to_string(d.device));
+  }
   // before anything is built or enqueued: building the state waits for the library's stream
   if (!host_form && stream_capturing(caller))
     refuse_in_capture("grow trees", (w0 + " is not capturable; call it outside the capture").c_str());
   ensure_uploaded(b);                      // throws where there is no device; the initial margin is a margin predict
   const DeviceInfo dev = b.dev;
   check_same_device(d, dev.ordinal);
+  if (e != nullptr) check_same_device(*e, dev.ordinal);
   if (!b.grow) b.grow = std::make_unique<GrowState>();
   GrowState& g = *b.grow;
   if (g.device != dev.ordinal) {
@@ -2247,6 +2295,19 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   room(g.d_Hhist, (size_t)(plan.hist_bytes / 16), 8, "the count histograms");
   room(g.d_best, (size_t)(1u << (max_depth - 1)) * F, sizeof(GrowCand), "the split candidates");
   room(g.d_nodes, R * kGrowMaxNodes, sizeof(GrowNode), "the node records");
+  const uint64_t ne = e != nullptr ? e->nrow : 0;
+  const size_t nsums = (R + 1) * 4;
+  GrowPlan eplan;                    // the held-out rows' binning
+  if (ev != nullptr) {
+    if (e != nullptr) {
+      eplan = plan_grow(ne, F, ncuts, max_depth, dev.num_cus);
+      room(g.d_eval_bins, (size_t)eplan.bins_bytes, 1, "the held-out bin planes (features x rows)");
+      room(g.d_eval_pred, ne, 4, "the held-out margin");
+      if (host_form) room(g.d_eval_labels, ne, 4, "the staged eval labels");
+    }
+    room(g.d_sums, nsums, 8, "the metric sums");
+    g.h_sums.ensure(nsums);
+  }
   g.d_tree_nodes.ensure(R);
   g.d_cuts.ensure(std::max<size_t>(ncuts, 1));
   g.d_cut_ptr.ensure(F + 1);
@@ -2260,7 +2321,7 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   for (uint32_t f = 0; f <= F; ++f) g.h_cut_ptr.p[f] = (uint32_t)cut_ptr[f];
   if (ncuts) memcpy(g.h_cuts.p, cut_values, ncuts * sizeof(float));
   hipStream_t stream = host_form ? lib_streams(dev.ordinal).exec : caller;
-  if (host_form && d.owned == nullptr) order_behind_caller(dev.ordinal, stream);
+  if (host_form && (d.owned == nullptr || (e != nullptr && e->owned == nullptr))) order_behind_caller(dev.ordinal, stream);
   // every earlier call has been waited for, so the buffers are free
   HIP_CHECK(hipMemcpyAsync(g.d_cut_ptr.p, g.h_cut_ptr.p, (F + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   if (ncuts) HIP_CHECK(hipMemcpyAsync(g.d_cuts.p, g.h_cuts.p, ncuts * sizeof(float), hipMemcpyHostToDevice, stream));
@@ -2278,6 +2339,20 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     HIP_CHECK(hipMemcpyAsync(g.d_saved_flag.p, b.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
     launch_predict_checked(b, d, 1, 0, g.d_pred.p, stream);
     HIP_CHECK(hipMemcpyAsync(b.d_flags.p, g.d_saved_flag.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+  }
+  if (ev != nullptr) HIP_CHECK(hipMemsetAsync(g.d_sums.p, 0, nsums * sizeof(unsigned long long), stream));
+  if (e != nullptr) {
+    // the held-out rows get what the training rows got: staged labels, and the margin of the forest so far
+    if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_eval_labels.p, ev->labels, ne * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (b.forest.trees.empty()) {
+      uint32_t base_bits = 0;
+      memcpy(&base_bits, &b.margin_base, sizeof base_bits);
+      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g.d_eval_pred.p), (int)base_bits, (size_t)ne, stream));
+    } else {
+      HIP_CHECK(hipMemcpyAsync(g.d_saved_flag.p, b.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+      launch_predict_checked(b, *e, 1, 0, g.d_eval_pred.p, stream);
+      HIP_CHECK(hipMemcpyAsync(b.d_flags.p, g.d_saved_flag.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    }
   }
   GrowArgs a;
   a.rows = d.d_data;
@@ -2304,24 +2379,123 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   a.gamma = gamma;
   a.min_child_rows = min_child_rows;
   hipError_t launched = (hipError_t)launch_grow_bin(a, plan, stream);
-  for (uint32_t r = 0; launched == hipSuccess && r < (uint32_t)rounds; ++r) launched = (hipError_t)launch_grow_tree(a, plan, r, stream);
+  hipError_t waited = hipSuccess;
+  uint32_t run = (uint32_t)rounds, best = 0;   // rounds grown, and the best of them by the held-out sums
+  if (ev == nullptr) {
+    for (uint32_t r = 0; launched == hipSuccess && r < (uint32_t)rounds; ++r) launched = (hipError_t)launch_grow_tree(a, plan, r, stream);
+  } else {
+    // the metric: the training rows' sums after every leaf kernel, the held-out rows' walk of every new tree, and both
+    // sets' sums of the forest as loaded
+    GrowEvalArgs mt;
+    mt.pred = g.d_pred.p;
+    mt.labels = a.labels;
+    mt.nrow = n;
+    mt.num_feature = F;
+    mt.nodes = g.d_nodes.p;
+    mt.tree_nodes = g.d_tree_nodes.p;
+    mt.sums = g.d_sums.p;
+    mt.state = g.d_state.p;
+    mt.max_depth = max_depth;
+    mt.label_flag = kGrowFlagLabel;
+    GrowEvalArgs me = mt;
+    const uint32_t tblocks = plan_grow_eval_blocks(n, dev.num_cus);
+    uint32_t eblocks = 0;
+    if (e != nullptr) {
+      GrowArgs ab = a;               // the binning alone, on the held-out arrays and the same staged cuts
+      ab.rows = e->d_data;
+      ab.nrow = ne;
+      ab.ncol = (uint32_t)e->ncol;
+      ab.missing = e->missing;
+      ab.labels = nullptr;
+      ab.bins = g.d_eval_bins.p;
+      ab.pos = nullptr;
+      ab.pred = nullptr;
+      if (launched == hipSuccess) launched = (hipError_t)launch_grow_bin(ab, eplan, stream);
+      me.bins = g.d_eval_bins.p;
+      me.pred = g.d_eval_pred.p;
+      me.labels = host_form ? g.d_eval_labels.p : ev->labels;
+      me.nrow = ne;
+      me.label_flag = kGrowFlagEvalLabel;
+      eblocks = plan_grow_eval_blocks(ne, dev.num_cus);
+      if (launched == hipSuccess) launched = (hipError_t)launch_grow_sse(me, eblocks, 0, kGrowEvalHeldOut, stream);
+    }
+    if (launched == hipSuccess) launched = (hipError_t)launch_grow_sse(mt, tblocks, 0, kGrowEvalTrain, stream);
+    std::vector<GrowSum> S(R + 1);   // the held-out sums, as far as they are known (patience >= 1)
+    const bool stepwise = ev->patience >= 1;
+    for (uint32_t r = 0; launched == hipSuccess && waited == hipSuccess && r < (uint32_t)rounds; ++r) {
+      launched = (hipError_t)launch_grow_tree(a, plan, r, stream);
+      if (launched == hipSuccess) launched = (hipError_t)launch_grow_sse(mt, tblocks, r + 1, kGrowEvalTrain, stream);
+      if (launched == hipSuccess && e != nullptr) launched = (hipError_t)launch_grow_walk_sse(me, eblocks, r, kGrowEvalHeldOut, stream);
+      if (!stepwise || launched != hipSuccess) continue;
+      // one small wait a round: this round's held-out sums (and round 0's, the first time) and the error word
+      const uint32_t t0 = r == 0 ? 0 : r + 1;
+      for (uint32_t t = t0; launched == hipSuccess && t <= r + 1; ++t) {
+        const size_t at = grow_sum_index(t, kGrowEvalHeldOut);
+        launched = hipMemcpyAsync(g.h_sums.p + at, g.d_sums.p + at, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
+      }
+      if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_state.p, g.d_state.p, sizeof(GrowLevelState), hipMemcpyDeviceToHost, stream);
+      if (launched != hipSuccess) break;
+      waited = hipStreamSynchronize(stream);
+      if (waited != hipSuccess) break;
+      if (g.h_state.p->error != 0) {   // refused below; nothing more is enqueued
+        run = r + 1;
+        break;
+      }
+      for (uint32_t t = t0; t <= r + 1; ++t) {
+        const size_t at = grow_sum_index(t, kGrowEvalHeldOut);
+        S[t].hi = g.h_sums.p[at];
+        S[t].lo = g.h_sums.p[at + 1];
+      }
+      best = grow_eval_best(S.data(), best, r + 1);
+      if (grow_eval_stops(best, r + 1, ev->patience)) {
+        run = r + 1;
+        break;
+      }
+    }
+    if (launched == hipSuccess && waited == hipSuccess)
+      launched = hipMemcpyAsync(g.h_sums.p, g.d_sums.p, nsums * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
+  }
   if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_nodes.p, g.d_nodes.p, R * kGrowMaxNodes * sizeof(GrowNode), hipMemcpyDeviceToHost, stream);
   if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_tree_nodes.p, g.d_tree_nodes.p, R * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
   if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_state.p, g.d_state.p, sizeof(GrowLevelState), hipMemcpyDeviceToHost, stream);
   // both forms wait, whatever was enqueued: the labels and the records are read from the caller's and the state's memory
-  const hipError_t waited = hipStreamSynchronize(stream);
-  if (!host_form) d.used_async = true;
+  const hipError_t waited_last = hipStreamSynchronize(stream);
+  if (!host_form) {
+    d.used_async = true;
+    if (e != nullptr) e->used_async = true;
+  }
   HIP_CHECK(launched);
   HIP_CHECK(waited);
+  HIP_CHECK(waited_last);
   const uint32_t flags = g.h_state.p->error;
   if (flags & kGrowFlagLabel)
     throw OhxError(w0 + ": a gradient pred - label is not finite or reaches 256 in size at some row and round: look for a "
                    "label that is NaN, infinite or far from the model's range; the forest is unchanged");
+  if (flags & kGrowFlagEvalLabel)
+    throw OhxError(w0 + ": a held-out residual pred - eval label is not finite or reaches 256 in size at some row and round: "
+                   "look for an eval label that is NaN, infinite or far from the model's range; the forest is unchanged");
   if (flags != 0) throw OhxError(w0 + ": the grow kernels reported error flags " + std::to_string(flags));
   // all or nothing: every round is done and the error word is clean
+  size_t keep = R;                     // the trees that are appended
+  if (ev != nullptr) {
+    if (e != nullptr) {
+      // the shared rule over the whole list, from the exact integers: what the round-by-round loop decided
+      std::vector<GrowSum> S(run + 1);
+      for (uint32_t t = 0; t <= run; ++t) {
+        S[t].hi = g.h_sums.p[grow_sum_index(t, kGrowEvalHeldOut)];
+        S[t].lo = g.h_sums.p[grow_sum_index(t, kGrowEvalHeldOut) + 1];
+      }
+      uint32_t run_again = 0;
+      grow_eval_stop(S.data(), run, ev->patience, &run_again, &best);
+      if (run_again != run) throw OhxError(w0 + ": the stop rule gave " + std::to_string(run_again) + " rounds over the sums of " + std::to_string(run));
+      if (ev->patience >= 1) keep = best;
+    } else {
+      best = run;
+    }
+  }
   std::vector<Tree> grown;
   bst_ulong added = 0;
-  for (size_t r = 0; r < R; ++r) {
+  for (size_t r = 0; r < keep; ++r) {
     grown.push_back(grow_assemble_tree(g.h_nodes.p + r * kGrowMaxNodes, g.h_tree_nodes.p[r], F));
     added += g.h_tree_nodes.p[r];
   }
@@ -2338,11 +2512,27 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     throw;
   }
   // everything built from the forest is dropped as a model load drops it; the leaf numbering has changed, so the visit
-  // state goes with its counters
-  invalidate_device_state(b);
-  b.contribs.reset();
-  drop_leaf_walk(b);
+  // state goes with its counters.  No tree kept (best == 0): the forest and everything built from it stay.
+  if (keep != 0) {
+    invalidate_device_state(b);
+    b.contribs.reset();
+    drop_leaf_walk(b);
+  }
   if (nodes_added != nullptr) *nodes_added = added;
+  if (ev != nullptr) {
+    for (uint32_t t = 0; t <= run; ++t) {
+      const unsigned long long* s = g.h_sums.p + grow_sum_index(t, kGrowEvalTrain);
+      GrowSum tr, he;
+      tr.hi = s[0];
+      tr.lo = s[1];
+      he.hi = s[2];
+      he.lo = s[3];
+      if (ev->train_rmse != nullptr) ev->train_rmse[t] = grow_sum_rmse(tr, n);
+      if (ev->eval_rmse != nullptr && e != nullptr) ev->eval_rmse[t] = grow_sum_rmse(he, ne);
+    }
+    *ev->rounds_run = (int)run;
+    *ev->best_round = (int)best;
+  }
 }
 
 // ---- quantile cuts from rows in HBM (cuts.hpp) ----
@@ -3024,6 +3214,49 @@ int OHXBoosterBoostTreesDevice(BoosterHandle handle, DMatrixHandle dmat, const f
   BoosterObj* b = as_booster(handle);
   boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows,
               nodes_added, false, static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesDevice");
+  API_END();
+}
+
+int OHXBoosterBoostTreesEval(BoosterHandle handle, DMatrixHandle dmat, const float* labels, bst_ulong nlabel,
+                             DMatrixHandle eval_dmat, const float* eval_labels, bst_ulong eval_nlabel,
+                             const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
+                             float lambda, float gamma, bst_ulong min_child_rows, int patience, double* train_rmse,
+                             double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  BoostEval ev;
+  ev.dmat = eval_dmat;
+  ev.labels = eval_labels;
+  ev.nlabel = eval_nlabel;
+  ev.patience = patience;
+  ev.train_rmse = train_rmse;
+  ev.eval_rmse = eval_rmse;
+  ev.rounds_run = rounds_run;
+  ev.best_round = best_round;
+  boost_trees(*b, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows,
+              nodes_added, true, nullptr, "OHXBoosterBoostTreesEval", &ev);
+  API_END();
+}
+
+int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels, bst_ulong nlabel,
+                                   DMatrixHandle eval_dmat, const float* d_eval_labels, bst_ulong eval_nlabel,
+                                   const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
+                                   float lambda, float gamma, bst_ulong min_child_rows, int patience, double* train_rmse,
+                                   double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added,
+                                   void* stream) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  BoostEval ev;
+  ev.dmat = eval_dmat;
+  ev.labels = d_eval_labels;
+  ev.nlabel = eval_nlabel;
+  ev.patience = patience;
+  ev.train_rmse = train_rmse;
+  ev.eval_rmse = eval_rmse;
+  ev.rounds_run = rounds_run;
+  ev.best_round = best_round;
+  boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows,
+              nodes_added, false, static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesEvalDevice", &ev);
   API_END();
 }
 

@@ -141,4 +141,16 @@ GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_
   return p;
 }
 
+uint32_t plan_grow_eval_blocks(uint64_t nrow, int num_cus) {
+  const uint64_t cus = num_cus > 0 ? (uint64_t)num_cus : 1;
+  const uint64_t want = (nrow + kGrowBlock - 1) / kGrowBlock, cap = cus * kGrowRowBlocksPerCu;
+  return (uint32_t)std::max<uint64_t>(1, std::min(want, cap));
+}
+
+double grow_sum_rmse(GrowSum s, uint64_t n) {
+  s = grow_sum_normal(s);
+  const unsigned __int128 S = ((unsigned __int128)s.hi << 32) + (unsigned __int128)s.lo;
+  return std::sqrt((double)S * (1.0 / 281474976710656.0) / (double)n);
+}
+
 }  // namespace ohx

@@ -26,6 +26,7 @@ constexpr int kGrowMaxDepth = 8;
 constexpr uint32_t kGrowMaxNodes = 512;        // node records kept per tree (a tree of depth 8 has at most 511)
 constexpr uint32_t kGrowFlagLabel = 1u;        // the error word: a gradient out of range (refit.hpp kRefitFlagLabel)
 constexpr uint32_t kGrowFlagState = 2u;        // a node id or a bin outside its table (never, from sound buffers)
+constexpr uint32_t kGrowFlagEvalLabel = 4u;    // the same as kGrowFlagLabel at a held-out row
 
 // gain(G, H) of the header: CalcGain of xgboost 1.6.0 with reg_alpha = 0 and max_delta_step = 0, on the fixed-point sum
 OHX_GROW_HD inline double grow_gain(int64_t G, uint64_t H, double lambda) {
@@ -114,6 +115,49 @@ GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t num_featu
 // A Tree of the forest from n node records; throws on a record that is not a tree in allocation order.
 Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature);
 
+// ---- the held-out metric (OHXBoosterBoostTreesEval; design in docs/20_boost_eval.md) ----
+
+// A sum of squares S = sum q^2 as the device keeps it: `hi` sums the high 32 bits of each q^2 and `lo` the low 32
+// bits, so S = hi * 2^32 + lo.  With at most 2^31 rows neither accumulator overflows.
+struct GrowSum {
+  uint64_t hi = 0, lo = 0;
+};
+// lo < 2^32 afterwards; what it held above goes into hi
+inline GrowSum grow_sum_normal(GrowSum s) {
+  GrowSum n;
+  n.hi = s.hi + (s.lo >> 32);
+  n.lo = s.lo & 0xFFFFFFFFull;
+  return n;
+}
+// a < b as the exact integers
+inline bool grow_sum_less(GrowSum a, GrowSum b) {
+  a = grow_sum_normal(a);
+  b = grow_sum_normal(b);
+  return a.hi != b.hi ? a.hi < b.hi : a.lo < b.lo;
+}
+// One step of the stop rule: the best round once S[t] is known.  Strict: a tie is not an improvement.
+inline uint32_t grow_eval_best(const GrowSum* S, uint32_t best, uint32_t t) { return grow_sum_less(S[t], S[best]) ? t : best; }
+inline bool grow_eval_stops(uint32_t best, uint32_t t, int patience) {
+  return patience >= 1 && t - best >= (uint32_t)patience;
+}
+// The stop rule over the held-out sums S[0 .. rounds]: best starts at 0; after tree t, best = t if S[t] < S[best]; with
+// patience >= 1 the run stops at the first t with t - best >= patience.  Sums past *rounds_run are not looked at.
+inline void grow_eval_stop(const GrowSum* S, uint32_t rounds, int patience, uint32_t* rounds_run, uint32_t* best) {
+  uint32_t b = 0, run = rounds;
+  for (uint32_t t = 1; t <= rounds; ++t) {
+    b = grow_eval_best(S, b, t);
+    if (grow_eval_stops(b, t, patience)) {
+      run = t;
+      break;
+    }
+  }
+  *rounds_run = run;
+  *best = b;
+}
+// sqrt( (double)S * 2^-48 / (double)n ): the exact integer rounded to nearest even as it becomes a double, an exact
+// scaling, then an IEEE division and square root.
+double grow_sum_rmse(GrowSum s, uint64_t n);
+
 // ---- the launch plan ----
 
 constexpr uint32_t kGrowBlock = 256;           // bin, split, partition and leaf kernels: a row per lane
@@ -142,6 +186,8 @@ struct GrowPlan {
   uint64_t hist_bytes = 0;    // the deepest level's global histograms: slots x num_feature x 256 x 16
 };
 GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus);
+// blocks of grow_sse_kernel and grow_walk_sse_kernel over n rows: a row per lane, kGrowBlock lanes, grid-stride
+uint32_t plan_grow_eval_blocks(uint64_t nrow, int num_cus);
 
 #ifdef __HIPCC__
 struct GrowLevelState {   // one per call, on the device
@@ -181,6 +227,28 @@ int launch_grow_bin(const GrowArgs& a, const GrowPlan& plan, void* stream);
 // Enqueues one tree, round `round`: per level the histogram memsets, the histogram, split and partition kernels, then
 // the leaf kernel (pred += leaf, pos = 0).  pos must be zero and pred the margin so far.  Returns a hipError_t.
 int launch_grow_tree(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
+
+// The metric kernels (grow_eval.hip).  sums is [rounds + 1][2 sets: training, held-out][hi, lo].
+struct GrowEvalArgs {
+  const uint8_t* bins = nullptr;   // [num_feature][nrow] of the rows walked (grow_walk_sse_kernel only)
+  float* pred = nullptr;           // [nrow] their running margin
+  const float* labels = nullptr;   // [nrow]
+  uint64_t nrow = 0;
+  uint32_t num_feature = 0;
+  const GrowNode* nodes = nullptr;       // [rounds][kGrowMaxNodes]
+  const uint32_t* tree_nodes = nullptr;  // [rounds]
+  unsigned long long* sums = nullptr;
+  GrowLevelState* state = nullptr;
+  int max_depth = 0;
+  uint32_t label_flag = 0;         // what a residual out of range raises: kGrowFlagLabel or kGrowFlagEvalLabel
+};
+constexpr uint32_t kGrowEvalTrain = 0, kGrowEvalHeldOut = 1;
+inline size_t grow_sum_index(uint32_t t, uint32_t set) { return ((size_t)t * 2 + set) * 2; }
+// Enqueues grow_sse_kernel: sums[t][set] += the squares of pred - labels over the rows of `a`.  Returns a hipError_t.
+int launch_grow_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream);
+// Enqueues grow_walk_sse_kernel: the rows of `a` walk tree `round` by their bins, pred += leaf, and
+// sums[round + 1][set] += the squares.  Returns a hipError_t.
+int launch_grow_walk_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream);
 #endif  // __HIPCC__
 
 }  // namespace ohx

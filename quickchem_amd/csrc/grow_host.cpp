@@ -1,7 +1,8 @@
 // Test support (libohx_synth.so): the host pieces of the tree grower (grow.hpp) without a GPU - the split choice on
 // injected histograms (the shared grow_best_split the split kernel runs per lane), the assembly of a tree from node
 // records appended to a booster and written in a file format, and the launch plan.  The product library runs the same
-// functions of grow.cpp behind OHXBoosterBoostTrees.
+// functions of grow.cpp behind OHXBoosterBoostTrees; and the host pieces of the held-out metric behind
+// OHXBoosterBoostTreesEval: the comparison of two sums, the stop rule, the RMSE of a sum and the launch shape.
 #include <cstdlib>
 #include <cstring>
 #include <string>
@@ -115,4 +116,53 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_plan(uint64_t nro
     synth_set_error(e.what());
     return -1;
   }
+}
+
+// ---- the held-out metric ----
+
+// sums: n pairs (hi, lo), the held-out sums after 0 .. n - 1 trees.  out: [0] rounds_run, [1] best_round
+extern "C" __attribute__((visibility("default"))) int ohx_grow_eval_stop(const uint64_t* sums, uint32_t n, int patience,
+                                                                        uint32_t out[2]) {
+  try {
+    if (n == 0) throw OhxError("ohx_grow_eval_stop: no sums");
+    if (patience < 0) throw OhxError("ohx_grow_eval_stop: patience must be >= 0");
+    std::vector<GrowSum> S(n);
+    for (uint32_t t = 0; t < n; ++t) {
+      S[t].hi = sums[2 * t];
+      S[t].lo = sums[2 * t + 1];
+    }
+    grow_eval_stop(S.data(), n - 1, patience, &out[0], &out[1]);
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// -1 / 0 / 1 as a < b, a == b, a > b; normal: a's (hi, lo) with lo < 2^32
+extern "C" __attribute__((visibility("default"))) int ohx_grow_eval_compare(const uint64_t a[2], const uint64_t b[2],
+                                                                           uint64_t normal[2]) {
+  GrowSum x, y;
+  x.hi = a[0];
+  x.lo = a[1];
+  y.hi = b[0];
+  y.lo = b[1];
+  const GrowSum nx = grow_sum_normal(x);
+  normal[0] = nx.hi;
+  normal[1] = nx.lo;
+  return grow_sum_less(x, y) ? -1 : grow_sum_less(y, x) ? 1 : 0;
+}
+
+extern "C" __attribute__((visibility("default"))) double ohx_grow_eval_rmse(uint64_t hi, uint64_t lo, uint64_t n) {
+  GrowSum s;
+  s.hi = hi;
+  s.lo = lo;
+  return grow_sum_rmse(s, n);
+}
+
+// info: [0] blocks of grow_sse_kernel and grow_walk_sse_kernel over nrow rows, [1] rows such a block takes per trip
+extern "C" __attribute__((visibility("default"))) int ohx_grow_eval_plan(uint64_t nrow, int num_cus, uint64_t info[2]) {
+  info[0] = plan_grow_eval_blocks(nrow, num_cus);
+  info[1] = kGrowBlock;
+  return 0;
 }

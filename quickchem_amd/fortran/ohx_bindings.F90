@@ -378,6 +378,46 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
+      !  Boosting with a held-out set (include/ohxgb.h; docs/20_boost_eval.md).  Interface blocks only.  eval_dmat: a
+      !  second DMatrix or c_null_ptr; eval_labels: c_loc of eval_nlabel real(c_float) on the host (d_eval_labels: their
+      !  DEVICE address), or c_null_ptr without a held-out set.  train_rmse / eval_rmse: c_loc of rounds + 1
+      !  real(c_double), or c_null_ptr; rounds_run / best_round: integer(c_int) out; nodes_added as above
+      function OHXBoosterBoostTreesEval(handle, dmat, labels, nlabel, eval_dmat, eval_labels, eval_nlabel, cut_ptr, &
+            cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows, patience, train_rmse, eval_rmse, &
+            rounds_run, best_round, nodes_added) bind(C, name="OHXBoosterBoostTreesEval") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat, eval_dmat, eval_labels
+         real(c_float), intent(in)       :: labels(*)
+         integer(c_int64_t), value       :: nlabel, eval_nlabel
+         integer(c_int64_t), intent(in)  :: cut_ptr(*)
+         real(c_float), intent(in)       :: cut_values(*)
+         integer(c_int), value           :: rounds, max_depth, patience
+         real(c_float), value            :: eta, lambda, gamma
+         integer(c_int64_t), value       :: min_child_rows
+         type(c_ptr), value              :: train_rmse, eval_rmse
+         integer(c_int), intent(out)     :: rounds_run, best_round
+         type(c_ptr), value              :: nodes_added
+         integer(c_int)                  :: rc
+      end function
+
+      function OHXBoosterBoostTreesEvalDevice(handle, dmat, d_labels, nlabel, eval_dmat, d_eval_labels, eval_nlabel, &
+            cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows, patience, train_rmse, &
+            eval_rmse, rounds_run, best_round, nodes_added, stream) &
+            bind(C, name="OHXBoosterBoostTreesEvalDevice") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat, d_labels, eval_dmat, d_eval_labels, stream
+         integer(c_int64_t), value       :: nlabel, eval_nlabel
+         integer(c_int64_t), intent(in)  :: cut_ptr(*)
+         real(c_float), intent(in)       :: cut_values(*)
+         integer(c_int), value           :: rounds, max_depth, patience
+         real(c_float), value            :: eta, lambda, gamma
+         integer(c_int64_t), value       :: min_child_rows
+         type(c_ptr), value              :: train_rmse, eval_rmse
+         integer(c_int), intent(out)     :: rounds_run, best_round
+         type(c_ptr), value              :: nodes_added
+         integer(c_int)                  :: rc
+      end function
+
       !  data: a row-major host sample (nrow x ncol); cut_ptr: ncol + 1 entries out; needed: the cut values in all
       function OHXQuantileCuts(data, nrow, ncol, missing, max_bins, cut_ptr, cut_values, cap, needed) &
             bind(C, name="OHXQuantileCuts") result(rc)

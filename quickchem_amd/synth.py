@@ -98,6 +98,11 @@ def _load():
             C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]
         lib.ohx_grow_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64),
                                       C.c_void_p]
+        lib.ohx_grow_eval_stop.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+        lib.ohx_grow_eval_compare.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ohx_grow_eval_rmse.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
+        lib.ohx_grow_eval_rmse.restype = C.c_double
+        lib.ohx_grow_eval_plan.argtypes = [C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
         lib.ohx_cuts_select.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int, C.c_uint64, C.c_void_p,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_cuts_keys.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -459,6 +464,37 @@ def grow_plan(nrow: int, num_feature: int = NFEAT, ncuts: int = 0, max_depth: in
             "bins_bytes": int(info[3]), "hist_bytes": int(info[4]), "hist_block_rows": int(info[5]),
             "max_pairs": int(info[6]), "pair_bytes": int(info[7]),
             "levels": [dict(zip(names, (int(v) for v in row))) for row in lev]}
+
+
+def boost_eval_stop(sums, patience: int):
+    """csrc/grow.hpp grow_eval_stop, the stop rule of OHXBoosterBoostTreesEval, over the held-out sums after 0, 1, ...
+    trees, each a pair (hi, lo) of uint64 with S = hi * 2^32 + lo (lo need not be below 2^32).
+    -> (rounds_run, best_round)."""
+    a = np.ascontiguousarray([[int(h), int(l)] for h, l in sums], dtype=np.uint64)
+    out = np.zeros(2, dtype=np.uint32)
+    _check(_load().ohx_grow_eval_stop(a.ctypes.data, len(a), patience, out.ctypes.data))
+    return int(out[0]), int(out[1])
+
+
+def boost_eval_compare(a, b):
+    """csrc/grow.hpp grow_sum_less both ways and grow_sum_normal on sums (hi, lo) -> (-1 / 0 / 1, a normalised)."""
+    a = np.ascontiguousarray([int(v) for v in a], dtype=np.uint64)
+    b = np.ascontiguousarray([int(v) for v in b], dtype=np.uint64)
+    normal = np.zeros(2, dtype=np.uint64)
+    rc = _load().ohx_grow_eval_compare(a.ctypes.data, b.ctypes.data, normal.ctypes.data)
+    return int(rc), (int(normal[0]), int(normal[1]))
+
+
+def boost_eval_rmse(hi: int, lo: int, n: int) -> float:
+    """csrc/grow.cpp grow_sum_rmse: sqrt((double)(hi * 2^32 + lo) * 2^-48 / n)."""
+    return float(_load().ohx_grow_eval_rmse(hi, lo, n))
+
+
+def grow_eval_plan(nrow: int, num_cus: int = 256):
+    """csrc/grow.cpp plan_grow_eval_blocks -> dict: blocks of grow_sse_kernel and grow_walk_sse_kernel, block_rows."""
+    info = (C.c_uint64 * 2)()
+    _check(_load().ohx_grow_eval_plan(nrow, num_cus, info))
+    return {"blocks": int(info[0]), "block_rows": int(info[1])}
 
 
 def quantile_cuts_select(x, missing: float = float("nan"), max_bins: int = 255, row_step: int = 1, bits=(12, 10, 10)):

@@ -13,7 +13,13 @@ of the same shape on one booster, which finds them, for 1 round and for `--round
 call.  The RMSE against the labels is taken before the call, after a refit, and after the refit plus `--rounds` rounds.
 
 The kernels' own times - the binning, and per level the histogram, split and partition kernels - come from a second
-run of this script under a kernel trace with --reps 1 --rounds 1 (docs/18_boost_trees.md 18.4 says how)."""
+run of this script under a kernel trace with --reps 1 --rounds 1 (docs/18_boost_trees.md 18.4 says how).
+
+`--holdout K` times OHXBoosterBoostTreesEvalDevice instead (docs/20_boost_eval.md): every K-th row is held out, the others
+are the training rows (both gathered once into matrices of their own in HBM).  The plain boost call on the training rows,
+the call with patience 0 and the call with `--patience` are each timed as the median of `--reps` calls after a first one,
+on fresh boosters, `--rounds` rounds.  The per-round RMSE of both sets as the call returns it is written beside the one
+this script computes itself, in torch from margin predicts, before the call and after its last kept tree."""
 from __future__ import annotations
 
 import argparse
@@ -31,6 +37,71 @@ import torch  # noqa: E402
 from quickchem_amd import capi, synth  # noqa: E402
 
 
+def holdout(args, model, rows, labels, n, F, stream):
+    """Every K-th row held out: the plain call on the training rows against the call with a held-out set."""
+    k = args.holdout
+    keep = torch.ones(n, dtype=torch.bool, device="cuda")
+    keep[::k] = False
+    xt, yt = rows[keep].contiguous(), labels[keep].contiguous()
+    xe, ye = rows[::k].contiguous(), labels[::k].contiguous()
+    del keep
+    torch.cuda.synchronize()
+    nt, ne = xt.shape[0], xe.shape[0]
+    dt = capi.DMatrix(device_ptr=xt.data_ptr(), nrow=nt, ncol=F, missing=synth.XX_MISS)
+    de = capi.DMatrix(device_ptr=xe.data_ptr(), nrow=ne, ncol=F, missing=synth.XX_MISS)
+    cuts = dt.quantile_cuts(max(1, nt // args.sample), args.max_bins, stream=stream)
+    pk = dict(rounds=args.rounds, max_depth=args.max_depth, eta=args.eta, reg_lambda=args.reg_lambda, stream=stream)
+
+    def own_rmse(b, dm, x, y):
+        out = torch.empty(x.shape[0], dtype=torch.float32, device="cuda")
+        b.predict_device(dm, out.data_ptr(), stream=stream)
+        torch.cuda.synchronize()
+        b.check()
+        return float(torch.sqrt(torch.mean((out.double() - y.double()) ** 2)).item())
+
+    def timed(call):
+        """-> (seconds of the calls after a first one, each on a fresh booster; the last result; its booster)."""
+        times, last, b = [], None, None
+        for _ in range(args.reps + 1):
+            if b is not None:
+                b.free()
+            b = capi.Booster(model_buffer=model.image)
+            torch.cuda.synchronize()
+            t = time.perf_counter()
+            last = call(b)
+            times.append(time.perf_counter() - t)
+        return times[1:] if args.reps else times, last, b
+
+    def summary(times):
+        return {"median_s": float(np.median(times)), "min_s": float(np.min(times)), "max_s": float(np.max(times))}
+
+    out = {"every": k, "training_rows": nt, "held_out_rows": ne, "rounds": args.rounds, "cut_values": int(cuts[0][-1]),
+           "eval_plan": {"training": synth.grow_eval_plan(nt, torch.cuda.get_device_properties(0).multi_processor_count),
+                         "held_out": synth.grow_eval_plan(ne, torch.cuda.get_device_properties(0).multi_processor_count)}}
+    times, nodes, b = timed(lambda b: b.boost_trees_device(dt, yt.data_ptr(), nt, cuts, **pk))
+    out["plain"] = dict(summary(times), nodes_added=nodes)
+    b.free()
+    for name, patience in (("patience_0", 0), (f"patience_{args.patience}", args.patience)):
+        b0 = capi.Booster(model_buffer=model.image)
+        before = None if args.skip_rmse else (own_rmse(b0, dt, xt, yt), own_rmse(b0, de, xe, ye))
+        b0.free()
+        times, r, b = timed(lambda b: b.boost_trees_eval_device(dt, yt.data_ptr(), nt, cuts, eval_set=(de, ye.data_ptr(), ne),
+                                                                patience=patience, **pk))
+        doc = dict(summary(times), rounds_run=r["rounds_run"], best_round=r["best_round"], nodes_added=r["nodes_added"],
+                   train_rmse=r["train_rmse"].tolist(), eval_rmse=r["eval_rmse"].tolist(),
+                   over_plain_s=float(np.median(times)) - out["plain"]["median_s"])
+        if before is not None:
+            # this script's own figures: the forest as loaded, and the forest the call left (its kept trees)
+            kept = r["best_round"] if patience >= 1 else r["rounds_run"]
+            doc["own_rmse"] = {"round_0": {"train": before[0], "eval": before[1]},
+                               f"round_{kept}": {"train": own_rmse(b, dt, xt, yt), "eval": own_rmse(b, de, xe, ye)}}
+        b.free()
+        out[name] = doc
+    for m in (dt, de):
+        m.free()
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "boost_timing.json"))
@@ -46,6 +117,8 @@ def main():
     ap.add_argument("--cuts", choices=("host", "device", "both"), default="both")
     ap.add_argument("--cuts-full", action="store_true", help="also time the device cuts on every row (row_step = 1)")
     ap.add_argument("--skip-rmse", action="store_true", help="time only (a run under a kernel trace)")
+    ap.add_argument("--holdout", type=int, default=0, help="hold out every K-th row and time the call with a held-out set")
+    ap.add_argument("--patience", type=int, default=3, help="with --holdout: the patience of the early-stopping call")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "boost_timing needs the MI355X"
     torch.cuda.set_device(0)
@@ -123,7 +196,10 @@ def main():
                                      reg_lambda=args.reg_lambda, stream=stream)
         return time.perf_counter() - t, nodes
 
-    for rounds in sorted({1, args.rounds}):
+    if args.holdout:
+        res["holdout"] = holdout(args, model, rows, labels, n, F, stream)
+        print("holdout", json.dumps(res["holdout"]), flush=True)
+    for rounds in ([] if args.holdout else sorted({1, args.rounds})):
         first, again, nodes = [], [], 0
         for _ in range(args.reps):
             b = capi.Booster(model_buffer=model.image)
@@ -139,11 +215,11 @@ def main():
         res[f"rounds_{rounds}"] = {"first_call_median_s": float(np.median(first)), "median_s": float(np.median(again)),
                                    "min_s": float(np.min(again)), "max_s": float(np.max(again)), "nodes_added": nodes}
         print(f"rounds_{rounds}", json.dumps(res[f"rounds_{rounds}"]), flush=True)
-    if args.rounds > 1:
+    if args.rounds > 1 and not args.holdout:
         per_round = (res[f"rounds_{args.rounds}"]["median_s"] - res["rounds_1"]["median_s"]) / (args.rounds - 1)
         res["per_round_s"] = per_round
         res["one_off_s"] = res["rounds_1"]["median_s"] - per_round
-    if not args.skip_rmse:
+    if not args.skip_rmse and not args.holdout:
         b = capi.Booster(model_buffer=model.image)
         res["rmse_before"] = rmse(b)
         b.refit_leaves_device(d, labels.data_ptr(), n, eta=1.0, reg_lambda=1.0, stream=stream)
