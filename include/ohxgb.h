@@ -645,6 +645,66 @@ int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, con
                                    float lambda, float gamma, bst_ulong min_child_rows, int patience, double* train_rmse,
                                    double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added,
                                    void* stream);
+/* Boosting with row weights (docs/21_row_weights.md): OHXBoosterBoostTreesEval with a weight per training row and per
+ * held-out row - a fit and an error weighted by air mass or cell area, or a fit that ignores some rows (weight 0)
+ * without a second matrix.  weights holds nlabel floats and eval_weights eval_nlabel floats; either may be NULL, and
+ * NULL means every weight is 1.0f.  Steps that are not restated here are those of OHXBoosterBoostTrees (the cuts, the
+ * bins, steps 2 and 6) and of OHXBoosterBoostTreesEval (the margins, the stop rule, what is kept, the held-out matrix).
+ * Weights and per-row quantities.  w is finite with 0 <= w < 256.  hq = (uint64) rint(w * 2^24), which is < 2^32: the
+ * row's hessian in the gradient's fixed point.  g = pred - y as in step 1; the refusal for g not finite or |g| >= 256
+ * looks at g before the weight, so a zero-weight row with a NaN label is still refused with "label".  gw = g * w is one
+ * float32 multiply, not fused; |gw| >= 256 is refused, and the message says "label".  q = (int64) rint(gw * 2^24):
+ * |q| < 2^32 and at most 2^31 rows keep G inside an int64, exactly as in step 1.
+ * Histograms.  Ghist[p][f][b] is the int64 sum of q and Hhist[p][f][b] the uint64 sum of hq over the node's rows in the
+ * bin; a sum of hq is < 2^63.  Integer adds only (no float atomics, no compare-and-swap): the sums depend on neither
+ * the order of the rows, the launch shape, the form, nor OHXDMatrixSetGrid.
+ * Gain, leaf and node records.  Hd = (double)H * 2^-24, the conversion rounded to nearest even and the scaling exact.
+ * gain(G, H) = (Gd * Gd) / (Hd + (double)lambda) and loss_chg = (gain(L) + gain(R)) - gain(P) as in step 4;
+ * base_weight = (float)( -Gd / (Hd + (double)lambda) ); sum_hess = (float)Hd; the leaf value is base_weight * eta, one
+ * float32 multiply.
+ * Valid candidates.  A candidate is valid when HL > 0 and HR > 0 as integers (so that lambda = 0 never divides by
+ * zero) and HLd >= (double)min_child_weight and HRd >= (double)min_child_weight; min_child_weight is finite and >= 0
+ * and takes the place of min_child_rows.  A node with Hd < 2 * min_child_weight (in double), or one at max_depth, is a
+ * leaf without evaluation.  The total order of the candidates, the tie rule, the node numbering and the record format
+ * are unchanged.
+ * The metric.  e = (int64) rint(g * 2^24) is the unweighted residual of OHXBoosterBoostTreesEval (its q).
+ * S_t = sum_r hq_r * e_r^2 is an exact integer < 2^127 and W = sum_r hq_r; W does not change between rounds.
+ * train_rmse[t] and eval_rmse[t] are sqrt( ((double)S_t * 2^-72) / ((double)W * 2^-24) ): both conversions are from
+ * unsigned __int128, rounded to nearest even; the scalings are exact; the division and the square root are IEEE double.
+ * On the device, with e^2 = a * 2^32 + b (a, b < 2^32) and m = 0xFFFFFFFF, a set keeps three uint64 accumulators a
+ * round: P2 += (hq * a) >> 32; P1 += ((hq * a) & m) + ((hq * b) >> 32); P0 += (hq * b) & m; so that
+ * S = P2 * 2^64 + P1 * 2^32 + P0.  hq, a, b < 2^32, so neither product overflows a uint64; a row adds less than 2^32 to
+ * P2, to P0 and to W and at most 2^33 - 2 to P1, so at 2^31 rows P2, P0 and W stay below 2^63 and P1 at or below
+ * 2^64 - 2^32: none of the accumulators can overflow.  The stop rule compares the exact S_eval[t], strictly, as for
+ * OHXBoosterBoostTreesEval.
+ * Consequences.  With all weights 1.0f (or NULL) and min_child_weight = (float)min_child_rows, the forest,
+ * XGBoosterSaveModel's bytes in all three formats and both RMSE arrays equal those of OHXBoosterBoostTreesEval (hq is
+ * 2^24, so Hd is the row count and S / W is sum q^2 / n).  A weight-0 row influences no tree and no sum.  A weight of 2
+ * or 4 equals that many copies of the row in every sum of the metric, and in every histogram wherever g * 2^24 is a
+ * whole number (|g| >= 0.5, or pred and y on the 2^-24 grid): rint(w * x) = w * rint(x) needs that, and a smaller g with
+ * bits below 2^-24 may differ from its copies by one unit of q.
+ * Refused, with the forest and every output untouched: everything OHXBoosterBoostTreesEval refuses, in the same order
+ * (min_child_weight not finite or negative stands where min_child_rows < 1 stood); eval_weights given without a
+ * held-out matrix; a weight that is not finite, is negative or is >= 256 (the message says "weight" for the training
+ * set and "eval weight" for the held-out set); a training set whose W is 0, or a held-out set whose W is 0.
+ * Everything else is OHXBoosterBoostTreesEval's: all or nothing; what a success drops; patience == 0 waits once, at the
+ * end, and patience >= 1 waits once a round; eval_dmat == NULL works as there, and eval_weights must then be NULL.  Not
+ * capturable.  The host form stages the weights with the labels; the device form takes d_weights and d_eval_weights in
+ * HBM (or NULL), ready on `stream`.  The staged weights and the wider sums are part of the grow state.  Calls on ONE
+ * booster must not run concurrently. */
+int OHXBoosterBoostTreesWeighted(BoosterHandle handle, DMatrixHandle dmat, const float* labels, const float* weights,
+                                 bst_ulong nlabel, DMatrixHandle eval_dmat, const float* eval_labels,
+                                 const float* eval_weights, bst_ulong eval_nlabel, const bst_ulong* cut_ptr,
+                                 const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
+                                 float min_child_weight, int patience, double* train_rmse, double* eval_rmse,
+                                 int* rounds_run, int* best_round, bst_ulong* nodes_added);
+int OHXBoosterBoostTreesWeightedDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels,
+                                       const float* d_weights, bst_ulong nlabel, DMatrixHandle eval_dmat,
+                                       const float* d_eval_labels, const float* d_eval_weights, bst_ulong eval_nlabel,
+                                       const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth,
+                                       float eta, float lambda, float gamma, float min_child_weight, int patience,
+                                       double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
+                                       bst_ulong* nodes_added, void* stream);
 int OHXQuantileCuts(const float* data, bst_ulong nrow, bst_ulong ncol, float missing, int max_bins, bst_ulong* cut_ptr,
                     float* cut_values, bst_ulong cap, bst_ulong* needed);
 /* OHXDMatrixQuantileCuts (docs/19_device_cuts.md) makes the same cuts from a DMatrix's rows where they lie, in HBM: no

@@ -651,7 +651,7 @@ struct RefitState {
 // first call on the loaded model; never a buffer of another path.
 struct GrowState {
   int device = -1;
-  bool prepared = false;
+  bool prepared = false, prepared_weighted = false;
   DevBuf<uint8_t> d_bins;
   DevBuf<uint16_t> d_pos;
   DevBuf<float> d_pred, d_labels, d_cuts;
@@ -670,19 +670,25 @@ struct GrowState {
   DevBuf<float> d_eval_pred, d_eval_labels;
   DevBuf<unsigned long long> d_sums;
   PinnedBuf<unsigned long long> h_sums;
+  // row weights (OHXBoosterBoostTreesWeighted): the staged weights of both sets, and W of both sets followed by the
+  // sums [rounds + 1][2 sets][p2, p1, p0]
+  DevBuf<float> d_weights, d_eval_weights;
+  DevBuf<unsigned long long> d_wsums;
+  PinnedBuf<unsigned long long> h_wsums;
   void release_device() {
     d_bins.release();
     d_pos.release();
     d_eval_bins.release();
     d_sums.release();
-    for (DevBuf<float>* f : {&d_pred, &d_labels, &d_cuts, &d_eval_pred, &d_eval_labels}) f->release();
+    d_wsums.release();
+    for (DevBuf<float>* f : {&d_pred, &d_labels, &d_cuts, &d_eval_pred, &d_eval_labels, &d_weights, &d_eval_weights}) f->release();
     for (DevBuf<uint32_t>* f : {&d_cut_ptr, &d_tree_nodes, &d_saved_flag}) f->release();
     d_Ghist.release();
     d_Hhist.release();
     d_best.release();
     d_nodes.release();
     d_state.release();
-    prepared = false;
+    prepared = prepared_weighted = false;
   }
 };
 
@@ -2203,14 +2209,24 @@ struct BoostEval {
   int* best_round = nullptr;
 };
 
-// Both forms of OHXBoosterBoostTrees, and of OHXBoosterBoostTreesEval where `ev` is given.  The refusals that need
+// What OHXBoosterBoostTreesWeighted adds to a call with `ev`: the weights of both sets (either may be NULL: all 1.0f)
+// and min_child_weight in place of min_child_rows.
+struct BoostWeights {
+  const float* weights = nullptr;
+  const float* eval_weights = nullptr;
+  float min_child_weight = 0.0f;
+};
+
+// Both forms of OHXBoosterBoostTrees, of OHXBoosterBoostTreesEval where `ev` is given, and of
+// OHXBoosterBoostTreesWeighted where `wt` is given too (then min_child_rows is not looked at).  The refusals that need
 // neither a matrix nor a device come first, in the header's order; nothing is enqueued before the last of them.
-// Without `ev` nothing of the metric is allocated or enqueued.
+// Without `ev` nothing of the metric is allocated or enqueued; without `wt` nothing of the weights.
 void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulong nlabel, const bst_ulong* cut_ptr,
                  const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
                  bst_ulong min_child_rows, bst_ulong* nodes_added, bool host_form, hipStream_t caller, const char* what,
-                 const BoostEval* ev = nullptr) {
+                 const BoostEval* ev = nullptr, const BoostWeights* wt = nullptr) {
   const std::string w0(what);
+  if (wt != nullptr && ev == nullptr) throw OhxError(w0 + ": the weighted call carries the metric");
   if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
   refuse_categorical(b, what);
   refuse_groups(b, what);
@@ -2228,7 +2244,9 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   if (!std::isfinite(eta)) throw OhxError(w0 + ": eta must be finite");
   if (!(std::isfinite(lambda) && lambda >= 0.0f)) throw OhxError(w0 + ": lambda must be finite and >= 0");
   if (!(std::isfinite(gamma) && gamma >= 0.0f)) throw OhxError(w0 + ": gamma must be finite and >= 0");
-  if (min_child_rows < 1) throw OhxError(w0 + ": min_child_rows must be >= 1");
+  if (wt == nullptr && min_child_rows < 1) throw OhxError(w0 + ": min_child_rows must be >= 1");
+  if (wt != nullptr && !(std::isfinite(wt->min_child_weight) && wt->min_child_weight >= 0.0f))
+    throw OhxError(w0 + ": min_child_weight must be finite and >= 0");
   grow_check_cuts(cut_ptr, cut_values, F, what);
   if (ev != nullptr) {
     if (ev->patience < 0) throw OhxError(w0 + ": patience must be >= 0");
@@ -2238,6 +2256,8 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
         throw OhxError(w0 + ": patience " + std::to_string(ev->patience) + " needs a held-out matrix to stop on (eval_dmat is NULL)");
       if (ev->labels != nullptr || ev->nlabel != 0)
         throw OhxError(w0 + ": eval labels are given without a held-out matrix (eval_dmat is NULL)");
+      if (wt != nullptr && wt->eval_weights != nullptr)
+        throw OhxError(w0 + ": eval weights are given without a held-out matrix (eval_dmat is NULL)");
     } else if (ev->labels == nullptr) {
       throw OhxError(w0 + ": eval labels is NULL");
     }
@@ -2277,9 +2297,13 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     HIP_CHECK((hipError_t)prepare_grow());
     g.prepared = true;
   }
+  if (wt != nullptr && !g.prepared_weighted) {
+    HIP_CHECK((hipError_t)prepare_grow_weighted());
+    g.prepared_weighted = true;
+  }
   const uint64_t n = d.nrow, ncuts = cut_ptr[F];
   const size_t R = (size_t)rounds;
-  const GrowPlan plan = plan_grow(n, F, ncuts, max_depth, dev.num_cus);
+  const GrowPlan plan = wt != nullptr ? plan_grow_weighted(n, F, ncuts, max_depth, dev.num_cus) : plan_grow(n, F, ncuts, max_depth, dev.num_cus);
   auto room = [&](auto& buf, size_t count, size_t elem, const char* name) {
     try {
       buf.ensure(count);
@@ -2292,12 +2316,18 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   room(g.d_pred, n, 4, "the running margin");
   if (host_form) room(g.d_labels, n, 4, "the staged labels");
   room(g.d_Ghist, (size_t)(plan.hist_bytes / 16), 8, "the gradient histograms");
-  room(g.d_Hhist, (size_t)(plan.hist_bytes / 16), 8, "the count histograms");
+  room(g.d_Hhist, (size_t)(plan.hist_bytes / 16), 8, wt != nullptr ? "the hessian histograms" : "the count histograms");
   room(g.d_best, (size_t)(1u << (max_depth - 1)) * F, sizeof(GrowCand), "the split candidates");
   room(g.d_nodes, R * kGrowMaxNodes, sizeof(GrowNode), "the node records");
   const uint64_t ne = e != nullptr ? e->nrow : 0;
-  const size_t nsums = (R + 1) * 4;
+  const size_t nsums = (R + 1) * 4, nwsums = grow_wide_count(R);
   GrowPlan eplan;                    // the held-out rows' binning
+  if (wt != nullptr) {
+    if (host_form && wt->weights != nullptr) room(g.d_weights, n, 4, "the staged weights");
+    if (host_form && wt->eval_weights != nullptr) room(g.d_eval_weights, ne, 4, "the staged eval weights");
+    room(g.d_wsums, nwsums, 8, "the weighted metric sums");
+    g.h_wsums.ensure(nwsums);
+  }
   if (ev != nullptr) {
     if (e != nullptr) {
       eplan = plan_grow(ne, F, ncuts, max_depth, dev.num_cus);
@@ -2305,8 +2335,10 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
       room(g.d_eval_pred, ne, 4, "the held-out margin");
       if (host_form) room(g.d_eval_labels, ne, 4, "the staged eval labels");
     }
-    room(g.d_sums, nsums, 8, "the metric sums");
-    g.h_sums.ensure(nsums);
+    if (wt == nullptr) {
+      room(g.d_sums, nsums, 8, "the metric sums");
+      g.h_sums.ensure(nsums);
+    }
   }
   g.d_tree_nodes.ensure(R);
   g.d_cuts.ensure(std::max<size_t>(ncuts, 1));
@@ -2340,7 +2372,14 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     launch_predict_checked(b, d, 1, 0, g.d_pred.p, stream);
     HIP_CHECK(hipMemcpyAsync(b.d_flags.p, g.d_saved_flag.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
   }
-  if (ev != nullptr) HIP_CHECK(hipMemsetAsync(g.d_sums.p, 0, nsums * sizeof(unsigned long long), stream));
+  if (ev != nullptr && wt == nullptr) HIP_CHECK(hipMemsetAsync(g.d_sums.p, 0, nsums * sizeof(unsigned long long), stream));
+  if (wt != nullptr) {
+    HIP_CHECK(hipMemsetAsync(g.d_wsums.p, 0, nwsums * sizeof(unsigned long long), stream));
+    if (host_form && wt->weights != nullptr)
+      HIP_CHECK(hipMemcpyAsync(g.d_weights.p, wt->weights, n * sizeof(float), hipMemcpyHostToDevice, stream));
+    if (host_form && wt->eval_weights != nullptr)
+      HIP_CHECK(hipMemcpyAsync(g.d_eval_weights.p, wt->eval_weights, ne * sizeof(float), hipMemcpyHostToDevice, stream));
+  }
   if (e != nullptr) {
     // the held-out rows get what the training rows got: staged labels, and the margin of the forest so far
     if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_eval_labels.p, ev->labels, ne * sizeof(float), hipMemcpyHostToDevice, stream));
@@ -2377,12 +2416,22 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   a.eta = eta;
   a.lambda = lambda;
   a.gamma = gamma;
-  a.min_child_rows = min_child_rows;
+  a.min_child_rows = wt != nullptr ? 1 : min_child_rows;
+  GrowWeightedArgs aw;                 // the level loop with weights
+  aw.g = a;
+  if (wt != nullptr) {
+    aw.weights = wt->weights == nullptr ? nullptr : host_form ? g.d_weights.p : wt->weights;
+    aw.min_child_weight = (double)wt->min_child_weight;
+  }
+  // one tree, and one set's sums after t trees, by the kernels of the call at hand
+  auto grow_tree = [&](uint32_t r) {
+    return (hipError_t)(wt != nullptr ? launch_grow_tree_weighted(aw, plan, r, stream) : launch_grow_tree(a, plan, r, stream));
+  };
   hipError_t launched = (hipError_t)launch_grow_bin(a, plan, stream);
   hipError_t waited = hipSuccess;
   uint32_t run = (uint32_t)rounds, best = 0;   // rounds grown, and the best of them by the held-out sums
   if (ev == nullptr) {
-    for (uint32_t r = 0; launched == hipSuccess && r < (uint32_t)rounds; ++r) launched = (hipError_t)launch_grow_tree(a, plan, r, stream);
+    for (uint32_t r = 0; launched == hipSuccess && r < (uint32_t)rounds; ++r) launched = grow_tree(r);
   } else {
     // the metric: the training rows' sums after every leaf kernel, the held-out rows' walk of every new tree, and both
     // sets' sums of the forest as loaded
@@ -2398,6 +2447,7 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     mt.max_depth = max_depth;
     mt.label_flag = kGrowFlagLabel;
     GrowEvalArgs me = mt;
+    GrowWeightedEvalArgs wmt, wme;   // the same with weights: the wide sums
     const uint32_t tblocks = plan_grow_eval_blocks(n, dev.num_cus);
     uint32_t eblocks = 0;
     if (e != nullptr) {
@@ -2417,21 +2467,45 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
       me.nrow = ne;
       me.label_flag = kGrowFlagEvalLabel;
       eblocks = plan_grow_eval_blocks(ne, dev.num_cus);
-      if (launched == hipSuccess) launched = (hipError_t)launch_grow_sse(me, eblocks, 0, kGrowEvalHeldOut, stream);
     }
-    if (launched == hipSuccess) launched = (hipError_t)launch_grow_sse(mt, tblocks, 0, kGrowEvalTrain, stream);
+    if (wt != nullptr) {
+      wmt.e = mt;
+      wmt.weights = aw.weights;
+      wmt.wsums = g.d_wsums.p;
+      wmt.weight_flag = kGrowFlagWeight;
+      wme.e = me;
+      wme.weights = wt->eval_weights == nullptr ? nullptr : host_form ? g.d_eval_weights.p : wt->eval_weights;
+      wme.wsums = g.d_wsums.p;
+      wme.weight_flag = kGrowFlagEvalWeight;
+    }
+    auto sum_train = [&](uint32_t t) {
+      return (hipError_t)(wt != nullptr ? launch_grow_sse_weighted(wmt, tblocks, t, kGrowEvalTrain, stream)
+                                        : launch_grow_sse(mt, tblocks, t, kGrowEvalTrain, stream));
+    };
+    // where the held-out sums of round t lie, and how many words they are
+    const unsigned long long* d_all = wt != nullptr ? g.d_wsums.p : g.d_sums.p;
+    unsigned long long* h_all = wt != nullptr ? g.h_wsums.p : g.h_sums.p;
+    const size_t nall = wt != nullptr ? nwsums : nsums, words = wt != nullptr ? 3 : 2;
+    auto held_at = [&](uint32_t t) { return wt != nullptr ? grow_wide_index(t, kGrowEvalHeldOut) : grow_sum_index(t, kGrowEvalHeldOut); };
+    if (launched == hipSuccess && e != nullptr)
+      launched = (hipError_t)(wt != nullptr ? launch_grow_sse_weighted(wme, eblocks, 0, kGrowEvalHeldOut, stream)
+                                            : launch_grow_sse(me, eblocks, 0, kGrowEvalHeldOut, stream));
+    if (launched == hipSuccess) launched = sum_train(0);
     std::vector<GrowSum> S(R + 1);   // the held-out sums, as far as they are known (patience >= 1)
+    std::vector<GrowWideSum> WS(wt != nullptr ? R + 1 : 0);
     const bool stepwise = ev->patience >= 1;
     for (uint32_t r = 0; launched == hipSuccess && waited == hipSuccess && r < (uint32_t)rounds; ++r) {
-      launched = (hipError_t)launch_grow_tree(a, plan, r, stream);
-      if (launched == hipSuccess) launched = (hipError_t)launch_grow_sse(mt, tblocks, r + 1, kGrowEvalTrain, stream);
-      if (launched == hipSuccess && e != nullptr) launched = (hipError_t)launch_grow_walk_sse(me, eblocks, r, kGrowEvalHeldOut, stream);
+      launched = grow_tree(r);
+      if (launched == hipSuccess) launched = sum_train(r + 1);
+      if (launched == hipSuccess && e != nullptr)
+        launched = (hipError_t)(wt != nullptr ? launch_grow_walk_sse_weighted(wme, eblocks, r, kGrowEvalHeldOut, stream)
+                                              : launch_grow_walk_sse(me, eblocks, r, kGrowEvalHeldOut, stream));
       if (!stepwise || launched != hipSuccess) continue;
       // one small wait a round: this round's held-out sums (and round 0's, the first time) and the error word
       const uint32_t t0 = r == 0 ? 0 : r + 1;
       for (uint32_t t = t0; launched == hipSuccess && t <= r + 1; ++t) {
-        const size_t at = grow_sum_index(t, kGrowEvalHeldOut);
-        launched = hipMemcpyAsync(g.h_sums.p + at, g.d_sums.p + at, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
+        const size_t at = held_at(t);
+        launched = hipMemcpyAsync(h_all + at, d_all + at, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
       }
       if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_state.p, g.d_state.p, sizeof(GrowLevelState), hipMemcpyDeviceToHost, stream);
       if (launched != hipSuccess) break;
@@ -2442,18 +2516,24 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
         break;
       }
       for (uint32_t t = t0; t <= r + 1; ++t) {
-        const size_t at = grow_sum_index(t, kGrowEvalHeldOut);
-        S[t].hi = g.h_sums.p[at];
-        S[t].lo = g.h_sums.p[at + 1];
+        const size_t at = held_at(t);
+        if (wt != nullptr) {
+          WS[t].p2 = h_all[at];
+          WS[t].p1 = h_all[at + 1];
+          WS[t].p0 = h_all[at + 2];
+        } else {
+          S[t].hi = h_all[at];
+          S[t].lo = h_all[at + 1];
+        }
       }
-      best = grow_eval_best(S.data(), best, r + 1);
+      best = wt != nullptr ? grow_eval_best(WS.data(), best, r + 1) : grow_eval_best(S.data(), best, r + 1);
       if (grow_eval_stops(best, r + 1, ev->patience)) {
         run = r + 1;
         break;
       }
     }
     if (launched == hipSuccess && waited == hipSuccess)
-      launched = hipMemcpyAsync(g.h_sums.p, g.d_sums.p, nsums * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
+      launched = hipMemcpyAsync(h_all, d_all, nall * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
   }
   if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_nodes.p, g.d_nodes.p, R * kGrowMaxNodes * sizeof(GrowNode), hipMemcpyDeviceToHost, stream);
   if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_tree_nodes.p, g.d_tree_nodes.p, R * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
@@ -2474,19 +2554,40 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   if (flags & kGrowFlagEvalLabel)
     throw OhxError(w0 + ": a held-out residual pred - eval label is not finite or reaches 256 in size at some row and round: "
                    "look for an eval label that is NaN, infinite or far from the model's range; the forest is unchanged");
+  if (flags & kGrowFlagWeight)
+    throw OhxError(w0 + ": a weight is not finite, is negative or reaches 256 at some training row; the forest is unchanged");
+  if (flags & kGrowFlagEvalWeight)
+    throw OhxError(w0 + ": an eval weight is not finite, is negative or reaches 256 at some held-out row; the forest is unchanged");
   if (flags != 0) throw OhxError(w0 + ": the grow kernels reported error flags " + std::to_string(flags));
+  if (wt != nullptr) {
+    if (g.h_wsums.p[kGrowEvalTrain] == 0ull)
+      throw OhxError(w0 + ": the weights of the training rows sum to 0 (every rint(w * 2^24) is 0); the forest is unchanged");
+    if (e != nullptr && g.h_wsums.p[kGrowEvalHeldOut] == 0ull)
+      throw OhxError(w0 + ": the eval weights of the held-out rows sum to 0 (every rint(w * 2^24) is 0); the forest is unchanged");
+  }
   // all or nothing: every round is done and the error word is clean
   size_t keep = R;                     // the trees that are appended
   if (ev != nullptr) {
     if (e != nullptr) {
       // the shared rule over the whole list, from the exact integers: what the round-by-round loop decided
-      std::vector<GrowSum> S(run + 1);
-      for (uint32_t t = 0; t <= run; ++t) {
-        S[t].hi = g.h_sums.p[grow_sum_index(t, kGrowEvalHeldOut)];
-        S[t].lo = g.h_sums.p[grow_sum_index(t, kGrowEvalHeldOut) + 1];
-      }
       uint32_t run_again = 0;
-      grow_eval_stop(S.data(), run, ev->patience, &run_again, &best);
+      if (wt != nullptr) {
+        std::vector<GrowWideSum> S(run + 1);
+        for (uint32_t t = 0; t <= run; ++t) {
+          const unsigned long long* s = g.h_wsums.p + grow_wide_index(t, kGrowEvalHeldOut);
+          S[t].p2 = s[0];
+          S[t].p1 = s[1];
+          S[t].p0 = s[2];
+        }
+        grow_eval_stop(S.data(), run, ev->patience, &run_again, &best);
+      } else {
+        std::vector<GrowSum> S(run + 1);
+        for (uint32_t t = 0; t <= run; ++t) {
+          S[t].hi = g.h_sums.p[grow_sum_index(t, kGrowEvalHeldOut)];
+          S[t].lo = g.h_sums.p[grow_sum_index(t, kGrowEvalHeldOut) + 1];
+        }
+        grow_eval_stop(S.data(), run, ev->patience, &run_again, &best);
+      }
       if (run_again != run) throw OhxError(w0 + ": the stop rule gave " + std::to_string(run_again) + " rounds over the sums of " + std::to_string(run));
       if (ev->patience >= 1) keep = best;
     } else {
@@ -2520,7 +2621,19 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   }
   if (nodes_added != nullptr) *nodes_added = added;
   if (ev != nullptr) {
-    for (uint32_t t = 0; t <= run; ++t) {
+    for (uint32_t t = 0; wt != nullptr && t <= run; ++t) {
+      const unsigned long long* s = g.h_wsums.p + grow_wide_index(t, kGrowEvalTrain);
+      GrowWideSum tr, he;
+      tr.p2 = s[0];
+      tr.p1 = s[1];
+      tr.p0 = s[2];
+      he.p2 = s[3];
+      he.p1 = s[4];
+      he.p0 = s[5];
+      if (ev->train_rmse != nullptr) ev->train_rmse[t] = grow_wide_rmse(tr, g.h_wsums.p[kGrowEvalTrain]);
+      if (ev->eval_rmse != nullptr && e != nullptr) ev->eval_rmse[t] = grow_wide_rmse(he, g.h_wsums.p[kGrowEvalHeldOut]);
+    }
+    for (uint32_t t = 0; wt == nullptr && t <= run; ++t) {
       const unsigned long long* s = g.h_sums.p + grow_sum_index(t, kGrowEvalTrain);
       GrowSum tr, he;
       tr.hi = s[0];
@@ -3257,6 +3370,59 @@ int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, con
   ev.best_round = best_round;
   boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows,
               nodes_added, false, static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesEvalDevice", &ev);
+  API_END();
+}
+
+int OHXBoosterBoostTreesWeighted(BoosterHandle handle, DMatrixHandle dmat, const float* labels, const float* weights,
+                                 bst_ulong nlabel, DMatrixHandle eval_dmat, const float* eval_labels,
+                                 const float* eval_weights, bst_ulong eval_nlabel, const bst_ulong* cut_ptr,
+                                 const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
+                                 float min_child_weight, int patience, double* train_rmse, double* eval_rmse,
+                                 int* rounds_run, int* best_round, bst_ulong* nodes_added) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  BoostEval ev;
+  ev.dmat = eval_dmat;
+  ev.labels = eval_labels;
+  ev.nlabel = eval_nlabel;
+  ev.patience = patience;
+  ev.train_rmse = train_rmse;
+  ev.eval_rmse = eval_rmse;
+  ev.rounds_run = rounds_run;
+  ev.best_round = best_round;
+  BoostWeights wt;
+  wt.weights = weights;
+  wt.eval_weights = eval_weights;
+  wt.min_child_weight = min_child_weight;
+  boost_trees(*b, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, 1, nodes_added, true,
+              nullptr, "OHXBoosterBoostTreesWeighted", &ev, &wt);
+  API_END();
+}
+
+int OHXBoosterBoostTreesWeightedDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels,
+                                       const float* d_weights, bst_ulong nlabel, DMatrixHandle eval_dmat,
+                                       const float* d_eval_labels, const float* d_eval_weights, bst_ulong eval_nlabel,
+                                       const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth,
+                                       float eta, float lambda, float gamma, float min_child_weight, int patience,
+                                       double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
+                                       bst_ulong* nodes_added, void* stream) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  BoostEval ev;
+  ev.dmat = eval_dmat;
+  ev.labels = d_eval_labels;
+  ev.nlabel = eval_nlabel;
+  ev.patience = patience;
+  ev.train_rmse = train_rmse;
+  ev.eval_rmse = eval_rmse;
+  ev.rounds_run = rounds_run;
+  ev.best_round = best_round;
+  BoostWeights wt;
+  wt.weights = d_weights;
+  wt.eval_weights = d_eval_weights;
+  wt.min_child_weight = min_child_weight;
+  boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, 1, nodes_added, false,
+              static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesWeightedDevice", &ev, &wt);
   API_END();
 }
 

@@ -77,6 +77,21 @@ GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t num_featu
   return best;
 }
 
+GrowCand grow_node_split_weighted(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr,
+                                  int64_t Gp, uint64_t Hp, float lambda, float min_child_weight) {
+  GrowCand best;
+  if (!grow_weight_splits(Hp, (double)min_child_weight)) return best;
+  for (uint32_t f = 0; f < num_feature; ++f) {
+    const int64_t* g = G + (size_t)f * kGrowBins;
+    const uint64_t* h = H + (size_t)f * kGrowBins;
+    const uint32_t ncut = (uint32_t)(cut_ptr[f + 1] - cut_ptr[f]);
+    const GrowCand c = grow_best_split_weighted(g, h, f, 0, ncut, ncut, 0, 0, g[kGrowMissingBin], h[kGrowMissingBin], Gp,
+                                                Hp, (double)lambda, (double)min_child_weight);
+    if (grow_better(c, best)) best = c;
+  }
+  return best;
+}
+
 Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature) {
   if (n == 0 || n > kGrowMaxNodes || n % 2 == 0) throw OhxError("grown tree: " + std::to_string(n) + " nodes is not a tree");
   Tree t;
@@ -111,7 +126,11 @@ Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature)
   return t;
 }
 
-GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus) {
+namespace {
+
+// the plan for histograms of pair_bytes a (node, feature) pair in LDS
+GrowPlan plan_grow_pairs(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus, uint32_t pair_bytes) {
+  const uint32_t max_pairs = kGrowLdsBytes / pair_bytes;
   GrowPlan p;
   const uint64_t cus = num_cus > 0 ? (uint64_t)num_cus : 1;
   const uint64_t want = (nrow + kGrowBlock - 1) / kGrowBlock, cap = cus * kGrowRowBlocksPerCu;
@@ -124,12 +143,12 @@ GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_
     l.slots = 1u << d;
     // all of a level's nodes in one block where they fit, then as many features as LDS still holds: a block reads pos,
     // pred and the label of every row once per group, and the bins of its own features only
-    l.node_group = std::min(l.slots, kGrowMaxPairs);
-    l.feat_group = std::max(1u, std::min(F, kGrowMaxPairs / l.node_group));
+    l.node_group = std::min(l.slots, max_pairs);
+    l.feat_group = std::max(1u, std::min(F, max_pairs / l.node_group));
     l.node_groups = (l.slots + l.node_group - 1) / l.node_group;
     l.feat_groups = (F + l.feat_group - 1) / l.feat_group;
     l.feat_group = (F + l.feat_groups - 1) / l.feat_groups;     // the same number of groups, evenly filled
-    l.lds_bytes = l.node_group * l.feat_group * kGrowPairBytes;
+    l.lds_bytes = l.node_group * l.feat_group * pair_bytes;
     const uint64_t groups = (uint64_t)l.node_groups * l.feat_groups;
     const uint64_t hwant = (nrow + kGrowHistBlock - 1) / kGrowHistBlock;
     const uint64_t hcap = std::max<uint64_t>(1, cus * kGrowHistBlocksPerCu / groups);
@@ -139,6 +158,16 @@ GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_
     p.hist_bytes = (uint64_t)l.slots * F * kGrowBins * 16;
   }
   return p;
+}
+
+}  // namespace
+
+GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus) {
+  return plan_grow_pairs(nrow, num_feature, ncuts, max_depth, num_cus, kGrowPairBytes);
+}
+
+GrowPlan plan_grow_weighted(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus) {
+  return plan_grow_pairs(nrow, num_feature, ncuts, max_depth, num_cus, kGrowWeightedPairBytes);
 }
 
 uint32_t plan_grow_eval_blocks(uint64_t nrow, int num_cus) {
@@ -151,6 +180,11 @@ double grow_sum_rmse(GrowSum s, uint64_t n) {
   s = grow_sum_normal(s);
   const unsigned __int128 S = ((unsigned __int128)s.hi << 32) + (unsigned __int128)s.lo;
   return std::sqrt((double)S * (1.0 / 281474976710656.0) / (double)n);
+}
+
+double grow_wide_rmse(GrowWideSum s, uint64_t W) {
+  const unsigned __int128 S = grow_wide_value(s);
+  return std::sqrt(((double)S * (1.0 / 4722366482869645213696.0)) / ((double)(unsigned __int128)W * (1.0 / 16777216.0)));
 }
 
 }  // namespace ohx

@@ -341,4 +341,17 @@ int launch_grow_tree(const GrowArgs& a, const GrowPlan& plan, uint32_t round, vo
   return hipGetLastError();
 }
 
+int launch_grow_partition(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream_) {
+  if (a.nrow == 0 || a.nrow > kRefitMaxRows || a.num_feature == 0 || a.num_feature > kGrowMaxFeatures || plan.row_blocks == 0)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grow_partition_kernel, dim3(plan.row_blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream_), a, round);
+  return hipGetLastError();
+}
+
+int launch_grow_leaf(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream_) {
+  if (a.nrow == 0 || a.nrow > kRefitMaxRows || plan.row_blocks == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grow_leaf_kernel, dim3(plan.row_blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream_), a, round);
+  return hipGetLastError();
+}
+
 }  // namespace ohx

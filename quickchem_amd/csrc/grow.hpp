@@ -27,6 +27,8 @@ constexpr uint32_t kGrowMaxNodes = 512;        // node records kept per tree (a 
 constexpr uint32_t kGrowFlagLabel = 1u;        // the error word: a gradient out of range (refit.hpp kRefitFlagLabel)
 constexpr uint32_t kGrowFlagState = 2u;        // a node id or a bin outside its table (never, from sound buffers)
 constexpr uint32_t kGrowFlagEvalLabel = 4u;    // the same as kGrowFlagLabel at a held-out row
+constexpr uint32_t kGrowFlagWeight = 8u;       // a training row's weight that is not finite, negative or >= 256
+constexpr uint32_t kGrowFlagEvalWeight = 16u;  // the same at a held-out row
 
 // gain(G, H) of the header: CalcGain of xgboost 1.6.0 with reg_alpha = 0 and max_delta_step = 0, on the fixed-point sum
 OHX_GROW_HD inline double grow_gain(int64_t G, uint64_t H, double lambda) {
@@ -85,6 +87,64 @@ OHX_GROW_HD inline GrowCand grow_best_split(const int64_t* G, const uint64_t* H,
   return best;
 }
 
+// ---- row weights (OHXBoosterBoostTreesWeighted; design in docs/21_row_weights.md) ----
+
+// A weight w is finite with 0 <= w < 256; the hessian of its row is hq = (uint64) rint(w * 2^24) < 2^32, and a sum H of
+// up to 2^31 of them stays below 2^63.  Hd = (double)H * 2^-24: the conversion rounds to nearest even, the scaling is
+// exact.
+constexpr float kGrowMaxWeight = 256.0f;
+OHX_GROW_HD inline double grow_hess(uint64_t H) { return (double)H * (1.0 / 16777216.0); }
+// (NaN fails both comparisons)
+OHX_GROW_HD inline bool grow_weight_sound(float w) { return w >= 0.0f && w < kGrowMaxWeight; }
+
+// gain(G, H) with the fixed-point hessian sum
+OHX_GROW_HD inline double grow_gain_weighted(int64_t G, uint64_t H, double lambda) {
+  const double Gd = (double)G * (1.0 / 16777216.0);
+  return (Gd * Gd) / (grow_hess(H) + lambda);
+}
+
+// grow_best_split with fixed-point hessian sums.  A candidate is valid when both children hold weight as integers
+// (HL > 0 and HR > 0: no gain is taken of an empty child, so lambda == 0 divides by no zero) and both have
+// Hd >= min_child_weight.  The order of the visits, grow_key and grow_better are grow_best_split's.
+OHX_GROW_HD inline GrowCand grow_best_split_weighted(const int64_t* G, const uint64_t* H, uint32_t f, uint32_t j0, uint32_t n,
+                                                     uint32_t ncut, int64_t GLb, uint64_t HLb, int64_t Gm, uint64_t Hm,
+                                                     int64_t Gp, uint64_t Hp, double lambda, double min_child_weight) {
+  GrowCand best;
+  const double parent = grow_gain_weighted(Gp, Hp, lambda);
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t j = j0 + k;
+    GLb += G[k];
+    HLb += H[k];
+    if (j >= ncut) continue;
+    for (uint32_t dl = 0; dl < 2; ++dl) {
+      GrowCand c;
+      c.GL = dl ? GLb + Gm : GLb;
+      c.HL = dl ? HLb + Hm : HLb;
+      const int64_t GR = Gp - c.GL;
+      const uint64_t HR = Hp - c.HL;
+      if (c.HL == 0 || HR == 0) continue;
+      if (grow_hess(c.HL) < min_child_weight || grow_hess(HR) < min_child_weight) continue;
+      c.loss_chg = (grow_gain_weighted(c.GL, c.HL, lambda) + grow_gain_weighted(GR, HR, lambda)) - parent;
+      c.key = grow_key(f, j, dl);
+      c.valid = 1;
+      if (grow_better(c, best)) best = c;
+    }
+  }
+  return best;
+}
+
+// A node with Hd < 2 * min_child_weight is a leaf without evaluation
+OHX_GROW_HD inline bool grow_weight_splits(uint64_t Hp, double min_child_weight) {
+  return !(grow_hess(Hp) < 2.0 * min_child_weight);
+}
+
+// refit_solve_leaf with the fixed-point hessian sum: base_weight = (float)(-Gd / (Hd + lambda)), leaf = base_weight * eta
+OHX_GROW_HD inline void grow_solve_leaf_weighted(int64_t G, uint64_t H, float eta, float lambda, float* leaf, float* weight) {
+  const float w = (float)(-((double)G * (1.0 / 16777216.0)) / (grow_hess(H) + (double)lambda));
+  *weight = w;
+  *leaf = w * eta;
+}
+
 // A node as the device leaves it.  Children are written as leaves when their parent splits and overwritten if they
 // split in turn, so every record is complete whenever the level loop stops.
 struct GrowNode {
@@ -112,6 +172,10 @@ void grow_check_cuts(const uint64_t* cut_ptr, const float* cut_values, uint32_t 
 // feature, ascending, replaced by a strictly better one only).
 GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr, int64_t Gp,
                          uint64_t Hp, float lambda, uint64_t min_child_rows);
+// The same over fixed-point hessian histograms (grow_best_split_weighted per feature); a node that
+// grow_weight_splits refuses has no candidate.
+GrowCand grow_node_split_weighted(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr,
+                                  int64_t Gp, uint64_t Hp, float lambda, float min_child_weight);
 // A Tree of the forest from n node records; throws on a record that is not a tree in allocation order.
 Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature);
 
@@ -136,13 +200,15 @@ inline bool grow_sum_less(GrowSum a, GrowSum b) {
   return a.hi != b.hi ? a.hi < b.hi : a.lo < b.lo;
 }
 // One step of the stop rule: the best round once S[t] is known.  Strict: a tie is not an improvement.
-inline uint32_t grow_eval_best(const GrowSum* S, uint32_t best, uint32_t t) { return grow_sum_less(S[t], S[best]) ? t : best; }
+template <class Sum>
+inline uint32_t grow_eval_best(const Sum* S, uint32_t best, uint32_t t) { return grow_sum_less(S[t], S[best]) ? t : best; }
 inline bool grow_eval_stops(uint32_t best, uint32_t t, int patience) {
   return patience >= 1 && t - best >= (uint32_t)patience;
 }
 // The stop rule over the held-out sums S[0 .. rounds]: best starts at 0; after tree t, best = t if S[t] < S[best]; with
 // patience >= 1 the run stops at the first t with t - best >= patience.  Sums past *rounds_run are not looked at.
-inline void grow_eval_stop(const GrowSum* S, uint32_t rounds, int patience, uint32_t* rounds_run, uint32_t* best) {
+template <class Sum>
+inline void grow_eval_stop(const Sum* S, uint32_t rounds, int patience, uint32_t* rounds_run, uint32_t* best) {
   uint32_t b = 0, run = rounds;
   for (uint32_t t = 1; t <= rounds; ++t) {
     b = grow_eval_best(S, b, t);
@@ -158,6 +224,22 @@ inline void grow_eval_stop(const GrowSum* S, uint32_t rounds, int patience, uint
 // scaling, then an IEEE division and square root.
 double grow_sum_rmse(GrowSum s, uint64_t n);
 
+// The weighted sum of squares S = sum hq * e^2 (e the unweighted fixed-point residual) as the device keeps it.  With
+// e^2 = a * 2^32 + b (a, b < 2^32) a row adds (hq * a) >> 32 to p2, ((hq * a) & m) + ((hq * b) >> 32) to p1 and
+// (hq * b) & m to p0, m = 0xFFFFFFFF: S = p2 * 2^64 + p1 * 2^32 + p0 < 2^127.  A row adds less than 2^32 to p2 and p0
+// and at most 2^33 - 2 to p1: with at most 2^31 rows p2, p0 < 2^63 and p1 <= 2^64 - 2^32, so none overflows.
+struct GrowWideSum {
+  uint64_t p2 = 0, p1 = 0, p0 = 0;
+};
+inline unsigned __int128 grow_wide_value(GrowWideSum s) {
+  return ((unsigned __int128)s.p2 << 64) + ((unsigned __int128)s.p1 << 32) + (unsigned __int128)s.p0;
+}
+// a < b as the exact integers (the stop rule's comparison: grow_eval_best and grow_eval_stop take either sum)
+inline bool grow_sum_less(GrowWideSum a, GrowWideSum b) { return grow_wide_value(a) < grow_wide_value(b); }
+// sqrt( ((double)S * 2^-72) / ((double)W * 2^-24) ), W = sum hq: both exact integers rounded to nearest even as they
+// become doubles, exact scalings, then an IEEE division and square root.
+double grow_wide_rmse(GrowWideSum s, uint64_t W);
+
 // ---- the launch plan ----
 
 constexpr uint32_t kGrowBlock = 256;           // bin, split, partition and leaf kernels: a row per lane
@@ -167,6 +249,8 @@ constexpr uint32_t kGrowHistBlocksPerCu = 2;   // over all of gridDim.y
 constexpr uint32_t kGrowLdsBytes = 160 * 1024; // a CU's LDS
 constexpr uint32_t kGrowPairBytes = kGrowBins * (8 + 4);          // one (node, feature) histogram in LDS
 constexpr uint32_t kGrowMaxPairs = kGrowLdsBytes / kGrowPairBytes; // 53
+constexpr uint32_t kGrowWeightedPairBytes = kGrowBins * (8 + 8);                   // with a fixed-point hessian sum
+constexpr uint32_t kGrowWeightedMaxPairs = kGrowLdsBytes / kGrowWeightedPairBytes; // 40
 // a block's 32-bit LDS count of a bin cannot overflow: trips x 1024 rows stay below 2^32
 constexpr uint64_t kGrowMaxTrips = (1ull << 22) - 1;
 
@@ -176,7 +260,7 @@ struct GrowLevelPlan {
   uint32_t feat_group = 0;    // features per block
   uint32_t node_groups = 0, feat_groups = 0;   // gridDim.y = node_groups x feat_groups
   uint32_t hist_blocks = 0;   // gridDim.x: blocks over the rows
-  uint32_t lds_bytes = 0;     // node_group x feat_group x 256 x 12
+  uint32_t lds_bytes = 0;     // node_group x feat_group x 256 x 12 (x 16 in the weighted plan)
 };
 struct GrowPlan {
   uint32_t row_blocks = 0;    // bin, partition and leaf kernels; one trip is row_blocks x 256 rows
@@ -186,6 +270,8 @@ struct GrowPlan {
   uint64_t hist_bytes = 0;    // the deepest level's global histograms: slots x num_feature x 256 x 16
 };
 GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus);
+// the same for grow_hist_weighted_kernel: 16 bytes a bin, at most 40 (node, feature) pairs a block
+GrowPlan plan_grow_weighted(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus);
 // blocks of grow_sse_kernel and grow_walk_sse_kernel over n rows: a row per lane, kGrowBlock lanes, grid-stride
 uint32_t plan_grow_eval_blocks(uint64_t nrow, int num_cus);
 
@@ -227,6 +313,10 @@ int launch_grow_bin(const GrowArgs& a, const GrowPlan& plan, void* stream);
 // Enqueues one tree, round `round`: per level the histogram memsets, the histogram, split and partition kernels, then
 // the leaf kernel (pred += leaf, pos = 0).  pos must be zero and pred the margin so far.  Returns a hipError_t.
 int launch_grow_tree(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
+// Enqueue grow_partition_kernel and grow_leaf_kernel alone, for a level loop of another file (grow_weighted.hip): they
+// read node records and bins, never a histogram or a weight.  Return a hipError_t.
+int launch_grow_partition(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
+int launch_grow_leaf(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
 
 // The metric kernels (grow_eval.hip).  sums is [rounds + 1][2 sets: training, held-out][hi, lo].
 struct GrowEvalArgs {
@@ -249,6 +339,34 @@ int launch_grow_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t
 // Enqueues grow_walk_sse_kernel: the rows of `a` walk tree `round` by their bins, pred += leaf, and
 // sums[round + 1][set] += the squares.  Returns a hipError_t.
 int launch_grow_walk_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream);
+
+// Row weights (grow_weighted.hip).  Hhist holds fixed-point hessian sums, GrowNode.H likewise; g.min_child_rows is not
+// read.
+struct GrowWeightedArgs {
+  GrowArgs g;
+  const float* weights = nullptr;   // [nrow], or nullptr: every weight is 1.0f
+  double min_child_weight = 0.0;
+};
+// Once per device before the first launch: the histogram kernel's dynamic LDS limit.  Returns a hipError_t.
+int prepare_grow_weighted();
+// launch_grow_tree with grow_hist_weighted_kernel and grow_split_weighted_kernel in the level loop; plan is
+// plan_grow_weighted's.  Returns a hipError_t.
+int launch_grow_tree_weighted(const GrowWeightedArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
+
+// The weighted metric.  wsums is [2 sets] W, then [rounds + 1][2 sets][p2, p1, p0]; e.sums is not read.
+struct GrowWeightedEvalArgs {
+  GrowEvalArgs e;
+  const float* weights = nullptr;   // [nrow], or nullptr
+  unsigned long long* wsums = nullptr;
+  uint32_t weight_flag = 0;         // what a weight out of range raises: kGrowFlagWeight or kGrowFlagEvalWeight
+};
+inline size_t grow_wide_index(uint32_t t, uint32_t set) { return 2 + ((size_t)t * 2 + set) * 3; }
+inline size_t grow_wide_count(size_t rounds) { return 2 + (rounds + 1) * 2 * 3; }
+// Enqueues grow_sse_weighted_kernel: wsums[t][set] += hq * e^2 over the rows of `a`; t == 0 also checks the weights
+// and adds W of the set.  Returns a hipError_t.
+int launch_grow_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream);
+// Enqueues grow_walk_sse_weighted_kernel: grow_walk_sse_kernel's walk, then wsums[round + 1][set] += hq * e^2.
+int launch_grow_walk_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream);
 #endif  // __HIPCC__
 
 }  // namespace ohx

@@ -166,3 +166,103 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_eval_plan(uint64_
   info[1] = kGrowBlock;
   return 0;
 }
+
+// ---- row weights ----
+
+// ohx_grow_node_split over fixed-point hessian histograms (grow_node_split_weighted); sums[1] is HL in fixed point
+extern "C" __attribute__((visibility("default"))) int ohx_grow_node_split_weighted(const int64_t* G, const uint64_t* H,
+                                                                                  uint32_t num_feature, const uint64_t* cut_ptr,
+                                                                                  int64_t Gp, uint64_t Hp, float lambda, float gamma,
+                                                                                  float min_child_weight, double* loss_chg,
+                                                                                  uint32_t out[5], uint64_t sums[2]) {
+  try {
+    const GrowCand c = grow_node_split_weighted(G, H, num_feature, cut_ptr, Gp, Hp, lambda, min_child_weight);
+    *loss_chg = c.loss_chg;
+    out[0] = c.valid;
+    out[1] = c.key >> 9;
+    out[2] = (c.key >> 1) & 255u;
+    out[3] = c.key & 1u;
+    out[4] = c.valid && c.loss_chg > (double)gamma ? 1u : 0u;
+    sums[0] = (uint64_t)c.GL;
+    sums[1] = c.HL;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// the weighted leaf solve: out[0] leaf value, out[1] base_weight, out[2] sum_hess
+extern "C" __attribute__((visibility("default"))) void ohx_grow_solve_leaf_weighted(int64_t G, uint64_t H, float eta, float lambda,
+                                                                                   float out[3]) {
+  grow_solve_leaf_weighted(G, H, eta, lambda, &out[0], &out[1]);
+  out[2] = (float)grow_hess(H);
+}
+
+// ohx_grow_plan by plan_grow_weighted
+extern "C" __attribute__((visibility("default"))) int ohx_grow_plan_weighted(uint64_t nrow, uint32_t num_feature, uint64_t ncuts,
+                                                                            int max_depth, int num_cus, uint64_t info[8],
+                                                                            uint64_t* levels) {
+  try {
+    if (max_depth < 1 || max_depth > kGrowMaxDepth) throw OhxError("ohx_grow_plan_weighted: max_depth must be in 1..8");
+    const GrowPlan p = plan_grow_weighted(nrow, num_feature, ncuts, max_depth, num_cus);
+    info[0] = p.row_blocks;
+    info[1] = kGrowBlock;
+    info[2] = p.bin_lds_bytes;
+    info[3] = p.bins_bytes;
+    info[4] = p.hist_bytes;
+    info[5] = kGrowHistBlock;
+    info[6] = kGrowWeightedMaxPairs;
+    info[7] = kGrowWeightedPairBytes;
+    for (size_t d = 0; d < p.levels.size(); ++d) {
+      const GrowLevelPlan& l = p.levels[d];
+      const uint64_t v[7] = {l.slots, l.node_group, l.feat_group, l.node_groups, l.feat_groups, l.hist_blocks, l.lds_bytes};
+      memcpy(levels + d * 7, v, sizeof v);
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// s: (p2, p1, p0); W: the sum of hq
+extern "C" __attribute__((visibility("default"))) double ohx_grow_weighted_rmse(const uint64_t s[3], uint64_t W) {
+  GrowWideSum x;
+  x.p2 = s[0];
+  x.p1 = s[1];
+  x.p0 = s[2];
+  return grow_wide_rmse(x, W);
+}
+
+// -1 / 0 / 1 as a < b, a == b, a > b, as the exact integers p2 * 2^64 + p1 * 2^32 + p0
+extern "C" __attribute__((visibility("default"))) int ohx_grow_weighted_compare(const uint64_t a[3], const uint64_t b[3]) {
+  GrowWideSum x, y;
+  x.p2 = a[0];
+  x.p1 = a[1];
+  x.p0 = a[2];
+  y.p2 = b[0];
+  y.p1 = b[1];
+  y.p0 = b[2];
+  return grow_sum_less(x, y) ? -1 : grow_sum_less(y, x) ? 1 : 0;
+}
+
+// the stop rule over n wide sums (p2, p1, p0).  out: [0] rounds_run, [1] best_round
+extern "C" __attribute__((visibility("default"))) int ohx_grow_weighted_stop(const uint64_t* sums, uint32_t n, int patience,
+                                                                            uint32_t out[2]) {
+  try {
+    if (n == 0) throw OhxError("ohx_grow_weighted_stop: no sums");
+    if (patience < 0) throw OhxError("ohx_grow_weighted_stop: patience must be >= 0");
+    std::vector<GrowWideSum> S(n);
+    for (uint32_t t = 0; t < n; ++t) {
+      S[t].p2 = sums[3 * t];
+      S[t].p1 = sums[3 * t + 1];
+      S[t].p0 = sums[3 * t + 2];
+    }
+    grow_eval_stop(S.data(), n - 1, patience, &out[0], &out[1]);
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}

@@ -1,0 +1,453 @@
+// gfx950 kernels of boosting with row weights (grow.hpp GrowWeightedArgs; design in docs/21_row_weights.md).
+//
+//   grow_hist_weighted_kernel      once per level: grow_hist_kernel with a second fixed-point sum in place of the row
+//                                  count - q = rint(g * w * 2^24) and hq = rint(w * 2^24) go into the block's LDS
+//                                  histogram with two 64-bit integer adds a feature, 16 bytes a bin; the block flushes
+//                                  the bins where either sum is nonzero with 64-bit global adds.
+//   grow_split_weighted_kernel<0>  grow_split_kernel<0> with the weighted gain and validity (grow_best_split_weighted).
+//   grow_split_weighted_kernel<1>  grow_split_kernel<1> with the weighted leaf solve and the min_child_weight rule.
+//   grow_sse_weighted_kernel       grow_sse_kernel with hq * e^2 in three 64-bit registers a lane; the launch for t = 0
+//                                  also checks the weights and sums W.
+//   grow_walk_sse_weighted_kernel  grow_walk_sse_kernel's walk, then the same sums.
+// The partition and leaf kernels read no weight and are grow.hip's own (launch_grow_partition, launch_grow_leaf).
+// Only integer adds: no float atomics, no compare-and-swap loops, and the same trees and sums whatever the order of the
+// rows or the launch shape.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "grow.hpp"
+#include "walk_device.hpp"
+
+namespace ohx {
+
+namespace {
+
+constexpr int kBlock = (int)kGrowBlock;
+constexpr int kHistBlock = (int)kGrowHistBlock;
+constexpr int kWaves = kBlock / kWave;
+constexpr unsigned long long kLow32 = 0xFFFFFFFFull;
+
+// the open nodes of level `level` (as in grow.hip): the root alone at level 0
+__device__ inline void level_range(const GrowArgs& a, uint32_t level, uint32_t* begin, uint32_t* end, uint32_t* next) {
+  if (level == 0) {
+    *begin = 0;
+    *end = 1;
+    *next = 1;
+  } else {
+    *begin = a.state->begin;
+    *end = a.state->end;
+    *next = a.state->next;
+  }
+}
+
+// a row's weight and its fixed-point hessian; false where the weight is out of range
+__device__ inline bool row_weight(const float* weights, uint64_t row, float* w, unsigned long long* hq) {
+  *w = weights != nullptr ? weights[row] : 1.0f;
+  if (!grow_weight_sound(*w)) {
+    *hq = 0ull;
+    return false;
+  }
+  *hq = (unsigned long long)__builtin_rintf(*w * kRefitGradScale);   // < 2^32
+  return true;
+}
+
+// grid (blocks over the rows, node groups x feature groups); dynamic LDS: node_group x feat_group x 256 x (8 + 8)
+__global__ __launch_bounds__(kHistBlock) void grow_hist_weighted_kernel(GrowWeightedArgs wa, uint32_t level, uint32_t node_group,
+                                                                        uint32_t feat_group, uint32_t feat_groups) {
+  extern __shared__ unsigned long long grow_whist[];
+  const GrowArgs& a = wa.g;
+  uint32_t begin, end, next;
+  level_range(a, level, &begin, &end, &next);
+  const uint32_t count = end - begin;
+  const uint32_t slot0 = (blockIdx.y / feat_groups) * node_group;
+  const uint32_t f0 = (blockIdx.y % feat_groups) * feat_group;
+  if (slot0 >= count || f0 >= a.num_feature) return;
+  const uint32_t nslots = count - slot0 < node_group ? count - slot0 : node_group;
+  const uint32_t nf = a.num_feature - f0 < feat_group ? a.num_feature - f0 : feat_group;
+  const uint32_t cells = node_group * feat_group * kGrowBins;
+  unsigned long long* Gl = grow_whist;
+  unsigned long long* Hl = grow_whist + cells;
+  for (uint32_t i = threadIdx.x; i < 2u * cells; i += kHistBlock) grow_whist[i] = 0ull;
+  __syncthreads();
+  const uint32_t first = begin + slot0;
+  uint32_t flags = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kHistBlock;
+  for (uint64_t row = (uint64_t)blockIdx.x * kHistBlock + threadIdx.x; row < a.nrow; row += stride) {
+    const uint32_t s = (uint32_t)a.pos[row] - first;   // (a node below `first` wraps past nslots)
+    if (s >= nslots) continue;
+    const float g = a.pred[row] - a.labels[row];
+    // the gradient before the weight (a NaN fails the comparison)
+    if (!(__builtin_fabsf(g) < kRefitMaxAbsGrad)) {
+      flags |= kGrowFlagLabel;
+      continue;
+    }
+    float w;
+    unsigned long long hq;
+    if (!row_weight(wa.weights, row, &w, &hq)) {
+      flags |= kGrowFlagWeight;
+      continue;
+    }
+    const float gw = g * w;   // one float32 multiply (-ffp-contract=off)
+    if (!(__builtin_fabsf(gw) < kRefitMaxAbsGrad)) {
+      flags |= kGrowFlagLabel;
+      continue;
+    }
+    const unsigned long long q = (unsigned long long)(long long)__builtin_rintf(gw * kRefitGradScale);
+    if (hq == 0ull && q == 0ull) continue;   // nothing to add
+    const uint8_t* bin = a.bins + (uint64_t)f0 * a.nrow + row;
+    const uint32_t base = s * feat_group * kGrowBins;
+    for (uint32_t k = 0; k < nf; ++k) {
+      const uint32_t i = base + k * kGrowBins + bin[(uint64_t)k * a.nrow];
+      atomicAdd(&Gl[i], q);
+      atomicAdd(&Hl[i], hq);
+    }
+  }
+  if (flags) atomicOr(&a.state->error, flags);
+  __syncthreads();
+  for (uint32_t i = threadIdx.x; i < cells; i += kHistBlock) {
+    const unsigned long long g = Gl[i], h = Hl[i];
+    if ((g | h) == 0ull) continue;
+    const uint32_t s = i / (feat_group * kGrowBins), k = (i / kGrowBins) % feat_group, b = i % kGrowBins;
+    if (s >= nslots || k >= nf) continue;
+    const uint64_t gi = ((uint64_t)(slot0 + s) * a.num_feature + f0 + k) * kGrowBins + b;
+    if (h != 0ull) atomicAdd(&a.Hhist[gi], h);
+    if (g != 0ull) atomicAdd(&a.Ghist[gi], g);
+  }
+}
+
+__device__ inline GrowCand shuffle_cand(const GrowCand& c, int d) {
+  GrowCand o;
+  o.loss_chg = __shfl_xor(c.loss_chg, d, kWave);
+  o.GL = __shfl_xor((long long)c.GL, d, kWave);
+  o.HL = __shfl_xor((unsigned long long)c.HL, d, kWave);
+  o.key = __shfl_xor(c.key, d, kWave);
+  o.valid = __shfl_xor(c.valid, d, kWave);
+  return o;
+}
+
+__device__ inline void write_leaf(const GrowArgs& a, GrowNode* nodes, uint32_t n, int64_t G, uint64_t H, int32_t parent) {
+  float leaf, weight;
+  grow_solve_leaf_weighted(G, H, a.eta, a.lambda, &leaf, &weight);
+  GrowNode r;
+  r.G = G;
+  r.H = H;
+  r.left = r.right = -1;
+  r.parent = parent;
+  r.feature = r.cut = r.default_left = 0;
+  r.value = leaf;
+  r.loss_chg = 0.0f;
+  r.sum_hess = (float)grow_hess(H);
+  r.base_weight = weight;
+  nodes[n] = r;
+}
+
+// PHASE 0: grid (blocks of four waves over slots x features).  PHASE 1: one block.
+template <int PHASE>
+__global__ __launch_bounds__(kBlock) void grow_split_weighted_kernel(GrowWeightedArgs wa, uint32_t level, uint32_t round) {
+  const GrowArgs& a = wa.g;
+  uint32_t begin, end, next;
+  level_range(a, level, &begin, &end, &next);
+  const uint32_t count = end - begin;
+  const uint32_t F = a.num_feature;
+  GrowNode* nodes = a.nodes + (uint64_t)round * kGrowMaxNodes;
+  if (PHASE == 0) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const uint32_t w = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
+    const uint32_t slot = w / F, f = w % F;
+    if (slot >= count) return;
+    const uint64_t at = ((uint64_t)slot * F + f) * kGrowBins + 4u * lane;
+    int64_t g4[4];
+    uint64_t h4[4];
+    int64_t gs = 0;
+    uint64_t hs = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      g4[k] = (int64_t)a.Ghist[at + k];
+      h4[k] = (uint64_t)a.Hhist[at + k];
+      gs += g4[k];
+      hs += h4[k];
+    }
+    // inclusive sums across the wave, then the sums below the lane's first bin
+    long long gi = gs;
+    unsigned long long hi = hs;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+      const long long gt = __shfl_up(gi, d, kWave);
+      const unsigned long long ht = __shfl_up(hi, d, kWave);
+      if (lane >= d) {
+        gi += gt;
+        hi += ht;
+      }
+    }
+    const int64_t Gp = __shfl(gi, kWave - 1, kWave);
+    const uint64_t Hp = __shfl(hi, kWave - 1, kWave);
+    const int64_t Gm = __shfl((long long)g4[3], kWave - 1, kWave);
+    const uint64_t Hm = __shfl((unsigned long long)h4[3], kWave - 1, kWave);
+    if (level == 0 && f == 0 && lane == 0) {   // the root's sums: every row is in one bin of feature 0
+      nodes[0].G = Gp;
+      nodes[0].H = Hp;
+    }
+    const uint32_t ncut = a.cut_ptr[f + 1] - a.cut_ptr[f];
+    GrowCand c = grow_best_split_weighted(g4, h4, f, 4u * lane, 4u, ncut, gi - gs, hi - hs, Gm, Hm, Gp, Hp, (double)a.lambda,
+                                          wa.min_child_weight);
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+      const GrowCand o = shuffle_cand(c, d);
+      if (grow_better(o, c)) c = o;
+    }
+    if (lane == 0) a.best[(uint64_t)slot * F + f] = c;
+  } else {
+    __shared__ uint32_t splits[kGrowMaxNodes / 2];
+    const uint32_t s = threadIdx.x;
+    const bool active = s < count && s < kGrowMaxNodes / 2;
+    const uint32_t node = begin + s;
+    GrowCand best;
+    int64_t Gp = 0;
+    uint64_t Hp = 0;
+    if (active) {
+      Gp = nodes[node].G;
+      Hp = nodes[node].H;
+      if (level == 0) write_leaf(a, nodes, 0, Gp, Hp, -1);
+      for (uint32_t f = 0; f < F; ++f) {
+        const GrowCand c = a.best[(uint64_t)s * F + f];
+        if (grow_better(c, best)) best = c;
+      }
+    }
+    const bool split = active && best.valid && best.loss_chg > (double)a.gamma && grow_weight_splits(Hp, wa.min_child_weight);
+    if (s < kGrowMaxNodes / 2) splits[s] = split ? 1u : 0u;
+    __syncthreads();
+    uint32_t below = 0, total = 0;
+    const uint32_t live = count < kGrowMaxNodes / 2 ? count : kGrowMaxNodes / 2;
+    for (uint32_t i = 0; i < live; ++i) {
+      total += splits[i];
+      if (i < s) below += splits[i];
+    }
+    if (next + 2u * total > kGrowMaxNodes) {   // (never: a tree of depth 8 has 511 nodes)
+      if (s == 0) atomicOr(&a.state->error, kGrowFlagState);
+      total = 0;
+    } else if (split) {
+      const uint32_t f = best.key >> 9, j = (best.key >> 1) & 255u, dl = best.key & 1u;
+      const uint32_t left = next + 2u * below;
+      nodes[node].left = (int32_t)left;
+      nodes[node].right = (int32_t)left + 1;
+      nodes[node].feature = f;
+      nodes[node].cut = j;
+      nodes[node].default_left = dl;
+      nodes[node].value = a.cuts[a.cut_ptr[f] + j];
+      nodes[node].loss_chg = (float)best.loss_chg;
+      write_leaf(a, nodes, left, best.GL, best.HL, (int32_t)(node | 0x80000000u));
+      write_leaf(a, nodes, left + 1, Gp - best.GL, Hp - best.HL, (int32_t)node);
+    }
+    if (s == 0) {
+      a.state->begin = next;
+      a.state->end = next + 2u * total;
+      a.state->next = next + 2u * total;
+      a.tree_nodes[round] = next + 2u * total;
+    }
+  }
+}
+
+// ---- the metric ----
+
+// a lane's sums: S in three parts, and W
+struct WideAcc {
+  unsigned long long p2 = 0, p1 = 0, p0 = 0, w = 0;
+};
+
+// one row's hq * e^2 into the lane's accumulators; false where the residual is out of range
+__device__ inline bool add_weighted_square(float pred, float label, unsigned long long hq, WideAcc* acc) {
+  const float g = pred - label;
+  // (a NaN fails the comparison)
+  if (!(__builtin_fabsf(g) < kRefitMaxAbsGrad)) return false;
+  const long long e = (long long)__builtin_rintf(g * kRefitGradScale);
+  const unsigned long long m = (unsigned long long)(e < 0 ? -e : e);   // <= 2^32 - 256
+  const unsigned long long sq = m * m;
+  const unsigned long long ha = hq * (sq >> 32), hb = hq * (sq & kLow32);   // hq, a, b < 2^32: neither product overflows
+  acc->p2 += ha >> 32;
+  acc->p1 += (ha & kLow32) + (hb >> 32);
+  acc->p0 += hb & kLow32;
+  return true;
+}
+
+// the block's sums leave it with one set of global adds: p2, p1, p0 to slot, and W to wslot where there is one
+__device__ inline void reduce_and_add(WideAcc acc, unsigned long long* slot, unsigned long long* wslot) {
+  __shared__ unsigned long long part[kWaves][4];
+#pragma unroll
+  for (int d = kWave / 2; d >= 1; d >>= 1) {
+    acc.p2 += __shfl_xor(acc.p2, d, kWave);
+    acc.p1 += __shfl_xor(acc.p1, d, kWave);
+    acc.p0 += __shfl_xor(acc.p0, d, kWave);
+    acc.w += __shfl_xor(acc.w, d, kWave);
+  }
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  if (lane == 0) {
+    part[wave][0] = acc.p2;
+    part[wave][1] = acc.p1;
+    part[wave][2] = acc.p0;
+    part[wave][3] = acc.w;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    unsigned long long t[4] = {0, 0, 0, 0};
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) t[k] += part[w][k];
+    }
+    atomicAdd(&slot[0], t[0]);
+    atomicAdd(&slot[1], t[1]);
+    atomicAdd(&slot[2], t[2]);
+    if (wslot != nullptr) atomicAdd(wslot, t[3]);
+  }
+}
+
+// grid (blocks).  wslot: the set's W at t = 0, else nullptr
+__global__ __launch_bounds__(kBlock) void grow_sse_weighted_kernel(GrowWeightedEvalArgs wa, unsigned long long* slot,
+                                                                   unsigned long long* wslot) {
+  const GrowEvalArgs& a = wa.e;
+  WideAcc acc;
+  uint32_t flags = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
+    float w;
+    unsigned long long hq;
+    const bool sound = row_weight(wa.weights, row, &w, &hq);
+    if (!add_weighted_square(a.pred[row], a.labels[row], hq, &acc)) flags |= a.label_flag;
+    if (!sound) flags |= wa.weight_flag;
+    acc.w += hq;
+  }
+  if (flags) atomicOr(&a.state->error, flags);
+  reduce_and_add(acc, slot, wslot);
+}
+
+// a node as the walk needs it (as in grow_eval.hip)
+struct EvalNode {
+  int32_t left, right;   // -1: a leaf
+  uint32_t fcd;          // feature << 9 | cut << 1 | default_left
+  float value;           // the leaf value
+};
+static_assert(sizeof(EvalNode) == 16, "16 bytes a node");
+
+// grid (blocks)
+__global__ __launch_bounds__(kBlock) void grow_walk_sse_weighted_kernel(GrowWeightedEvalArgs wa, uint32_t round,
+                                                                        unsigned long long* slot) {
+  __shared__ EvalNode tree[kGrowMaxNodes];
+  const GrowEvalArgs& a = wa.e;
+  const uint32_t count = a.tree_nodes[round];
+  if (count == 0 || count > kGrowMaxNodes) {   // (never: the split kernel writes it, and refuses a 513th node itself)
+    if (threadIdx.x == 0) atomicOr(&a.state->error, kGrowFlagState);
+    return;
+  }
+  const GrowNode* nodes = a.nodes + (uint64_t)round * kGrowMaxNodes;
+  for (uint32_t i = threadIdx.x; i < count; i += kBlock) {
+    EvalNode e;
+    e.left = nodes[i].left;
+    e.right = nodes[i].right;
+    e.fcd = (nodes[i].feature << 9) | ((nodes[i].cut & 255u) << 1) | (nodes[i].default_left != 0u ? 1u : 0u);
+    e.value = nodes[i].value;
+    tree[i] = e;
+  }
+  __syncthreads();
+  WideAcc acc;
+  uint32_t flags = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
+    uint32_t p = 0;
+    bool sound = true;
+    for (int d = 0; d < a.max_depth; ++d) {
+      const EvalNode e = tree[p];
+      if (e.left < 0) break;
+      const uint32_t f = e.fcd >> 9;
+      if (f >= a.num_feature) {
+        sound = false;
+        break;
+      }
+      const uint32_t b = a.bins[(uint64_t)f * a.nrow + row];
+      const bool go_left = b == kGrowMissingBin ? (e.fcd & 1u) != 0u : b <= ((e.fcd >> 1) & 255u);
+      p = (uint32_t)(go_left ? e.left : e.right);
+      if (p >= count) {
+        sound = false;
+        break;
+      }
+    }
+    if (!sound || tree[p].left >= 0) {   // (tree[p] is read only while p < count)
+      flags |= kGrowFlagState;
+      continue;
+    }
+    const float pred = a.pred[row] + tree[p].value;
+    a.pred[row] = pred;
+    float w;
+    unsigned long long hq;
+    if (!row_weight(wa.weights, row, &w, &hq)) flags |= wa.weight_flag;
+    if (!add_weighted_square(pred, a.labels[row], hq, &acc)) flags |= a.label_flag;
+  }
+  if (flags) atomicOr(&a.state->error, flags);
+  reduce_and_add(acc, slot, nullptr);
+}
+
+bool eval_args_sound(const GrowWeightedEvalArgs& wa, uint32_t blocks, uint32_t set) {
+  const GrowEvalArgs& a = wa.e;
+  return a.nrow != 0 && a.nrow <= kRefitMaxRows && blocks != 0 && set <= 1 && a.pred != nullptr && a.labels != nullptr &&
+         wa.wsums != nullptr && a.state != nullptr &&
+         ((a.label_flag == kGrowFlagLabel && wa.weight_flag == kGrowFlagWeight) ||
+          (a.label_flag == kGrowFlagEvalLabel && wa.weight_flag == kGrowFlagEvalWeight));
+}
+
+}  // namespace
+
+int prepare_grow_weighted() {
+  return raise_lds_limit(grow_hist_weighted_kernel, kGrowWeightedMaxPairs * kGrowWeightedPairBytes);
+}
+
+int launch_grow_tree_weighted(const GrowWeightedArgs& wa, const GrowPlan& plan, uint32_t round, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  const GrowArgs& a = wa.g;
+  if (a.nrow == 0 || a.nrow > kRefitMaxRows || a.num_feature == 0 || a.num_feature > kGrowMaxFeatures || a.max_depth < 1 ||
+      a.max_depth > kGrowMaxDepth || plan.levels.size() != (size_t)a.max_depth || plan.row_blocks == 0 ||
+      !(wa.min_child_weight >= 0.0))
+    return hipErrorInvalidValue;
+  const uint32_t F = a.num_feature;
+  hipError_t e = hipSuccess;
+  for (uint32_t d = 0; d < (uint32_t)a.max_depth; ++d) {
+    const GrowLevelPlan& l = plan.levels[d];
+    if (l.slots != (1u << d) || l.node_group * l.feat_group > kGrowWeightedMaxPairs || l.node_group == 0 || l.feat_group == 0 ||
+        l.lds_bytes != l.node_group * l.feat_group * kGrowWeightedPairBytes || l.node_groups * l.node_group < l.slots ||
+        l.feat_groups * l.feat_group < F || l.hist_blocks == 0)
+      return hipErrorInvalidValue;
+    const size_t bytes = (size_t)l.slots * F * kGrowBins * sizeof(unsigned long long);
+    if ((e = hipMemsetAsync(a.Ghist, 0, bytes, stream)) != hipSuccess) return e;
+    if ((e = hipMemsetAsync(a.Hhist, 0, bytes, stream)) != hipSuccess) return e;
+    hipLaunchKernelGGL(grow_hist_weighted_kernel, dim3(l.hist_blocks, l.node_groups * l.feat_groups), dim3(kHistBlock),
+                       l.lds_bytes, stream, wa, d, l.node_group, l.feat_group, l.feat_groups);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    const uint32_t waves = l.slots * F, per_block = kBlock / kWave;
+    hipLaunchKernelGGL(grow_split_weighted_kernel<0>, dim3((waves + per_block - 1) / per_block), dim3(kBlock), 0, stream, wa, d,
+                       round);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(grow_split_weighted_kernel<1>, dim3(1), dim3(kBlock), 0, stream, wa, d, round);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if ((e = (hipError_t)launch_grow_partition(a, plan, round, stream)) != hipSuccess) return e;
+  }
+  return launch_grow_leaf(a, plan, round, stream);
+}
+
+int launch_grow_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!eval_args_sound(a, blocks, set)) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grow_sse_weighted_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, a.wsums + grow_wide_index(t, set),
+                     t == 0 ? a.wsums + set : nullptr);
+  return hipGetLastError();
+}
+
+int launch_grow_walk_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!eval_args_sound(a, blocks, set) || a.e.bins == nullptr || a.e.nodes == nullptr || a.e.tree_nodes == nullptr ||
+      a.e.num_feature == 0 || a.e.num_feature > kGrowMaxFeatures || a.e.max_depth < 1 || a.e.max_depth > kGrowMaxDepth)
+    return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grow_walk_sse_weighted_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, round,
+                     a.wsums + grow_wide_index(round + 1, set));
+  return hipGetLastError();
+}
+
+}  // namespace ohx

@@ -418,6 +418,44 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
+      !  Boosting with row weights (include/ohxgb.h; docs/21_row_weights.md).  Interface blocks only.  weights /
+      !  eval_weights: c_loc of nlabel / eval_nlabel real(c_float) on the host (d_weights / d_eval_weights: their DEVICE
+      !  addresses), or c_null_ptr for weights of 1.  min_child_weight stands where min_child_rows stood.  The rest as above
+      function OHXBoosterBoostTreesWeighted(handle, dmat, labels, weights, nlabel, eval_dmat, eval_labels, eval_weights, &
+            eval_nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_weight, patience, &
+            train_rmse, eval_rmse, rounds_run, best_round, nodes_added) &
+            bind(C, name="OHXBoosterBoostTreesWeighted") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat, weights, eval_dmat, eval_labels, eval_weights
+         real(c_float), intent(in)       :: labels(*)
+         integer(c_int64_t), value       :: nlabel, eval_nlabel
+         integer(c_int64_t), intent(in)  :: cut_ptr(*)
+         real(c_float), intent(in)       :: cut_values(*)
+         integer(c_int), value           :: rounds, max_depth, patience
+         real(c_float), value            :: eta, lambda, gamma, min_child_weight
+         type(c_ptr), value              :: train_rmse, eval_rmse
+         integer(c_int), intent(out)     :: rounds_run, best_round
+         type(c_ptr), value              :: nodes_added
+         integer(c_int)                  :: rc
+      end function
+
+      function OHXBoosterBoostTreesWeightedDevice(handle, dmat, d_labels, d_weights, nlabel, eval_dmat, d_eval_labels, &
+            d_eval_weights, eval_nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_weight, &
+            patience, train_rmse, eval_rmse, rounds_run, best_round, nodes_added, stream) &
+            bind(C, name="OHXBoosterBoostTreesWeightedDevice") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat, d_labels, d_weights, eval_dmat, d_eval_labels, d_eval_weights, stream
+         integer(c_int64_t), value       :: nlabel, eval_nlabel
+         integer(c_int64_t), intent(in)  :: cut_ptr(*)
+         real(c_float), intent(in)       :: cut_values(*)
+         integer(c_int), value           :: rounds, max_depth, patience
+         real(c_float), value            :: eta, lambda, gamma, min_child_weight
+         type(c_ptr), value              :: train_rmse, eval_rmse
+         integer(c_int), intent(out)     :: rounds_run, best_round
+         type(c_ptr), value              :: nodes_added
+         integer(c_int)                  :: rc
+      end function
+
       !  data: a row-major host sample (nrow x ncol); cut_ptr: ncol + 1 entries out; needed: the cut values in all
       function OHXQuantileCuts(data, nrow, ncol, missing, max_bins, cut_ptr, cut_values, cap, needed) &
             bind(C, name="OHXQuantileCuts") result(rc)

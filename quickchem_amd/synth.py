@@ -103,6 +103,16 @@ def _load():
         lib.ohx_grow_eval_rmse.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
         lib.ohx_grow_eval_rmse.restype = C.c_double
         lib.ohx_grow_eval_plan.argtypes = [C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+        lib.ohx_grow_node_split_weighted.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint64,
+                                                     C.c_float, C.c_float, C.c_float, C.POINTER(C.c_double), C.c_void_p,
+                                                     C.c_void_p]
+        lib.ohx_grow_solve_leaf_weighted.argtypes = [C.c_int64, C.c_uint64, C.c_float, C.c_float, C.c_void_p]
+        lib.ohx_grow_solve_leaf_weighted.restype = None
+        lib.ohx_grow_plan_weighted.argtypes = lib.ohx_grow_plan.argtypes
+        lib.ohx_grow_weighted_rmse.argtypes = [C.c_void_p, C.c_uint64]
+        lib.ohx_grow_weighted_rmse.restype = C.c_double
+        lib.ohx_grow_weighted_compare.argtypes = [C.c_void_p, C.c_void_p]
+        lib.ohx_grow_weighted_stop.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         lib.ohx_cuts_select.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int, C.c_uint64, C.c_void_p,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_cuts_keys.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -495,6 +505,62 @@ def grow_eval_plan(nrow: int, num_cus: int = 256):
     info = (C.c_uint64 * 2)()
     _check(_load().ohx_grow_eval_plan(nrow, num_cus, info))
     return {"blocks": int(info[0]), "block_rows": int(info[1])}
+
+
+def grow_node_split_weighted(G, H, cut_ptr, Gp: int, Hp: int, reg_lambda: float, gamma: float, min_child_weight: float):
+    """csrc/grow.cpp grow_node_split_weighted (the shared grow_best_split_weighted per feature) on injected histograms
+    G int64 / H uint64 (fixed-point hessian sums) [num_feature][256] -> dict as grow_node_split's; HL in fixed point."""
+    G = np.ascontiguousarray(G, dtype=np.int64)
+    H = np.ascontiguousarray(H, dtype=np.uint64)
+    cut_ptr = np.ascontiguousarray(cut_ptr, dtype=np.uint64)
+    assert G.shape == H.shape and G.ndim == 2 and G.shape[1] == 256 and cut_ptr.size == G.shape[0] + 1
+    loss = C.c_double()
+    out, sums = np.zeros(5, dtype=np.uint32), np.zeros(2, dtype=np.uint64)
+    _check(_load().ohx_grow_node_split_weighted(G.ctypes.data, H.ctypes.data, G.shape[0], cut_ptr.ctypes.data, Gp, Hp,
+                                                reg_lambda, gamma, min_child_weight, C.byref(loss), out.ctypes.data,
+                                                sums.ctypes.data))
+    return {"valid": bool(out[0]), "feature": int(out[1]), "j": int(out[2]), "default_left": int(out[3]),
+            "splits": bool(out[4]), "loss_chg": float(loss.value), "GL": int(sums[:1].view(np.int64)[0]), "HL": int(sums[1])}
+
+
+def grow_solve_leaf_weighted(G: int, H: int, eta: float, reg_lambda: float):
+    """csrc/grow.hpp grow_solve_leaf_weighted and grow_hess -> (leaf value, base_weight, sum_hess) as float32."""
+    out = np.zeros(3, dtype=np.float32)
+    _load().ohx_grow_solve_leaf_weighted(G, H, eta, reg_lambda, out.ctypes.data)
+    return out[0], out[1], out[2]
+
+
+def grow_plan_weighted(nrow: int, num_feature: int = NFEAT, ncuts: int = 0, max_depth: int = 6, num_cus: int = 256):
+    """csrc/grow.hpp plan_grow_weighted -> the dict of grow_plan, for the 16-byte bins of the weighted histogram kernel."""
+    info = (C.c_uint64 * 8)()
+    lev = np.zeros((max(max_depth, 1), 7), dtype=np.uint64)
+    _check(_load().ohx_grow_plan_weighted(nrow, num_feature, ncuts, max_depth, num_cus, info, lev.ctypes.data))
+    names = ("slots", "node_group", "feat_group", "node_groups", "feat_groups", "hist_blocks", "lds_bytes")
+    return {"row_blocks": int(info[0]), "block_rows": int(info[1]), "bin_lds_bytes": int(info[2]),
+            "bins_bytes": int(info[3]), "hist_bytes": int(info[4]), "hist_block_rows": int(info[5]),
+            "max_pairs": int(info[6]), "pair_bytes": int(info[7]),
+            "levels": [dict(zip(names, (int(v) for v in row))) for row in lev]}
+
+
+def boost_weighted_rmse(p2: int, p1: int, p0: int, W: int) -> float:
+    """csrc/grow.cpp grow_wide_rmse: sqrt(((double)(p2 * 2^64 + p1 * 2^32 + p0) * 2^-72) / ((double)W * 2^-24))."""
+    s = np.ascontiguousarray([p2, p1, p0], dtype=np.uint64)
+    return float(_load().ohx_grow_weighted_rmse(s.ctypes.data, W))
+
+
+def boost_weighted_compare(a, b) -> int:
+    """csrc/grow.hpp grow_sum_less on wide sums (p2, p1, p0), both ways -> -1 / 0 / 1."""
+    a = np.ascontiguousarray([int(v) for v in a], dtype=np.uint64)
+    b = np.ascontiguousarray([int(v) for v in b], dtype=np.uint64)
+    return int(_load().ohx_grow_weighted_compare(a.ctypes.data, b.ctypes.data))
+
+
+def boost_weighted_stop(sums, patience: int):
+    """csrc/grow.hpp grow_eval_stop over wide sums (p2, p1, p0) after 0, 1, ... trees -> (rounds_run, best_round)."""
+    a = np.ascontiguousarray([[int(v) for v in s] for s in sums], dtype=np.uint64)
+    out = np.zeros(2, dtype=np.uint32)
+    _check(_load().ohx_grow_weighted_stop(a.ctypes.data, len(a), patience, out.ctypes.data))
+    return int(out[0]), int(out[1])
 
 
 def quantile_cuts_select(x, missing: float = float("nan"), max_bins: int = 255, row_step: int = 1, bits=(12, 10, 10)):

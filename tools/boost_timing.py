@@ -19,7 +19,11 @@ run of this script under a kernel trace with --reps 1 --rounds 1 (docs/18_boost_
 are the training rows (both gathered once into matrices of their own in HBM).  The plain boost call on the training rows,
 the call with patience 0 and the call with `--patience` are each timed as the median of `--reps` calls after a first one,
 on fresh boosters, `--rounds` rounds.  The per-round RMSE of both sets as the call returns it is written beside the one
-this script computes itself, in torch from margin predicts, before the call and after its last kept tree."""
+this script computes itself, in torch from margin predicts, before the call and after its last kept tree.
+
+`--weights ones|random` times OHXBoosterBoostTreesWeightedDevice (docs/21_row_weights.md) wherever `--weights none` (the
+default) times the plain call, with a weight of 1.0 a row or weights uniform in [0, 4) in HBM, no held-out set and
+min_child_weight 1; the timings stand under the same keys, so three runs that differ in `--weights` alone compare."""
 from __future__ import annotations
 
 import argparse
@@ -119,7 +123,11 @@ def main():
     ap.add_argument("--skip-rmse", action="store_true", help="time only (a run under a kernel trace)")
     ap.add_argument("--holdout", type=int, default=0, help="hold out every K-th row and time the call with a held-out set")
     ap.add_argument("--patience", type=int, default=3, help="with --holdout: the patience of the early-stopping call")
+    ap.add_argument("--weights", choices=("none", "ones", "random"), default="none",
+                    help="ones / random: time OHXBoosterBoostTreesWeightedDevice in place of the plain call")
     args = ap.parse_args()
+    if args.weights != "none" and args.holdout:
+        ap.error("--weights times the call without a held-out set: leave --holdout out")
     assert torch.cuda.is_available(), "boost_timing needs the MI355X"
     torch.cuda.set_device(0)
     model = synth.make_model()
@@ -172,7 +180,7 @@ def main():
         res["cuts_full_plan"] = synth.cuts_plan(n, 1, F, cus)
     ncuts = int(cuts[0][-1])
     res["cut_values"] = ncuts
-    res["plan"] = synth.grow_plan(n, F, ncuts, args.max_depth, cus)
+    res["plan"] = (synth.grow_plan if args.weights == "none" else synth.grow_plan_weighted)(n, F, ncuts, args.max_depth, cus)
     print("cuts", json.dumps({k: v for k, v in res.items() if k.startswith("cuts_") and not k.endswith("plan")}), flush=True)
 
     def margins(b):
@@ -189,11 +197,26 @@ def main():
     def rmse(b):
         return float(torch.sqrt(torch.mean((margins(b).double() - labels.double()) ** 2)).item())
 
+    weights = None
+    if args.weights == "ones":
+        weights = torch.ones(n, dtype=torch.float32, device="cuda")
+    elif args.weights == "random":
+        weights = torch.rand(n, dtype=torch.float32, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1)) * 4.0
+    res["weights"] = args.weights
+    last = {}                              # what the weighted call returned last
+
     def boost(b, rounds):
         torch.cuda.synchronize()
         t = time.perf_counter()
-        nodes = b.boost_trees_device(d, labels.data_ptr(), n, cuts, rounds=rounds, max_depth=args.max_depth, eta=args.eta,
-                                     reg_lambda=args.reg_lambda, stream=stream)
+        if weights is None:
+            nodes = b.boost_trees_device(d, labels.data_ptr(), n, cuts, rounds=rounds, max_depth=args.max_depth, eta=args.eta,
+                                         reg_lambda=args.reg_lambda, stream=stream)
+        else:
+            r = b.boost_trees_weighted_device(d, labels.data_ptr(), n, cuts, weights_ptr=weights.data_ptr(), rounds=rounds,
+                                              max_depth=args.max_depth, eta=args.eta, reg_lambda=args.reg_lambda,
+                                              min_child_weight=1.0, stream=stream)
+            nodes = r["nodes_added"]
+            last.update(rounds=rounds, train_rmse=r["train_rmse"].tolist())
         return time.perf_counter() - t, nodes
 
     if args.holdout:
@@ -214,6 +237,8 @@ def main():
             b.free()
         res[f"rounds_{rounds}"] = {"first_call_median_s": float(np.median(first)), "median_s": float(np.median(again)),
                                    "min_s": float(np.min(again)), "max_s": float(np.max(again)), "nodes_added": nodes}
+        if last:
+            res[f"rounds_{rounds}"]["train_rmse"] = last["train_rmse"]
         print(f"rounds_{rounds}", json.dumps(res[f"rounds_{rounds}"]), flush=True)
     if args.rounds > 1 and not args.holdout:
         per_round = (res[f"rounds_{args.rounds}"]["median_s"] - res["rounds_1"]["median_s"]) / (args.rounds - 1)
