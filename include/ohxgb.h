@@ -705,6 +705,54 @@ int OHXBoosterBoostTreesWeightedDevice(BoosterHandle handle, DMatrixHandle dmat,
                                        float eta, float lambda, float gamma, float min_child_weight, int patience,
                                        double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
                                        bst_ulong* nodes_added, void* stream);
+/* Boosting with row and column subsampling (docs/22_sampling.md): OHXBoosterBoostTreesWeighted with three more
+ * arguments before patience - subsample, the fraction of the rows a tree is fitted to; colsample_bytree, the fraction of
+ * the features it may split on; and the seed of the draws.  Every tree of a call draws a fresh bag of rows and a fresh
+ * set of features, on the GPU, inside the one call.  Everything not restated here is OHXBoosterBoostTreesWeighted's:
+ * weights (NULL means 1.0f), min_child_weight, the metric, the stop rule, what is kept, all or nothing, what a success
+ * drops, the two forms, not capturable.
+ * The mix function.  All arithmetic is uint64 and wraps:
+ *   mix(z): z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31
+ * Tree keys.  gamma64 = 0x9E3779B97F4A7C15.  Tree t = 1..rounds of the call has index i = T0 + t - 1, where T0 is the
+ * number of trees the forest holds when the call starts.  K_row(i) = mix(seed + gamma64 * (2i + 1)) and
+ * K_col(i) = mix(seed + gamma64 * (2i + 2)).
+ * Rows.  k_s = (uint32) rint((double)subsample * 2^24).  Row r is the 0-based row of the training matrix; it is in the
+ * bag of tree i exactly when (mix(K_row(i) + r) >> 40) < k_s.  k_s == 2^24 (subsample 1.0f) puts every row in and
+ * draws nothing.
+ * Columns.  F is the booster's num_feature and n_sel = max(1, (int) floor((double)colsample_bytree * F)).  Feature f
+ * has key c_f = mix(K_col(i) + f); the selected set is the n_sel features smallest by (c_f, f), kept in ascending f.
+ * n_sel == F selects all and draws nothing.
+ * The tree.  Tree t is the tree OHXBoosterBoostTreesWeighted grows at that round from the same running margin with two
+ * changes: every out-of-bag row has weight 0, and every unselected feature has an empty cut list.  So out-of-bag rows
+ * add nothing to any histogram; node sums, sum_hess, base_weight and min_child_weight are over the bag; the candidates,
+ * their total order (f, j, dl) with the original f, ties, node numbering and records are unchanged.
+ * Everything else sees every row at its full weight: pred += leaf(row) for every row, in or out of the bag;
+ * train_rmse, eval_rmse, W, the stop rule and the range and weight refusals cover all rows, and a NaN label on an
+ * out-of-bag row is still refused with "label".
+ * The result depends on the order of the rows only through r in the draw.  Launch shape, form, stream and
+ * OHXDMatrixSetGrid change nothing.  Integer adds only.
+ * Consequence.  With subsample = colsample_bytree = 1.0f and any seed, the forest, XGBoosterSaveModel's bytes in all
+ * three formats and both RMSE arrays equal those of OHXBoosterBoostTreesWeighted.
+ * Refused, with the forest and every output untouched: everything OHXBoosterBoostTreesWeighted refuses, in the same
+ * order; after min_child_weight and before the cuts, subsample not finite, <= 0, > 1, or with k_s == 0, then
+ * colsample_bytree not finite, <= 0, or > 1; and, on the device, a round whose bag holds no weight (root H == 0), also
+ * a round whose tree would have been discarded (the message says "bag").  The bag's bit plane and the selected features
+ * of every round are part of the grow state.  Calls on ONE booster must not run concurrently. */
+int OHXBoosterBoostTreesSampled(BoosterHandle handle, DMatrixHandle dmat, const float* labels, const float* weights,
+                                bst_ulong nlabel, DMatrixHandle eval_dmat, const float* eval_labels,
+                                const float* eval_weights, bst_ulong eval_nlabel, const bst_ulong* cut_ptr,
+                                const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
+                                float min_child_weight, float subsample, float colsample_bytree, uint64_t seed, int patience,
+                                double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
+                                bst_ulong* nodes_added);
+int OHXBoosterBoostTreesSampledDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels,
+                                      const float* d_weights, bst_ulong nlabel, DMatrixHandle eval_dmat,
+                                      const float* d_eval_labels, const float* d_eval_weights, bst_ulong eval_nlabel,
+                                      const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth,
+                                      float eta, float lambda, float gamma, float min_child_weight, float subsample,
+                                      float colsample_bytree, uint64_t seed, int patience, double* train_rmse,
+                                      double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added,
+                                      void* stream);
 int OHXQuantileCuts(const float* data, bst_ulong nrow, bst_ulong ncol, float missing, int max_bins, bst_ulong* cut_ptr,
                     float* cut_values, bst_ulong cap, bst_ulong* needed);
 /* OHXDMatrixQuantileCuts (docs/19_device_cuts.md) makes the same cuts from a DMatrix's rows where they lie, in HBM: no

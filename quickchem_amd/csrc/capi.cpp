@@ -651,7 +651,7 @@ struct RefitState {
 // first call on the loaded model; never a buffer of another path.
 struct GrowState {
   int device = -1;
-  bool prepared = false, prepared_weighted = false;
+  bool prepared = false, prepared_weighted = false, prepared_sampled = false;
   DevBuf<uint8_t> d_bins;
   DevBuf<uint16_t> d_pos;
   DevBuf<float> d_pred, d_labels, d_cuts;
@@ -675,7 +675,14 @@ struct GrowState {
   DevBuf<float> d_weights, d_eval_weights;
   DevBuf<unsigned long long> d_wsums;
   PinnedBuf<unsigned long long> h_wsums;
+  // subsampling (OHXBoosterBoostTreesSampled): the bag's bit plane of the tree at hand, a bit a row, and the selected
+  // features of every round [rounds][n_sel]
+  DevBuf<unsigned long long> d_bag;
+  DevBuf<uint8_t> d_features;
+  PinnedBuf<uint8_t> h_features;
   void release_device() {
+    d_bag.release();
+    d_features.release();
     d_bins.release();
     d_pos.release();
     d_eval_bins.release();
@@ -688,7 +695,7 @@ struct GrowState {
     d_best.release();
     d_nodes.release();
     d_state.release();
-    prepared = prepared_weighted = false;
+    prepared = prepared_weighted = prepared_sampled = false;
   }
 };
 
@@ -2217,16 +2224,27 @@ struct BoostWeights {
   float min_child_weight = 0.0f;
 };
 
-// Both forms of OHXBoosterBoostTrees, of OHXBoosterBoostTreesEval where `ev` is given, and of
-// OHXBoosterBoostTreesWeighted where `wt` is given too (then min_child_rows is not looked at).  The refusals that need
+// What OHXBoosterBoostTreesSampled adds to a call with `wt`: the fraction of the rows and of the features a tree sees,
+// and the seed of the draws.
+struct BoostSampling {
+  float subsample = 1.0f;
+  float colsample_bytree = 1.0f;
+  uint64_t seed = 0;
+};
+
+// Both forms of OHXBoosterBoostTrees, of OHXBoosterBoostTreesEval where `ev` is given, of
+// OHXBoosterBoostTreesWeighted where `wt` is given too (then min_child_rows is not looked at), and of
+// OHXBoosterBoostTreesSampled where `sp` is given as well.  The refusals that need
 // neither a matrix nor a device come first, in the header's order; nothing is enqueued before the last of them.
-// Without `ev` nothing of the metric is allocated or enqueued; without `wt` nothing of the weights.
+// Without `ev` nothing of the metric is allocated or enqueued; without `wt` nothing of the weights; without `sp`, or
+// with a subsample and a colsample_bytree of 1, nothing of the sampling: that call takes the weighted path.
 void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulong nlabel, const bst_ulong* cut_ptr,
                  const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
                  bst_ulong min_child_rows, bst_ulong* nodes_added, bool host_form, hipStream_t caller, const char* what,
-                 const BoostEval* ev = nullptr, const BoostWeights* wt = nullptr) {
+                 const BoostEval* ev = nullptr, const BoostWeights* wt = nullptr, const BoostSampling* sp = nullptr) {
   const std::string w0(what);
   if (wt != nullptr && ev == nullptr) throw OhxError(w0 + ": the weighted call carries the metric");
+  if (sp != nullptr && wt == nullptr) throw OhxError(w0 + ": the sampled call carries the weights");
   if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
   refuse_categorical(b, what);
   refuse_groups(b, what);
@@ -2247,6 +2265,15 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   if (wt == nullptr && min_child_rows < 1) throw OhxError(w0 + ": min_child_rows must be >= 1");
   if (wt != nullptr && !(std::isfinite(wt->min_child_weight) && wt->min_child_weight >= 0.0f))
     throw OhxError(w0 + ": min_child_weight must be finite and >= 0");
+  uint32_t k_s = kGrowSampleOne, n_sel = F;   // the bag's threshold and the features a tree sees
+  if (sp != nullptr) {
+    k_s = grow_sample_threshold(sp->subsample);
+    if (k_s == 0)
+      throw OhxError(w0 + ": subsample must be finite, > 0 and <= 1, and rint(subsample * 2^24) must be >= 1");
+    n_sel = grow_num_selected(F, sp->colsample_bytree);
+    if (n_sel == 0) throw OhxError(w0 + ": colsample_bytree must be finite, > 0 and <= 1");
+  }
+  const bool sampled = k_s != kGrowSampleOne || n_sel != F;
   grow_check_cuts(cut_ptr, cut_values, F, what);
   if (ev != nullptr) {
     if (ev->patience < 0) throw OhxError(w0 + ": patience must be >= 0");
@@ -2301,9 +2328,17 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     HIP_CHECK((hipError_t)prepare_grow_weighted());
     g.prepared_weighted = true;
   }
+  if (sampled && !g.prepared_sampled) {
+    HIP_CHECK((hipError_t)prepare_grow_sampled());
+    g.prepared_sampled = true;
+  }
   const uint64_t n = d.nrow, ncuts = cut_ptr[F];
   const size_t R = (size_t)rounds;
   const GrowPlan plan = wt != nullptr ? plan_grow_weighted(n, F, ncuts, max_depth, dev.num_cus) : plan_grow(n, F, ncuts, max_depth, dev.num_cus);
+  // the level loop over a tree's n_sel features: compact histograms and candidates (the bins hold every feature)
+  const GrowPlan splan = sampled ? plan_grow_weighted(n, n_sel, ncuts, max_depth, dev.num_cus) : GrowPlan();
+  const uint64_t hist_bytes = sampled ? splan.hist_bytes : plan.hist_bytes;
+  const uint64_t tree0 = b.forest.trees.size();   // T0: tree t of the call is tree tree0 + t - 1 of the draws
   auto room = [&](auto& buf, size_t count, size_t elem, const char* name) {
     try {
       buf.ensure(count);
@@ -2315,8 +2350,8 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   room(g.d_pos, n, 2, "the row positions");
   room(g.d_pred, n, 4, "the running margin");
   if (host_form) room(g.d_labels, n, 4, "the staged labels");
-  room(g.d_Ghist, (size_t)(plan.hist_bytes / 16), 8, "the gradient histograms");
-  room(g.d_Hhist, (size_t)(plan.hist_bytes / 16), 8, wt != nullptr ? "the hessian histograms" : "the count histograms");
+  room(g.d_Ghist, (size_t)(hist_bytes / 16), 8, "the gradient histograms");
+  room(g.d_Hhist, (size_t)(hist_bytes / 16), 8, wt != nullptr ? "the hessian histograms" : "the count histograms");
   room(g.d_best, (size_t)(1u << (max_depth - 1)) * F, sizeof(GrowCand), "the split candidates");
   room(g.d_nodes, R * kGrowMaxNodes, sizeof(GrowNode), "the node records");
   const uint64_t ne = e != nullptr ? e->nrow : 0;
@@ -2327,6 +2362,16 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     if (host_form && wt->eval_weights != nullptr) room(g.d_eval_weights, ne, 4, "the staged eval weights");
     room(g.d_wsums, nwsums, 8, "the weighted metric sums");
     g.h_wsums.ensure(nwsums);
+  }
+  const size_t bag_words = (size_t)((n + 63) / 64);
+  if (sampled) {
+    if (k_s != kGrowSampleOne) room(g.d_bag, bag_words, 8, "the bag's bit plane");
+    room(g.d_features, R * n_sel, 1, "the selected features of every round");
+    g.h_features.ensure(R * n_sel);
+    // every round's list before anything is enqueued
+    for (size_t r = 0; r < R; ++r)
+      if (grow_pick_features(sp->seed, tree0 + r, F, sp->colsample_bytree, g.h_features.p + r * n_sel) != n_sel)
+        throw OhxError(w0 + ": the selected features of round " + std::to_string(r + 1) + " are not " + std::to_string(n_sel));
   }
   if (ev != nullptr) {
     if (e != nullptr) {
@@ -2360,6 +2405,7 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   HIP_CHECK(hipMemsetAsync(g.d_state.p, 0, sizeof(GrowLevelState), stream));
   HIP_CHECK(hipMemsetAsync(g.d_tree_nodes.p, 0, R * sizeof(uint32_t), stream));
   HIP_CHECK(hipMemsetAsync(g.d_pos.p, 0, n * sizeof(uint16_t), stream));
+  if (sampled) HIP_CHECK(hipMemcpyAsync(g.d_features.p, g.h_features.p, R * n_sel, hipMemcpyHostToDevice, stream));
   if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_labels.p, labels, n * sizeof(float), hipMemcpyHostToDevice, stream));
   // The margin of the forest so far, by the predict path.  Its kernels raise the booster's sticky inf flag for +-inf in
   // a device matrix; bins take +-inf as the floats they are, so the flag word is put back as it was.
@@ -2423,8 +2469,24 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     aw.weights = wt->weights == nullptr ? nullptr : host_form ? g.d_weights.p : wt->weights;
     aw.min_child_weight = (double)wt->min_child_weight;
   }
+  GrowSampledArgs as;                  // the level loop over a bag of the rows and a tree's features
+  if (sampled) {
+    as.w = aw;
+    as.bag = k_s != kGrowSampleOne ? g.d_bag.p : nullptr;
+    as.features = g.d_features.p;
+    as.n_sel = n_sel;
+    as.k_s = k_s;
+  }
   // one tree, and one set's sums after t trees, by the kernels of the call at hand
   auto grow_tree = [&](uint32_t r) {
+    if (sampled) {
+      if (as.bag != nullptr) {
+        as.row_key = grow_row_key(sp->seed, tree0 + r);
+        const hipError_t drawn = (hipError_t)launch_grow_bag(as, plan, stream);
+        if (drawn != hipSuccess) return drawn;
+      }
+      return (hipError_t)launch_grow_tree_sampled(as, plan, splan, r, stream);
+    }
     return (hipError_t)(wt != nullptr ? launch_grow_tree_weighted(aw, plan, r, stream) : launch_grow_tree(a, plan, r, stream));
   };
   hipError_t launched = (hipError_t)launch_grow_bin(a, plan, stream);
@@ -2558,6 +2620,9 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     throw OhxError(w0 + ": a weight is not finite, is negative or reaches 256 at some training row; the forest is unchanged");
   if (flags & kGrowFlagEvalWeight)
     throw OhxError(w0 + ": an eval weight is not finite, is negative or reaches 256 at some held-out row; the forest is unchanged");
+  if (flags & kGrowFlagBag)
+    throw OhxError(w0 + ": the bag of some round holds no weight (every row drawn by subsample has rint(w * 2^24) == 0, or none "
+                   "was drawn): raise subsample or change the seed; the forest is unchanged");
   if (flags != 0) throw OhxError(w0 + ": the grow kernels reported error flags " + std::to_string(flags));
   if (wt != nullptr) {
     if (g.h_wsums.p[kGrowEvalTrain] == 0ull)
@@ -2600,7 +2665,7 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     grown.push_back(grow_assemble_tree(g.h_nodes.p + r * kGrowMaxNodes, g.h_tree_nodes.p[r], F));
     added += g.h_tree_nodes.p[r];
   }
-  const size_t T0 = b.forest.trees.size();
+  const size_t T0 = (size_t)tree0;
   for (Tree& t : grown) {
     b.forest.trees.push_back(std::move(t));
     b.forest.tree_info.push_back(0);
@@ -3423,6 +3488,69 @@ int OHXBoosterBoostTreesWeightedDevice(BoosterHandle handle, DMatrixHandle dmat,
   wt.min_child_weight = min_child_weight;
   boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, 1, nodes_added, false,
               static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesWeightedDevice", &ev, &wt);
+  API_END();
+}
+
+int OHXBoosterBoostTreesSampled(BoosterHandle handle, DMatrixHandle dmat, const float* labels, const float* weights,
+                                bst_ulong nlabel, DMatrixHandle eval_dmat, const float* eval_labels,
+                                const float* eval_weights, bst_ulong eval_nlabel, const bst_ulong* cut_ptr,
+                                const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
+                                float min_child_weight, float subsample, float colsample_bytree, uint64_t seed, int patience,
+                                double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
+                                bst_ulong* nodes_added) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  BoostEval ev;
+  ev.dmat = eval_dmat;
+  ev.labels = eval_labels;
+  ev.nlabel = eval_nlabel;
+  ev.patience = patience;
+  ev.train_rmse = train_rmse;
+  ev.eval_rmse = eval_rmse;
+  ev.rounds_run = rounds_run;
+  ev.best_round = best_round;
+  BoostWeights wt;
+  wt.weights = weights;
+  wt.eval_weights = eval_weights;
+  wt.min_child_weight = min_child_weight;
+  BoostSampling sp;
+  sp.subsample = subsample;
+  sp.colsample_bytree = colsample_bytree;
+  sp.seed = seed;
+  boost_trees(*b, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, 1, nodes_added, true,
+              nullptr, "OHXBoosterBoostTreesSampled", &ev, &wt, &sp);
+  API_END();
+}
+
+int OHXBoosterBoostTreesSampledDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels,
+                                      const float* d_weights, bst_ulong nlabel, DMatrixHandle eval_dmat,
+                                      const float* d_eval_labels, const float* d_eval_weights, bst_ulong eval_nlabel,
+                                      const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth,
+                                      float eta, float lambda, float gamma, float min_child_weight, float subsample,
+                                      float colsample_bytree, uint64_t seed, int patience, double* train_rmse,
+                                      double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added,
+                                      void* stream) {
+  API_BEGIN();
+  BoosterObj* b = as_booster(handle);
+  BoostEval ev;
+  ev.dmat = eval_dmat;
+  ev.labels = d_eval_labels;
+  ev.nlabel = eval_nlabel;
+  ev.patience = patience;
+  ev.train_rmse = train_rmse;
+  ev.eval_rmse = eval_rmse;
+  ev.rounds_run = rounds_run;
+  ev.best_round = best_round;
+  BoostWeights wt;
+  wt.weights = d_weights;
+  wt.eval_weights = d_eval_weights;
+  wt.min_child_weight = min_child_weight;
+  BoostSampling sp;
+  sp.subsample = subsample;
+  sp.colsample_bytree = colsample_bytree;
+  sp.seed = seed;
+  boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, 1, nodes_added, false,
+              static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesSampledDevice", &ev, &wt, &sp);
   API_END();
 }
 

@@ -6,6 +6,7 @@
 #include <algorithm>
 #include <cmath>
 #include <string>
+#include <utility>
 
 namespace ohx {
 
@@ -90,6 +91,25 @@ GrowCand grow_node_split_weighted(const int64_t* G, const uint64_t* H, uint32_t 
     if (grow_better(c, best)) best = c;
   }
   return best;
+}
+
+uint32_t grow_pick_features(uint64_t seed, uint64_t i, uint32_t F, float colsample, uint8_t* out) {
+  const uint32_t n_sel = F <= kGrowMaxFeatures ? grow_num_selected(F, colsample) : 0;
+  if (n_sel == 0) return 0;
+  if (n_sel == F) {
+    for (uint32_t f = 0; f < F; ++f) out[f] = (uint8_t)f;
+    return n_sel;
+  }
+  const uint64_t key = grow_col_key(seed, i);
+  std::pair<uint64_t, uint32_t> c[kGrowMaxFeatures];
+  for (uint32_t f = 0; f < F; ++f) c[f] = {grow_mix(key + f), f};
+  std::sort(c, c + F);   // by (c_f, f)
+  bool in[kGrowMaxFeatures] = {};
+  for (uint32_t k = 0; k < n_sel; ++k) in[c[k].second] = true;
+  uint32_t k = 0;
+  for (uint32_t f = 0; f < F; ++f)
+    if (in[f]) out[k++] = (uint8_t)f;
+  return n_sel;
 }
 
 Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature) {

@@ -29,6 +29,7 @@ constexpr uint32_t kGrowFlagState = 2u;        // a node id or a bin outside its
 constexpr uint32_t kGrowFlagEvalLabel = 4u;    // the same as kGrowFlagLabel at a held-out row
 constexpr uint32_t kGrowFlagWeight = 8u;       // a training row's weight that is not finite, negative or >= 256
 constexpr uint32_t kGrowFlagEvalWeight = 16u;  // the same at a held-out row
+constexpr uint32_t kGrowFlagBag = 32u;         // a round whose bag of rows holds no weight (root H == 0)
 
 // gain(G, H) of the header: CalcGain of xgboost 1.6.0 with reg_alpha = 0 and max_delta_step = 0, on the fixed-point sum
 OHX_GROW_HD inline double grow_gain(int64_t G, uint64_t H, double lambda) {
@@ -145,6 +146,36 @@ OHX_GROW_HD inline void grow_solve_leaf_weighted(int64_t G, uint64_t H, float et
   *leaf = w * eta;
 }
 
+// ---- row and column subsampling (OHXBoosterBoostTreesSampled; design in docs/22_sampling.md) ----
+
+// The header's mix function; all arithmetic is uint64 and wraps.
+constexpr uint64_t kGrowGamma64 = 0x9E3779B97F4A7C15ull;
+constexpr uint32_t kGrowSampleOne = 1u << 24;   // k_s of subsample 1.0f: every row is in and nothing is drawn
+OHX_GROW_HD inline uint64_t grow_mix(uint64_t z) {
+  z ^= z >> 30;
+  z *= 0xBF58476D1CE4E5B9ull;
+  z ^= z >> 27;
+  z *= 0x94D049BB133111EBull;
+  z ^= z >> 31;
+  return z;
+}
+// K_row(i) and K_col(i) of tree i, counted over the whole forest
+OHX_GROW_HD inline uint64_t grow_row_key(uint64_t seed, uint64_t i) { return grow_mix(seed + kGrowGamma64 * (2ull * i + 1ull)); }
+OHX_GROW_HD inline uint64_t grow_col_key(uint64_t seed, uint64_t i) { return grow_mix(seed + kGrowGamma64 * (2ull * i + 2ull)); }
+// row r is in the bag of the tree with key K_row when the top 24 bits of its draw lie below k_s
+OHX_GROW_HD inline bool grow_in_bag(uint64_t row_key, uint64_t r, uint32_t k_s) { return (uint32_t)(grow_mix(row_key + r) >> 40) < k_s; }
+// k_s = (uint32) rint((double)subsample * 2^24); 0 where subsample is not finite, <= 0 or > 1 (0 is refused)
+inline uint32_t grow_sample_threshold(float subsample) {
+  if (!(subsample > 0.0f && subsample <= 1.0f)) return 0;
+  return (uint32_t)std::rint((double)subsample * 16777216.0);
+}
+// n_sel = max(1, (int) floor((double)colsample * F)); 0 where colsample is not finite, <= 0 or > 1
+inline uint32_t grow_num_selected(uint32_t F, float colsample) {
+  if (!(colsample > 0.0f && colsample <= 1.0f) || F == 0) return 0;
+  const uint32_t n = (uint32_t)std::floor((double)colsample * (double)F);
+  return n < 1 ? 1 : n;
+}
+
 // A node as the device leaves it.  Children are written as leaves when their parent splits and overwritten if they
 // split in turn, so every record is complete whenever the level loop stops.
 struct GrowNode {
@@ -176,6 +207,10 @@ GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t num_featu
 // grow_weight_splits refuses has no candidate.
 GrowCand grow_node_split_weighted(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr,
                                   int64_t Gp, uint64_t Hp, float lambda, float min_child_weight);
+// The features of tree i: the n_sel = grow_num_selected(F, colsample) features smallest by (mix(K_col(i) + f), f), written
+// to out[0 .. n_sel) in ascending f.  n_sel == F writes 0 .. F - 1 and draws nothing.  Returns n_sel (0: colsample is
+// unsound, F is 0 or above kGrowMaxFeatures; nothing is written).
+uint32_t grow_pick_features(uint64_t seed, uint64_t i, uint32_t F, float colsample, uint8_t* out);
 // A Tree of the forest from n node records; throws on a record that is not a tree in allocation order.
 Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature);
 
@@ -367,6 +402,25 @@ inline size_t grow_wide_count(size_t rounds) { return 2 + (rounds + 1) * 2 * 3; 
 int launch_grow_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream);
 // Enqueues grow_walk_sse_weighted_kernel: grow_walk_sse_kernel's walk, then wsums[round + 1][set] += hq * e^2.
 int launch_grow_walk_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream);
+
+// Row and column subsampling (grow_sampled.hip).  The histograms, `best` and the memsets are compact:
+// [slots][n_sel][256]; the node records, pos, pred and the bins are those of the weighted call.
+struct GrowSampledArgs {
+  GrowWeightedArgs w;
+  unsigned long long* bag = nullptr;   // [ceil(nrow / 64)] a bit a row, or nullptr: every row is in the bag
+  const uint8_t* features = nullptr;   // [rounds][n_sel] the selected features of every round, ascending
+  uint32_t n_sel = 0;
+  uint64_t row_key = 0;                // K_row of the tree at hand (grow_bag_kernel)
+  uint32_t k_s = kGrowSampleOne;
+};
+// Once per device before the first launch: the histogram kernel's dynamic LDS limit.  Returns a hipError_t.
+int prepare_grow_sampled();
+// Enqueues grow_bag_kernel: the bit plane of the tree with a.row_key.  a.bag must not be nullptr.  Returns a hipError_t.
+int launch_grow_bag(const GrowSampledArgs& a, const GrowPlan& plan, void* stream);
+// launch_grow_tree_weighted with grow_hist_sampled_kernel and grow_split_sampled_kernel in the level loop.  plan is
+// plan_grow_weighted's over all features (the partition and leaf kernels); levels is plan_grow_weighted's over n_sel
+// features (the histogram kernel).  Returns a hipError_t.
+int launch_grow_tree_sampled(const GrowSampledArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
 #endif  // __HIPCC__
 
 }  // namespace ohx

@@ -266,3 +266,68 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_weighted_stop(con
     return -1;
   }
 }
+
+// ---- row and column subsampling (OHXBoosterBoostTreesSampled) ----
+
+// out[r] = 1 where row r is in the bag of tree `tree` (grow_row_key, grow_in_bag with grow_sample_threshold(subsample));
+// *k_s: the threshold.  A subsample that is refused (k_s == 0) is an error.
+extern "C" __attribute__((visibility("default"))) int ohx_grow_bag(uint64_t seed, uint64_t tree, uint64_t nrow, float subsample,
+                                                                  uint8_t* out, uint32_t* k_s) {
+  try {
+    const uint32_t k = grow_sample_threshold(subsample);
+    if (k == 0) throw OhxError("ohx_grow_bag: subsample must be finite, > 0 and <= 1, and rint(subsample * 2^24) >= 1");
+    *k_s = k;
+    const uint64_t key = grow_row_key(seed, tree);
+    for (uint64_t r = 0; r < nrow; ++r) out[r] = k == kGrowSampleOne || grow_in_bag(key, r, k) ? 1 : 0;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// out[0 .. *n_sel): the features of tree `tree` (grow_pick_features); out holds F entries
+extern "C" __attribute__((visibility("default"))) int ohx_grow_features(uint64_t seed, uint64_t tree, uint32_t F, float colsample,
+                                                                       uint8_t* out, uint32_t* n_sel) {
+  try {
+    if (F == 0 || F > kGrowMaxFeatures) throw OhxError("ohx_grow_features: 1 to 128 features");
+    const uint32_t n = grow_pick_features(seed, tree, F, colsample, out);
+    if (n == 0) throw OhxError("ohx_grow_features: colsample_bytree must be finite, > 0 and <= 1");
+    *n_sel = n;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// the level plan of a sampled call: plan_grow_weighted over n_sel = grow_num_selected(num_feature, colsample) features;
+// info as ohx_grow_plan_weighted's with info[3] the bin planes of all num_feature features, and info[8] = n_sel
+extern "C" __attribute__((visibility("default"))) int ohx_grow_plan_sampled(uint64_t nrow, uint32_t num_feature, float colsample,
+                                                                           uint64_t ncuts, int max_depth, int num_cus,
+                                                                           uint64_t info[9], uint64_t* levels) {
+  try {
+    if (max_depth < 1 || max_depth > kGrowMaxDepth) throw OhxError("ohx_grow_plan_sampled: max_depth must be in 1..8");
+    const uint32_t n_sel = num_feature <= kGrowMaxFeatures ? grow_num_selected(num_feature, colsample) : 0;
+    if (n_sel == 0) throw OhxError("ohx_grow_plan_sampled: 1 to 128 features and a colsample_bytree in (0, 1]");
+    const GrowPlan p = plan_grow_weighted(nrow, n_sel, ncuts, max_depth, num_cus);
+    info[0] = p.row_blocks;
+    info[1] = kGrowBlock;
+    info[2] = p.bin_lds_bytes;
+    info[3] = (uint64_t)num_feature * nrow;
+    info[4] = p.hist_bytes;
+    info[5] = kGrowHistBlock;
+    info[6] = kGrowWeightedMaxPairs;
+    info[7] = kGrowWeightedPairBytes;
+    info[8] = n_sel;
+    for (size_t d = 0; d < p.levels.size(); ++d) {
+      const GrowLevelPlan& l = p.levels[d];
+      const uint64_t v[7] = {l.slots, l.node_group, l.feat_group, l.node_groups, l.feat_groups, l.hist_blocks, l.lds_bytes};
+      memcpy(levels + d * 7, v, sizeof v);
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}

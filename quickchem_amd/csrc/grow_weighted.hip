@@ -17,6 +17,7 @@
 #include <cstdint>
 
 #include "grow.hpp"
+#include "grow_split_device.hpp"
 #include "walk_device.hpp"
 
 namespace ohx {
@@ -27,19 +28,6 @@ constexpr int kBlock = (int)kGrowBlock;
 constexpr int kHistBlock = (int)kGrowHistBlock;
 constexpr int kWaves = kBlock / kWave;
 constexpr unsigned long long kLow32 = 0xFFFFFFFFull;
-
-// the open nodes of level `level` (as in grow.hip): the root alone at level 0
-__device__ inline void level_range(const GrowArgs& a, uint32_t level, uint32_t* begin, uint32_t* end, uint32_t* next) {
-  if (level == 0) {
-    *begin = 0;
-    *end = 1;
-    *next = 1;
-  } else {
-    *begin = a.state->begin;
-    *end = a.state->end;
-    *next = a.state->next;
-  }
-}
 
 // a row's weight and its fixed-point hessian; false where the weight is out of range
 __device__ inline bool row_weight(const float* weights, uint64_t row, float* w, unsigned long long* hq) {
@@ -58,7 +46,7 @@ __global__ __launch_bounds__(kHistBlock) void grow_hist_weighted_kernel(GrowWeig
   extern __shared__ unsigned long long grow_whist[];
   const GrowArgs& a = wa.g;
   uint32_t begin, end, next;
-  level_range(a, level, &begin, &end, &next);
+  grow_level_range(a, level, &begin, &end, &next);
   const uint32_t count = end - begin;
   const uint32_t slot0 = (blockIdx.y / feat_groups) * node_group;
   const uint32_t f0 = (blockIdx.y % feat_groups) * feat_group;
@@ -116,135 +104,14 @@ __global__ __launch_bounds__(kHistBlock) void grow_hist_weighted_kernel(GrowWeig
   }
 }
 
-__device__ inline GrowCand shuffle_cand(const GrowCand& c, int d) {
-  GrowCand o;
-  o.loss_chg = __shfl_xor(c.loss_chg, d, kWave);
-  o.GL = __shfl_xor((long long)c.GL, d, kWave);
-  o.HL = __shfl_xor((unsigned long long)c.HL, d, kWave);
-  o.key = __shfl_xor(c.key, d, kWave);
-  o.valid = __shfl_xor(c.valid, d, kWave);
-  return o;
-}
-
-__device__ inline void write_leaf(const GrowArgs& a, GrowNode* nodes, uint32_t n, int64_t G, uint64_t H, int32_t parent) {
-  float leaf, weight;
-  grow_solve_leaf_weighted(G, H, a.eta, a.lambda, &leaf, &weight);
-  GrowNode r;
-  r.G = G;
-  r.H = H;
-  r.left = r.right = -1;
-  r.parent = parent;
-  r.feature = r.cut = r.default_left = 0;
-  r.value = leaf;
-  r.loss_chg = 0.0f;
-  r.sum_hess = (float)grow_hess(H);
-  r.base_weight = weight;
-  nodes[n] = r;
-}
-
-// PHASE 0: grid (blocks of four waves over slots x features).  PHASE 1: one block.
+// PHASE 0: grid (blocks of four waves over slots x features).  PHASE 1: one block.  The bodies are grow_split_device.hpp's,
+// here with a histogram column for every feature.
 template <int PHASE>
 __global__ __launch_bounds__(kBlock) void grow_split_weighted_kernel(GrowWeightedArgs wa, uint32_t level, uint32_t round) {
-  const GrowArgs& a = wa.g;
-  uint32_t begin, end, next;
-  level_range(a, level, &begin, &end, &next);
-  const uint32_t count = end - begin;
-  const uint32_t F = a.num_feature;
-  GrowNode* nodes = a.nodes + (uint64_t)round * kGrowMaxNodes;
   if (PHASE == 0) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t w = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
-    const uint32_t slot = w / F, f = w % F;
-    if (slot >= count) return;
-    const uint64_t at = ((uint64_t)slot * F + f) * kGrowBins + 4u * lane;
-    int64_t g4[4];
-    uint64_t h4[4];
-    int64_t gs = 0;
-    uint64_t hs = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      g4[k] = (int64_t)a.Ghist[at + k];
-      h4[k] = (uint64_t)a.Hhist[at + k];
-      gs += g4[k];
-      hs += h4[k];
-    }
-    // inclusive sums across the wave, then the sums below the lane's first bin
-    long long gi = gs;
-    unsigned long long hi = hs;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const long long gt = __shfl_up(gi, d, kWave);
-      const unsigned long long ht = __shfl_up(hi, d, kWave);
-      if (lane >= d) {
-        gi += gt;
-        hi += ht;
-      }
-    }
-    const int64_t Gp = __shfl(gi, kWave - 1, kWave);
-    const uint64_t Hp = __shfl(hi, kWave - 1, kWave);
-    const int64_t Gm = __shfl((long long)g4[3], kWave - 1, kWave);
-    const uint64_t Hm = __shfl((unsigned long long)h4[3], kWave - 1, kWave);
-    if (level == 0 && f == 0 && lane == 0) {   // the root's sums: every row is in one bin of feature 0
-      nodes[0].G = Gp;
-      nodes[0].H = Hp;
-    }
-    const uint32_t ncut = a.cut_ptr[f + 1] - a.cut_ptr[f];
-    GrowCand c = grow_best_split_weighted(g4, h4, f, 4u * lane, 4u, ncut, gi - gs, hi - hs, Gm, Hm, Gp, Hp, (double)a.lambda,
-                                          wa.min_child_weight);
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const GrowCand o = shuffle_cand(c, d);
-      if (grow_better(o, c)) c = o;
-    }
-    if (lane == 0) a.best[(uint64_t)slot * F + f] = c;
+    grow_split_weighted_columns(wa, level, round, wa.g.num_feature, GrowIdentityMap());
   } else {
-    __shared__ uint32_t splits[kGrowMaxNodes / 2];
-    const uint32_t s = threadIdx.x;
-    const bool active = s < count && s < kGrowMaxNodes / 2;
-    const uint32_t node = begin + s;
-    GrowCand best;
-    int64_t Gp = 0;
-    uint64_t Hp = 0;
-    if (active) {
-      Gp = nodes[node].G;
-      Hp = nodes[node].H;
-      if (level == 0) write_leaf(a, nodes, 0, Gp, Hp, -1);
-      for (uint32_t f = 0; f < F; ++f) {
-        const GrowCand c = a.best[(uint64_t)s * F + f];
-        if (grow_better(c, best)) best = c;
-      }
-    }
-    const bool split = active && best.valid && best.loss_chg > (double)a.gamma && grow_weight_splits(Hp, wa.min_child_weight);
-    if (s < kGrowMaxNodes / 2) splits[s] = split ? 1u : 0u;
-    __syncthreads();
-    uint32_t below = 0, total = 0;
-    const uint32_t live = count < kGrowMaxNodes / 2 ? count : kGrowMaxNodes / 2;
-    for (uint32_t i = 0; i < live; ++i) {
-      total += splits[i];
-      if (i < s) below += splits[i];
-    }
-    if (next + 2u * total > kGrowMaxNodes) {   // (never: a tree of depth 8 has 511 nodes)
-      if (s == 0) atomicOr(&a.state->error, kGrowFlagState);
-      total = 0;
-    } else if (split) {
-      const uint32_t f = best.key >> 9, j = (best.key >> 1) & 255u, dl = best.key & 1u;
-      const uint32_t left = next + 2u * below;
-      nodes[node].left = (int32_t)left;
-      nodes[node].right = (int32_t)left + 1;
-      nodes[node].feature = f;
-      nodes[node].cut = j;
-      nodes[node].default_left = dl;
-      nodes[node].value = a.cuts[a.cut_ptr[f] + j];
-      nodes[node].loss_chg = (float)best.loss_chg;
-      write_leaf(a, nodes, left, best.GL, best.HL, (int32_t)(node | 0x80000000u));
-      write_leaf(a, nodes, left + 1, Gp - best.GL, Hp - best.HL, (int32_t)node);
-    }
-    if (s == 0) {
-      a.state->begin = next;
-      a.state->end = next + 2u * total;
-      a.state->next = next + 2u * total;
-      a.tree_nodes[round] = next + 2u * total;
-    }
+    grow_split_weighted_nodes<false>(wa, level, round, wa.g.num_feature);
   }
 }
 

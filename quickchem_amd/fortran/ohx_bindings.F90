@@ -456,6 +456,45 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
+      !  Boosting with row and column subsampling (include/ohxgb.h; docs/22_sampling.md).  Interface blocks only.  The
+      !  weighted call with subsample, colsample_bytree (both in (0, 1]) and seed (the 64 bits of a uint64) before patience
+      function OHXBoosterBoostTreesSampled(handle, dmat, labels, weights, nlabel, eval_dmat, eval_labels, eval_weights, &
+            eval_nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_weight, subsample, &
+            colsample_bytree, seed, patience, train_rmse, eval_rmse, rounds_run, best_round, nodes_added) &
+            bind(C, name="OHXBoosterBoostTreesSampled") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat, weights, eval_dmat, eval_labels, eval_weights
+         real(c_float), intent(in)       :: labels(*)
+         integer(c_int64_t), value       :: nlabel, eval_nlabel
+         integer(c_int64_t), intent(in)  :: cut_ptr(*)
+         real(c_float), intent(in)       :: cut_values(*)
+         integer(c_int), value           :: rounds, max_depth, patience
+         real(c_float), value            :: eta, lambda, gamma, min_child_weight, subsample, colsample_bytree
+         integer(c_int64_t), value       :: seed
+         type(c_ptr), value              :: train_rmse, eval_rmse
+         integer(c_int), intent(out)     :: rounds_run, best_round
+         type(c_ptr), value              :: nodes_added
+         integer(c_int)                  :: rc
+      end function
+
+      function OHXBoosterBoostTreesSampledDevice(handle, dmat, d_labels, d_weights, nlabel, eval_dmat, d_eval_labels, &
+            d_eval_weights, eval_nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_weight, &
+            subsample, colsample_bytree, seed, patience, train_rmse, eval_rmse, rounds_run, best_round, nodes_added, &
+            stream) bind(C, name="OHXBoosterBoostTreesSampledDevice") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat, d_labels, d_weights, eval_dmat, d_eval_labels, d_eval_weights, stream
+         integer(c_int64_t), value       :: nlabel, eval_nlabel
+         integer(c_int64_t), intent(in)  :: cut_ptr(*)
+         real(c_float), intent(in)       :: cut_values(*)
+         integer(c_int), value           :: rounds, max_depth, patience
+         real(c_float), value            :: eta, lambda, gamma, min_child_weight, subsample, colsample_bytree
+         integer(c_int64_t), value       :: seed
+         type(c_ptr), value              :: train_rmse, eval_rmse
+         integer(c_int), intent(out)     :: rounds_run, best_round
+         type(c_ptr), value              :: nodes_added
+         integer(c_int)                  :: rc
+      end function
+
       !  data: a row-major host sample (nrow x ncol); cut_ptr: ncol + 1 entries out; needed: the cut values in all
       function OHXQuantileCuts(data, nrow, ncol, missing, max_bins, cut_ptr, cut_values, cap, needed) &
             bind(C, name="OHXQuantileCuts") result(rc)

@@ -113,6 +113,10 @@ def _load():
         lib.ohx_grow_weighted_rmse.restype = C.c_double
         lib.ohx_grow_weighted_compare.argtypes = [C.c_void_p, C.c_void_p]
         lib.ohx_grow_weighted_stop.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
+        lib.ohx_grow_bag.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p]
+        lib.ohx_grow_features.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
+        lib.ohx_grow_plan_sampled.argtypes = [C.c_uint64, C.c_uint32, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
+                                              C.c_void_p]
         lib.ohx_cuts_select.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int, C.c_uint64, C.c_void_p,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_cuts_keys.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -561,6 +565,39 @@ def boost_weighted_stop(sums, patience: int):
     out = np.zeros(2, dtype=np.uint32)
     _check(_load().ohx_grow_weighted_stop(a.ctypes.data, len(a), patience, out.ctypes.data))
     return int(out[0]), int(out[1])
+
+
+def boost_bag(seed: int, tree: int, nrow: int, subsample: float):
+    """csrc/grow.hpp grow_row_key, grow_in_bag and grow_sample_threshold: the bag of tree `tree` (its index in the whole
+    forest) over rows 0 .. nrow - 1 -> (bool [nrow], k_s).  Raises where the subsample is one the call refuses."""
+    out = np.zeros(max(nrow, 1), dtype=np.uint8)
+    ks = C.c_uint32()
+    _check(_load().ohx_grow_bag(int(seed) & 0xFFFFFFFFFFFFFFFF, int(tree) & 0xFFFFFFFFFFFFFFFF, nrow, subsample, out.ctypes.data,
+                                C.addressof(ks)))
+    return out[:nrow].astype(bool), int(ks.value)
+
+
+def boost_features(seed: int, tree: int, F: int, colsample: float):
+    """csrc/grow.cpp grow_pick_features: the features tree `tree` may split on, ascending (uint8 [n_sel])."""
+    out = np.zeros(max(F, 1), dtype=np.uint8)
+    n = C.c_uint32()
+    _check(_load().ohx_grow_features(int(seed) & 0xFFFFFFFFFFFFFFFF, int(tree) & 0xFFFFFFFFFFFFFFFF, F, colsample, out.ctypes.data,
+                                     C.addressof(n)))
+    return out[:int(n.value)].copy()
+
+
+def grow_plan_sampled(nrow: int, num_feature: int = NFEAT, colsample: float = 1.0, ncuts: int = 0, max_depth: int = 6,
+                      num_cus: int = 256):
+    """The level plan of OHXBoosterBoostTreesSampled: csrc/grow.hpp plan_grow_weighted over the n_sel features a tree
+    sees -> the dict of grow_plan_weighted with n_sel; bins_bytes are the planes of all num_feature features."""
+    info = (C.c_uint64 * 9)()
+    lev = np.zeros((max(max_depth, 1), 7), dtype=np.uint64)
+    _check(_load().ohx_grow_plan_sampled(nrow, num_feature, colsample, ncuts, max_depth, num_cus, info, lev.ctypes.data))
+    names = ("slots", "node_group", "feat_group", "node_groups", "feat_groups", "hist_blocks", "lds_bytes")
+    return {"row_blocks": int(info[0]), "block_rows": int(info[1]), "bin_lds_bytes": int(info[2]),
+            "bins_bytes": int(info[3]), "hist_bytes": int(info[4]), "hist_block_rows": int(info[5]),
+            "max_pairs": int(info[6]), "pair_bytes": int(info[7]), "n_sel": int(info[8]),
+            "levels": [dict(zip(names, (int(v) for v in row))) for row in lev]}
 
 
 def quantile_cuts_select(x, missing: float = float("nan"), max_bins: int = 255, row_step: int = 1, bits=(12, 10, 10)):

@@ -23,7 +23,11 @@ this script computes itself, in torch from margin predicts, before the call and 
 
 `--weights ones|random` times OHXBoosterBoostTreesWeightedDevice (docs/21_row_weights.md) wherever `--weights none` (the
 default) times the plain call, with a weight of 1.0 a row or weights uniform in [0, 4) in HBM, no held-out set and
-min_child_weight 1; the timings stand under the same keys, so three runs that differ in `--weights` alone compare."""
+min_child_weight 1; the timings stand under the same keys, so three runs that differ in `--weights` alone compare.
+
+`--subsample S` and / or `--colsample C` time OHXBoosterBoostTreesSampledDevice (docs/22_sampling.md) in the same place,
+with `--seed` and the weights `--weights` names (none: a NULL pointer); the plan written is the one over the n_sel features
+a tree sees.  `--subsample 1 --colsample 1` is the sampled entry point on the weighted path."""
 from __future__ import annotations
 
 import argparse
@@ -125,7 +129,16 @@ def main():
     ap.add_argument("--patience", type=int, default=3, help="with --holdout: the patience of the early-stopping call")
     ap.add_argument("--weights", choices=("none", "ones", "random"), default="none",
                     help="ones / random: time OHXBoosterBoostTreesWeightedDevice in place of the plain call")
+    ap.add_argument("--subsample", type=float, default=None, help="time OHXBoosterBoostTreesSampledDevice with this fraction of the rows a tree")
+    ap.add_argument("--colsample", type=float, default=None, help="... and this fraction of the features a tree (colsample_bytree)")
+    ap.add_argument("--seed", type=int, default=0, help="the seed of the sampled call's draws")
     args = ap.parse_args()
+    sampled = args.subsample is not None or args.colsample is not None
+    if sampled:
+        args.subsample = 1.0 if args.subsample is None else args.subsample
+        args.colsample = 1.0 if args.colsample is None else args.colsample
+    if sampled and args.holdout:
+        ap.error("--subsample / --colsample time the call without a held-out set: leave --holdout out")
     if args.weights != "none" and args.holdout:
         ap.error("--weights times the call without a held-out set: leave --holdout out")
     assert torch.cuda.is_available(), "boost_timing needs the MI355X"
@@ -180,7 +193,11 @@ def main():
         res["cuts_full_plan"] = synth.cuts_plan(n, 1, F, cus)
     ncuts = int(cuts[0][-1])
     res["cut_values"] = ncuts
-    res["plan"] = (synth.grow_plan if args.weights == "none" else synth.grow_plan_weighted)(n, F, ncuts, args.max_depth, cus)
+    if sampled:
+        res["plan"] = synth.grow_plan_sampled(n, F, args.colsample, ncuts, args.max_depth, cus)
+        res["sampling"] = {"subsample": args.subsample, "colsample_bytree": args.colsample, "seed": args.seed}
+    else:
+        res["plan"] = (synth.grow_plan if args.weights == "none" else synth.grow_plan_weighted)(n, F, ncuts, args.max_depth, cus)
     print("cuts", json.dumps({k: v for k, v in res.items() if k.startswith("cuts_") and not k.endswith("plan")}), flush=True)
 
     def margins(b):
@@ -208,7 +225,14 @@ def main():
     def boost(b, rounds):
         torch.cuda.synchronize()
         t = time.perf_counter()
-        if weights is None:
+        if sampled:
+            r = b.boost_trees_sampled_device(d, labels.data_ptr(), n, cuts, weights_ptr=weights.data_ptr() if weights is not None else 0,
+                                             rounds=rounds, max_depth=args.max_depth, eta=args.eta, reg_lambda=args.reg_lambda,
+                                             min_child_weight=1.0, subsample=args.subsample, colsample_bytree=args.colsample,
+                                             seed=args.seed, stream=stream)
+            nodes = r["nodes_added"]
+            last.update(rounds=rounds, train_rmse=r["train_rmse"].tolist())
+        elif weights is None:
             nodes = b.boost_trees_device(d, labels.data_ptr(), n, cuts, rounds=rounds, max_depth=args.max_depth, eta=args.eta,
                                          reg_lambda=args.reg_lambda, stream=stream)
         else:
