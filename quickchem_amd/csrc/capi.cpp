@@ -651,7 +651,7 @@ struct RefitState {
 // first call on the loaded model; never a buffer of another path.
 struct GrowState {
   int device = -1;
-  bool prepared = false, prepared_weighted = false, prepared_sampled = false;
+  bool prepared = false;               // prepare_grow has raised the LDS limits on `device`
   DevBuf<uint8_t> d_bins;
   DevBuf<uint16_t> d_pos;
   DevBuf<float> d_pred, d_labels, d_cuts;
@@ -665,16 +665,14 @@ struct GrowState {
   PinnedBuf<float> h_cuts;
   PinnedBuf<GrowLevelState> h_state;
   // the held-out metric (OHXBoosterBoostTreesEval): the held-out rows' bin planes, margin and staged labels, and the
-  // sums [rounds + 1][2 sets][hi, lo]
+  // sums in the layout of the call's kind: [rounds + 1][2 sets][hi, lo], or with row weights W of both sets followed
+  // by [rounds + 1][2 sets][p2, p1, p0]
   DevBuf<uint8_t> d_eval_bins;
   DevBuf<float> d_eval_pred, d_eval_labels;
   DevBuf<unsigned long long> d_sums;
   PinnedBuf<unsigned long long> h_sums;
-  // row weights (OHXBoosterBoostTreesWeighted): the staged weights of both sets, and W of both sets followed by the
-  // sums [rounds + 1][2 sets][p2, p1, p0]
+  // row weights (OHXBoosterBoostTreesWeighted): the staged weights of both sets
   DevBuf<float> d_weights, d_eval_weights;
-  DevBuf<unsigned long long> d_wsums;
-  PinnedBuf<unsigned long long> h_wsums;
   // subsampling (OHXBoosterBoostTreesSampled): the bag's bit plane of the tree at hand, a bit a row, and the selected
   // features of every round [rounds][n_sel]
   DevBuf<unsigned long long> d_bag;
@@ -687,7 +685,6 @@ struct GrowState {
     d_pos.release();
     d_eval_bins.release();
     d_sums.release();
-    d_wsums.release();
     for (DevBuf<float>* f : {&d_pred, &d_labels, &d_cuts, &d_eval_pred, &d_eval_labels, &d_weights, &d_eval_weights}) f->release();
     for (DevBuf<uint32_t>* f : {&d_cut_ptr, &d_tree_nodes, &d_saved_flag}) f->release();
     d_Ghist.release();
@@ -695,7 +692,7 @@ struct GrowState {
     d_best.release();
     d_nodes.release();
     d_state.release();
-    prepared = prepared_weighted = prepared_sampled = false;
+    prepared = false;
   }
 };
 
@@ -2204,8 +2201,12 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
 
 // ---- boosting new trees (grow.hpp) ----
 
-// What OHXBoosterBoostTreesEval adds to a boost call: the held-out set, the patience and where the results go.
+// The optional parts of a boost call.  OHXBoosterBoostTreesEval adds the held-out set, the patience and where the
+// results go; OHXBoosterBoostTreesWeighted the weights of both sets (either may be NULL: all 1.0f) and min_child_weight
+// in place of min_child_rows; OHXBoosterBoostTreesSampled the fraction of the rows and of the features a tree sees, and
+// the seed of the draws.
 struct BoostEval {
+  bool present = false;
   DMatrixHandle dmat = nullptr;      // NULL: no held-out set
   const float* labels = nullptr;
   bst_ulong nlabel = 0;
@@ -2215,36 +2216,128 @@ struct BoostEval {
   int* rounds_run = nullptr;
   int* best_round = nullptr;
 };
-
-// What OHXBoosterBoostTreesWeighted adds to a call with `ev`: the weights of both sets (either may be NULL: all 1.0f)
-// and min_child_weight in place of min_child_rows.
 struct BoostWeights {
+  bool present = false;
   const float* weights = nullptr;
   const float* eval_weights = nullptr;
   float min_child_weight = 0.0f;
 };
-
-// What OHXBoosterBoostTreesSampled adds to a call with `wt`: the fraction of the rows and of the features a tree sees,
-// and the seed of the draws.
 struct BoostSampling {
+  bool present = false;
   float subsample = 1.0f;
   float colsample_bytree = 1.0f;
   uint64_t seed = 0;
 };
 
-// Both forms of OHXBoosterBoostTrees, of OHXBoosterBoostTreesEval where `ev` is given, of
-// OHXBoosterBoostTreesWeighted where `wt` is given too (then min_child_rows is not looked at), and of
-// OHXBoosterBoostTreesSampled where `sp` is given as well.  The refusals that need
-// neither a matrix nor a device come first, in the header's order; nothing is enqueued before the last of them.
-// Without `ev` nothing of the metric is allocated or enqueued; without `wt` nothing of the weights; without `sp`, or
-// with a subsample and a colsample_bytree of 1, nothing of the sampling: that call takes the weighted path.
-void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulong nlabel, const bst_ulong* cut_ptr,
-                 const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
-                 bst_ulong min_child_rows, bst_ulong* nodes_added, bool host_form, hipStream_t caller, const char* what,
-                 const BoostEval* ev = nullptr, const BoostWeights* wt = nullptr, const BoostSampling* sp = nullptr) {
-  const std::string w0(what);
-  if (wt != nullptr && ev == nullptr) throw OhxError(w0 + ": the weighted call carries the metric");
-  if (sp != nullptr && wt == nullptr) throw OhxError(w0 + ": the sampled call carries the weights");
+// One call of any OHXBoosterBoostTrees* entry point: the training set, the hyper-parameters, the optional parts, and
+// the form (host arrays staged on the library's stream, or device arrays on the caller's).
+struct BoostCall {
+  const char* what = "";
+  bool host_form = true;
+  hipStream_t caller = nullptr;
+  DMatrixHandle dmat = nullptr;
+  const float* labels = nullptr;
+  bst_ulong nlabel = 0;
+  const bst_ulong* cut_ptr = nullptr;
+  const float* cut_values = nullptr;
+  int rounds = 0, max_depth = 0;
+  float eta = 0.0f, lambda = 0.0f, gamma = 0.0f;
+  bst_ulong min_child_rows = 1;      // not looked at where `weights` is present
+  bst_ulong* nodes_added = nullptr;
+  BoostEval eval;
+  BoostWeights weights;
+  BoostSampling sampling;
+};
+
+BoostCall boost_call(const char* what, bool host_form, void* stream, DMatrixHandle dmat, const float* labels, bst_ulong nlabel,
+                     const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta, float lambda,
+                     float gamma, bst_ulong* nodes_added) {
+  BoostCall c;
+  c.what = what;
+  c.host_form = host_form;
+  c.caller = static_cast<hipStream_t>(stream);
+  c.dmat = dmat;
+  c.labels = labels;
+  c.nlabel = nlabel;
+  c.cut_ptr = cut_ptr;
+  c.cut_values = cut_values;
+  c.rounds = rounds;
+  c.max_depth = max_depth;
+  c.eta = eta;
+  c.lambda = lambda;
+  c.gamma = gamma;
+  c.nodes_added = nodes_added;
+  return c;
+}
+
+BoostEval boost_eval(DMatrixHandle dmat, const float* labels, bst_ulong nlabel, int patience, double* train_rmse,
+                     double* eval_rmse, int* rounds_run, int* best_round) {
+  BoostEval ev;
+  ev.present = true;
+  ev.dmat = dmat;
+  ev.labels = labels;
+  ev.nlabel = nlabel;
+  ev.patience = patience;
+  ev.train_rmse = train_rmse;
+  ev.eval_rmse = eval_rmse;
+  ev.rounds_run = rounds_run;
+  ev.best_round = best_round;
+  return ev;
+}
+
+BoostWeights boost_weights(const float* weights, const float* eval_weights, float min_child_weight) {
+  BoostWeights wt;
+  wt.present = true;
+  wt.weights = weights;
+  wt.eval_weights = eval_weights;
+  wt.min_child_weight = min_child_weight;
+  return wt;
+}
+
+// The kind of a call, and in one place what it runs: its level plan, its tree launcher, its metric launchers and the
+// layout of its metric sums (the words of one sum, where sum (t, set) lies, and the words in all for `rounds` rounds).
+// Plain: row counts and 12-byte bins.  Weighted: fixed-point hessians.  Sampled: the same over a bag and a feature list.
+// (Calls, not a table of function addresses: a build of this file alone links without the grower until it is used.)
+struct BoostKind {
+  enum Which { Plain, Weighted, Sampled } which;
+  bool wide() const { return which != Plain; }
+  GrowPlan plan(uint64_t n, uint32_t F, uint64_t ncuts, int max_depth, int num_cus) const {
+    return wide() ? plan_grow_weighted(n, F, ncuts, max_depth, num_cus) : plan_grow(n, F, ncuts, max_depth, num_cus);
+  }
+  hipError_t tree(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream) const {
+    switch (which) {
+      case Sampled: return (hipError_t)launch_grow_tree_sampled(a, plan, levels, round, stream);
+      case Weighted: return (hipError_t)launch_grow_tree_weighted(a, plan, levels, round, stream);
+      default: return (hipError_t)launch_grow_tree(a, plan, levels, round, stream);
+    }
+  }
+  hipError_t sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream) const {
+    return (hipError_t)(wide() ? launch_grow_sse_weighted(a, blocks, t, set, stream) : launch_grow_sse(a, blocks, t, set, stream));
+  }
+  hipError_t walk_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream) const {
+    return (hipError_t)(wide() ? launch_grow_walk_sse_weighted(a, blocks, round, set, stream)
+                               : launch_grow_walk_sse(a, blocks, round, set, stream));
+  }
+  size_t words() const { return wide() ? 3 : 2; }
+  size_t index(uint32_t t, uint32_t set) const { return wide() ? grow_wide_index(t, set) : grow_sum_index(t, set); }
+  size_t count(size_t rounds) const { return wide() ? grow_wide_count(rounds) : grow_sum_count(rounds); }
+  const char* sums_name() const { return wide() ? "the weighted metric sums" : "the metric sums"; }
+  const char* hess_name() const { return wide() ? "the hessian histograms" : "the count histograms"; }
+};
+
+// Every OHXBoosterBoostTrees* entry point, in both forms.  The refusals that need neither a matrix nor a device come
+// first, in the header's order; nothing is enqueued before the last of them.  Without `eval` nothing of the metric is
+// allocated or enqueued; without `weights` nothing of the weights; without `sampling`, or with a subsample and a
+// colsample_bytree of 1, nothing of the sampling: that call takes the weighted path.
+void boost_trees(BoosterObj& b, const BoostCall& c) {
+  const std::string w0(c.what);
+  const char* what = c.what;
+  const BoostEval& ev = c.eval;
+  const BoostWeights& wt = c.weights;
+  const bool weighted = wt.present, host_form = c.host_form;
+  const int max_depth = c.max_depth;
+  if (weighted && !ev.present) throw OhxError(w0 + ": the weighted call carries the metric");
+  if (c.sampling.present && !weighted) throw OhxError(w0 + ": the sampled call carries the weights");
   if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
   refuse_categorical(b, what);
   refuse_groups(b, what);
@@ -2252,63 +2345,65 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     throw OhxError(w0 + " fits squared-error trees (gradient pred - label, hessian 1): the objective " + b.forest.objective +
                    " is not reg:squarederror");
   if (!b.margin_error.empty()) throw OhxError(b.margin_error);
-  if (labels == nullptr) throw OhxError(w0 + ": labels is NULL");
-  if (cut_ptr == nullptr || cut_values == nullptr) throw OhxError(w0 + ": the cuts are NULL");
+  if (c.labels == nullptr) throw OhxError(w0 + ": labels is NULL");
+  if (c.cut_ptr == nullptr || c.cut_values == nullptr) throw OhxError(w0 + ": the cuts are NULL");
   const uint32_t F = b.forest.num_feature;
   if (F == 0 || F > kGrowMaxFeatures)
     throw OhxError(w0 + ": the booster has " + std::to_string(F) + " features; 1 to 128 are binned (their cuts are staged in LDS)");
-  if (rounds < 1) throw OhxError(w0 + ": rounds must be >= 1");
+  if (c.rounds < 1) throw OhxError(w0 + ": rounds must be >= 1");
   if (max_depth < 1 || max_depth > kGrowMaxDepth) throw OhxError(w0 + ": max_depth must be in 1..8");
-  if (!std::isfinite(eta)) throw OhxError(w0 + ": eta must be finite");
-  if (!(std::isfinite(lambda) && lambda >= 0.0f)) throw OhxError(w0 + ": lambda must be finite and >= 0");
-  if (!(std::isfinite(gamma) && gamma >= 0.0f)) throw OhxError(w0 + ": gamma must be finite and >= 0");
-  if (wt == nullptr && min_child_rows < 1) throw OhxError(w0 + ": min_child_rows must be >= 1");
-  if (wt != nullptr && !(std::isfinite(wt->min_child_weight) && wt->min_child_weight >= 0.0f))
+  if (!std::isfinite(c.eta)) throw OhxError(w0 + ": eta must be finite");
+  if (!(std::isfinite(c.lambda) && c.lambda >= 0.0f)) throw OhxError(w0 + ": lambda must be finite and >= 0");
+  if (!(std::isfinite(c.gamma) && c.gamma >= 0.0f)) throw OhxError(w0 + ": gamma must be finite and >= 0");
+  if (!weighted && c.min_child_rows < 1) throw OhxError(w0 + ": min_child_rows must be >= 1");
+  if (weighted && !(std::isfinite(wt.min_child_weight) && wt.min_child_weight >= 0.0f))
     throw OhxError(w0 + ": min_child_weight must be finite and >= 0");
   uint32_t k_s = kGrowSampleOne, n_sel = F;   // the bag's threshold and the features a tree sees
-  if (sp != nullptr) {
-    k_s = grow_sample_threshold(sp->subsample);
+  if (c.sampling.present) {
+    k_s = grow_sample_threshold(c.sampling.subsample);
     if (k_s == 0)
       throw OhxError(w0 + ": subsample must be finite, > 0 and <= 1, and rint(subsample * 2^24) must be >= 1");
-    n_sel = grow_num_selected(F, sp->colsample_bytree);
+    n_sel = grow_num_selected(F, c.sampling.colsample_bytree);
     if (n_sel == 0) throw OhxError(w0 + ": colsample_bytree must be finite, > 0 and <= 1");
   }
-  const bool sampled = k_s != kGrowSampleOne || n_sel != F;
-  grow_check_cuts(cut_ptr, cut_values, F, what);
-  if (ev != nullptr) {
-    if (ev->patience < 0) throw OhxError(w0 + ": patience must be >= 0");
-    if (ev->rounds_run == nullptr || ev->best_round == nullptr) throw OhxError(w0 + ": rounds_run or best_round is NULL");
-    if (ev->dmat == nullptr) {
-      if (ev->patience >= 1)
-        throw OhxError(w0 + ": patience " + std::to_string(ev->patience) + " needs a held-out matrix to stop on (eval_dmat is NULL)");
-      if (ev->labels != nullptr || ev->nlabel != 0)
+  grow_check_cuts(c.cut_ptr, c.cut_values, F, what);
+  if (ev.present) {
+    if (ev.patience < 0) throw OhxError(w0 + ": patience must be >= 0");
+    if (ev.rounds_run == nullptr || ev.best_round == nullptr) throw OhxError(w0 + ": rounds_run or best_round is NULL");
+    if (ev.dmat == nullptr) {
+      if (ev.patience >= 1)
+        throw OhxError(w0 + ": patience " + std::to_string(ev.patience) + " needs a held-out matrix to stop on (eval_dmat is NULL)");
+      if (ev.labels != nullptr || ev.nlabel != 0)
         throw OhxError(w0 + ": eval labels are given without a held-out matrix (eval_dmat is NULL)");
-      if (wt != nullptr && wt->eval_weights != nullptr)
+      if (wt.eval_weights != nullptr)
         throw OhxError(w0 + ": eval weights are given without a held-out matrix (eval_dmat is NULL)");
-    } else if (ev->labels == nullptr) {
+    } else if (ev.labels == nullptr) {
       throw OhxError(w0 + ": eval labels is NULL");
     }
   }
-  DMatrixObj& d = *as_dmat(dmat);
+  DMatrixObj& d = *as_dmat(c.dmat);
   if (d.nrow == 0) throw OhxError(w0 + ": the matrix has no rows");
-  if (nlabel != d.nrow) throw OhxError(w0 + ": " + std::to_string(nlabel) + " labels for " + std::to_string(d.nrow) + " rows");
+  if (c.nlabel != d.nrow) throw OhxError(w0 + ": " + std::to_string(c.nlabel) + " labels for " + std::to_string(d.nrow) + " rows");
   if (d.nrow > kRefitMaxRows) throw OhxError(w0 + ": at most 2^31 rows per call (" + std::to_string(d.nrow) + " given)");
   check_columns(b, d.ncol);
   DMatrixObj* e = nullptr;           // the held-out matrix
-  if (ev != nullptr && ev->dmat != nullptr) {
-    if (ev->dmat != dmat && !g_dmats.has(ev->dmat)) throw OhxError(w0 + ": the held-out DMatrix handle is invalid or has been freed");
-    e = static_cast<DMatrixObj*>(ev->dmat);
+  if (ev.dmat != nullptr) {
+    if (ev.dmat != c.dmat && !g_dmats.has(ev.dmat)) throw OhxError(w0 + ": the held-out DMatrix handle is invalid or has been freed");
+    e = static_cast<DMatrixObj*>(ev.dmat);
     if (e->nrow == 0) throw OhxError(w0 + ": the held-out matrix has no rows");
-    if (ev->nlabel != e->nrow)
-      throw OhxError(w0 + ": " + std::to_string(ev->nlabel) + " eval labels for " + std::to_string(e->nrow) + " held-out rows");
+    if (ev.nlabel != e->nrow)
+      throw OhxError(w0 + ": " + std::to_string(ev.nlabel) + " eval labels for " + std::to_string(e->nrow) + " held-out rows");
     if (e->nrow > kRefitMaxRows) throw OhxError(w0 + ": at most 2^31 held-out rows per call (" + std::to_string(e->nrow) + " given)");
     check_columns(b, e->ncol);
     if (e->device >= 0 && d.device >= 0 && e->device != d.device)
       throw OhxError(w0 + ": the held-out DMatrix lives on HIP device " + std::to_string(e->device) + " but the training matrix on device " +
                      std::to_string(d.device));
   }
+  // the kind of the call, once: everything below that differs by kernel or by sum layout asks `kind`
+  const bool sampled = k_s != kGrowSampleOne || n_sel != F;
+  const BoostKind kind{sampled ? BoostKind::Sampled : weighted ? BoostKind::Weighted : BoostKind::Plain};
   // before anything is built or enqueued: building the state waits for the library's stream
-  if (!host_form && stream_capturing(caller))
+  if (!host_form && stream_capturing(c.caller))
     refuse_in_capture("grow trees", (w0 + " is not capturable; call it outside the capture").c_str());
   ensure_uploaded(b);                      // throws where there is no device; the initial margin is a margin predict
   const DeviceInfo dev = b.dev;
@@ -2324,20 +2419,12 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     HIP_CHECK((hipError_t)prepare_grow());
     g.prepared = true;
   }
-  if (wt != nullptr && !g.prepared_weighted) {
-    HIP_CHECK((hipError_t)prepare_grow_weighted());
-    g.prepared_weighted = true;
-  }
-  if (sampled && !g.prepared_sampled) {
-    HIP_CHECK((hipError_t)prepare_grow_sampled());
-    g.prepared_sampled = true;
-  }
-  const uint64_t n = d.nrow, ncuts = cut_ptr[F];
-  const size_t R = (size_t)rounds;
-  const GrowPlan plan = wt != nullptr ? plan_grow_weighted(n, F, ncuts, max_depth, dev.num_cus) : plan_grow(n, F, ncuts, max_depth, dev.num_cus);
+  const uint64_t n = d.nrow, ncuts = c.cut_ptr[F];
+  const size_t R = (size_t)c.rounds;
+  const GrowPlan plan = kind.plan(n, F, ncuts, max_depth, dev.num_cus);
   // the level loop over a tree's n_sel features: compact histograms and candidates (the bins hold every feature)
-  const GrowPlan splan = sampled ? plan_grow_weighted(n, n_sel, ncuts, max_depth, dev.num_cus) : GrowPlan();
-  const uint64_t hist_bytes = sampled ? splan.hist_bytes : plan.hist_bytes;
+  const GrowPlan splan = sampled ? kind.plan(n, n_sel, ncuts, max_depth, dev.num_cus) : GrowPlan();
+  const GrowPlan& levels = sampled ? splan : plan;
   const uint64_t tree0 = b.forest.trees.size();   // T0: tree t of the call is tree tree0 + t - 1 of the draws
   auto room = [&](auto& buf, size_t count, size_t elem, const char* name) {
     try {
@@ -2346,22 +2433,25 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
       throw OhxError(w0 + ": " + name + " of " + std::to_string((uint64_t)count * elem) + " bytes cannot be allocated (" + e.what() + ")");
     }
   };
+  const size_t nsums = kind.count(R);
+  auto sums_room = [&]() {
+    room(g.d_sums, nsums, 8, kind.sums_name());
+    g.h_sums.ensure(nsums);
+  };
   room(g.d_bins, (size_t)plan.bins_bytes, 1, "the bin planes (features x rows)");
   room(g.d_pos, n, 2, "the row positions");
   room(g.d_pred, n, 4, "the running margin");
   if (host_form) room(g.d_labels, n, 4, "the staged labels");
-  room(g.d_Ghist, (size_t)(hist_bytes / 16), 8, "the gradient histograms");
-  room(g.d_Hhist, (size_t)(hist_bytes / 16), 8, wt != nullptr ? "the hessian histograms" : "the count histograms");
+  room(g.d_Ghist, (size_t)(levels.hist_bytes / 16), 8, "the gradient histograms");
+  room(g.d_Hhist, (size_t)(levels.hist_bytes / 16), 8, kind.hess_name());
   room(g.d_best, (size_t)(1u << (max_depth - 1)) * F, sizeof(GrowCand), "the split candidates");
   room(g.d_nodes, R * kGrowMaxNodes, sizeof(GrowNode), "the node records");
   const uint64_t ne = e != nullptr ? e->nrow : 0;
-  const size_t nsums = (R + 1) * 4, nwsums = grow_wide_count(R);
   GrowPlan eplan;                    // the held-out rows' binning
-  if (wt != nullptr) {
-    if (host_form && wt->weights != nullptr) room(g.d_weights, n, 4, "the staged weights");
-    if (host_form && wt->eval_weights != nullptr) room(g.d_eval_weights, ne, 4, "the staged eval weights");
-    room(g.d_wsums, nwsums, 8, "the weighted metric sums");
-    g.h_wsums.ensure(nwsums);
+  if (weighted) {
+    if (host_form && wt.weights != nullptr) room(g.d_weights, n, 4, "the staged weights");
+    if (host_form && wt.eval_weights != nullptr) room(g.d_eval_weights, ne, 4, "the staged eval weights");
+    sums_room();
   }
   const size_t bag_words = (size_t)((n + 63) / 64);
   if (sampled) {
@@ -2370,20 +2460,17 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     g.h_features.ensure(R * n_sel);
     // every round's list before anything is enqueued
     for (size_t r = 0; r < R; ++r)
-      if (grow_pick_features(sp->seed, tree0 + r, F, sp->colsample_bytree, g.h_features.p + r * n_sel) != n_sel)
+      if (grow_pick_features(c.sampling.seed, tree0 + r, F, c.sampling.colsample_bytree, g.h_features.p + r * n_sel) != n_sel)
         throw OhxError(w0 + ": the selected features of round " + std::to_string(r + 1) + " are not " + std::to_string(n_sel));
   }
-  if (ev != nullptr) {
+  if (ev.present) {
     if (e != nullptr) {
       eplan = plan_grow(ne, F, ncuts, max_depth, dev.num_cus);
       room(g.d_eval_bins, (size_t)eplan.bins_bytes, 1, "the held-out bin planes (features x rows)");
       room(g.d_eval_pred, ne, 4, "the held-out margin");
       if (host_form) room(g.d_eval_labels, ne, 4, "the staged eval labels");
     }
-    if (wt == nullptr) {
-      room(g.d_sums, nsums, 8, "the metric sums");
-      g.h_sums.ensure(nsums);
-    }
+    if (!weighted) sums_room();
   }
   g.d_tree_nodes.ensure(R);
   g.d_cuts.ensure(std::max<size_t>(ncuts, 1));
@@ -2395,10 +2482,23 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   g.h_cuts.ensure(std::max<size_t>(ncuts, 1));
   g.h_cut_ptr.ensure(F + 1);
   g.h_state.ensure(1);
-  for (uint32_t f = 0; f <= F; ++f) g.h_cut_ptr.p[f] = (uint32_t)cut_ptr[f];
-  if (ncuts) memcpy(g.h_cuts.p, cut_values, ncuts * sizeof(float));
-  hipStream_t stream = host_form ? lib_streams(dev.ordinal).exec : caller;
+  for (uint32_t f = 0; f <= F; ++f) g.h_cut_ptr.p[f] = (uint32_t)c.cut_ptr[f];
+  if (ncuts) memcpy(g.h_cuts.p, c.cut_values, ncuts * sizeof(float));
+  hipStream_t stream = host_form ? lib_streams(dev.ordinal).exec : c.caller;
   if (host_form && (d.owned == nullptr || (e != nullptr && e->owned == nullptr))) order_behind_caller(dev.ordinal, stream);
+  // The margin of the forest so far over the rows of `m`, by the predict path.  Its kernels raise the booster's sticky
+  // inf flag for +-inf in a device matrix; bins take +-inf as the floats they are, so the flag word is put back as it was.
+  auto initial_margin = [&](DMatrixObj& m, float* pred, uint64_t rows) {
+    if (b.forest.trees.empty()) {
+      uint32_t base_bits = 0;
+      memcpy(&base_bits, &b.margin_base, sizeof base_bits);
+      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(pred), (int)base_bits, (size_t)rows, stream));
+    } else {
+      HIP_CHECK(hipMemcpyAsync(g.d_saved_flag.p, b.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+      launch_predict_checked(b, m, 1, 0, pred, stream);
+      HIP_CHECK(hipMemcpyAsync(b.d_flags.p, g.d_saved_flag.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
+    }
+  };
   // every earlier call has been waited for, so the buffers are free
   HIP_CHECK(hipMemcpyAsync(g.d_cut_ptr.p, g.h_cut_ptr.p, (F + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
   if (ncuts) HIP_CHECK(hipMemcpyAsync(g.d_cuts.p, g.h_cuts.p, ncuts * sizeof(float), hipMemcpyHostToDevice, stream));
@@ -2406,46 +2506,29 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   HIP_CHECK(hipMemsetAsync(g.d_tree_nodes.p, 0, R * sizeof(uint32_t), stream));
   HIP_CHECK(hipMemsetAsync(g.d_pos.p, 0, n * sizeof(uint16_t), stream));
   if (sampled) HIP_CHECK(hipMemcpyAsync(g.d_features.p, g.h_features.p, R * n_sel, hipMemcpyHostToDevice, stream));
-  if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_labels.p, labels, n * sizeof(float), hipMemcpyHostToDevice, stream));
-  // The margin of the forest so far, by the predict path.  Its kernels raise the booster's sticky inf flag for +-inf in
-  // a device matrix; bins take +-inf as the floats they are, so the flag word is put back as it was.
-  if (b.forest.trees.empty()) {
-    uint32_t base_bits = 0;
-    memcpy(&base_bits, &b.margin_base, sizeof base_bits);
-    HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g.d_pred.p), (int)base_bits, (size_t)n, stream));
-  } else {
-    HIP_CHECK(hipMemcpyAsync(g.d_saved_flag.p, b.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-    launch_predict_checked(b, d, 1, 0, g.d_pred.p, stream);
-    HIP_CHECK(hipMemcpyAsync(b.d_flags.p, g.d_saved_flag.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-  }
-  if (ev != nullptr && wt == nullptr) HIP_CHECK(hipMemsetAsync(g.d_sums.p, 0, nsums * sizeof(unsigned long long), stream));
-  if (wt != nullptr) {
-    HIP_CHECK(hipMemsetAsync(g.d_wsums.p, 0, nwsums * sizeof(unsigned long long), stream));
-    if (host_form && wt->weights != nullptr)
-      HIP_CHECK(hipMemcpyAsync(g.d_weights.p, wt->weights, n * sizeof(float), hipMemcpyHostToDevice, stream));
-    if (host_form && wt->eval_weights != nullptr)
-      HIP_CHECK(hipMemcpyAsync(g.d_eval_weights.p, wt->eval_weights, ne * sizeof(float), hipMemcpyHostToDevice, stream));
-  }
+  if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_labels.p, c.labels, n * sizeof(float), hipMemcpyHostToDevice, stream));
+  initial_margin(d, g.d_pred.p, n);
+  if (ev.present) HIP_CHECK(hipMemsetAsync(g.d_sums.p, 0, nsums * sizeof(unsigned long long), stream));
+  if (host_form && wt.weights != nullptr)
+    HIP_CHECK(hipMemcpyAsync(g.d_weights.p, wt.weights, n * sizeof(float), hipMemcpyHostToDevice, stream));
+  if (host_form && wt.eval_weights != nullptr)
+    HIP_CHECK(hipMemcpyAsync(g.d_eval_weights.p, wt.eval_weights, ne * sizeof(float), hipMemcpyHostToDevice, stream));
   if (e != nullptr) {
     // the held-out rows get what the training rows got: staged labels, and the margin of the forest so far
-    if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_eval_labels.p, ev->labels, ne * sizeof(float), hipMemcpyHostToDevice, stream));
-    if (b.forest.trees.empty()) {
-      uint32_t base_bits = 0;
-      memcpy(&base_bits, &b.margin_base, sizeof base_bits);
-      HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(g.d_eval_pred.p), (int)base_bits, (size_t)ne, stream));
-    } else {
-      HIP_CHECK(hipMemcpyAsync(g.d_saved_flag.p, b.d_flags.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-      launch_predict_checked(b, *e, 1, 0, g.d_eval_pred.p, stream);
-      HIP_CHECK(hipMemcpyAsync(b.d_flags.p, g.d_saved_flag.p, sizeof(uint32_t), hipMemcpyDeviceToDevice, stream));
-    }
+    if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_eval_labels.p, ev.labels, ne * sizeof(float), hipMemcpyHostToDevice, stream));
+    initial_margin(*e, g.d_eval_pred.p, ne);
   }
+  // a weight array as the kernels read it: the staged copy, the caller's device array, or nullptr (all 1.0f)
+  auto device_weights = [&](const float* given, DevBuf<float>& staged) {
+    return given == nullptr ? nullptr : host_form ? staged.p : given;
+  };
   GrowArgs a;
   a.rows = d.d_data;
   a.nrow = n;
   a.ncol = (uint32_t)d.ncol;
   a.num_feature = F;
   a.missing = d.missing;
-  a.labels = host_form ? g.d_labels.p : labels;
+  a.labels = host_form ? g.d_labels.p : c.labels;
   a.cut_ptr = g.d_cut_ptr.p;
   a.cuts = g.d_cuts.p;
   a.ncuts = (uint32_t)ncuts;
@@ -2459,41 +2542,35 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
   a.tree_nodes = g.d_tree_nodes.p;
   a.state = g.d_state.p;
   a.max_depth = max_depth;
-  a.eta = eta;
-  a.lambda = lambda;
-  a.gamma = gamma;
-  a.min_child_rows = wt != nullptr ? 1 : min_child_rows;
-  GrowWeightedArgs aw;                 // the level loop with weights
-  aw.g = a;
-  if (wt != nullptr) {
-    aw.weights = wt->weights == nullptr ? nullptr : host_form ? g.d_weights.p : wt->weights;
-    aw.min_child_weight = (double)wt->min_child_weight;
+  a.eta = c.eta;
+  a.lambda = c.lambda;
+  a.gamma = c.gamma;
+  a.min_child_rows = c.min_child_rows;
+  a.weights = device_weights(wt.weights, g.d_weights);
+  a.min_child_weight = (double)wt.min_child_weight;
+  if (sampled) {                       // a bag of the rows and a tree's features
+    a.bag = k_s != kGrowSampleOne ? g.d_bag.p : nullptr;
+    a.features = g.d_features.p;
+    a.n_sel = n_sel;
+    a.k_s = k_s;
   }
-  GrowSampledArgs as;                  // the level loop over a bag of the rows and a tree's features
-  if (sampled) {
-    as.w = aw;
-    as.bag = k_s != kGrowSampleOne ? g.d_bag.p : nullptr;
-    as.features = g.d_features.p;
-    as.n_sel = n_sel;
-    as.k_s = k_s;
-  }
-  // one tree, and one set's sums after t trees, by the kernels of the call at hand
+  // one tree by the kernels of the call's kind
   auto grow_tree = [&](uint32_t r) {
-    if (sampled) {
-      if (as.bag != nullptr) {
-        as.row_key = grow_row_key(sp->seed, tree0 + r);
-        const hipError_t drawn = (hipError_t)launch_grow_bag(as, plan, stream);
-        if (drawn != hipSuccess) return drawn;
-      }
-      return (hipError_t)launch_grow_tree_sampled(as, plan, splan, r, stream);
+    if (a.bag != nullptr) {
+      a.row_key = grow_row_key(c.sampling.seed, tree0 + r);
+      const hipError_t drawn = (hipError_t)launch_grow_bag(a, plan, stream);
+      if (drawn != hipSuccess) return drawn;
     }
-    return (hipError_t)(wt != nullptr ? launch_grow_tree_weighted(aw, plan, r, stream) : launch_grow_tree(a, plan, r, stream));
+    return kind.tree(a, plan, levels, r, stream);
   };
   hipError_t launched = (hipError_t)launch_grow_bin(a, plan, stream);
   hipError_t waited = hipSuccess;
-  uint32_t run = (uint32_t)rounds, best = 0;   // rounds grown, and the best of them by the held-out sums
-  if (ev == nullptr) {
-    for (uint32_t r = 0; launched == hipSuccess && r < (uint32_t)rounds; ++r) launched = grow_tree(r);
+  uint32_t run = (uint32_t)c.rounds, best = 0;   // rounds grown, and the best of them by the held-out sums
+  // the held-out sum after t trees as the exact integer, from the host copy of the sums
+  auto held = [&](uint32_t t) { return grow_sum_value(g.h_sums.p + kind.index(t, kGrowEvalHeldOut), kind.words()); };
+  std::vector<unsigned __int128> S(ev.present ? R + 1 : 0);   // the held-out sums, as far as they are known
+  if (!ev.present) {
+    for (uint32_t r = 0; launched == hipSuccess && r < (uint32_t)c.rounds; ++r) launched = grow_tree(r);
   } else {
     // the metric: the training rows' sums after every leaf kernel, the held-out rows' walk of every new tree, and both
     // sets' sums of the forest as loaded
@@ -2504,12 +2581,13 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     mt.num_feature = F;
     mt.nodes = g.d_nodes.p;
     mt.tree_nodes = g.d_tree_nodes.p;
-    mt.sums = g.d_sums.p;
+    mt.sums = mt.wsums = g.d_sums.p;   // (a kind's kernels read the one of its layout)
     mt.state = g.d_state.p;
     mt.max_depth = max_depth;
     mt.label_flag = kGrowFlagLabel;
+    mt.weights = a.weights;
+    mt.weight_flag = kGrowFlagWeight;
     GrowEvalArgs me = mt;
-    GrowWeightedEvalArgs wmt, wme;   // the same with weights: the wide sums
     const uint32_t tblocks = plan_grow_eval_blocks(n, dev.num_cus);
     uint32_t eblocks = 0;
     if (e != nullptr) {
@@ -2525,49 +2603,27 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
       if (launched == hipSuccess) launched = (hipError_t)launch_grow_bin(ab, eplan, stream);
       me.bins = g.d_eval_bins.p;
       me.pred = g.d_eval_pred.p;
-      me.labels = host_form ? g.d_eval_labels.p : ev->labels;
+      me.labels = host_form ? g.d_eval_labels.p : ev.labels;
       me.nrow = ne;
       me.label_flag = kGrowFlagEvalLabel;
+      me.weights = device_weights(wt.eval_weights, g.d_eval_weights);
+      me.weight_flag = kGrowFlagEvalWeight;
       eblocks = plan_grow_eval_blocks(ne, dev.num_cus);
     }
-    if (wt != nullptr) {
-      wmt.e = mt;
-      wmt.weights = aw.weights;
-      wmt.wsums = g.d_wsums.p;
-      wmt.weight_flag = kGrowFlagWeight;
-      wme.e = me;
-      wme.weights = wt->eval_weights == nullptr ? nullptr : host_form ? g.d_eval_weights.p : wt->eval_weights;
-      wme.wsums = g.d_wsums.p;
-      wme.weight_flag = kGrowFlagEvalWeight;
-    }
-    auto sum_train = [&](uint32_t t) {
-      return (hipError_t)(wt != nullptr ? launch_grow_sse_weighted(wmt, tblocks, t, kGrowEvalTrain, stream)
-                                        : launch_grow_sse(mt, tblocks, t, kGrowEvalTrain, stream));
-    };
-    // where the held-out sums of round t lie, and how many words they are
-    const unsigned long long* d_all = wt != nullptr ? g.d_wsums.p : g.d_sums.p;
-    unsigned long long* h_all = wt != nullptr ? g.h_wsums.p : g.h_sums.p;
-    const size_t nall = wt != nullptr ? nwsums : nsums, words = wt != nullptr ? 3 : 2;
-    auto held_at = [&](uint32_t t) { return wt != nullptr ? grow_wide_index(t, kGrowEvalHeldOut) : grow_sum_index(t, kGrowEvalHeldOut); };
-    if (launched == hipSuccess && e != nullptr)
-      launched = (hipError_t)(wt != nullptr ? launch_grow_sse_weighted(wme, eblocks, 0, kGrowEvalHeldOut, stream)
-                                            : launch_grow_sse(me, eblocks, 0, kGrowEvalHeldOut, stream));
+    auto sum_train = [&](uint32_t t) { return kind.sse(mt, tblocks, t, kGrowEvalTrain, stream); };
+    if (launched == hipSuccess && e != nullptr) launched = kind.sse(me, eblocks, 0, kGrowEvalHeldOut, stream);
     if (launched == hipSuccess) launched = sum_train(0);
-    std::vector<GrowSum> S(R + 1);   // the held-out sums, as far as they are known (patience >= 1)
-    std::vector<GrowWideSum> WS(wt != nullptr ? R + 1 : 0);
-    const bool stepwise = ev->patience >= 1;
-    for (uint32_t r = 0; launched == hipSuccess && waited == hipSuccess && r < (uint32_t)rounds; ++r) {
+    const bool stepwise = ev.patience >= 1;
+    for (uint32_t r = 0; launched == hipSuccess && waited == hipSuccess && r < (uint32_t)c.rounds; ++r) {
       launched = grow_tree(r);
       if (launched == hipSuccess) launched = sum_train(r + 1);
-      if (launched == hipSuccess && e != nullptr)
-        launched = (hipError_t)(wt != nullptr ? launch_grow_walk_sse_weighted(wme, eblocks, r, kGrowEvalHeldOut, stream)
-                                              : launch_grow_walk_sse(me, eblocks, r, kGrowEvalHeldOut, stream));
+      if (launched == hipSuccess && e != nullptr) launched = kind.walk_sse(me, eblocks, r, kGrowEvalHeldOut, stream);
       if (!stepwise || launched != hipSuccess) continue;
       // one small wait a round: this round's held-out sums (and round 0's, the first time) and the error word
       const uint32_t t0 = r == 0 ? 0 : r + 1;
       for (uint32_t t = t0; launched == hipSuccess && t <= r + 1; ++t) {
-        const size_t at = held_at(t);
-        launched = hipMemcpyAsync(h_all + at, d_all + at, words * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
+        const size_t at = kind.index(t, kGrowEvalHeldOut);
+        launched = hipMemcpyAsync(g.h_sums.p + at, g.d_sums.p + at, kind.words() * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
       }
       if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_state.p, g.d_state.p, sizeof(GrowLevelState), hipMemcpyDeviceToHost, stream);
       if (launched != hipSuccess) break;
@@ -2577,25 +2633,15 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
         run = r + 1;
         break;
       }
-      for (uint32_t t = t0; t <= r + 1; ++t) {
-        const size_t at = held_at(t);
-        if (wt != nullptr) {
-          WS[t].p2 = h_all[at];
-          WS[t].p1 = h_all[at + 1];
-          WS[t].p0 = h_all[at + 2];
-        } else {
-          S[t].hi = h_all[at];
-          S[t].lo = h_all[at + 1];
-        }
-      }
-      best = wt != nullptr ? grow_eval_best(WS.data(), best, r + 1) : grow_eval_best(S.data(), best, r + 1);
-      if (grow_eval_stops(best, r + 1, ev->patience)) {
+      for (uint32_t t = t0; t <= r + 1; ++t) S[t] = held(t);
+      best = grow_eval_best(S.data(), best, r + 1);
+      if (grow_eval_stops(best, r + 1, ev.patience)) {
         run = r + 1;
         break;
       }
     }
     if (launched == hipSuccess && waited == hipSuccess)
-      launched = hipMemcpyAsync(h_all, d_all, nall * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
+      launched = hipMemcpyAsync(g.h_sums.p, g.d_sums.p, nsums * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
   }
   if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_nodes.p, g.d_nodes.p, R * kGrowMaxNodes * sizeof(GrowNode), hipMemcpyDeviceToHost, stream);
   if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_tree_nodes.p, g.d_tree_nodes.p, R * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
@@ -2624,37 +2670,22 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     throw OhxError(w0 + ": the bag of some round holds no weight (every row drawn by subsample has rint(w * 2^24) == 0, or none "
                    "was drawn): raise subsample or change the seed; the forest is unchanged");
   if (flags != 0) throw OhxError(w0 + ": the grow kernels reported error flags " + std::to_string(flags));
-  if (wt != nullptr) {
-    if (g.h_wsums.p[kGrowEvalTrain] == 0ull)
+  if (weighted) {                      // W of both sets leads the wide sums
+    if (g.h_sums.p[kGrowEvalTrain] == 0ull)
       throw OhxError(w0 + ": the weights of the training rows sum to 0 (every rint(w * 2^24) is 0); the forest is unchanged");
-    if (e != nullptr && g.h_wsums.p[kGrowEvalHeldOut] == 0ull)
+    if (e != nullptr && g.h_sums.p[kGrowEvalHeldOut] == 0ull)
       throw OhxError(w0 + ": the eval weights of the held-out rows sum to 0 (every rint(w * 2^24) is 0); the forest is unchanged");
   }
   // all or nothing: every round is done and the error word is clean
   size_t keep = R;                     // the trees that are appended
-  if (ev != nullptr) {
+  if (ev.present) {
     if (e != nullptr) {
       // the shared rule over the whole list, from the exact integers: what the round-by-round loop decided
       uint32_t run_again = 0;
-      if (wt != nullptr) {
-        std::vector<GrowWideSum> S(run + 1);
-        for (uint32_t t = 0; t <= run; ++t) {
-          const unsigned long long* s = g.h_wsums.p + grow_wide_index(t, kGrowEvalHeldOut);
-          S[t].p2 = s[0];
-          S[t].p1 = s[1];
-          S[t].p0 = s[2];
-        }
-        grow_eval_stop(S.data(), run, ev->patience, &run_again, &best);
-      } else {
-        std::vector<GrowSum> S(run + 1);
-        for (uint32_t t = 0; t <= run; ++t) {
-          S[t].hi = g.h_sums.p[grow_sum_index(t, kGrowEvalHeldOut)];
-          S[t].lo = g.h_sums.p[grow_sum_index(t, kGrowEvalHeldOut) + 1];
-        }
-        grow_eval_stop(S.data(), run, ev->patience, &run_again, &best);
-      }
+      for (uint32_t t = 0; t <= run; ++t) S[t] = held(t);
+      grow_eval_stop(S.data(), run, ev.patience, &run_again, &best);
       if (run_again != run) throw OhxError(w0 + ": the stop rule gave " + std::to_string(run_again) + " rounds over the sums of " + std::to_string(run));
-      if (ev->patience >= 1) keep = best;
+      if (ev.patience >= 1) keep = best;
     } else {
       best = run;
     }
@@ -2684,32 +2715,29 @@ void boost_trees(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ulo
     b.contribs.reset();
     drop_leaf_walk(b);
   }
-  if (nodes_added != nullptr) *nodes_added = added;
-  if (ev != nullptr) {
-    for (uint32_t t = 0; wt != nullptr && t <= run; ++t) {
-      const unsigned long long* s = g.h_wsums.p + grow_wide_index(t, kGrowEvalTrain);
-      GrowWideSum tr, he;
-      tr.p2 = s[0];
-      tr.p1 = s[1];
-      tr.p0 = s[2];
-      he.p2 = s[3];
-      he.p1 = s[4];
-      he.p0 = s[5];
-      if (ev->train_rmse != nullptr) ev->train_rmse[t] = grow_wide_rmse(tr, g.h_wsums.p[kGrowEvalTrain]);
-      if (ev->eval_rmse != nullptr && e != nullptr) ev->eval_rmse[t] = grow_wide_rmse(he, g.h_wsums.p[kGrowEvalHeldOut]);
+  if (c.nodes_added != nullptr) *c.nodes_added = added;
+  if (ev.present) {
+    // the RMSE of sum (t, set): the wide sum over the set's W, or the plain sum over the set's rows
+    auto rmse = [&](uint32_t t, uint32_t set) {
+      const unsigned long long* s = g.h_sums.p + kind.index(t, set);
+      if (weighted) {
+        GrowWideSum x;
+        x.p2 = s[0];
+        x.p1 = s[1];
+        x.p0 = s[2];
+        return grow_wide_rmse(x, g.h_sums.p[set]);
+      }
+      GrowSum x;
+      x.hi = s[0];
+      x.lo = s[1];
+      return grow_sum_rmse(x, set == kGrowEvalTrain ? n : ne);
+    };
+    for (uint32_t t = 0; t <= run; ++t) {
+      if (ev.train_rmse != nullptr) ev.train_rmse[t] = rmse(t, kGrowEvalTrain);
+      if (ev.eval_rmse != nullptr && e != nullptr) ev.eval_rmse[t] = rmse(t, kGrowEvalHeldOut);
     }
-    for (uint32_t t = 0; wt == nullptr && t <= run; ++t) {
-      const unsigned long long* s = g.h_sums.p + grow_sum_index(t, kGrowEvalTrain);
-      GrowSum tr, he;
-      tr.hi = s[0];
-      tr.lo = s[1];
-      he.hi = s[2];
-      he.lo = s[3];
-      if (ev->train_rmse != nullptr) ev->train_rmse[t] = grow_sum_rmse(tr, n);
-      if (ev->eval_rmse != nullptr && e != nullptr) ev->eval_rmse[t] = grow_sum_rmse(he, ne);
-    }
-    *ev->rounds_run = (int)run;
-    *ev->best_round = (int)best;
+    *ev.rounds_run = (int)run;
+    *ev.best_round = (int)best;
   }
 }
 
@@ -3379,9 +3407,10 @@ int OHXBoosterBoostTrees(BoosterHandle handle, DMatrixHandle dmat, const float* 
                          const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
                          float lambda, float gamma, bst_ulong min_child_rows, bst_ulong* nodes_added) {
   API_BEGIN();
-  BoosterObj* b = as_booster(handle);
-  boost_trees(*b, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows,
-              nodes_added, true, nullptr, "OHXBoosterBoostTrees");
+  BoostCall c = boost_call("OHXBoosterBoostTrees", true, nullptr, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth,
+                           eta, lambda, gamma, nodes_added);
+  c.min_child_rows = min_child_rows;
+  boost_trees(*as_booster(handle), c);
   API_END();
 }
 
@@ -3389,9 +3418,10 @@ int OHXBoosterBoostTreesDevice(BoosterHandle handle, DMatrixHandle dmat, const f
                                const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth, float eta,
                                float lambda, float gamma, bst_ulong min_child_rows, bst_ulong* nodes_added, void* stream) {
   API_BEGIN();
-  BoosterObj* b = as_booster(handle);
-  boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows,
-              nodes_added, false, static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesDevice");
+  BoostCall c = boost_call("OHXBoosterBoostTreesDevice", false, stream, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds,
+                           max_depth, eta, lambda, gamma, nodes_added);
+  c.min_child_rows = min_child_rows;
+  boost_trees(*as_booster(handle), c);
   API_END();
 }
 
@@ -3401,18 +3431,11 @@ int OHXBoosterBoostTreesEval(BoosterHandle handle, DMatrixHandle dmat, const flo
                              float lambda, float gamma, bst_ulong min_child_rows, int patience, double* train_rmse,
                              double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added) {
   API_BEGIN();
-  BoosterObj* b = as_booster(handle);
-  BoostEval ev;
-  ev.dmat = eval_dmat;
-  ev.labels = eval_labels;
-  ev.nlabel = eval_nlabel;
-  ev.patience = patience;
-  ev.train_rmse = train_rmse;
-  ev.eval_rmse = eval_rmse;
-  ev.rounds_run = rounds_run;
-  ev.best_round = best_round;
-  boost_trees(*b, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows,
-              nodes_added, true, nullptr, "OHXBoosterBoostTreesEval", &ev);
+  BoostCall c = boost_call("OHXBoosterBoostTreesEval", true, nullptr, dmat, labels, nlabel, cut_ptr, cut_values, rounds,
+                           max_depth, eta, lambda, gamma, nodes_added);
+  c.min_child_rows = min_child_rows;
+  c.eval = boost_eval(eval_dmat, eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
+  boost_trees(*as_booster(handle), c);
   API_END();
 }
 
@@ -3423,18 +3446,11 @@ int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, con
                                    double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added,
                                    void* stream) {
   API_BEGIN();
-  BoosterObj* b = as_booster(handle);
-  BoostEval ev;
-  ev.dmat = eval_dmat;
-  ev.labels = d_eval_labels;
-  ev.nlabel = eval_nlabel;
-  ev.patience = patience;
-  ev.train_rmse = train_rmse;
-  ev.eval_rmse = eval_rmse;
-  ev.rounds_run = rounds_run;
-  ev.best_round = best_round;
-  boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_rows,
-              nodes_added, false, static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesEvalDevice", &ev);
+  BoostCall c = boost_call("OHXBoosterBoostTreesEvalDevice", false, stream, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds,
+                           max_depth, eta, lambda, gamma, nodes_added);
+  c.min_child_rows = min_child_rows;
+  c.eval = boost_eval(eval_dmat, d_eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
+  boost_trees(*as_booster(handle), c);
   API_END();
 }
 
@@ -3445,22 +3461,11 @@ int OHXBoosterBoostTreesWeighted(BoosterHandle handle, DMatrixHandle dmat, const
                                  float min_child_weight, int patience, double* train_rmse, double* eval_rmse,
                                  int* rounds_run, int* best_round, bst_ulong* nodes_added) {
   API_BEGIN();
-  BoosterObj* b = as_booster(handle);
-  BoostEval ev;
-  ev.dmat = eval_dmat;
-  ev.labels = eval_labels;
-  ev.nlabel = eval_nlabel;
-  ev.patience = patience;
-  ev.train_rmse = train_rmse;
-  ev.eval_rmse = eval_rmse;
-  ev.rounds_run = rounds_run;
-  ev.best_round = best_round;
-  BoostWeights wt;
-  wt.weights = weights;
-  wt.eval_weights = eval_weights;
-  wt.min_child_weight = min_child_weight;
-  boost_trees(*b, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, 1, nodes_added, true,
-              nullptr, "OHXBoosterBoostTreesWeighted", &ev, &wt);
+  BoostCall c = boost_call("OHXBoosterBoostTreesWeighted", true, nullptr, dmat, labels, nlabel, cut_ptr, cut_values, rounds,
+                           max_depth, eta, lambda, gamma, nodes_added);
+  c.eval = boost_eval(eval_dmat, eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
+  c.weights = boost_weights(weights, eval_weights, min_child_weight);
+  boost_trees(*as_booster(handle), c);
   API_END();
 }
 
@@ -3472,22 +3477,11 @@ int OHXBoosterBoostTreesWeightedDevice(BoosterHandle handle, DMatrixHandle dmat,
                                        double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
                                        bst_ulong* nodes_added, void* stream) {
   API_BEGIN();
-  BoosterObj* b = as_booster(handle);
-  BoostEval ev;
-  ev.dmat = eval_dmat;
-  ev.labels = d_eval_labels;
-  ev.nlabel = eval_nlabel;
-  ev.patience = patience;
-  ev.train_rmse = train_rmse;
-  ev.eval_rmse = eval_rmse;
-  ev.rounds_run = rounds_run;
-  ev.best_round = best_round;
-  BoostWeights wt;
-  wt.weights = d_weights;
-  wt.eval_weights = d_eval_weights;
-  wt.min_child_weight = min_child_weight;
-  boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, 1, nodes_added, false,
-              static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesWeightedDevice", &ev, &wt);
+  BoostCall c = boost_call("OHXBoosterBoostTreesWeightedDevice", false, stream, dmat, d_labels, nlabel, cut_ptr, cut_values,
+                           rounds, max_depth, eta, lambda, gamma, nodes_added);
+  c.eval = boost_eval(eval_dmat, d_eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
+  c.weights = boost_weights(d_weights, d_eval_weights, min_child_weight);
+  boost_trees(*as_booster(handle), c);
   API_END();
 }
 
@@ -3499,26 +3493,12 @@ int OHXBoosterBoostTreesSampled(BoosterHandle handle, DMatrixHandle dmat, const 
                                 double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
                                 bst_ulong* nodes_added) {
   API_BEGIN();
-  BoosterObj* b = as_booster(handle);
-  BoostEval ev;
-  ev.dmat = eval_dmat;
-  ev.labels = eval_labels;
-  ev.nlabel = eval_nlabel;
-  ev.patience = patience;
-  ev.train_rmse = train_rmse;
-  ev.eval_rmse = eval_rmse;
-  ev.rounds_run = rounds_run;
-  ev.best_round = best_round;
-  BoostWeights wt;
-  wt.weights = weights;
-  wt.eval_weights = eval_weights;
-  wt.min_child_weight = min_child_weight;
-  BoostSampling sp;
-  sp.subsample = subsample;
-  sp.colsample_bytree = colsample_bytree;
-  sp.seed = seed;
-  boost_trees(*b, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, 1, nodes_added, true,
-              nullptr, "OHXBoosterBoostTreesSampled", &ev, &wt, &sp);
+  BoostCall c = boost_call("OHXBoosterBoostTreesSampled", true, nullptr, dmat, labels, nlabel, cut_ptr, cut_values, rounds,
+                           max_depth, eta, lambda, gamma, nodes_added);
+  c.eval = boost_eval(eval_dmat, eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
+  c.weights = boost_weights(weights, eval_weights, min_child_weight);
+  c.sampling = {true, subsample, colsample_bytree, seed};
+  boost_trees(*as_booster(handle), c);
   API_END();
 }
 
@@ -3531,26 +3511,12 @@ int OHXBoosterBoostTreesSampledDevice(BoosterHandle handle, DMatrixHandle dmat, 
                                       double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added,
                                       void* stream) {
   API_BEGIN();
-  BoosterObj* b = as_booster(handle);
-  BoostEval ev;
-  ev.dmat = eval_dmat;
-  ev.labels = d_eval_labels;
-  ev.nlabel = eval_nlabel;
-  ev.patience = patience;
-  ev.train_rmse = train_rmse;
-  ev.eval_rmse = eval_rmse;
-  ev.rounds_run = rounds_run;
-  ev.best_round = best_round;
-  BoostWeights wt;
-  wt.weights = d_weights;
-  wt.eval_weights = d_eval_weights;
-  wt.min_child_weight = min_child_weight;
-  BoostSampling sp;
-  sp.subsample = subsample;
-  sp.colsample_bytree = colsample_bytree;
-  sp.seed = seed;
-  boost_trees(*b, dmat, d_labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, 1, nodes_added, false,
-              static_cast<hipStream_t>(stream), "OHXBoosterBoostTreesSampledDevice", &ev, &wt, &sp);
+  BoostCall c = boost_call("OHXBoosterBoostTreesSampledDevice", false, stream, dmat, d_labels, nlabel, cut_ptr, cut_values,
+                           rounds, max_depth, eta, lambda, gamma, nodes_added);
+  c.eval = boost_eval(eval_dmat, d_eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
+  c.weights = boost_weights(d_weights, d_eval_weights, min_child_weight);
+  c.sampling = {true, subsample, colsample_bytree, seed};
+  boost_trees(*as_booster(handle), c);
   API_END();
 }
 

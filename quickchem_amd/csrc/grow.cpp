@@ -1,6 +1,6 @@
-// Host side of the tree grower (grow.hpp): the quantile cuts, the cut checks, the split choice of one node over its
-// features, the assembly of a Tree from the device's node records and the launch plan.  No device code: libohx_synth.so
-// links it too, for the tests that need no GPU.
+// Host side of the tree grower (grow.hpp): the quantile cuts, the cut checks, the features of a tree, the assembly of a
+// Tree from the device's node records and the launch plan.  No device code: libohx_synth.so links it too, for the
+// tests that need no GPU.
 #include "grow.hpp"
 
 #include <algorithm>
@@ -62,35 +62,6 @@ void grow_check_cuts(const uint64_t* cut_ptr, const float* cut_values, uint32_t 
         throw OhxError(std::string(what) + ": the cuts of feature " + std::to_string(f) + " are not strictly ascending");
     }
   }
-}
-
-GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr, int64_t Gp,
-                         uint64_t Hp, float lambda, uint64_t min_child_rows) {
-  GrowCand best;
-  for (uint32_t f = 0; f < num_feature; ++f) {
-    const int64_t* g = G + (size_t)f * kGrowBins;
-    const uint64_t* h = H + (size_t)f * kGrowBins;
-    const uint32_t ncut = (uint32_t)(cut_ptr[f + 1] - cut_ptr[f]);
-    const GrowCand c = grow_best_split(g, h, f, 0, ncut, ncut, 0, 0, g[kGrowMissingBin], h[kGrowMissingBin], Gp, Hp,
-                                       (double)lambda, min_child_rows);
-    if (grow_better(c, best)) best = c;
-  }
-  return best;
-}
-
-GrowCand grow_node_split_weighted(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr,
-                                  int64_t Gp, uint64_t Hp, float lambda, float min_child_weight) {
-  GrowCand best;
-  if (!grow_weight_splits(Hp, (double)min_child_weight)) return best;
-  for (uint32_t f = 0; f < num_feature; ++f) {
-    const int64_t* g = G + (size_t)f * kGrowBins;
-    const uint64_t* h = H + (size_t)f * kGrowBins;
-    const uint32_t ncut = (uint32_t)(cut_ptr[f + 1] - cut_ptr[f]);
-    const GrowCand c = grow_best_split_weighted(g, h, f, 0, ncut, ncut, 0, 0, g[kGrowMissingBin], h[kGrowMissingBin], Gp,
-                                                Hp, (double)lambda, (double)min_child_weight);
-    if (grow_better(c, best)) best = c;
-  }
-  return best;
 }
 
 uint32_t grow_pick_features(uint64_t seed, uint64_t i, uint32_t F, float colsample, uint8_t* out) {

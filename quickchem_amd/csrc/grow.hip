@@ -18,6 +18,7 @@
 #include <cstdint>
 
 #include "grow.hpp"
+#include "grow_device.hpp"
 #include "walk_device.hpp"
 
 namespace ohx {
@@ -26,19 +27,6 @@ namespace {
 
 constexpr int kBlock = (int)kGrowBlock;
 constexpr int kHistBlock = (int)kGrowHistBlock;
-
-// the open nodes of level `level`: the root alone at level 0, whatever the state word still holds from the last tree
-__device__ inline void level_range(const GrowArgs& a, uint32_t level, uint32_t* begin, uint32_t* end, uint32_t* next) {
-  if (level == 0) {
-    *begin = 0;
-    *end = 1;
-    *next = 1;
-  } else {
-    *begin = a.state->begin;
-    *end = a.state->end;
-    *next = a.state->next;
-  }
-}
 
 // grid (blocks); dynamic LDS: the cuts
 __global__ __launch_bounds__(kBlock) void grow_bin_kernel(GrowArgs a) {
@@ -75,7 +63,7 @@ __global__ __launch_bounds__(kHistBlock) void grow_hist_kernel(GrowArgs a, uint3
                                                                uint32_t feat_group, uint32_t feat_groups) {
   extern __shared__ unsigned long long grow_hist[];
   uint32_t begin, end, next;
-  level_range(a, level, &begin, &end, &next);
+  grow_level_range(a, level, &begin, &end, &next);
   const uint32_t count = end - begin;
   const uint32_t slot0 = (blockIdx.y / feat_groups) * node_group;
   const uint32_t f0 = (blockIdx.y % feat_groups) * feat_group;
@@ -123,134 +111,15 @@ __global__ __launch_bounds__(kHistBlock) void grow_hist_kernel(GrowArgs a, uint3
   }
 }
 
-__device__ inline GrowCand shuffle_cand(const GrowCand& c, int d) {
-  GrowCand o;
-  o.loss_chg = __shfl_xor(c.loss_chg, d, kWave);
-  o.GL = __shfl_xor((long long)c.GL, d, kWave);
-  o.HL = __shfl_xor((unsigned long long)c.HL, d, kWave);
-  o.key = __shfl_xor(c.key, d, kWave);
-  o.valid = __shfl_xor(c.valid, d, kWave);
-  return o;
-}
-
-__device__ inline void write_leaf(const GrowArgs& a, GrowNode* nodes, uint32_t n, int64_t G, uint64_t H, int32_t parent) {
-  float leaf, weight;
-  refit_solve_leaf(G, H, a.eta, a.lambda, &leaf, &weight);
-  GrowNode r;
-  r.G = G;
-  r.H = H;
-  r.left = r.right = -1;
-  r.parent = parent;
-  r.feature = r.cut = r.default_left = 0;
-  r.value = leaf;
-  r.loss_chg = 0.0f;
-  r.sum_hess = (float)H;
-  r.base_weight = weight;
-  nodes[n] = r;
-}
-
-// PHASE 0: grid (blocks of four waves over slots x features).  PHASE 1: one block.
+// PHASE 0: grid (blocks of four waves over slots x features).  PHASE 1: one block.  The bodies are grow_device.hpp's,
+// here with a row count for a hessian sum and a histogram column for every feature.
 template <int PHASE>
 __global__ __launch_bounds__(kBlock) void grow_split_kernel(GrowArgs a, uint32_t level, uint32_t round) {
-  uint32_t begin, end, next;
-  level_range(a, level, &begin, &end, &next);
-  const uint32_t count = end - begin;
-  const uint32_t F = a.num_feature;
-  GrowNode* nodes = a.nodes + (uint64_t)round * kGrowMaxNodes;
+  const GrowCountHess hess{a.min_child_rows};
   if (PHASE == 0) {
-    const int lane = threadIdx.x & (kWave - 1);
-    const uint32_t w = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave;
-    const uint32_t slot = w / F, f = w % F;
-    if (slot >= count) return;
-    const uint64_t at = ((uint64_t)slot * F + f) * kGrowBins + 4u * lane;
-    int64_t g4[4];
-    uint64_t h4[4];
-    int64_t gs = 0;
-    uint64_t hs = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-      g4[k] = (int64_t)a.Ghist[at + k];
-      h4[k] = (uint64_t)a.Hhist[at + k];
-      gs += g4[k];
-      hs += h4[k];
-    }
-    // inclusive sums across the wave, then the sums below the lane's first bin
-    long long gi = gs;
-    unsigned long long hi = hs;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const long long gt = __shfl_up(gi, d, kWave);
-      const unsigned long long ht = __shfl_up(hi, d, kWave);
-      if (lane >= d) {
-        gi += gt;
-        hi += ht;
-      }
-    }
-    const int64_t Gp = __shfl(gi, kWave - 1, kWave);
-    const uint64_t Hp = __shfl(hi, kWave - 1, kWave);
-    const int64_t Gm = __shfl((long long)g4[3], kWave - 1, kWave);
-    const uint64_t Hm = __shfl((unsigned long long)h4[3], kWave - 1, kWave);
-    if (level == 0 && f == 0 && lane == 0) {   // the root's sums: every row is in one bin of feature 0
-      nodes[0].G = Gp;
-      nodes[0].H = Hp;
-    }
-    const uint32_t ncut = a.cut_ptr[f + 1] - a.cut_ptr[f];
-    GrowCand c = grow_best_split(g4, h4, f, 4u * lane, 4u, ncut, gi - gs, hi - hs, Gm, Hm, Gp, Hp, (double)a.lambda,
-                                 a.min_child_rows);
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-      const GrowCand o = shuffle_cand(c, d);
-      if (grow_better(o, c)) c = o;
-    }
-    if (lane == 0) a.best[(uint64_t)slot * F + f] = c;
+    grow_split_columns(a, hess, level, round, a.num_feature, GrowIdentityMap());
   } else {
-    __shared__ uint32_t splits[kGrowMaxNodes / 2];
-    const uint32_t s = threadIdx.x;
-    const bool active = s < count && s < kGrowMaxNodes / 2;
-    const uint32_t node = begin + s;
-    GrowCand best;
-    int64_t Gp = 0;
-    uint64_t Hp = 0;
-    if (active) {
-      Gp = nodes[node].G;
-      Hp = nodes[node].H;
-      if (level == 0) write_leaf(a, nodes, 0, Gp, Hp, -1);
-      for (uint32_t f = 0; f < F; ++f) {
-        const GrowCand c = a.best[(uint64_t)s * F + f];
-        if (grow_better(c, best)) best = c;
-      }
-    }
-    const bool split = active && best.valid && best.loss_chg > (double)a.gamma;
-    if (s < kGrowMaxNodes / 2) splits[s] = split ? 1u : 0u;
-    __syncthreads();
-    uint32_t below = 0, total = 0;
-    const uint32_t live = count < kGrowMaxNodes / 2 ? count : kGrowMaxNodes / 2;
-    for (uint32_t i = 0; i < live; ++i) {
-      total += splits[i];
-      if (i < s) below += splits[i];
-    }
-    if (next + 2u * total > kGrowMaxNodes) {   // (never: a tree of depth 8 has 511 nodes)
-      if (s == 0) atomicOr(&a.state->error, kGrowFlagState);
-      total = 0;
-    } else if (split) {
-      const uint32_t f = best.key >> 9, j = (best.key >> 1) & 255u, dl = best.key & 1u;
-      const uint32_t left = next + 2u * below;
-      nodes[node].left = (int32_t)left;
-      nodes[node].right = (int32_t)left + 1;
-      nodes[node].feature = f;
-      nodes[node].cut = j;
-      nodes[node].default_left = dl;
-      nodes[node].value = a.cuts[a.cut_ptr[f] + j];
-      nodes[node].loss_chg = (float)best.loss_chg;
-      write_leaf(a, nodes, left, best.GL, best.HL, (int32_t)(node | 0x80000000u));
-      write_leaf(a, nodes, left + 1, Gp - best.GL, Hp - best.HL, (int32_t)node);
-    }
-    if (s == 0) {
-      a.state->begin = next;
-      a.state->end = next + 2u * total;
-      a.state->next = next + 2u * total;
-      a.tree_nodes[round] = next + 2u * total;
-    }
+    grow_split_nodes<false>(a, hess, level, round, a.num_feature);
   }
 }
 
@@ -293,7 +162,7 @@ __global__ __launch_bounds__(kBlock) void grow_leaf_kernel(GrowArgs a, uint32_t 
 
 }  // namespace
 
-int prepare_grow() {
+int grow_lds_limits() {
   hipError_t e = raise_lds_limit(grow_bin_kernel, kGrowMaxFeatures * kGrowMaxCuts * sizeof(float));
   if (e != hipSuccess) return e;
   return raise_lds_limit(grow_hist_kernel, kGrowMaxPairs * kGrowPairBytes);
@@ -309,36 +178,18 @@ int launch_grow_bin(const GrowArgs& a, const GrowPlan& plan, void* stream_) {
   return hipGetLastError();
 }
 
-int launch_grow_tree(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream_) {
+int launch_grow_tree(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (a.nrow == 0 || a.nrow > kRefitMaxRows || a.num_feature == 0 || a.num_feature > kGrowMaxFeatures || a.max_depth < 1 ||
-      a.max_depth > kGrowMaxDepth || plan.levels.size() != (size_t)a.max_depth || plan.row_blocks == 0 || a.min_child_rows < 1)
-    return hipErrorInvalidValue;
-  const uint32_t F = a.num_feature;
-  hipError_t e = hipSuccess;
-  for (uint32_t d = 0; d < (uint32_t)a.max_depth; ++d) {
-    const GrowLevelPlan& l = plan.levels[d];
-    if (l.slots != (1u << d) || l.node_group * l.feat_group > kGrowMaxPairs || l.node_group == 0 || l.feat_group == 0 ||
-        l.lds_bytes != l.node_group * l.feat_group * kGrowPairBytes || l.node_groups * l.node_group < l.slots ||
-        l.feat_groups * l.feat_group < F || l.hist_blocks == 0 ||
-        (a.nrow + (uint64_t)l.hist_blocks * kGrowHistBlock - 1) / ((uint64_t)l.hist_blocks * kGrowHistBlock) > kGrowMaxTrips)
-      return hipErrorInvalidValue;
-    const size_t bytes = (size_t)l.slots * F * kGrowBins * sizeof(unsigned long long);
-    if ((e = hipMemsetAsync(a.Ghist, 0, bytes, stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(a.Hhist, 0, bytes, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(grow_hist_kernel, dim3(l.hist_blocks, l.node_groups * l.feat_groups), dim3(kHistBlock), l.lds_bytes,
-                       stream, a, d, l.node_group, l.feat_group, l.feat_groups);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const uint32_t waves = l.slots * F, per_block = kBlock / kWave;
-    hipLaunchKernelGGL(grow_split_kernel<0>, dim3((waves + per_block - 1) / per_block), dim3(kBlock), 0, stream, a, d, round);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(grow_split_kernel<1>, dim3(1), dim3(kBlock), 0, stream, a, d, round);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(grow_partition_kernel, dim3(plan.row_blocks), dim3(kBlock), 0, stream, a, round);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-  }
-  hipLaunchKernelGGL(grow_leaf_kernel, dim3(plan.row_blocks), dim3(kBlock), 0, stream, a, round);
-  return hipGetLastError();
+  if (a.min_child_rows < 1) return hipErrorInvalidValue;
+  // (kGrowMaxTrips: this histogram kernel alone counts a bin's rows in 32 bits of LDS)
+  return grow_launch_tree(
+      a, plan, levels, round, stream, a.num_feature, kGrowPairBytes, kGrowMaxTrips,
+      [&](const GrowLevelPlan& l, uint32_t d) {
+        hipLaunchKernelGGL(grow_hist_kernel, dim3(l.hist_blocks, l.node_groups * l.feat_groups), dim3(kHistBlock), l.lds_bytes,
+                           stream, a, d, l.node_group, l.feat_group, l.feat_groups);
+      },
+      [&](uint32_t blocks, uint32_t d) { hipLaunchKernelGGL(grow_split_kernel<0>, dim3(blocks), dim3(kBlock), 0, stream, a, d, round); },
+      [&](uint32_t d) { hipLaunchKernelGGL(grow_split_kernel<1>, dim3(1), dim3(kBlock), 0, stream, a, d, round); });
 }
 
 int launch_grow_partition(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream_) {

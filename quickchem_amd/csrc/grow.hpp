@@ -6,8 +6,9 @@
 // depends on neither the order of the rows nor the launch shape.  The gradient is the refit's 2^-24 fixed point and the
 // leaf solve is refit_solve_leaf itself (refit.hpp).
 //
-// What host and device share is in this header: the gain, the comparison of two candidates, the scan of one feature's
-// bins, and the launch plan.
+// What host and device share is in this header: the gain, the comparison of two candidates, the hessian policy of the
+// two kinds of hessian sum, the scan of one feature's bins over a policy, and the launch plan.  What the kernel files
+// share is in grow_device.hpp.
 #pragma once
 #include <cstdint>
 #include <vector>
@@ -31,10 +32,11 @@ constexpr uint32_t kGrowFlagWeight = 8u;       // a training row's weight that i
 constexpr uint32_t kGrowFlagEvalWeight = 16u;  // the same at a held-out row
 constexpr uint32_t kGrowFlagBag = 32u;         // a round whose bag of rows holds no weight (root H == 0)
 
-// gain(G, H) of the header: CalcGain of xgboost 1.6.0 with reg_alpha = 0 and max_delta_step = 0, on the fixed-point sum
-OHX_GROW_HD inline double grow_gain(int64_t G, uint64_t H, double lambda) {
+// gain(G, Hd) of the header: CalcGain of xgboost 1.6.0 with reg_alpha = 0 and max_delta_step = 0, on the fixed-point
+// gradient sum and the hessian sum as its policy (below) makes it a double
+OHX_GROW_HD inline double grow_gain(int64_t G, double Hd, double lambda) {
   const double Gd = (double)G * (1.0 / 16777216.0);
-  return (Gd * Gd) / ((double)H + lambda);
+  return (Gd * Gd) / (Hd + lambda);
 }
 
 // One candidate.  key orders the candidates of a node: (feature << 9) | (j << 1) | dl
@@ -58,37 +60,7 @@ OHX_GROW_HD inline bool grow_better(const GrowCand& a, const GrowCand& b) {
   return a.key < b.key;
 }
 
-// The best candidate among cuts j0 .. j0 + n - 1 (those below ncut) of feature f.  G / H point at bin j0; GLb / HLb
-// are the sums over the bins below j0; Gm / Hm the missing bin; Gp / Hp the node.  Candidates are visited in ascending
-// (j, dl) and replaced only by a strictly better one.  The host calls it with j0 = 0, n = ncut; a lane of
-// grow_split_kernel with its four bins.
-OHX_GROW_HD inline GrowCand grow_best_split(const int64_t* G, const uint64_t* H, uint32_t f, uint32_t j0, uint32_t n,
-                                            uint32_t ncut, int64_t GLb, uint64_t HLb, int64_t Gm, uint64_t Hm, int64_t Gp,
-                                            uint64_t Hp, double lambda, uint64_t min_child_rows) {
-  GrowCand best;
-  const double parent = grow_gain(Gp, Hp, lambda);
-  for (uint32_t k = 0; k < n; ++k) {
-    const uint32_t j = j0 + k;
-    GLb += G[k];
-    HLb += H[k];
-    if (j >= ncut) continue;
-    for (uint32_t dl = 0; dl < 2; ++dl) {
-      GrowCand c;
-      c.GL = dl ? GLb + Gm : GLb;
-      c.HL = dl ? HLb + Hm : HLb;
-      const int64_t GR = Gp - c.GL;
-      const uint64_t HR = Hp - c.HL;
-      if (c.HL < min_child_rows || HR < min_child_rows) continue;
-      c.loss_chg = (grow_gain(c.GL, c.HL, lambda) + grow_gain(GR, HR, lambda)) - parent;
-      c.key = grow_key(f, j, dl);
-      c.valid = 1;
-      if (grow_better(c, best)) best = c;
-    }
-  }
-  return best;
-}
-
-// ---- row weights (OHXBoosterBoostTreesWeighted; design in docs/21_row_weights.md) ----
+// ---- the hessian policy: what the two kinds of hessian sum do differently, for host and device alike ----
 
 // A weight w is finite with 0 <= w < 256; the hessian of its row is hq = (uint64) rint(w * 2^24) < 2^32, and a sum H of
 // up to 2^31 of them stays below 2^63.  Hd = (double)H * 2^-24: the conversion rounds to nearest even, the scaling is
@@ -97,21 +69,54 @@ constexpr float kGrowMaxWeight = 256.0f;
 OHX_GROW_HD inline double grow_hess(uint64_t H) { return (double)H * (1.0 / 16777216.0); }
 // (NaN fails both comparisons)
 OHX_GROW_HD inline bool grow_weight_sound(float w) { return w >= 0.0f && w < kGrowMaxWeight; }
-
-// gain(G, H) with the fixed-point hessian sum
-OHX_GROW_HD inline double grow_gain_weighted(int64_t G, uint64_t H, double lambda) {
-  const double Gd = (double)G * (1.0 / 16777216.0);
-  return (Gd * Gd) / (grow_hess(H) + lambda);
+// A node with Hd < 2 * min_child_weight is a leaf without evaluation
+OHX_GROW_HD inline bool grow_weight_splits(uint64_t Hp, double min_child_weight) {
+  return !(grow_hess(Hp) < 2.0 * min_child_weight);
+}
+// refit_solve_leaf with the fixed-point hessian sum: base_weight = (float)(-Gd / (Hd + lambda)), leaf = base_weight * eta
+OHX_GROW_HD inline void grow_solve_leaf_weighted(int64_t G, uint64_t H, float eta, float lambda, float* leaf, float* weight) {
+  const float w = (float)(-((double)G * (1.0 / 16777216.0)) / (grow_hess(H) + (double)lambda));
+  *weight = w;
+  *leaf = w * eta;
 }
 
-// grow_best_split with fixed-point hessian sums.  A candidate is valid when both children hold weight as integers
-// (HL > 0 and HR > 0: no gain is taken of an empty child, so lambda == 0 divides by no zero) and both have
-// Hd >= min_child_weight.  The order of the visits, grow_key and grow_better are grow_best_split's.
-OHX_GROW_HD inline GrowCand grow_best_split_weighted(const int64_t* G, const uint64_t* H, uint32_t f, uint32_t j0, uint32_t n,
-                                                     uint32_t ncut, int64_t GLb, uint64_t HLb, int64_t Gm, uint64_t Hm,
-                                                     int64_t Gp, uint64_t Hp, double lambda, double min_child_weight) {
+// "count": H counts rows (OHXBoosterBoostTrees, OHXBoosterBoostTreesEval).  Children hold min_child_rows rows each.
+struct GrowCountHess {
+  uint64_t min_child_rows;
+  OHX_GROW_HD double hess(uint64_t H) const { return (double)H; }
+  OHX_GROW_HD bool admits(uint64_t HL, uint64_t HR) const { return !(HL < min_child_rows || HR < min_child_rows); }
+  OHX_GROW_HD bool evaluates(uint64_t) const { return true; }
+  OHX_GROW_HD float sum_hess(uint64_t H) const { return (float)H; }
+  OHX_GROW_HD void solve_leaf(int64_t G, uint64_t H, float eta, float lambda, float* leaf, float* weight) const {
+    refit_solve_leaf(G, H, eta, lambda, leaf, weight);
+  }
+};
+// "fixed-point": H sums hq (the calls with row weights).  Both children hold weight as integers (HL > 0 and HR > 0: no
+// gain is taken of an empty child, so lambda == 0 divides by no zero) and both have Hd >= min_child_weight.
+struct GrowFixedHess {
+  double min_child_weight;
+  OHX_GROW_HD double hess(uint64_t H) const { return grow_hess(H); }
+  OHX_GROW_HD bool admits(uint64_t HL, uint64_t HR) const {
+    if (HL == 0 || HR == 0) return false;
+    return !(grow_hess(HL) < min_child_weight || grow_hess(HR) < min_child_weight);
+  }
+  OHX_GROW_HD bool evaluates(uint64_t Hp) const { return grow_weight_splits(Hp, min_child_weight); }
+  OHX_GROW_HD float sum_hess(uint64_t H) const { return (float)grow_hess(H); }
+  OHX_GROW_HD void solve_leaf(int64_t G, uint64_t H, float eta, float lambda, float* leaf, float* weight) const {
+    grow_solve_leaf_weighted(G, H, eta, lambda, leaf, weight);
+  }
+};
+
+// The best candidate among cuts j0 .. j0 + n - 1 (those below ncut) of feature f.  G / H point at bin j0; GLb / HLb
+// are the sums over the bins below j0; Gm / Hm the missing bin; Gp / Hp the node.  Candidates are visited in ascending
+// (j, dl) and replaced only by a strictly better one.  The host calls it with j0 = 0, n = ncut; a lane of a split
+// kernel with its four bins.
+template <class Hess>
+OHX_GROW_HD inline GrowCand grow_best_split(const int64_t* G, const uint64_t* H, uint32_t f, uint32_t j0, uint32_t n,
+                                            uint32_t ncut, int64_t GLb, uint64_t HLb, int64_t Gm, uint64_t Hm, int64_t Gp,
+                                            uint64_t Hp, double lambda, const Hess& hess) {
   GrowCand best;
-  const double parent = grow_gain_weighted(Gp, Hp, lambda);
+  const double parent = grow_gain(Gp, hess.hess(Hp), lambda);
   for (uint32_t k = 0; k < n; ++k) {
     const uint32_t j = j0 + k;
     GLb += G[k];
@@ -123,27 +128,14 @@ OHX_GROW_HD inline GrowCand grow_best_split_weighted(const int64_t* G, const uin
       c.HL = dl ? HLb + Hm : HLb;
       const int64_t GR = Gp - c.GL;
       const uint64_t HR = Hp - c.HL;
-      if (c.HL == 0 || HR == 0) continue;
-      if (grow_hess(c.HL) < min_child_weight || grow_hess(HR) < min_child_weight) continue;
-      c.loss_chg = (grow_gain_weighted(c.GL, c.HL, lambda) + grow_gain_weighted(GR, HR, lambda)) - parent;
+      if (!hess.admits(c.HL, HR)) continue;
+      c.loss_chg = (grow_gain(c.GL, hess.hess(c.HL), lambda) + grow_gain(GR, hess.hess(HR), lambda)) - parent;
       c.key = grow_key(f, j, dl);
       c.valid = 1;
       if (grow_better(c, best)) best = c;
     }
   }
   return best;
-}
-
-// A node with Hd < 2 * min_child_weight is a leaf without evaluation
-OHX_GROW_HD inline bool grow_weight_splits(uint64_t Hp, double min_child_weight) {
-  return !(grow_hess(Hp) < 2.0 * min_child_weight);
-}
-
-// refit_solve_leaf with the fixed-point hessian sum: base_weight = (float)(-Gd / (Hd + lambda)), leaf = base_weight * eta
-OHX_GROW_HD inline void grow_solve_leaf_weighted(int64_t G, uint64_t H, float eta, float lambda, float* leaf, float* weight) {
-  const float w = (float)(-((double)G * (1.0 / 16777216.0)) / (grow_hess(H) + (double)lambda));
-  *weight = w;
-  *leaf = w * eta;
 }
 
 // ---- row and column subsampling (OHXBoosterBoostTreesSampled; design in docs/22_sampling.md) ----
@@ -200,13 +192,22 @@ uint64_t quantile_cuts(const float* data, uint64_t nrow, uint64_t ncol, float mi
 // are finite and strictly ascending within a feature.
 void grow_check_cuts(const uint64_t* cut_ptr, const float* cut_values, uint32_t num_feature, const char* what);
 // The best split of one node over all features from its histograms G / H [num_feature][256] (grow_best_split per
-// feature, ascending, replaced by a strictly better one only).
-GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr, int64_t Gp,
-                         uint64_t Hp, float lambda, uint64_t min_child_rows);
-// The same over fixed-point hessian histograms (grow_best_split_weighted per feature); a node that
-// grow_weight_splits refuses has no candidate.
-GrowCand grow_node_split_weighted(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr,
-                                  int64_t Gp, uint64_t Hp, float lambda, float min_child_weight);
+// feature, ascending, replaced by a strictly better one only).  A node its policy does not evaluate has no candidate.
+template <class Hess>
+inline GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr, int64_t Gp,
+                                uint64_t Hp, float lambda, const Hess& hess) {
+  GrowCand best;
+  if (!hess.evaluates(Hp)) return best;
+  for (uint32_t f = 0; f < num_feature; ++f) {
+    const int64_t* g = G + (size_t)f * kGrowBins;
+    const uint64_t* h = H + (size_t)f * kGrowBins;
+    const uint32_t ncut = (uint32_t)(cut_ptr[f + 1] - cut_ptr[f]);
+    const GrowCand c = grow_best_split(g, h, f, 0, ncut, ncut, 0, 0, g[kGrowMissingBin], h[kGrowMissingBin], Gp, Hp,
+                                       (double)lambda, hess);
+    if (grow_better(c, best)) best = c;
+  }
+  return best;
+}
 // The features of tree i: the n_sel = grow_num_selected(F, colsample) features smallest by (mix(K_col(i) + f), f), written
 // to out[0 .. n_sel) in ascending f.  n_sel == F writes 0 .. F - 1 and draws nothing.  Returns n_sel (0: colsample is
 // unsound, F is 0 or above kGrowMaxFeatures; nothing is written).
@@ -234,6 +235,8 @@ inline bool grow_sum_less(GrowSum a, GrowSum b) {
   b = grow_sum_normal(b);
   return a.hi != b.hi ? a.hi < b.hi : a.lo < b.lo;
 }
+// the same where a sum is held as the exact integer itself (grow_sum_value)
+inline bool grow_sum_less(unsigned __int128 a, unsigned __int128 b) { return a < b; }
 // One step of the stop rule: the best round once S[t] is known.  Strict: a tie is not an improvement.
 template <class Sum>
 inline uint32_t grow_eval_best(const Sum* S, uint32_t best, uint32_t t) { return grow_sum_less(S[t], S[best]) ? t : best; }
@@ -271,6 +274,13 @@ inline unsigned __int128 grow_wide_value(GrowWideSum s) {
 }
 // a < b as the exact integers (the stop rule's comparison: grow_eval_best and grow_eval_stop take either sum)
 inline bool grow_sum_less(GrowWideSum a, GrowWideSum b) { return grow_wide_value(a) < grow_wide_value(b); }
+// Either sum as the exact integer, from the device's words: (hi, lo) where words == 2, (p2, p1, p0) where words == 3.
+// Each word stands 2^32 above the next.
+inline unsigned __int128 grow_sum_value(const unsigned long long* s, size_t words) {
+  unsigned __int128 v = 0;
+  for (size_t k = 0; k < words; ++k) v = (v << 32) + (unsigned __int128)s[k];
+  return v;
+}
 // sqrt( ((double)S * 2^-72) / ((double)W * 2^-24) ), W = sum hq: both exact integers rounded to nearest even as they
 // become doubles, exact scalings, then an IEEE division and square root.
 double grow_wide_rmse(GrowWideSum s, uint64_t W);
@@ -340,22 +350,51 @@ struct GrowArgs {
   int max_depth = 0;
   float eta = 0.0f, lambda = 0.0f, gamma = 0.0f;
   uint64_t min_child_rows = 1;
+  // row weights (grow_weighted.hip, grow_sampled.hip): Hhist and GrowNode.H hold fixed-point hessian sums, and
+  // min_child_rows is not read
+  const float* weights = nullptr;      // [nrow], or nullptr: every weight is 1.0f
+  double min_child_weight = 0.0;
+  // row and column subsampling (grow_sampled.hip): the histograms, `best` and the memsets are compact,
+  // [slots][n_sel][256]; the node records, pos, pred and the bins are those of every call
+  unsigned long long* bag = nullptr;   // [ceil(nrow / 64)] a bit a row, or nullptr: every row is in the bag
+  const uint8_t* features = nullptr;   // [rounds][n_sel] the selected features of every round, ascending
+  uint32_t n_sel = 0;
+  uint64_t row_key = 0;                // K_row of the tree at hand (grow_bag_kernel)
+  uint32_t k_s = kGrowSampleOne;
 };
-// Once per device before the first launch: the dynamic LDS limits.  Returns a hipError_t.
-int prepare_grow();
+// Once per device before the first launch: the dynamic LDS limits of the bin kernel and of the three histogram kernels,
+// each raised by the file that holds the kernel (raising one that a call never launches changes nothing).  Return a
+// hipError_t.
+int grow_lds_limits();            // grow.hip
+int grow_lds_limits_weighted();   // grow_weighted.hip
+int grow_lds_limits_sampled();    // grow_sampled.hip
+inline int prepare_grow() {
+  int e = grow_lds_limits();
+  if (e == 0) e = grow_lds_limits_weighted();
+  if (e == 0) e = grow_lds_limits_sampled();
+  return e;
+}
 // Enqueues the binning.  bins must be sized by the plan.  Returns a hipError_t.
 int launch_grow_bin(const GrowArgs& a, const GrowPlan& plan, void* stream);
-// Enqueues one tree, round `round`: per level the histogram memsets, the histogram, split and partition kernels, then
-// the leaf kernel (pred += leaf, pos = 0).  pos must be zero and pred the margin so far.  Returns a hipError_t.
-int launch_grow_tree(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
-// Enqueue grow_partition_kernel and grow_leaf_kernel alone, for a level loop of another file (grow_weighted.hip): they
+// Enqueue one tree, round `round`: per level the histogram memsets, the histogram, split and partition kernels, then
+// the leaf kernel (pred += leaf, pos = 0); the one level loop is grow_device.hpp's.  pos must be zero and pred the
+// margin so far.  `plan` serves the partition and leaf kernels; `levels` the histogram kernel: plan_grow's for
+// launch_grow_tree, plan_grow_weighted's for the other two, over the n_sel features of a sampled call (else `plan`
+// itself).  Return a hipError_t.
+int launch_grow_tree(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
+int launch_grow_tree_weighted(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
+int launch_grow_tree_sampled(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
+// Enqueue grow_partition_kernel and grow_leaf_kernel alone, for the level loop as the other files instantiate it: they
 // read node records and bins, never a histogram or a weight.  Return a hipError_t.
 int launch_grow_partition(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
 int launch_grow_leaf(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
+// Enqueues grow_bag_kernel: the bit plane of the tree with a.row_key.  a.bag must not be nullptr.  Returns a hipError_t.
+int launch_grow_bag(const GrowArgs& a, const GrowPlan& plan, void* stream);
 
-// The metric kernels (grow_eval.hip).  sums is [rounds + 1][2 sets: training, held-out][hi, lo].
+// The metric kernels.  sums is [rounds + 1][2 sets: training, held-out][hi, lo] (grow_eval.hip); with weights
+// (grow_weighted.hip) wsums is [2 sets] W, then [rounds + 1][2 sets][p2, p1, p0], and sums is not read.
 struct GrowEvalArgs {
-  const uint8_t* bins = nullptr;   // [num_feature][nrow] of the rows walked (grow_walk_sse_kernel only)
+  const uint8_t* bins = nullptr;   // [num_feature][nrow] of the rows walked (the walk kernels only)
   float* pred = nullptr;           // [nrow] their running margin
   const float* labels = nullptr;   // [nrow]
   uint64_t nrow = 0;
@@ -366,61 +405,25 @@ struct GrowEvalArgs {
   GrowLevelState* state = nullptr;
   int max_depth = 0;
   uint32_t label_flag = 0;         // what a residual out of range raises: kGrowFlagLabel or kGrowFlagEvalLabel
+  const float* weights = nullptr;  // [nrow], or nullptr
+  unsigned long long* wsums = nullptr;
+  uint32_t weight_flag = 0;        // what a weight out of range raises: kGrowFlagWeight or kGrowFlagEvalWeight
 };
 constexpr uint32_t kGrowEvalTrain = 0, kGrowEvalHeldOut = 1;
 inline size_t grow_sum_index(uint32_t t, uint32_t set) { return ((size_t)t * 2 + set) * 2; }
+inline size_t grow_sum_count(size_t rounds) { return (rounds + 1) * 2 * 2; }
+inline size_t grow_wide_index(uint32_t t, uint32_t set) { return 2 + ((size_t)t * 2 + set) * 3; }
+inline size_t grow_wide_count(size_t rounds) { return 2 + (rounds + 1) * 2 * 3; }
 // Enqueues grow_sse_kernel: sums[t][set] += the squares of pred - labels over the rows of `a`.  Returns a hipError_t.
 int launch_grow_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream);
 // Enqueues grow_walk_sse_kernel: the rows of `a` walk tree `round` by their bins, pred += leaf, and
 // sums[round + 1][set] += the squares.  Returns a hipError_t.
 int launch_grow_walk_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream);
-
-// Row weights (grow_weighted.hip).  Hhist holds fixed-point hessian sums, GrowNode.H likewise; g.min_child_rows is not
-// read.
-struct GrowWeightedArgs {
-  GrowArgs g;
-  const float* weights = nullptr;   // [nrow], or nullptr: every weight is 1.0f
-  double min_child_weight = 0.0;
-};
-// Once per device before the first launch: the histogram kernel's dynamic LDS limit.  Returns a hipError_t.
-int prepare_grow_weighted();
-// launch_grow_tree with grow_hist_weighted_kernel and grow_split_weighted_kernel in the level loop; plan is
-// plan_grow_weighted's.  Returns a hipError_t.
-int launch_grow_tree_weighted(const GrowWeightedArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
-
-// The weighted metric.  wsums is [2 sets] W, then [rounds + 1][2 sets][p2, p1, p0]; e.sums is not read.
-struct GrowWeightedEvalArgs {
-  GrowEvalArgs e;
-  const float* weights = nullptr;   // [nrow], or nullptr
-  unsigned long long* wsums = nullptr;
-  uint32_t weight_flag = 0;         // what a weight out of range raises: kGrowFlagWeight or kGrowFlagEvalWeight
-};
-inline size_t grow_wide_index(uint32_t t, uint32_t set) { return 2 + ((size_t)t * 2 + set) * 3; }
-inline size_t grow_wide_count(size_t rounds) { return 2 + (rounds + 1) * 2 * 3; }
 // Enqueues grow_sse_weighted_kernel: wsums[t][set] += hq * e^2 over the rows of `a`; t == 0 also checks the weights
 // and adds W of the set.  Returns a hipError_t.
-int launch_grow_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream);
+int launch_grow_sse_weighted(const GrowEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream);
 // Enqueues grow_walk_sse_weighted_kernel: grow_walk_sse_kernel's walk, then wsums[round + 1][set] += hq * e^2.
-int launch_grow_walk_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream);
-
-// Row and column subsampling (grow_sampled.hip).  The histograms, `best` and the memsets are compact:
-// [slots][n_sel][256]; the node records, pos, pred and the bins are those of the weighted call.
-struct GrowSampledArgs {
-  GrowWeightedArgs w;
-  unsigned long long* bag = nullptr;   // [ceil(nrow / 64)] a bit a row, or nullptr: every row is in the bag
-  const uint8_t* features = nullptr;   // [rounds][n_sel] the selected features of every round, ascending
-  uint32_t n_sel = 0;
-  uint64_t row_key = 0;                // K_row of the tree at hand (grow_bag_kernel)
-  uint32_t k_s = kGrowSampleOne;
-};
-// Once per device before the first launch: the histogram kernel's dynamic LDS limit.  Returns a hipError_t.
-int prepare_grow_sampled();
-// Enqueues grow_bag_kernel: the bit plane of the tree with a.row_key.  a.bag must not be nullptr.  Returns a hipError_t.
-int launch_grow_bag(const GrowSampledArgs& a, const GrowPlan& plan, void* stream);
-// launch_grow_tree_weighted with grow_hist_sampled_kernel and grow_split_sampled_kernel in the level loop.  plan is
-// plan_grow_weighted's over all features (the partition and leaf kernels); levels is plan_grow_weighted's over n_sel
-// features (the histogram kernel).  Returns a hipError_t.
-int launch_grow_tree_sampled(const GrowSampledArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
+int launch_grow_walk_sse_weighted(const GrowEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream);
 #endif  // __HIPCC__
 
 }  // namespace ohx

@@ -12,6 +12,7 @@
 #include <cstdint>
 
 #include "grow.hpp"
+#include "grow_device.hpp"
 #include "walk_device.hpp"
 
 namespace ohx {
@@ -20,14 +21,6 @@ namespace {
 
 constexpr int kBlock = (int)kGrowBlock;
 constexpr int kWaves = kBlock / kWave;
-
-// a node as the walk needs it
-struct EvalNode {
-  int32_t left, right;   // -1: a leaf
-  uint32_t fcd;          // feature << 9 | cut << 1 | default_left
-  float value;           // the leaf value
-};
-static_assert(sizeof(EvalNode) == 16, "16 bytes a node");
 
 // one row's square into the lane's accumulators; false where the residual is out of range
 __device__ inline bool add_square(float pred, float label, unsigned long long* hi, unsigned long long* lo) {
@@ -82,48 +75,18 @@ __global__ __launch_bounds__(kBlock) void grow_sse_kernel(GrowEvalArgs a, unsign
 // grid (blocks)
 __global__ __launch_bounds__(kBlock) void grow_walk_sse_kernel(GrowEvalArgs a, uint32_t round, unsigned long long* slot) {
   __shared__ EvalNode tree[kGrowMaxNodes];
-  const uint32_t count = a.tree_nodes[round];
-  if (count == 0 || count > kGrowMaxNodes) {   // (never: the split kernel writes it, and refuses a 513th node itself)
-    if (threadIdx.x == 0) atomicOr(&a.state->error, kGrowFlagState);
-    return;
-  }
-  const GrowNode* nodes = a.nodes + (uint64_t)round * kGrowMaxNodes;
-  for (uint32_t i = threadIdx.x; i < count; i += kBlock) {
-    EvalNode e;
-    e.left = nodes[i].left;
-    e.right = nodes[i].right;
-    e.fcd = (nodes[i].feature << 9) | ((nodes[i].cut & 255u) << 1) | (nodes[i].default_left != 0u ? 1u : 0u);
-    e.value = nodes[i].value;
-    tree[i] = e;
-  }
-  __syncthreads();
+  const uint32_t count = grow_stage_tree(a, round, tree);
+  if (count == 0) return;
   unsigned long long hi = 0, lo = 0;
   uint32_t flags = 0;
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
-    uint32_t p = 0;
-    bool sound = true;
-    for (int d = 0; d < a.max_depth; ++d) {
-      const EvalNode e = tree[p];
-      if (e.left < 0) break;
-      const uint32_t f = e.fcd >> 9;
-      if (f >= a.num_feature) {
-        sound = false;
-        break;
-      }
-      const uint32_t b = a.bins[(uint64_t)f * a.nrow + row];
-      const bool go_left = b == kGrowMissingBin ? (e.fcd & 1u) != 0u : b <= ((e.fcd >> 1) & 255u);
-      p = (uint32_t)(go_left ? e.left : e.right);
-      if (p >= count) {
-        sound = false;
-        break;
-      }
-    }
-    if (!sound || tree[p].left >= 0) {   // (tree[p] is read only while p < count)
+    uint32_t leaf;
+    if (!grow_walk_row(a, tree, count, row, &leaf)) {
       flags |= kGrowFlagState;
       continue;
     }
-    const float pred = a.pred[row] + tree[p].value;
+    const float pred = a.pred[row] + tree[leaf].value;
     a.pred[row] = pred;
     if (!add_square(pred, a.labels[row], &hi, &lo)) flags |= a.label_flag;
   }

@@ -16,6 +16,27 @@ void synth_set_error(const std::string& m);   // synth_host.cpp
 
 using namespace ohx;
 
+namespace {
+
+// a plan as the ohx_grow_plan* exports hand it out: info[0 .. 7] and max_depth x 7 level figures
+void write_plan(const GrowPlan& p, uint64_t bins_bytes, uint32_t pair_bytes, uint64_t* info, uint64_t* levels) {
+  info[0] = p.row_blocks;
+  info[1] = kGrowBlock;
+  info[2] = p.bin_lds_bytes;
+  info[3] = bins_bytes;
+  info[4] = p.hist_bytes;
+  info[5] = kGrowHistBlock;
+  info[6] = kGrowLdsBytes / pair_bytes;
+  info[7] = pair_bytes;
+  for (size_t d = 0; d < p.levels.size(); ++d) {
+    const GrowLevelPlan& l = p.levels[d];
+    const uint64_t v[7] = {l.slots, l.node_group, l.feat_group, l.node_groups, l.feat_groups, l.hist_blocks, l.lds_bytes};
+    memcpy(levels + d * 7, v, sizeof v);
+  }
+}
+
+}  // namespace
+
 // G / H: [num_feature][256].  out: [0] valid, [1] feature, [2] j, [3] default_left, [4] splits (valid and
 // loss_chg > gamma); sums: [0] GL, [1] HL
 extern "C" __attribute__((visibility("default"))) int ohx_grow_node_split(const int64_t* G, const uint64_t* H,
@@ -24,7 +45,7 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_node_split(const 
                                                                          uint64_t min_child_rows, double* loss_chg,
                                                                          uint32_t out[5], int64_t sums[2]) {
   try {
-    const GrowCand c = grow_node_split(G, H, num_feature, cut_ptr, Gp, Hp, lambda, min_child_rows);
+    const GrowCand c = grow_node_split(G, H, num_feature, cut_ptr, Gp, Hp, lambda, GrowCountHess{min_child_rows});
     *loss_chg = c.loss_chg;
     out[0] = c.valid;
     out[1] = c.key >> 9;
@@ -97,20 +118,7 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_plan(uint64_t nro
                                                                    uint64_t* levels) {
   try {
     if (max_depth < 1 || max_depth > kGrowMaxDepth) throw OhxError("ohx_grow_plan: max_depth must be in 1..8");
-    const GrowPlan p = plan_grow(nrow, num_feature, ncuts, max_depth, num_cus);
-    info[0] = p.row_blocks;
-    info[1] = kGrowBlock;
-    info[2] = p.bin_lds_bytes;
-    info[3] = p.bins_bytes;
-    info[4] = p.hist_bytes;
-    info[5] = kGrowHistBlock;
-    info[6] = kGrowMaxPairs;
-    info[7] = kGrowPairBytes;
-    for (size_t d = 0; d < p.levels.size(); ++d) {
-      const GrowLevelPlan& l = p.levels[d];
-      const uint64_t v[7] = {l.slots, l.node_group, l.feat_group, l.node_groups, l.feat_groups, l.hist_blocks, l.lds_bytes};
-      memcpy(levels + d * 7, v, sizeof v);
-    }
+    write_plan(plan_grow(nrow, num_feature, ncuts, max_depth, num_cus), (uint64_t)num_feature * nrow, kGrowPairBytes, info, levels);
     return 0;
   } catch (const std::exception& e) {
     synth_set_error(e.what());
@@ -169,14 +177,14 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_eval_plan(uint64_
 
 // ---- row weights ----
 
-// ohx_grow_node_split over fixed-point hessian histograms (grow_node_split_weighted); sums[1] is HL in fixed point
+// ohx_grow_node_split over fixed-point hessian histograms (the GrowFixedHess policy); sums[1] is HL in fixed point
 extern "C" __attribute__((visibility("default"))) int ohx_grow_node_split_weighted(const int64_t* G, const uint64_t* H,
                                                                                   uint32_t num_feature, const uint64_t* cut_ptr,
                                                                                   int64_t Gp, uint64_t Hp, float lambda, float gamma,
                                                                                   float min_child_weight, double* loss_chg,
                                                                                   uint32_t out[5], uint64_t sums[2]) {
   try {
-    const GrowCand c = grow_node_split_weighted(G, H, num_feature, cut_ptr, Gp, Hp, lambda, min_child_weight);
+    const GrowCand c = grow_node_split(G, H, num_feature, cut_ptr, Gp, Hp, lambda, GrowFixedHess{(double)min_child_weight});
     *loss_chg = c.loss_chg;
     out[0] = c.valid;
     out[1] = c.key >> 9;
@@ -205,20 +213,8 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_plan_weighted(uin
                                                                             uint64_t* levels) {
   try {
     if (max_depth < 1 || max_depth > kGrowMaxDepth) throw OhxError("ohx_grow_plan_weighted: max_depth must be in 1..8");
-    const GrowPlan p = plan_grow_weighted(nrow, num_feature, ncuts, max_depth, num_cus);
-    info[0] = p.row_blocks;
-    info[1] = kGrowBlock;
-    info[2] = p.bin_lds_bytes;
-    info[3] = p.bins_bytes;
-    info[4] = p.hist_bytes;
-    info[5] = kGrowHistBlock;
-    info[6] = kGrowWeightedMaxPairs;
-    info[7] = kGrowWeightedPairBytes;
-    for (size_t d = 0; d < p.levels.size(); ++d) {
-      const GrowLevelPlan& l = p.levels[d];
-      const uint64_t v[7] = {l.slots, l.node_group, l.feat_group, l.node_groups, l.feat_groups, l.hist_blocks, l.lds_bytes};
-      memcpy(levels + d * 7, v, sizeof v);
-    }
+    write_plan(plan_grow_weighted(nrow, num_feature, ncuts, max_depth, num_cus), (uint64_t)num_feature * nrow, kGrowWeightedPairBytes, info,
+               levels);
     return 0;
   } catch (const std::exception& e) {
     synth_set_error(e.what());
@@ -310,21 +306,8 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_plan_sampled(uint
     if (max_depth < 1 || max_depth > kGrowMaxDepth) throw OhxError("ohx_grow_plan_sampled: max_depth must be in 1..8");
     const uint32_t n_sel = num_feature <= kGrowMaxFeatures ? grow_num_selected(num_feature, colsample) : 0;
     if (n_sel == 0) throw OhxError("ohx_grow_plan_sampled: 1 to 128 features and a colsample_bytree in (0, 1]");
-    const GrowPlan p = plan_grow_weighted(nrow, n_sel, ncuts, max_depth, num_cus);
-    info[0] = p.row_blocks;
-    info[1] = kGrowBlock;
-    info[2] = p.bin_lds_bytes;
-    info[3] = (uint64_t)num_feature * nrow;
-    info[4] = p.hist_bytes;
-    info[5] = kGrowHistBlock;
-    info[6] = kGrowWeightedMaxPairs;
-    info[7] = kGrowWeightedPairBytes;
+    write_plan(plan_grow_weighted(nrow, n_sel, ncuts, max_depth, num_cus), (uint64_t)num_feature * nrow, kGrowWeightedPairBytes, info, levels);
     info[8] = n_sel;
-    for (size_t d = 0; d < p.levels.size(); ++d) {
-      const GrowLevelPlan& l = p.levels[d];
-      const uint64_t v[7] = {l.slots, l.node_group, l.feat_group, l.node_groups, l.feat_groups, l.hist_blocks, l.lds_bytes};
-      memcpy(levels + d * 7, v, sizeof v);
-    }
     return 0;
   } catch (const std::exception& e) {
     synth_set_error(e.what());

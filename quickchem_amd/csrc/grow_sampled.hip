@@ -1,4 +1,4 @@
-// gfx950 kernels of boosting with row and column subsampling (grow.hpp GrowSampledArgs; design in docs/22_sampling.md).
+// gfx950 kernels of boosting with row and column subsampling (grow.hpp GrowArgs; design in docs/22_sampling.md).
 //
 //   grow_bag_kernel               once per tree: a lane takes a row and evaluates the draw (grow_in_bag); the wave's 64
 //                                 results become one 64-bit word of the bit plane bag[ceil(nrow / 64)], written by one
@@ -9,7 +9,7 @@
 //                                 A lane whose bit of the plane is clear goes on before it reads pred, label or weight.
 //                                 The block's features sit four to a word in scalar registers, and a word's four bin
 //                                 loads are in flight together.
-//   grow_split_sampled_kernel<0>  grow_split_device.hpp's phase 0 over n_sel columns; the feature goes into the key and
+//   grow_split_sampled_kernel<0>  grow_device.hpp's phase 0 over n_sel columns; the feature goes into the key and
 //                                 the cut lookup.
 //   grow_split_sampled_kernel<1>  its phase 1; a root without weight raises kGrowFlagBag.
 // The partition, leaf and metric kernels see every row and are those of the weighted call (launch_grow_partition,
@@ -19,7 +19,7 @@
 #include <cstdint>
 
 #include "grow.hpp"
-#include "grow_split_device.hpp"
+#include "grow_device.hpp"
 #include "walk_device.hpp"
 
 namespace ohx {
@@ -34,36 +34,35 @@ static_assert(kGrowMaxFeatures <= 256, "a feature is a byte");
 
 // grid (blocks over the words x 64 rows).  A wave's rows are one word: the block's first row and the stride are
 // multiples of 64, and the loop's bound is too, so all 64 lanes take every trip together.
-__global__ __launch_bounds__(kBlock) void grow_bag_kernel(GrowSampledArgs sa) {
-  const uint64_t nrow = sa.w.g.nrow;
+__global__ __launch_bounds__(kBlock) void grow_bag_kernel(GrowArgs a) {
+  const uint64_t nrow = a.nrow;
   const uint64_t padded = ((nrow + 63) / 64) * 64;
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < padded; row += stride) {
-    const bool in = row < nrow && grow_in_bag(sa.row_key, row, sa.k_s);
+    const bool in = row < nrow && grow_in_bag(a.row_key, row, a.k_s);
     const unsigned long long word = __ballot(in);
-    if ((threadIdx.x & (kWave - 1)) == 0) sa.bag[row >> 6] = word;
+    if ((threadIdx.x & (kWave - 1)) == 0) a.bag[row >> 6] = word;
   }
 }
 
 // grid (blocks over the rows, node groups x feature groups); dynamic LDS: node_group x feat_group x 256 x (8 + 8).
 // The unrolled row loop keeps up to 40 plane offsets in scalar registers; eight waves a SIMD (two blocks a CU where LDS
 // allows) are asked for, so the compiler parks what does not fit 96 of them in lanes of a vector register, never scratch.
-__global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void grow_hist_sampled_kernel(GrowSampledArgs sa, uint32_t level, uint32_t round,
+__global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_waves_per_eu(8, 8))) void grow_hist_sampled_kernel(GrowArgs a, uint32_t level, uint32_t round,
                                                                        uint32_t node_group, uint32_t feat_group,
                                                                        uint32_t feat_groups) {
   extern __shared__ unsigned long long grow_shist[];
-  const GrowArgs& a = sa.w.g;
   uint32_t begin, end, next;
   grow_level_range(a, level, &begin, &end, &next);
   const uint32_t count = end - begin;
   const uint32_t slot0 = (blockIdx.y / feat_groups) * node_group;
   const uint32_t k0 = (blockIdx.y % feat_groups) * feat_group;   // the block's first column of the selected list
-  if (slot0 >= count || k0 >= sa.n_sel) return;
+  if (slot0 >= count || k0 >= a.n_sel) return;
   const uint32_t nslots = count - slot0 < node_group ? count - slot0 : node_group;
-  const uint32_t nf = sa.n_sel - k0 < feat_group ? sa.n_sel - k0 : feat_group;
+  const uint32_t nf = a.n_sel - k0 < feat_group ? a.n_sel - k0 : feat_group;
   // the block's features leave memory once: a byte each in wave-uniform words, so that the row loop forms a bin plane's
   // address with scalar arithmetic and loads nothing on the way to it
-  const uint8_t* feat = sa.features + (uint64_t)round * sa.n_sel + k0;
+  const uint8_t* feat = a.features + (uint64_t)round * a.n_sel + k0;
   uint32_t pack[kPackWords];
 #pragma unroll
   for (uint32_t j = 0; j < kPackWords; ++j) {
@@ -82,10 +81,10 @@ __global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_waves_per_eu(8, 8
   uint32_t flags = 0;
   const uint64_t stride = (uint64_t)gridDim.x * kHistBlock;
   for (uint64_t row = (uint64_t)blockIdx.x * kHistBlock + threadIdx.x; row < a.nrow; row += stride) {
-    if (sa.bag != nullptr) {
+    if (a.bag != nullptr) {
       // the wave's rows share one word (the first row of a wave and the stride are multiples of 64; rows < 2^31)
       const uint32_t word = __builtin_amdgcn_readfirstlane((uint32_t)(row >> 6));
-      if (((sa.bag[word] >> (row & 63u)) & 1ull) == 0ull) continue;
+      if (((a.bag[word] >> (row & 63u)) & 1ull) == 0ull) continue;
     }
     const uint32_t s = (uint32_t)a.pos[row] - first;   // (a node below `first` wraps past nslots)
     if (s >= nslots) continue;
@@ -95,7 +94,7 @@ __global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_waves_per_eu(8, 8
       flags |= kGrowFlagLabel;
       continue;
     }
-    const float w = sa.w.weights != nullptr ? sa.w.weights[row] : 1.0f;
+    const float w = a.weights != nullptr ? a.weights[row] : 1.0f;
     if (!grow_weight_sound(w)) {
       flags |= kGrowFlagWeight;
       continue;
@@ -143,7 +142,7 @@ __global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_waves_per_eu(8, 8
     if ((g | h) == 0ull) continue;
     const uint32_t s = i / (feat_group * kGrowBins), k = (i / kGrowBins) % feat_group, b = i % kGrowBins;
     if (s >= nslots || k >= nf) continue;
-    const uint64_t gi = ((uint64_t)(slot0 + s) * sa.n_sel + k0 + k) * kGrowBins + b;
+    const uint64_t gi = ((uint64_t)(slot0 + s) * a.n_sel + k0 + k) * kGrowBins + b;
     if (h != 0ull) atomicAdd(&a.Hhist[gi], h);
     if (g != 0ull) atomicAdd(&a.Ghist[gi], g);
   }
@@ -151,65 +150,48 @@ __global__ __launch_bounds__(kHistBlock) __attribute__((amdgpu_waves_per_eu(8, 8
 
 // PHASE 0: grid (blocks of four waves over slots x n_sel).  PHASE 1: one block.
 template <int PHASE>
-__global__ __launch_bounds__(kBlock) void grow_split_sampled_kernel(GrowSampledArgs sa, uint32_t level, uint32_t round) {
+__global__ __launch_bounds__(kBlock) void grow_split_sampled_kernel(GrowArgs a, uint32_t level, uint32_t round) {
+  const GrowFixedHess hess{a.min_child_weight};
   if (PHASE == 0) {
     GrowListMap map;
-    map.list = sa.features + (uint64_t)round * sa.n_sel;
-    grow_split_weighted_columns(sa.w, level, round, sa.n_sel, map);
+    map.list = a.features + (uint64_t)round * a.n_sel;
+    grow_split_columns(a, hess, level, round, a.n_sel, map);
   } else {
-    grow_split_weighted_nodes<true>(sa.w, level, round, sa.n_sel);
+    grow_split_nodes<true>(a, hess, level, round, a.n_sel);
   }
 }
 
-bool sampled_args_sound(const GrowSampledArgs& sa) {
-  const GrowArgs& a = sa.w.g;
-  return a.nrow != 0 && a.nrow <= kRefitMaxRows && a.num_feature != 0 && a.num_feature <= kGrowMaxFeatures && sa.n_sel != 0 &&
-         sa.n_sel <= a.num_feature && sa.k_s != 0 && sa.k_s <= kGrowSampleOne;
+bool sampled_args_sound(const GrowArgs& a) {
+  return a.nrow != 0 && a.nrow <= kRefitMaxRows && a.num_feature != 0 && a.num_feature <= kGrowMaxFeatures && a.n_sel != 0 &&
+         a.n_sel <= a.num_feature && a.k_s != 0 && a.k_s <= kGrowSampleOne;
 }
 
 }  // namespace
 
-int prepare_grow_sampled() {
+int grow_lds_limits_sampled() {
   return raise_lds_limit(grow_hist_sampled_kernel, kGrowWeightedMaxPairs * kGrowWeightedPairBytes);
 }
 
-int launch_grow_bag(const GrowSampledArgs& sa, const GrowPlan& plan, void* stream_) {
+int launch_grow_bag(const GrowArgs& a, const GrowPlan& plan, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (!sampled_args_sound(sa) || sa.bag == nullptr || plan.row_blocks == 0) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(grow_bag_kernel, dim3(plan.row_blocks), dim3(kBlock), 0, stream, sa);
+  if (!sampled_args_sound(a) || a.bag == nullptr || plan.row_blocks == 0) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(grow_bag_kernel, dim3(plan.row_blocks), dim3(kBlock), 0, stream, a);
   return hipGetLastError();
 }
 
-int launch_grow_tree_sampled(const GrowSampledArgs& sa, const GrowPlan& plan, const GrowPlan& levels, uint32_t round,
-                             void* stream_) {
+int launch_grow_tree_sampled(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const GrowArgs& a = sa.w.g;
-  if (!sampled_args_sound(sa) || sa.features == nullptr || a.max_depth < 1 || a.max_depth > kGrowMaxDepth ||
-      levels.levels.size() != (size_t)a.max_depth || plan.row_blocks == 0 || !(sa.w.min_child_weight >= 0.0))
-    return hipErrorInvalidValue;
-  const uint32_t C = sa.n_sel;
-  hipError_t e = hipSuccess;
-  for (uint32_t d = 0; d < (uint32_t)a.max_depth; ++d) {
-    const GrowLevelPlan& l = levels.levels[d];
-    if (l.slots != (1u << d) || l.node_group * l.feat_group > kGrowWeightedMaxPairs || l.node_group == 0 || l.feat_group == 0 ||
-        l.lds_bytes != l.node_group * l.feat_group * kGrowWeightedPairBytes || l.node_groups * l.node_group < l.slots ||
-        l.feat_groups * l.feat_group < C || l.hist_blocks == 0)
-      return hipErrorInvalidValue;
-    const size_t bytes = (size_t)l.slots * C * kGrowBins * sizeof(unsigned long long);
-    if ((e = hipMemsetAsync(a.Ghist, 0, bytes, stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(a.Hhist, 0, bytes, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(grow_hist_sampled_kernel, dim3(l.hist_blocks, l.node_groups * l.feat_groups), dim3(kHistBlock),
-                       l.lds_bytes, stream, sa, d, round, l.node_group, l.feat_group, l.feat_groups);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const uint32_t waves = l.slots * C, per_block = kBlock / kWave;
-    hipLaunchKernelGGL(grow_split_sampled_kernel<0>, dim3((waves + per_block - 1) / per_block), dim3(kBlock), 0, stream, sa, d,
-                       round);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(grow_split_sampled_kernel<1>, dim3(1), dim3(kBlock), 0, stream, sa, d, round);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = (hipError_t)launch_grow_partition(a, plan, round, stream)) != hipSuccess) return e;
-  }
-  return launch_grow_leaf(a, plan, round, stream);
+  if (!sampled_args_sound(a) || a.features == nullptr || !(a.min_child_weight >= 0.0)) return hipErrorInvalidValue;
+  return grow_launch_tree(
+      a, plan, levels, round, stream, a.n_sel, kGrowWeightedPairBytes, 0,
+      [&](const GrowLevelPlan& l, uint32_t d) {
+        hipLaunchKernelGGL(grow_hist_sampled_kernel, dim3(l.hist_blocks, l.node_groups * l.feat_groups), dim3(kHistBlock),
+                           l.lds_bytes, stream, a, d, round, l.node_group, l.feat_group, l.feat_groups);
+      },
+      [&](uint32_t blocks, uint32_t d) {
+        hipLaunchKernelGGL(grow_split_sampled_kernel<0>, dim3(blocks), dim3(kBlock), 0, stream, a, d, round);
+      },
+      [&](uint32_t d) { hipLaunchKernelGGL(grow_split_sampled_kernel<1>, dim3(1), dim3(kBlock), 0, stream, a, d, round); });
 }
 
 }  // namespace ohx

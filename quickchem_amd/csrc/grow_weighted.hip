@@ -1,11 +1,12 @@
-// gfx950 kernels of boosting with row weights (grow.hpp GrowWeightedArgs; design in docs/21_row_weights.md).
+// gfx950 kernels of boosting with row weights (grow.hpp GrowArgs; design in docs/21_row_weights.md).
 //
 //   grow_hist_weighted_kernel      once per level: grow_hist_kernel with a second fixed-point sum in place of the row
 //                                  count - q = rint(g * w * 2^24) and hq = rint(w * 2^24) go into the block's LDS
 //                                  histogram with two 64-bit integer adds a feature, 16 bytes a bin; the block flushes
 //                                  the bins where either sum is nonzero with 64-bit global adds.
-//   grow_split_weighted_kernel<0>  grow_split_kernel<0> with the weighted gain and validity (grow_best_split_weighted).
-//   grow_split_weighted_kernel<1>  grow_split_kernel<1> with the weighted leaf solve and the min_child_weight rule.
+//   grow_split_weighted_kernel<0>  grow_split_kernel<0> with the fixed-point hessian policy (grow.hpp GrowFixedHess): its gain and
+//                                  validity.
+//   grow_split_weighted_kernel<1>  grow_split_kernel<1> with that policy: its leaf solve and the min_child_weight rule.
 //   grow_sse_weighted_kernel       grow_sse_kernel with hq * e^2 in three 64-bit registers a lane; the launch for t = 0
 //                                  also checks the weights and sums W.
 //   grow_walk_sse_weighted_kernel  grow_walk_sse_kernel's walk, then the same sums.
@@ -17,7 +18,7 @@
 #include <cstdint>
 
 #include "grow.hpp"
-#include "grow_split_device.hpp"
+#include "grow_device.hpp"
 #include "walk_device.hpp"
 
 namespace ohx {
@@ -41,10 +42,9 @@ __device__ inline bool row_weight(const float* weights, uint64_t row, float* w, 
 }
 
 // grid (blocks over the rows, node groups x feature groups); dynamic LDS: node_group x feat_group x 256 x (8 + 8)
-__global__ __launch_bounds__(kHistBlock) void grow_hist_weighted_kernel(GrowWeightedArgs wa, uint32_t level, uint32_t node_group,
+__global__ __launch_bounds__(kHistBlock) void grow_hist_weighted_kernel(GrowArgs a, uint32_t level, uint32_t node_group,
                                                                         uint32_t feat_group, uint32_t feat_groups) {
   extern __shared__ unsigned long long grow_whist[];
-  const GrowArgs& a = wa.g;
   uint32_t begin, end, next;
   grow_level_range(a, level, &begin, &end, &next);
   const uint32_t count = end - begin;
@@ -72,7 +72,7 @@ __global__ __launch_bounds__(kHistBlock) void grow_hist_weighted_kernel(GrowWeig
     }
     float w;
     unsigned long long hq;
-    if (!row_weight(wa.weights, row, &w, &hq)) {
+    if (!row_weight(a.weights, row, &w, &hq)) {
       flags |= kGrowFlagWeight;
       continue;
     }
@@ -104,14 +104,15 @@ __global__ __launch_bounds__(kHistBlock) void grow_hist_weighted_kernel(GrowWeig
   }
 }
 
-// PHASE 0: grid (blocks of four waves over slots x features).  PHASE 1: one block.  The bodies are grow_split_device.hpp's,
-// here with a histogram column for every feature.
+// PHASE 0: grid (blocks of four waves over slots x features).  PHASE 1: one block.  The bodies are grow_device.hpp's,
+// here with the fixed-point hessian sum and a histogram column for every feature.
 template <int PHASE>
-__global__ __launch_bounds__(kBlock) void grow_split_weighted_kernel(GrowWeightedArgs wa, uint32_t level, uint32_t round) {
+__global__ __launch_bounds__(kBlock) void grow_split_weighted_kernel(GrowArgs a, uint32_t level, uint32_t round) {
+  const GrowFixedHess hess{a.min_child_weight};
   if (PHASE == 0) {
-    grow_split_weighted_columns(wa, level, round, wa.g.num_feature, GrowIdentityMap());
+    grow_split_columns(a, hess, level, round, a.num_feature, GrowIdentityMap());
   } else {
-    grow_split_weighted_nodes<false>(wa, level, round, wa.g.num_feature);
+    grow_split_nodes<false>(a, hess, level, round, a.num_feature);
   }
 }
 
@@ -170,136 +171,77 @@ __device__ inline void reduce_and_add(WideAcc acc, unsigned long long* slot, uns
 }
 
 // grid (blocks).  wslot: the set's W at t = 0, else nullptr
-__global__ __launch_bounds__(kBlock) void grow_sse_weighted_kernel(GrowWeightedEvalArgs wa, unsigned long long* slot,
+__global__ __launch_bounds__(kBlock) void grow_sse_weighted_kernel(GrowEvalArgs a, unsigned long long* slot,
                                                                    unsigned long long* wslot) {
-  const GrowEvalArgs& a = wa.e;
   WideAcc acc;
   uint32_t flags = 0;
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
     float w;
     unsigned long long hq;
-    const bool sound = row_weight(wa.weights, row, &w, &hq);
+    const bool sound = row_weight(a.weights, row, &w, &hq);
     if (!add_weighted_square(a.pred[row], a.labels[row], hq, &acc)) flags |= a.label_flag;
-    if (!sound) flags |= wa.weight_flag;
+    if (!sound) flags |= a.weight_flag;
     acc.w += hq;
   }
   if (flags) atomicOr(&a.state->error, flags);
   reduce_and_add(acc, slot, wslot);
 }
 
-// a node as the walk needs it (as in grow_eval.hip)
-struct EvalNode {
-  int32_t left, right;   // -1: a leaf
-  uint32_t fcd;          // feature << 9 | cut << 1 | default_left
-  float value;           // the leaf value
-};
-static_assert(sizeof(EvalNode) == 16, "16 bytes a node");
-
 // grid (blocks)
-__global__ __launch_bounds__(kBlock) void grow_walk_sse_weighted_kernel(GrowWeightedEvalArgs wa, uint32_t round,
-                                                                        unsigned long long* slot) {
+__global__ __launch_bounds__(kBlock) void grow_walk_sse_weighted_kernel(GrowEvalArgs a, uint32_t round, unsigned long long* slot) {
   __shared__ EvalNode tree[kGrowMaxNodes];
-  const GrowEvalArgs& a = wa.e;
-  const uint32_t count = a.tree_nodes[round];
-  if (count == 0 || count > kGrowMaxNodes) {   // (never: the split kernel writes it, and refuses a 513th node itself)
-    if (threadIdx.x == 0) atomicOr(&a.state->error, kGrowFlagState);
-    return;
-  }
-  const GrowNode* nodes = a.nodes + (uint64_t)round * kGrowMaxNodes;
-  for (uint32_t i = threadIdx.x; i < count; i += kBlock) {
-    EvalNode e;
-    e.left = nodes[i].left;
-    e.right = nodes[i].right;
-    e.fcd = (nodes[i].feature << 9) | ((nodes[i].cut & 255u) << 1) | (nodes[i].default_left != 0u ? 1u : 0u);
-    e.value = nodes[i].value;
-    tree[i] = e;
-  }
-  __syncthreads();
+  const uint32_t count = grow_stage_tree(a, round, tree);
+  if (count == 0) return;
   WideAcc acc;
   uint32_t flags = 0;
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
-    uint32_t p = 0;
-    bool sound = true;
-    for (int d = 0; d < a.max_depth; ++d) {
-      const EvalNode e = tree[p];
-      if (e.left < 0) break;
-      const uint32_t f = e.fcd >> 9;
-      if (f >= a.num_feature) {
-        sound = false;
-        break;
-      }
-      const uint32_t b = a.bins[(uint64_t)f * a.nrow + row];
-      const bool go_left = b == kGrowMissingBin ? (e.fcd & 1u) != 0u : b <= ((e.fcd >> 1) & 255u);
-      p = (uint32_t)(go_left ? e.left : e.right);
-      if (p >= count) {
-        sound = false;
-        break;
-      }
-    }
-    if (!sound || tree[p].left >= 0) {   // (tree[p] is read only while p < count)
+    uint32_t leaf;
+    if (!grow_walk_row(a, tree, count, row, &leaf)) {
       flags |= kGrowFlagState;
       continue;
     }
-    const float pred = a.pred[row] + tree[p].value;
+    const float pred = a.pred[row] + tree[leaf].value;
     a.pred[row] = pred;
     float w;
     unsigned long long hq;
-    if (!row_weight(wa.weights, row, &w, &hq)) flags |= wa.weight_flag;
+    if (!row_weight(a.weights, row, &w, &hq)) flags |= a.weight_flag;
     if (!add_weighted_square(pred, a.labels[row], hq, &acc)) flags |= a.label_flag;
   }
   if (flags) atomicOr(&a.state->error, flags);
   reduce_and_add(acc, slot, nullptr);
 }
 
-bool eval_args_sound(const GrowWeightedEvalArgs& wa, uint32_t blocks, uint32_t set) {
-  const GrowEvalArgs& a = wa.e;
+bool eval_args_sound(const GrowEvalArgs& a, uint32_t blocks, uint32_t set) {
   return a.nrow != 0 && a.nrow <= kRefitMaxRows && blocks != 0 && set <= 1 && a.pred != nullptr && a.labels != nullptr &&
-         wa.wsums != nullptr && a.state != nullptr &&
-         ((a.label_flag == kGrowFlagLabel && wa.weight_flag == kGrowFlagWeight) ||
-          (a.label_flag == kGrowFlagEvalLabel && wa.weight_flag == kGrowFlagEvalWeight));
+         a.wsums != nullptr && a.state != nullptr &&
+         ((a.label_flag == kGrowFlagLabel && a.weight_flag == kGrowFlagWeight) ||
+          (a.label_flag == kGrowFlagEvalLabel && a.weight_flag == kGrowFlagEvalWeight));
 }
 
 }  // namespace
 
-int prepare_grow_weighted() {
+int grow_lds_limits_weighted() {
   return raise_lds_limit(grow_hist_weighted_kernel, kGrowWeightedMaxPairs * kGrowWeightedPairBytes);
 }
 
-int launch_grow_tree_weighted(const GrowWeightedArgs& wa, const GrowPlan& plan, uint32_t round, void* stream_) {
+int launch_grow_tree_weighted(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  const GrowArgs& a = wa.g;
-  if (a.nrow == 0 || a.nrow > kRefitMaxRows || a.num_feature == 0 || a.num_feature > kGrowMaxFeatures || a.max_depth < 1 ||
-      a.max_depth > kGrowMaxDepth || plan.levels.size() != (size_t)a.max_depth || plan.row_blocks == 0 ||
-      !(wa.min_child_weight >= 0.0))
-    return hipErrorInvalidValue;
-  const uint32_t F = a.num_feature;
-  hipError_t e = hipSuccess;
-  for (uint32_t d = 0; d < (uint32_t)a.max_depth; ++d) {
-    const GrowLevelPlan& l = plan.levels[d];
-    if (l.slots != (1u << d) || l.node_group * l.feat_group > kGrowWeightedMaxPairs || l.node_group == 0 || l.feat_group == 0 ||
-        l.lds_bytes != l.node_group * l.feat_group * kGrowWeightedPairBytes || l.node_groups * l.node_group < l.slots ||
-        l.feat_groups * l.feat_group < F || l.hist_blocks == 0)
-      return hipErrorInvalidValue;
-    const size_t bytes = (size_t)l.slots * F * kGrowBins * sizeof(unsigned long long);
-    if ((e = hipMemsetAsync(a.Ghist, 0, bytes, stream)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(a.Hhist, 0, bytes, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(grow_hist_weighted_kernel, dim3(l.hist_blocks, l.node_groups * l.feat_groups), dim3(kHistBlock),
-                       l.lds_bytes, stream, wa, d, l.node_group, l.feat_group, l.feat_groups);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    const uint32_t waves = l.slots * F, per_block = kBlock / kWave;
-    hipLaunchKernelGGL(grow_split_weighted_kernel<0>, dim3((waves + per_block - 1) / per_block), dim3(kBlock), 0, stream, wa, d,
-                       round);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    hipLaunchKernelGGL(grow_split_weighted_kernel<1>, dim3(1), dim3(kBlock), 0, stream, wa, d, round);
-    if ((e = hipGetLastError()) != hipSuccess) return e;
-    if ((e = (hipError_t)launch_grow_partition(a, plan, round, stream)) != hipSuccess) return e;
-  }
-  return launch_grow_leaf(a, plan, round, stream);
+  if (!(a.min_child_weight >= 0.0)) return hipErrorInvalidValue;
+  return grow_launch_tree(
+      a, plan, levels, round, stream, a.num_feature, kGrowWeightedPairBytes, 0,
+      [&](const GrowLevelPlan& l, uint32_t d) {
+        hipLaunchKernelGGL(grow_hist_weighted_kernel, dim3(l.hist_blocks, l.node_groups * l.feat_groups), dim3(kHistBlock),
+                           l.lds_bytes, stream, a, d, l.node_group, l.feat_group, l.feat_groups);
+      },
+      [&](uint32_t blocks, uint32_t d) {
+        hipLaunchKernelGGL(grow_split_weighted_kernel<0>, dim3(blocks), dim3(kBlock), 0, stream, a, d, round);
+      },
+      [&](uint32_t d) { hipLaunchKernelGGL(grow_split_weighted_kernel<1>, dim3(1), dim3(kBlock), 0, stream, a, d, round); });
 }
 
-int launch_grow_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream_) {
+int launch_grow_sse_weighted(const GrowEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!eval_args_sound(a, blocks, set)) return hipErrorInvalidValue;
   hipLaunchKernelGGL(grow_sse_weighted_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, a.wsums + grow_wide_index(t, set),
@@ -307,10 +249,10 @@ int launch_grow_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uin
   return hipGetLastError();
 }
 
-int launch_grow_walk_sse_weighted(const GrowWeightedEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream_) {
+int launch_grow_walk_sse_weighted(const GrowEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (!eval_args_sound(a, blocks, set) || a.e.bins == nullptr || a.e.nodes == nullptr || a.e.tree_nodes == nullptr ||
-      a.e.num_feature == 0 || a.e.num_feature > kGrowMaxFeatures || a.e.max_depth < 1 || a.e.max_depth > kGrowMaxDepth)
+  if (!eval_args_sound(a, blocks, set) || a.bins == nullptr || a.nodes == nullptr || a.tree_nodes == nullptr ||
+      a.num_feature == 0 || a.num_feature > kGrowMaxFeatures || a.max_depth < 1 || a.max_depth > kGrowMaxDepth)
     return hipErrorInvalidValue;
   hipLaunchKernelGGL(grow_walk_sse_weighted_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, round,
                      a.wsums + grow_wide_index(round + 1, set));

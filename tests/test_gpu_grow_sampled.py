@@ -415,3 +415,53 @@ def test_refusals_leave_the_model_unchanged_and_a_valid_call_follows(torch_cuda,
     for m in (d, ed, dd, de, d1):
         m.free()
     b.free()
+
+
+# ---- the kinds of call in sequence on one handle ----
+
+def test_the_four_kinds_in_sequence_on_one_handle_leave_what_fresh_boosters_leave(torch_cuda, tmp_path):
+    """One booster takes a plain Device call, a Sampled, a Weighted, an Eval and a plain call again, 2 rounds each: the
+    kinds share the handle's grow state - its one prepared flag and its buffers, sized by a different plan each time.
+    After every step the saved bytes (all three formats) equal those of a fresh booster loaded from the previous
+    step's UBJSON bytes and given that one call: save then load keeps every field bit for bit (the comparison itself
+    would show a field that did not)."""
+    torch = torch_cuda
+    js, x, y, ex, ey, cuts = case(3, 4097, 65, missing=-999.0)
+    w = weights(5, 4097)
+    kw = dict(rounds=2, max_depth=3, eta=0.5)
+    d = capi.DMatrix(x, missing=-999.0)
+    ed = capi.DMatrix(ex, missing=NAN)
+    yd = torch.from_numpy(y).cuda()
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def plain_device(b):
+        return b.boost_trees_device(d, yd.data_ptr(), y.size, cuts, stream=stream, **kw)
+
+    steps = [("plain Device", plain_device),
+             ("Sampled", lambda b: b.boost_trees_sampled(d, y, cuts, subsample=0.5, colsample_bytree=0.5, seed=3, **kw)),
+             ("Weighted", lambda b: b.boost_trees_weighted(d, y, cuts, weights=w, **kw)),
+             ("Eval", lambda b: b.boost_trees_eval(d, y, cuts, eval_set=(ed, ey), patience=0, **kw)),
+             ("plain again", lambda b: b.boost_trees(d, y, cuts, **kw))]
+    one = capi.Booster(model_buffer=js)
+    before, trees = js, ntrees(js)
+    for what, call in steps:
+        got = call(one)
+        twin = capi.Booster(model_buffer=before)
+        want = call(twin)
+        if isinstance(want, dict):
+            assert (got["nodes_added"], got["rounds_run"], got["best_round"]) == (want["nodes_added"], 2, 2), what
+            assert got["train_rmse"].tolist() == want["train_rmse"].tolist(), what
+            if want["eval_rmse"] is not None:
+                assert got["eval_rmse"].tolist() == want["eval_rmse"].tolist(), what
+        else:
+            assert got == want > 2, what
+        after = saved(one, tmp_path)
+        assert after == saved(twin, tmp_path), what
+        twin.free()
+        trees += 2
+        assert ntrees(after[0]) == trees, what
+        before = after[1]
+    torch.cuda.synchronize()
+    for m in (d, ed):
+        m.free()
+    one.free()

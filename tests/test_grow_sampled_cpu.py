@@ -320,14 +320,30 @@ def test_the_kernel_files_hold_their_own_kernels():
     src = open(os.path.join(helpers.ROOT, "quickchem_amd", "csrc", "grow_sampled.hip")).read()
     assert sorted(set(re.findall(r"void (grow_\w+_kernel)\(", src))) == sorted(
         ["grow_bag_kernel", "grow_hist_sampled_kernel", "grow_split_sampled_kernel"])
-    # the split body is one text for the weighted and the sampled kernels
-    shared = open(os.path.join(helpers.ROOT, "quickchem_amd", "csrc", "grow_split_device.hpp")).read()
-    assert "grow_best_split_weighted(" in shared and "__global__" not in shared
-    for name in ("grow_weighted.hip", "grow_sampled.hip"):
-        text = open(os.path.join(helpers.ROOT, "quickchem_amd", "csrc", name)).read()
-        assert '#include "grow_split_device.hpp"' in text and "grow_best_split_weighted(" not in text, name
+    csrc = os.path.join(helpers.ROOT, "quickchem_amd", "csrc")
+    assert not os.path.exists(os.path.join(csrc, "grow_split_device.hpp")), "grow_device.hpp replaces it"
+    # the split choice is one text for the plain, the weighted and the sampled kernels: the shared header holds both
+    # phases, the only call of the scan among the device files, and no kernel
+    shared = open(os.path.join(csrc, "grow_device.hpp")).read()
+    assert shared.count("grow_best_split<") == 1 and "__global__" not in shared
+    for what in ("void grow_level_range(", "GrowCand grow_shuffle_cand(", "void grow_write_leaf(", "void grow_split_columns(",
+                 "void grow_split_nodes(", "hipError_t grow_launch_tree("):
+        assert shared.count(what) == 1, what
+    assert len(re.findall(r"for \(uint32_t d = 0; d < \(uint32_t\)a\.max_depth; \+\+d\)", shared)) == 1, "the one level loop"
+    for name in ("grow.hip", "grow_weighted.hip", "grow_sampled.hip"):
+        text = open(os.path.join(csrc, name)).read()
+        assert '#include "grow_device.hpp"' in text, name
+        assert "grow_split_columns(" in text and "grow_split_nodes<" in text and "grow_launch_tree(" in text, name
+        # no split scan, no prefix sums, no candidate shuffle, no leaf record and no level loop of its own
+        for own in ("grow_best_split", "__shfl_up", "__shfl_xor(c.", "r.base_weight", "a.max_depth; ++d", "hipMemsetAsync"):
+            assert own not in text, (name, own)
+    hdr = open(os.path.join(csrc, "grow.hpp")).read()
+    assert len(re.findall(r"GrowCand grow_best_split\(", hdr)) == 1 and "grow_best_split_weighted" not in hdr
+    for gone in ("GrowWeightedArgs", "GrowSampledArgs", "GrowWeightedEvalArgs", "prepare_grow_weighted", "prepare_grow_sampled"):
+        for name in sorted(os.listdir(csrc)):
+            assert gone not in open(os.path.join(csrc, name), errors="replace").read(), (gone, name)
     for name in ("grow.hip", "grow_eval.hip", "grow_weighted.hip"):
-        assert "sampled" not in open(os.path.join(helpers.ROOT, "quickchem_amd", "csrc", name)).read(), name
+        assert "sampled" not in open(os.path.join(csrc, name)).read(), name
 
 
 # ---- the host functions under sanitizers ----

@@ -260,6 +260,39 @@ def test_split_random_histograms_against_the_restatement():
     _split_case(Gh, Hh, [1], lam=0.0)
 
 
+def test_the_two_hessian_policies_choose_the_same_split_of_unit_weights():
+    """One scan and one node split serve both hessian policies (grow.hpp): the count policy on (G, H) and the
+    fixed-point policy on (G, H << 24) with min_child_weight = (float)min_child_rows give the same key, loss_chg, GL
+    and HL - (double)H and (double)(H << 24) * 2^-24 are the same double, and HL < min_child_rows covers HL == 0."""
+    rng = np.random.default_rng(22)
+    cases = 0
+    for case in range(48):
+        nf = (1, 3)[case % 2]
+        ncuts = rng.integers(1, 255, nf)
+        n = int(rng.integers(2, 300))
+        q = W.grad_fixed(rng.uniform(-2, 2, n).astype(np.float32), np.ones(n, np.float32))
+        Gh, Hh = _hist(nf)
+        for f in range(nf):
+            b = rng.integers(0, ncuts[f] + 1, n)
+            b[rng.random(n) < 0.2] = 255
+            np.add.at(Gh[f], b, q)
+            np.add.at(Hh[f], b, np.uint64(1))
+        ptr = np.concatenate([[0], np.cumsum(ncuts)]).astype(np.uint64)
+        Gp = int(Gh[0].sum())
+        for mcr in (1, 2, n // 2 + 1):
+            for lam in (0.0, 1.0):
+                count = synth.grow_node_split(Gh, Hh, ptr, Gp, n, lam, 0.0, mcr)
+                fixed = synth.grow_node_split_weighted(Gh, Hh << np.uint64(24), ptr, Gp, n << 24, lam, 0.0, float(mcr))
+                for k in ("valid", "feature", "j", "default_left", "splits", "GL"):
+                    assert count[k] == fixed[k], (case, mcr, lam, k, count, fixed)
+                assert np.float64(count["loss_chg"]).view(np.uint64) == np.float64(fixed["loss_chg"]).view(np.uint64)
+                assert count["HL"] == fixed["HL"] >> 24 and fixed["HL"] & ((1 << 24) - 1) == 0
+                if mcr == n // 2 + 1:
+                    assert not count["valid"], "no two children hold more than half the rows each"
+                cases += count["valid"]
+    assert cases > 100, "most cases have a split to compare"
+
+
 def test_the_leaf_solve():
     for Gs, H, eta, lam in ((-5 * Q, 7 * Q // 2, 1.0, 0.0), (3 * Q + 1, Q // 3, 0.3, 1.0), (0, Q, 0.5, 0.0),
                             (-(1 << 60) - 1, (1 << 62) + 5, 0.1, 1e-3), (17, 1, 1.0, 0.0)):
@@ -461,6 +494,18 @@ def test_the_earlier_kernel_files_hold_no_weighted_kernel():
     src = open(os.path.join(helpers.ROOT, "quickchem_amd", "csrc", "grow_weighted.hip")).read()
     assert sorted(set(re.findall(r"void (grow_\w+_kernel)\(", src))) == sorted(
         ["grow_hist_weighted_kernel", "grow_split_weighted_kernel", "grow_sse_weighted_kernel", "grow_walk_sse_weighted_kernel"])
+    # the held-out rows' walk is one text: the node, the staging and the walk are the shared header's, and both metric
+    # files call them and step through no tree[p] of their own
+    shared = open(os.path.join(helpers.ROOT, "quickchem_amd", "csrc", "grow_device.hpp")).read()
+    assert "weighted" not in shared and "sampled" not in shared, "the shared text takes neither file's word"
+    for what in ("struct EvalNode", "grow_stage_tree(const", "grow_walk_row(const"):
+        assert shared.count(what) == 1, what
+    assert "tree[p]" in shared
+    for name in ("grow_eval.hip", "grow_weighted.hip"):
+        src = open(os.path.join(helpers.ROOT, "quickchem_amd", "csrc", name)).read()
+        assert '#include "grow_device.hpp"' in src, name
+        assert "grow_stage_tree(" in src and "grow_walk_row(" in src, name
+        assert "tree[p]" not in src and "struct EvalNode" not in src, name
 
 
 # ---- the host functions under sanitizers ----

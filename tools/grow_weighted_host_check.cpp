@@ -107,7 +107,7 @@ static void check_splits(int histograms, uint64_t seed) {
     }
     const float lambda = it % 2 ? 0.0f : 1.0f;
     const float mcw = (float)((rng() % 4) * 0.25 * ((double)Hp / 16777216.0));
-    const GrowCand c = grow_node_split_weighted(G.data(), H.data(), F, cut_ptr.data(), Gp, Hp, lambda, mcw);
+    const GrowCand c = grow_node_split(G.data(), H.data(), F, cut_ptr.data(), Gp, Hp, lambda, GrowFixedHess{(double)mcw});
     EXPECT(!std::isnan(c.loss_chg));
     if (c.valid) {
       const uint32_t f = c.key >> 9, j = (c.key >> 1) & 255u;
@@ -127,7 +127,7 @@ static void check_splits(int histograms, uint64_t seed) {
   const uint64_t cut_ptr[2] = {0, 1};
   G[1] = 3 << 24;
   H[1] = 2 << 24;
-  const GrowCand c = grow_node_split_weighted(G.data(), H.data(), 1, cut_ptr, G[1], H[1], 0.0f, 0.0f);
+  const GrowCand c = grow_node_split(G.data(), H.data(), 1, cut_ptr, G[1], H[1], 0.0f, GrowFixedHess{0.0});
   EXPECT(!c.valid && c.loss_chg == 0.0);
 }
 
