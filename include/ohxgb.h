@@ -753,6 +753,43 @@ int OHXBoosterBoostTreesSampledDevice(BoosterHandle handle, DMatrixHandle dmat, 
                                       float colsample_bytree, uint64_t seed, int patience, double* train_rmse,
                                       double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added,
                                       void* stream);
+/* Trees deeper than eight levels (docs/23_deep_trees.md): OHXBoosterBoostTreesWeighted with max_depth in 1..18.  The
+ * argument lists are those of the Weighted call and of its Device form.  Everything is OHXBoosterBoostTreesWeighted's,
+ * word for word: the cuts and the bins; hq, q, the integer histograms, the candidates, their total order and the ties;
+ * node numbering in allocation order, level by level, in ascending id, and the records; min_child_weight, the metric,
+ * the stop rule, what is kept, all or nothing, what a success drops, the two forms, not capturable.  One thing changes:
+ * max_depth is in 1..18.  Eighteen is the depth the walk kernels, the path tables and the file formats are exercised
+ * at; nothing deeper has run.
+ * The size of a tree.  A split needs HL > 0 and HR > 0, so every leaf holds a row: a tree has at most
+ * min(2^(max_depth + 1) - 1, 2 * nrow - 1) nodes.  The node table of the call holds min(2^(max_depth + 1), 2 * nrow)
+ * records a round; the histograms of the levels from 8 on are kept in HBM for a batch of node slots at a time, so the
+ * scratch does not grow with the depth.  The sums are integers: which kernel makes them, and in how many batches,
+ * cannot change a bit.
+ * Consequences.  With max_depth <= 8 the forest, XGBoosterSaveModel's bytes in all three formats and both RMSE arrays
+ * equal those of OHXBoosterBoostTreesWeighted (the call takes that path as it is).  With unit weights and
+ * min_child_weight = (float)min_child_rows they equal those of OHXBoosterBoostTreesEval, at any max_depth both accept.
+ * Waiting.  With max_depth <= 8 the call waits as the Weighted call does.  With max_depth > 8 it also waits, in every
+ * tree, once per level from level 7 on for the 16-byte level word (the ids of the open nodes): the host enqueues exactly
+ * the batches the next level needs and ends the tree at the first level without an open node, so a request for depth 18
+ * on rows that stop splitting at level 12 enqueues no empty level.  Levels below 7 read nothing back.  The device form
+ * therefore waits for `stream` inside the call.
+ * Row and column subsampling are not offered at these depths: there is no Deep form of the Sampled call.
+ * Refused, with the forest and every output untouched: everything OHXBoosterBoostTreesWeighted refuses, in the same
+ * order, the max_depth message reading "max_depth must be in 1..18"; a node table or a scratch buffer that cannot be
+ * allocated is refused with its bytes.  The uint32 row positions and the held-out walk's node table are part of the
+ * grow state.  Calls on ONE booster must not run concurrently. */
+int OHXBoosterBoostTreesDeep(BoosterHandle handle, DMatrixHandle dmat, const float* labels, const float* weights,
+                             bst_ulong nlabel, DMatrixHandle eval_dmat, const float* eval_labels, const float* eval_weights,
+                             bst_ulong eval_nlabel, const bst_ulong* cut_ptr, const float* cut_values, int rounds,
+                             int max_depth, float eta, float lambda, float gamma, float min_child_weight, int patience,
+                             double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
+                             bst_ulong* nodes_added);
+int OHXBoosterBoostTreesDeepDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels, const float* d_weights,
+                                   bst_ulong nlabel, DMatrixHandle eval_dmat, const float* d_eval_labels,
+                                   const float* d_eval_weights, bst_ulong eval_nlabel, const bst_ulong* cut_ptr,
+                                   const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
+                                   float min_child_weight, int patience, double* train_rmse, double* eval_rmse,
+                                   int* rounds_run, int* best_round, bst_ulong* nodes_added, void* stream);
 int OHXQuantileCuts(const float* data, bst_ulong nrow, bst_ulong ncol, float missing, int max_bins, bst_ulong* cut_ptr,
                     float* cut_values, bst_ulong cap, bst_ulong* needed);
 /* OHXDMatrixQuantileCuts (docs/19_device_cuts.md) makes the same cuts from a DMatrix's rows where they lie, in HBM: no

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "OHXBoosterBoostTrees", "OHXBoosterBoostTreesDevice", "OHXBoosterBoostTreesEval", "OHXBoosterBoostTreesEvalDevice",
     "OHXBoosterBoostTreesWeighted", "OHXBoosterBoostTreesWeightedDevice",
     "OHXBoosterBoostTreesSampled", "OHXBoosterBoostTreesSampledDevice",
+    "OHXBoosterBoostTreesDeep", "OHXBoosterBoostTreesDeepDevice",
     "OHXQuantileCuts", "OHXDMatrixQuantileCuts",
     "OHXSelectCells", "OHXSelectCellsDevice", "OHXGatherCells", "OHXGatherCellsDevice",
     "OHXScatterCells", "OHXScatterCellsDevice",
@@ -149,6 +150,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.OHXBoosterBoostTreesWeighted.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, i32, i32, f32, f32, f32, f32,
                                                  i32, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u64)]
     lib.OHXBoosterBoostTreesWeightedDevice.argtypes = lib.OHXBoosterBoostTreesWeighted.argtypes + [vp]
+    lib.OHXBoosterBoostTreesDeep.argtypes = lib.OHXBoosterBoostTreesWeighted.argtypes
+    lib.OHXBoosterBoostTreesDeepDevice.argtypes = lib.OHXBoosterBoostTreesWeightedDevice.argtypes
     lib.OHXBoosterBoostTreesSampled.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, i32, i32, f32, f32, f32, f32,
                                                 f32, f32, u64, i32, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u64)]
     lib.OHXBoosterBoostTreesSampledDevice.argtypes = lib.OHXBoosterBoostTreesSampled.argtypes + [vp]
@@ -567,6 +570,12 @@ class Booster:
         """OHXBoosterBoostTreesWeighted: boost_trees_eval with a weight per row (0 <= w < 256; None: all 1) in the
         histograms, the leaves and both RMSEs.  eval_set = (DMatrix, labels[, weights]).  min_child_weight stands where
         min_child_rows stood.  -> the dict of boost_trees_eval."""
+        return self._boost_weighted("OHXBoosterBoostTreesWeighted", dmat, labels, cuts, weights, eval_set, rounds, max_depth,
+                                    eta, reg_lambda, gamma, min_child_weight, patience)
+
+    def _boost_weighted(self, entry, dmat, labels, cuts, weights, eval_set, rounds, max_depth, eta, reg_lambda, gamma,
+                        min_child_weight, patience) -> dict:
+        """The host form of the Weighted call, or of an entry point with its argument list."""
         y = np.ascontiguousarray(labels, dtype=np.float32).reshape(-1)
         w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1) if weights is not None else None
         if w is not None and w.size != y.size:
@@ -582,7 +591,7 @@ class Booster:
         k = max(int(rounds), 0) + 1
         train, held = np.full(k, np.nan), np.full(k, np.nan)
         run, best, n = C.c_int32(), C.c_int32(), C.c_uint64()
-        check(self.lib, self.lib.OHXBoosterBoostTreesWeighted(
+        check(self.lib, getattr(self.lib, entry)(
             self.handle, dmat.handle, y.ctypes.data, w.ctypes.data if w is not None else None, y.size,
             ed.handle if ed is not None else None, ey.ctypes.data if ey is not None else None,
             ew.ctypes.data if ew is not None else None, ey.size if ey is not None else 0, cut_ptr.ctypes.data,
@@ -597,17 +606,43 @@ class Booster:
         """The same with labels and weights in device memory: labels_ptr, weights_ptr (0: all 1) and
         eval_set = (DMatrix, eval_labels_ptr, eval_nlabel[, eval_weights_ptr]) are torch data_ptr()s of float32 ready
         on `stream`; the cuts stay host arrays.  Enqueues on `stream`; waits as boost_trees_eval_device (not capturable)."""
+        return self._boost_weighted_device("OHXBoosterBoostTreesWeightedDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
+                                           eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, patience,
+                                           stream)
+
+    def _boost_weighted_device(self, entry, dmat, labels_ptr, nlabel, cuts, weights_ptr, eval_set, rounds, max_depth, eta,
+                               reg_lambda, gamma, min_child_weight, patience, stream) -> dict:
+        """The device form of the Weighted call, or of an entry point with its argument list."""
         cut_ptr, cut_values = self._cuts(cuts)
         ed, eptr, en, ewptr = (tuple(eval_set) + (0,))[:4] if eval_set is not None else (None, None, 0, 0)
         k = max(int(rounds), 0) + 1
         train, held = np.full(k, np.nan), np.full(k, np.nan)
         run, best, n = C.c_int32(), C.c_int32(), C.c_uint64()
-        check(self.lib, self.lib.OHXBoosterBoostTreesWeightedDevice(
+        check(self.lib, getattr(self.lib, entry)(
             self.handle, dmat.handle, labels_ptr, weights_ptr or None, nlabel, ed.handle if ed is not None else None,
             eptr or None, ewptr or None, en, cut_ptr.ctypes.data, cut_values.ctypes.data, rounds, max_depth, eta,
             reg_lambda, gamma, min_child_weight, patience, train.ctypes.data, held.ctypes.data, C.byref(run),
             C.byref(best), C.byref(n), stream or None))
         return self._eval_result(train, held, run, best, n, ed is not None)
+
+    def boost_trees_deep(self, dmat: DMatrix, labels, cuts, weights=None, eval_set=None, rounds: int = 1,
+                         max_depth: int = 12, eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
+                         min_child_weight: float = 1.0, patience: int = 0) -> dict:
+        """OHXBoosterBoostTreesDeep: boost_trees_weighted with max_depth up to 18.  From level 8 on a level's histograms
+        are kept in HBM for a batch of nodes at a time, and the call waits once a level for the ids of the open nodes.
+        Up to depth 8 it is boost_trees_weighted itself.  -> the dict of boost_trees_eval."""
+        return self._boost_weighted("OHXBoosterBoostTreesDeep", dmat, labels, cuts, weights, eval_set, rounds, max_depth, eta,
+                                    reg_lambda, gamma, min_child_weight, patience)
+
+    def boost_trees_deep_device(self, dmat: DMatrix, labels_ptr: int, nlabel: int, cuts, weights_ptr: int = 0,
+                                eval_set=None, rounds: int = 1, max_depth: int = 12, eta: float = 0.3,
+                                reg_lambda: float = 1.0, gamma: float = 0.0, min_child_weight: float = 1.0,
+                                patience: int = 0, stream: int = 0) -> dict:
+        """The same with labels and weights in device memory, as boost_trees_weighted_device takes them.  With
+        max_depth > 8 the call waits for `stream` once a level from level 7 on."""
+        return self._boost_weighted_device("OHXBoosterBoostTreesDeepDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
+                                           eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, patience,
+                                           stream)
 
     def boost_trees_sampled(self, dmat: DMatrix, labels, cuts, weights=None, eval_set=None, rounds: int = 1,
                             max_depth: int = 6, eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,

@@ -678,9 +678,15 @@ struct GrowState {
   DevBuf<unsigned long long> d_bag;
   DevBuf<uint8_t> d_features;
   PinnedBuf<uint8_t> h_features;
+  // deep trees (OHXBoosterBoostTreesDeep with max_depth > 8): the uint32 positions of the levels from 8 on, and the tree
+  // at hand as the held-out walk reads it
+  DevBuf<uint32_t> d_pos_deep;
+  DevBuf<uint8_t> d_eval_nodes;          // [node stride] x kGrowEvalNodeBytes
   void release_device() {
     d_bag.release();
     d_features.release();
+    d_pos_deep.release();
+    d_eval_nodes.release();
     d_bins.release();
     d_pos.release();
     d_eval_bins.release();
@@ -2247,6 +2253,7 @@ struct BoostCall {
   BoostEval eval;
   BoostWeights weights;
   BoostSampling sampling;
+  bool deep = false;                 // OHXBoosterBoostTreesDeep: max_depth up to 18
 };
 
 BoostCall boost_call(const char* what, bool host_form, void* stream, DMatrixHandle dmat, const float* labels, bst_ulong nlabel,
@@ -2297,15 +2304,36 @@ BoostWeights boost_weights(const float* weights, const float* eval_weights, floa
 // The kind of a call, and in one place what it runs: its level plan, its tree launcher, its metric launchers and the
 // layout of its metric sums (the words of one sum, where sum (t, set) lies, and the words in all for `rounds` rounds).
 // Plain: row counts and 12-byte bins.  Weighted: fixed-point hessians.  Sampled: the same over a bag and a feature list.
+// Deep: the weighted kind to level 7 and histograms in HBM from level 8 on, with its own node stride and held-out walk;
+// `deep` is its plan and `deep_args` what its kernels take beyond GrowArgs (filled by boost_trees once the buffers stand).
 // (Calls, not a table of function addresses: a build of this file alone links without the grower until it is used.)
 struct BoostKind {
-  enum Which { Plain, Weighted, Sampled } which;
+  enum Which { Plain, Weighted, Sampled, Deep } which;
+  GrowDeepPlan deep;
+  GrowDeepArgs deep_args;
+  GrowLevelState* h_state = nullptr;   // where the Deep kind's tree launcher waits for the level word
   bool wide() const { return which != Plain; }
-  GrowPlan plan(uint64_t n, uint32_t F, uint64_t ncuts, int max_depth, int num_cus) const {
+  GrowPlan plan(uint64_t n, uint32_t F, uint64_t ncuts, int max_depth, int num_cus) {
+    if (which == Deep) {
+      deep = plan_grow_deep(n, F, ncuts, max_depth, num_cus);
+      GrowPlan p = deep.lds;           // the streaming kernels and the bins; the histograms of either path
+      p.hist_bytes = std::max(p.hist_bytes, deep.scratch_bytes);
+      return p;
+    }
     return wide() ? plan_grow_weighted(n, F, ncuts, max_depth, num_cus) : plan_grow(n, F, ncuts, max_depth, num_cus);
+  }
+  // node records of one round, and the candidates of a level
+  size_t node_stride() const { return which == Deep ? (size_t)deep.node_stride : (size_t)kGrowMaxNodes; }
+  size_t best_count(uint32_t F, int max_depth) const {
+    return which == Deep ? (size_t)(deep.best_bytes / sizeof(GrowCand)) : (size_t)(1u << (max_depth - 1)) * F;
   }
   hipError_t tree(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream) const {
     switch (which) {
+      case Deep: {
+        GrowDeepArgs d = deep_args;
+        d.g = a;
+        return (hipError_t)launch_grow_tree_deep(d, deep, round, h_state, stream);
+      }
       case Sampled: return (hipError_t)launch_grow_tree_sampled(a, plan, levels, round, stream);
       case Weighted: return (hipError_t)launch_grow_tree_weighted(a, plan, levels, round, stream);
       default: return (hipError_t)launch_grow_tree(a, plan, levels, round, stream);
@@ -2315,6 +2343,7 @@ struct BoostKind {
     return (hipError_t)(wide() ? launch_grow_sse_weighted(a, blocks, t, set, stream) : launch_grow_sse(a, blocks, t, set, stream));
   }
   hipError_t walk_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream) const {
+    if (which == Deep) return (hipError_t)launch_grow_walk_sse_deep(a, deep_args, blocks, round, set, stream);
     return (hipError_t)(wide() ? launch_grow_walk_sse_weighted(a, blocks, round, set, stream)
                                : launch_grow_walk_sse(a, blocks, round, set, stream));
   }
@@ -2338,6 +2367,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   const int max_depth = c.max_depth;
   if (weighted && !ev.present) throw OhxError(w0 + ": the weighted call carries the metric");
   if (c.sampling.present && !weighted) throw OhxError(w0 + ": the sampled call carries the weights");
+  if (c.deep && (!weighted || c.sampling.present)) throw OhxError(w0 + ": the deep call is the weighted call");
   if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
   refuse_categorical(b, what);
   refuse_groups(b, what);
@@ -2351,7 +2381,8 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (F == 0 || F > kGrowMaxFeatures)
     throw OhxError(w0 + ": the booster has " + std::to_string(F) + " features; 1 to 128 are binned (their cuts are staged in LDS)");
   if (c.rounds < 1) throw OhxError(w0 + ": rounds must be >= 1");
-  if (max_depth < 1 || max_depth > kGrowMaxDepth) throw OhxError(w0 + ": max_depth must be in 1..8");
+  if (max_depth < 1 || max_depth > (c.deep ? kGrowDeepMaxDepth : kGrowMaxDepth))
+    throw OhxError(w0 + (c.deep ? ": max_depth must be in 1..18" : ": max_depth must be in 1..8"));
   if (!std::isfinite(c.eta)) throw OhxError(w0 + ": eta must be finite");
   if (!(std::isfinite(c.lambda) && c.lambda >= 0.0f)) throw OhxError(w0 + ": lambda must be finite and >= 0");
   if (!(std::isfinite(c.gamma) && c.gamma >= 0.0f)) throw OhxError(w0 + ": gamma must be finite and >= 0");
@@ -2401,7 +2432,9 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   }
   // the kind of the call, once: everything below that differs by kernel or by sum layout asks `kind`
   const bool sampled = k_s != kGrowSampleOne || n_sel != F;
-  const BoostKind kind{sampled ? BoostKind::Sampled : weighted ? BoostKind::Weighted : BoostKind::Plain};
+  // (the Deep entry point at max_depth <= 8 takes the weighted kind as it is)
+  const bool deep = c.deep && max_depth > kGrowMaxDepth;
+  BoostKind kind{deep ? BoostKind::Deep : sampled ? BoostKind::Sampled : weighted ? BoostKind::Weighted : BoostKind::Plain};
   // before anything is built or enqueued: building the state waits for the library's stream
   if (!host_form && stream_capturing(c.caller))
     refuse_in_capture("grow trees", (w0 + " is not capturable; call it outside the capture").c_str());
@@ -2444,8 +2477,13 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (host_form) room(g.d_labels, n, 4, "the staged labels");
   room(g.d_Ghist, (size_t)(levels.hist_bytes / 16), 8, "the gradient histograms");
   room(g.d_Hhist, (size_t)(levels.hist_bytes / 16), 8, kind.hess_name());
-  room(g.d_best, (size_t)(1u << (max_depth - 1)) * F, sizeof(GrowCand), "the split candidates");
-  room(g.d_nodes, R * kGrowMaxNodes, sizeof(GrowNode), "the node records");
+  room(g.d_best, kind.best_count(F, max_depth), sizeof(GrowCand), "the split candidates");
+  const size_t stride = kind.node_stride();
+  room(g.d_nodes, R * stride, sizeof(GrowNode), "the node records");
+  if (deep) {
+    room(g.d_pos_deep, n, 4, "the row positions of the deep levels");
+    if (e != nullptr) room(g.d_eval_nodes, stride * kGrowEvalNodeBytes, 1, "the held-out walk's node table");
+  }
   const uint64_t ne = e != nullptr ? e->nrow : 0;
   GrowPlan eplan;                    // the held-out rows' binning
   if (weighted) {
@@ -2465,7 +2503,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   }
   if (ev.present) {
     if (e != nullptr) {
-      eplan = plan_grow(ne, F, ncuts, max_depth, dev.num_cus);
+      eplan = plan_grow(ne, F, ncuts, std::min(max_depth, kGrowMaxDepth), dev.num_cus);
       room(g.d_eval_bins, (size_t)eplan.bins_bytes, 1, "the held-out bin planes (features x rows)");
       room(g.d_eval_pred, ne, 4, "the held-out margin");
       if (host_form) room(g.d_eval_labels, ne, 4, "the staged eval labels");
@@ -2477,7 +2515,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   g.d_cut_ptr.ensure(F + 1);
   g.d_state.ensure(1);
   g.d_saved_flag.ensure(1);
-  g.h_nodes.ensure(R * kGrowMaxNodes);
+  if (!deep) g.h_nodes.ensure(R * kGrowMaxNodes);   // (the Deep kind sizes it by the records in use, at the end)
   g.h_tree_nodes.ensure(R);
   g.h_cuts.ensure(std::max<size_t>(ncuts, 1));
   g.h_cut_ptr.ensure(F + 1);
@@ -2505,6 +2543,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   HIP_CHECK(hipMemsetAsync(g.d_state.p, 0, sizeof(GrowLevelState), stream));
   HIP_CHECK(hipMemsetAsync(g.d_tree_nodes.p, 0, R * sizeof(uint32_t), stream));
   HIP_CHECK(hipMemsetAsync(g.d_pos.p, 0, n * sizeof(uint16_t), stream));
+  if (deep) HIP_CHECK(hipMemsetAsync(g.d_pos_deep.p, 0, n * sizeof(uint32_t), stream));
   if (sampled) HIP_CHECK(hipMemcpyAsync(g.d_features.p, g.h_features.p, R * n_sel, hipMemcpyHostToDevice, stream));
   if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_labels.p, c.labels, n * sizeof(float), hipMemcpyHostToDevice, stream));
   initial_margin(d, g.d_pred.p, n);
@@ -2553,6 +2592,13 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     a.features = g.d_features.p;
     a.n_sel = n_sel;
     a.k_s = k_s;
+  }
+  if (deep) {
+    kind.deep_args.pos = g.d_pos_deep.p;
+    kind.deep_args.node_stride = (uint32_t)stride;
+    kind.deep_args.eval_nodes = e != nullptr ? g.d_eval_nodes.p : nullptr;
+    kind.deep_args.g = a;              // (the walk launcher reads the records and their counts from it)
+    kind.h_state = g.h_state.p;
   }
   // one tree by the kernels of the call's kind
   auto grow_tree = [&](uint32_t r) {
@@ -2643,11 +2689,23 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     if (launched == hipSuccess && waited == hipSuccess)
       launched = hipMemcpyAsync(g.h_sums.p, g.d_sums.p, nsums * sizeof(unsigned long long), hipMemcpyDeviceToHost, stream);
   }
-  if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_nodes.p, g.d_nodes.p, R * kGrowMaxNodes * sizeof(GrowNode), hipMemcpyDeviceToHost, stream);
+  if (launched == hipSuccess && !deep)
+    launched = hipMemcpyAsync(g.h_nodes.p, g.d_nodes.p, R * kGrowMaxNodes * sizeof(GrowNode), hipMemcpyDeviceToHost, stream);
   if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_tree_nodes.p, g.d_tree_nodes.p, R * sizeof(uint32_t), hipMemcpyDeviceToHost, stream);
   if (launched == hipSuccess) launched = hipMemcpyAsync(g.h_state.p, g.d_state.p, sizeof(GrowLevelState), hipMemcpyDeviceToHost, stream);
   // both forms wait, whatever was enqueued: the labels and the records are read from the caller's and the state's memory
-  const hipError_t waited_last = hipStreamSynchronize(stream);
+  hipError_t waited_last = hipStreamSynchronize(stream);
+  // the Deep kind: the counts first, then only the records in use, packed round after round
+  std::vector<size_t> first(R + 1, 0);
+  if (deep && launched == hipSuccess && waited == hipSuccess && waited_last == hipSuccess && g.h_state.p->error == 0) {
+    for (size_t r = 0; r < R; ++r) first[r + 1] = first[r] + std::min<size_t>(g.h_tree_nodes.p[r], stride);
+    g.h_nodes.ensure(std::max<size_t>(first[R], 1));
+    for (size_t r = 0; launched == hipSuccess && r < R; ++r)
+      if (first[r + 1] != first[r])
+        launched = hipMemcpyAsync(g.h_nodes.p + first[r], g.d_nodes.p + r * stride, (first[r + 1] - first[r]) * sizeof(GrowNode),
+                                  hipMemcpyDeviceToHost, stream);
+    waited_last = hipStreamSynchronize(stream);
+  }
   if (!host_form) {
     d.used_async = true;
     if (e != nullptr) e->used_async = true;
@@ -2693,7 +2751,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   std::vector<Tree> grown;
   bst_ulong added = 0;
   for (size_t r = 0; r < keep; ++r) {
-    grown.push_back(grow_assemble_tree(g.h_nodes.p + r * kGrowMaxNodes, g.h_tree_nodes.p[r], F));
+    grown.push_back(grow_assemble_tree(g.h_nodes.p + (deep ? first[r] : r * kGrowMaxNodes), g.h_tree_nodes.p[r], F, (uint32_t)stride));
     added += g.h_tree_nodes.p[r];
   }
   const size_t T0 = (size_t)tree0;
@@ -3516,6 +3574,38 @@ int OHXBoosterBoostTreesSampledDevice(BoosterHandle handle, DMatrixHandle dmat, 
   c.eval = boost_eval(eval_dmat, d_eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
   c.weights = boost_weights(d_weights, d_eval_weights, min_child_weight);
   c.sampling = {true, subsample, colsample_bytree, seed};
+  boost_trees(*as_booster(handle), c);
+  API_END();
+}
+
+int OHXBoosterBoostTreesDeep(BoosterHandle handle, DMatrixHandle dmat, const float* labels, const float* weights,
+                             bst_ulong nlabel, DMatrixHandle eval_dmat, const float* eval_labels, const float* eval_weights,
+                             bst_ulong eval_nlabel, const bst_ulong* cut_ptr, const float* cut_values, int rounds,
+                             int max_depth, float eta, float lambda, float gamma, float min_child_weight, int patience,
+                             double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
+                             bst_ulong* nodes_added) {
+  API_BEGIN();
+  BoostCall c = boost_call("OHXBoosterBoostTreesDeep", true, nullptr, dmat, labels, nlabel, cut_ptr, cut_values, rounds,
+                           max_depth, eta, lambda, gamma, nodes_added);
+  c.eval = boost_eval(eval_dmat, eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
+  c.weights = boost_weights(weights, eval_weights, min_child_weight);
+  c.deep = true;
+  boost_trees(*as_booster(handle), c);
+  API_END();
+}
+
+int OHXBoosterBoostTreesDeepDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels, const float* d_weights,
+                                   bst_ulong nlabel, DMatrixHandle eval_dmat, const float* d_eval_labels,
+                                   const float* d_eval_weights, bst_ulong eval_nlabel, const bst_ulong* cut_ptr,
+                                   const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
+                                   float min_child_weight, int patience, double* train_rmse, double* eval_rmse,
+                                   int* rounds_run, int* best_round, bst_ulong* nodes_added, void* stream) {
+  API_BEGIN();
+  BoostCall c = boost_call("OHXBoosterBoostTreesDeepDevice", false, stream, dmat, d_labels, nlabel, cut_ptr, cut_values,
+                           rounds, max_depth, eta, lambda, gamma, nodes_added);
+  c.eval = boost_eval(eval_dmat, d_eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
+  c.weights = boost_weights(d_weights, d_eval_weights, min_child_weight);
+  c.deep = true;
   boost_trees(*as_booster(handle), c);
   API_END();
 }

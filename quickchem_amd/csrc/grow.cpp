@@ -83,8 +83,8 @@ uint32_t grow_pick_features(uint64_t seed, uint64_t i, uint32_t F, float colsamp
   return n_sel;
 }
 
-Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature) {
-  if (n == 0 || n > kGrowMaxNodes || n % 2 == 0) throw OhxError("grown tree: " + std::to_string(n) + " nodes is not a tree");
+Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature, uint32_t max_nodes) {
+  if (n == 0 || n > max_nodes || n % 2 == 0) throw OhxError("grown tree: " + std::to_string(n) + " nodes is not a tree");
   Tree t;
   t.resize(n);
   t.num_feature = (int32_t)num_feature;
@@ -159,6 +159,21 @@ GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_
 
 GrowPlan plan_grow_weighted(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus) {
   return plan_grow_pairs(nrow, num_feature, ncuts, max_depth, num_cus, kGrowWeightedPairBytes);
+}
+
+GrowDeepPlan plan_grow_deep(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus) {
+  GrowDeepPlan p;
+  p.lds = plan_grow_weighted(nrow, num_feature, ncuts, std::min(max_depth, kGrowMaxDepth), num_cus);
+  p.batch = kGrowDeepBatch;
+  // a row per lane in natural order, as the other streaming kernels: a block outside the batch costs one load a row
+  p.hist_blocks = p.lds.row_blocks;
+  p.node_stride = grow_deep_node_stride(nrow, max_depth);
+  const uint64_t F = std::max<uint32_t>(num_feature, 1);
+  const uint64_t open = grow_deep_max_open(nrow, max_depth);
+  if (max_depth > kGrowMaxDepth) p.scratch_bytes = std::min<uint64_t>(p.batch, open) * F * kGrowBins * 16;
+  // (the levels in LDS index `best` by 2^d slots, whatever the rows)
+  p.best_bytes = std::max<uint64_t>(open, 1ull << (std::min(max_depth, kGrowMaxDepth) - 1)) * F * sizeof(GrowCand);
+  return p;
 }
 
 uint32_t plan_grow_eval_blocks(uint64_t nrow, int num_cus) {

@@ -10,6 +10,7 @@
 // two kinds of hessian sum, the scan of one feature's bins over a policy, and the launch plan.  What the kernel files
 // share is in grow_device.hpp.
 #pragma once
+#include <algorithm>
 #include <cstdint>
 #include <vector>
 
@@ -25,6 +26,9 @@ constexpr uint32_t kGrowMaxCuts = 254;         // per feature
 constexpr uint32_t kGrowMaxFeatures = 128;     // the cuts of all features fit LDS: 128 x 254 floats
 constexpr int kGrowMaxDepth = 8;
 constexpr uint32_t kGrowMaxNodes = 512;        // node records kept per tree (a tree of depth 8 has at most 511)
+// the Deep call (grow_deep.hip; design in docs/23_deep_trees.md): levels 8 and deeper keep their histograms in HBM
+constexpr int kGrowDeepMaxDepth = 18;          // the depth the walk kernels, the path tables and the formats are exercised at
+constexpr uint32_t kGrowDeepBatch = 1024;      // node slots whose histograms a batch of a deep level holds
 constexpr uint32_t kGrowFlagLabel = 1u;        // the error word: a gradient out of range (refit.hpp kRefitFlagLabel)
 constexpr uint32_t kGrowFlagState = 2u;        // a node id or a bin outside its table (never, from sound buffers)
 constexpr uint32_t kGrowFlagEvalLabel = 4u;    // the same as kGrowFlagLabel at a held-out row
@@ -212,8 +216,9 @@ inline GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t nu
 // to out[0 .. n_sel) in ascending f.  n_sel == F writes 0 .. F - 1 and draws nothing.  Returns n_sel (0: colsample is
 // unsound, F is 0 or above kGrowMaxFeatures; nothing is written).
 uint32_t grow_pick_features(uint64_t seed, uint64_t i, uint32_t F, float colsample, uint8_t* out);
-// A Tree of the forest from n node records; throws on a record that is not a tree in allocation order.
-Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature);
+// A Tree of the forest from n node records (at most max_nodes: the stride of the call's node table); throws on a record
+// that is not a tree in allocation order.
+Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature, uint32_t max_nodes = kGrowMaxNodes);
 
 // ---- the held-out metric (OHXBoosterBoostTreesEval; design in docs/20_boost_eval.md) ----
 
@@ -320,6 +325,47 @@ GrowPlan plan_grow_weighted(uint64_t nrow, uint32_t num_feature, uint64_t ncuts,
 // blocks of grow_sse_kernel and grow_walk_sse_kernel over n rows: a row per lane, kGrowBlock lanes, grid-stride
 uint32_t plan_grow_eval_blocks(uint64_t nrow, int num_cus);
 
+// ---- the Deep call's plan ----
+
+// Node records of one round: min(2^(max_depth + 1), 2 * nrow).  A split needs weight on both sides, so every leaf holds
+// a row and a tree has at most 2 * nrow - 1 nodes; by its depth at most 2^(max_depth + 1) - 1.
+inline uint64_t grow_deep_node_stride(uint64_t nrow, int max_depth) {
+  return std::min<uint64_t>(1ull << (max_depth + 1), 2 * nrow);
+}
+// The open nodes a level can have at most: half a full last level's children, and never more than the rows.
+inline uint64_t grow_deep_max_open(uint64_t nrow, int max_depth) {
+  return std::max<uint64_t>(1, std::min<uint64_t>(1ull << (max_depth - 1), nrow));
+}
+struct GrowDeepPlan {
+  GrowPlan lds;               // plan_grow_weighted over levels 0 .. min(max_depth, 8) - 1
+  uint32_t batch = 0;         // kGrowDeepBatch
+  uint32_t hist_blocks = 0;   // grid of grow_deep_hist_kernel: kGrowBlock lanes a block, a row per lane, grid-stride
+  uint64_t scratch_bytes = 0; // Ghist and Hhist of one batch together: min(batch, max open) x F x 256 x 16; 0 at depth <= 8
+  uint64_t best_bytes = 0;    // the candidates of a level: max(max open, 2^(min(max_depth, 8) - 1)) x F x sizeof(GrowCand)
+  uint64_t node_stride = 0;   // grow_deep_node_stride
+};
+GrowDeepPlan plan_grow_deep(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus);
+
+// The child ids of a level with any number of open nodes, as one block of `width` lanes hands them out: the slots are
+// walked in chunks of `width` with a running total; a slot's `below` is the running total plus the exclusive scan of
+// its chunk's split flags, and its children are grow_child_id(next, below) and the id after it - so ids ascend in node
+// order across chunk borders.  The host's statement, scanned serially; grow_deep_split_kernel scans a chunk with ballots
+// and takes its ids from the same grow_child_id.  left[s] is written where flag[s] != 0.  Returns the splits.
+OHX_GROW_HD inline uint32_t grow_child_id(uint32_t next, uint32_t below) { return next + 2u * below; }
+inline uint32_t grow_chunked_children(const uint8_t* flag, uint32_t count, uint32_t width, uint32_t next, uint32_t* left) {
+  uint32_t running = 0;
+  for (uint32_t c0 = 0; c0 < count; c0 += width) {
+    const uint32_t nc = count - c0 < width ? count - c0 : width;
+    uint32_t scan = 0;
+    for (uint32_t i = 0; i < nc; ++i) {
+      if (flag[c0 + i]) left[c0 + i] = grow_child_id(next, running + scan);
+      scan += flag[c0 + i] ? 1u : 0u;
+    }
+    running += scan;
+  }
+  return running;
+}
+
 #ifdef __HIPCC__
 struct GrowLevelState {   // one per call, on the device
   uint32_t begin, end;    // the open nodes of the level at hand: ids [begin, end)
@@ -384,6 +430,8 @@ int launch_grow_bin(const GrowArgs& a, const GrowPlan& plan, void* stream);
 int launch_grow_tree(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
 int launch_grow_tree_weighted(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
 int launch_grow_tree_sampled(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
+// launch_grow_tree_weighted without the leaf kernel: the rows stay on their nodes after the last level's partition
+int launch_grow_levels_weighted(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
 // Enqueue grow_partition_kernel and grow_leaf_kernel alone, for the level loop as the other files instantiate it: they
 // read node records and bins, never a histogram or a weight.  Return a hipError_t.
 int launch_grow_partition(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
@@ -424,6 +472,27 @@ int launch_grow_walk_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t round,
 int launch_grow_sse_weighted(const GrowEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream);
 // Enqueues grow_walk_sse_weighted_kernel: grow_walk_sse_kernel's walk, then wsums[round + 1][set] += hq * e^2.
 int launch_grow_walk_sse_weighted(const GrowEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream);
+
+// ---- the Deep call (grow_deep.hip) ----
+
+constexpr size_t kGrowEvalNodeBytes = 16;   // an EvalNode of grow_device.hpp: a node as the held-out walk reads it
+// What the deep kernels take: the call's GrowArgs with `nodes` and `tree_nodes` at the call's first round, Ghist / Hhist
+// the scratch of one batch and `best` the candidates of a whole level, and what the deep levels add.
+struct GrowDeepArgs {
+  GrowArgs g;
+  uint32_t* pos = nullptr;         // [nrow] the node a row stands on from level 8 on
+  uint32_t node_stride = 0;        // node records of one round
+  void* eval_nodes = nullptr;      // [node_stride] EvalNodes: the tree at hand as the held-out walk reads it
+};
+// One tree of a call with max_depth > 8, round `round`: levels 0 - 7 by launch_grow_levels_weighted on the tree's own
+// records, then per deep level the batches (two memsets, the histogram kernel and split phase 0 each), split phase 1,
+// the partition, and one wait for the level word on h_state (pinned); then the leaf kernel.  The tree ends at the first
+// level without an open node.  a.g.pos and a.pos must be zero and pred the margin so far.  Returns a hipError_t.
+int launch_grow_tree_deep(const GrowDeepArgs& a, const GrowDeepPlan& plan, uint32_t round, GrowLevelState* h_state, void* stream);
+// Enqueues grow_deep_stage_kernel and grow_deep_walk_sse_kernel: eval_nodes from the records of tree `round`, then
+// launch_grow_walk_sse_weighted's walk and sums over the rows of `a`, its nodes read from HBM.  Returns a hipError_t.
+int launch_grow_walk_sse_deep(const GrowEvalArgs& a, const GrowDeepArgs& d, uint32_t blocks, uint32_t round, uint32_t set,
+                              void* stream);
 #endif  // __HIPCC__
 
 }  // namespace ohx

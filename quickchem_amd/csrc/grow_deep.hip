@@ -1,0 +1,305 @@
+// gfx950 kernels of the Deep call (grow.hpp GrowDeepArgs; design in docs/23_deep_trees.md): trees of depth 9 to 18.
+// Levels 0 - 7 are the weighted call's own (launch_grow_levels_weighted); from level 8 on a level has more open nodes
+// than LDS holds histograms for, so the histograms of a batch of kGrowDeepBatch node slots live in HBM.
+//
+//   grow_deep_widen_kernel     once per tree, after level 7: the uint16 position of a row becomes the uint32 one the
+//                              deep levels use, and the uint16 one is zeroed for the next tree.
+//   grow_deep_hist_kernel      once per batch: a lane takes a row in natural order; a row outside the batch leaves
+//                              after the one load of its position, the others make g, w, hq and q as
+//                              grow_hist_weighted_kernel does, in its order and with its flags, and add q and hq with
+//                              two no-return 64-bit integer global adds a feature.  No LDS.
+//   grow_deep_split_kernel<0>  once per batch: grow_split_columns with the fixed-point hessian policy over the batch's
+//                              histograms; best[slot][f] is indexed by the level's slot.
+//   grow_deep_split_kernel<1>  once per level, one block: the level's slots in chunks of the block's width with a
+//                              running total; a lane decides its node by grow_decide_node, a ballot scan of the chunk's
+//                              split flags plus the running total gives `below`, the children are grow_child_id.
+//   grow_deep_partition_kernel grow_partition_kernel on the uint32 positions and the call's node stride.
+//   grow_deep_leaf_kernel      grow_leaf_kernel on the same.
+//   grow_deep_stage_kernel     once per round with a held-out set: the tree's GrowNodes as 16-byte EvalNodes in HBM.
+//   grow_deep_walk_sse_kernel  grow_walk_sse_weighted_kernel with grow_walk_row reading that table; nothing in LDS but
+//                              the reduction's partial sums.
+// Only integer adds: no float atomics, no compare-and-swap loops, and the same trees and sums whatever the order of the
+// rows, the batch size or the launch shape.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "grow.hpp"
+#include "grow_device.hpp"
+#include "grow_sums_device.hpp"
+#include "walk_device.hpp"
+
+namespace ohx {
+
+namespace {
+
+static_assert(sizeof(EvalNode) == kGrowEvalNodeBytes, "the host sizes the walk's table by it");
+constexpr int kBlock = (int)kGrowBlock;
+constexpr int kWaves = kBlock / kWave;
+
+// The tree at hand as round 0 of its own table: what the shared split phases and the weighted levels index by round.
+__host__ __device__ inline GrowArgs tree_args(const GrowDeepArgs& a, uint32_t round) {
+  GrowArgs t = a.g;
+  t.nodes = a.g.nodes + (uint64_t)round * a.node_stride;
+  t.tree_nodes = a.g.tree_nodes + round;
+  return t;
+}
+
+// grid (blocks)
+__global__ __launch_bounds__(kBlock) void grow_deep_widen_kernel(GrowDeepArgs a) {
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.g.nrow; row += stride) {
+    a.pos[row] = a.g.pos[row];
+    a.g.pos[row] = 0;
+  }
+}
+
+// grid (blocks).  The batch is the level's slots [batch0, batch0 + nslots); Ghist / Hhist are [nslots][F][256].
+__global__ __launch_bounds__(kBlock) void grow_deep_hist_kernel(GrowDeepArgs d, uint32_t batch0, uint32_t nslots) {
+  const GrowArgs& a = d.g;
+  const uint32_t begin = a.state->begin, end = a.state->end;
+  const uint32_t count = end - begin;
+  if (batch0 >= count) return;
+  const uint32_t live = count - batch0 < nslots ? count - batch0 : nslots;   // (the host's count is the device's)
+  const uint32_t first = begin + batch0;
+  uint32_t flags = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
+    const uint32_t s = d.pos[row] - first;   // (a node below `first` wraps past live)
+    if (s >= live) continue;
+    const float g = a.pred[row] - a.labels[row];
+    // the gradient before the weight (a NaN fails the comparison)
+    if (!(__builtin_fabsf(g) < kRefitMaxAbsGrad)) {
+      flags |= kGrowFlagLabel;
+      continue;
+    }
+    float w;
+    unsigned long long hq;
+    if (!grow_row_weight(a.weights, row, &w, &hq)) {
+      flags |= kGrowFlagWeight;
+      continue;
+    }
+    const float gw = g * w;   // one float32 multiply (-ffp-contract=off)
+    if (!(__builtin_fabsf(gw) < kRefitMaxAbsGrad)) {
+      flags |= kGrowFlagLabel;
+      continue;
+    }
+    const unsigned long long q = (unsigned long long)(long long)__builtin_rintf(gw * kRefitGradScale);
+    if (hq == 0ull && q == 0ull) continue;   // nothing to add
+    const uint8_t* bin = a.bins + row;
+    const uint64_t base = (uint64_t)s * a.num_feature * kGrowBins;
+    for (uint32_t f = 0; f < a.num_feature; ++f) {
+      const uint64_t i = base + (uint64_t)f * kGrowBins + bin[(uint64_t)f * a.nrow];   // s < live, f < F, bin < 256
+      atomicAdd(&a.Ghist[i], q);
+      atomicAdd(&a.Hhist[i], hq);
+    }
+  }
+  if (flags) atomicOr(&a.state->error, flags);
+}
+
+// PHASE 0: grid (blocks of four waves over the batch's slots x features).  PHASE 1: one block.
+template <int PHASE>
+__global__ __launch_bounds__(kBlock) void grow_deep_split_kernel(GrowDeepArgs d, uint32_t level, uint32_t round, uint32_t batch0) {
+  const GrowArgs a = tree_args(d, round);
+  const GrowFixedHess hess{a.min_child_weight};
+  if (PHASE == 0) {
+    grow_split_columns(a, hess, level, 0, a.num_feature, GrowIdentityMap(), batch0);
+    return;
+  }
+  __shared__ uint32_t wave_splits[kWaves];
+  const uint32_t begin = a.state->begin, end = a.state->end, next = a.state->next;
+  const uint32_t count = end - begin;
+  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
+  uint32_t running = 0;   // the splits of the chunks before this one: the same in every lane
+  bool full = false;      // a child id past the round's records (never: grow_deep_node_stride)
+  for (uint32_t c0 = 0; c0 < count; c0 += kBlock) {
+    const uint32_t s = c0 + threadIdx.x;
+    const uint32_t node = begin + s;
+    GrowDecision dec;
+    if (s < count) dec = grow_decide_node<false>(a, hess, a.nodes, level, node, s, a.num_feature);
+    const bool split = s < count && dec.split;
+    // the exclusive scan of the chunk's flags: the lanes below in the wave, and the waves below in the block
+    const unsigned long long votes = __ballot(split);
+    if (lane == 0) wave_splits[wave] = (uint32_t)__popcll(votes);
+    __syncthreads();
+    uint32_t scan = (uint32_t)__popcll(votes & ((1ull << lane) - 1ull)), chunk = 0;
+#pragma unroll
+    for (int w = 0; w < kWaves; ++w) {
+      if (w < wave) scan += wave_splits[w];
+      chunk += wave_splits[w];
+    }
+    __syncthreads();   // wave_splits is written again in the next chunk
+    if (split) {
+      const uint32_t left = grow_child_id(next, running + scan);
+      if (left + 1u < d.node_stride) grow_write_split(a, hess, a.nodes, node, dec, left);
+      else full = true;
+    }
+    running += chunk;
+  }
+  if (full) atomicOr(&a.state->error, kGrowFlagState);
+  uint32_t total = next + 2u * running;
+  if (total > d.node_stride) total = next;   // (never; the flag is raised above) nothing is open: the tree ends
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    a.state->begin = next;
+    a.state->end = total;
+    a.state->next = total;
+    a.tree_nodes[0] = total;
+  }
+}
+
+// grid (blocks)
+__global__ __launch_bounds__(kBlock) void grow_deep_partition_kernel(GrowDeepArgs d, uint32_t round) {
+  const GrowArgs& a = d.g;
+  const GrowNode* nodes = a.nodes + (uint64_t)round * d.node_stride;
+  const uint32_t next = a.state->next;
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
+    const uint32_t p = d.pos[row];
+    if (p >= next || p >= d.node_stride) {
+      atomicOr(&a.state->error, kGrowFlagState);
+      continue;
+    }
+    const int32_t left = nodes[p].left;
+    if (left < 0) continue;
+    const uint32_t f = nodes[p].feature;
+    if (f >= a.num_feature) {
+      atomicOr(&a.state->error, kGrowFlagState);
+      continue;
+    }
+    const uint32_t b = a.bins[(uint64_t)f * a.nrow + row];
+    const bool go_left = b == kGrowMissingBin ? nodes[p].default_left != 0u : b <= nodes[p].cut;
+    d.pos[row] = (uint32_t)(go_left ? left : nodes[p].right);
+  }
+}
+
+// grid (blocks)
+__global__ __launch_bounds__(kBlock) void grow_deep_leaf_kernel(GrowDeepArgs d, uint32_t round) {
+  const GrowArgs& a = d.g;
+  const GrowNode* nodes = a.nodes + (uint64_t)round * d.node_stride;
+  const uint32_t next = a.state->next;
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
+    const uint32_t p = d.pos[row];
+    if (p < next && p < d.node_stride) a.pred[row] += nodes[p].value;
+    else atomicOr(&a.state->error, kGrowFlagState);
+    d.pos[row] = 0;
+  }
+}
+
+// ---- the held-out walk ----
+
+// grid (blocks).  The count is checked by the walk kernel; here it only bounds the copy.
+__global__ __launch_bounds__(kBlock) void grow_deep_stage_kernel(GrowDeepArgs d, uint32_t round) {
+  const GrowNode* nodes = d.g.nodes + (uint64_t)round * d.node_stride;
+  uint32_t count = d.g.tree_nodes[round];
+  if (count > d.node_stride) count = d.node_stride;
+  for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < count; i += gridDim.x * kBlock) static_cast<EvalNode*>(d.eval_nodes)[i] = grow_eval_node(nodes[i]);
+}
+
+// grid (blocks)
+__global__ __launch_bounds__(kBlock) void grow_deep_walk_sse_kernel(GrowEvalArgs a, const EvalNode* tree, uint32_t node_stride,
+                                                                    uint32_t round, unsigned long long* slot) {
+  const uint32_t count = a.tree_nodes[round];
+  GrowWideAcc acc;
+  uint32_t flags = 0;
+  if (count == 0 || count > node_stride) {   // (never: the split kernel writes it, and writes no record past the stride)
+    flags = kGrowFlagState;
+  } else {
+    const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+    for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
+      uint32_t leaf;
+      if (!grow_walk_row(a, tree, count, row, &leaf)) {
+        flags |= kGrowFlagState;
+        continue;
+      }
+      const float pred = a.pred[row] + tree[leaf].value;
+      a.pred[row] = pred;
+      float w;
+      unsigned long long hq;
+      if (!grow_row_weight(a.weights, row, &w, &hq)) flags |= a.weight_flag;
+      if (!grow_add_weighted_square(pred, a.labels[row], hq, &acc)) flags |= a.label_flag;
+    }
+  }
+  if (flags) atomicOr(&a.state->error, flags);
+  grow_reduce_wide(acc, slot, nullptr);
+}
+
+bool deep_args_sound(const GrowDeepArgs& d, const GrowDeepPlan& plan) {
+  const GrowArgs& a = d.g;
+  return a.nrow != 0 && a.nrow <= kRefitMaxRows && a.num_feature != 0 && a.num_feature <= kGrowMaxFeatures &&
+         a.max_depth > kGrowMaxDepth && a.max_depth <= kGrowDeepMaxDepth && a.min_child_weight >= 0.0 && d.pos != nullptr &&
+         d.node_stride != 0 && (uint64_t)d.node_stride == grow_deep_node_stride(a.nrow, a.max_depth) &&
+         plan.node_stride == d.node_stride && plan.batch != 0 && plan.hist_blocks != 0 && plan.lds.row_blocks != 0 &&
+         plan.lds.levels.size() == (size_t)kGrowMaxDepth &&
+         plan.scratch_bytes == std::min<uint64_t>(plan.batch, grow_deep_max_open(a.nrow, a.max_depth)) * a.num_feature * kGrowBins * 16;
+}
+
+}  // namespace
+
+int launch_grow_tree_deep(const GrowDeepArgs& d, const GrowDeepPlan& plan, uint32_t round, GrowLevelState* h_state, void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (!deep_args_sound(d, plan) || h_state == nullptr) return hipErrorInvalidValue;
+  // levels 0 - 7: the weighted call's kernels on the tree's own records (a tree of 8 levels has at most 511 of them, and
+  // no more than 2 * nrow - 1: within the stride either way)
+  GrowArgs top = tree_args(d, round);
+  top.max_depth = kGrowMaxDepth;
+  hipError_t e = (hipError_t)launch_grow_levels_weighted(top, plan.lds, plan.lds, 0, stream);
+  if (e != hipSuccess) return e;
+  // the level word after phase 1 of level d - 1: the open nodes of level d
+  auto level_word = [&]() {
+    hipError_t r = hipMemcpyAsync(h_state, d.g.state, sizeof(GrowLevelState), hipMemcpyDeviceToHost, stream);
+    return r != hipSuccess ? r : hipStreamSynchronize(stream);
+  };
+  if ((e = level_word()) != hipSuccess) return e;
+  uint32_t count = h_state->end - h_state->begin;
+  if (count == 0 || h_state->error != 0) return (hipError_t)launch_grow_leaf(top, plan.lds, 0, stream);
+  const dim3 rows(plan.lds.row_blocks), block(kBlock);
+  hipLaunchKernelGGL(grow_deep_widen_kernel, rows, block, 0, stream, d);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  const uint64_t max_open = grow_deep_max_open(d.g.nrow, d.g.max_depth);
+  for (uint32_t level = kGrowMaxDepth; level < (uint32_t)d.g.max_depth && count != 0 && h_state->error == 0; ++level) {
+    if (count > max_open) return hipErrorInvalidValue;   // (never: `best` holds max_open slots)
+    for (uint32_t batch0 = 0; batch0 < count; batch0 += plan.batch) {
+      const uint32_t nslots = std::min(plan.batch, count - batch0);
+      const size_t bytes = (size_t)nslots * d.g.num_feature * kGrowBins * sizeof(unsigned long long);
+      if ((e = hipMemsetAsync(d.g.Ghist, 0, bytes, stream)) != hipSuccess) return e;
+      if ((e = hipMemsetAsync(d.g.Hhist, 0, bytes, stream)) != hipSuccess) return e;
+      hipLaunchKernelGGL(grow_deep_hist_kernel, dim3(plan.hist_blocks), block, 0, stream, d, batch0, nslots);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+      const uint32_t waves = nslots * d.g.num_feature;
+      hipLaunchKernelGGL(grow_deep_split_kernel<0>, dim3((waves + kWaves - 1) / kWaves), block, 0, stream, d, level, round, batch0);
+      if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(grow_deep_split_kernel<1>, dim3(1), block, 0, stream, d, level, round, 0u);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(grow_deep_partition_kernel, rows, block, 0, stream, d, round);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    if (level + 1 == (uint32_t)d.g.max_depth) break;   // the last level: nothing follows that needs the count
+    if ((e = level_word()) != hipSuccess) return e;
+    count = h_state->end - h_state->begin;
+  }
+  hipLaunchKernelGGL(grow_deep_leaf_kernel, rows, block, 0, stream, d, round);
+  return hipGetLastError();
+}
+
+int launch_grow_walk_sse_deep(const GrowEvalArgs& a, const GrowDeepArgs& d, uint32_t blocks, uint32_t round, uint32_t set,
+                              void* stream_) {
+  hipStream_t stream = static_cast<hipStream_t>(stream_);
+  if (a.nrow == 0 || a.nrow > kRefitMaxRows || blocks == 0 || set > 1 || a.pred == nullptr || a.labels == nullptr ||
+      a.wsums == nullptr || a.state == nullptr || a.bins == nullptr || a.tree_nodes == nullptr || d.eval_nodes == nullptr ||
+      d.node_stride == 0 || a.num_feature == 0 || a.num_feature > kGrowMaxFeatures || a.max_depth < 1 ||
+      a.max_depth > kGrowDeepMaxDepth ||
+      !((a.label_flag == kGrowFlagLabel && a.weight_flag == kGrowFlagWeight) ||
+        (a.label_flag == kGrowFlagEvalLabel && a.weight_flag == kGrowFlagEvalWeight)))
+    return hipErrorInvalidValue;
+  const uint32_t stage_blocks = std::min<uint32_t>(blocks, (d.node_stride + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(grow_deep_stage_kernel, dim3(stage_blocks), dim3(kBlock), 0, stream, d, round);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(grow_deep_walk_sse_kernel, dim3(blocks), dim3(kBlock), 0, stream, a, (const EvalNode*)d.eval_nodes,
+                     d.node_stride, round, a.wsums + grow_wide_index(round + 1, set));
+  return hipGetLastError();
+}
+
+}  // namespace ohx

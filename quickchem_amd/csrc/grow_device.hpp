@@ -70,20 +70,22 @@ __device__ inline void grow_write_leaf(const GrowArgs& a, const Hess& hess, Grow
 
 // Phase 0: a wave per (slot, column); blocks of kGrowBlock lanes over slots x ncols - integer prefix sums across the 256
 // bins, the shared gain in double, and a butterfly reduction by the total order of grow_better.  The best candidate of
-// the column's feature goes to best[slot][column]; the wave of column 0 leaves the root's sums at level 0.
+// the column's feature goes to best[slot][column]; the wave of column 0 leaves the root's sums at level 0.  The
+// histograms hold the slots from slot0 on (a batch of the level: grow_deep.hip); `best` is indexed by the level's slot.
 template <class Hess, class Map>
 __device__ inline void grow_split_columns(const GrowArgs& a, const Hess& hess, uint32_t level, uint32_t round, uint32_t ncols,
-                                          Map map) {
+                                          Map map, uint32_t slot0 = 0) {
   uint32_t begin, end, next;
   grow_level_range(a, level, &begin, &end, &next);
   const uint32_t count = end - begin;
   GrowNode* nodes = a.nodes + (uint64_t)round * kGrowMaxNodes;
   const int lane = threadIdx.x & (kWave - 1);
   const uint32_t w = blockIdx.x * (kGrowBlock / kWave) + threadIdx.x / kWave;
-  const uint32_t slot = w / ncols, k = w % ncols;
+  const uint32_t local = w / ncols, k = w % ncols;
+  const uint32_t slot = slot0 + local;
   if (slot >= count) return;
   const uint32_t f = map(k);
-  const uint64_t at = ((uint64_t)slot * ncols + k) * kGrowBins + 4u * lane;
+  const uint64_t at = ((uint64_t)local * ncols + k) * kGrowBins + 4u * lane;
   int64_t g4[4];
   uint64_t h4[4];
   int64_t gs = 0;
@@ -125,8 +127,50 @@ __device__ inline void grow_split_columns(const GrowArgs& a, const Hess& hess, u
   if (lane == 0) a.best[(uint64_t)slot * ncols + k] = c;
 }
 
+// The decision of one open node, written once for both phase-1 kernels: its sums, the best of its columns
+// (best[slot][0 .. ncols), ascending, replaced by a strictly better one only), and whether it splits.  At level 0 the
+// root's record is written as a leaf first.  BAG: a root that holds no weight raises kGrowFlagBag.
+struct GrowDecision {
+  GrowCand best;
+  int64_t Gp = 0;
+  uint64_t Hp = 0;
+  bool split = false;
+};
+template <bool BAG, class Hess>
+__device__ inline GrowDecision grow_decide_node(const GrowArgs& a, const Hess& hess, GrowNode* nodes, uint32_t level,
+                                                uint32_t node, uint32_t slot, uint32_t ncols) {
+  GrowDecision d;
+  d.Gp = nodes[node].G;
+  d.Hp = nodes[node].H;
+  if (level == 0) {
+    grow_write_leaf(a, hess, nodes, 0, d.Gp, d.Hp, -1);
+    if (BAG && d.Hp == 0) atomicOr(&a.state->error, kGrowFlagBag);
+  }
+  for (uint32_t k = 0; k < ncols; ++k) {
+    const GrowCand c = a.best[(uint64_t)slot * ncols + k];
+    if (grow_better(c, d.best)) d.best = c;
+  }
+  d.split = d.best.valid && d.best.loss_chg > (double)a.gamma && hess.evaluates(d.Hp);
+  return d;
+}
+// The records of a node that splits into `left` and left + 1: its own fields and both children as leaves.
+template <class Hess>
+__device__ inline void grow_write_split(const GrowArgs& a, const Hess& hess, GrowNode* nodes, uint32_t node,
+                                        const GrowDecision& d, uint32_t left) {
+  const uint32_t f = d.best.key >> 9, j = (d.best.key >> 1) & 255u, dl = d.best.key & 1u;
+  nodes[node].left = (int32_t)left;
+  nodes[node].right = (int32_t)left + 1;
+  nodes[node].feature = f;
+  nodes[node].cut = j;
+  nodes[node].default_left = dl;
+  nodes[node].value = a.cuts[a.cut_ptr[f] + j];
+  nodes[node].loss_chg = (float)d.best.loss_chg;
+  grow_write_leaf(a, hess, nodes, left, d.best.GL, d.best.HL, (int32_t)(node | 0x80000000u));
+  grow_write_leaf(a, hess, nodes, left + 1, d.Gp - d.best.GL, d.Hp - d.best.HL, (int32_t)node);
+}
+
 // Phase 1: one block, a lane per open node takes the best of its columns, the splitting nodes get their child ids in
-// ascending node order, the records are written.  BAG: a root that holds no weight raises kGrowFlagBag.
+// ascending node order, the records are written.
 template <bool BAG, class Hess>
 __device__ inline void grow_split_nodes(const GrowArgs& a, const Hess& hess, uint32_t level, uint32_t round, uint32_t ncols) {
   __shared__ uint32_t splits[kGrowMaxNodes / 2];
@@ -137,22 +181,9 @@ __device__ inline void grow_split_nodes(const GrowArgs& a, const Hess& hess, uin
   const uint32_t s = threadIdx.x;
   const bool active = s < count && s < kGrowMaxNodes / 2;
   const uint32_t node = begin + s;
-  GrowCand best;
-  int64_t Gp = 0;
-  uint64_t Hp = 0;
-  if (active) {
-    Gp = nodes[node].G;
-    Hp = nodes[node].H;
-    if (level == 0) {
-      grow_write_leaf(a, hess, nodes, 0, Gp, Hp, -1);
-      if (BAG && Hp == 0) atomicOr(&a.state->error, kGrowFlagBag);
-    }
-    for (uint32_t k = 0; k < ncols; ++k) {
-      const GrowCand c = a.best[(uint64_t)s * ncols + k];
-      if (grow_better(c, best)) best = c;
-    }
-  }
-  const bool split = active && best.valid && best.loss_chg > (double)a.gamma && hess.evaluates(Hp);
+  GrowDecision d;
+  if (active) d = grow_decide_node<BAG>(a, hess, nodes, level, node, s, ncols);
+  const bool split = active && d.split;
   if (s < kGrowMaxNodes / 2) splits[s] = split ? 1u : 0u;
   __syncthreads();
   uint32_t below = 0, total = 0;
@@ -165,17 +196,7 @@ __device__ inline void grow_split_nodes(const GrowArgs& a, const Hess& hess, uin
     if (s == 0) atomicOr(&a.state->error, kGrowFlagState);
     total = 0;
   } else if (split) {
-    const uint32_t f = best.key >> 9, j = (best.key >> 1) & 255u, dl = best.key & 1u;
-    const uint32_t left = next + 2u * below;
-    nodes[node].left = (int32_t)left;
-    nodes[node].right = (int32_t)left + 1;
-    nodes[node].feature = f;
-    nodes[node].cut = j;
-    nodes[node].default_left = dl;
-    nodes[node].value = a.cuts[a.cut_ptr[f] + j];
-    nodes[node].loss_chg = (float)best.loss_chg;
-    grow_write_leaf(a, hess, nodes, left, best.GL, best.HL, (int32_t)(node | 0x80000000u));
-    grow_write_leaf(a, hess, nodes, left + 1, Gp - best.GL, Hp - best.HL, (int32_t)node);
+    grow_write_split(a, hess, nodes, node, d, next + 2u * below);
   }
   if (s == 0) {
     a.state->begin = next;
@@ -194,6 +215,14 @@ struct EvalNode {
   float value;           // the leaf value
 };
 static_assert(sizeof(EvalNode) == 16, "16 bytes a node");
+__device__ inline EvalNode grow_eval_node(const GrowNode& n) {
+  EvalNode e;
+  e.left = n.left;
+  e.right = n.right;
+  e.fcd = (n.feature << 9) | ((n.cut & 255u) << 1) | (n.default_left != 0u ? 1u : 0u);
+  e.value = n.value;
+  return e;
+}
 
 // The block stages the records of tree `round` in tree[kGrowMaxNodes] (LDS) and meets at a barrier.  Returns the
 // tree's nodes, or 0 where the count is unsound: the error word is raised, no barrier is met, and the block ends.
@@ -204,14 +233,7 @@ __device__ inline uint32_t grow_stage_tree(const GrowEvalArgs& a, uint32_t round
     return 0;
   }
   const GrowNode* nodes = a.nodes + (uint64_t)round * kGrowMaxNodes;
-  for (uint32_t i = threadIdx.x; i < count; i += kGrowBlock) {
-    EvalNode e;
-    e.left = nodes[i].left;
-    e.right = nodes[i].right;
-    e.fcd = (nodes[i].feature << 9) | ((nodes[i].cut & 255u) << 1) | (nodes[i].default_left != 0u ? 1u : 0u);
-    e.value = nodes[i].value;
-    tree[i] = e;
-  }
+  for (uint32_t i = threadIdx.x; i < count; i += kGrowBlock) tree[i] = grow_eval_node(nodes[i]);
   __syncthreads();
   return count;
 }
@@ -241,11 +263,12 @@ __device__ inline bool grow_walk_row(const GrowEvalArgs& a, const EvalNode* tree
 // file instantiates it with its own three launches (hist takes the level's plan and the level; split0 the blocks and the
 // level; split1 the level) over `ncols` histogram columns of pair_bytes a (node, column) pair in LDS.  max_trips bounds
 // the trips of a histogram block over the rows where its LDS hessian is a 32-bit count (grow_hist_kernel:
-// kGrowMaxTrips); 0 where it is a 64-bit sum, which 2^31 rows cannot overflow.
+// kGrowMaxTrips); 0 where it is a 64-bit sum, which 2^31 rows cannot overflow.  leaf == false leaves the rows standing on
+// their nodes after the last level's partition: the caller goes on from there (the deep levels of grow_deep.hip).
 template <class Hist, class Split0, class Split1>
 inline hipError_t grow_launch_tree(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round,
                                    hipStream_t stream, uint32_t ncols, uint32_t pair_bytes, uint64_t max_trips, Hist hist,
-                                   Split0 split0, Split1 split1) {
+                                   Split0 split0, Split1 split1, bool leaf = true) {
   if (a.nrow == 0 || a.nrow > kRefitMaxRows || a.num_feature == 0 || a.num_feature > kGrowMaxFeatures || a.max_depth < 1 ||
       a.max_depth > kGrowMaxDepth || levels.levels.size() != (size_t)a.max_depth || plan.row_blocks == 0 || ncols == 0 ||
       ncols > a.num_feature)
@@ -272,7 +295,7 @@ inline hipError_t grow_launch_tree(const GrowArgs& a, const GrowPlan& plan, cons
     if ((e = hipGetLastError()) != hipSuccess) return e;
     if ((e = (hipError_t)launch_grow_partition(a, plan, round, stream)) != hipSuccess) return e;
   }
-  return (hipError_t)launch_grow_leaf(a, plan, round, stream);
+  return leaf ? (hipError_t)launch_grow_leaf(a, plan, round, stream) : hipSuccess;
 }
 
 }  // namespace ohx

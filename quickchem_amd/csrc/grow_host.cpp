@@ -314,3 +314,46 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_plan_sampled(uint
     return -1;
   }
 }
+
+// ---- the Deep call (OHXBoosterBoostTreesDeep) ----
+
+// node slots whose histograms a batch of a deep level holds
+extern "C" __attribute__((visibility("default"))) uint32_t ohx_grow_deep_batch() { return kGrowDeepBatch; }
+
+// plan_grow_deep.  info and levels as ohx_grow_plan_weighted's, for the min(max_depth, 8) levels kept in LDS; deep: [0]
+// batch, [1] blocks of the global histogram kernel, [2] rows such a block takes per trip, [3] bytes of a batch's
+// histograms, [4] bytes of a level's candidates, [5] node records of one round
+extern "C" __attribute__((visibility("default"))) int ohx_grow_plan_deep(uint64_t nrow, uint32_t num_feature, uint64_t ncuts,
+                                                                        int max_depth, int num_cus, uint64_t info[8],
+                                                                        uint64_t* levels, uint64_t deep[6]) {
+  try {
+    if (max_depth < 1 || max_depth > kGrowDeepMaxDepth) throw OhxError("ohx_grow_plan_deep: max_depth must be in 1..18");
+    if (nrow == 0) throw OhxError("ohx_grow_plan_deep: no rows");
+    const GrowDeepPlan p = plan_grow_deep(nrow, num_feature, ncuts, max_depth, num_cus);
+    write_plan(p.lds, (uint64_t)num_feature * nrow, kGrowWeightedPairBytes, info, levels);
+    deep[0] = p.batch;
+    deep[1] = p.hist_blocks;
+    deep[2] = kGrowBlock;
+    deep[3] = p.scratch_bytes;
+    deep[4] = p.best_bytes;
+    deep[5] = p.node_stride;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// grow_chunked_children: the child ids a block of `width` lanes hands the `count` open nodes of a level whose split
+// flags are flag[]; left[s] is written where flag[s] != 0; *splits: their number
+extern "C" __attribute__((visibility("default"))) int ohx_grow_deep_children(const uint8_t* flag, uint32_t count, uint32_t width,
+                                                                            uint32_t next, uint32_t* left, uint32_t* splits) {
+  try {
+    if (width == 0) throw OhxError("ohx_grow_deep_children: width must be >= 1");
+    *splits = grow_chunked_children(flag, count, width, next, left);
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}

@@ -10,6 +10,7 @@
 //   grow_sse_weighted_kernel       grow_sse_kernel with hq * e^2 in three 64-bit registers a lane; the launch for t = 0
 //                                  also checks the weights and sums W.
 //   grow_walk_sse_weighted_kernel  grow_walk_sse_kernel's walk, then the same sums.
+// A row's weight, the three-part sums and their reduction are grow_sums_device.hpp's (grow_deep.hip walks with them too).
 // The partition and leaf kernels read no weight and are grow.hip's own (launch_grow_partition, launch_grow_leaf).
 // Only integer adds: no float atomics, no compare-and-swap loops, and the same trees and sums whatever the order of the
 // rows or the launch shape.
@@ -19,6 +20,7 @@
 
 #include "grow.hpp"
 #include "grow_device.hpp"
+#include "grow_sums_device.hpp"
 #include "walk_device.hpp"
 
 namespace ohx {
@@ -27,19 +29,6 @@ namespace {
 
 constexpr int kBlock = (int)kGrowBlock;
 constexpr int kHistBlock = (int)kGrowHistBlock;
-constexpr int kWaves = kBlock / kWave;
-constexpr unsigned long long kLow32 = 0xFFFFFFFFull;
-
-// a row's weight and its fixed-point hessian; false where the weight is out of range
-__device__ inline bool row_weight(const float* weights, uint64_t row, float* w, unsigned long long* hq) {
-  *w = weights != nullptr ? weights[row] : 1.0f;
-  if (!grow_weight_sound(*w)) {
-    *hq = 0ull;
-    return false;
-  }
-  *hq = (unsigned long long)__builtin_rintf(*w * kRefitGradScale);   // < 2^32
-  return true;
-}
 
 // grid (blocks over the rows, node groups x feature groups); dynamic LDS: node_group x feat_group x 256 x (8 + 8)
 __global__ __launch_bounds__(kHistBlock) void grow_hist_weighted_kernel(GrowArgs a, uint32_t level, uint32_t node_group,
@@ -72,7 +61,7 @@ __global__ __launch_bounds__(kHistBlock) void grow_hist_weighted_kernel(GrowArgs
     }
     float w;
     unsigned long long hq;
-    if (!row_weight(a.weights, row, &w, &hq)) {
+    if (!grow_row_weight(a.weights, row, &w, &hq)) {
       flags |= kGrowFlagWeight;
       continue;
     }
@@ -118,74 +107,22 @@ __global__ __launch_bounds__(kBlock) void grow_split_weighted_kernel(GrowArgs a,
 
 // ---- the metric ----
 
-// a lane's sums: S in three parts, and W
-struct WideAcc {
-  unsigned long long p2 = 0, p1 = 0, p0 = 0, w = 0;
-};
-
-// one row's hq * e^2 into the lane's accumulators; false where the residual is out of range
-__device__ inline bool add_weighted_square(float pred, float label, unsigned long long hq, WideAcc* acc) {
-  const float g = pred - label;
-  // (a NaN fails the comparison)
-  if (!(__builtin_fabsf(g) < kRefitMaxAbsGrad)) return false;
-  const long long e = (long long)__builtin_rintf(g * kRefitGradScale);
-  const unsigned long long m = (unsigned long long)(e < 0 ? -e : e);   // <= 2^32 - 256
-  const unsigned long long sq = m * m;
-  const unsigned long long ha = hq * (sq >> 32), hb = hq * (sq & kLow32);   // hq, a, b < 2^32: neither product overflows
-  acc->p2 += ha >> 32;
-  acc->p1 += (ha & kLow32) + (hb >> 32);
-  acc->p0 += hb & kLow32;
-  return true;
-}
-
-// the block's sums leave it with one set of global adds: p2, p1, p0 to slot, and W to wslot where there is one
-__device__ inline void reduce_and_add(WideAcc acc, unsigned long long* slot, unsigned long long* wslot) {
-  __shared__ unsigned long long part[kWaves][4];
-#pragma unroll
-  for (int d = kWave / 2; d >= 1; d >>= 1) {
-    acc.p2 += __shfl_xor(acc.p2, d, kWave);
-    acc.p1 += __shfl_xor(acc.p1, d, kWave);
-    acc.p0 += __shfl_xor(acc.p0, d, kWave);
-    acc.w += __shfl_xor(acc.w, d, kWave);
-  }
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  if (lane == 0) {
-    part[wave][0] = acc.p2;
-    part[wave][1] = acc.p1;
-    part[wave][2] = acc.p0;
-    part[wave][3] = acc.w;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    unsigned long long t[4] = {0, 0, 0, 0};
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-#pragma unroll
-      for (int k = 0; k < 4; ++k) t[k] += part[w][k];
-    }
-    atomicAdd(&slot[0], t[0]);
-    atomicAdd(&slot[1], t[1]);
-    atomicAdd(&slot[2], t[2]);
-    if (wslot != nullptr) atomicAdd(wslot, t[3]);
-  }
-}
-
 // grid (blocks).  wslot: the set's W at t = 0, else nullptr
 __global__ __launch_bounds__(kBlock) void grow_sse_weighted_kernel(GrowEvalArgs a, unsigned long long* slot,
                                                                    unsigned long long* wslot) {
-  WideAcc acc;
+  GrowWideAcc acc;
   uint32_t flags = 0;
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
     float w;
     unsigned long long hq;
-    const bool sound = row_weight(a.weights, row, &w, &hq);
-    if (!add_weighted_square(a.pred[row], a.labels[row], hq, &acc)) flags |= a.label_flag;
+    const bool sound = grow_row_weight(a.weights, row, &w, &hq);
+    if (!grow_add_weighted_square(a.pred[row], a.labels[row], hq, &acc)) flags |= a.label_flag;
     if (!sound) flags |= a.weight_flag;
     acc.w += hq;
   }
   if (flags) atomicOr(&a.state->error, flags);
-  reduce_and_add(acc, slot, wslot);
+  grow_reduce_wide(acc, slot, wslot);
 }
 
 // grid (blocks)
@@ -193,7 +130,7 @@ __global__ __launch_bounds__(kBlock) void grow_walk_sse_weighted_kernel(GrowEval
   __shared__ EvalNode tree[kGrowMaxNodes];
   const uint32_t count = grow_stage_tree(a, round, tree);
   if (count == 0) return;
-  WideAcc acc;
+  GrowWideAcc acc;
   uint32_t flags = 0;
   const uint64_t stride = (uint64_t)gridDim.x * kBlock;
   for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
@@ -206,11 +143,11 @@ __global__ __launch_bounds__(kBlock) void grow_walk_sse_weighted_kernel(GrowEval
     a.pred[row] = pred;
     float w;
     unsigned long long hq;
-    if (!row_weight(a.weights, row, &w, &hq)) flags |= a.weight_flag;
-    if (!add_weighted_square(pred, a.labels[row], hq, &acc)) flags |= a.label_flag;
+    if (!grow_row_weight(a.weights, row, &w, &hq)) flags |= a.weight_flag;
+    if (!grow_add_weighted_square(pred, a.labels[row], hq, &acc)) flags |= a.label_flag;
   }
   if (flags) atomicOr(&a.state->error, flags);
-  reduce_and_add(acc, slot, nullptr);
+  grow_reduce_wide(acc, slot, nullptr);
 }
 
 bool eval_args_sound(const GrowEvalArgs& a, uint32_t blocks, uint32_t set) {
@@ -226,8 +163,10 @@ int grow_lds_limits_weighted() {
   return raise_lds_limit(grow_hist_weighted_kernel, kGrowWeightedMaxPairs * kGrowWeightedPairBytes);
 }
 
-int launch_grow_tree_weighted(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+namespace {
+
+hipError_t weighted_levels(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, hipStream_t stream,
+                           bool leaf) {
   if (!(a.min_child_weight >= 0.0)) return hipErrorInvalidValue;
   return grow_launch_tree(
       a, plan, levels, round, stream, a.num_feature, kGrowWeightedPairBytes, 0,
@@ -238,7 +177,17 @@ int launch_grow_tree_weighted(const GrowArgs& a, const GrowPlan& plan, const Gro
       [&](uint32_t blocks, uint32_t d) {
         hipLaunchKernelGGL(grow_split_weighted_kernel<0>, dim3(blocks), dim3(kBlock), 0, stream, a, d, round);
       },
-      [&](uint32_t d) { hipLaunchKernelGGL(grow_split_weighted_kernel<1>, dim3(1), dim3(kBlock), 0, stream, a, d, round); });
+      [&](uint32_t d) { hipLaunchKernelGGL(grow_split_weighted_kernel<1>, dim3(1), dim3(kBlock), 0, stream, a, d, round); }, leaf);
+}
+
+}  // namespace
+
+int launch_grow_tree_weighted(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream) {
+  return weighted_levels(a, plan, levels, round, static_cast<hipStream_t>(stream), true);
+}
+
+int launch_grow_levels_weighted(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream) {
+  return weighted_levels(a, plan, levels, round, static_cast<hipStream_t>(stream), false);
 }
 
 int launch_grow_sse_weighted(const GrowEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream_) {

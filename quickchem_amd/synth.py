@@ -117,6 +117,12 @@ def _load():
         lib.ohx_grow_features.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
         lib.ohx_grow_plan_sampled.argtypes = [C.c_uint64, C.c_uint32, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
                                               C.c_void_p]
+        lib.ohx_grow_deep_batch.argtypes = []
+        lib.ohx_grow_deep_batch.restype = C.c_uint32
+        lib.ohx_grow_plan_deep.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64),
+                                           C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.ohx_grow_deep_children.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
+                                               C.POINTER(C.c_uint32)]
         lib.ohx_cuts_select.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int, C.c_uint64, C.c_void_p,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_cuts_keys.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -544,6 +550,39 @@ def grow_plan_weighted(nrow: int, num_feature: int = NFEAT, ncuts: int = 0, max_
             "bins_bytes": int(info[3]), "hist_bytes": int(info[4]), "hist_block_rows": int(info[5]),
             "max_pairs": int(info[6]), "pair_bytes": int(info[7]),
             "levels": [dict(zip(names, (int(v) for v in row))) for row in lev]}
+
+
+def grow_deep_batch() -> int:
+    """csrc/grow.hpp kGrowDeepBatch: the node slots whose histograms a batch of a deep level holds."""
+    return int(_load().ohx_grow_deep_batch())
+
+
+def grow_plan_deep(nrow: int, num_feature: int = NFEAT, ncuts: int = 0, max_depth: int = 12, num_cus: int = 256):
+    """csrc/grow.hpp plan_grow_deep -> the dict of grow_plan_weighted over the min(max_depth, 8) levels kept in LDS, and
+    for the levels from 8 on: batch, deep_hist_blocks, deep_block_rows, scratch_bytes (a batch's histograms; 0 up to
+    depth 8), best_bytes (a level's candidates) and node_stride (node records of one round)."""
+    info = (C.c_uint64 * 8)()
+    deep = (C.c_uint64 * 6)()
+    lev = np.zeros((max(min(max_depth, 8), 1), 7), dtype=np.uint64)
+    _check(_load().ohx_grow_plan_deep(nrow, num_feature, ncuts, max_depth, num_cus, info, lev.ctypes.data, deep))
+    names = ("slots", "node_group", "feat_group", "node_groups", "feat_groups", "hist_blocks", "lds_bytes")
+    return {"row_blocks": int(info[0]), "block_rows": int(info[1]), "bin_lds_bytes": int(info[2]),
+            "bins_bytes": int(info[3]), "hist_bytes": int(info[4]), "hist_block_rows": int(info[5]),
+            "max_pairs": int(info[6]), "pair_bytes": int(info[7]),
+            "levels": [dict(zip(names, (int(v) for v in row))) for row in lev],
+            "batch": int(deep[0]), "deep_hist_blocks": int(deep[1]), "deep_block_rows": int(deep[2]),
+            "scratch_bytes": int(deep[3]), "best_bytes": int(deep[4]), "node_stride": int(deep[5])}
+
+
+def grow_deep_children(flags, width: int, next_id: int):
+    """csrc/grow.hpp grow_chunked_children: the left-child ids a block of `width` lanes hands the open nodes of a level
+    with these split flags, walking them in chunks with a running total -> (left uint32 [count], 0 where a node does
+    not split; the number of splits)."""
+    f = np.ascontiguousarray(flags, dtype=np.uint8)
+    left = np.zeros(max(f.size, 1), dtype=np.uint32)
+    n = C.c_uint32()
+    _check(_load().ohx_grow_deep_children(f.ctypes.data, f.size, width, next_id, left.ctypes.data, C.byref(n)))
+    return left[:f.size], int(n.value)
 
 
 def boost_weighted_rmse(p2: int, p1: int, p0: int, W: int) -> float:

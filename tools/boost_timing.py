@@ -27,7 +27,11 @@ min_child_weight 1; the timings stand under the same keys, so three runs that di
 
 `--subsample S` and / or `--colsample C` time OHXBoosterBoostTreesSampledDevice (docs/22_sampling.md) in the same place,
 with `--seed` and the weights `--weights` names (none: a NULL pointer); the plan written is the one over the n_sel features
-a tree sees.  `--subsample 1 --colsample 1` is the sampled entry point on the weighted path."""
+a tree sees.  `--subsample 1 --colsample 1` is the sampled entry point on the weighted path.
+
+`--deep` times OHXBoosterBoostTreesDeepDevice (docs/23_deep_trees.md) in the same place, with any `--max-depth` up to 18
+and the weights `--weights` names (none: a NULL pointer); the plan written is plan_grow_deep's.  `--deep-only` skips the
+first-call timing and the refit, for a run under a kernel trace or a quick look at one depth."""
 from __future__ import annotations
 
 import argparse
@@ -132,6 +136,8 @@ def main():
     ap.add_argument("--subsample", type=float, default=None, help="time OHXBoosterBoostTreesSampledDevice with this fraction of the rows a tree")
     ap.add_argument("--colsample", type=float, default=None, help="... and this fraction of the features a tree (colsample_bytree)")
     ap.add_argument("--seed", type=int, default=0, help="the seed of the sampled call's draws")
+    ap.add_argument("--deep", action="store_true", help="time OHXBoosterBoostTreesDeepDevice: --max-depth up to 18")
+    ap.add_argument("--deep-only", action="store_true", help="with --deep: one call a round count on a fresh booster, no refit")
     args = ap.parse_args()
     sampled = args.subsample is not None or args.colsample is not None
     if sampled:
@@ -139,6 +145,8 @@ def main():
         args.colsample = 1.0 if args.colsample is None else args.colsample
     if sampled and args.holdout:
         ap.error("--subsample / --colsample time the call without a held-out set: leave --holdout out")
+    if args.deep and (sampled or args.holdout):
+        ap.error("--deep times the Deep call alone: leave --subsample / --colsample / --holdout out")
     if args.weights != "none" and args.holdout:
         ap.error("--weights times the call without a held-out set: leave --holdout out")
     assert torch.cuda.is_available(), "boost_timing needs the MI355X"
@@ -196,6 +204,9 @@ def main():
     if sampled:
         res["plan"] = synth.grow_plan_sampled(n, F, args.colsample, ncuts, args.max_depth, cus)
         res["sampling"] = {"subsample": args.subsample, "colsample_bytree": args.colsample, "seed": args.seed}
+    elif args.deep:
+        res["plan"] = synth.grow_plan_deep(n, F, ncuts, args.max_depth, cus)
+        res["deep"] = True
     else:
         res["plan"] = (synth.grow_plan if args.weights == "none" else synth.grow_plan_weighted)(n, F, ncuts, args.max_depth, cus)
     print("cuts", json.dumps({k: v for k, v in res.items() if k.startswith("cuts_") and not k.endswith("plan")}), flush=True)
@@ -232,6 +243,12 @@ def main():
                                              seed=args.seed, stream=stream)
             nodes = r["nodes_added"]
             last.update(rounds=rounds, train_rmse=r["train_rmse"].tolist())
+        elif args.deep:
+            r = b.boost_trees_deep_device(d, labels.data_ptr(), n, cuts, weights_ptr=weights.data_ptr() if weights is not None else 0,
+                                          rounds=rounds, max_depth=args.max_depth, eta=args.eta, reg_lambda=args.reg_lambda,
+                                          min_child_weight=1.0, stream=stream)
+            nodes = r["nodes_added"]
+            last.update(rounds=rounds, train_rmse=r["train_rmse"].tolist())
         elif weights is None:
             nodes = b.boost_trees_device(d, labels.data_ptr(), n, cuts, rounds=rounds, max_depth=args.max_depth, eta=args.eta,
                                          reg_lambda=args.reg_lambda, stream=stream)
@@ -253,6 +270,9 @@ def main():
             dt, nodes = boost(b, rounds)
             first.append(dt)
             b.free()
+            if args.deep_only:
+                again.append(dt)
+                continue
             # a call that finds its buffers: the second on one booster, continuing from the first
             b = capi.Booster(model_buffer=model.image)
             boost(b, rounds)
@@ -268,7 +288,7 @@ def main():
         per_round = (res[f"rounds_{args.rounds}"]["median_s"] - res["rounds_1"]["median_s"]) / (args.rounds - 1)
         res["per_round_s"] = per_round
         res["one_off_s"] = res["rounds_1"]["median_s"] - per_round
-    if not args.skip_rmse and not args.holdout:
+    if not args.skip_rmse and not args.holdout and not args.deep_only:
         b = capi.Booster(model_buffer=model.image)
         res["rmse_before"] = rmse(b)
         b.refit_leaves_device(d, labels.data_ptr(), n, eta=1.0, reg_lambda=1.0, stream=stream)
