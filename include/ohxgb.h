@@ -774,6 +774,7 @@ int OHXBoosterBoostTreesSampledDevice(BoosterHandle handle, DMatrixHandle dmat, 
  * on rows that stop splitting at level 12 enqueues no empty level.  Levels below 7 read nothing back.  The device form
  * therefore waits for `stream` inside the call.
  * Row and column subsampling are not offered at these depths: there is no Deep form of the Sampled call.
+ * (OHXBoosterBoostTreesDeepSampled, below, has since become that form; this call still takes neither fraction.)
  * Refused, with the forest and every output untouched: everything OHXBoosterBoostTreesWeighted refuses, in the same
  * order, the max_depth message reading "max_depth must be in 1..18"; a node table or a scratch buffer that cannot be
  * allocated is refused with its bytes.  The uint32 row positions and the held-out walk's node table are part of the
@@ -790,6 +791,45 @@ int OHXBoosterBoostTreesDeepDevice(BoosterHandle handle, DMatrixHandle dmat, con
                                    const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
                                    float min_child_weight, int patience, double* train_rmse, double* eval_rmse,
                                    int* rounds_run, int* best_round, bst_ulong* nodes_added, void* stream);
+/* Row and column subsampling for trees deeper than eight levels (docs/24_deep_sampled.md): OHXBoosterBoostTreesSampled
+ * with max_depth in 1..18.  The argument lists are those of the Sampled call and of its Device form, argument for
+ * argument.  The call is OHXBoosterBoostTreesSampled, word for word: the mix function, the tree keys with T0, the bag,
+ * n_sel and the selection by (c_f, f); the tree is the Weighted call's where every out-of-bag row has weight 0 and every
+ * unselected feature has an empty cut list; everything else sees every row at its full weight - pred += leaf(row) for
+ * every row, train_rmse, eval_rmse, W, the stop rule, the range and weight refusals, a NaN label on an out-of-bag row
+ * refused with "label", and the round whose bag holds no weight refused with "bag".  One thing changes: max_depth is in
+ * 1..18.
+ * The size of a tree and the waiting are OHXBoosterBoostTreesDeep's: at most min(2^(max_depth + 1) - 1, 2 * nrow - 1)
+ * nodes, a node table of min(2^(max_depth + 1), 2 * nrow) records a round, and with max_depth > 8 one wait per level
+ * from level 7 on for the 16-byte level word, in every tree; the host enqueues no empty level.  From level 8 on a row
+ * outside the bag makes no add and an unselected feature none for any row: the histograms of a batch of node slots are
+ * compact, n_sel columns a slot, and the scratch is min(batch, open nodes) * n_sel * 256 * 16 bytes.
+ * Integer adds only.  The result depends on the order of the rows only through r in the draw.  Launch shape, batch
+ * size, form, stream and OHXDMatrixSetGrid change nothing.
+ * Consequences.  With max_depth <= 8 the forest, XGBoosterSaveModel's bytes in all three formats and both RMSE arrays
+ * equal those of OHXBoosterBoostTreesSampled (the call takes that path as it is).  With subsample = colsample_bytree =
+ * 1.0f and any seed they equal those of OHXBoosterBoostTreesDeep, at any max_depth (nothing is drawn, allocated or
+ * enqueued for the sampling).
+ * Refused, with the forest and every output untouched: everything OHXBoosterBoostTreesSampled refuses, in the same
+ * order - the fractions after min_child_weight and before the cuts - the max_depth message reading "max_depth must be
+ * in 1..18"; every buffer that cannot be allocated is refused with its bytes.  Not capturable.  The bag's bit plane, the
+ * selected features of every round, the uint32 row positions and the held-out walk's node table are part of the grow
+ * state.  Calls on ONE booster must not run concurrently. */
+int OHXBoosterBoostTreesDeepSampled(BoosterHandle handle, DMatrixHandle dmat, const float* labels, const float* weights,
+                                    bst_ulong nlabel, DMatrixHandle eval_dmat, const float* eval_labels,
+                                    const float* eval_weights, bst_ulong eval_nlabel, const bst_ulong* cut_ptr,
+                                    const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
+                                    float min_child_weight, float subsample, float colsample_bytree, uint64_t seed,
+                                    int patience, double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
+                                    bst_ulong* nodes_added);
+int OHXBoosterBoostTreesDeepSampledDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels,
+                                          const float* d_weights, bst_ulong nlabel, DMatrixHandle eval_dmat,
+                                          const float* d_eval_labels, const float* d_eval_weights, bst_ulong eval_nlabel,
+                                          const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth,
+                                          float eta, float lambda, float gamma, float min_child_weight, float subsample,
+                                          float colsample_bytree, uint64_t seed, int patience, double* train_rmse,
+                                          double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added,
+                                          void* stream);
 int OHXQuantileCuts(const float* data, bst_ulong nrow, bst_ulong ncol, float missing, int max_bins, bst_ulong* cut_ptr,
                     float* cut_values, bst_ulong cap, bst_ulong* needed);
 /* OHXDMatrixQuantileCuts (docs/19_device_cuts.md) makes the same cuts from a DMatrix's rows where they lie, in HBM: no

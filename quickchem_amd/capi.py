@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "OHXBoosterBoostTreesWeighted", "OHXBoosterBoostTreesWeightedDevice",
     "OHXBoosterBoostTreesSampled", "OHXBoosterBoostTreesSampledDevice",
     "OHXBoosterBoostTreesDeep", "OHXBoosterBoostTreesDeepDevice",
+    "OHXBoosterBoostTreesDeepSampled", "OHXBoosterBoostTreesDeepSampledDevice",
     "OHXQuantileCuts", "OHXDMatrixQuantileCuts",
     "OHXSelectCells", "OHXSelectCellsDevice", "OHXGatherCells", "OHXGatherCellsDevice",
     "OHXScatterCells", "OHXScatterCellsDevice",
@@ -155,6 +156,8 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
     lib.OHXBoosterBoostTreesSampled.argtypes = [vp, vp, vp, vp, u64, vp, vp, vp, u64, vp, vp, i32, i32, f32, f32, f32, f32,
                                                 f32, f32, u64, i32, vp, vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(u64)]
     lib.OHXBoosterBoostTreesSampledDevice.argtypes = lib.OHXBoosterBoostTreesSampled.argtypes + [vp]
+    lib.OHXBoosterBoostTreesDeepSampled.argtypes = lib.OHXBoosterBoostTreesSampled.argtypes
+    lib.OHXBoosterBoostTreesDeepSampledDevice.argtypes = lib.OHXBoosterBoostTreesSampledDevice.argtypes
     lib.OHXQuantileCuts.argtypes = [vp, u64, u64, f32, i32, vp, vp, u64, C.POINTER(u64)]
     lib.OHXDMatrixQuantileCuts.argtypes = [vp, u64, i32, vp, vp, u64, C.POINTER(u64), vp]
     lib.OHXBoosterPredictFields.argtypes = [vp, C.POINTER(vp), C.POINTER(C.c_int32), i32, i32, i32, i32, i32, i32, i32,
@@ -651,6 +654,12 @@ class Booster:
         """OHXBoosterBoostTreesSampled: boost_trees_weighted where every tree is fitted to a fresh bag of the rows
         (a fraction `subsample`) and may split on a fresh set of the features (a fraction `colsample_bytree`), both
         drawn on the GPU from `seed` (a uint64) and the tree's index in the forest.  -> the dict of boost_trees_eval."""
+        return self._boost_sampled("OHXBoosterBoostTreesSampled", dmat, labels, cuts, weights, eval_set, rounds, max_depth, eta,
+                                   reg_lambda, gamma, min_child_weight, subsample, colsample_bytree, seed, patience)
+
+    def _boost_sampled(self, entry, dmat, labels, cuts, weights, eval_set, rounds, max_depth, eta, reg_lambda, gamma,
+                       min_child_weight, subsample, colsample_bytree, seed, patience) -> dict:
+        """The host form of the Sampled call, or of an entry point with its argument list."""
         y = np.ascontiguousarray(labels, dtype=np.float32).reshape(-1)
         w = np.ascontiguousarray(weights, dtype=np.float32).reshape(-1) if weights is not None else None
         if w is not None and w.size != y.size:
@@ -666,7 +675,7 @@ class Booster:
         k = max(int(rounds), 0) + 1
         train, held = np.full(k, np.nan), np.full(k, np.nan)
         run, best, n = C.c_int32(), C.c_int32(), C.c_uint64()
-        check(self.lib, self.lib.OHXBoosterBoostTreesSampled(
+        check(self.lib, getattr(self.lib, entry)(
             self.handle, dmat.handle, y.ctypes.data, w.ctypes.data if w is not None else None, y.size,
             ed.handle if ed is not None else None, ey.ctypes.data if ey is not None else None,
             ew.ctypes.data if ew is not None else None, ey.size if ey is not None else 0, cut_ptr.ctypes.data,
@@ -681,17 +690,46 @@ class Booster:
                                    subsample: float = 1.0, colsample_bytree: float = 1.0, seed: int = 0,
                                    patience: int = 0, stream: int = 0) -> dict:
         """The same with labels and weights in device memory, as boost_trees_weighted_device takes them."""
+        return self._boost_sampled_device("OHXBoosterBoostTreesSampledDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
+                                          eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, subsample,
+                                          colsample_bytree, seed, patience, stream)
+
+    def _boost_sampled_device(self, entry, dmat, labels_ptr, nlabel, cuts, weights_ptr, eval_set, rounds, max_depth, eta,
+                              reg_lambda, gamma, min_child_weight, subsample, colsample_bytree, seed, patience, stream) -> dict:
+        """The device form of the Sampled call, or of an entry point with its argument list."""
         cut_ptr, cut_values = self._cuts(cuts)
         ed, eptr, en, ewptr = (tuple(eval_set) + (0,))[:4] if eval_set is not None else (None, None, 0, 0)
         k = max(int(rounds), 0) + 1
         train, held = np.full(k, np.nan), np.full(k, np.nan)
         run, best, n = C.c_int32(), C.c_int32(), C.c_uint64()
-        check(self.lib, self.lib.OHXBoosterBoostTreesSampledDevice(
+        check(self.lib, getattr(self.lib, entry)(
             self.handle, dmat.handle, labels_ptr, weights_ptr or None, nlabel, ed.handle if ed is not None else None,
             eptr or None, ewptr or None, en, cut_ptr.ctypes.data, cut_values.ctypes.data, rounds, max_depth, eta,
             reg_lambda, gamma, min_child_weight, subsample, colsample_bytree, int(seed) & 0xFFFFFFFFFFFFFFFF, patience,
             train.ctypes.data, held.ctypes.data, C.byref(run), C.byref(best), C.byref(n), stream or None))
         return self._eval_result(train, held, run, best, n, ed is not None)
+
+    def boost_trees_deep_sampled(self, dmat: DMatrix, labels, cuts, weights=None, eval_set=None, rounds: int = 1,
+                                 max_depth: int = 12, eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
+                                 min_child_weight: float = 1.0, subsample: float = 1.0, colsample_bytree: float = 1.0,
+                                 seed: int = 0, patience: int = 0) -> dict:
+        """OHXBoosterBoostTreesDeepSampled: boost_trees_sampled with max_depth up to 18.  From level 8 on a level's
+        histograms are kept in HBM for a batch of nodes at a time, over the bag's rows and the tree's features only, and
+        the call waits once a level for the ids of the open nodes.  Up to depth 8 it is boost_trees_sampled itself; with
+        both fractions 1 it is boost_trees_deep.  -> the dict of boost_trees_eval."""
+        return self._boost_sampled("OHXBoosterBoostTreesDeepSampled", dmat, labels, cuts, weights, eval_set, rounds, max_depth,
+                                   eta, reg_lambda, gamma, min_child_weight, subsample, colsample_bytree, seed, patience)
+
+    def boost_trees_deep_sampled_device(self, dmat: DMatrix, labels_ptr: int, nlabel: int, cuts, weights_ptr: int = 0,
+                                        eval_set=None, rounds: int = 1, max_depth: int = 12, eta: float = 0.3,
+                                        reg_lambda: float = 1.0, gamma: float = 0.0, min_child_weight: float = 1.0,
+                                        subsample: float = 1.0, colsample_bytree: float = 1.0, seed: int = 0,
+                                        patience: int = 0, stream: int = 0) -> dict:
+        """The same with labels and weights in device memory, as boost_trees_weighted_device takes them.  With
+        max_depth > 8 the call waits for `stream` once a level from level 7 on."""
+        return self._boost_sampled_device("OHXBoosterBoostTreesDeepSampledDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
+                                          eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, subsample,
+                                          colsample_bytree, seed, patience, stream)
 
     def predict_fields(self, fields: Sequence[np.ndarray], is2d: Sequence[bool], pl_feature: int, im: int, jm: int,
                        km: int, k1: int, k2: int, missing: float, oh_ml: np.ndarray, *, apply_pow10: bool = True,

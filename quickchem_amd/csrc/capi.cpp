@@ -2253,7 +2253,7 @@ struct BoostCall {
   BoostEval eval;
   BoostWeights weights;
   BoostSampling sampling;
-  bool deep = false;                 // OHXBoosterBoostTreesDeep: max_depth up to 18
+  bool deep = false;                 // OHXBoosterBoostTreesDeep and ...DeepSampled: max_depth up to 18
 };
 
 BoostCall boost_call(const char* what, bool host_form, void* stream, DMatrixHandle dmat, const float* labels, bst_ulong nlabel,
@@ -2306,6 +2306,8 @@ BoostWeights boost_weights(const float* weights, const float* eval_weights, floa
 // Plain: row counts and 12-byte bins.  Weighted: fixed-point hessians.  Sampled: the same over a bag and a feature list.
 // Deep: the weighted kind to level 7 and histograms in HBM from level 8 on, with its own node stride and held-out walk;
 // `deep` is its plan and `deep_args` what its kernels take beyond GrowArgs (filled by boost_trees once the buffers stand).
+// It answers with or without sampling: over a bag and a feature list its levels to 7 are the sampled kind's, and its plan
+// is the one over the tree's columns.
 // (Calls, not a table of function addresses: a build of this file alone links without the grower until it is used.)
 struct BoostKind {
   enum Which { Plain, Weighted, Sampled, Deep } which;
@@ -2313,14 +2315,20 @@ struct BoostKind {
   GrowDeepArgs deep_args;
   GrowLevelState* h_state = nullptr;   // where the Deep kind's tree launcher waits for the level word
   bool wide() const { return which != Plain; }
-  GrowPlan plan(uint64_t n, uint32_t F, uint64_t ncuts, int max_depth, int num_cus) {
+  // The call's one plan, asked for once: the level loop over `cols` histogram columns - F itself, or the n_sel features
+  // a tree of a sampled call sees (compact histograms and candidates) - the streaming kernels, which do not depend on
+  // the columns, and the bin planes of all F features.
+  GrowPlan plan(uint64_t n, uint32_t F, uint32_t cols, uint64_t ncuts, int max_depth, int num_cus) {
+    GrowPlan p;
     if (which == Deep) {
-      deep = plan_grow_deep(n, F, ncuts, max_depth, num_cus);
-      GrowPlan p = deep.lds;           // the streaming kernels and the bins; the histograms of either path
+      deep = plan_grow_deep_sampled(n, F, cols, ncuts, max_depth, num_cus);
+      p = deep.lds;                    // the histograms of either path
       p.hist_bytes = std::max(p.hist_bytes, deep.scratch_bytes);
-      return p;
+    } else {
+      p = wide() ? plan_grow_weighted(n, cols, ncuts, max_depth, num_cus) : plan_grow(n, cols, ncuts, max_depth, num_cus);
     }
-    return wide() ? plan_grow_weighted(n, F, ncuts, max_depth, num_cus) : plan_grow(n, F, ncuts, max_depth, num_cus);
+    p.bins_bytes = (uint64_t)F * n;    // the bins hold every feature
+    return p;
   }
   // node records of one round, and the candidates of a level
   size_t node_stride() const { return which == Deep ? (size_t)deep.node_stride : (size_t)kGrowMaxNodes; }
@@ -2367,7 +2375,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   const int max_depth = c.max_depth;
   if (weighted && !ev.present) throw OhxError(w0 + ": the weighted call carries the metric");
   if (c.sampling.present && !weighted) throw OhxError(w0 + ": the sampled call carries the weights");
-  if (c.deep && (!weighted || c.sampling.present)) throw OhxError(w0 + ": the deep call is the weighted call");
+  if (c.deep && !weighted) throw OhxError(w0 + ": the deep call carries the weights");
   if (!b.loaded) throw OhxError("the booster holds no model: call XGBoosterLoadModel first");
   refuse_categorical(b, what);
   refuse_groups(b, what);
@@ -2432,7 +2440,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   }
   // the kind of the call, once: everything below that differs by kernel or by sum layout asks `kind`
   const bool sampled = k_s != kGrowSampleOne || n_sel != F;
-  // (the Deep entry point at max_depth <= 8 takes the weighted kind as it is)
+  // (the Deep entry points at max_depth <= 8 take the weighted or the sampled kind as it is)
   const bool deep = c.deep && max_depth > kGrowMaxDepth;
   BoostKind kind{deep ? BoostKind::Deep : sampled ? BoostKind::Sampled : weighted ? BoostKind::Weighted : BoostKind::Plain};
   // before anything is built or enqueued: building the state waits for the library's stream
@@ -2454,10 +2462,9 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   }
   const uint64_t n = d.nrow, ncuts = c.cut_ptr[F];
   const size_t R = (size_t)c.rounds;
-  const GrowPlan plan = kind.plan(n, F, ncuts, max_depth, dev.num_cus);
-  // the level loop over a tree's n_sel features: compact histograms and candidates (the bins hold every feature)
-  const GrowPlan splan = sampled ? kind.plan(n, n_sel, ncuts, max_depth, dev.num_cus) : GrowPlan();
-  const GrowPlan& levels = sampled ? splan : plan;
+  // (n_sel == F where nothing is sampled)
+  const GrowPlan plan = kind.plan(n, F, n_sel, ncuts, max_depth, dev.num_cus);
+  const GrowPlan& levels = plan;
   const uint64_t tree0 = b.forest.trees.size();   // T0: tree t of the call is tree tree0 + t - 1 of the draws
   auto room = [&](auto& buf, size_t count, size_t elem, const char* name) {
     try {
@@ -3605,6 +3612,43 @@ int OHXBoosterBoostTreesDeepDevice(BoosterHandle handle, DMatrixHandle dmat, con
                            rounds, max_depth, eta, lambda, gamma, nodes_added);
   c.eval = boost_eval(eval_dmat, d_eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
   c.weights = boost_weights(d_weights, d_eval_weights, min_child_weight);
+  c.deep = true;
+  boost_trees(*as_booster(handle), c);
+  API_END();
+}
+
+int OHXBoosterBoostTreesDeepSampled(BoosterHandle handle, DMatrixHandle dmat, const float* labels, const float* weights,
+                                    bst_ulong nlabel, DMatrixHandle eval_dmat, const float* eval_labels,
+                                    const float* eval_weights, bst_ulong eval_nlabel, const bst_ulong* cut_ptr,
+                                    const float* cut_values, int rounds, int max_depth, float eta, float lambda, float gamma,
+                                    float min_child_weight, float subsample, float colsample_bytree, uint64_t seed,
+                                    int patience, double* train_rmse, double* eval_rmse, int* rounds_run, int* best_round,
+                                    bst_ulong* nodes_added) {
+  API_BEGIN();
+  BoostCall c = boost_call("OHXBoosterBoostTreesDeepSampled", true, nullptr, dmat, labels, nlabel, cut_ptr, cut_values, rounds,
+                           max_depth, eta, lambda, gamma, nodes_added);
+  c.eval = boost_eval(eval_dmat, eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
+  c.weights = boost_weights(weights, eval_weights, min_child_weight);
+  c.sampling = {true, subsample, colsample_bytree, seed};
+  c.deep = true;
+  boost_trees(*as_booster(handle), c);
+  API_END();
+}
+
+int OHXBoosterBoostTreesDeepSampledDevice(BoosterHandle handle, DMatrixHandle dmat, const float* d_labels,
+                                          const float* d_weights, bst_ulong nlabel, DMatrixHandle eval_dmat,
+                                          const float* d_eval_labels, const float* d_eval_weights, bst_ulong eval_nlabel,
+                                          const bst_ulong* cut_ptr, const float* cut_values, int rounds, int max_depth,
+                                          float eta, float lambda, float gamma, float min_child_weight, float subsample,
+                                          float colsample_bytree, uint64_t seed, int patience, double* train_rmse,
+                                          double* eval_rmse, int* rounds_run, int* best_round, bst_ulong* nodes_added,
+                                          void* stream) {
+  API_BEGIN();
+  BoostCall c = boost_call("OHXBoosterBoostTreesDeepSampledDevice", false, stream, dmat, d_labels, nlabel, cut_ptr, cut_values,
+                           rounds, max_depth, eta, lambda, gamma, nodes_added);
+  c.eval = boost_eval(eval_dmat, d_eval_labels, eval_nlabel, patience, train_rmse, eval_rmse, rounds_run, best_round);
+  c.weights = boost_weights(d_weights, d_eval_weights, min_child_weight);
+  c.sampling = {true, subsample, colsample_bytree, seed};
   c.deep = true;
   boost_trees(*as_booster(handle), c);
   API_END();

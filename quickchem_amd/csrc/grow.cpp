@@ -176,6 +176,12 @@ GrowDeepPlan plan_grow_deep(uint64_t nrow, uint32_t num_feature, uint64_t ncuts,
   return p;
 }
 
+GrowDeepPlan plan_grow_deep_sampled(uint64_t nrow, uint32_t num_feature, uint32_t n_sel, uint64_t ncuts, int max_depth, int num_cus) {
+  GrowDeepPlan p = plan_grow_deep(nrow, n_sel, ncuts, max_depth, num_cus);
+  p.lds.bins_bytes = (uint64_t)num_feature * nrow;   // the bins hold every feature
+  return p;
+}
+
 uint32_t plan_grow_eval_blocks(uint64_t nrow, int num_cus) {
   const uint64_t cus = num_cus > 0 ? (uint64_t)num_cus : 1;
   const uint64_t want = (nrow + kGrowBlock - 1) / kGrowBlock, cap = cus * kGrowRowBlocksPerCu;

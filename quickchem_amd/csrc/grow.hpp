@@ -345,6 +345,11 @@ struct GrowDeepPlan {
   uint64_t node_stride = 0;   // grow_deep_node_stride
 };
 GrowDeepPlan plan_grow_deep(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus);
+// The same for a tree that sees n_sel of the num_feature features (OHXBoosterBoostTreesDeepSampled): plan_grow_deep over
+// n_sel histogram columns - lds is plan_grow_weighted(nrow, n_sel, ..), the scratch min(batch, max open) x n_sel x 256 x
+// 16 bytes and `best` max(max open, 128) x n_sel candidates - with the bin planes of all num_feature features.
+// n_sel == num_feature is plan_grow_deep itself.
+GrowDeepPlan plan_grow_deep_sampled(uint64_t nrow, uint32_t num_feature, uint32_t n_sel, uint64_t ncuts, int max_depth, int num_cus);
 
 // The child ids of a level with any number of open nodes, as one block of `width` lanes hands them out: the slots are
 // walked in chunks of `width` with a running total; a slot's `below` is the running total plus the exclusive scan of
@@ -432,6 +437,8 @@ int launch_grow_tree_weighted(const GrowArgs& a, const GrowPlan& plan, const Gro
 int launch_grow_tree_sampled(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
 // launch_grow_tree_weighted without the leaf kernel: the rows stay on their nodes after the last level's partition
 int launch_grow_levels_weighted(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
+// launch_grow_tree_sampled without the leaf kernel, likewise
+int launch_grow_levels_sampled(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream);
 // Enqueue grow_partition_kernel and grow_leaf_kernel alone, for the level loop as the other files instantiate it: they
 // read node records and bins, never a histogram or a weight.  Return a hipError_t.
 int launch_grow_partition(const GrowArgs& a, const GrowPlan& plan, uint32_t round, void* stream);
@@ -477,17 +484,20 @@ int launch_grow_walk_sse_weighted(const GrowEvalArgs& a, uint32_t blocks, uint32
 
 constexpr size_t kGrowEvalNodeBytes = 16;   // an EvalNode of grow_device.hpp: a node as the held-out walk reads it
 // What the deep kernels take: the call's GrowArgs with `nodes` and `tree_nodes` at the call's first round, Ghist / Hhist
-// the scratch of one batch and `best` the candidates of a whole level, and what the deep levels add.
+// the scratch of one batch and `best` the candidates of a whole level, and what the deep levels add.  With g.features
+// (OHXBoosterBoostTreesDeepSampled) the histograms and `best` are compact over g.n_sel columns and g.bag, where it is
+// not nullptr, is the bag of the tree at hand.
 struct GrowDeepArgs {
   GrowArgs g;
   uint32_t* pos = nullptr;         // [nrow] the node a row stands on from level 8 on
   uint32_t node_stride = 0;        // node records of one round
   void* eval_nodes = nullptr;      // [node_stride] EvalNodes: the tree at hand as the held-out walk reads it
 };
-// One tree of a call with max_depth > 8, round `round`: levels 0 - 7 by launch_grow_levels_weighted on the tree's own
-// records, then per deep level the batches (two memsets, the histogram kernel and split phase 0 each), split phase 1,
-// the partition, and one wait for the level word on h_state (pinned); then the leaf kernel.  The tree ends at the first
-// level without an open node.  a.g.pos and a.pos must be zero and pred the margin so far.  Returns a hipError_t.
+// One tree of a call with max_depth > 8, round `round`: levels 0 - 7 by launch_grow_levels_weighted (with g.features, by
+// launch_grow_levels_sampled) on the tree's own records, then per deep level the batches (two memsets, the histogram
+// kernel and split phase 0 each, of the kind), split phase 1, the partition, and one wait for the level word on h_state
+// (pinned); then the leaf kernel.  The tree ends at the first level without an open node.  a.g.pos and a.pos must be
+// zero and pred the margin so far.  Returns a hipError_t.
 int launch_grow_tree_deep(const GrowDeepArgs& a, const GrowDeepPlan& plan, uint32_t round, GrowLevelState* h_state, void* stream);
 // Enqueues grow_deep_stage_kernel and grow_deep_walk_sse_kernel: eval_nodes from the records of tree `round`, then
 // launch_grow_walk_sse_weighted's walk and sums over the rows of `a`, its nodes read from HBM.  Returns a hipError_t.

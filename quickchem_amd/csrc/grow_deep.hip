@@ -18,6 +18,16 @@
 //   grow_deep_stage_kernel     once per round with a held-out set: the tree's GrowNodes as 16-byte EvalNodes in HBM.
 //   grow_deep_walk_sse_kernel  grow_walk_sse_weighted_kernel with grow_walk_row reading that table; nothing in LDS but
 //                              the reduction's partial sums.
+// The Deep Sampled call (OHXBoosterBoostTreesDeepSampled; design in docs/24_deep_sampled.md) grows the same levels over a
+// bag of the rows and a tree's feature list; its levels 0 - 7 are the sampled call's own (launch_grow_levels_sampled):
+//   grow_deep_hist_sampled_kernel      grow_deep_hist_kernel over the bag and the list: the bag's word first, by one
+//                                      scalar load a wave, then the position; the adds go to the compact
+//                                      [slots][n_sel][256] histograms, the bins come from the planes of the list.
+//   grow_deep_split_sampled_kernel<0>  grow_split_columns over n_sel columns and the list; the feature goes into the
+//                                      key and the cut lookup.
+//   grow_deep_split_sampled_kernel<1>  the chunked walk of grow_deep_split_kernel<1> (grow_deep_split_chunks, written
+//                                      once) over n_sel columns.
+// The widen, partition, leaf, stage and walk kernels see every row, in or out of the bag, and are the ones above.
 // Only integer adds: no float atomics, no compare-and-swap loops, and the same trees and sums whatever the order of the
 // rows, the batch size or the launch shape.
 #include <hip/hip_runtime.h>
@@ -97,15 +107,10 @@ __global__ __launch_bounds__(kBlock) void grow_deep_hist_kernel(GrowDeepArgs d, 
   if (flags) atomicOr(&a.state->error, flags);
 }
 
-// PHASE 0: grid (blocks of four waves over the batch's slots x features).  PHASE 1: one block.
-template <int PHASE>
-__global__ __launch_bounds__(kBlock) void grow_deep_split_kernel(GrowDeepArgs d, uint32_t level, uint32_t round, uint32_t batch0) {
-  const GrowArgs a = tree_args(d, round);
-  const GrowFixedHess hess{a.min_child_weight};
-  if (PHASE == 0) {
-    grow_split_columns(a, hess, level, 0, a.num_feature, GrowIdentityMap(), batch0);
-    return;
-  }
+// Split phase 1 of a deep level, written once for both kinds: one block walks the level's slots in chunks of its width
+// with a running total (grow.hpp grow_chunked_children) and decides every node over `ncols` columns of `best`.
+__device__ inline void grow_deep_split_chunks(const GrowArgs& a, const GrowFixedHess& hess, uint32_t node_stride, uint32_t level,
+                                              uint32_t ncols) {
   __shared__ uint32_t wave_splits[kWaves];
   const uint32_t begin = a.state->begin, end = a.state->end, next = a.state->next;
   const uint32_t count = end - begin;
@@ -116,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void grow_deep_split_kernel(GrowDeepArgs d,
     const uint32_t s = c0 + threadIdx.x;
     const uint32_t node = begin + s;
     GrowDecision dec;
-    if (s < count) dec = grow_decide_node<false>(a, hess, a.nodes, level, node, s, a.num_feature);
+    if (s < count) dec = grow_decide_node<false>(a, hess, a.nodes, level, node, s, ncols);
     const bool split = s < count && dec.split;
     // the exclusive scan of the chunk's flags: the lanes below in the wave, and the waves below in the block
     const unsigned long long votes = __ballot(split);
@@ -131,14 +136,14 @@ __global__ __launch_bounds__(kBlock) void grow_deep_split_kernel(GrowDeepArgs d,
     __syncthreads();   // wave_splits is written again in the next chunk
     if (split) {
       const uint32_t left = grow_child_id(next, running + scan);
-      if (left + 1u < d.node_stride) grow_write_split(a, hess, a.nodes, node, dec, left);
+      if (left + 1u < node_stride) grow_write_split(a, hess, a.nodes, node, dec, left);
       else full = true;
     }
     running += chunk;
   }
   if (full) atomicOr(&a.state->error, kGrowFlagState);
   uint32_t total = next + 2u * running;
-  if (total > d.node_stride) total = next;   // (never; the flag is raised above) nothing is open: the tree ends
+  if (total > node_stride) total = next;   // (never; the flag is raised above) nothing is open: the tree ends
   __syncthreads();
   if (threadIdx.x == 0) {
     a.state->begin = next;
@@ -146,6 +151,144 @@ __global__ __launch_bounds__(kBlock) void grow_deep_split_kernel(GrowDeepArgs d,
     a.state->next = total;
     a.tree_nodes[0] = total;
   }
+}
+
+// PHASE 0: grid (blocks of four waves over the batch's slots x features).  PHASE 1: one block.
+template <int PHASE>
+__global__ __launch_bounds__(kBlock) void grow_deep_split_kernel(GrowDeepArgs d, uint32_t level, uint32_t round, uint32_t batch0) {
+  const GrowArgs a = tree_args(d, round);
+  const GrowFixedHess hess{a.min_child_weight};
+  if (PHASE == 0) {
+    grow_split_columns(a, hess, level, 0, a.num_feature, GrowIdentityMap(), batch0);
+    return;
+  }
+  grow_deep_split_chunks(a, hess, d.node_stride, level, a.num_feature);
+}
+
+// ---- the deep levels over a bag and a feature list ----
+
+// A block's features, four to a 32-bit word kept in scalar registers: the packing of grow_hist_sampled_kernel, and the
+// only path.  A block takes kDeepPackFeatures columns of the list and gridDim.y covers a longer one (up to four groups
+// at 128 features), so the unrolled row loop keeps at most 32 plane offsets in scalar registers; a row of a second group
+// reads its bag bit, position, margin, label and weight once more, which is little beside its 32 bins and 64 adds.
+constexpr uint32_t kDeepPackWords = 8;
+constexpr uint32_t kDeepPackFeatures = 4 * kDeepPackWords;
+static_assert(kGrowMaxFeatures <= 256, "a feature is a byte");
+// 64-bit words that nothing writes while the kernel runs (the bag's bit plane)
+typedef const unsigned long long __attribute__((address_space(4))) * GrowConstWords;
+
+// grid (blocks over the rows, groups of kDeepPackFeatures columns).  grow_deep_hist_kernel over the bag d.g.bag (nullptr:
+// every row is in) and the n_sel features d.g.features[round][..]; Ghist / Hhist are compact, [nslots][n_sel][256].
+// Eight waves a SIMD are asked for: the compiler then parks 125 scalar values (the hoisted plane offsets) in lanes of
+// vector registers and reads 112 back in the row loop, never scratch.  Measured against a build without the attribute
+// (seven waves, 81 lane reads in the loop) on the C360 L72 rows at depth 18, 10 rounds: 4.78 against 4.86 s at
+// (0.5, 0.5) and 14.44 against 14.54 s at 26 of 27 features (docs/24_deep_sampled.md 24.4).
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(8, 8)))
+void grow_deep_hist_sampled_kernel(GrowDeepArgs d, uint32_t round, uint32_t batch0, uint32_t nslots) {
+  const GrowArgs& a = d.g;
+  const uint32_t begin = a.state->begin, end = a.state->end;
+  const uint32_t count = end - begin;
+  if (batch0 >= count) return;
+  const uint32_t live = count - batch0 < nslots ? count - batch0 : nslots;   // (the host's count is the device's)
+  const uint32_t first = begin + batch0;
+  const uint32_t n_sel = a.n_sel;
+  const uint32_t k0 = blockIdx.y * kDeepPackFeatures;   // the block's first column of the list
+  if (k0 >= n_sel) return;
+  const uint32_t nf = n_sel - k0 < kDeepPackFeatures ? n_sel - k0 : kDeepPackFeatures;
+  // the block's features leave memory once: a byte each in wave-uniform words, so that the row loop forms a bin plane's
+  // address with scalar arithmetic and loads nothing on the way to it
+  const uint8_t* feat = a.features + (uint64_t)round * n_sel + k0;
+  uint32_t pack[kDeepPackWords];
+#pragma unroll
+  for (uint32_t j = 0; j < kDeepPackWords; ++j) {
+    uint32_t v = 0;
+#pragma unroll
+    for (uint32_t b = 0; b < 4; ++b)   // (a byte past the last feature repeats the word's first: see the row loop)
+      if (4 * j < nf) v |= (uint32_t)feat[4 * j + b < nf ? 4 * j + b : 4 * j] << (8 * b);
+    pack[j] = __builtin_amdgcn_readfirstlane(v);
+  }
+  uint32_t flags = 0;
+  const uint64_t stride = (uint64_t)gridDim.x * kBlock;
+  for (uint64_t row = (uint64_t)blockIdx.x * kBlock + threadIdx.x; row < a.nrow; row += stride) {
+    if (a.bag != nullptr) {
+      // A wave's 64 rows share one word of the plane: a block starts at a multiple of kBlock, a wave at a multiple of 64
+      // within it, and the stride is a multiple of kBlock, so the wave's first row is a multiple of 64 on every trip and
+      // its lanes are the 64 rows after it (those below nrow).  rows < 2^31, so the word index fits 32 bits.
+      // The plane is written by grow_bag_kernel before this kernel starts and by nothing while it runs; the kernel's own
+      // global adds keep the compiler from proving that, so the word is read through the constant address space, which
+      // says so and makes the read the scalar load it is in grow_hist_sampled_kernel.
+      const uint32_t word = __builtin_amdgcn_readfirstlane((uint32_t)(row >> 6));
+      const unsigned long long bits = ((GrowConstWords)a.bag)[word];
+      if (((bits >> (row & 63u)) & 1ull) == 0ull) continue;   // out of the bag: nothing else is read
+    }
+    const uint32_t s = d.pos[row] - first;   // (a node below `first` wraps past live)
+    if (s >= live) continue;
+    const float g = a.pred[row] - a.labels[row];
+    // the gradient before the weight (a NaN fails the comparison)
+    if (!(__builtin_fabsf(g) < kRefitMaxAbsGrad)) {
+      flags |= kGrowFlagLabel;
+      continue;
+    }
+    float w;
+    unsigned long long hq;
+    if (!grow_row_weight(a.weights, row, &w, &hq)) {
+      flags |= kGrowFlagWeight;
+      continue;
+    }
+    const float gw = g * w;   // one float32 multiply (-ffp-contract=off)
+    if (!(__builtin_fabsf(gw) < kRefitMaxAbsGrad)) {
+      flags |= kGrowFlagLabel;
+      continue;
+    }
+    const unsigned long long q = (unsigned long long)(long long)__builtin_rintf(gw * kRefitGradScale);
+    if (hq == 0ull && q == 0ull) continue;   // nothing to add
+    const uint8_t* bins = a.bins + row;
+    const uint64_t base = ((uint64_t)s * n_sel + k0) * kGrowBins;   // s < live <= nslots, k0 + k < n_sel, a bin is a byte
+    unsigned long long* G = a.Ghist + base;
+    unsigned long long* H = a.Hhist + base;
+    // a word's four bin loads leave together, then their adds: the lane waits for memory once a word, not once a
+    // feature.  A byte past the block's last feature repeats the word's first feature: its load reads the address the
+    // first load reads, and is not used.
+#pragma unroll
+    for (uint32_t j = 0; j < kDeepPackWords; ++j) {
+      if (4 * j >= nf) break;
+      const uint32_t p = pack[j];
+      const uint32_t b0 = bins[(uint64_t)(p & 255u) * a.nrow], b1 = bins[(uint64_t)((p >> 8) & 255u) * a.nrow];
+      const uint32_t b2 = bins[(uint64_t)((p >> 16) & 255u) * a.nrow], b3 = bins[(uint64_t)(p >> 24) * a.nrow];
+      const uint32_t at = 4 * j * kGrowBins;
+      atomicAdd(&G[at + b0], q);
+      atomicAdd(&H[at + b0], hq);
+      if (4 * j + 1 < nf) {
+        atomicAdd(&G[at + kGrowBins + b1], q);
+        atomicAdd(&H[at + kGrowBins + b1], hq);
+      }
+      if (4 * j + 2 < nf) {
+        atomicAdd(&G[at + 2 * kGrowBins + b2], q);
+        atomicAdd(&H[at + 2 * kGrowBins + b2], hq);
+      }
+      if (4 * j + 3 < nf) {
+        atomicAdd(&G[at + 3 * kGrowBins + b3], q);
+        atomicAdd(&H[at + 3 * kGrowBins + b3], hq);
+      }
+    }
+  }
+  if (flags) atomicOr(&a.state->error, flags);
+}
+
+// PHASE 0: grid (blocks of four waves over the batch's slots x n_sel).  PHASE 1: one block.  (kGrowFlagBag is raised by
+// the sampled phase 1 at level 0, which is never a deep level.)
+template <int PHASE>
+__global__ __launch_bounds__(kBlock) void grow_deep_split_sampled_kernel(GrowDeepArgs d, uint32_t level, uint32_t round,
+                                                                         uint32_t batch0) {
+  const GrowArgs a = tree_args(d, round);
+  const GrowFixedHess hess{a.min_child_weight};
+  if (PHASE == 0) {
+    GrowListMap map;
+    map.list = a.features + (uint64_t)round * a.n_sel;
+    grow_split_columns(a, hess, level, 0, a.n_sel, map, batch0);
+    return;
+  }
+  grow_deep_split_chunks(a, hess, d.node_stride, level, a.n_sel);
 }
 
 // grid (blocks)
@@ -225,14 +368,19 @@ __global__ __launch_bounds__(kBlock) void grow_deep_walk_sse_kernel(GrowEvalArgs
   grow_reduce_wide(acc, slot, nullptr);
 }
 
+// the histogram columns of a tree: the tree's feature list where the call has one, else every feature
+uint32_t deep_columns(const GrowArgs& a) { return a.features != nullptr ? a.n_sel : a.num_feature; }
+
 bool deep_args_sound(const GrowDeepArgs& d, const GrowDeepPlan& plan) {
   const GrowArgs& a = d.g;
-  return a.nrow != 0 && a.nrow <= kRefitMaxRows && a.num_feature != 0 && a.num_feature <= kGrowMaxFeatures &&
+  const uint32_t ncols = deep_columns(a);
+  return a.nrow != 0 && a.nrow <= kRefitMaxRows && a.num_feature != 0 && a.num_feature <= kGrowMaxFeatures && ncols != 0 &&
+         ncols <= a.num_feature && (a.features != nullptr || a.bag == nullptr) &&
          a.max_depth > kGrowMaxDepth && a.max_depth <= kGrowDeepMaxDepth && a.min_child_weight >= 0.0 && d.pos != nullptr &&
          d.node_stride != 0 && (uint64_t)d.node_stride == grow_deep_node_stride(a.nrow, a.max_depth) &&
          plan.node_stride == d.node_stride && plan.batch != 0 && plan.hist_blocks != 0 && plan.lds.row_blocks != 0 &&
          plan.lds.levels.size() == (size_t)kGrowMaxDepth &&
-         plan.scratch_bytes == std::min<uint64_t>(plan.batch, grow_deep_max_open(a.nrow, a.max_depth)) * a.num_feature * kGrowBins * 16;
+         plan.scratch_bytes == std::min<uint64_t>(plan.batch, grow_deep_max_open(a.nrow, a.max_depth)) * ncols * kGrowBins * 16;
 }
 
 }  // namespace
@@ -240,11 +388,15 @@ bool deep_args_sound(const GrowDeepArgs& d, const GrowDeepPlan& plan) {
 int launch_grow_tree_deep(const GrowDeepArgs& d, const GrowDeepPlan& plan, uint32_t round, GrowLevelState* h_state, void* stream_) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
   if (!deep_args_sound(d, plan) || h_state == nullptr) return hipErrorInvalidValue;
-  // levels 0 - 7: the weighted call's kernels on the tree's own records (a tree of 8 levels has at most 511 of them, and
-  // no more than 2 * nrow - 1: within the stride either way)
+  // levels 0 - 7: the weighted call's kernels, or the sampled call's over the bag and the tree's list, on the tree's own
+  // records (a tree of 8 levels has at most 511 of them, and no more than 2 * nrow - 1: within the stride either way)
+  const bool sampled = d.g.features != nullptr;
+  const uint32_t ncols = deep_columns(d.g);
   GrowArgs top = tree_args(d, round);
   top.max_depth = kGrowMaxDepth;
-  hipError_t e = (hipError_t)launch_grow_levels_weighted(top, plan.lds, plan.lds, 0, stream);
+  if (sampled) top.features += (uint64_t)round * ncols;   // round 0 of its own list, as of its own records
+  hipError_t e = (hipError_t)(sampled ? launch_grow_levels_sampled(top, plan.lds, plan.lds, 0, stream)
+                                      : launch_grow_levels_weighted(top, plan.lds, plan.lds, 0, stream));
   if (e != hipSuccess) return e;
   // the level word after phase 1 of level d - 1: the open nodes of level d
   auto level_word = [&]() {
@@ -262,16 +414,21 @@ int launch_grow_tree_deep(const GrowDeepArgs& d, const GrowDeepPlan& plan, uint3
     if (count > max_open) return hipErrorInvalidValue;   // (never: `best` holds max_open slots)
     for (uint32_t batch0 = 0; batch0 < count; batch0 += plan.batch) {
       const uint32_t nslots = std::min(plan.batch, count - batch0);
-      const size_t bytes = (size_t)nslots * d.g.num_feature * kGrowBins * sizeof(unsigned long long);
+      const size_t bytes = (size_t)nslots * ncols * kGrowBins * sizeof(unsigned long long);
       if ((e = hipMemsetAsync(d.g.Ghist, 0, bytes, stream)) != hipSuccess) return e;
       if ((e = hipMemsetAsync(d.g.Hhist, 0, bytes, stream)) != hipSuccess) return e;
-      hipLaunchKernelGGL(grow_deep_hist_kernel, dim3(plan.hist_blocks), block, 0, stream, d, batch0, nslots);
+      if (sampled)
+        hipLaunchKernelGGL(grow_deep_hist_sampled_kernel, dim3(plan.hist_blocks, (ncols + kDeepPackFeatures - 1) / kDeepPackFeatures),
+                           block, 0, stream, d, round, batch0, nslots);
+      else hipLaunchKernelGGL(grow_deep_hist_kernel, dim3(plan.hist_blocks), block, 0, stream, d, batch0, nslots);
       if ((e = hipGetLastError()) != hipSuccess) return e;
-      const uint32_t waves = nslots * d.g.num_feature;
-      hipLaunchKernelGGL(grow_deep_split_kernel<0>, dim3((waves + kWaves - 1) / kWaves), block, 0, stream, d, level, round, batch0);
+      const dim3 waves((nslots * ncols + kWaves - 1) / kWaves);
+      if (sampled) hipLaunchKernelGGL(grow_deep_split_sampled_kernel<0>, waves, block, 0, stream, d, level, round, batch0);
+      else hipLaunchKernelGGL(grow_deep_split_kernel<0>, waves, block, 0, stream, d, level, round, batch0);
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    hipLaunchKernelGGL(grow_deep_split_kernel<1>, dim3(1), block, 0, stream, d, level, round, 0u);
+    if (sampled) hipLaunchKernelGGL(grow_deep_split_sampled_kernel<1>, dim3(1), block, 0, stream, d, level, round, 0u);
+    else hipLaunchKernelGGL(grow_deep_split_kernel<1>, dim3(1), block, 0, stream, d, level, round, 0u);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(grow_deep_partition_kernel, rows, block, 0, stream, d, round);
     if ((e = hipGetLastError()) != hipSuccess) return e;

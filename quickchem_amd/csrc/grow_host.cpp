@@ -344,6 +344,31 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_plan_deep(uint64_
   }
 }
 
+// plan_grow_deep_sampled over n_sel of the num_feature features (OHXBoosterBoostTreesDeepSampled): info, levels and deep
+// as ohx_grow_plan_deep's over n_sel columns, with info[3] the bin planes of all num_feature features
+extern "C" __attribute__((visibility("default"))) int ohx_grow_plan_deep_sampled(uint64_t nrow, uint32_t num_feature, uint32_t n_sel,
+                                                                                uint64_t ncuts, int max_depth, int num_cus,
+                                                                                uint64_t info[8], uint64_t* levels, uint64_t deep[6]) {
+  try {
+    if (max_depth < 1 || max_depth > kGrowDeepMaxDepth) throw OhxError("ohx_grow_plan_deep_sampled: max_depth must be in 1..18");
+    if (nrow == 0) throw OhxError("ohx_grow_plan_deep_sampled: no rows");
+    if (num_feature == 0 || num_feature > kGrowMaxFeatures || n_sel == 0 || n_sel > num_feature)
+      throw OhxError("ohx_grow_plan_deep_sampled: 1 to 128 features and 1 to num_feature of them selected");
+    const GrowDeepPlan p = plan_grow_deep_sampled(nrow, num_feature, n_sel, ncuts, max_depth, num_cus);
+    write_plan(p.lds, p.lds.bins_bytes, kGrowWeightedPairBytes, info, levels);
+    deep[0] = p.batch;
+    deep[1] = p.hist_blocks;
+    deep[2] = kGrowBlock;
+    deep[3] = p.scratch_bytes;
+    deep[4] = p.best_bytes;
+    deep[5] = p.node_stride;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
 // grow_chunked_children: the child ids a block of `width` lanes hands the `count` open nodes of a level whose split
 // flags are flag[]; left[s] is written where flag[s] != 0; *splits: their number
 extern "C" __attribute__((visibility("default"))) int ohx_grow_deep_children(const uint8_t* flag, uint32_t count, uint32_t width,

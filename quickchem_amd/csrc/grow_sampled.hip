@@ -179,8 +179,10 @@ int launch_grow_bag(const GrowArgs& a, const GrowPlan& plan, void* stream_) {
   return hipGetLastError();
 }
 
-int launch_grow_tree_sampled(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream_) {
-  hipStream_t stream = static_cast<hipStream_t>(stream_);
+namespace {
+
+hipError_t sampled_levels(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, hipStream_t stream,
+                          bool leaf) {
   if (!sampled_args_sound(a) || a.features == nullptr || !(a.min_child_weight >= 0.0)) return hipErrorInvalidValue;
   return grow_launch_tree(
       a, plan, levels, round, stream, a.n_sel, kGrowWeightedPairBytes, 0,
@@ -191,7 +193,17 @@ int launch_grow_tree_sampled(const GrowArgs& a, const GrowPlan& plan, const Grow
       [&](uint32_t blocks, uint32_t d) {
         hipLaunchKernelGGL(grow_split_sampled_kernel<0>, dim3(blocks), dim3(kBlock), 0, stream, a, d, round);
       },
-      [&](uint32_t d) { hipLaunchKernelGGL(grow_split_sampled_kernel<1>, dim3(1), dim3(kBlock), 0, stream, a, d, round); });
+      [&](uint32_t d) { hipLaunchKernelGGL(grow_split_sampled_kernel<1>, dim3(1), dim3(kBlock), 0, stream, a, d, round); }, leaf);
+}
+
+}  // namespace
+
+int launch_grow_tree_sampled(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream) {
+  return sampled_levels(a, plan, levels, round, static_cast<hipStream_t>(stream), true);
+}
+
+int launch_grow_levels_sampled(const GrowArgs& a, const GrowPlan& plan, const GrowPlan& levels, uint32_t round, void* stream) {
+  return sampled_levels(a, plan, levels, round, static_cast<hipStream_t>(stream), false);
 }
 
 }  // namespace ohx

@@ -532,6 +532,46 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
+      !  Row and column subsampling for trees deeper than eight levels (include/ohxgb.h; docs/24_deep_sampled.md).
+      !  Interface blocks only.  The sampled call's argument lists with max_depth in 1..18; with max_depth > 8 the call
+      !  waits once a level from level 7 on
+      function OHXBoosterBoostTreesDeepSampled(handle, dmat, labels, weights, nlabel, eval_dmat, eval_labels, eval_weights, &
+            eval_nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_weight, subsample, &
+            colsample_bytree, seed, patience, train_rmse, eval_rmse, rounds_run, best_round, nodes_added) &
+            bind(C, name="OHXBoosterBoostTreesDeepSampled") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat, weights, eval_dmat, eval_labels, eval_weights
+         real(c_float), intent(in)       :: labels(*)
+         integer(c_int64_t), value       :: nlabel, eval_nlabel
+         integer(c_int64_t), intent(in)  :: cut_ptr(*)
+         real(c_float), intent(in)       :: cut_values(*)
+         integer(c_int), value           :: rounds, max_depth, patience
+         real(c_float), value            :: eta, lambda, gamma, min_child_weight, subsample, colsample_bytree
+         integer(c_int64_t), value       :: seed
+         type(c_ptr), value              :: train_rmse, eval_rmse
+         integer(c_int), intent(out)     :: rounds_run, best_round
+         type(c_ptr), value              :: nodes_added
+         integer(c_int)                  :: rc
+      end function
+
+      function OHXBoosterBoostTreesDeepSampledDevice(handle, dmat, d_labels, d_weights, nlabel, eval_dmat, d_eval_labels, &
+            d_eval_weights, eval_nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_weight, &
+            subsample, colsample_bytree, seed, patience, train_rmse, eval_rmse, rounds_run, best_round, nodes_added, &
+            stream) bind(C, name="OHXBoosterBoostTreesDeepSampledDevice") result(rc)
+         import :: c_int, c_ptr, c_float, c_int64_t
+         type(c_ptr), value              :: handle, dmat, d_labels, d_weights, eval_dmat, d_eval_labels, d_eval_weights, stream
+         integer(c_int64_t), value       :: nlabel, eval_nlabel
+         integer(c_int64_t), intent(in)  :: cut_ptr(*)
+         real(c_float), intent(in)       :: cut_values(*)
+         integer(c_int), value           :: rounds, max_depth, patience
+         real(c_float), value            :: eta, lambda, gamma, min_child_weight, subsample, colsample_bytree
+         integer(c_int64_t), value       :: seed
+         type(c_ptr), value              :: train_rmse, eval_rmse
+         integer(c_int), intent(out)     :: rounds_run, best_round
+         type(c_ptr), value              :: nodes_added
+         integer(c_int)                  :: rc
+      end function
+
       !  data: a row-major host sample (nrow x ncol); cut_ptr: ncol + 1 entries out; needed: the cut values in all
       function OHXQuantileCuts(data, nrow, ncol, missing, max_bins, cut_ptr, cut_values, cap, needed) &
             bind(C, name="OHXQuantileCuts") result(rc)

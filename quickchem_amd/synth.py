@@ -121,6 +121,8 @@ def _load():
         lib.ohx_grow_deep_batch.restype = C.c_uint32
         lib.ohx_grow_plan_deep.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64),
                                            C.c_void_p, C.POINTER(C.c_uint64)]
+        lib.ohx_grow_plan_deep_sampled.argtypes = [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_int, C.c_int,
+                                                   C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64)]
         lib.ohx_grow_deep_children.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                                C.POINTER(C.c_uint32)]
         lib.ohx_cuts_select.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int, C.c_uint64, C.c_void_p,
@@ -572,6 +574,24 @@ def grow_plan_deep(nrow: int, num_feature: int = NFEAT, ncuts: int = 0, max_dept
             "levels": [dict(zip(names, (int(v) for v in row))) for row in lev],
             "batch": int(deep[0]), "deep_hist_blocks": int(deep[1]), "deep_block_rows": int(deep[2]),
             "scratch_bytes": int(deep[3]), "best_bytes": int(deep[4]), "node_stride": int(deep[5])}
+
+
+def grow_plan_deep_sampled(nrow: int, num_feature: int = NFEAT, n_sel: int = NFEAT, ncuts: int = 0, max_depth: int = 12,
+                           num_cus: int = 256):
+    """csrc/grow.hpp plan_grow_deep_sampled -> the dict of grow_plan_deep over the n_sel features a tree of
+    OHXBoosterBoostTreesDeepSampled sees (levels, hist_bytes, scratch_bytes and best_bytes count n_sel columns), with
+    bins_bytes the planes of all num_feature features, and n_sel."""
+    info = (C.c_uint64 * 8)()
+    deep = (C.c_uint64 * 6)()
+    lev = np.zeros((max(min(max_depth, 8), 1), 7), dtype=np.uint64)
+    _check(_load().ohx_grow_plan_deep_sampled(nrow, num_feature, n_sel, ncuts, max_depth, num_cus, info, lev.ctypes.data, deep))
+    names = ("slots", "node_group", "feat_group", "node_groups", "feat_groups", "hist_blocks", "lds_bytes")
+    return {"row_blocks": int(info[0]), "block_rows": int(info[1]), "bin_lds_bytes": int(info[2]),
+            "bins_bytes": int(info[3]), "hist_bytes": int(info[4]), "hist_block_rows": int(info[5]),
+            "max_pairs": int(info[6]), "pair_bytes": int(info[7]),
+            "levels": [dict(zip(names, (int(v) for v in row))) for row in lev],
+            "batch": int(deep[0]), "deep_hist_blocks": int(deep[1]), "deep_block_rows": int(deep[2]),
+            "scratch_bytes": int(deep[3]), "best_bytes": int(deep[4]), "node_stride": int(deep[5]), "n_sel": int(n_sel)}
 
 
 def grow_deep_children(flags, width: int, next_id: int):

@@ -31,7 +31,11 @@ a tree sees.  `--subsample 1 --colsample 1` is the sampled entry point on the we
 
 `--deep` times OHXBoosterBoostTreesDeepDevice (docs/23_deep_trees.md) in the same place, with any `--max-depth` up to 18
 and the weights `--weights` names (none: a NULL pointer); the plan written is plan_grow_deep's.  `--deep-only` skips the
-first-call timing and the refit, for a run under a kernel trace or a quick look at one depth."""
+first-call timing and the refit, for a run under a kernel trace or a quick look at one depth.
+
+`--deep` with `--subsample S` and / or `--colsample C` times OHXBoosterBoostTreesDeepSampledDevice
+(docs/24_deep_sampled.md) in the same place, with `--seed`; the plan written is plan_grow_deep_sampled's over the n_sel
+features a tree sees.  Without the two fractions `--deep` does what it did."""
 from __future__ import annotations
 
 import argparse
@@ -136,7 +140,7 @@ def main():
     ap.add_argument("--subsample", type=float, default=None, help="time OHXBoosterBoostTreesSampledDevice with this fraction of the rows a tree")
     ap.add_argument("--colsample", type=float, default=None, help="... and this fraction of the features a tree (colsample_bytree)")
     ap.add_argument("--seed", type=int, default=0, help="the seed of the sampled call's draws")
-    ap.add_argument("--deep", action="store_true", help="time OHXBoosterBoostTreesDeepDevice: --max-depth up to 18")
+    ap.add_argument("--deep", action="store_true", help="time OHXBoosterBoostTreesDeepDevice (with --subsample / --colsample: ...DeepSampledDevice): --max-depth up to 18")
     ap.add_argument("--deep-only", action="store_true", help="with --deep: one call a round count on a fresh booster, no refit")
     args = ap.parse_args()
     sampled = args.subsample is not None or args.colsample is not None
@@ -145,8 +149,8 @@ def main():
         args.colsample = 1.0 if args.colsample is None else args.colsample
     if sampled and args.holdout:
         ap.error("--subsample / --colsample time the call without a held-out set: leave --holdout out")
-    if args.deep and (sampled or args.holdout):
-        ap.error("--deep times the Deep call alone: leave --subsample / --colsample / --holdout out")
+    if args.deep and args.holdout:
+        ap.error("--deep times the call without a held-out set: leave --holdout out")
     if args.weights != "none" and args.holdout:
         ap.error("--weights times the call without a held-out set: leave --holdout out")
     assert torch.cuda.is_available(), "boost_timing needs the MI355X"
@@ -201,7 +205,12 @@ def main():
         res["cuts_full_plan"] = synth.cuts_plan(n, 1, F, cus)
     ncuts = int(cuts[0][-1])
     res["cut_values"] = ncuts
-    if sampled:
+    if sampled and args.deep:
+        n_sel = int(synth.boost_features(args.seed, 0, F, args.colsample).size)
+        res["plan"] = synth.grow_plan_deep_sampled(n, F, n_sel, ncuts, args.max_depth, cus)
+        res["sampling"] = {"subsample": args.subsample, "colsample_bytree": args.colsample, "seed": args.seed}
+        res["deep"] = True
+    elif sampled:
         res["plan"] = synth.grow_plan_sampled(n, F, args.colsample, ncuts, args.max_depth, cus)
         res["sampling"] = {"subsample": args.subsample, "colsample_bytree": args.colsample, "seed": args.seed}
     elif args.deep:
@@ -237,10 +246,10 @@ def main():
         torch.cuda.synchronize()
         t = time.perf_counter()
         if sampled:
-            r = b.boost_trees_sampled_device(d, labels.data_ptr(), n, cuts, weights_ptr=weights.data_ptr() if weights is not None else 0,
-                                             rounds=rounds, max_depth=args.max_depth, eta=args.eta, reg_lambda=args.reg_lambda,
-                                             min_child_weight=1.0, subsample=args.subsample, colsample_bytree=args.colsample,
-                                             seed=args.seed, stream=stream)
+            call = b.boost_trees_deep_sampled_device if args.deep else b.boost_trees_sampled_device
+            r = call(d, labels.data_ptr(), n, cuts, weights_ptr=weights.data_ptr() if weights is not None else 0, rounds=rounds,
+                     max_depth=args.max_depth, eta=args.eta, reg_lambda=args.reg_lambda, min_child_weight=1.0,
+                     subsample=args.subsample, colsample_bytree=args.colsample, seed=args.seed, stream=stream)
             nodes = r["nodes_added"]
             last.update(rounds=rounds, train_rmse=r["train_rmse"].tolist())
         elif args.deep:
