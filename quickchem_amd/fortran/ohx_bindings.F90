@@ -20,6 +20,15 @@ module ohx_bindings
    public :: OHXBoosterGetNumCategoricalSplits
    public :: OHXSelectCells, OHXSelectCellsDevice, OHXGatherCells, OHXGatherCellsDevice
    public :: OHXScatterCells, OHXScatterCellsDevice
+   public :: OHXDMatrixCreateFromDevice
+   public :: OHXBoosterCountVisits, OHXBoosterCountVisitsDevice, OHXBoosterGetVisitCounts, OHXBoosterResetVisitCounts
+   public :: OHXBoosterRefreshCover, OHXBoosterRefitLeaves, OHXBoosterRefitLeavesDevice
+   public :: OHXBoosterBoostTrees, OHXBoosterBoostTreesDevice, OHXBoosterBoostTreesEval, OHXBoosterBoostTreesEvalDevice
+   public :: OHXBoosterBoostTreesWeighted, OHXBoosterBoostTreesWeightedDevice
+   public :: OHXBoosterBoostTreesSampled, OHXBoosterBoostTreesSampledDevice
+   public :: OHXBoosterBoostTreesDeep, OHXBoosterBoostTreesDeepDevice
+   public :: OHXBoosterBoostTreesDeepSampled, OHXBoosterBoostTreesDeepSampledDevice
+   public :: OHXQuantileCuts, OHXDMatrixQuantileCuts
    public :: ohx_last_error, ohx_c_string
 
    integer, parameter :: OHX_UNIQUE_ID_BYTES = 128
@@ -265,6 +274,18 @@ module ohx_bindings
          integer(c_int)                 :: rc
       end function
 
+      ! A DMatrix over rows that already lie in HBM (ohxgb.h part 2): d_data is the DEVICE address of nrow x ncol
+      ! real(c_float), row-major (in Fortran a (ncol, nrow) array); the matrix borrows it until XGDMatrixFree.
+      function OHXDMatrixCreateFromDevice(d_data, nrow, ncol, missing, out) &
+            bind(C, name="OHXDMatrixCreateFromDevice") result(rc)
+         import :: c_int, c_float, c_int64_t, c_ptr
+         type(c_ptr), value             :: d_data
+         integer(c_int64_t), value      :: nrow, ncol
+         real(c_float), value           :: missing
+         type(c_ptr), intent(out)       :: out
+         integer(c_int)                 :: rc
+      end function
+
       ! Optional hint: the DMatrix rows are rows row0.. of the (im,jm,*) gather (ohxgb.h); speed only.
       function OHXDMatrixSetGrid(handle, im, jm, row0) bind(C, name="OHXDMatrixSetGrid") result(rc)
          import :: c_int, c_ptr, c_int64_t
@@ -284,7 +305,7 @@ module ohx_bindings
       end function
 
       !  Node visit counts and the covers refreshed from them (include/ohxgb.h; docs/16_visit_counts.md).
-      !  Interface blocks only: nothing the oracle-linked drivers link calls them.
+      !  Called by tests/fortran/train_driver.F90; nothing the oracle-linked drivers link calls them.
       function OHXBoosterCountVisits(handle, dmat) bind(C, name="OHXBoosterCountVisits") result(rc)
          import :: c_int, c_ptr
          type(c_ptr), value :: handle, dmat
@@ -320,8 +341,8 @@ module ohx_bindings
          integer(c_int)       :: rc
       end function
 
-      !  Leaf refit (include/ohxgb.h; docs/17_leaf_refit.md).  Interface blocks only: nothing the oracle-linked drivers
-      !  link calls them.  labels: nlabel real(c_float) on the host; d_labels: their DEVICE address (c_ptr).
+      !  Leaf refit (include/ohxgb.h; docs/17_leaf_refit.md).  Called by tests/fortran/train_driver.F90; nothing the
+      !  oracle-linked drivers link calls them.  labels: nlabel real(c_float) on the host; d_labels: their DEVICE address (c_ptr).
       !  leaves_refit: c_loc of an integer(c_int64_t), or c_null_ptr - the header allows NULL
       function OHXBoosterRefitLeaves(handle, dmat, labels, nlabel, eta, lambda, unvisited, leaves_refit) &
             bind(C, name="OHXBoosterRefitLeaves") result(rc)
@@ -346,7 +367,8 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
-      !  Boosting new trees (include/ohxgb.h; docs/18_boost_trees.md).  Interface blocks only.  labels: nlabel
+      !  Called by tests/fortran/train_driver.F90.
+      !  Boosting new trees (include/ohxgb.h; docs/18_boost_trees.md).  labels: nlabel
       !  real(c_float) on the host; d_labels: their DEVICE address (c_ptr); cut_ptr / cut_values: HOST arrays in both
       !  forms.  nodes_added: c_loc of an integer(c_int64_t), or c_null_ptr
       function OHXBoosterBoostTrees(handle, dmat, labels, nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, &
@@ -378,7 +400,8 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
-      !  Boosting with a held-out set (include/ohxgb.h; docs/20_boost_eval.md).  Interface blocks only.  eval_dmat: a
+      !  Called by tests/fortran/train_driver.F90.
+      !  Boosting with a held-out set (include/ohxgb.h; docs/20_boost_eval.md).  eval_dmat: a
       !  second DMatrix or c_null_ptr; eval_labels: c_loc of eval_nlabel real(c_float) on the host (d_eval_labels: their
       !  DEVICE address), or c_null_ptr without a held-out set.  train_rmse / eval_rmse: c_loc of rounds + 1
       !  real(c_double), or c_null_ptr; rounds_run / best_round: integer(c_int) out; nodes_added as above
@@ -418,7 +441,8 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
-      !  Boosting with row weights (include/ohxgb.h; docs/21_row_weights.md).  Interface blocks only.  weights /
+      !  Called by tests/fortran/train_driver.F90.
+      !  Boosting with row weights (include/ohxgb.h; docs/21_row_weights.md).  weights /
       !  eval_weights: c_loc of nlabel / eval_nlabel real(c_float) on the host (d_weights / d_eval_weights: their DEVICE
       !  addresses), or c_null_ptr for weights of 1.  min_child_weight stands where min_child_rows stood.  The rest as above
       function OHXBoosterBoostTreesWeighted(handle, dmat, labels, weights, nlabel, eval_dmat, eval_labels, eval_weights, &
@@ -456,7 +480,8 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
-      !  Boosting with row and column subsampling (include/ohxgb.h; docs/22_sampling.md).  Interface blocks only.  The
+      !  Called by tests/fortran/train_driver.F90.
+      !  Boosting with row and column subsampling (include/ohxgb.h; docs/22_sampling.md).  The
       !  weighted call with subsample, colsample_bytree (both in (0, 1]) and seed (the 64 bits of a uint64) before patience
       function OHXBoosterBoostTreesSampled(handle, dmat, labels, weights, nlabel, eval_dmat, eval_labels, eval_weights, &
             eval_nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_weight, subsample, &
@@ -495,7 +520,8 @@ module ohx_bindings
          integer(c_int)                  :: rc
       end function
 
-      !  Trees deeper than eight levels (include/ohxgb.h; docs/23_deep_trees.md).  Interface blocks only.  The weighted
+      !  Called by tests/fortran/train_driver.F90.
+      !  Trees deeper than eight levels (include/ohxgb.h; docs/23_deep_trees.md).  The weighted
       !  call's argument lists with max_depth in 1..18; with max_depth > 8 the call waits once a level from level 7 on
       function OHXBoosterBoostTreesDeep(handle, dmat, labels, weights, nlabel, eval_dmat, eval_labels, eval_weights, &
             eval_nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_weight, patience, &
@@ -533,7 +559,8 @@ module ohx_bindings
       end function
 
       !  Row and column subsampling for trees deeper than eight levels (include/ohxgb.h; docs/24_deep_sampled.md).
-      !  Interface blocks only.  The sampled call's argument lists with max_depth in 1..18; with max_depth > 8 the call
+      !  Called by tests/fortran/train_driver.F90.
+      !  The sampled call's argument lists with max_depth in 1..18; with max_depth > 8 the call
       !  waits once a level from level 7 on
       function OHXBoosterBoostTreesDeepSampled(handle, dmat, labels, weights, nlabel, eval_dmat, eval_labels, eval_weights, &
             eval_nlabel, cut_ptr, cut_values, rounds, max_depth, eta, lambda, gamma, min_child_weight, subsample, &
