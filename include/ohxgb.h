@@ -202,6 +202,20 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *   "ohx_cat_kernel"  auto | direct : boosters with categorical splits: direct = margins by the kernel without LDS
  *                     too (auto: the tile kernel where a block's tiles fit a CU's LDS, up to 160 features)
  *   "ohx_device"      HIP device ordinal for this booster
+ *   "ohx_objective"   squarederror (default) | pseudohuber : the loss the OHXBoosterBoostTrees* calls fit, as the
+ *                     (gradient, hessian) pair of a row (defined bit for bit with OHXBoosterBoostTreesWeighted below;
+ *                     docs/26_objectives.md).  Any other value returns -1 and the message names "ohx_objective".  Kept on
+ *                     the handle, written into no model file; the forest's own objective name is not changed.  The name
+ *                     "objective" without the prefix is an xgboost parameter and is ignored.  With pseudohuber the calls
+ *                     that keep row counts, not hessian sums - OHXBoosterBoostTrees[Device], OHXBoosterBoostTreesEval[Device]
+ *                     - and OHXBoosterRefitLeaves[Device] return -1 before anything is enqueued; the message names
+ *                     OHXBoosterBoostTreesWeighted
+ *   "ohx_huber_slope" the slope delta of pseudohuber: a decimal number, finite, 2^-10 <= delta <= 256 (default 1).
+ *                     Anything else returns -1 and the message names "ohx_huber_slope"
+ *   "ohx_grow_pairs"  auto (default) | on : for tests and measurement.  on = squared error goes through the pair kernels
+ *                     too (a pass that writes every row's pair once a round, and histogram kernels that read it); auto =
+ *                     only an objective that needs them does.  The same bits either way.  With none of the three set
+ *                     every boost call runs the kernels it ran before they existed
  * None of them changes a prediction.
  * xgboost's own parameter names ("nthread", "predictor", ...) are accepted and
  * ignored. */
@@ -687,6 +701,26 @@ int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, con
  * (min_child_weight not finite or negative stands where min_child_rows < 1 stood); eval_weights given without a
  * held-out matrix; a weight that is not finite, is negative or is >= 256 (the message says "weight" for the training
  * set and "eval weight" for the held-out set); a training set whose W is 0, or a held-out set whose W is 0.
+ * The objective ("ohx_objective", "ohx_huber_slope" of XGBoosterSetParam).  What is stated above is squarederror.  In
+ * general a training row r has, at the start of every round, a pair (q, hq) made as follows; every operation is float32
+ * and rounds once, nothing is fused into a multiply-add, the division and the square root are IEEE:
+ *   z  = pred - y                      refused ("label") if not finite or |z| >= 256 - before the weight, as above
+ *   w  = weight (NULL: 1.0f)           refused ("weight") if not finite, < 0 or >= 256
+ *   squarederror:  g = z; h = 1.0f
+ *   pseudohuber:   d2 = delta * delta; z2 = z * z; s = sqrtf(1.0f + z2 / d2); g = z / s; c = d2 + z2; h = d2 / (c * s)
+ *   gw = g * w   refused ("label") if |gw| >= 256;   hw = h * w
+ *   q  = (int64) rint(gw * 2^24);      hq = (uint64) rint(hw * 2^24)     (h <= 1, so hq < 2^32)
+ * This restates PseudoHuberRegression::GetGradient of xgboost 1.6.0; parity with libxgboost is not pinned, the text above
+ * is the definition.  With delta >= 2^-10 and |z| < 256 nothing overflows (z2 / d2 < 2^36).  The pair does not depend on
+ * whether float32 denormals are flushed to zero: 1 + z2 / d2 and d2 + z2 absorb a denormal z2, and a denormal g gives
+ * q = 0 either way.  A row that is out of the bag of a sampled call has the pair (0, 0); its label and its weight are
+ * checked all the same.  Everything downstream is the text above with this q and hq: the histograms, the candidates and
+ * their order, min_child_weight on Hd, sum_hess = (float)Hd, base_weight and the leaf.  The metric is unchanged - the RMSE
+ * of the margin against the labels, weighted by rint(w * 2^24), whose W is constant over the rounds - and so are the stop
+ * rule, what is kept, all or nothing, the forms and "not capturable".  With pseudohuber a round whose root has H == 0
+ * (every in-bag hq rounds to 0: a leaf would divide by lambda alone) is refused, the message says "hessian", and the
+ * forest and every output are untouched, as for "bag".  The same holds for OHXBoosterBoostTreesSampled, ...Deep and
+ * ...DeepSampled.
  * Everything else is OHXBoosterBoostTreesEval's: all or nothing; what a success drops; patience == 0 waits once, at the
  * end, and patience >= 1 waits once a round; eval_dmat == NULL works as there, and eval_weights must then be NULL.  Not
  * capturable.  The host form stages the weights with the labels; the device form takes d_weights and d_eval_weights in

@@ -652,6 +652,7 @@ struct RefitState {
 struct GrowState {
   int device = -1;
   bool prepared = false;               // prepare_grow has raised the LDS limits on `device`
+  bool pairs_prepared = false;         // grow_lds_limits_pairs has: at the first call that takes the pair path
   DevBuf<uint8_t> d_bins;
   DevBuf<uint16_t> d_pos;
   DevBuf<float> d_pred, d_labels, d_cuts;
@@ -682,7 +683,16 @@ struct GrowState {
   // at hand as the held-out walk reads it
   DevBuf<uint32_t> d_pos_deep;
   DevBuf<uint8_t> d_eval_nodes;          // [node stride] x kGrowEvalNodeBytes
+  // the pair path (grow_pairs.hip): the planes of the round at hand, 12 bytes a row, and the list 0 .. F - 1; allocated
+  // only where the pair path runs
+  DevBuf<long long> d_pair_q;
+  DevBuf<uint32_t> d_pair_hq;
+  DevBuf<uint8_t> d_identity;
+  PinnedBuf<uint8_t> h_identity;
   void release_device() {
+    d_pair_q.release();
+    d_pair_hq.release();
+    d_identity.release();
     d_bag.release();
     d_features.release();
     d_pos_deep.release();
@@ -699,6 +709,7 @@ struct GrowState {
     d_nodes.release();
     d_state.release();
     prepared = false;
+    pairs_prepared = false;
   }
 };
 
@@ -842,6 +853,10 @@ struct BoosterObj {
   bool visits_use_lds = false;          // "ohx_visits_kernel" = lds: trees whose leaf histogram fits in LDS keep it there
                                         // (auto and global: every tree the global way - the faster at C360; same integers)
   uint32_t visits_lds_leaves = 0;       // "ohx_visits_lds_leaves": leaves a block's LDS histogram may hold (0 = what fits)
+  // boosting (docs/26_objectives.md): kept on the handle, never written into a model file
+  uint32_t grow_objective = kGrowObjSquared;   // "ohx_objective": squarederror or pseudohuber
+  float grow_slope = 1.0f;                     // "ohx_huber_slope": delta of pseudohuber
+  bool grow_pairs_on = false;                  // "ohx_grow_pairs" = on: squared error goes through the pair kernels too (same bits)
   std::unique_ptr<RefitState> refit;
   std::unique_ptr<GrowState> grow;
 };
@@ -2092,6 +2107,9 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
   if (!objective_is_identity(b.forest.objective))
     throw OhxError(std::string(what) + " refits squared-error leaves (gradient pred - label, hessian 1): the objective " +
                    b.forest.objective + " is not reg:squarederror");
+  if (b.grow_objective != kGrowObjSquared)
+    throw OhxError(std::string(what) + " refits squared-error leaves (hessian 1 a row): it is refused while ohx_objective=pseudohuber "
+                   "is set; grow with OHXBoosterBoostTreesWeighted, or set ohx_objective=squarederror; nothing was enqueued");
   if (labels == nullptr) throw OhxError(std::string(what) + ": labels is NULL");
   if (!std::isfinite(eta)) throw OhxError(std::string(what) + ": eta must be finite");
   if (!(std::isfinite(lambda) && lambda >= 0.0f)) throw OhxError(std::string(what) + ": lambda must be finite and >= 0");
@@ -2314,6 +2332,11 @@ struct BoostKind {
   GrowDeepPlan deep;
   GrowDeepArgs deep_args;
   GrowLevelState* h_state = nullptr;   // where the Deep kind's tree launcher waits for the level word
+  // pairs or inline: with `pairs` a round's (gradient, hessian) pairs are made once by grow_pairs.hip's pair kernel and
+  // its histogram kernels read them (every objective but squared error, and squared error under ohx_grow_pairs = on);
+  // without, the histogram kernels of the kind make g = pred - label themselves
+  bool pairs = false;
+  GrowPairArgs pair_args;
   bool wide() const { return which != Plain; }
   // The call's one plan, asked for once: the level loop over `cols` histogram columns - F itself, or the n_sel features
   // a tree of a sampled call sees (compact histograms and candidates) - the streaming kernels, which do not depend on
@@ -2340,10 +2363,15 @@ struct BoostKind {
       case Deep: {
         GrowDeepArgs d = deep_args;
         d.g = a;
-        return (hipError_t)launch_grow_tree_deep(d, deep, round, h_state, stream);
+        return (hipError_t)(pairs ? launch_grow_tree_deep_pairs(d, pair_args, deep, round, h_state, stream)
+                                  : launch_grow_tree_deep(d, deep, round, h_state, stream));
       }
-      case Sampled: return (hipError_t)launch_grow_tree_sampled(a, plan, levels, round, stream);
-      case Weighted: return (hipError_t)launch_grow_tree_weighted(a, plan, levels, round, stream);
+      case Sampled:
+        return (hipError_t)(pairs ? launch_grow_tree_pairs(a, pair_args, plan, levels, round, stream)
+                                  : launch_grow_tree_sampled(a, plan, levels, round, stream));
+      case Weighted:
+        return (hipError_t)(pairs ? launch_grow_tree_pairs(a, pair_args, plan, levels, round, stream)
+                                  : launch_grow_tree_weighted(a, plan, levels, round, stream));
       default: return (hipError_t)launch_grow_tree(a, plan, levels, round, stream);
     }
   }
@@ -2382,6 +2410,9 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (!objective_is_identity(b.forest.objective))
     throw OhxError(w0 + " fits squared-error trees (gradient pred - label, hessian 1): the objective " + b.forest.objective +
                    " is not reg:squarederror");
+  if (b.grow_objective != kGrowObjSquared && !weighted)
+    throw OhxError(w0 + " keeps row counts, not hessian sums: with ohx_objective=pseudohuber call OHXBoosterBoostTreesWeighted "
+                   "(weights may be NULL) or a later form; nothing was enqueued and the forest is unchanged");
   if (!b.margin_error.empty()) throw OhxError(b.margin_error);
   if (c.labels == nullptr) throw OhxError(w0 + ": labels is NULL");
   if (c.cut_ptr == nullptr || c.cut_values == nullptr) throw OhxError(w0 + ": the cuts are NULL");
@@ -2443,6 +2474,10 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   // (the Deep entry points at max_depth <= 8 take the weighted or the sampled kind as it is)
   const bool deep = c.deep && max_depth > kGrowMaxDepth;
   BoostKind kind{deep ? BoostKind::Deep : sampled ? BoostKind::Sampled : weighted ? BoostKind::Weighted : BoostKind::Plain};
+  // (the Plain kind has no pair path: its hessian is a row count)
+  kind.pairs = weighted && (b.grow_objective != kGrowObjSquared || b.grow_pairs_on);
+  kind.pair_args.objective = b.grow_objective;
+  kind.pair_args.slope = b.grow_slope;
   // before anything is built or enqueued: building the state waits for the library's stream
   if (!host_form && stream_capturing(c.caller))
     refuse_in_capture("grow trees", (w0 + " is not capturable; call it outside the capture").c_str());
@@ -2459,6 +2494,10 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (!g.prepared) {
     HIP_CHECK((hipError_t)prepare_grow());
     g.prepared = true;
+  }
+  if (kind.pairs && !g.pairs_prepared) {
+    HIP_CHECK((hipError_t)grow_lds_limits_pairs());
+    g.pairs_prepared = true;
   }
   const uint64_t n = d.nrow, ncuts = c.cut_ptr[F];
   const size_t R = (size_t)c.rounds;
@@ -2497,6 +2536,13 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     if (host_form && wt.weights != nullptr) room(g.d_weights, n, 4, "the staged weights");
     if (host_form && wt.eval_weights != nullptr) room(g.d_eval_weights, ne, 4, "the staged eval weights");
     sums_room();
+  }
+  if (kind.pairs) {
+    room(g.d_pair_q, (size_t)(plan.pairs_bytes / kGrowPairRowBytes), 8, "the gradient plane of the pairs");
+    room(g.d_pair_hq, (size_t)(plan.pairs_bytes / kGrowPairRowBytes), 4, "the hessian plane of the pairs");
+    room(g.d_identity, F, 1, "the list of every feature");
+    g.h_identity.ensure(F);
+    for (uint32_t f = 0; f < F; ++f) g.h_identity.p[f] = (uint8_t)f;
   }
   const size_t bag_words = (size_t)((n + 63) / 64);
   if (sampled) {
@@ -2552,6 +2598,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   HIP_CHECK(hipMemsetAsync(g.d_pos.p, 0, n * sizeof(uint16_t), stream));
   if (deep) HIP_CHECK(hipMemsetAsync(g.d_pos_deep.p, 0, n * sizeof(uint32_t), stream));
   if (sampled) HIP_CHECK(hipMemcpyAsync(g.d_features.p, g.h_features.p, R * n_sel, hipMemcpyHostToDevice, stream));
+  if (kind.pairs) HIP_CHECK(hipMemcpyAsync(g.d_identity.p, g.h_identity.p, F, hipMemcpyHostToDevice, stream));
   if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_labels.p, c.labels, n * sizeof(float), hipMemcpyHostToDevice, stream));
   initial_margin(d, g.d_pred.p, n);
   if (ev.present) HIP_CHECK(hipMemsetAsync(g.d_sums.p, 0, nsums * sizeof(unsigned long long), stream));
@@ -2599,6 +2646,11 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     a.features = g.d_features.p;
     a.n_sel = n_sel;
     a.k_s = k_s;
+  }
+  if (kind.pairs) {
+    kind.pair_args.q = g.d_pair_q.p;
+    kind.pair_args.hq = g.d_pair_hq.p;
+    kind.pair_args.identity = g.d_identity.p;
   }
   if (deep) {
     kind.deep_args.pos = g.d_pos_deep.p;
@@ -2731,6 +2783,9 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     throw OhxError(w0 + ": a weight is not finite, is negative or reaches 256 at some training row; the forest is unchanged");
   if (flags & kGrowFlagEvalWeight)
     throw OhxError(w0 + ": an eval weight is not finite, is negative or reaches 256 at some held-out row; the forest is unchanged");
+  if (flags & kGrowFlagHess)
+    throw OhxError(w0 + ": the root of some round holds no hessian (every in-bag rint(h * w * 2^24) is 0: the residuals are far "
+                   "beyond ohx_huber_slope, the weights are 0, or no row was drawn); raise ohx_huber_slope; the forest is unchanged");
   if (flags & kGrowFlagBag)
     throw OhxError(w0 + ": the bag of some round holds no weight (every row drawn by subsample has rint(w * 2^24) == 0, or none "
                    "was drawn): raise subsample or change the seed; the forest is unchanged");
@@ -3266,6 +3321,20 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
         throw OhxError("ohx_visits_lds_leaves must be auto or a whole number >= 0");
     }
     b->visits_lds_leaves = (uint32_t)k;
+  } else if (n == "ohx_objective") {
+    // boosting: what a row's (gradient, hessian) pair is made from (docs/26_objectives.md); on the handle, in no file
+    if (v != "squarederror" && v != "pseudohuber") throw OhxError("ohx_objective must be squarederror or pseudohuber");
+    b->grow_objective = v == "pseudohuber" ? kGrowObjPseudoHuber : kGrowObjSquared;
+  } else if (n == "ohx_huber_slope") {
+    char* end = nullptr;
+    const float k = strtof(value, &end);
+    if (v.empty() || end == value || *end != '\0' || !grow_slope_sound(k))
+      throw OhxError("ohx_huber_slope must be a decimal number with 2^-10 <= slope <= 256");
+    b->grow_slope = k;
+  } else if (n == "ohx_grow_pairs") {
+    // "on": squared error goes through the pair kernels too (the same bits); auto: only an objective that needs them
+    if (v != "auto" && v != "on") throw OhxError("ohx_grow_pairs must be auto or on");
+    b->grow_pairs_on = v == "on";
   } else if (n == "ohx_device") {
     int k = atoi(value);
     if (k != b->device_pref) {

@@ -158,7 +158,9 @@ GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_
 }
 
 GrowPlan plan_grow_weighted(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus) {
-  return plan_grow_pairs(nrow, num_feature, ncuts, max_depth, num_cus, kGrowWeightedPairBytes);
+  GrowPlan p = plan_grow_pairs(nrow, num_feature, ncuts, max_depth, num_cus, kGrowWeightedPairBytes);
+  p.pairs_bytes = grow_pair_plane_bytes(nrow);   // allocated only where the pair path runs
+  return p;
 }
 
 GrowDeepPlan plan_grow_deep(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus) {

@@ -7,11 +7,13 @@
 // leaf solve is refit_solve_leaf itself (refit.hpp).
 //
 // What host and device share is in this header: the gain, the comparison of two candidates, the hessian policy of the
-// two kinds of hessian sum, the scan of one feature's bins over a policy, and the launch plan.  What the kernel files
-// share is in grow_device.hpp.
+// two kinds of hessian sum, the (gradient, hessian) pair of a row by the call's objective, the scan of one feature's bins
+// over a policy, and the launch plan.  What the kernel files share is in grow_device.hpp.
 #pragma once
 #include <algorithm>
+#include <cmath>
 #include <cstdint>
+#include <functional>
 #include <vector>
 
 #include "refit.hpp"
@@ -35,6 +37,7 @@ constexpr uint32_t kGrowFlagEvalLabel = 4u;    // the same as kGrowFlagLabel at 
 constexpr uint32_t kGrowFlagWeight = 8u;       // a training row's weight that is not finite, negative or >= 256
 constexpr uint32_t kGrowFlagEvalWeight = 16u;  // the same at a held-out row
 constexpr uint32_t kGrowFlagBag = 32u;         // a round whose bag of rows holds no weight (root H == 0)
+constexpr uint32_t kGrowFlagHess = 64u;        // pseudo-Huber: a round whose root holds no hessian (root H == 0)
 
 // gain(G, Hd) of the header: CalcGain of xgboost 1.6.0 with reg_alpha = 0 and max_delta_step = 0, on the fixed-point
 // gradient sum and the hessian sum as its policy (below) makes it a double
@@ -82,6 +85,54 @@ OHX_GROW_HD inline void grow_solve_leaf_weighted(int64_t G, uint64_t H, float et
   const float w = (float)(-((double)G * (1.0 / 16777216.0)) / (grow_hess(H) + (double)lambda));
   *weight = w;
   *leaf = w * eta;
+}
+
+// ---- the objective: a row's (gradient, hessian) pair in fixed point (design in docs/26_objectives.md) ----
+
+// "ohx_objective": what a row's pair is made from.  squarederror is g = z, h = 1; pseudohuber is xgboost 1.6.0's
+// PseudoHuberRegression::GetGradient with slope delta ("ohx_huber_slope").
+constexpr uint32_t kGrowObjSquared = 0, kGrowObjPseudoHuber = 1;
+constexpr float kGrowMinSlope = 0.0009765625f;   // 2^-10
+constexpr float kGrowMaxSlope = 256.0f;
+// (NaN fails both comparisons)
+inline bool grow_slope_sound(float slope) { return slope >= kGrowMinSlope && slope <= kGrowMaxSlope; }
+// Bytes of the pair planes of n rows: an int64 q and a uint32 hq a row
+constexpr uint64_t kGrowPairRowBytes = 8 + 4;
+inline uint64_t grow_pair_plane_bytes(uint64_t nrow) { return nrow * kGrowPairRowBytes; }
+
+// The pair of one row, the header's definition operation by operation: every operation is float32 and rounds once
+// (-ffp-contract=off: no fused multiply-add), the division and the square root are IEEE.  Returns the flags the row
+// raises (kGrowFlagLabel, kGrowFlagWeight), and then the pair (0, 0).  With slope >= 2^-10 and |z| < 256 nothing
+// overflows (z2 / d2 < 2^36), and the result does not depend on whether float32 denormals are flushed: 1 + z2 / d2
+// and d2 + z2 absorb a denormal z2, and a denormal g gives q = 0 either way.
+template <uint32_t OBJ>
+OHX_GROW_HD inline uint32_t grow_pair(float slope, float pred, float label, float w, int64_t* q, uint32_t* hq) {
+  *q = 0;
+  *hq = 0;
+  const float z = pred - label;
+  // the residual before the weight (a NaN fails the comparison)
+  if (!(__builtin_fabsf(z) < kRefitMaxAbsGrad)) return kGrowFlagLabel;
+  if (!grow_weight_sound(w)) return kGrowFlagWeight;
+  float g = z, h = 1.0f;
+  if (OBJ == kGrowObjPseudoHuber) {
+    const float d2 = slope * slope;
+    const float z2 = z * z;
+    const float s = sqrtf(1.0f + z2 / d2);
+    g = z / s;
+    const float c = d2 + z2;
+    h = d2 / (c * s);
+  }
+  const float gw = g * w;
+  if (!(__builtin_fabsf(gw) < kRefitMaxAbsGrad)) return kGrowFlagLabel;
+  const float hw = h * w;
+  *q = (int64_t)__builtin_rintf(gw * kRefitGradScale);
+  *hq = (uint32_t)(uint64_t)__builtin_rintf(hw * kRefitGradScale);   // h <= 1 and w < 256: below 2^32
+  return 0;
+}
+// the same with the objective as a value (the host's callers)
+inline uint32_t grow_pair_of(uint32_t objective, float slope, float pred, float label, float w, int64_t* q, uint32_t* hq) {
+  return objective == kGrowObjPseudoHuber ? grow_pair<kGrowObjPseudoHuber>(slope, pred, label, w, q, hq)
+                                          : grow_pair<kGrowObjSquared>(slope, pred, label, w, q, hq);
 }
 
 // "count": H counts rows (OHXBoosterBoostTrees, OHXBoosterBoostTreesEval).  Children hold min_child_rows rows each.
@@ -318,6 +369,7 @@ struct GrowPlan {
   std::vector<GrowLevelPlan> levels;   // max_depth entries
   uint64_t bins_bytes = 0;    // num_feature x nrow
   uint64_t hist_bytes = 0;    // the deepest level's global histograms: slots x num_feature x 256 x 16
+  uint64_t pairs_bytes = 0;   // the pair planes where the pair path runs (grow_pairs.hip): nrow x 12; 0 in plan_grow
 };
 GrowPlan plan_grow(uint64_t nrow, uint32_t num_feature, uint64_t ncuts, int max_depth, int num_cus);
 // the same for grow_hist_weighted_kernel: 16 bytes a bin, at most 40 (node, feature) pairs a block
@@ -425,6 +477,9 @@ inline int prepare_grow() {
   if (e == 0) e = grow_lds_limits_sampled();
   return e;
 }
+// The same for the pair path's histogram kernel (grow_pairs.hip), once per device before the first call that takes the
+// pair path and not before: a call at default settings touches nothing of that file, its code object included.
+int grow_lds_limits_pairs();
 // Enqueues the binning.  bins must be sized by the plan.  Returns a hipError_t.
 int launch_grow_bin(const GrowArgs& a, const GrowPlan& plan, void* stream);
 // Enqueue one tree, round `round`: per level the histogram memsets, the histogram, split and partition kernels, then
@@ -499,6 +554,36 @@ struct GrowDeepArgs {
 // (pinned); then the leaf kernel.  The tree ends at the first level without an open node.  a.g.pos and a.pos must be
 // zero and pred the margin so far.  Returns a hipError_t.
 int launch_grow_tree_deep(const GrowDeepArgs& a, const GrowDeepPlan& plan, uint32_t round, GrowLevelState* h_state, void* stream);
+// What differs between the Deep call's inline path and its pair path (grow_pairs.hip), as launches: `top` enqueues levels
+// 0 - 7 without the leaf kernel on the tree's own records (round 0 of its own table and list) and returns a hipError_t;
+// `hist` enqueues the histogram kernel of one batch of a deep level.  The level loop, its waits, the split phases of the
+// deep levels (they read histograms alone) and the widen, partition and leaf kernels are launch_grow_tree_deep's own.
+struct GrowDeepLaunches {
+  std::function<int(const GrowArgs& top, const GrowPlan& lds, void* stream)> top;
+  std::function<void(const GrowDeepArgs& d, uint32_t round, uint32_t batch0, uint32_t nslots, uint32_t hist_blocks, void* stream)> hist;
+};
+int launch_grow_tree_deep_with(const GrowDeepArgs& a, const GrowDeepPlan& plan, uint32_t round, GrowLevelState* h_state,
+                               void* stream, const GrowDeepLaunches& launches);
+
+// ---- the pair path (grow_pairs.hip; design in docs/26_objectives.md) ----
+
+// What the pair kernels take beyond GrowArgs: the planes the pair kernel writes once a round and the histogram kernels
+// read, the objective, and the list that stands for "every feature" where the call has no list of its own.
+struct GrowPairArgs {
+  long long* q = nullptr;            // [nrow] rint(g * w * 2^24)
+  uint32_t* hq = nullptr;            // [nrow] rint(h * w * 2^24)
+  const uint8_t* identity = nullptr; // [num_feature] 0 .. F - 1
+  uint32_t objective = kGrowObjSquared;
+  float slope = 1.0f;
+};
+// launch_grow_tree_weighted (a.features == nullptr) or launch_grow_tree_sampled (a.features != nullptr) on pairs: the
+// pair kernel over every row, then the levels with the histogram kernel that reads the planes, then the leaf kernel.
+// With kGrowObjPseudoHuber a root without hessian raises kGrowFlagHess.  Returns a hipError_t.
+int launch_grow_tree_pairs(const GrowArgs& a, const GrowPairArgs& p, const GrowPlan& plan, const GrowPlan& levels, uint32_t round,
+                           void* stream);
+// launch_grow_tree_deep on pairs, with or without a bag and a list.  Returns a hipError_t.
+int launch_grow_tree_deep_pairs(const GrowDeepArgs& a, const GrowPairArgs& p, const GrowDeepPlan& plan, uint32_t round,
+                                GrowLevelState* h_state, void* stream);
 // Enqueues grow_deep_stage_kernel and grow_deep_walk_sse_kernel: eval_nodes from the records of tree `round`, then
 // launch_grow_walk_sse_weighted's walk and sums over the rows of `a`, its nodes read from HBM.  Returns a hipError_t.
 int launch_grow_walk_sse_deep(const GrowEvalArgs& a, const GrowDeepArgs& d, uint32_t blocks, uint32_t round, uint32_t set,

@@ -28,6 +28,8 @@
 //   grow_deep_split_sampled_kernel<1>  the chunked walk of grow_deep_split_kernel<1> (grow_deep_split_chunks, written
 //                                      once) over n_sel columns.
 // The widen, partition, leaf, stage and walk kernels see every row, in or out of the bag, and are the ones above.
+// The level loop on the host (launch_grow_tree_deep_with) takes the launches of levels 0 - 7 and of a deep level's
+// histogram as parameters: launch_grow_tree_deep gives it this file's, the pair path (grow_pairs.hip) its own.
 // Only integer adds: no float atomics, no compare-and-swap loops, and the same trees and sums whatever the order of the
 // rows, the batch size or the launch shape.
 #include <hip/hip_runtime.h>
@@ -385,18 +387,35 @@ bool deep_args_sound(const GrowDeepArgs& d, const GrowDeepPlan& plan) {
 
 }  // namespace
 
+// The inline path's launches: the gradient is made in the histogram kernels, from pred, label and weight.
 int launch_grow_tree_deep(const GrowDeepArgs& d, const GrowDeepPlan& plan, uint32_t round, GrowLevelState* h_state, void* stream_) {
+  GrowDeepLaunches l;
+  // levels 0 - 7: the weighted call's kernels, or the sampled call's over the bag and the tree's list
+  l.top = [](const GrowArgs& top, const GrowPlan& lds, void* s) {
+    return top.features != nullptr ? launch_grow_levels_sampled(top, lds, lds, 0, s) : launch_grow_levels_weighted(top, lds, lds, 0, s);
+  };
+  l.hist = [](const GrowDeepArgs& a, uint32_t r, uint32_t batch0, uint32_t nslots, uint32_t hist_blocks, void* s) {
+    hipStream_t stream = static_cast<hipStream_t>(s);
+    if (a.g.features != nullptr)
+      hipLaunchKernelGGL(grow_deep_hist_sampled_kernel, dim3(hist_blocks, (a.g.n_sel + kDeepPackFeatures - 1) / kDeepPackFeatures),
+                         dim3(kBlock), 0, stream, a, r, batch0, nslots);
+    else hipLaunchKernelGGL(grow_deep_hist_kernel, dim3(hist_blocks), dim3(kBlock), 0, stream, a, batch0, nslots);
+  };
+  return launch_grow_tree_deep_with(d, plan, round, h_state, stream_, l);
+}
+
+int launch_grow_tree_deep_with(const GrowDeepArgs& d, const GrowDeepPlan& plan, uint32_t round, GrowLevelState* h_state,
+                               void* stream_, const GrowDeepLaunches& launches) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (!deep_args_sound(d, plan) || h_state == nullptr) return hipErrorInvalidValue;
-  // levels 0 - 7: the weighted call's kernels, or the sampled call's over the bag and the tree's list, on the tree's own
-  // records (a tree of 8 levels has at most 511 of them, and no more than 2 * nrow - 1: within the stride either way)
+  if (!deep_args_sound(d, plan) || h_state == nullptr || !launches.top || !launches.hist) return hipErrorInvalidValue;
+  // levels 0 - 7 on the tree's own records (a tree of 8 levels has at most 511 of them, and no more than 2 * nrow - 1:
+  // within the stride either way)
   const bool sampled = d.g.features != nullptr;
   const uint32_t ncols = deep_columns(d.g);
   GrowArgs top = tree_args(d, round);
   top.max_depth = kGrowMaxDepth;
   if (sampled) top.features += (uint64_t)round * ncols;   // round 0 of its own list, as of its own records
-  hipError_t e = (hipError_t)(sampled ? launch_grow_levels_sampled(top, plan.lds, plan.lds, 0, stream)
-                                      : launch_grow_levels_weighted(top, plan.lds, plan.lds, 0, stream));
+  hipError_t e = (hipError_t)launches.top(top, plan.lds, stream);
   if (e != hipSuccess) return e;
   // the level word after phase 1 of level d - 1: the open nodes of level d
   auto level_word = [&]() {
@@ -417,10 +436,7 @@ int launch_grow_tree_deep(const GrowDeepArgs& d, const GrowDeepPlan& plan, uint3
       const size_t bytes = (size_t)nslots * ncols * kGrowBins * sizeof(unsigned long long);
       if ((e = hipMemsetAsync(d.g.Ghist, 0, bytes, stream)) != hipSuccess) return e;
       if ((e = hipMemsetAsync(d.g.Hhist, 0, bytes, stream)) != hipSuccess) return e;
-      if (sampled)
-        hipLaunchKernelGGL(grow_deep_hist_sampled_kernel, dim3(plan.hist_blocks, (ncols + kDeepPackFeatures - 1) / kDeepPackFeatures),
-                           block, 0, stream, d, round, batch0, nslots);
-      else hipLaunchKernelGGL(grow_deep_hist_kernel, dim3(plan.hist_blocks), block, 0, stream, d, batch0, nslots);
+      launches.hist(d, round, batch0, nslots, plan.hist_blocks, stream);
       if ((e = hipGetLastError()) != hipSuccess) return e;
       const dim3 waves((nslots * ncols + kWaves - 1) / kWaves);
       if (sampled) hipLaunchKernelGGL(grow_deep_split_sampled_kernel<0>, waves, block, 0, stream, d, level, round, batch0);

@@ -382,3 +382,39 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_deep_children(con
     return -1;
   }
 }
+
+// ---- the objective's pair (docs/26_objectives.md) ----
+
+// grow.hpp grow_pair over n rows: objective 0 squarederror, 1 pseudohuber with `slope`.  w may be NULL (every weight
+// 1.0f).  q int64 [n], hq uint32 [n]; *flags: the kGrowFlag* bits the rows raise together (a row that raises one has the
+// pair (0, 0)).  An objective or a slope the library refuses is an error.
+extern "C" __attribute__((visibility("default"))) int ohx_grow_pairs(uint32_t objective, float slope, const float* pred,
+                                                                    const float* y, const float* w, uint64_t n, int64_t* q,
+                                                                    uint32_t* hq, uint32_t* flags) {
+  try {
+    if (objective != kGrowObjSquared && objective != kGrowObjPseudoHuber) throw OhxError("ohx_grow_pairs: objective must be 0 or 1");
+    if (objective == kGrowObjPseudoHuber && !grow_slope_sound(slope)) throw OhxError("ohx_grow_pairs: 2^-10 <= slope <= 256");
+    uint32_t raised = 0;
+    for (uint64_t r = 0; r < n; ++r) raised |= grow_pair_of(objective, slope, pred[r], y[r], w != nullptr ? w[r] : 1.0f, &q[r], &hq[r]);
+    *flags = raised;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// the bytes of the pair planes in the plan of n rows, and the bytes a row
+extern "C" __attribute__((visibility("default"))) int ohx_grow_pairs_plan(uint64_t nrow, uint32_t num_feature, uint64_t ncuts,
+                                                                         int max_depth, int num_cus, uint64_t info[2]) {
+  try {
+    if (max_depth < 1 || max_depth > kGrowDeepMaxDepth) throw OhxError("ohx_grow_pairs_plan: max_depth must be in 1..18");
+    if (nrow == 0) throw OhxError("ohx_grow_pairs_plan: no rows");
+    info[0] = plan_grow_deep(nrow, num_feature, ncuts, max_depth, num_cus).lds.pairs_bytes;
+    info[1] = kGrowPairRowBytes;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}

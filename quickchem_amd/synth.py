@@ -125,6 +125,9 @@ def _load():
                                                    C.POINTER(C.c_uint64), C.c_void_p, C.POINTER(C.c_uint64)]
         lib.ohx_grow_deep_children.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p,
                                                C.POINTER(C.c_uint32)]
+        lib.ohx_grow_pairs.argtypes = [C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                       C.c_void_p, C.POINTER(C.c_uint32)]
+        lib.ohx_grow_pairs_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         lib.ohx_cuts_select.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int, C.c_uint64, C.c_void_p,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_cuts_keys.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -603,6 +606,34 @@ def grow_deep_children(flags, width: int, next_id: int):
     n = C.c_uint32()
     _check(_load().ohx_grow_deep_children(f.ctypes.data, f.size, width, next_id, left.ctypes.data, C.byref(n)))
     return left[:f.size], int(n.value)
+
+
+GROW_OBJECTIVES = {"squarederror": 0, "pseudohuber": 1}
+GROW_FLAG_LABEL, GROW_FLAG_WEIGHT = 1, 8   # csrc/grow.hpp kGrowFlagLabel, kGrowFlagWeight
+
+
+def ohx_grow_pairs(objective: str, slope: float, pred, y, w=None):
+    """csrc/grow.hpp grow_pair over the rows: the fixed-point (gradient, hessian) pair of every row by `objective`
+    ("squarederror" or "pseudohuber" with `slope`) -> (q int64 [n], hq uint32 [n], flags).  A row that raises a flag
+    (GROW_FLAG_LABEL, GROW_FLAG_WEIGHT) has the pair (0, 0).  w None: every weight is 1."""
+    pred = np.ascontiguousarray(pred, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    assert pred.shape == y.shape and pred.ndim == 1
+    wa = None if w is None else np.ascontiguousarray(w, dtype=np.float32)
+    assert wa is None or wa.shape == y.shape
+    q = np.zeros(max(y.size, 1), dtype=np.int64)
+    hq = np.zeros(max(y.size, 1), dtype=np.uint32)
+    flags = C.c_uint32()
+    _check(_load().ohx_grow_pairs(GROW_OBJECTIVES[objective], float(slope), pred.ctypes.data, y.ctypes.data,
+                                  None if wa is None else wa.ctypes.data, y.size, q.ctypes.data, hq.ctypes.data, C.byref(flags)))
+    return q[:y.size], hq[:y.size], int(flags.value)
+
+
+def grow_pairs_plan(nrow: int, num_feature: int, ncuts: int, max_depth: int, num_cus: int):
+    """The pair planes in the plan of a call (csrc/grow.hpp GrowPlan.pairs_bytes) -> {"pairs_bytes", "row_bytes"}."""
+    info = (C.c_uint64 * 2)()
+    _check(_load().ohx_grow_pairs_plan(nrow, num_feature, ncuts, max_depth, num_cus, info))
+    return {"pairs_bytes": int(info[0]), "row_bytes": int(info[1])}
 
 
 def boost_weighted_rmse(p2: int, p1: int, p0: int, W: int) -> float:

@@ -1,0 +1,347 @@
+"""The boosting objectives on the GPU (csrc/grow_pairs.hip; "ohx_objective", "ohx_huber_slope", "ohx_grow_pairs" of
+XGBoosterSetParam).  Every array of every new tree, nodes_added, rounds_run and best_round are compared as integers or bit
+for bit, both RMSE arrays with ==, and models byte for byte in all three formats.
+
+The expected values are the restatement's (tests/grow_objective_support.py, written from the header) and, where the
+header states an equality, another call on a twin booster: squared error through the pair kernels against the inline
+kernels.  The model of every case has no tree, so the margin a restatement starts from is the model's base.  What a case
+is meant to reach - a level beyond 7, more open nodes than a batch holds, hessians that change from round to round - is
+asserted from the restatement before the GPU is asked."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from quickchem_amd import capi, synth
+from tests import grow_deep_support as D
+from tests import grow_objective_support as O
+from tests import grow_support as G
+from tests.test_gpu_grow import held, same_new_trees
+from tests.test_gpu_grow_eval import same_result, saved
+
+pytestmark = pytest.mark.gpu
+
+NAN = float("nan")
+KINDS = ("weighted", "sampled", "deep", "deep_sampled")
+SLOPES = (0.5, 1.0, 3.7)
+NFEAT = 4                     # colsample 0.5 keeps two of them
+N, HELD = 4097, 1300
+ROWS_PAST_A_STRIDE = 256 * 8 * 256 + 4097 + 64 + 1   # the streaming grids hold 8 blocks of 256 rows a CU: a second trip
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    torch.cuda.set_device(0)
+    return torch
+
+
+def kind_kw(kind, deep_depth=11):
+    """The hyper-parameters of a kind, as the Python binding names them."""
+    kw = dict(eta=0.125, reg_lambda=1.0, min_child_weight=0.0, max_depth=deep_depth if "deep" in kind else 6)
+    if "sampled" in kind:
+        kw.update(subsample=0.5, colsample_bytree=0.5, seed=11)
+    return kw
+
+
+def restated(kind, objective, slope, n=N, seed=26, rounds=2, held_out=HELD, patience=0, deep_depth=11, **more):
+    kw = kind_kw(kind, deep_depth)
+    return O.restated(objective, slope, n, seed, kw["max_depth"], nfeat=NFEAT, rounds=rounds, held_out=held_out,
+                      patience=patience, subsample=kw.get("subsample", 1.0), colsample=kw.get("colsample_bytree", 1.0),
+                      draw_seed=kw.get("seed", 0), **more)
+
+
+def booster(params=(), nfeat=NFEAT, base=O.BASE):
+    b = capi.Booster(model_buffer=G.empty_model(nfeat, base=base))
+    for k, v in params:
+        b.set_param(k, v)
+    return b
+
+
+def call(torch, b, kind, x, y, w, cuts, ev, device=False, grid=False, **kw):
+    """One call of `kind` in the host or the device form -> (the result dict, the matrices to free)."""
+    keep = []
+    if device:
+        s = torch.cuda.Stream()
+        with torch.cuda.stream(s):
+            tx, ty = torch.from_numpy(x).to("cuda"), torch.from_numpy(y).to("cuda")
+            tw = torch.from_numpy(w).to("cuda") if w is not None else None
+            if ev is not None:
+                tex, tey = torch.from_numpy(ev[0]).to("cuda"), torch.from_numpy(ev[2]).to("cuda")
+                tew = torch.from_numpy(ev[3]).to("cuda") if ev[3] is not None else None
+        s.synchronize()
+        d = capi.DMatrix(device_ptr=tx.data_ptr(), nrow=x.shape[0], ncol=x.shape[1], missing=NAN)
+        ed = capi.DMatrix(device_ptr=tex.data_ptr(), nrow=ev[0].shape[0], ncol=ev[0].shape[1], missing=NAN) if ev is not None else None
+        es = (ed, tey.data_ptr(), len(ev[2]), tew.data_ptr() if tew is not None else 0) if ev is not None else None
+        got = getattr(b, "boost_trees_" + kind + "_device")(d, ty.data_ptr(), len(y), cuts, weights_ptr=tw.data_ptr() if tw is not None else 0,
+                                                          eval_set=es, stream=s.cuda_stream, **kw)
+    else:
+        d = capi.DMatrix(x, missing=NAN)
+        ed = capi.DMatrix(ev[0], missing=ev[1]) if ev is not None else None
+        if grid:
+            d.set_grid(17, 241, 0)
+        got = getattr(b, "boost_trees_" + kind)(d, y, cuts, weights=w, eval_set=(ed, ev[2], ev[3]) if ev is not None else None, **kw)
+    keep += [m for m in (d, ed) if m is not None]
+    return got, keep
+
+
+def done(b, mats):
+    for m in mats:
+        m.free()
+    b.free()
+
+
+def same_arrays(got, other, what):
+    for k in ("train_rmse", "eval_rmse"):
+        assert (got[k] is None) == (other[k] is None) and (got[k] is None or got[k].tolist() == other[k].tolist()), (what, k)
+    for k in ("rounds_run", "best_round", "nodes_added"):
+        assert got[k] == other[k], (what, k, got[k], other[k])
+
+
+# ---- 1. squared error through the pair kernels against the inline kernels ----
+
+@pytest.mark.parametrize("device", (False, True), ids=("host", "device"))
+@pytest.mark.parametrize("kind", KINDS)
+def test_squared_error_by_the_pair_kernels_is_the_inline_path_bit_for_bit(torch_cuda, tmp_path, kind, device):
+    x, y, w, cuts, ev = O.inputs(N, 261, NFEAT, 64, HELD)
+    kw = dict(kind_kw(kind), rounds=3)
+    results = []
+    for params in ((), (("ohx_grow_pairs", "on"),)):
+        b = booster(params)
+        got, mats = call(torch_cuda, b, kind, x, y, w, cuts, ev, device=device, **kw)
+        results.append((got, saved(b, tmp_path)))
+        done(b, mats)
+    (inline, inline_bytes), (by_pairs, pair_bytes) = results
+    assert inline["nodes_added"] > 60 and inline["rounds_run"] == 3
+    same_arrays(by_pairs, inline, kind)
+    assert pair_bytes == inline_bytes, kind
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_rows_past_one_stride_of_the_streaming_grids(torch_cuda, tmp_path, kind):
+    """More rows than 8 blocks of 256 a CU hold in one trip, and a last bag word that is not full: the pair kernel, both
+    histogram kernels and the inline path take a second trip."""
+    n = ROWS_PAST_A_STRIDE
+    assert n % 64 != 0
+    x, y, w, _, _ = O.inputs(n, 262, NFEAT, 8, 0)
+    cuts = G.quantile_cuts(x[:N], NAN, 16)
+    kw = dict(kind_kw(kind, deep_depth=10), rounds=2, max_depth=10 if "deep" in kind else 3)
+    results = []
+    for params in ((), (("ohx_grow_pairs", "on"),), (("ohx_objective", "pseudohuber"),)):
+        b = booster(params)
+        got, mats = call(torch_cuda, b, kind, x, y, w, cuts, None, **kw)
+        results.append((got, saved(b, tmp_path)))
+        done(b, mats)
+    same_arrays(results[1][0], results[0][0], kind)
+    assert results[1][1] == results[0][1], kind
+    assert results[2][1] != results[0][1], "the loss is another one"
+
+
+# ---- 2. pseudo-Huber against the restatement ----
+
+def check(torch, tmp_path, kind, want, x, y, w, cuts, ev, params, what, device=False, base=O.BASE, **kw):
+    b = booster(params, nfeat=x.shape[1], base=base)
+    got, mats = call(torch, b, kind, x, y, w, cuts, ev, device=device, **kw)
+    same_result(got, want, what)
+    same_new_trees(held(b, tmp_path)[0], want["trees"], 0, what)
+    image = saved(b, tmp_path)
+    done(b, mats)
+    return got, image
+
+
+@pytest.mark.parametrize("slope", SLOPES)
+@pytest.mark.parametrize("kind", KINDS)
+def test_pseudohuber_against_the_restatement(torch_cuda, tmp_path, kind, slope):
+    x, y, w, cuts, ev, want = restated(kind, "pseudohuber", slope, rounds=3, patience=2)
+    assert np.count_nonzero(w == 0.0) > 300 and np.count_nonzero(np.abs(y) > 10.0) > 100, "zero weights and outlier labels"
+    assert want["best_round"] >= 1 and len(want["all_trees"]) >= 2 and not np.array_equal(want["hessians"][0], want["hessians"][1]), "the hessians move"
+    assert len(np.unique(want["hessians"][0])) > 1000, "and are no row weights"
+    if "deep" in kind:
+        assert D.depth_of(want["all_trees"][0]) > 8 and D.levels(want["all_trees"][0])[8][1] > 0, "level 8 splits"
+    kw = dict(kind_kw(kind), rounds=3, patience=2)
+    # the keyword arguments of the binding set the handle
+    got, image = check(torch_cuda, tmp_path, kind, want, x, y, w, cuts, ev, (), f"{kind} at {slope}", objective="pseudohuber",
+                       huber_slope=slope, **kw)
+    if slope == 1.0:   # the device form, its parameters set by XGBoosterSetParam
+        params = (("ohx_objective", "pseudohuber"), ("ohx_huber_slope", "1"))
+        _, device_image = check(torch_cuda, tmp_path, kind, want, x, y, w, cuts, ev, params, f"{kind}, device form", device=True, **kw)
+        assert device_image == image
+
+
+@pytest.mark.parametrize("kind,n,sampling", (("deep", 24000, {}), ("deep_sampled", 32000, dict(subsample=0.7, colsample_bytree=0.75, seed=11))))
+def test_pseudohuber_with_more_open_nodes_than_a_batch_holds(torch_cuda, tmp_path, kind, n, sampling):
+    """Unweighted rows at depth 16, one round (the rounds after the first are the cases above); the sampled case over 0.7
+    of the rows and three of the four features."""
+    x, y, w, cuts, ev, want = O.restated("pseudohuber", 1.0, n, 263, 16, nfeat=NFEAT, rounds=1, weighted=False,
+                                         subsample=sampling.get("subsample", 1.0), colsample=sampling.get("colsample_bytree", 1.0),
+                                         draw_seed=sampling.get("seed", 0))
+    batch = synth.grow_deep_batch()
+    assert max(o for o, _ in D.levels(want["trees"][0])) > batch, "a level of two batches"
+    kw = dict(kind_kw(kind, deep_depth=16), rounds=1, **sampling)
+    check(torch_cuda, tmp_path, kind, want, x, y, None, cuts, None, (("ohx_objective", "pseudohuber"),), kind + ", two batches", **kw)
+
+
+def test_tiny_residuals_do_not_depend_on_denormals(torch_cuda, tmp_path):
+    """z = 0, +-2^-70, float32 denormals and the smallest normals beside ordinary residuals, from a base margin of 0."""
+    rng = np.random.default_rng(264)
+    x, y, w, cuts, _ = O.inputs(N, 264, 3, 32, 0)
+    tiny = np.asarray([0.0, 2.0 ** -70, -2.0 ** -70, 2.0 ** -149, -2.0 ** -149, 2.0 ** -130, -2.0 ** -127, 2.0 ** -126, 3e-39], np.float32)
+    y[::2] = rng.choice(tiny, len(y[::2]))
+    for slope in (2.0 ** -10, 1.0, 256.0):
+        want = O.boost("pseudohuber", slope, np.zeros(N, np.float32), x, NAN, y, w, cuts, 3, rounds=2, max_depth=4, eta=0.5,
+                       min_child_weight=0.0)
+        params = (("ohx_objective", "pseudohuber"), ("ohx_huber_slope", repr(float(slope))))
+        check(torch_cuda, tmp_path, "weighted", want, x, y, w, cuts, None, params, f"tiny residuals at {slope}", base=0.0, rounds=2,
+              max_depth=4, eta=0.5, min_child_weight=0.0)
+
+
+# ---- 3. the order of the rows, and the grid ----
+
+@pytest.mark.parametrize("kind", ("weighted", "deep"))
+def test_row_order_and_the_grid_change_nothing(torch_cuda, tmp_path, kind):
+    x, y, w, cuts, ev, want = restated(kind, "pseudohuber", 1.0, rounds=3, patience=2)
+    kw = dict(kind_kw(kind), rounds=3, patience=2)
+    params = (("ohx_objective", "pseudohuber"),)
+    _, image = check(torch_cuda, tmp_path, kind, want, x, y, w, cuts, ev, params, kind, **kw)
+    order = np.random.default_rng(265).permutation(N)
+    b = booster(params)
+    got, mats = call(torch_cuda, b, kind, np.ascontiguousarray(x[order]), y[order], w[order], cuts, ev, grid=True, **kw)
+    same_result(got, want, kind + ", permuted")
+    assert saved(b, tmp_path) == image, "permuted rows on a grid"
+    done(b, mats)
+
+
+# ---- 4. the loss matters ----
+
+def test_the_loss_matters_on_outlier_labels(torch_cuda, tmp_path):
+    x, y, w, cuts, ev = O.inputs(N, 261, NFEAT, 64, HELD)
+    images = []
+    for params in ((), (("ohx_objective", "pseudohuber"),)):
+        b = booster(params)
+        got, mats = call(torch_cuda, b, "weighted", x, y, w, cuts, ev, **dict(kind_kw("weighted"), rounds=2))
+        images.append(saved(b, tmp_path))
+        done(b, mats)
+    assert images[0] != images[1]
+
+
+# ---- 5. refusals ----
+
+def test_refusals_leave_the_forest_and_the_outputs_alone(torch_cuda, tmp_path):
+    x, y, w, cuts, ev = O.inputs(N, 266, NFEAT, 64, HELD)
+    kw = dict(kind_kw("weighted"), rounds=2)
+    b = booster()
+    d = capi.DMatrix(x, missing=NAN)
+    b.boost_trees_weighted(d, y, cuts, weights=w, **kw)      # a forest to leave alone
+    before = saved(b, tmp_path)
+
+    def untouched(what):
+        assert saved(b, tmp_path) == before, what
+
+    # parameter values: the message names the parameter, and the handle keeps what it had
+    with pytest.raises(capi.OhxError, match="ohx_objective"):
+        b.set_param("ohx_objective", "logistic")
+    for bad in ("0", "nan", repr(2.0 ** -11), "257", "steep", "", "-1", "inf"):
+        with pytest.raises(capi.OhxError, match="ohx_huber_slope"):
+            b.set_param("ohx_huber_slope", bad)
+    with pytest.raises(capi.OhxError, match="ohx_grow_pairs"):
+        b.set_param("ohx_grow_pairs", "off")
+    b.set_param("objective", "reg:pseudohubererror")           # the name without the prefix stays ignored
+    twin = booster()
+    twin.boost_trees_weighted(d, y, cuts, weights=w, **kw)
+    twin.boost_trees_weighted(d, y, cuts, weights=w, **kw)
+    b.boost_trees_weighted(d, y, cuts, weights=w, **kw)
+    assert saved(b, tmp_path) == saved(twin, tmp_path), "refused values changed nothing: still squared error, slope 1"
+    twin.free()
+    before = saved(b, tmp_path)
+
+    # the calls that keep row counts, and the refit, under pseudohuber
+    b.set_param("ohx_objective", "pseudohuber")
+    with pytest.raises(capi.OhxError, match="OHXBoosterBoostTreesWeighted"):
+        b.boost_trees(d, y, cuts, rounds=1, max_depth=3)
+    with pytest.raises(capi.OhxError, match="OHXBoosterBoostTreesWeighted"):
+        b.boost_trees_eval(d, y, cuts, rounds=1, max_depth=3)
+    tx, ty = torch_cuda.from_numpy(x).cuda(), torch_cuda.from_numpy(y).cuda()
+    dd = capi.DMatrix(device_ptr=tx.data_ptr(), nrow=N, ncol=NFEAT, missing=NAN)
+    torch_cuda.cuda.synchronize()
+    with pytest.raises(capi.OhxError, match="OHXBoosterBoostTreesWeighted"):
+        b.boost_trees_device(dd, ty.data_ptr(), N, cuts, rounds=1, max_depth=3)
+    with pytest.raises(capi.OhxError, match="OHXBoosterBoostTreesWeighted"):
+        b.boost_trees_eval_device(dd, ty.data_ptr(), N, cuts, rounds=1, max_depth=3)
+    with pytest.raises(capi.OhxError, match="pseudohuber"):
+        b.refit_leaves(d, y)
+    with pytest.raises(capi.OhxError, match="pseudohuber"):
+        b.refit_leaves_device(dd, ty.data_ptr(), N)
+    untouched("the count calls and the refit")
+
+    # preset outputs through the C interface itself
+    ptr, vals = b._cuts(cuts)
+
+    def raw(labels, weights, rounds=2, depth=3, sampled=None):
+        train, evals = np.full(rounds + 1, -7.0), np.full(rounds + 1, -7.0)
+        run, best, added = C.c_int32(-7), C.c_int32(-7), C.c_uint64(77)
+        lab = np.ascontiguousarray(labels, np.float32)
+        wts = np.ascontiguousarray(weights, np.float32)
+        if sampled is None:
+            rc = b.lib.OHXBoosterBoostTreesWeighted(b.handle, d.handle, lab.ctypes.data, wts.ctypes.data, N, None, None, None, 0,
+                                                    ptr.ctypes.data, vals.ctypes.data, rounds, depth, 0.5, 1.0, 0.0, 0.0, 0,
+                                                    train.ctypes.data, evals.ctypes.data, C.byref(run), C.byref(best), C.byref(added))
+        else:
+            rc = b.lib.OHXBoosterBoostTreesSampled(b.handle, d.handle, lab.ctypes.data, wts.ctypes.data, N, None, None, None, 0,
+                                                   ptr.ctypes.data, vals.ctypes.data, rounds, depth, 0.5, 1.0, 0.0, 0.0, sampled[0], 1.0,
+                                                   sampled[1], 0, train.ctypes.data, evals.ctypes.data, C.byref(run), C.byref(best),
+                                                   C.byref(added))
+        with pytest.raises(capi.OhxError) as err:
+            capi.check(b.lib, rc)
+        assert np.all(train == -7.0) and np.all(evals == -7.0) and run.value == -7 and best.value == -7 and added.value == 77
+        return str(err.value)
+
+    # a NaN label on a row that is out of the bag
+    from tests import grow_sampled_support as P
+    seed = 5
+    out = np.flatnonzero(~P.bag(seed, 4, N, 0.5) & ~P.bag(seed, 5, N, 0.5))     # trees 4 and 5 of the forest
+    assert len(out) > 500
+    bad = y.copy()
+    bad[out[0]] = np.nan
+    assert "label" in raw(bad, w, sampled=(0.5, seed))
+    untouched("a NaN label out of the bag")
+    # a bad weight, and a weighted gradient that reaches 256
+    heavy = w.copy()
+    heavy[3] = -1.0
+    assert "weight" in raw(y, heavy)
+    untouched("a negative weight")
+    # every hessian rounds to 0: slope 2^-10 and residuals near 200 (h = d2 / ((d2 + z2) s) is about 2^-30 / 200^3)
+    b.set_param("ohx_huber_slope", repr(2.0 ** -10))
+    far = (200.0 + 10.0 * np.random.default_rng(267).random(N)).astype(np.float32)
+    q, hq = O.pairs("pseudohuber", 2.0 ** -10, np.full(N, O.BASE, np.float32), far, np.ones(N, np.float32))
+    assert not hq.any() and np.all(q != 0), "gradients, and no hessian"
+    assert "hessian" in raw(far, np.ones(N, np.float32))
+    untouched("no hessian")
+    assert "hessian" in raw(far, np.ones(N, np.float32), sampled=(0.5, seed))
+    untouched("no hessian in a bag")
+    # at squared error the same labels are no refusal
+    b.set_param("ohx_objective", "squarederror")
+    b.boost_trees_weighted(d, far, cuts, **kw)
+    assert saved(b, tmp_path) != before
+    done(b, [d, dd])
+
+
+# ---- 6. resetting ----
+
+def test_setting_squarederror_again_restores_the_default_bytes(torch_cuda, tmp_path):
+    x, y, w, cuts, ev = O.inputs(N, 268, NFEAT, 64, HELD)
+    kw = dict(kind_kw("sampled"), rounds=2)
+    plain = booster()
+    _, mats = call(torch_cuda, plain, "sampled", x, y, w, cuts, ev, **kw)
+    image = saved(plain, tmp_path)
+    done(plain, mats)
+    b = booster((("ohx_objective", "pseudohuber"), ("ohx_huber_slope", "3.7"), ("ohx_grow_pairs", "on")))
+    _, mats = call(torch_cuda, b, "sampled", x, y, w, cuts, ev, **kw)
+    assert saved(b, tmp_path) != image
+    b.free()
+    b = booster((("ohx_objective", "pseudohuber"), ("ohx_huber_slope", "3.7"), ("ohx_grow_pairs", "on")))
+    b.set_param("ohx_objective", "squarederror")
+    b.set_param("ohx_grow_pairs", "auto")
+    got, more = call(torch_cuda, b, "sampled", x, y, w, cuts, ev, **kw)
+    assert saved(b, tmp_path) == image
+    done(b, mats + more)

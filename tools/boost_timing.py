@@ -35,7 +35,13 @@ first-call timing and the refit, for a run under a kernel trace or a quick look 
 
 `--deep` with `--subsample S` and / or `--colsample C` times OHXBoosterBoostTreesDeepSampledDevice
 (docs/24_deep_sampled.md) in the same place, with `--seed`; the plan written is plan_grow_deep_sampled's over the n_sel
-features a tree sees.  Without the two fractions `--deep` does what it did."""
+features a tree sees.  Without the two fractions `--deep` does what it did.
+
+`--objective pseudohuber` (with `--huber-slope`) and `--pairs on` set "ohx_objective", "ohx_huber_slope" and
+"ohx_grow_pairs" on every booster that is timed (docs/26_objectives.md): the calls with row weights, `--weights`,
+`--subsample` / `--colsample` or `--deep`, then go through the pair kernels.  Three runs that differ in these alone compare
+the inline path, squared error on pairs and pseudo-Huber.  The refit at the end is a squared-error step and is left out
+under pseudohuber."""
 from __future__ import annotations
 
 import argparse
@@ -142,6 +148,9 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="the seed of the sampled call's draws")
     ap.add_argument("--deep", action="store_true", help="time OHXBoosterBoostTreesDeepDevice (with --subsample / --colsample: ...DeepSampledDevice): --max-depth up to 18")
     ap.add_argument("--deep-only", action="store_true", help="with --deep: one call a round count on a fresh booster, no refit")
+    ap.add_argument("--objective", choices=("squarederror", "pseudohuber"), default="squarederror", help="ohx_objective of the timed boosters")
+    ap.add_argument("--huber-slope", type=float, default=1.0, help="ohx_huber_slope of the timed boosters")
+    ap.add_argument("--pairs", choices=("auto", "on"), default="auto", help="ohx_grow_pairs of the timed boosters")
     args = ap.parse_args()
     sampled = args.subsample is not None or args.colsample is not None
     if sampled:
@@ -153,6 +162,8 @@ def main():
         ap.error("--deep times the call without a held-out set: leave --holdout out")
     if args.weights != "none" and args.holdout:
         ap.error("--weights times the call without a held-out set: leave --holdout out")
+    if (args.objective != "squarederror" or args.pairs != "auto") and (args.holdout or not (sampled or args.deep or args.weights != "none")):
+        ap.error("--objective / --pairs time a call with row weights: give --weights, --subsample / --colsample or --deep, and no --holdout")
     assert torch.cuda.is_available(), "boost_timing needs the MI355X"
     torch.cuda.set_device(0)
     model = synth.make_model()
@@ -240,6 +251,16 @@ def main():
     elif args.weights == "random":
         weights = torch.rand(n, dtype=torch.float32, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1)) * 4.0
     res["weights"] = args.weights
+    res["objective"] = {"ohx_objective": args.objective, "ohx_huber_slope": args.huber_slope, "ohx_grow_pairs": args.pairs}
+    res["pair_planes"] = synth.grow_pairs_plan(n, F, ncuts, args.max_depth, cus)
+
+    def timed_booster():
+        b = capi.Booster(model_buffer=model.image)
+        b.set_param("ohx_objective", args.objective)
+        b.set_param("ohx_huber_slope", repr(args.huber_slope))
+        b.set_param("ohx_grow_pairs", args.pairs)
+        return b
+
     last = {}                              # what the weighted call returned last
 
     def boost(b, rounds):
@@ -275,7 +296,7 @@ def main():
     for rounds in ([] if args.holdout else sorted({1, args.rounds})):
         first, again, nodes = [], [], 0
         for _ in range(args.reps):
-            b = capi.Booster(model_buffer=model.image)
+            b = timed_booster()
             dt, nodes = boost(b, rounds)
             first.append(dt)
             b.free()
@@ -283,7 +304,7 @@ def main():
                 again.append(dt)
                 continue
             # a call that finds its buffers: the second on one booster, continuing from the first
-            b = capi.Booster(model_buffer=model.image)
+            b = timed_booster()
             boost(b, rounds)
             dt, _ = boost(b, rounds)
             again.append(dt)
@@ -297,7 +318,7 @@ def main():
         per_round = (res[f"rounds_{args.rounds}"]["median_s"] - res["rounds_1"]["median_s"]) / (args.rounds - 1)
         res["per_round_s"] = per_round
         res["one_off_s"] = res["rounds_1"]["median_s"] - per_round
-    if not args.skip_rmse and not args.holdout and not args.deep_only:
+    if not args.skip_rmse and not args.holdout and not args.deep_only and args.objective == "squarederror":
         b = capi.Booster(model_buffer=model.image)
         res["rmse_before"] = rmse(b)
         b.refit_leaves_device(d, labels.data_ptr(), n, eta=1.0, reg_lambda=1.0, stream=stream)
