@@ -216,6 +216,21 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *                     too (a pass that writes every row's pair once a round, and histogram kernels that read it); auto =
  *                     only an objective that needs them does.  The same bits either way.  With none of the three set
  *                     every boost call runs the kernels it ran before they existed
+ *   "ohx_reg_alpha"   the L1 threshold alpha on a node's gradient sum: a decimal number, finite, >= 0 (default 0)
+ *   "ohx_max_delta_step" the bound m on |base_weight|: a decimal number, finite, >= 0 (default 0 = off).  Both enter the
+ *                     gain and the leaf of OHXBoosterBoostTreesWeighted, ...Sampled, ...Deep and ...DeepSampled as defined
+ *                     with the Weighted call below (docs/27_regularisation_and_metrics.md).  Anything else ("", "1x",
+ *                     "1 ", nan, inf, a negative number) returns -1 and the message names the parameter
+ *   "ohx_eval_metric" rmse (default) | mae | pseudohuber : what train_rmse[] and eval_rmse[] of those four calls hold and
+ *                     what their stop rule compares (defined with the Weighted call below; delta is "ohx_huber_slope"
+ *                     whatever the objective).  Any other value returns -1 and the message names "ohx_eval_metric".
+ *                     All three are kept on the handle and written into no model file; the names without the prefix are
+ *                     xgboost's and stay ignored.  While ohx_reg_alpha or ohx_max_delta_step is not 0 or the metric is
+ *                     not rmse, OHXBoosterBoostTrees[Device] and OHXBoosterBoostTreesEval[Device] (row counts and
+ *                     two-word sums) return -1 before anything is enqueued, and while ohx_reg_alpha or
+ *                     ohx_max_delta_step is not 0 so does OHXBoosterRefitLeaves[Device] (it would refit unregularised
+ *                     leaves); the message names OHXBoosterBoostTreesWeighted.  With all three at their defaults every
+ *                     boost call runs the kernels it ran before they existed
  * None of them changes a prediction.
  * xgboost's own parameter names ("nthread", "predictor", ...) are accepted and
  * ignored. */
@@ -721,6 +736,39 @@ int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, con
  * (every in-bag hq rounds to 0: a leaf would divide by lambda alone) is refused, the message says "hessian", and the
  * forest and every output are untouched, as for "bag".  The same holds for OHXBoosterBoostTreesSampled, ...Deep and
  * ...DeepSampled.
+ * Regularisation ("ohx_reg_alpha" = alpha, "ohx_max_delta_step" = m of XGBoosterSetParam).  What is stated above is
+ * alpha = 0 and m = 0.  In general, with Gd = (double)G * 2^-24, Hd = (double)H * 2^-24, D = Hd + (double)lambda and alpha
+ * and m widened to double; every operation is a double operation and rounds once, nothing is fused:
+ *   T  = Gd >  alpha ? Gd - alpha : (Gd < -alpha ? Gd + alpha : +0.0)          ThresholdL1 of xgboost 1.6.0 param.h
+ *   w  = (-T) / D;   if (m > 0 && fabs(w) > m) w = copysign(m, w)
+ *   gain(G, H) = m == 0 ?  (T * T) / D
+ *                        : -((2.0 * Gd) * w + (D * w) * w) - (2.0 * alpha) * fabs(w)
+ *   base_weight = (float)w;   leaf = base_weight * eta  (one float32 multiply)
+ *   loss_chg = (gain(L) + gain(R)) - gain(P)      as above
+ * With alpha = 0 and m = 0 these are, bit for bit, the gain and the leaf above, a base_weight of -0.0f at G == 0
+ * included.  Where |Gd| <= alpha, T is +0.0 and base_weight is -0.0f.  The second gain form is twice the reduction of the
+ * regularised objective at the clipped w; mathematically it is the first form wherever nothing is clipped.  It departs
+ * from CalcGain of xgboost 1.6.0 in this: CalcGain also takes the first form whenever max_delta_step == 0, but with a
+ * step it returns -(2 G w + D w^2) + alpha |w| on the clipped w, returns 0 below min_child_weight, and works on its own
+ * floating-point sums; here the L1 term enters the clipped form as -2 alpha |w|, so that the form is the regularised
+ * objective's own reduction and agrees with the first wherever nothing is clipped, min_child_weight stays a rule on
+ * which splits are admitted, and everything is double.  Parity with libxgboost is not pinned; the
+ * text above is the definition.  Unchanged: the candidates and their total order, the ties, which splits are admitted and
+ * which nodes are evaluated, min_child_weight on Hd, sum_hess, the node numbering, the record format and the refusals of
+ * a root with H == 0 ("bag", "hessian").  A loss_chg may now be negative where a child is clipped; such a candidate loses
+ * to gamma >= 0 as any other.
+ * The metric ("ohx_eval_metric").  What is stated above is rmse.  For one row z = pred - y in float32 (refused as above if
+ * not finite or |z| >= 256), hq = rint(w * 2^24), delta = "ohx_huber_slope" whatever the objective, and
+ *   rmse         sq = e * e,  e = (int64) rint(z * 2^24)
+ *   mae          sq = |e|
+ *   pseudohuber  d2 = delta * delta; z2 = z * z; s = sqrtf(1.0f + z2 / d2); mf = z2 / (1.0f + s);   float32, IEEE, not fused
+ *                sq = (uint64) rint(mf * 2^24)
+ * mf is delta^2 (s - 1) written without a cancellation at small z; mf <= delta |z| < 2^16, so sq < 2^40, and a denormal z2
+ * or mf gives sq = 0 whether or not denormals are flushed.  S = sum hq * sq is exact and W is as above.  train_rmse[t] and
+ * eval_rmse[t] - the arrays keep their names - then hold, for mae and pseudohuber, ((double)S_t * 2^-48) / ((double)W *
+ * 2^-24), both conversions from unsigned __int128 and no square root: the weighted mean absolute error, and the weighted
+ * mean of delta^2 (sqrt(1 + z^2 / delta^2) - 1).  The stop rule compares the exact S_eval[t] of the metric, strictly, as
+ * above.  The same holds for OHXBoosterBoostTreesSampled, ...Deep and ...DeepSampled.
  * Everything else is OHXBoosterBoostTreesEval's: all or nothing; what a success drops; patience == 0 waits once, at the
  * end, and patience >= 1 waits once a round; eval_dmat == NULL works as there, and eval_weights must then be NULL.  Not
  * capturable.  The host form stages the weights with the labels; the device form takes d_weights and d_eval_weights in

@@ -857,6 +857,10 @@ struct BoosterObj {
   uint32_t grow_objective = kGrowObjSquared;   // "ohx_objective": squarederror or pseudohuber
   float grow_slope = 1.0f;                     // "ohx_huber_slope": delta of pseudohuber
   bool grow_pairs_on = false;                  // "ohx_grow_pairs" = on: squared error goes through the pair kernels too (same bits)
+  // (docs/27_regularisation_and_metrics.md): likewise on the handle alone
+  float grow_alpha = 0.0f;                     // "ohx_reg_alpha": the L1 threshold on a node's gradient sum
+  float grow_max_delta_step = 0.0f;            // "ohx_max_delta_step": the bound on |base_weight|; 0 is off
+  uint32_t grow_metric = kGrowMetricRmse;      // "ohx_eval_metric": what train_rmse[] / eval_rmse[] hold and the stop rule compares
   std::unique_ptr<RefitState> refit;
   std::unique_ptr<GrowState> grow;
 };
@@ -2110,6 +2114,9 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
   if (b.grow_objective != kGrowObjSquared)
     throw OhxError(std::string(what) + " refits squared-error leaves (hessian 1 a row): it is refused while ohx_objective=pseudohuber "
                    "is set; grow with OHXBoosterBoostTreesWeighted, or set ohx_objective=squarederror; nothing was enqueued");
+  if (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f)
+    throw OhxError(std::string(what) + " refits unregularised leaves: it is refused while ohx_reg_alpha or ohx_max_delta_step is set; "
+                   "grow with OHXBoosterBoostTreesWeighted, or set both to 0; nothing was enqueued");
   if (labels == nullptr) throw OhxError(std::string(what) + ": labels is NULL");
   if (!std::isfinite(eta)) throw OhxError(std::string(what) + ": eta must be finite");
   if (!(std::isfinite(lambda) && lambda >= 0.0f)) throw OhxError(std::string(what) + ": lambda must be finite and >= 0");
@@ -2337,6 +2344,14 @@ struct BoostKind {
   // without, the histogram kernels of the kind make g = pred - label themselves
   bool pairs = false;
   GrowPairArgs pair_args;
+  // regularised (ohx_reg_alpha or ohx_max_delta_step is not 0; then `pairs` holds too): the pair path with grow_reg.hip's
+  // split launches.  metric: what a row adds to the sums; away from rmse the metric kernels are grow_reg.hip's.  The two
+  // choices are independent, and with neither nothing of grow_reg.hip is touched.
+  bool regularised = false;
+  GrowPairSplits reg_splits;
+  uint32_t metric = kGrowMetricRmse;
+  float slope = 1.0f;
+  const GrowPairSplits* splits() const { return regularised ? &reg_splits : nullptr; }
   bool wide() const { return which != Plain; }
   // The call's one plan, asked for once: the level loop over `cols` histogram columns - F itself, or the n_sel features
   // a tree of a sampled call sees (compact histograms and candidates) - the streaming kernels, which do not depend on
@@ -2363,22 +2378,26 @@ struct BoostKind {
       case Deep: {
         GrowDeepArgs d = deep_args;
         d.g = a;
-        return (hipError_t)(pairs ? launch_grow_tree_deep_pairs(d, pair_args, deep, round, h_state, stream)
+        return (hipError_t)(pairs ? launch_grow_tree_deep_pairs(d, pair_args, deep, round, h_state, stream, splits())
                                   : launch_grow_tree_deep(d, deep, round, h_state, stream));
       }
       case Sampled:
-        return (hipError_t)(pairs ? launch_grow_tree_pairs(a, pair_args, plan, levels, round, stream)
+        return (hipError_t)(pairs ? launch_grow_tree_pairs(a, pair_args, plan, levels, round, stream, splits())
                                   : launch_grow_tree_sampled(a, plan, levels, round, stream));
       case Weighted:
-        return (hipError_t)(pairs ? launch_grow_tree_pairs(a, pair_args, plan, levels, round, stream)
+        return (hipError_t)(pairs ? launch_grow_tree_pairs(a, pair_args, plan, levels, round, stream, splits())
                                   : launch_grow_tree_weighted(a, plan, levels, round, stream));
       default: return (hipError_t)launch_grow_tree(a, plan, levels, round, stream);
     }
   }
   hipError_t sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream) const {
+    if (metric != kGrowMetricRmse) return (hipError_t)launch_grow_sse_metric(a, metric, slope, blocks, t, set, stream);
     return (hipError_t)(wide() ? launch_grow_sse_weighted(a, blocks, t, set, stream) : launch_grow_sse(a, blocks, t, set, stream));
   }
   hipError_t walk_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream) const {
+    if (metric != kGrowMetricRmse)
+      return (hipError_t)(which == Deep ? launch_grow_walk_sse_deep_metric(a, deep_args, metric, slope, blocks, round, set, stream)
+                                        : launch_grow_walk_sse_metric(a, metric, slope, blocks, round, set, stream));
     if (which == Deep) return (hipError_t)launch_grow_walk_sse_deep(a, deep_args, blocks, round, set, stream);
     return (hipError_t)(wide() ? launch_grow_walk_sse_weighted(a, blocks, round, set, stream)
                                : launch_grow_walk_sse(a, blocks, round, set, stream));
@@ -2413,6 +2432,9 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (b.grow_objective != kGrowObjSquared && !weighted)
     throw OhxError(w0 + " keeps row counts, not hessian sums: with ohx_objective=pseudohuber call OHXBoosterBoostTreesWeighted "
                    "(weights may be NULL) or a later form; nothing was enqueued and the forest is unchanged");
+  if (!weighted && (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f || b.grow_metric != kGrowMetricRmse))
+    throw OhxError(w0 + " keeps row counts and two-word sums: with ohx_reg_alpha, ohx_max_delta_step or ohx_eval_metric set call "
+                   "OHXBoosterBoostTreesWeighted (weights may be NULL) or a later form; nothing was enqueued and the forest is unchanged");
   if (!b.margin_error.empty()) throw OhxError(b.margin_error);
   if (c.labels == nullptr) throw OhxError(w0 + ": labels is NULL");
   if (c.cut_ptr == nullptr || c.cut_values == nullptr) throw OhxError(w0 + ": the cuts are NULL");
@@ -2475,7 +2497,12 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   const bool deep = c.deep && max_depth > kGrowMaxDepth;
   BoostKind kind{deep ? BoostKind::Deep : sampled ? BoostKind::Sampled : weighted ? BoostKind::Weighted : BoostKind::Plain};
   // (the Plain kind has no pair path: its hessian is a row count)
-  kind.pairs = weighted && (b.grow_objective != kGrowObjSquared || b.grow_pairs_on);
+  kind.regularised = weighted && (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f);
+  kind.pairs = weighted && (b.grow_objective != kGrowObjSquared || b.grow_pairs_on || kind.regularised);
+  if (kind.regularised)
+    kind.reg_splits = grow_reg_splits(GrowRegHess{(double)wt.min_child_weight, b.grow_alpha, b.grow_max_delta_step});
+  kind.metric = weighted ? b.grow_metric : kGrowMetricRmse;
+  kind.slope = b.grow_slope;
   kind.pair_args.objective = b.grow_objective;
   kind.pair_args.slope = b.grow_slope;
   // before anything is built or enqueued: building the state waits for the library's stream
@@ -2845,7 +2872,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
         x.p2 = s[0];
         x.p1 = s[1];
         x.p0 = s[2];
-        return grow_wide_rmse(x, g.h_sums.p[set]);
+        return kind.metric == kGrowMetricRmse ? grow_wide_rmse(x, g.h_sums.p[set]) : grow_wide_mean(x, g.h_sums.p[set]);
       }
       GrowSum x;
       x.hi = s[0];
@@ -3331,6 +3358,16 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
     if (v.empty() || end == value || *end != '\0' || !grow_slope_sound(k))
       throw OhxError("ohx_huber_slope must be a decimal number with 2^-10 <= slope <= 256");
     b->grow_slope = k;
+  } else if (n == "ohx_reg_alpha" || n == "ohx_max_delta_step") {
+    // boosting: CalcWeight / CalcGain's other two parameters (docs/27_regularisation_and_metrics.md); on the handle, in no file
+    char* end = nullptr;
+    const float k = strtof(value, &end);
+    if (v.empty() || end == value || *end != '\0' || !grow_reg_sound(k))
+      throw OhxError(n + " must be a finite decimal number >= 0");
+    (n == "ohx_reg_alpha" ? b->grow_alpha : b->grow_max_delta_step) = k;
+  } else if (n == "ohx_eval_metric") {
+    if (v != "rmse" && v != "mae" && v != "pseudohuber") throw OhxError("ohx_eval_metric must be rmse, mae or pseudohuber");
+    b->grow_metric = v == "mae" ? kGrowMetricMae : v == "pseudohuber" ? kGrowMetricPseudoHuber : kGrowMetricRmse;
   } else if (n == "ohx_grow_pairs") {
     // "on": squared error goes through the pair kernels too (the same bits); auto: only an objective that needs them
     if (v != "auto" && v != "on") throw OhxError("ohx_grow_pairs must be auto or on");

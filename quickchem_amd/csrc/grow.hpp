@@ -142,6 +142,7 @@ struct GrowCountHess {
   OHX_GROW_HD bool admits(uint64_t HL, uint64_t HR) const { return !(HL < min_child_rows || HR < min_child_rows); }
   OHX_GROW_HD bool evaluates(uint64_t) const { return true; }
   OHX_GROW_HD float sum_hess(uint64_t H) const { return (float)H; }
+  OHX_GROW_HD double gain(int64_t G, uint64_t H, double lambda) const { return grow_gain(G, hess(H), lambda); }
   OHX_GROW_HD void solve_leaf(int64_t G, uint64_t H, float eta, float lambda, float* leaf, float* weight) const {
     refit_solve_leaf(G, H, eta, lambda, leaf, weight);
   }
@@ -157,8 +158,63 @@ struct GrowFixedHess {
   }
   OHX_GROW_HD bool evaluates(uint64_t Hp) const { return grow_weight_splits(Hp, min_child_weight); }
   OHX_GROW_HD float sum_hess(uint64_t H) const { return (float)grow_hess(H); }
+  OHX_GROW_HD double gain(int64_t G, uint64_t H, double lambda) const { return grow_gain(G, hess(H), lambda); }
   OHX_GROW_HD void solve_leaf(int64_t G, uint64_t H, float eta, float lambda, float* leaf, float* weight) const {
     grow_solve_leaf_weighted(G, H, eta, lambda, leaf, weight);
+  }
+};
+
+// ---- reg_alpha and max_delta_step (design in docs/27_regularisation_and_metrics.md) ----
+
+// ThresholdL1 of xgboost 1.6.0's param.h on the gradient sum as a double: +0.0 where |Gd| <= alpha
+OHX_GROW_HD inline double grow_threshold_l1(double Gd, double alpha) {
+  return Gd > alpha ? Gd - alpha : (Gd < -alpha ? Gd + alpha : 0.0);
+}
+// The header's w of a node with D = Hd + lambda: (-T) / D, clipped to +-m where m > 0.  Every operation is a double
+// operation and rounds once.  T == +0.0 gives -0.0 (D > 0).
+OHX_GROW_HD inline double grow_reg_weight(double Gd, double D, double alpha, double m) {
+  double w = (-grow_threshold_l1(Gd, alpha)) / D;
+  if (m > 0.0 && __builtin_fabs(w) > m) w = __builtin_copysign(m, w);
+  return w;
+}
+// The header's gain(G, H): T^2 / D where nothing can be clipped (m == 0), else twice the reduction of the regularised
+// objective at the clipped w.  With alpha == 0 and m == 0 it is grow_gain bit for bit (Gd - 0.0 is Gd, and G == 0 gives
+// 0.0 * 0.0 either way).
+OHX_GROW_HD inline double grow_reg_gain(int64_t G, double Hd, double lambda, double alpha, double m) {
+  const double Gd = (double)G * (1.0 / 16777216.0);
+  const double D = Hd + lambda;
+  if (m == 0.0) {
+    const double T = grow_threshold_l1(Gd, alpha);
+    return (T * T) / D;
+  }
+  const double w = grow_reg_weight(Gd, D, alpha, m);
+  return -((2.0 * Gd) * w + (D * w) * w) - (2.0 * alpha) * __builtin_fabs(w);
+}
+// base_weight = (float)w, leaf = base_weight * eta (one float32 multiply).  With alpha == 0 and m == 0 it is
+// grow_solve_leaf_weighted bit for bit, a base_weight of -0.0f at G == 0 included.
+OHX_GROW_HD inline void grow_solve_leaf_reg(int64_t G, uint64_t H, float eta, float lambda, float alpha, float max_delta_step,
+                                            float* leaf, float* weight) {
+  const float w = (float)grow_reg_weight((double)G * (1.0 / 16777216.0), grow_hess(H) + (double)lambda, (double)alpha,
+                                         (double)max_delta_step);
+  *weight = w;
+  *leaf = w * eta;
+}
+// (NaN fails both comparisons)
+inline bool grow_reg_sound(float v) { return v >= 0.0f && v < INFINITY; }
+// "regularised": GrowFixedHess with "ohx_reg_alpha" and "ohx_max_delta_step" in the gain and the leaf.  What a split may
+// be (admits), which nodes are looked at (evaluates) and sum_hess are GrowFixedHess's.  16 bytes: a kernel argument.
+struct GrowRegHess {
+  double min_child_weight;
+  float alpha, max_delta_step;
+  OHX_GROW_HD double hess(uint64_t H) const { return grow_hess(H); }
+  OHX_GROW_HD bool admits(uint64_t HL, uint64_t HR) const { return GrowFixedHess{min_child_weight}.admits(HL, HR); }
+  OHX_GROW_HD bool evaluates(uint64_t Hp) const { return grow_weight_splits(Hp, min_child_weight); }
+  OHX_GROW_HD float sum_hess(uint64_t H) const { return (float)grow_hess(H); }
+  OHX_GROW_HD double gain(int64_t G, uint64_t H, double lambda) const {
+    return grow_reg_gain(G, grow_hess(H), lambda, (double)alpha, (double)max_delta_step);
+  }
+  OHX_GROW_HD void solve_leaf(int64_t G, uint64_t H, float eta, float lambda, float* leaf, float* weight) const {
+    grow_solve_leaf_reg(G, H, eta, lambda, alpha, max_delta_step, leaf, weight);
   }
 };
 
@@ -171,7 +227,7 @@ OHX_GROW_HD inline GrowCand grow_best_split(const int64_t* G, const uint64_t* H,
                                             uint32_t ncut, int64_t GLb, uint64_t HLb, int64_t Gm, uint64_t Hm, int64_t Gp,
                                             uint64_t Hp, double lambda, const Hess& hess) {
   GrowCand best;
-  const double parent = grow_gain(Gp, hess.hess(Hp), lambda);
+  const double parent = hess.gain(Gp, Hp, lambda);
   for (uint32_t k = 0; k < n; ++k) {
     const uint32_t j = j0 + k;
     GLb += G[k];
@@ -184,7 +240,7 @@ OHX_GROW_HD inline GrowCand grow_best_split(const int64_t* G, const uint64_t* H,
       const int64_t GR = Gp - c.GL;
       const uint64_t HR = Hp - c.HL;
       if (!hess.admits(c.HL, HR)) continue;
-      c.loss_chg = (grow_gain(c.GL, hess.hess(c.HL), lambda) + grow_gain(GR, hess.hess(HR), lambda)) - parent;
+      c.loss_chg = (hess.gain(c.GL, c.HL, lambda) + hess.gain(GR, HR, lambda)) - parent;
       c.key = grow_key(f, j, dl);
       c.valid = 1;
       if (grow_better(c, best)) best = c;
@@ -340,6 +396,42 @@ inline unsigned __int128 grow_sum_value(const unsigned long long* s, size_t word
 // sqrt( ((double)S * 2^-72) / ((double)W * 2^-24) ), W = sum hq: both exact integers rounded to nearest even as they
 // become doubles, exact scalings, then an IEEE division and square root.
 double grow_wide_rmse(GrowWideSum s, uint64_t W);
+
+// "ohx_eval_metric": what one row adds to S beside its hq (design in docs/27_regularisation_and_metrics.md).  rmse is the
+// square of the fixed-point residual, as ever; mae its size; pseudohuber delta^2 (sqrt(1 + z^2 / delta^2) - 1) in the
+// form that cancels nothing, every operation float32 and rounding once, the division and the square root IEEE.
+constexpr uint32_t kGrowMetricRmse = 0, kGrowMetricMae = 1, kGrowMetricPseudoHuber = 2;
+// sq of the header for z = pred - label; false (and sq = 0) where z is not finite or |z| >= 256.  sq < 2^64 for rmse,
+// < 2^32 for mae and < 2^40 for pseudohuber (mf <= delta |z| < 2^16).  A denormal z2 or mf gives 0 whether or not
+// denormals are flushed: 1 + z2 / d2 absorbs the one and rint(mf * 2^24) the other.
+template <uint32_t METRIC>
+OHX_GROW_HD inline bool grow_metric_row(float slope, float pred, float label, uint64_t* sq) {
+  *sq = 0;
+  const float z = pred - label;
+  // (a NaN fails the comparison)
+  if (!(__builtin_fabsf(z) < kRefitMaxAbsGrad)) return false;
+  if (METRIC == kGrowMetricPseudoHuber) {
+    const float d2 = slope * slope;
+    const float z2 = z * z;
+    const float s = sqrtf(1.0f + z2 / d2);
+    const float mf = z2 / (1.0f + s);
+    *sq = (uint64_t)__builtin_rintf(mf * kRefitGradScale);
+    return true;
+  }
+  const long long e = (long long)__builtin_rintf(z * kRefitGradScale);
+  const uint64_t m = (uint64_t)(e < 0 ? -e : e);   // <= 2^32 - 256
+  *sq = METRIC == kGrowMetricMae ? m : m * m;
+  return true;
+}
+// the same with the metric as a value (the host's callers)
+inline bool grow_metric_row_of(uint32_t metric, float slope, float pred, float label, uint64_t* sq) {
+  return metric == kGrowMetricPseudoHuber ? grow_metric_row<kGrowMetricPseudoHuber>(slope, pred, label, sq)
+         : metric == kGrowMetricMae       ? grow_metric_row<kGrowMetricMae>(slope, pred, label, sq)
+                                          : grow_metric_row<kGrowMetricRmse>(slope, pred, label, sq);
+}
+// What mae and pseudohuber report: ((double)S * 2^-48) / ((double)W * 2^-24), both exact integers rounded to nearest
+// even as they become doubles, exact scalings, then an IEEE division.  No square root.
+double grow_wide_mean(GrowWideSum s, uint64_t W);
 
 // ---- the launch plan ----
 
@@ -561,7 +653,13 @@ int launch_grow_tree_deep(const GrowDeepArgs& a, const GrowDeepPlan& plan, uint3
 struct GrowDeepLaunches {
   std::function<int(const GrowArgs& top, const GrowPlan& lds, void* stream)> top;
   std::function<void(const GrowDeepArgs& d, uint32_t round, uint32_t batch0, uint32_t nslots, uint32_t hist_blocks, void* stream)> hist;
+  // The split phases of a deep level, where they are not grow_deep.hip's own (empty: they are): phase 0 over `blocks`
+  // blocks of four waves for the batch from batch0 on, and phase 1, one block.
+  std::function<void(const GrowDeepArgs& d, uint32_t level, uint32_t round, uint32_t batch0, uint32_t blocks, void* stream)> split0;
+  std::function<void(const GrowDeepArgs& d, uint32_t level, uint32_t round, void* stream)> split1;
 };
+// Enqueues grow_deep_stage_kernel alone: eval_nodes from the records of tree `round`.  Returns a hipError_t.
+int launch_grow_deep_stage(const GrowDeepArgs& d, uint32_t blocks, uint32_t round, void* stream);
 int launch_grow_tree_deep_with(const GrowDeepArgs& a, const GrowDeepPlan& plan, uint32_t round, GrowLevelState* h_state,
                                void* stream, const GrowDeepLaunches& launches);
 
@@ -576,14 +674,39 @@ struct GrowPairArgs {
   uint32_t objective = kGrowObjSquared;
   float slope = 1.0f;
 };
+// What a root with H == 0 raises at level 0 (the ROOT of the pair path's split kernels): nothing (the weighted call at
+// squared error), kGrowFlagBag (the sampled call at squared error) or kGrowFlagHess (pseudo-Huber, bag or no bag).
+constexpr int kGrowRootNone = 0, kGrowRootBag = 1, kGrowRootHess = 2;
+// The split launches of the pair path where they are not its own (grow_reg.hip gives its regularised ones): levels 0 - 7
+// over the columns `list[0 .. ncols)` - phase 0 over `blocks` blocks of four waves, phase 1 one block with the call's
+// `root` - and the deep levels' as GrowDeepLaunches takes them.  Everything else of a tree is launched as ever.
+struct GrowPairSplits {
+  std::function<void(const GrowArgs& a, const uint8_t* list, uint32_t ncols, uint32_t blocks, uint32_t level, uint32_t round, void* stream)> split0;
+  std::function<void(const GrowArgs& a, const uint8_t* list, uint32_t ncols, int root, uint32_t level, uint32_t round, void* stream)> split1;
+  std::function<void(const GrowDeepArgs& d, uint32_t level, uint32_t round, uint32_t batch0, uint32_t blocks, void* stream)> deep_split0;
+  std::function<void(const GrowDeepArgs& d, uint32_t level, uint32_t round, void* stream)> deep_split1;
+};
 // launch_grow_tree_weighted (a.features == nullptr) or launch_grow_tree_sampled (a.features != nullptr) on pairs: the
 // pair kernel over every row, then the levels with the histogram kernel that reads the planes, then the leaf kernel.
-// With kGrowObjPseudoHuber a root without hessian raises kGrowFlagHess.  Returns a hipError_t.
+// With kGrowObjPseudoHuber a root without hessian raises kGrowFlagHess.  `splits`: nullptr, or the split launches to
+// use in place of this file's.  Returns a hipError_t.
 int launch_grow_tree_pairs(const GrowArgs& a, const GrowPairArgs& p, const GrowPlan& plan, const GrowPlan& levels, uint32_t round,
-                           void* stream);
+                           void* stream, const GrowPairSplits* splits = nullptr);
 // launch_grow_tree_deep on pairs, with or without a bag and a list.  Returns a hipError_t.
 int launch_grow_tree_deep_pairs(const GrowDeepArgs& a, const GrowPairArgs& p, const GrowDeepPlan& plan, uint32_t round,
-                                GrowLevelState* h_state, void* stream);
+                                GrowLevelState* h_state, void* stream, const GrowPairSplits* splits = nullptr);
+
+// ---- reg_alpha, max_delta_step and the metrics on the GPU (grow_reg.hip; design in docs/27_regularisation_and_metrics.md) ----
+
+// The regularised split launches of a call: grow_split_reg_kernel for levels 0 - 7 and grow_deep_split_reg_kernel below.
+GrowPairSplits grow_reg_splits(const GrowRegHess& hess);
+// launch_grow_sse_weighted, launch_grow_walk_sse_weighted and launch_grow_walk_sse_deep with the row's term of `metric`
+// (kGrowMetricMae or kGrowMetricPseudoHuber; slope is delta) in place of the square: the same sums, flags and layout.
+int launch_grow_sse_metric(const GrowEvalArgs& a, uint32_t metric, float slope, uint32_t blocks, uint32_t t, uint32_t set, void* stream);
+int launch_grow_walk_sse_metric(const GrowEvalArgs& a, uint32_t metric, float slope, uint32_t blocks, uint32_t round, uint32_t set,
+                                void* stream);
+int launch_grow_walk_sse_deep_metric(const GrowEvalArgs& a, const GrowDeepArgs& d, uint32_t metric, float slope, uint32_t blocks,
+                                     uint32_t round, uint32_t set, void* stream);
 // Enqueues grow_deep_stage_kernel and grow_deep_walk_sse_kernel: eval_nodes from the records of tree `round`, then
 // launch_grow_walk_sse_weighted's walk and sums over the rows of `a`, its nodes read from HBM.  Returns a hipError_t.
 int launch_grow_walk_sse_deep(const GrowEvalArgs& a, const GrowDeepArgs& d, uint32_t blocks, uint32_t round, uint32_t set,

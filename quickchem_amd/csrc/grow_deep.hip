@@ -37,6 +37,7 @@
 #include <cstdint>
 
 #include "grow.hpp"
+#include "grow_deep_device.hpp"
 #include "grow_device.hpp"
 #include "grow_sums_device.hpp"
 #include "walk_device.hpp"
@@ -49,13 +50,8 @@ static_assert(sizeof(EvalNode) == kGrowEvalNodeBytes, "the host sizes the walk's
 constexpr int kBlock = (int)kGrowBlock;
 constexpr int kWaves = kBlock / kWave;
 
-// The tree at hand as round 0 of its own table: what the shared split phases and the weighted levels index by round.
-__host__ __device__ inline GrowArgs tree_args(const GrowDeepArgs& a, uint32_t round) {
-  GrowArgs t = a.g;
-  t.nodes = a.g.nodes + (uint64_t)round * a.node_stride;
-  t.tree_nodes = a.g.tree_nodes + round;
-  return t;
-}
+// (the tree at hand as round 0 of its own table: grow_deep_device.hpp)
+__host__ __device__ inline GrowArgs tree_args(const GrowDeepArgs& a, uint32_t round) { return grow_deep_tree_args(a, round); }
 
 // grid (blocks)
 __global__ __launch_bounds__(kBlock) void grow_deep_widen_kernel(GrowDeepArgs a) {
@@ -109,51 +105,8 @@ __global__ __launch_bounds__(kBlock) void grow_deep_hist_kernel(GrowDeepArgs d, 
   if (flags) atomicOr(&a.state->error, flags);
 }
 
-// Split phase 1 of a deep level, written once for both kinds: one block walks the level's slots in chunks of its width
-// with a running total (grow.hpp grow_chunked_children) and decides every node over `ncols` columns of `best`.
-__device__ inline void grow_deep_split_chunks(const GrowArgs& a, const GrowFixedHess& hess, uint32_t node_stride, uint32_t level,
-                                              uint32_t ncols) {
-  __shared__ uint32_t wave_splits[kWaves];
-  const uint32_t begin = a.state->begin, end = a.state->end, next = a.state->next;
-  const uint32_t count = end - begin;
-  const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-  uint32_t running = 0;   // the splits of the chunks before this one: the same in every lane
-  bool full = false;      // a child id past the round's records (never: grow_deep_node_stride)
-  for (uint32_t c0 = 0; c0 < count; c0 += kBlock) {
-    const uint32_t s = c0 + threadIdx.x;
-    const uint32_t node = begin + s;
-    GrowDecision dec;
-    if (s < count) dec = grow_decide_node<false>(a, hess, a.nodes, level, node, s, ncols);
-    const bool split = s < count && dec.split;
-    // the exclusive scan of the chunk's flags: the lanes below in the wave, and the waves below in the block
-    const unsigned long long votes = __ballot(split);
-    if (lane == 0) wave_splits[wave] = (uint32_t)__popcll(votes);
-    __syncthreads();
-    uint32_t scan = (uint32_t)__popcll(votes & ((1ull << lane) - 1ull)), chunk = 0;
-#pragma unroll
-    for (int w = 0; w < kWaves; ++w) {
-      if (w < wave) scan += wave_splits[w];
-      chunk += wave_splits[w];
-    }
-    __syncthreads();   // wave_splits is written again in the next chunk
-    if (split) {
-      const uint32_t left = grow_child_id(next, running + scan);
-      if (left + 1u < node_stride) grow_write_split(a, hess, a.nodes, node, dec, left);
-      else full = true;
-    }
-    running += chunk;
-  }
-  if (full) atomicOr(&a.state->error, kGrowFlagState);
-  uint32_t total = next + 2u * running;
-  if (total > node_stride) total = next;   // (never; the flag is raised above) nothing is open: the tree ends
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    a.state->begin = next;
-    a.state->end = total;
-    a.state->next = total;
-    a.tree_nodes[0] = total;
-  }
-}
+// Split phase 1 of a deep level is written once, over a hessian policy, in grow_deep_device.hpp (grow_deep_split_chunks:
+// its chunk loop is `for (uint32_t c0 = 0; c0 < count; c0 += kBlock)` with a running total); grow_reg.hip instantiates it too.
 
 // PHASE 0: grid (blocks of four waves over the batch's slots x features).  PHASE 1: one block.
 template <int PHASE>
@@ -439,11 +392,13 @@ int launch_grow_tree_deep_with(const GrowDeepArgs& d, const GrowDeepPlan& plan, 
       launches.hist(d, round, batch0, nslots, plan.hist_blocks, stream);
       if ((e = hipGetLastError()) != hipSuccess) return e;
       const dim3 waves((nslots * ncols + kWaves - 1) / kWaves);
-      if (sampled) hipLaunchKernelGGL(grow_deep_split_sampled_kernel<0>, waves, block, 0, stream, d, level, round, batch0);
+      if (launches.split0) launches.split0(d, level, round, batch0, waves.x, stream);
+      else if (sampled) hipLaunchKernelGGL(grow_deep_split_sampled_kernel<0>, waves, block, 0, stream, d, level, round, batch0);
       else hipLaunchKernelGGL(grow_deep_split_kernel<0>, waves, block, 0, stream, d, level, round, batch0);
       if ((e = hipGetLastError()) != hipSuccess) return e;
     }
-    if (sampled) hipLaunchKernelGGL(grow_deep_split_sampled_kernel<1>, dim3(1), block, 0, stream, d, level, round, 0u);
+    if (launches.split1) launches.split1(d, level, round, stream);
+    else if (sampled) hipLaunchKernelGGL(grow_deep_split_sampled_kernel<1>, dim3(1), block, 0, stream, d, level, round, 0u);
     else hipLaunchKernelGGL(grow_deep_split_kernel<1>, dim3(1), block, 0, stream, d, level, round, 0u);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(grow_deep_partition_kernel, rows, block, 0, stream, d, round);
@@ -453,6 +408,14 @@ int launch_grow_tree_deep_with(const GrowDeepArgs& d, const GrowDeepPlan& plan, 
     count = h_state->end - h_state->begin;
   }
   hipLaunchKernelGGL(grow_deep_leaf_kernel, rows, block, 0, stream, d, round);
+  return hipGetLastError();
+}
+
+int launch_grow_deep_stage(const GrowDeepArgs& d, uint32_t blocks, uint32_t round, void* stream_) {
+  if (blocks == 0 || d.eval_nodes == nullptr || d.node_stride == 0 || d.g.nodes == nullptr || d.g.tree_nodes == nullptr)
+    return hipErrorInvalidValue;
+  const uint32_t stage_blocks = std::min<uint32_t>(blocks, (d.node_stride + kBlock - 1) / kBlock);
+  hipLaunchKernelGGL(grow_deep_stage_kernel, dim3(stage_blocks), dim3(kBlock), 0, static_cast<hipStream_t>(stream_), d, round);
   return hipGetLastError();
 }
 

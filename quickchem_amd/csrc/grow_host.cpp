@@ -418,3 +418,57 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_pairs_plan(uint64
     return -1;
   }
 }
+
+// ---- reg_alpha, max_delta_step and the metrics (docs/27_regularisation_and_metrics.md) ----
+
+// the header's gain(G, H) of GrowRegHess, as a double
+extern "C" __attribute__((visibility("default"))) double ohx_grow_reg_gain(int64_t G, uint64_t H, float lambda, float alpha,
+                                                                            float max_delta_step) {
+  return GrowRegHess{0.0, alpha, max_delta_step}.gain(G, H, (double)lambda);
+}
+
+// out: (leaf, base_weight, sum_hess) of GrowRegHess
+extern "C" __attribute__((visibility("default"))) void ohx_grow_reg_leaf(int64_t G, uint64_t H, float eta, float lambda, float alpha,
+                                                                         float max_delta_step, float out[3]) {
+  const GrowRegHess hess{0.0, alpha, max_delta_step};
+  hess.solve_leaf(G, H, eta, lambda, &out[0], &out[1]);
+  out[2] = hess.sum_hess(H);
+}
+
+// A node's best split over its histograms by GrowRegHess (grow_node_split): out = (valid, key, GL, HL), *loss_chg.
+extern "C" __attribute__((visibility("default"))) int ohx_grow_reg_node_split(const int64_t* G, const uint64_t* H, uint32_t num_feature,
+                                                                              const uint64_t* cut_ptr, int64_t Gp, uint64_t Hp,
+                                                                              float lambda, float min_child_weight, float alpha,
+                                                                              float max_delta_step, uint64_t out[4], double* loss_chg) {
+  const GrowCand c = grow_node_split(G, H, num_feature, cut_ptr, Gp, Hp, lambda,
+                                     GrowRegHess{(double)min_child_weight, alpha, max_delta_step});
+  out[0] = c.valid;
+  out[1] = c.key;
+  out[2] = (uint64_t)c.GL;
+  out[3] = c.HL;
+  *loss_chg = c.loss_chg;
+  return 0;
+}
+
+// sq of every row by `metric` (0 rmse, 1 mae, 2 pseudohuber with `slope`); sound[r] = 0 where the residual is refused
+extern "C" __attribute__((visibility("default"))) int ohx_grow_metric_row(uint32_t metric, float slope, const float* pred, const float* y,
+                                                                         uint64_t n, uint64_t* sq, uint8_t* sound) {
+  try {
+    if (metric > kGrowMetricPseudoHuber) throw OhxError("ohx_grow_metric_row: metric must be 0, 1 or 2");
+    if (metric == kGrowMetricPseudoHuber && !grow_slope_sound(slope)) throw OhxError("ohx_grow_metric_row: 2^-10 <= slope <= 256");
+    for (uint64_t r = 0; r < n; ++r) sound[r] = grow_metric_row_of(metric, slope, pred[r], y[r], &sq[r]) ? 1 : 0;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// s: (p2, p1, p0); W: the sum of hq
+extern "C" __attribute__((visibility("default"))) double ohx_grow_weighted_mean(const uint64_t s[3], uint64_t W) {
+  GrowWideSum x;
+  x.p2 = s[0];
+  x.p1 = s[1];
+  x.p0 = s[2];
+  return grow_wide_mean(x, W);
+}

@@ -48,6 +48,7 @@ constexpr uint32_t kDeepPackWords = 8;
 constexpr uint32_t kDeepPackFeatures = 4 * kDeepPackWords;
 static_assert(kGrowMaxFeatures <= 256, "a feature is a byte");
 enum : int { kRootNone = 0, kRootBag = 1, kRootHess = 2 };
+static_assert(kRootNone == kGrowRootNone && kRootBag == kGrowRootBag && kRootHess == kGrowRootHess, "grow.hpp names them for the host");
 
 // grid (blocks over the rows).  A block's first row and the stride are multiples of 64, so a wave's rows share one word
 // of the bag.  24 bytes a row with weights (20 without), and an eighth of a byte with a bag.
@@ -236,8 +237,9 @@ hipError_t launch_pair_kernel(const GrowArgs& a, const GrowPairArgs& p, const Gr
 
 // The pair kernel, then grow_device.hpp's level loop with this file's launches.  `list`: the tree's own list or nullptr.
 hipError_t pairs_levels(const GrowArgs& a, const GrowPairArgs& p, const uint8_t* list, const GrowPlan& plan, const GrowPlan& levels,
-                        uint32_t round, hipStream_t stream, bool leaf) {
+                        uint32_t round, hipStream_t stream, bool leaf, const GrowPairSplits* splits) {
   if (!pairs_args_sound(a, p)) return hipErrorInvalidValue;
+  if (splits != nullptr && (!splits->split0 || !splits->split1)) return hipErrorInvalidValue;
   const GrowPairPlanes k = planes_of(a, p, list);
   hipError_t e = launch_pair_kernel(a, p, k, plan, stream);
   if (e != hipSuccess) return e;
@@ -249,9 +251,11 @@ hipError_t pairs_levels(const GrowArgs& a, const GrowPairArgs& p, const uint8_t*
                            stream, a, k, d, l.node_group, l.feat_group, l.feat_groups);
       },
       [&](uint32_t blocks, uint32_t d) {
+        if (splits != nullptr) return splits->split0(a, k.list, k.ncols, blocks, d, round, stream);
         hipLaunchKernelGGL((grow_split_pairs_kernel<0, kRootNone>), dim3(blocks), dim3(kBlock), 0, stream, a, k, d, round);
       },
       [&](uint32_t d) {
+        if (splits != nullptr) return splits->split1(a, k.list, k.ncols, root, d, round, stream);
         if (root == kRootHess) hipLaunchKernelGGL((grow_split_pairs_kernel<1, kRootHess>), dim3(1), dim3(kBlock), 0, stream, a, k, d, round);
         else if (root == kRootBag) hipLaunchKernelGGL((grow_split_pairs_kernel<1, kRootBag>), dim3(1), dim3(kBlock), 0, stream, a, k, d, round);
         else hipLaunchKernelGGL((grow_split_pairs_kernel<1, kRootNone>), dim3(1), dim3(kBlock), 0, stream, a, k, d, round);
@@ -264,18 +268,23 @@ hipError_t pairs_levels(const GrowArgs& a, const GrowPairArgs& p, const uint8_t*
 int grow_lds_limits_pairs() { return raise_lds_limit(grow_hist_pairs_kernel, kGrowWeightedMaxPairs * kGrowWeightedPairBytes); }
 
 int launch_grow_tree_pairs(const GrowArgs& a, const GrowPairArgs& p, const GrowPlan& plan, const GrowPlan& levels, uint32_t round,
-                           void* stream) {
+                           void* stream, const GrowPairSplits* splits) {
   const uint8_t* list = a.features != nullptr ? a.features + (uint64_t)round * a.n_sel : nullptr;
-  return pairs_levels(a, p, list, plan, levels, round, static_cast<hipStream_t>(stream), true);
+  return pairs_levels(a, p, list, plan, levels, round, static_cast<hipStream_t>(stream), true, splits);
 }
 
 int launch_grow_tree_deep_pairs(const GrowDeepArgs& d, const GrowPairArgs& p, const GrowDeepPlan& plan, uint32_t round,
-                                GrowLevelState* h_state, void* stream) {
+                                GrowLevelState* h_state, void* stream, const GrowPairSplits* splits) {
   if (!pairs_args_sound(d.g, p)) return hipErrorInvalidValue;
+  if (splits != nullptr && (!splits->deep_split0 || !splits->deep_split1)) return hipErrorInvalidValue;
   GrowDeepLaunches l;
+  if (splits != nullptr) {
+    l.split0 = splits->deep_split0;
+    l.split1 = splits->deep_split1;
+  }
   // (top.features is the tree's own list already: round 0 of its own list, as of its own records)
-  l.top = [&p](const GrowArgs& top, const GrowPlan& lds, void* s) {
-    return (int)pairs_levels(top, p, top.features, lds, lds, 0, static_cast<hipStream_t>(s), false);
+  l.top = [&p, splits](const GrowArgs& top, const GrowPlan& lds, void* s) {
+    return (int)pairs_levels(top, p, top.features, lds, lds, 0, static_cast<hipStream_t>(s), false, splits);
   };
   l.hist = [&p](const GrowDeepArgs& a, uint32_t r, uint32_t batch0, uint32_t nslots, uint32_t hist_blocks, void* s) {
     const GrowPairPlanes k = planes_of(a.g, p, a.g.features != nullptr ? a.g.features + (uint64_t)r * a.g.n_sel : nullptr);

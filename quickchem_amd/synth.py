@@ -128,6 +128,15 @@ def _load():
         lib.ohx_grow_pairs.argtypes = [C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                        C.c_void_p, C.POINTER(C.c_uint32)]
         lib.ohx_grow_pairs_plan.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        lib.ohx_grow_reg_gain.argtypes = [C.c_int64, C.c_uint64, C.c_float, C.c_float, C.c_float]
+        lib.ohx_grow_reg_gain.restype = C.c_double
+        lib.ohx_grow_reg_leaf.argtypes = [C.c_int64, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_void_p]
+        lib.ohx_grow_reg_leaf.restype = None
+        lib.ohx_grow_reg_node_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint64, C.c_float,
+                                                C.c_float, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_double)]
+        lib.ohx_grow_metric_row.argtypes = [C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
+        lib.ohx_grow_weighted_mean.argtypes = [C.c_void_p, C.c_uint64]
+        lib.ohx_grow_weighted_mean.restype = C.c_double
         lib.ohx_cuts_select.argtypes = [C.c_void_p, C.c_uint64, C.c_uint64, C.c_float, C.c_int, C.c_uint64, C.c_void_p,
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_cuts_keys.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
@@ -634,6 +643,58 @@ def grow_pairs_plan(nrow: int, num_feature: int, ncuts: int, max_depth: int, num
     info = (C.c_uint64 * 2)()
     _check(_load().ohx_grow_pairs_plan(nrow, num_feature, ncuts, max_depth, num_cus, info))
     return {"pairs_bytes": int(info[0]), "row_bytes": int(info[1])}
+
+
+GROW_METRICS = {"rmse": 0, "mae": 1, "pseudohuber": 2}
+
+
+def ohx_grow_reg_gain(G: int, H: int, reg_lambda: float, reg_alpha: float, max_delta_step: float) -> float:
+    """csrc/grow.hpp GrowRegHess.gain: the regularised gain of a node's fixed-point sums, a double."""
+    return float(_load().ohx_grow_reg_gain(int(G), int(H), reg_lambda, reg_alpha, max_delta_step))
+
+
+def ohx_grow_reg_leaf(G: int, H: int, eta: float, reg_lambda: float, reg_alpha: float, max_delta_step: float):
+    """csrc/grow.hpp GrowRegHess.solve_leaf -> (leaf, base_weight, sum_hess) float32."""
+    out = np.zeros(3, dtype=np.float32)
+    _load().ohx_grow_reg_leaf(int(G), int(H), eta, reg_lambda, reg_alpha, max_delta_step, out.ctypes.data)
+    return out[0], out[1], out[2]
+
+
+def grow_reg_node_split(Gh, Hh, cut_ptr, Gp: int, Hp: int, reg_lambda: float, min_child_weight: float, reg_alpha: float,
+                        max_delta_step: float):
+    """csrc/grow.hpp grow_node_split with GrowRegHess over the histograms Gh int64 / Hh uint64 [F][256] -> None or
+    (loss_chg, f, j, dl, GL, HL)."""
+    Gh = np.ascontiguousarray(Gh, dtype=np.int64)
+    Hh = np.ascontiguousarray(Hh, dtype=np.uint64)
+    ptr = np.ascontiguousarray(cut_ptr, dtype=np.uint64)
+    assert Gh.shape == Hh.shape and Gh.shape[1] == 256 and len(ptr) == Gh.shape[0] + 1
+    out = np.zeros(4, dtype=np.uint64)
+    loss = C.c_double()
+    _check(_load().ohx_grow_reg_node_split(Gh.ctypes.data, Hh.ctypes.data, Gh.shape[0], ptr.ctypes.data, int(Gp), int(Hp), reg_lambda,
+                                           min_child_weight, reg_alpha, max_delta_step, out.ctypes.data, C.byref(loss)))
+    if not int(out[0]):
+        return None
+    key = int(out[1])
+    return float(loss.value), key >> 9, (key >> 1) & 255, key & 1, int(out[2:3].view(np.int64)[0]), int(out[3])
+
+
+def ohx_grow_metric_row(metric: str, slope: float, pred, y):
+    """csrc/grow.hpp grow_metric_row over the rows: what a row adds to S beside its hq by `metric` ("rmse", "mae" or
+    "pseudohuber" with `slope`) -> (sq uint64 [n], sound bool [n]); a refused residual has sq = 0."""
+    pred = np.ascontiguousarray(pred, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    assert pred.shape == y.shape and pred.ndim == 1
+    sq = np.zeros(max(y.size, 1), dtype=np.uint64)
+    sound = np.zeros(max(y.size, 1), dtype=np.uint8)
+    _check(_load().ohx_grow_metric_row(GROW_METRICS[metric], float(slope), pred.ctypes.data, y.ctypes.data, y.size, sq.ctypes.data,
+                                       sound.ctypes.data))
+    return sq[:y.size], sound[:y.size].astype(bool)
+
+
+def boost_weighted_mean(p2: int, p1: int, p0: int, W: int) -> float:
+    """csrc/grow.cpp grow_wide_mean: ((double)(p2 * 2^64 + p1 * 2^32 + p0) * 2^-48) / ((double)W * 2^-24)."""
+    s = np.ascontiguousarray([p2, p1, p0], dtype=np.uint64)
+    return float(_load().ohx_grow_weighted_mean(s.ctypes.data, W))
 
 
 def boost_weighted_rmse(p2: int, p1: int, p0: int, W: int) -> float:

@@ -1,0 +1,293 @@
+""""ohx_reg_alpha", "ohx_max_delta_step" and "ohx_eval_metric" on the GPU (csrc/grow_reg.hip, through XGBoosterSetParam and
+the keywords of the Python binding).  Every array of every new tree, nodes_added, rounds_run and best_round are compared
+as integers or bit for bit, both metric arrays with ==, and models byte for byte in all three formats.
+
+The expected values are the restatement's (tests/grow_reg_support.py, written from the header) and, where the header
+states an equality, another call on a twin booster.  The model of every case has no tree, so the margin a restatement
+starts from is the model's base.  What a case is meant to reach - weights that are clipped, weights that are zeroed, a stop
+rule that the metric moves - is asserted from the restatement before the GPU is asked."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from quickchem_amd import capi, synth
+from tests import grow_deep_support as D
+from tests import grow_objective_support as O
+from tests import grow_reg_support as RG
+from tests import grow_support as G
+from tests.test_gpu_grow import held, same_new_trees
+from tests.test_gpu_grow_eval import same_result, saved
+from tests.test_gpu_grow_objective import KINDS, N, HELD, NFEAT, NAN, ROWS_PAST_A_STRIDE, booster, call, done, kind_kw, same_arrays
+
+pytestmark = pytest.mark.gpu
+
+SEED = 26
+# (objective, alpha, m): the cases of the issue, each binding on the restatement
+REG_CASES = (("pseudohuber", 0.0, 0.5), ("pseudohuber", 0.5, 0.0), ("pseudohuber", 0.5, 0.5), ("squarederror", 2.0, 1.0))
+
+
+@pytest.fixture(scope="module")
+def torch_cuda():
+    import torch
+    assert torch.cuda.is_available(), "these tests need the MI355X"
+    torch.cuda.set_device(0)
+    return torch
+
+
+def restated(kind, objective="squarederror", slope=1.0, alpha=0.0, m=0.0, metric="rmse", n=N, seed=SEED, rounds=2, held_out=HELD,
+             patience=0, deep_depth=11, max_depth=None, **more):
+    kw = kind_kw(kind, deep_depth)
+    return RG.restated(objective, slope, alpha, m, metric, n, seed, max_depth or kw["max_depth"], nfeat=NFEAT, rounds=rounds,
+                       held_out=held_out, patience=patience, subsample=kw.get("subsample", 1.0),
+                       colsample=kw.get("colsample_bytree", 1.0), draw_seed=kw.get("seed", 0), **more)
+
+
+def params_of(objective="squarederror", slope=1.0, alpha=0.0, m=0.0, metric="rmse"):
+    return (("ohx_objective", objective), ("ohx_huber_slope", repr(float(slope))), ("ohx_reg_alpha", repr(float(alpha))),
+            ("ohx_max_delta_step", repr(float(m))), ("ohx_eval_metric", metric))
+
+
+def check(torch, tmp_path, kind, want, x, y, w, cuts, ev, params, what, device=False, **kw):
+    b = booster(params, nfeat=x.shape[1])
+    got, mats = call(torch, b, kind, x, y, w, cuts, ev, device=device, **kw)
+    same_result(got, want, what)
+    same_new_trees(held(b, tmp_path)[0], want["trees"], 0, what)
+    image = saved(b, tmp_path)
+    done(b, mats)
+    return got, image
+
+
+# ---- 1. every kind against the restatement ----
+
+@pytest.mark.parametrize("device", (False, True), ids=("host", "device"))
+@pytest.mark.parametrize("objective,alpha,m", REG_CASES)
+@pytest.mark.parametrize("kind", KINDS)
+def test_regularised_trees_against_the_restatement(torch_cuda, tmp_path, kind, objective, alpha, m, device):
+    x, y, w, cuts, ev, want = restated(kind, objective, 1.0, alpha, m)
+    seen = [s for tree in want["seen"] for s in tree]
+    clipped, zeroed, neither = RG.binding(seen, m)
+    assert neither > 0 and (m == 0 or clipped > 0) and (alpha == 0 or zeroed > 0), (clipped, zeroed, neither)
+    *_, plain = restated(kind, objective, 1.0)
+    assert any(not np.array_equal(a["base_weight"], b["base_weight"]) for a, b in zip(want["trees"], plain["trees"])), "the tree differs"
+    if "deep" in kind:
+        assert D.depth_of(want["all_trees"][0]) > 8 and D.levels(want["all_trees"][0])[8][1] > 0, "level 8 splits"
+    kw = dict(kind_kw(kind), rounds=2)
+    what = f"{kind}, {objective} at ({alpha}, {m})"
+    if device:     # the device form, its parameters set by XGBoosterSetParam
+        check(torch_cuda, tmp_path, kind, want, x, y, w, cuts, ev, params_of(objective, 1.0, alpha, m), what, device=True, **kw)
+    else:          # the host form, by the keyword arguments of the binding
+        check(torch_cuda, tmp_path, kind, want, x, y, w, cuts, ev, (), what, objective=objective, huber_slope=1.0, reg_alpha=alpha,
+              max_delta_step=m, **kw)
+
+
+# ---- 2. deep levels with more open nodes than a batch holds ----
+
+@pytest.mark.parametrize("kind,n,sampling", (("deep", 24000, {}), ("deep_sampled", 32000, dict(subsample=0.9, colsample_bytree=0.75, seed=11))))
+def test_regularised_with_more_open_nodes_than_a_batch_holds(torch_cuda, tmp_path, kind, n, sampling):
+    """Depth 16, one round, (alpha, m) = (0.5, 0.5).  At weights of 1 an alpha of 0.5 closes these rows' small nodes long before a
+    level holds 1024 of them (404 on the restatement), so every row weighs 128: a node's sums grow with the weight, alpha does
+    not, and a level of the restated tree has more open nodes than a batch while weights are still clipped and zeroed."""
+    x, y, _, cuts, _ = O.inputs(n, 263, NFEAT, 64, 0)
+    w = np.full(n, 128.0, np.float32)
+    want = RG.boost("pseudohuber", 1.0, 0.5, 0.5, "rmse", np.full(n, O.BASE, np.float32), x, NAN, y, w, cuts, NFEAT, rounds=1, max_depth=16,
+                    eta=0.125, lam=1.0, min_child_weight=0.0, subsample=sampling.get("subsample", 1.0),
+                    colsample_bytree=sampling.get("colsample_bytree", 1.0), seed=sampling.get("seed", 0))
+    batch = synth.grow_deep_batch()
+    assert max(o for o, _ in D.levels(want["trees"][0])) > batch, "a level of two batches"
+    clipped, zeroed, neither = RG.binding(want["seen"][0], 0.5)
+    assert clipped > 0 and zeroed > 0 and neither > 0
+    kw = dict(kind_kw(kind, deep_depth=16), rounds=1, **sampling)
+    check(torch_cuda, tmp_path, kind, want, x, y, w, cuts, None, params_of("pseudohuber", 1.0, 0.5, 0.5), kind + ", two batches", **kw)
+
+
+# ---- 3. more rows than one trip of the streaming grids, in both sets ----
+
+@pytest.fixture(scope="module")
+def long_rows():
+    n = ROWS_PAST_A_STRIDE
+    x, y, w, _, ev = O.inputs(n, 272, NFEAT, 8, n)
+    cuts = G.quantile_cuts(x[:N], NAN, 16)
+    return x, y, w, cuts, ev
+
+
+@pytest.mark.parametrize("metric", RG.METRICS)
+def test_rows_past_one_stride_of_the_streaming_grids(torch_cuda, tmp_path, long_rows, metric):
+    """The metric kernels take a second trip over the training rows and over the held-out rows; the sums are the
+    restatement's exact integers, seen through the doubles the call returns."""
+    x, y, w, cuts, ev = long_rows
+    n = len(y)
+    assert n % 64 != 0 and len(ev[2]) == n
+    want = RG.boost("squarederror", 3.7, 0.0, 0.0, metric, np.full(n, O.BASE, np.float32), x, NAN, y, w, cuts, NFEAT, eval_set=ev,
+                    eval_pred=np.full(n, O.BASE, np.float32), rounds=2, max_depth=3, eta=0.125, lam=1.0, min_child_weight=0.0)
+    assert len(set(want["train_sums"])) == 3 and len(set(want["eval_sums"])) == 3
+    check(torch_cuda, tmp_path, "weighted", want, x, y, w, cuts, ev, params_of(slope=3.7, metric=metric), f"long rows, {metric}", rounds=2,
+          max_depth=3, eta=0.125, reg_lambda=1.0, min_child_weight=0.0)
+
+
+# ---- 4. the metrics of every kind ----
+
+@pytest.mark.parametrize("metric,slope", (("mae", 1.0), ("pseudohuber", 0.5), ("pseudohuber", 3.7)))
+@pytest.mark.parametrize("kind", KINDS)
+def test_metrics_against_the_restatement(torch_cuda, tmp_path, kind, metric, slope):
+    """The objective stays squared error: the metric alone leaves the tree kernels inline, and delta is the slope all the same."""
+    x, y, w, cuts, ev, want = restated(kind, "squarederror", slope, metric=metric, rounds=3, patience=2)
+    *_, by_rmse = restated(kind, "squarederror", slope, rounds=3, patience=2)
+    assert want["train_rmse"] != by_rmse["train_rmse"] and want["eval_rmse"] != by_rmse["eval_rmse"]
+    kw = dict(kind_kw(kind), rounds=3, patience=2)
+    check(torch_cuda, tmp_path, kind, want, x, y, w, cuts, ev, (), f"{kind}, {metric} at {slope}", huber_slope=slope, eval_metric=metric, **kw)
+
+
+@pytest.mark.parametrize("kind", ("weighted", "deep_sampled"))
+def test_metrics_under_the_regularised_pseudohuber_objective(torch_cuda, tmp_path, kind):
+    x, y, w, cuts, ev, want = restated(kind, "pseudohuber", 1.0, 0.5, 0.5, "pseudohuber", rounds=3, patience=2)
+    kw = dict(kind_kw(kind), rounds=3, patience=2)
+    check(torch_cuda, tmp_path, kind, want, x, y, w, cuts, ev, params_of("pseudohuber", 1.0, 0.5, 0.5, "pseudohuber"), kind, device=True, **kw)
+
+
+@pytest.mark.parametrize("kind", KINDS)
+def test_rmse_set_explicitly_is_the_default(torch_cuda, tmp_path, kind):
+    x, y, w, cuts, ev = O.inputs(N, 273, NFEAT, 64, HELD)
+    kw = dict(kind_kw(kind), rounds=2)
+    results = []
+    for params in ((), (("ohx_eval_metric", "rmse"),)):
+        b = booster(params)
+        got, mats = call(torch_cuda, b, kind, x, y, w, cuts, ev, **kw)
+        results.append((got, saved(b, tmp_path)))
+        done(b, mats)
+    same_arrays(results[1][0], results[0][0], kind)
+    assert results[1][1] == results[0][1], kind
+
+
+# ---- 5. the metric decides what is kept ----
+
+def test_the_metric_decides_what_is_kept_at_squared_error(torch_cuda, tmp_path):
+    stops = {}
+    for metric in RG.METRICS:
+        x, y, w, cuts, ev, want = restated("weighted", "squarederror", 1.0, metric=metric, rounds=12, patience=2, max_depth=3)
+        stops[metric] = (want["rounds_run"], want["best_round"])
+    assert stops == {"rmse": (5, 3), "mae": (9, 7), "pseudohuber": (9, 7)}, stops
+    for metric in RG.METRICS:
+        x, y, w, cuts, ev, want = restated("weighted", "squarederror", 1.0, metric=metric, rounds=12, patience=2, max_depth=3)
+        kw = dict(kind_kw("weighted"), rounds=12, patience=2, max_depth=3)
+        b = booster(params_of(metric=metric))
+        got, mats = call(torch_cuda, b, "weighted", x, y, w, cuts, ev, **kw)
+        same_result(got, want, metric)
+        trees = held(b, tmp_path)[0]
+        assert (got["rounds_run"], got["best_round"]) == stops[metric] and len(trees) == stops[metric][1]
+        same_new_trees(trees, want["trees"], 0, metric)
+        done(b, mats)
+
+
+def test_the_robust_metric_keeps_the_robust_loss_going(torch_cuda, tmp_path):
+    """Pseudo-Huber at depth 6 and patience 1: the RMSE of labels with wild cells stops the call at round 9 and keeps 8
+    trees, while its own error is still falling at round 12."""
+    stops = {}
+    for metric in RG.METRICS:
+        x, y, w, cuts, ev, want = restated("weighted", "pseudohuber", 1.0, metric=metric, rounds=12, patience=1)
+        stops[metric] = (want["rounds_run"], want["best_round"])
+    assert stops == {"rmse": (9, 8), "mae": (12, 12), "pseudohuber": (12, 12)}, stops
+    for metric in ("rmse", "pseudohuber"):
+        x, y, w, cuts, ev, want = restated("weighted", "pseudohuber", 1.0, metric=metric, rounds=12, patience=1)
+        kw = dict(kind_kw("weighted"), rounds=12, patience=1)
+        got, _ = check(torch_cuda, tmp_path, "weighted", want, x, y, w, cuts, ev, params_of("pseudohuber", metric=metric), metric, **kw)
+        assert (got["rounds_run"], got["best_round"]) == stops[metric]
+
+
+# ---- 6. the defaults ----
+
+@pytest.mark.parametrize("objective", O.OBJECTIVES)
+def test_setting_the_defaults_again_restores_the_default_bytes(torch_cuda, tmp_path, objective):
+    x, y, w, cuts, ev = O.inputs(N, 274, NFEAT, 64, HELD)
+    kw = dict(kind_kw("sampled"), rounds=2)
+    plain = booster((("ohx_objective", objective),))
+    first, mats = call(torch_cuda, plain, "sampled", x, y, w, cuts, ev, **kw)
+    image = saved(plain, tmp_path)
+    done(plain, mats)
+    b = booster(params_of(objective, 1.0, 0.5, 0.5, "mae"))
+    other, mats = call(torch_cuda, b, "sampled", x, y, w, cuts, ev, **kw)
+    assert saved(b, tmp_path) != image and other["train_rmse"].tolist() != first["train_rmse"].tolist()
+    done(b, mats)
+    b = booster(params_of(objective, 1.0, 0.5, 0.5, "mae"))
+    for name, value in (("ohx_reg_alpha", "0"), ("ohx_max_delta_step", "0"), ("ohx_eval_metric", "rmse")):
+        b.set_param(name, value)
+    got, mats = call(torch_cuda, b, "sampled", x, y, w, cuts, ev, **kw)
+    same_arrays(got, first, objective)
+    assert saved(b, tmp_path) == image
+    done(b, mats)
+
+
+# ---- 7. the order of the rows, and the grid ----
+
+@pytest.mark.parametrize("kind", ("weighted", "deep"))
+def test_row_order_and_the_grid_change_nothing(torch_cuda, tmp_path, kind):
+    x, y, w, cuts, ev, want = restated(kind, "pseudohuber", 1.0, 0.5, 0.5, "mae")
+    kw = dict(kind_kw(kind), rounds=2)
+    params = params_of("pseudohuber", 1.0, 0.5, 0.5, "mae")
+    _, image = check(torch_cuda, tmp_path, kind, want, x, y, w, cuts, ev, params, kind, **kw)
+    order = np.random.default_rng(275).permutation(N)
+    b = booster(params)
+    got, mats = call(torch_cuda, b, kind, np.ascontiguousarray(x[order]), y[order], w[order], cuts, ev, grid=True, **kw)
+    same_result(got, want, kind + ", permuted")
+    assert saved(b, tmp_path) == image, "permuted rows on a grid"
+    done(b, mats)
+
+
+# ---- 8. refusals ----
+
+def test_refusals_leave_the_forest_and_the_outputs_alone(torch_cuda, tmp_path):
+    x, y, w, cuts, ev = O.inputs(N, 276, NFEAT, 64, HELD)
+    kw = dict(kind_kw("weighted"), rounds=2)
+    b = booster()
+    d = capi.DMatrix(x, missing=NAN)
+    b.boost_trees_weighted(d, y, cuts, weights=w, **kw)      # a forest to leave alone
+    before = saved(b, tmp_path)
+    tx, ty = torch_cuda.from_numpy(x).cuda(), torch_cuda.from_numpy(y).cuda()
+    dd = capi.DMatrix(device_ptr=tx.data_ptr(), nrow=N, ncol=NFEAT, missing=NAN)
+    torch_cuda.cuda.synchronize()
+    defaults = {"ohx_reg_alpha": "0", "ohx_max_delta_step": "0", "ohx_eval_metric": "rmse"}
+    for name, value in (("ohx_reg_alpha", "0.5"), ("ohx_max_delta_step", "0.5"), ("ohx_eval_metric", "mae")):
+        b.set_param(name, value)
+        for refused in (lambda: b.boost_trees(d, y, cuts, rounds=1, max_depth=3),
+                        lambda: b.boost_trees_eval(d, y, cuts, rounds=1, max_depth=3),
+                        lambda: b.boost_trees_device(dd, ty.data_ptr(), N, cuts, rounds=1, max_depth=3),
+                        lambda: b.boost_trees_eval_device(dd, ty.data_ptr(), N, cuts, rounds=1, max_depth=3)):
+            with pytest.raises(capi.OhxError, match="OHXBoosterBoostTreesWeighted"):
+                refused()
+        if name == "ohx_eval_metric":      # the metric does not concern the refit
+            twin = booster()
+            twin.boost_trees_weighted(d, y, cuts, weights=w, **kw)
+            twin.set_param(name, value)
+            twin.refit_leaves(d, y)
+            twin.free()
+        else:
+            with pytest.raises(capi.OhxError, match="OHXBoosterBoostTreesWeighted"):
+                b.refit_leaves(d, y)
+            with pytest.raises(capi.OhxError, match="OHXBoosterBoostTreesWeighted"):
+                b.refit_leaves_device(dd, ty.data_ptr(), N)
+        assert saved(b, tmp_path) == before, name
+        b.set_param(name, defaults[name])
+    # a refused value leaves the handle's setting
+    for name in ("ohx_reg_alpha", "ohx_max_delta_step"):
+        with pytest.raises(capi.OhxError, match=name):
+            b.set_param(name, "-1")
+    with pytest.raises(capi.OhxError, match="ohx_eval_metric"):
+        b.set_param("ohx_eval_metric", "mse")
+    b.boost_trees(d, y, cuts, rounds=1, max_depth=3)         # the defaults again: the count call is no refusal
+    before = saved(b, tmp_path)
+
+    # a NaN label under mae: "label", and preset outputs stay, through the C interface itself
+    b.set_param("ohx_eval_metric", "mae")
+    ptr, vals = b._cuts(cuts)
+    bad = y.copy()
+    bad[7] = np.nan
+    train, evals = np.full(3, -7.0), np.full(3, -7.0)
+    run, best, added = C.c_int32(-7), C.c_int32(-7), C.c_uint64(77)
+    rc = b.lib.OHXBoosterBoostTreesWeighted(b.handle, d.handle, bad.ctypes.data, w.ctypes.data, N, None, None, None, 0, ptr.ctypes.data,
+                                            vals.ctypes.data, 2, 3, 0.5, 1.0, 0.0, 0.0, 0, train.ctypes.data, evals.ctypes.data,
+                                            C.byref(run), C.byref(best), C.byref(added))
+    with pytest.raises(capi.OhxError, match="label"):
+        capi.check(b.lib, rc)
+    assert np.all(train == -7.0) and np.all(evals == -7.0) and run.value == -7 and best.value == -7 and added.value == 77
+    assert saved(b, tmp_path) == before, "a NaN label under mae"
+    done(b, [d, dd])

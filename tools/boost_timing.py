@@ -151,6 +151,9 @@ def main():
     ap.add_argument("--objective", choices=("squarederror", "pseudohuber"), default="squarederror", help="ohx_objective of the timed boosters")
     ap.add_argument("--huber-slope", type=float, default=1.0, help="ohx_huber_slope of the timed boosters")
     ap.add_argument("--pairs", choices=("auto", "on"), default="auto", help="ohx_grow_pairs of the timed boosters")
+    ap.add_argument("--reg-alpha", type=float, default=0.0, help="ohx_reg_alpha of the timed boosters")
+    ap.add_argument("--max-delta-step", type=float, default=0.0, help="ohx_max_delta_step of the timed boosters")
+    ap.add_argument("--eval-metric", choices=("rmse", "mae", "pseudohuber"), default="rmse", help="ohx_eval_metric of the timed boosters")
     args = ap.parse_args()
     sampled = args.subsample is not None or args.colsample is not None
     if sampled:
@@ -162,8 +165,9 @@ def main():
         ap.error("--deep times the call without a held-out set: leave --holdout out")
     if args.weights != "none" and args.holdout:
         ap.error("--weights times the call without a held-out set: leave --holdout out")
-    if (args.objective != "squarederror" or args.pairs != "auto") and (args.holdout or not (sampled or args.deep or args.weights != "none")):
-        ap.error("--objective / --pairs time a call with row weights: give --weights, --subsample / --colsample or --deep, and no --holdout")
+    regularised = args.reg_alpha != 0.0 or args.max_delta_step != 0.0 or args.eval_metric != "rmse"
+    if (args.objective != "squarederror" or args.pairs != "auto" or regularised) and (args.holdout or not (sampled or args.deep or args.weights != "none")):
+        ap.error("--objective / --pairs / --reg-alpha / --max-delta-step / --eval-metric time a call with row weights: give --weights, --subsample / --colsample or --deep, and no --holdout")
     assert torch.cuda.is_available(), "boost_timing needs the MI355X"
     torch.cuda.set_device(0)
     model = synth.make_model()
@@ -252,6 +256,7 @@ def main():
         weights = torch.rand(n, dtype=torch.float32, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1)) * 4.0
     res["weights"] = args.weights
     res["objective"] = {"ohx_objective": args.objective, "ohx_huber_slope": args.huber_slope, "ohx_grow_pairs": args.pairs}
+    res["regularisation"] = {"ohx_reg_alpha": args.reg_alpha, "ohx_max_delta_step": args.max_delta_step, "ohx_eval_metric": args.eval_metric}
     res["pair_planes"] = synth.grow_pairs_plan(n, F, ncuts, args.max_depth, cus)
 
     def timed_booster():
@@ -259,6 +264,10 @@ def main():
         b.set_param("ohx_objective", args.objective)
         b.set_param("ohx_huber_slope", repr(args.huber_slope))
         b.set_param("ohx_grow_pairs", args.pairs)
+        if regularised:        # (left unset otherwise: the tool then also runs against a library from before the parameters)
+            b.set_param("ohx_reg_alpha", repr(args.reg_alpha))
+            b.set_param("ohx_max_delta_step", repr(args.max_delta_step))
+            b.set_param("ohx_eval_metric", args.eval_metric)
         return b
 
     last = {}                              # what the weighted call returned last
@@ -318,7 +327,7 @@ def main():
         per_round = (res[f"rounds_{args.rounds}"]["median_s"] - res["rounds_1"]["median_s"]) / (args.rounds - 1)
         res["per_round_s"] = per_round
         res["one_off_s"] = res["rounds_1"]["median_s"] - per_round
-    if not args.skip_rmse and not args.holdout and not args.deep_only and args.objective == "squarederror":
+    if not args.skip_rmse and not args.holdout and not args.deep_only and args.objective == "squarederror" and not regularised:
         b = capi.Booster(model_buffer=model.image)
         res["rmse_before"] = rmse(b)
         b.refit_leaves_device(d, labels.data_ptr(), n, eta=1.0, reg_lambda=1.0, stream=stream)
