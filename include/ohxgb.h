@@ -231,6 +231,22 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *                     ohx_max_delta_step is not 0 so does OHXBoosterRefitLeaves[Device] (it would refit unregularised
  *                     leaves); the message names OHXBoosterBoostTreesWeighted.  With all three at their defaults every
  *                     boost call runs the kernels it ran before they existed
+ *   "ohx_monotone_constraints" the monotone constraints of boosting: `(` entries `)` with the entries separated by `,`,
+ *                     each -1, 0, 1 or +1; spaces and tabs between tokens are ignored, so Python's str((1, 0, -1)) is
+ *                     valid; () is the default, none.  Entry f is c_f, the constraint on feature f of the booster: +1 =
+ *                     a new tree must not fall as x_f rises, -1 = must not rise, 0 = free; fewer entries than
+ *                     num_feature means 0 for the rest.  At most 128 entries.  Anything else ("", no parentheses, 2, 1.0,
+ *                     a trailing comma, 129 entries) returns -1 and the message names "ohx_monotone_constraints".  A
+ *                     list whose entries are all 0 is the default: such a call launches nothing new and produces the
+ *                     default's bytes.  Kept on the handle and written into no model file; the name without the prefix
+ *                     is xgboost's and stays ignored.  It acts on OHXBoosterBoostTreesWeighted, ...Sampled, ...Deep and
+ *                     ...DeepSampled as defined with the Weighted call below (docs/28_monotone_constraints.md).  More
+ *                     entries than num_feature make each of those calls return -1 before anything is enqueued, and the
+ *                     message names the parameter.  While some c_f != 0, OHXBoosterBoostTrees[Device] and
+ *                     OHXBoosterBoostTreesEval[Device] (row counts; their split kernels keep no intervals) and
+ *                     OHXBoosterRefitLeaves[Device] (a refit would undo the intervals) return -1 before anything is
+ *                     enqueued; the message names OHXBoosterBoostTreesWeighted.  In every refusal the forest and the
+ *                     outputs are untouched
  * None of them changes a prediction.
  * xgboost's own parameter names ("nthread", "predictor", ...) are accepted and
  * ignored. */
@@ -757,6 +773,26 @@ int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, con
  * which nodes are evaluated, min_child_weight on Hd, sum_hess, the node numbering, the record format and the refusals of
  * a root with H == 0 ("bag", "hessian").  A loss_chg may now be negative where a child is clipped; such a candidate loses
  * to gamma >= 0 as any other.
+ * Monotone constraints ("ohx_monotone_constraints": c_f of feature f).  What is stated above is every c_f = 0.  With any
+ * c_f != 0 ("active"), and Gd, Hd, D, alpha and m as under Regularisation - every operation is a double operation and
+ * rounds once, nothing is fused - every node p carries an interval (lo_p, hi_p) of doubles, the root's (-inf, +inf), and
+ *   w(G, H; lo, hi) = the w above (L1 threshold, then the step clip), then clamped:  w < lo ? lo : (w > hi ? hi : w)
+ *   gain_w(G, H, w) = -((2.0 * Gd) * w + (D * w) * w) - (2.0 * alpha) * fabs(w)
+ * gain_w is the second gain form above at a weight that is given; with active constraints it is used for every node of
+ * the tree, whatever m is.  For candidate (f, j, dl) of node p, wL = w(GL, HL; lo_p, hi_p) and wR likewise.  It is
+ * admitted when the rule above admits it and c_f == 0, or c_f > 0 && wL <= wR, or c_f < 0 && wL >= wR, and
+ *   loss_chg = (gain_w(L, wL) + gain_w(R, wR)) - gain_w(P, w(Gp, Hp; lo_p, hi_p))
+ * When p splits on f, mid = (wL + wR) * 0.5; with c_f > 0 the left child gets (lo_p, mid) and the right (mid, hi_p), with
+ * c_f < 0 the left gets (mid, hi_p) and the right (lo_p, mid), and with c_f == 0 both inherit (lo_p, hi_p).  wL and wR lie
+ * in the children's own intervals, so a child's weight is the same under its parent's interval and under its own.
+ *   base_weight = (float) w(G, H; lo, hi) with the node's own interval;   leaf = base_weight * eta  (one float32 multiply)
+ * Unchanged: the candidates and their total order (f, j, dl) with the original f under a feature list, and the ties; which
+ * splits the rule above admits and which nodes are evaluated, min_child_weight on Hd, and sum_hess; the node numbering,
+ * the record format and the refusals of a root with H == 0; the bag, the metrics, the stop rule, all or nothing, both forms
+ * and "not capturable".  A negative loss_chg loses to gamma >= 0 as above.  The consequence: for eta > 0 a new tree is
+ * non-decreasing (c_f = 1) or non-increasing (c_f = -1) in x_f over non-missing values, with every other feature fixed;
+ * a row whose x_f is missing goes where default_left sends it and is outside the claim.  Parity with libxgboost is not
+ * pinned; the text above is the definition.  The same holds for OHXBoosterBoostTreesSampled, ...Deep and ...DeepSampled.
  * The metric ("ohx_eval_metric").  What is stated above is rmse.  For one row z = pred - y in float32 (refused as above if
  * not finite or |z| >= 256), hq = rint(w * 2^24), delta = "ohx_huber_slope" whatever the objective, and
  *   rmse         sq = e * e,  e = (int64) rint(z * 2^24)

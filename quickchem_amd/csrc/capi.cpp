@@ -689,7 +689,14 @@ struct GrowState {
   DevBuf<uint32_t> d_pair_hq;
   DevBuf<uint8_t> d_identity;
   PinnedBuf<uint8_t> h_identity;
+  // monotone constraints (grow_mono.hip): the weight intervals of the tree at hand, two doubles a node of the call's node
+  // stride, and the constraints of every feature; allocated only where a constraint is active
+  DevBuf<double> d_mono_bounds;
+  DevBuf<int8_t> d_mono_constraints;
+  PinnedBuf<int8_t> h_mono_constraints;
   void release_device() {
+    d_mono_bounds.release();
+    d_mono_constraints.release();
     d_pair_q.release();
     d_pair_hq.release();
     d_identity.release();
@@ -861,6 +868,9 @@ struct BoosterObj {
   float grow_alpha = 0.0f;                     // "ohx_reg_alpha": the L1 threshold on a node's gradient sum
   float grow_max_delta_step = 0.0f;            // "ohx_max_delta_step": the bound on |base_weight|; 0 is off
   uint32_t grow_metric = kGrowMetricRmse;      // "ohx_eval_metric": what train_rmse[] / eval_rmse[] hold and the stop rule compares
+  // (docs/28_monotone_constraints.md): "ohx_monotone_constraints", entry f is c_f; empty is the default, and a list of
+  // zeros is kept as the empty list it stands for
+  std::vector<int8_t> grow_mono;
   std::unique_ptr<RefitState> refit;
   std::unique_ptr<GrowState> grow;
 };
@@ -2099,6 +2109,42 @@ void read_visit_counts(BoosterObj& b, VisitState& v, hipStream_t stream) {
   visit_node_sums(b.forest, w.vf, reinterpret_cast<const uint64_t*>(v.h_leaf.p), v.node_counts.data());
 }
 
+// "ohx_monotone_constraints": `(` entries `)` separated by `,`, each -1, 0, 1 or +1, spaces and tabs between tokens; at most
+// kGrowMaxConstraints entries.  A list of zeros is the default and comes back empty.
+std::vector<int8_t> parse_monotone_constraints(const char* value) {
+  const OhxError bad("ohx_monotone_constraints must be a list such as (1,0,-1): entries -1, 0, 1 or +1 in parentheses, separated by "
+                     "commas, at most 128 of them");
+  std::vector<int8_t> c;
+  const char* p = value;
+  auto blanks = [&]() {
+    while (*p == ' ' || *p == '\t') ++p;
+  };
+  blanks();
+  if (*p++ != '(') throw bad;
+  blanks();
+  if (*p != ')') {
+    for (;;) {
+      int8_t v;
+      if (p[0] == '0') v = 0, p += 1;
+      else if (p[0] == '1') v = 1, p += 1;
+      else if (p[0] == '+' && p[1] == '1') v = 1, p += 2;
+      else if (p[0] == '-' && p[1] == '1') v = -1, p += 2;
+      else throw bad;
+      if (c.size() == kGrowMaxConstraints) throw bad;
+      c.push_back(v);
+      blanks();
+      if (*p == ')') break;
+      if (*p++ != ',') throw bad;
+      blanks();
+    }
+  }
+  ++p;
+  blanks();
+  if (*p != '\0') throw bad;
+  if (std::all_of(c.begin(), c.end(), [](int8_t v) { return v == 0; })) c.clear();
+  return c;
+}
+
 // ---- leaf refit (refit.hpp) ----
 
 // Both forms of OHXBoosterRefitLeaves.  The refusals that need neither a matrix nor a device come first, in the
@@ -2117,6 +2163,9 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
   if (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f)
     throw OhxError(std::string(what) + " refits unregularised leaves: it is refused while ohx_reg_alpha or ohx_max_delta_step is set; "
                    "grow with OHXBoosterBoostTreesWeighted, or set both to 0; nothing was enqueued");
+  if (!b.grow_mono.empty())
+    throw OhxError(std::string(what) + " refits every leaf on its own and would undo the weight intervals: it is refused while "
+                   "ohx_monotone_constraints is active; grow with OHXBoosterBoostTreesWeighted, or set it to (); nothing was enqueued");
   if (labels == nullptr) throw OhxError(std::string(what) + ": labels is NULL");
   if (!std::isfinite(eta)) throw OhxError(std::string(what) + ": eta must be finite");
   if (!(std::isfinite(lambda) && lambda >= 0.0f)) throw OhxError(std::string(what) + ": lambda must be finite and >= 0");
@@ -2347,11 +2396,14 @@ struct BoostKind {
   // regularised (ohx_reg_alpha or ohx_max_delta_step is not 0; then `pairs` holds too): the pair path with grow_reg.hip's
   // split launches.  metric: what a row adds to the sums; away from rmse the metric kernels are grow_reg.hip's.  The two
   // choices are independent, and with neither nothing of grow_reg.hip is touched.
-  bool regularised = false;
+  // constrained (ohx_monotone_constraints holds an entry that is not 0; then `pairs` holds too, and `regularised` is not
+  // asked): the pair path with grow_mono.hip's split launches, which carry alpha and max_delta_step themselves.  Without
+  // it nothing of grow_mono.hip is touched.
+  bool regularised = false, constrained = false;
   GrowPairSplits reg_splits;
   uint32_t metric = kGrowMetricRmse;
   float slope = 1.0f;
-  const GrowPairSplits* splits() const { return regularised ? &reg_splits : nullptr; }
+  const GrowPairSplits* splits() const { return constrained || regularised ? &reg_splits : nullptr; }
   bool wide() const { return which != Plain; }
   // The call's one plan, asked for once: the level loop over `cols` histogram columns - F itself, or the n_sel features
   // a tree of a sampled call sees (compact histograms and candidates) - the streaming kernels, which do not depend on
@@ -2435,6 +2487,12 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (!weighted && (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f || b.grow_metric != kGrowMetricRmse))
     throw OhxError(w0 + " keeps row counts and two-word sums: with ohx_reg_alpha, ohx_max_delta_step or ohx_eval_metric set call "
                    "OHXBoosterBoostTreesWeighted (weights may be NULL) or a later form; nothing was enqueued and the forest is unchanged");
+  if (!weighted && !b.grow_mono.empty())
+    throw OhxError(w0 + " keeps row counts, and its split kernels no weight intervals: with ohx_monotone_constraints active call "
+                   "OHXBoosterBoostTreesWeighted (weights may be NULL) or a later form; nothing was enqueued and the forest is unchanged");
+  if (b.grow_mono.size() > (size_t)b.forest.num_feature)
+    throw OhxError(w0 + ": ohx_monotone_constraints has " + std::to_string(b.grow_mono.size()) + " entries but the booster " +
+                   std::to_string(b.forest.num_feature) + " features; nothing was enqueued and the forest is unchanged");
   if (!b.margin_error.empty()) throw OhxError(b.margin_error);
   if (c.labels == nullptr) throw OhxError(w0 + ": labels is NULL");
   if (c.cut_ptr == nullptr || c.cut_values == nullptr) throw OhxError(w0 + ": the cuts are NULL");
@@ -2497,8 +2555,9 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   const bool deep = c.deep && max_depth > kGrowMaxDepth;
   BoostKind kind{deep ? BoostKind::Deep : sampled ? BoostKind::Sampled : weighted ? BoostKind::Weighted : BoostKind::Plain};
   // (the Plain kind has no pair path: its hessian is a row count)
-  kind.regularised = weighted && (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f);
-  kind.pairs = weighted && (b.grow_objective != kGrowObjSquared || b.grow_pairs_on || kind.regularised);
+  kind.constrained = weighted && !b.grow_mono.empty();
+  kind.regularised = weighted && !kind.constrained && (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f);
+  kind.pairs = weighted && (b.grow_objective != kGrowObjSquared || b.grow_pairs_on || kind.regularised || kind.constrained);
   if (kind.regularised)
     kind.reg_splits = grow_reg_splits(GrowRegHess{(double)wt.min_child_weight, b.grow_alpha, b.grow_max_delta_step});
   kind.metric = weighted ? b.grow_metric : kGrowMetricRmse;
@@ -2571,6 +2630,12 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     g.h_identity.ensure(F);
     for (uint32_t f = 0; f < F; ++f) g.h_identity.p[f] = (uint8_t)f;
   }
+  if (kind.constrained) {
+    room(g.d_mono_bounds, 2 * stride, 8, "the weight intervals of the monotone constraints");
+    room(g.d_mono_constraints, F, 1, "the monotone constraints of every feature");
+    g.h_mono_constraints.ensure(F);
+    for (uint32_t f = 0; f < F; ++f) g.h_mono_constraints.p[f] = f < b.grow_mono.size() ? b.grow_mono[f] : (int8_t)0;
+  }
   const size_t bag_words = (size_t)((n + 63) / 64);
   if (sampled) {
     if (k_s != kGrowSampleOne) room(g.d_bag, bag_words, 8, "the bag's bit plane");
@@ -2626,6 +2691,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (deep) HIP_CHECK(hipMemsetAsync(g.d_pos_deep.p, 0, n * sizeof(uint32_t), stream));
   if (sampled) HIP_CHECK(hipMemcpyAsync(g.d_features.p, g.h_features.p, R * n_sel, hipMemcpyHostToDevice, stream));
   if (kind.pairs) HIP_CHECK(hipMemcpyAsync(g.d_identity.p, g.h_identity.p, F, hipMemcpyHostToDevice, stream));
+  if (kind.constrained) HIP_CHECK(hipMemcpyAsync(g.d_mono_constraints.p, g.h_mono_constraints.p, F, hipMemcpyHostToDevice, stream));
   if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_labels.p, c.labels, n * sizeof(float), hipMemcpyHostToDevice, stream));
   initial_margin(d, g.d_pred.p, n);
   if (ev.present) HIP_CHECK(hipMemsetAsync(g.d_sums.p, 0, nsums * sizeof(unsigned long long), stream));
@@ -2679,6 +2745,9 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     kind.pair_args.hq = g.d_pair_hq.p;
     kind.pair_args.identity = g.d_identity.p;
   }
+  if (kind.constrained)
+    kind.reg_splits = grow_mono_splits(GrowMonoArgs{GrowRegHess{(double)wt.min_child_weight, b.grow_alpha, b.grow_max_delta_step},
+                                                    g.d_mono_bounds.p, g.d_mono_constraints.p});
   if (deep) {
     kind.deep_args.pos = g.d_pos_deep.p;
     kind.deep_args.node_stride = (uint32_t)stride;
@@ -3368,6 +3437,9 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
   } else if (n == "ohx_eval_metric") {
     if (v != "rmse" && v != "mae" && v != "pseudohuber") throw OhxError("ohx_eval_metric must be rmse, mae or pseudohuber");
     b->grow_metric = v == "mae" ? kGrowMetricMae : v == "pseudohuber" ? kGrowMetricPseudoHuber : kGrowMetricRmse;
+  } else if (n == "ohx_monotone_constraints") {
+    // boosting: c_f of every feature (docs/28_monotone_constraints.md); on the handle, in no file
+    b->grow_mono = parse_monotone_constraints(value);
   } else if (n == "ohx_grow_pairs") {
     // "on": squared error goes through the pair kernels too (the same bits); auto: only an objective that needs them
     if (v != "auto" && v != "on") throw OhxError("ohx_grow_pairs must be auto or on");

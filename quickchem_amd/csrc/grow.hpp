@@ -218,6 +218,73 @@ struct GrowRegHess {
   }
 };
 
+// ---- monotone constraints (design in docs/28_monotone_constraints.md) ----
+
+// "ohx_monotone_constraints": entry f is c_f in {-1, 0, +1}; at most one a feature
+constexpr uint32_t kGrowMaxConstraints = kGrowMaxFeatures;
+// The header's w(G, H; lo, hi): grow_reg_weight clamped into the node's interval.  -0.0 passes an interval that starts at
+// +0.0 (it is not below it).
+OHX_GROW_HD inline double grow_mono_weight(double Gd, double D, double alpha, double m, double lo, double hi) {
+  const double w = grow_reg_weight(Gd, D, alpha, m);
+  return w < lo ? lo : (w > hi ? hi : w);
+}
+// The header's gain_w(G, H, w): twice the reduction of the regularised objective at the weight w, the second form of
+// grow_reg_gain at a weight that is given
+OHX_GROW_HD inline double grow_gain_at(double Gd, double D, double alpha, double w) {
+  return -((2.0 * Gd) * w + (D * w) * w) - (2.0 * alpha) * __builtin_fabs(w);
+}
+// "constrained": GrowRegHess as one (node, feature) sees it - with the node's interval (lo, hi) of weights and the
+// feature's constraint c.  Its gain is gain_w at the clamped weight whatever max_delta_step is, and it admits a candidate
+// by the gradient sums of both children too (its own grow_best_split below): the children's weights must stand in the order c asks
+// for.  What GrowFixedHess admits, which nodes are looked at and sum_hess are unchanged.
+struct GrowMonoHess {
+  GrowRegHess reg;
+  double lo, hi;
+  int32_t c;
+  OHX_GROW_HD double hess(uint64_t H) const { return grow_hess(H); }
+  OHX_GROW_HD bool admits(uint64_t HL, uint64_t HR) const { return reg.admits(HL, HR); }
+  OHX_GROW_HD bool evaluates(uint64_t Hp) const { return reg.evaluates(Hp); }
+  OHX_GROW_HD float sum_hess(uint64_t H) const { return reg.sum_hess(H); }
+  OHX_GROW_HD double weight(int64_t G, uint64_t H, double lambda) const {
+    return grow_mono_weight((double)G * (1.0 / 16777216.0), grow_hess(H) + lambda, (double)reg.alpha, (double)reg.max_delta_step, lo,
+                            hi);
+  }
+  OHX_GROW_HD double gain(int64_t G, uint64_t H, double lambda) const {
+    return grow_gain_at((double)G * (1.0 / 16777216.0), grow_hess(H) + lambda, (double)reg.alpha, weight(G, H, lambda));
+  }
+  OHX_GROW_HD bool ordered(double wL, double wR) const { return c == 0 || (c > 0 ? wL <= wR : wL >= wR); }
+  OHX_GROW_HD void solve_leaf(int64_t G, uint64_t H, float eta, float lambda, float* leaf, float* w) const {
+    *w = (float)weight(G, H, (double)lambda);
+    *leaf = *w * eta;
+  }
+  // The intervals of the children of a split on this policy's feature, out = (lo_L, hi_L, lo_R, hi_R): the parent's cut
+  // at mid = (wL + wR) * 0.5 on the side c names, or the parent's own where c == 0
+  OHX_GROW_HD void children(int64_t GL, uint64_t HL, int64_t GR, uint64_t HR, double lambda, double out[4]) const {
+    out[0] = out[2] = lo;
+    out[1] = out[3] = hi;
+    if (c == 0) return;
+    const double mid = (weight(GL, HL, lambda) + weight(GR, HR, lambda)) * 0.5;
+    if (c > 0) out[1] = out[2] = mid;
+    else out[0] = out[3] = mid;
+  }
+};
+// What a split kernel of constrained boosting takes: the regularisation, the intervals of the tree at hand - two doubles
+// (lo, hi) a node id; the root's is (-inf, +inf) and is never read, so nothing is reset between trees: every other node
+// has its interval written when its parent splits - and the constraints of all num_feature features
+struct GrowMonoArgs {
+  GrowRegHess reg;
+  double* bounds;
+  const int8_t* constraints;
+  OHX_GROW_HD GrowMonoHess at(uint32_t node, uint32_t f) const {
+    GrowMonoHess h;
+    h.reg = reg;
+    h.lo = node == 0 ? -INFINITY : bounds[2 * (uint64_t)node];
+    h.hi = node == 0 ? INFINITY : bounds[2 * (uint64_t)node + 1];
+    h.c = constraints[f];
+    return h;
+  }
+};
+
 // The best candidate among cuts j0 .. j0 + n - 1 (those below ncut) of feature f.  G / H point at bin j0; GLb / HLb
 // are the sums over the bins below j0; Gm / Hm the missing bin; Gp / Hp the node.  Candidates are visited in ascending
 // (j, dl) and replaced only by a strictly better one.  The host calls it with j0 = 0, n = ncut; a lane of a split
@@ -241,6 +308,41 @@ OHX_GROW_HD inline GrowCand grow_best_split(const int64_t* G, const uint64_t* H,
       const uint64_t HR = Hp - c.HL;
       if (!hess.admits(c.HL, HR)) continue;
       c.loss_chg = (hess.gain(c.GL, c.HL, lambda) + hess.gain(GR, HR, lambda)) - parent;
+      c.key = grow_key(f, j, dl);
+      c.valid = 1;
+      if (grow_better(c, best)) best = c;
+    }
+  }
+  return best;
+}
+
+// The same scan for the constrained policy, written beside the one above so that no other instantiation moves: a
+// candidate is admitted by the hessian sums as ever and by the order of the children's weights, and its loss_chg is taken
+// at those weights.  The candidates, their order and the ties are the scan's above.
+template <>
+OHX_GROW_HD inline GrowCand grow_best_split<GrowMonoHess>(const int64_t* G, const uint64_t* H, uint32_t f, uint32_t j0, uint32_t n,
+                                                          uint32_t ncut, int64_t GLb, uint64_t HLb, int64_t Gm, uint64_t Hm,
+                                                          int64_t Gp, uint64_t Hp, double lambda, const GrowMonoHess& hess) {
+  GrowCand best;
+  const double alpha = (double)hess.reg.alpha;
+  const double parent = hess.gain(Gp, Hp, lambda);
+  for (uint32_t k = 0; k < n; ++k) {
+    const uint32_t j = j0 + k;
+    GLb += G[k];
+    HLb += H[k];
+    if (j >= ncut) continue;
+    for (uint32_t dl = 0; dl < 2; ++dl) {
+      GrowCand c;
+      c.GL = dl ? GLb + Gm : GLb;
+      c.HL = dl ? HLb + Hm : HLb;
+      const int64_t GR = Gp - c.GL;
+      const uint64_t HR = Hp - c.HL;
+      if (!hess.admits(c.HL, HR)) continue;
+      const double wL = hess.weight(c.GL, c.HL, lambda), wR = hess.weight(GR, HR, lambda);
+      if (!hess.ordered(wL, wR)) continue;
+      c.loss_chg = (grow_gain_at((double)c.GL * (1.0 / 16777216.0), grow_hess(c.HL) + lambda, alpha, wL) +
+                    grow_gain_at((double)GR * (1.0 / 16777216.0), grow_hess(HR) + lambda, alpha, wR)) -
+                   parent;
       c.key = grow_key(f, j, dl);
       c.valid = 1;
       if (grow_better(c, best)) best = c;
@@ -316,6 +418,29 @@ inline GrowCand grow_node_split(const int64_t* G, const uint64_t* H, uint32_t nu
     const GrowCand c = grow_best_split(g, h, f, 0, ncut, ncut, 0, 0, g[kGrowMissingBin], h[kGrowMissingBin], Gp, Hp,
                                        (double)lambda, hess);
     if (grow_better(c, best)) best = c;
+  }
+  return best;
+}
+// The same under monotone constraints: the node's interval (lo, hi), and feature f scanned with constraints[f] (num_feature
+// entries).  children: the intervals grow_write_split hands the children of the winner, (lo_L, hi_L, lo_R, hi_R).
+inline GrowCand grow_mono_node_split(const int64_t* G, const uint64_t* H, uint32_t num_feature, const uint64_t* cut_ptr, int64_t Gp,
+                                     uint64_t Hp, float lambda, const GrowRegHess& reg, double lo, double hi, const int8_t* constraints,
+                                     double children[4]) {
+  GrowCand best;
+  GrowMonoHess hess{reg, lo, hi, 0};
+  hess.children(0, 0, 0, 0, (double)lambda, children);
+  if (!hess.evaluates(Hp)) return best;
+  for (uint32_t f = 0; f < num_feature; ++f) {
+    const int64_t* g = G + (size_t)f * kGrowBins;
+    const uint64_t* h = H + (size_t)f * kGrowBins;
+    const uint32_t ncut = (uint32_t)(cut_ptr[f + 1] - cut_ptr[f]);
+    hess.c = constraints[f];
+    const GrowCand c = grow_best_split(g, h, f, 0, ncut, ncut, 0, 0, g[kGrowMissingBin], h[kGrowMissingBin], Gp, Hp, (double)lambda, hess);
+    if (grow_better(c, best)) best = c;
+  }
+  if (best.valid) {
+    hess.c = constraints[best.key >> 9];
+    hess.children(best.GL, best.HL, Gp - best.GL, Hp - best.HL, (double)lambda, children);
   }
   return best;
 }
@@ -707,6 +832,11 @@ int launch_grow_walk_sse_metric(const GrowEvalArgs& a, uint32_t metric, float sl
                                 void* stream);
 int launch_grow_walk_sse_deep_metric(const GrowEvalArgs& a, const GrowDeepArgs& d, uint32_t metric, float slope, uint32_t blocks,
                                      uint32_t round, uint32_t set, void* stream);
+// ---- monotone constraints on the GPU (grow_mono.hip; design in docs/28_monotone_constraints.md) ----
+
+// The constrained split launches of a call: grow_split_mono_kernel for levels 0 - 7 and grow_deep_split_mono_kernel below.
+// m.bounds holds two doubles a node of the call's node stride, m.constraints num_feature entries; both on the device.
+GrowPairSplits grow_mono_splits(const GrowMonoArgs& m);
 // Enqueues grow_deep_stage_kernel and grow_deep_walk_sse_kernel: eval_nodes from the records of tree `round`, then
 // launch_grow_walk_sse_weighted's walk and sums over the rows of `a`, its nodes read from HBM.  Returns a hipError_t.
 int launch_grow_walk_sse_deep(const GrowEvalArgs& a, const GrowDeepArgs& d, uint32_t blocks, uint32_t round, uint32_t set,

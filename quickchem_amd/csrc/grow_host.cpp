@@ -450,6 +450,45 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_reg_node_split(co
   return 0;
 }
 
+// ---- monotone constraints (docs/28_monotone_constraints.md) ----
+
+// the header's w(G, H; lo, hi) of GrowMonoHess, as a double
+extern "C" __attribute__((visibility("default"))) double ohx_grow_mono_weight(int64_t G, uint64_t H, float lambda, float alpha,
+                                                                               float max_delta_step, double lo, double hi) {
+  return GrowMonoHess{GrowRegHess{0.0, alpha, max_delta_step}, lo, hi, 0}.weight(G, H, (double)lambda);
+}
+
+// the header's gain_w(G, H, w), as a double
+extern "C" __attribute__((visibility("default"))) double ohx_grow_mono_gain(int64_t G, uint64_t H, float lambda, float alpha, double w) {
+  return grow_gain_at((double)G * (1.0 / 16777216.0), grow_hess(H) + (double)lambda, (double)alpha, w);
+}
+
+// out: (leaf, base_weight, sum_hess) of GrowMonoHess under the interval (lo, hi)
+extern "C" __attribute__((visibility("default"))) void ohx_grow_mono_leaf(int64_t G, uint64_t H, float eta, float lambda, float alpha,
+                                                                          float max_delta_step, double lo, double hi, float out[3]) {
+  const GrowMonoHess hess{GrowRegHess{0.0, alpha, max_delta_step}, lo, hi, 0};
+  hess.solve_leaf(G, H, eta, lambda, &out[0], &out[1]);
+  out[2] = hess.sum_hess(H);
+}
+
+// A node's best split over its histograms under its interval (lo, hi) and the constraints of the num_feature features
+// (grow_mono_node_split): out = (valid, key, GL, HL), *loss_chg, and children = (lo_L, hi_L, lo_R, hi_R).
+extern "C" __attribute__((visibility("default"))) int ohx_grow_mono_node_split(const int64_t* G, const uint64_t* H, uint32_t num_feature,
+                                                                               const uint64_t* cut_ptr, int64_t Gp, uint64_t Hp,
+                                                                               float lambda, float min_child_weight, float alpha,
+                                                                               float max_delta_step, double lo, double hi,
+                                                                               const int8_t* constraints, uint64_t out[4],
+                                                                               double* loss_chg, double children[4]) {
+  const GrowCand c = grow_mono_node_split(G, H, num_feature, cut_ptr, Gp, Hp, lambda,
+                                          GrowRegHess{(double)min_child_weight, alpha, max_delta_step}, lo, hi, constraints, children);
+  out[0] = c.valid;
+  out[1] = c.key;
+  out[2] = (uint64_t)c.GL;
+  out[3] = c.HL;
+  *loss_chg = c.loss_chg;
+  return 0;
+}
+
 // sq of every row by `metric` (0 rmse, 1 mae, 2 pseudohuber with `slope`); sound[r] = 0 where the residual is refused
 extern "C" __attribute__((visibility("default"))) int ohx_grow_metric_row(uint32_t metric, float slope, const float* pred, const float* y,
                                                                          uint64_t n, uint64_t* sq, uint8_t* sound) {

@@ -134,6 +134,16 @@ def _load():
         lib.ohx_grow_reg_leaf.restype = None
         lib.ohx_grow_reg_node_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint64, C.c_float,
                                                 C.c_float, C.c_float, C.c_float, C.c_void_p, C.POINTER(C.c_double)]
+        lib.ohx_grow_mono_weight.argtypes = [C.c_int64, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_double, C.c_double]
+        lib.ohx_grow_mono_weight.restype = C.c_double
+        lib.ohx_grow_mono_gain.argtypes = [C.c_int64, C.c_uint64, C.c_float, C.c_float, C.c_double]
+        lib.ohx_grow_mono_gain.restype = C.c_double
+        lib.ohx_grow_mono_leaf.argtypes = [C.c_int64, C.c_uint64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_double,
+                                           C.c_double, C.c_void_p]
+        lib.ohx_grow_mono_leaf.restype = None
+        lib.ohx_grow_mono_node_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint64, C.c_float,
+                                                 C.c_float, C.c_float, C.c_float, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
+                                                 C.POINTER(C.c_double), C.c_void_p]
         lib.ohx_grow_metric_row.argtypes = [C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.ohx_grow_weighted_mean.argtypes = [C.c_void_p, C.c_uint64]
         lib.ohx_grow_weighted_mean.restype = C.c_double
@@ -676,6 +686,45 @@ def grow_reg_node_split(Gh, Hh, cut_ptr, Gp: int, Hp: int, reg_lambda: float, mi
         return None
     key = int(out[1])
     return float(loss.value), key >> 9, (key >> 1) & 255, key & 1, int(out[2:3].view(np.int64)[0]), int(out[3])
+
+
+def ohx_grow_mono_weight(G: int, H: int, reg_lambda: float, reg_alpha: float, max_delta_step: float, lo: float, hi: float) -> float:
+    """csrc/grow.hpp GrowMonoHess.weight: the regularised weight of a node's fixed-point sums clamped into (lo, hi), a double."""
+    return float(_load().ohx_grow_mono_weight(int(G), int(H), reg_lambda, reg_alpha, max_delta_step, lo, hi))
+
+
+def ohx_grow_mono_gain(G: int, H: int, reg_lambda: float, reg_alpha: float, w: float) -> float:
+    """csrc/grow.hpp grow_gain_at: gain_w of a node's fixed-point sums at the weight w, a double."""
+    return float(_load().ohx_grow_mono_gain(int(G), int(H), reg_lambda, reg_alpha, w))
+
+
+def ohx_grow_mono_leaf(G: int, H: int, eta: float, reg_lambda: float, reg_alpha: float, max_delta_step: float, lo: float, hi: float):
+    """csrc/grow.hpp GrowMonoHess.solve_leaf under the interval (lo, hi) -> (leaf, base_weight, sum_hess) float32."""
+    out = np.zeros(3, dtype=np.float32)
+    _load().ohx_grow_mono_leaf(int(G), int(H), eta, reg_lambda, reg_alpha, max_delta_step, lo, hi, out.ctypes.data)
+    return out[0], out[1], out[2]
+
+
+def grow_mono_node_split(Gh, Hh, cut_ptr, Gp: int, Hp: int, reg_lambda: float, min_child_weight: float, reg_alpha: float,
+                         max_delta_step: float, lo: float, hi: float, constraints):
+    """csrc/grow.hpp grow_mono_node_split over the histograms Gh int64 / Hh uint64 [F][256], the node's interval (lo, hi) and
+    the F constraints -> None or (loss_chg, f, j, dl, GL, HL, (lo_L, hi_L, lo_R, hi_R))."""
+    Gh = np.ascontiguousarray(Gh, dtype=np.int64)
+    Hh = np.ascontiguousarray(Hh, dtype=np.uint64)
+    ptr = np.ascontiguousarray(cut_ptr, dtype=np.uint64)
+    con = np.ascontiguousarray(constraints, dtype=np.int8)
+    assert Gh.shape == Hh.shape and Gh.shape[1] == 256 and len(ptr) == Gh.shape[0] + 1 and con.shape == (Gh.shape[0],)
+    out = np.zeros(4, dtype=np.uint64)
+    children = np.zeros(4, dtype=np.float64)
+    loss = C.c_double()
+    _check(_load().ohx_grow_mono_node_split(Gh.ctypes.data, Hh.ctypes.data, Gh.shape[0], ptr.ctypes.data, int(Gp), int(Hp), reg_lambda,
+                                            min_child_weight, reg_alpha, max_delta_step, lo, hi, con.ctypes.data, out.ctypes.data,
+                                            C.byref(loss), children.ctypes.data))
+    if not int(out[0]):
+        return None
+    key = int(out[1])
+    return (float(loss.value), key >> 9, (key >> 1) & 255, key & 1, int(out[2:3].view(np.int64)[0]), int(out[3]),
+            tuple(float(v) for v in children))
 
 
 def ohx_grow_metric_row(metric: str, slope: float, pred, y):

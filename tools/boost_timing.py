@@ -41,7 +41,12 @@ features a tree sees.  Without the two fractions `--deep` does what it did.
 "ohx_grow_pairs" on every booster that is timed (docs/26_objectives.md): the calls with row weights, `--weights`,
 `--subsample` / `--colsample` or `--deep`, then go through the pair kernels.  Three runs that differ in these alone compare
 the inline path, squared error on pairs and pseudo-Huber.  The refit at the end is a squared-error step and is left out
-under pseudohuber."""
+under pseudohuber.
+
+`--monotone "(1,0,-1)"` sets "ohx_monotone_constraints" on every booster that is timed (docs/28_monotone_constraints.md): the
+calls with row weights then take the constrained split kernels over the pair path.  Against a run with `--pairs on
+--max-delta-step 0.5` - the same pair and histogram kernels and the same gain form - the difference is the split kernels
+and the trees they choose; the node counts stand beside the times."""
 from __future__ import annotations
 
 import argparse
@@ -154,6 +159,7 @@ def main():
     ap.add_argument("--reg-alpha", type=float, default=0.0, help="ohx_reg_alpha of the timed boosters")
     ap.add_argument("--max-delta-step", type=float, default=0.0, help="ohx_max_delta_step of the timed boosters")
     ap.add_argument("--eval-metric", choices=("rmse", "mae", "pseudohuber"), default="rmse", help="ohx_eval_metric of the timed boosters")
+    ap.add_argument("--monotone", default=None, help="ohx_monotone_constraints of the timed boosters, as the parameter is written: \"(1,0,-1)\"")
     args = ap.parse_args()
     sampled = args.subsample is not None or args.colsample is not None
     if sampled:
@@ -166,8 +172,8 @@ def main():
     if args.weights != "none" and args.holdout:
         ap.error("--weights times the call without a held-out set: leave --holdout out")
     regularised = args.reg_alpha != 0.0 or args.max_delta_step != 0.0 or args.eval_metric != "rmse"
-    if (args.objective != "squarederror" or args.pairs != "auto" or regularised) and (args.holdout or not (sampled or args.deep or args.weights != "none")):
-        ap.error("--objective / --pairs / --reg-alpha / --max-delta-step / --eval-metric time a call with row weights: give --weights, --subsample / --colsample or --deep, and no --holdout")
+    if (args.objective != "squarederror" or args.pairs != "auto" or regularised or args.monotone is not None) and (args.holdout or not (sampled or args.deep or args.weights != "none")):
+        ap.error("--objective / --pairs / --reg-alpha / --max-delta-step / --eval-metric / --monotone time a call with row weights: give --weights, --subsample / --colsample or --deep, and no --holdout")
     assert torch.cuda.is_available(), "boost_timing needs the MI355X"
     torch.cuda.set_device(0)
     model = synth.make_model()
@@ -257,6 +263,7 @@ def main():
     res["weights"] = args.weights
     res["objective"] = {"ohx_objective": args.objective, "ohx_huber_slope": args.huber_slope, "ohx_grow_pairs": args.pairs}
     res["regularisation"] = {"ohx_reg_alpha": args.reg_alpha, "ohx_max_delta_step": args.max_delta_step, "ohx_eval_metric": args.eval_metric}
+    res["monotone_constraints"] = args.monotone
     res["pair_planes"] = synth.grow_pairs_plan(n, F, ncuts, args.max_depth, cus)
 
     def timed_booster():
@@ -268,6 +275,8 @@ def main():
             b.set_param("ohx_reg_alpha", repr(args.reg_alpha))
             b.set_param("ohx_max_delta_step", repr(args.max_delta_step))
             b.set_param("ohx_eval_metric", args.eval_metric)
+        if args.monotone is not None:
+            b.set_param("ohx_monotone_constraints", args.monotone)
         return b
 
     last = {}                              # what the weighted call returned last
@@ -327,7 +336,7 @@ def main():
         per_round = (res[f"rounds_{args.rounds}"]["median_s"] - res["rounds_1"]["median_s"]) / (args.rounds - 1)
         res["per_round_s"] = per_round
         res["one_off_s"] = res["rounds_1"]["median_s"] - per_round
-    if not args.skip_rmse and not args.holdout and not args.deep_only and args.objective == "squarederror" and not regularised:
+    if not args.skip_rmse and not args.holdout and not args.deep_only and args.objective == "squarederror" and not regularised and args.monotone is None:
         b = capi.Booster(model_buffer=model.image)
         res["rmse_before"] = rmse(b)
         b.refit_leaves_device(d, labels.data_ptr(), n, eta=1.0, reg_lambda=1.0, stream=stream)
