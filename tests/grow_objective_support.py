@@ -167,9 +167,19 @@ def inputs(n, seed, nfeat=3, bins=64, held_out=0):
     return x, y, w, G.quantile_cuts(x, float("nan"), bins), ev
 
 
+def kind_kw(kind, deep_depth=11):
+    """The hyper-parameters of a kind ("weighted", "sampled", "deep", "deep_sampled"), as the Python binding names them: the one
+    point at which the GPU tests of the objectives, the regularisation and the constraints grow their trees
+    (tests/grow_audit_support.py moves away from it)."""
+    kw = dict(eta=0.125, reg_lambda=1.0, min_child_weight=0.0, max_depth=deep_depth if "deep" in kind else 6)
+    if "sampled" in kind:
+        kw.update(subsample=0.5, colsample_bytree=0.5, seed=11)
+    return kw
+
+
 @functools.lru_cache(maxsize=None)
 def restated(objective, slope, n, seed, max_depth, bins=64, nfeat=3, rounds=2, held_out=0, patience=0, subsample=1.0,
-             colsample=1.0, draw_seed=0, lam=1.0, mcw=0.0, weighted=True):
+             colsample=1.0, draw_seed=0, lam=1.0, mcw=0.0, weighted=True, eta=0.125, gamma=0.0):
     """One restated case on the common inputs, computed once and shared (the result is not to be changed).
     -> (x, y, w, cuts, ev, the dict of boost)."""
     x, y, w, cuts, ev = inputs(n, seed, nfeat, bins, held_out)
@@ -178,6 +188,6 @@ def restated(objective, slope, n, seed, max_depth, bins=64, nfeat=3, rounds=2, h
         ev = (ev[0], ev[1], ev[2], None) if ev is not None else None
     want = boost(objective, slope, np.full(n, BASE, F32), x, float("nan"), y, w, cuts, nfeat, eval_set=ev,
                  eval_pred=np.full(held_out, BASE, F32) if held_out else None, rounds=rounds, patience=patience,
-                 max_depth=max_depth, eta=0.125, lam=lam, gamma=0.0, min_child_weight=mcw, subsample=subsample,
+                 max_depth=max_depth, eta=eta, lam=lam, gamma=gamma, min_child_weight=mcw, subsample=subsample,
                  colsample_bytree=colsample, seed=draw_seed)
     return x, y, w, cuts, ev, want

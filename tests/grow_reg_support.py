@@ -211,7 +211,7 @@ def boost(objective, slope, alpha, m, metric, pred, x, missing, y, w, cuts, num_
 
 @functools.lru_cache(maxsize=None)
 def restated(objective, slope, alpha, m, metric, n, seed, max_depth, bins=64, nfeat=3, rounds=2, held_out=0, patience=0,
-             subsample=1.0, colsample=1.0, draw_seed=0, lam=1.0, mcw=0.0, weighted=True, eta=0.125):
+             subsample=1.0, colsample=1.0, draw_seed=0, lam=1.0, mcw=0.0, weighted=True, eta=0.125, gamma=0.0):
     """One restated case on grow_objective_support.inputs, computed once and shared (the result is not to be changed).
     -> (x, y, w, cuts, ev, the dict of boost)."""
     x, y, w, cuts, ev = O.inputs(n, seed, nfeat, bins, held_out)
@@ -220,6 +220,6 @@ def restated(objective, slope, alpha, m, metric, n, seed, max_depth, bins=64, nf
         ev = (ev[0], ev[1], ev[2], None) if ev is not None else None
     want = boost(objective, slope, alpha, m, metric, np.full(n, BASE, F32), x, float("nan"), y, w, cuts, nfeat, eval_set=ev,
                  eval_pred=np.full(held_out, BASE, F32) if held_out else None, rounds=rounds, patience=patience,
-                 max_depth=max_depth, eta=eta, lam=lam, gamma=0.0, min_child_weight=mcw, subsample=subsample,
+                 max_depth=max_depth, eta=eta, lam=lam, gamma=gamma, min_child_weight=mcw, subsample=subsample,
                  colsample_bytree=colsample, seed=draw_seed)
     return x, y, w, cuts, ev, want

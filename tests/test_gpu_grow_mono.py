@@ -6,7 +6,7 @@ The expected values are the restatement's (tests/grow_mono_support.py, written f
 states an equality, another call on a twin booster.  The model of every case has no tree, so the margin a restatement
 starts from is the model's base.  What a case is meant to reach - a tree that the constraints change, a level beyond 7,
 more open nodes than a batch holds, a tree whose list lacks a constrained feature - is asserted from the restatement before
-the GPU is asked."""
+the GPU is asked.  gamma, lambda, min_child_weight and eta away from kind_kw's values: tests/test_gpu_grow_hyper.py."""
 import ctypes as C
 
 import numpy as np

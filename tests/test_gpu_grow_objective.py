@@ -6,7 +6,8 @@ The expected values are the restatement's (tests/grow_objective_support.py, writ
 header states an equality, another call on a twin booster: squared error through the pair kernels against the inline
 kernels.  The model of every case has no tree, so the margin a restatement starts from is the model's base.  What a case
 is meant to reach - a level beyond 7, more open nodes than a batch holds, hessians that change from round to round - is
-asserted from the restatement before the GPU is asked."""
+asserted from the restatement before the GPU is asked.  gamma, lambda, min_child_weight and eta away from kind_kw's values:
+tests/test_gpu_grow_hyper.py."""
 import ctypes as C
 
 import numpy as np
@@ -16,6 +17,7 @@ from quickchem_amd import capi, synth
 from tests import grow_deep_support as D
 from tests import grow_objective_support as O
 from tests import grow_support as G
+from tests.grow_objective_support import kind_kw
 from tests.test_gpu_grow import held, same_new_trees
 from tests.test_gpu_grow_eval import same_result, saved
 
@@ -35,14 +37,6 @@ def torch_cuda():
     assert torch.cuda.is_available(), "these tests need the MI355X"
     torch.cuda.set_device(0)
     return torch
-
-
-def kind_kw(kind, deep_depth=11):
-    """The hyper-parameters of a kind, as the Python binding names them."""
-    kw = dict(eta=0.125, reg_lambda=1.0, min_child_weight=0.0, max_depth=deep_depth if "deep" in kind else 6)
-    if "sampled" in kind:
-        kw.update(subsample=0.5, colsample_bytree=0.5, seed=11)
-    return kw
 
 
 def restated(kind, objective, slope, n=N, seed=26, rounds=2, held_out=HELD, patience=0, deep_depth=11, **more):

@@ -5,7 +5,8 @@ as integers or bit for bit, both metric arrays with ==, and models byte for byte
 The expected values are the restatement's (tests/grow_reg_support.py, written from the header) and, where the header
 states an equality, another call on a twin booster.  The model of every case has no tree, so the margin a restatement
 starts from is the model's base.  What a case is meant to reach - weights that are clipped, weights that are zeroed, a stop
-rule that the metric moves - is asserted from the restatement before the GPU is asked."""
+rule that the metric moves - is asserted from the restatement before the GPU is asked.  gamma, lambda, min_child_weight and
+eta away from kind_kw's values: tests/test_gpu_grow_hyper.py."""
 import ctypes as C
 
 import numpy as np
