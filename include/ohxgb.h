@@ -247,6 +247,17 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *                     OHXBoosterRefitLeaves[Device] (a refit would undo the intervals) return -1 before anything is
  *                     enqueued; the message names OHXBoosterBoostTreesWeighted.  In every refusal the forest and the
  *                     outputs are untouched
+ *   "ohx_colsample_bylevel", "ohx_colsample_bynode" boosting: the fraction of a tree's features that a level of the tree
+ *                     sees, and the fraction of a level's features that one node may split on.  Each is a decimal float,
+ *                     finite, with 0 < v <= 1; the default is 1.  Anything else ("", not a number, 0, a negative, > 1,
+ *                     nan, inf) returns -1 and the message names the parameter.  Both are kept on the handle and written
+ *                     into no model file; the names without the prefix are xgboost's and stay ignored.  They act on
+ *                     OHXBoosterBoostTreesSampled[Device] and OHXBoosterBoostTreesDeepSampled[Device], the calls that
+ *                     carry a seed, as defined with the Sampled call below (docs/29_colsample_level_node.md).  While
+ *                     either is not 1, OHXBoosterBoostTrees[Device], ...Eval[Device], ...Weighted[Device] and
+ *                     ...Deep[Device] return -1 before anything is enqueued; the message names
+ *                     OHXBoosterBoostTreesSampled, and the forest and every output are untouched.
+ *                     OHXBoosterRefitLeaves chooses no split and is unaffected
  * None of them changes a prediction.
  * xgboost's own parameter names ("nthread", "predictor", ...) are accepted and
  * ignored. */
@@ -851,6 +862,39 @@ int OHXBoosterBoostTreesWeightedDevice(BoosterHandle handle, DMatrixHandle dmat,
  * OHXDMatrixSetGrid change nothing.  Integer adds only.
  * Consequence.  With subsample = colsample_bytree = 1.0f and any seed, the forest, XGBoosterSaveModel's bytes in all
  * three formats and both RMSE arrays equal those of OHXBoosterBoostTreesWeighted.
+ * Column sampling by level and by node ("ohx_colsample_bylevel", "ohx_colsample_bynode"; docs/29_colsample_level_node.md).
+ * What is stated above is both at 1.  The nesting tree -> level -> node and the max(1, floor(...)) at each stage are
+ * ColumnSampler's of xgboost 1.6.0; the draws are this library's own.  mix, gamma64, K_col(i) and i = T0 + t - 1 are those
+ * above, and S_tree is the tree's n_sel selected features, drawn exactly as above.
+ *   Level.  d is the depth of the nodes being split, the root's being 0.
+ *     n_lvl = max(1, (int) floor((double)colsample_bylevel * n_sel)).  K_lvl(i, d) = mix(K_col(i) + gamma64 * (d + 1)).
+ *     Feature f of S_tree has key mix(K_lvl(i, d) + f); S_lvl(d) is the n_lvl features of S_tree smallest by (key, f), kept
+ *     in ascending f.  n_lvl == n_sel draws nothing: S_lvl(d) = S_tree.
+ *   Node.  p is the node's id in the tree in allocation order, the root being 0.
+ *     n_node = max(1, (int) floor((double)colsample_bynode * n_lvl)).  K_node(i, p) = mix(K_col(i) + gamma64 * (32 + p)).
+ *     Feature f of S_lvl(d) has key mix(K_node(i, p) + f); S_node(p) is the n_node features of S_lvl(d) smallest by
+ *     (key, f).  n_node == n_lvl draws nothing: S_node(p) = S_lvl(d).  d + 1 <= 18 < 32, so level keys and node keys
+ *     never share an input.
+ *   The tree.  The candidates of node p are the (f, j, dl) with f in S_node(p).  Everything else is as stated above, word
+ *     for word: the bag; the integer histograms; the total order (f, j, dl) with the original f, and the ties; which
+ *     splits are admitted and which nodes are evaluated; the node's sums, sum_hess and base_weight; the gain form of
+ *     whichever of the objective, the regularisation and the monotone constraints is active; the node numbering and the
+ *     records; the refusal of a root with H == 0; the margins and the metrics over every row; the stop rule, all or
+ *     nothing, both forms, not capturable.
+ *   The result depends on the seed, the tree index, the level, the node id and the feature; not on the launch shape, the
+ *   batch size of the deep levels, the form, the stream or OHXDMatrixSetGrid.  The two fractions compose with both
+ *   objectives, ohx_reg_alpha, ohx_max_delta_step, ohx_monotone_constraints, all three metrics, weights, a held-out set
+ *   and patience, and with any subsample and colsample_bytree, 1.0 included.
+ *   C1.  With n_lvl == n_sel and n_node == n_lvl the call takes the path it takes without the two parameters, whatever
+ *     their values or the seed - in particular with both at 1: the forest, XGBoosterSaveModel's bytes in all three
+ *     formats and both metric arrays equal those of the same call at the defaults, and nothing of the kernels of column
+ *     sampling by level and node is launched, set or loaded.
+ *   C2.  Every split node p of a new tree has its feature in S_node(p); all split nodes of one level have their features
+ *     in that level's S_lvl(d).  With n_lvl == 1 every split of a level is on the same feature.
+ *   C3.  OHXBoosterBoostTreesDeepSampled at max_depth <= 8 equals OHXBoosterBoostTreesSampled with the same parameters,
+ *     in bytes and arrays.
+ *   The level lists of every round, rounds x max_depth x n_lvl bytes, are part of the grow state, made before anything
+ *   is enqueued; where they cannot be allocated the call returns -1 and the message names the bytes.
  * Refused, with the forest and every output untouched: everything OHXBoosterBoostTreesWeighted refuses, in the same
  * order; after min_child_weight and before the cuts, subsample not finite, <= 0, > 1, or with k_s == 0, then
  * colsample_bytree not finite, <= 0, or > 1; and, on the device, a round whose bag holds no weight (root H == 0), also

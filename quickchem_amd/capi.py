@@ -568,13 +568,19 @@ class Booster:
         return self._eval_result(train, held, run, best, n, ed is not None)
 
     def _set_objective(self, objective, huber_slope, reg_alpha=None, max_delta_step=None, eval_metric=None,
-                       monotone_constraints=None) -> None:
+                       monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> None:
         """objective= and huber_slope= of the boost_trees_* methods: "squarederror" or "pseudohuber" and its slope, set on
         the handle by set_param("ohx_objective") and set_param("ohx_huber_slope") and kept for later calls (they go into
         no model file).  reg_alpha=, max_delta_step= and eval_metric= ("rmse", "mae" or "pseudohuber": what the two
         metric arrays hold and the stop rule compares) likewise, by "ohx_reg_alpha", "ohx_max_delta_step" and
         "ohx_eval_metric".  monotone_constraints= is a sequence of ints in {-1, 0, 1}, one a feature from feature 0 on, or
-        the string itself ("(1,0,-1)"), set by "ohx_monotone_constraints"; () is none.  None leaves the handle's setting."""
+        the string itself ("(1,0,-1)"), set by "ohx_monotone_constraints"; () is none.  colsample_bylevel= and
+        colsample_bynode= (the calls that carry a seed take them) are fractions in (0, 1], set by "ohx_colsample_bylevel" and
+        "ohx_colsample_bynode".  None leaves the handle's setting."""
+        if colsample_bylevel is not None:
+            self.set_param("ohx_colsample_bylevel", repr(float(colsample_bylevel)))
+        if colsample_bynode is not None:
+            self.set_param("ohx_colsample_bynode", repr(float(colsample_bynode)))
         if monotone_constraints is not None:
             if not isinstance(monotone_constraints, str):
                 monotone_constraints = "(" + ",".join(str(int(c)) for c in monotone_constraints) + ")"
@@ -687,11 +693,13 @@ class Booster:
                             min_child_weight: float = 1.0, subsample: float = 1.0, colsample_bytree: float = 1.0,
                             seed: int = 0, patience: int = 0,
                             *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
         """OHXBoosterBoostTreesSampled: boost_trees_weighted where every tree is fitted to a fresh bag of the rows
         (a fraction `subsample`) and may split on a fresh set of the features (a fraction `colsample_bytree`), both
-        drawn on the GPU from `seed` (a uint64) and the tree's index in the forest.  -> the dict of boost_trees_eval."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        drawn on the GPU from `seed` (a uint64) and the tree's index in the forest.  colsample_bylevel= and
+        colsample_bynode= narrow the tree's features again for every level and every node.  -> the dict of boost_trees_eval."""
+        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+                            colsample_bylevel, colsample_bynode)
         return self._boost_sampled("OHXBoosterBoostTreesSampled", dmat, labels, cuts, weights, eval_set, rounds, max_depth, eta,
                                    reg_lambda, gamma, min_child_weight, subsample, colsample_bytree, seed, patience)
 
@@ -728,9 +736,10 @@ class Booster:
                                    subsample: float = 1.0, colsample_bytree: float = 1.0, seed: int = 0,
                                    patience: int = 0, stream: int = 0,
                                    *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
         """The same with labels and weights in device memory, as boost_trees_weighted_device takes them."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+                            colsample_bylevel, colsample_bynode)
         return self._boost_sampled_device("OHXBoosterBoostTreesSampledDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
                                           eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, subsample,
                                           colsample_bytree, seed, patience, stream)
@@ -755,12 +764,13 @@ class Booster:
                                  min_child_weight: float = 1.0, subsample: float = 1.0, colsample_bytree: float = 1.0,
                                  seed: int = 0, patience: int = 0,
                                  *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
         """OHXBoosterBoostTreesDeepSampled: boost_trees_sampled with max_depth up to 18.  From level 8 on a level's
         histograms are kept in HBM for a batch of nodes at a time, over the bag's rows and the tree's features only, and
         the call waits once a level for the ids of the open nodes.  Up to depth 8 it is boost_trees_sampled itself; with
         both fractions 1 it is boost_trees_deep.  -> the dict of boost_trees_eval."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+                            colsample_bylevel, colsample_bynode)
         return self._boost_sampled("OHXBoosterBoostTreesDeepSampled", dmat, labels, cuts, weights, eval_set, rounds, max_depth,
                                    eta, reg_lambda, gamma, min_child_weight, subsample, colsample_bytree, seed, patience)
 
@@ -770,10 +780,11 @@ class Booster:
                                         subsample: float = 1.0, colsample_bytree: float = 1.0, seed: int = 0,
                                         patience: int = 0, stream: int = 0,
                                         *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
         """The same with labels and weights in device memory, as boost_trees_weighted_device takes them.  With
         max_depth > 8 the call waits for `stream` once a level from level 7 on."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+                            colsample_bylevel, colsample_bynode)
         return self._boost_sampled_device("OHXBoosterBoostTreesDeepSampledDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
                                           eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, subsample,
                                           colsample_bytree, seed, patience, stream)

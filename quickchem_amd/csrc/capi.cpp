@@ -694,7 +694,12 @@ struct GrowState {
   DevBuf<double> d_mono_bounds;
   DevBuf<int8_t> d_mono_constraints;
   PinnedBuf<int8_t> h_mono_constraints;
+  // column sampling by level and by node (grow_colsample.hip): the lists of every round and level, [rounds][max_depth][n_lvl];
+  // allocated only where a fraction takes a feature away
+  DevBuf<uint8_t> d_level_lists;
+  PinnedBuf<uint8_t> h_level_lists;
   void release_device() {
+    d_level_lists.release();
     d_mono_bounds.release();
     d_mono_constraints.release();
     d_pair_q.release();
@@ -871,6 +876,9 @@ struct BoosterObj {
   // (docs/28_monotone_constraints.md): "ohx_monotone_constraints", entry f is c_f; empty is the default, and a list of
   // zeros is kept as the empty list it stands for
   std::vector<int8_t> grow_mono;
+  // (docs/29_colsample_level_node.md): "ohx_colsample_bylevel" and "ohx_colsample_bynode", the fraction of a tree's features a
+  // level sees and of a level's a node does; 1 is the default
+  float grow_bylevel = 1.0f, grow_bynode = 1.0f;
   std::unique_ptr<RefitState> refit;
   std::unique_ptr<GrowState> grow;
 };
@@ -2399,11 +2407,14 @@ struct BoostKind {
   // constrained (ohx_monotone_constraints holds an entry that is not 0; then `pairs` holds too, and `regularised` is not
   // asked): the pair path with grow_mono.hip's split launches, which carry alpha and max_delta_step themselves.  Without
   // it nothing of grow_mono.hip is touched.
-  bool regularised = false, constrained = false;
+  // column-sampled (ohx_colsample_bylevel or ohx_colsample_bynode takes a feature away from a level or a node; then
+  // `pairs` holds too): the pair path over the level's list with grow_colsample.hip's split launches, under the policy
+  // `regularised` / `constrained` name or the fixed-point one.  Without it nothing of grow_colsample.hip is touched.
+  bool regularised = false, constrained = false, colsampled = false;
   GrowPairSplits reg_splits;
   uint32_t metric = kGrowMetricRmse;
   float slope = 1.0f;
-  const GrowPairSplits* splits() const { return constrained || regularised ? &reg_splits : nullptr; }
+  const GrowPairSplits* splits() const { return constrained || regularised || colsampled ? &reg_splits : nullptr; }
   bool wide() const { return which != Plain; }
   // The call's one plan, asked for once: the level loop over `cols` histogram columns - F itself, or the n_sel features
   // a tree of a sampled call sees (compact histograms and candidates) - the streaming kernels, which do not depend on
@@ -2490,6 +2501,10 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (!weighted && !b.grow_mono.empty())
     throw OhxError(w0 + " keeps row counts, and its split kernels no weight intervals: with ohx_monotone_constraints active call "
                    "OHXBoosterBoostTreesWeighted (weights may be NULL) or a later form; nothing was enqueued and the forest is unchanged");
+  if (!c.sampling.present && (b.grow_bylevel != 1.0f || b.grow_bynode != 1.0f))
+    throw OhxError(w0 + " draws nothing and carries no seed: with ohx_colsample_bylevel or ohx_colsample_bynode below 1 call "
+                   "OHXBoosterBoostTreesSampled or OHXBoosterBoostTreesDeepSampled, or set both to 1; nothing was enqueued and the "
+                   "forest is unchanged");
   if (b.grow_mono.size() > (size_t)b.forest.num_feature)
     throw OhxError(w0 + ": ohx_monotone_constraints has " + std::to_string(b.grow_mono.size()) + " entries but the booster " +
                    std::to_string(b.forest.num_feature) + " features; nothing was enqueued and the forest is unchanged");
@@ -2515,6 +2530,13 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
       throw OhxError(w0 + ": subsample must be finite, > 0 and <= 1, and rint(subsample * 2^24) must be >= 1");
     n_sel = grow_num_selected(F, c.sampling.colsample_bytree);
     if (n_sel == 0) throw OhxError(w0 + ": colsample_bytree must be finite, > 0 and <= 1");
+  }
+  // the features a level sees of a tree's, and a node of a level's (the handle's fractions are sound: XGBoosterSetParam)
+  uint32_t n_lvl = n_sel, n_node = n_sel;
+  if (c.sampling.present) {
+    n_lvl = grow_num_selected(n_sel, b.grow_bylevel);
+    n_node = grow_num_selected(n_lvl, b.grow_bynode);
+    if (n_lvl == 0 || n_node == 0) throw OhxError(w0 + ": ohx_colsample_bylevel and ohx_colsample_bynode must be finite, > 0 and <= 1");
   }
   grow_check_cuts(c.cut_ptr, c.cut_values, F, what);
   if (ev.present) {
@@ -2550,15 +2572,18 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
                      std::to_string(d.device));
   }
   // the kind of the call, once: everything below that differs by kernel or by sum layout asks `kind`
-  const bool sampled = k_s != kGrowSampleOne || n_sel != F;
+  // (a call whose fractions take no feature away is the call it is today, whatever the fractions)
+  const bool colsampled = n_lvl != n_sel || n_node != n_lvl;
+  const bool sampled = k_s != kGrowSampleOne || n_sel != F || colsampled;
   // (the Deep entry points at max_depth <= 8 take the weighted or the sampled kind as it is)
   const bool deep = c.deep && max_depth > kGrowMaxDepth;
   BoostKind kind{deep ? BoostKind::Deep : sampled ? BoostKind::Sampled : weighted ? BoostKind::Weighted : BoostKind::Plain};
   // (the Plain kind has no pair path: its hessian is a row count)
   kind.constrained = weighted && !b.grow_mono.empty();
   kind.regularised = weighted && !kind.constrained && (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f);
-  kind.pairs = weighted && (b.grow_objective != kGrowObjSquared || b.grow_pairs_on || kind.regularised || kind.constrained);
-  if (kind.regularised)
+  kind.colsampled = colsampled;
+  kind.pairs = weighted && (b.grow_objective != kGrowObjSquared || b.grow_pairs_on || kind.regularised || kind.constrained || colsampled);
+  if (kind.regularised && !colsampled)
     kind.reg_splits = grow_reg_splits(GrowRegHess{(double)wt.min_child_weight, b.grow_alpha, b.grow_max_delta_step});
   kind.metric = weighted ? b.grow_metric : kGrowMetricRmse;
   kind.slope = b.grow_slope;
@@ -2587,8 +2612,8 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   }
   const uint64_t n = d.nrow, ncuts = c.cut_ptr[F];
   const size_t R = (size_t)c.rounds;
-  // (n_sel == F where nothing is sampled)
-  const GrowPlan plan = kind.plan(n, F, n_sel, ncuts, max_depth, dev.num_cus);
+  // (n_sel == F where nothing is sampled, and n_lvl == n_sel where no level draws)
+  const GrowPlan plan = kind.plan(n, F, n_lvl, ncuts, max_depth, dev.num_cus);
   const GrowPlan& levels = plan;
   const uint64_t tree0 = b.forest.trees.size();   // T0: tree t of the call is tree tree0 + t - 1 of the draws
   auto room = [&](auto& buf, size_t count, size_t elem, const char* name) {
@@ -2646,6 +2671,18 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
       if (grow_pick_features(c.sampling.seed, tree0 + r, F, c.sampling.colsample_bytree, g.h_features.p + r * n_sel) != n_sel)
         throw OhxError(w0 + ": the selected features of round " + std::to_string(r + 1) + " are not " + std::to_string(n_sel));
   }
+  const size_t level_bytes = R * (size_t)max_depth * n_lvl;
+  if (colsampled) {
+    room(g.d_level_lists, level_bytes, 1, "the level lists of every round");
+    g.h_level_lists.ensure(level_bytes);
+    // every round's and level's list before anything is enqueued
+    for (size_t r = 0; r < R; ++r)
+      for (uint32_t lv = 0; lv < (uint32_t)max_depth; ++lv)
+        if (grow_pick_level_features(c.sampling.seed, tree0 + r, lv, g.h_features.p + r * n_sel, n_sel, b.grow_bylevel,
+                                     g.h_level_lists.p + (r * (size_t)max_depth + lv) * n_lvl) != n_lvl)
+          throw OhxError(w0 + ": the features of level " + std::to_string(lv) + " of round " + std::to_string(r + 1) + " are not " +
+                         std::to_string(n_lvl));
+  }
   if (ev.present) {
     if (e != nullptr) {
       eplan = plan_grow(ne, F, ncuts, std::min(max_depth, kGrowMaxDepth), dev.num_cus);
@@ -2690,6 +2727,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   HIP_CHECK(hipMemsetAsync(g.d_pos.p, 0, n * sizeof(uint16_t), stream));
   if (deep) HIP_CHECK(hipMemsetAsync(g.d_pos_deep.p, 0, n * sizeof(uint32_t), stream));
   if (sampled) HIP_CHECK(hipMemcpyAsync(g.d_features.p, g.h_features.p, R * n_sel, hipMemcpyHostToDevice, stream));
+  if (colsampled) HIP_CHECK(hipMemcpyAsync(g.d_level_lists.p, g.h_level_lists.p, level_bytes, hipMemcpyHostToDevice, stream));
   if (kind.pairs) HIP_CHECK(hipMemcpyAsync(g.d_identity.p, g.h_identity.p, F, hipMemcpyHostToDevice, stream));
   if (kind.constrained) HIP_CHECK(hipMemcpyAsync(g.d_mono_constraints.p, g.h_mono_constraints.p, F, hipMemcpyHostToDevice, stream));
   if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_labels.p, c.labels, n * sizeof(float), hipMemcpyHostToDevice, stream));
@@ -2745,9 +2783,22 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     kind.pair_args.hq = g.d_pair_hq.p;
     kind.pair_args.identity = g.d_identity.p;
   }
-  if (kind.constrained)
+  if (colsampled) {
+    GrowColsampleArgs cs;
+    cs.lists = g.d_level_lists.p;
+    cs.depth = (uint32_t)max_depth;
+    cs.n_lvl = n_lvl;
+    cs.n_node = n_node;
+    cs.seed = c.sampling.seed;
+    cs.tree0 = tree0;
+    const GrowRegHess reg{(double)wt.min_child_weight, b.grow_alpha, b.grow_max_delta_step};
+    kind.reg_splits = kind.constrained    ? grow_colsample_splits(cs, GrowMonoArgs{reg, g.d_mono_bounds.p, g.d_mono_constraints.p})
+                      : kind.regularised ? grow_colsample_splits(cs, reg)
+                                         : grow_colsample_splits(cs, GrowFixedHess{(double)wt.min_child_weight});
+  } else if (kind.constrained) {
     kind.reg_splits = grow_mono_splits(GrowMonoArgs{GrowRegHess{(double)wt.min_child_weight, b.grow_alpha, b.grow_max_delta_step},
                                                     g.d_mono_bounds.p, g.d_mono_constraints.p});
+  }
   if (deep) {
     kind.deep_args.pos = g.d_pos_deep.p;
     kind.deep_args.node_stride = (uint32_t)stride;
@@ -3440,6 +3491,14 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
   } else if (n == "ohx_monotone_constraints") {
     // boosting: c_f of every feature (docs/28_monotone_constraints.md); on the handle, in no file
     b->grow_mono = parse_monotone_constraints(value);
+  } else if (n == "ohx_colsample_bylevel" || n == "ohx_colsample_bynode") {
+    // boosting: the fraction of a tree's features a level sees, and of a level's a node does
+    // (docs/29_colsample_level_node.md); on the handle, in no file
+    char* end = nullptr;
+    const float k = strtof(value, &end);
+    if (v.empty() || end == value || *end != '\0' || !(k > 0.0f && k <= 1.0f))
+      throw OhxError(n + " must be a finite decimal number with 0 < v <= 1");
+    (n == "ohx_colsample_bylevel" ? b->grow_bylevel : b->grow_bynode) = k;
   } else if (n == "ohx_grow_pairs") {
     // "on": squared error goes through the pair kernels too (the same bits); auto: only an objective that needs them
     if (v != "auto" && v != "on") throw OhxError("ohx_grow_pairs must be auto or on");

@@ -83,6 +83,40 @@ uint32_t grow_pick_features(uint64_t seed, uint64_t i, uint32_t F, float colsamp
   return n_sel;
 }
 
+namespace {
+
+// the `take` entries of list[0 .. n) smallest by (mix(key + f), f), in the list's order
+void pick_by_key(uint64_t key, const uint8_t* list, uint32_t n, uint32_t take, uint8_t* out) {
+  std::pair<std::pair<uint64_t, uint32_t>, uint32_t> c[kGrowMaxFeatures];   // ((key, f), position)
+  for (uint32_t k = 0; k < n; ++k) c[k] = {{grow_mix(key + list[k]), list[k]}, k};
+  std::sort(c, c + n);
+  bool in[kGrowMaxFeatures] = {};
+  for (uint32_t k = 0; k < take; ++k) in[c[k].second] = true;
+  uint32_t at = 0;
+  for (uint32_t k = 0; k < n; ++k)
+    if (in[k]) out[at++] = list[k];
+}
+
+}  // namespace
+
+uint32_t grow_pick_level_features(uint64_t seed, uint64_t i, uint32_t d, const uint8_t* tree_list, uint32_t n_sel, float bylevel,
+                                  uint8_t* out) {
+  const uint32_t n_lvl = n_sel <= kGrowMaxFeatures ? grow_num_selected(n_sel, bylevel) : 0;
+  if (n_lvl == 0) return 0;
+  if (n_lvl == n_sel) std::copy(tree_list, tree_list + n_sel, out);
+  else pick_by_key(grow_level_key(grow_col_key(seed, i), d), tree_list, n_sel, n_lvl, out);
+  return n_lvl;
+}
+
+uint32_t grow_pick_node_features(uint64_t seed, uint64_t i, uint32_t p, const uint8_t* level_list, uint32_t n_lvl, float bynode,
+                                 uint8_t* out) {
+  const uint32_t n_node = n_lvl <= kGrowMaxFeatures ? grow_num_selected(n_lvl, bynode) : 0;
+  if (n_node == 0) return 0;
+  if (n_node == n_lvl) std::copy(level_list, level_list + n_lvl, out);
+  else pick_by_key(grow_node_key(grow_col_key(seed, i), p), level_list, n_lvl, n_node, out);
+  return n_node;
+}
+
 Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature, uint32_t max_nodes) {
   if (n == 0 || n > max_nodes || n % 2 == 0) throw OhxError("grown tree: " + std::to_string(n) + " nodes is not a tree");
   Tree t;

@@ -381,6 +381,31 @@ inline uint32_t grow_num_selected(uint32_t F, float colsample) {
   return n < 1 ? 1 : n;
 }
 
+// ---- column sampling by level and by node ("ohx_colsample_bylevel", "ohx_colsample_bynode"; design in
+// docs/29_colsample_level_node.md) ----
+
+// K_lvl(i, d) and K_node(i, p) from K_col(i): d is the depth of the nodes being split (the root's is 0), p the node's id
+// in the tree in allocation order.  d + 1 <= 18 < 32, so a level key and a node key never share an input.
+constexpr uint64_t kGrowNodeKeyBase = 32;
+OHX_GROW_HD inline uint64_t grow_level_key(uint64_t col_key, uint32_t d) { return grow_mix(col_key + kGrowGamma64 * ((uint64_t)d + 1ull)); }
+OHX_GROW_HD inline uint64_t grow_node_key(uint64_t col_key, uint32_t p) {
+  return grow_mix(col_key + kGrowGamma64 * (kGrowNodeKeyBase + (uint64_t)p));
+}
+// (key, f) of one feature below that of another: the order both draws take their smallest by
+OHX_GROW_HD inline bool grow_draw_below(uint64_t ka, uint32_t fa, uint64_t kb, uint32_t fb) { return ka != kb ? ka < kb : fa < fb; }
+// What a split kernel of a column-sampled call takes: the lists of every round and level of the call, [rounds][depth][n_lvl]
+// bytes on the device, each ascending; n_node of the n_lvl features of its level are a node's; and what K_col of round r is
+// made from, the tree being tree0 + r of the draws.
+struct GrowColsampleArgs {
+  const uint8_t* lists = nullptr;
+  uint32_t depth = 0, n_lvl = 0, n_node = 0;
+  uint64_t seed = 0, tree0 = 0;
+  OHX_GROW_HD const uint8_t* list(uint32_t round, uint32_t level) const {
+    return lists + ((uint64_t)round * depth + level) * n_lvl;
+  }
+  OHX_GROW_HD uint64_t col_key(uint32_t round) const { return grow_col_key(seed, tree0 + round); }
+};
+
 // A node as the device leaves it.  Children are written as leaves when their parent splits and overwritten if they
 // split in turn, so every record is complete whenever the level loop stops.
 struct GrowNode {
@@ -448,6 +473,26 @@ inline GrowCand grow_mono_node_split(const int64_t* G, const uint64_t* H, uint32
 // to out[0 .. n_sel) in ascending f.  n_sel == F writes 0 .. F - 1 and draws nothing.  Returns n_sel (0: colsample is
 // unsound, F is 0 or above kGrowMaxFeatures; nothing is written).
 uint32_t grow_pick_features(uint64_t seed, uint64_t i, uint32_t F, float colsample, uint8_t* out);
+// The features of level d of tree i: the n_lvl = grow_num_selected(n_sel, bylevel) features of tree_list[0 .. n_sel)
+// smallest by (mix(K_lvl(i, d) + f), f), written to out[0 .. n_lvl) in the list's order.  n_lvl == n_sel copies the list
+// and draws nothing.  Returns n_lvl (0: bylevel is unsound, n_sel is 0 or above kGrowMaxFeatures; nothing is written).
+uint32_t grow_pick_level_features(uint64_t seed, uint64_t i, uint32_t d, const uint8_t* tree_list, uint32_t n_sel, float bylevel,
+                                  uint8_t* out);
+// The same for node p of that level over level_list[0 .. n_lvl): n_node = grow_num_selected(n_lvl, bynode) features by
+// (mix(K_node(i, p) + f), f).
+uint32_t grow_pick_node_features(uint64_t seed, uint64_t i, uint32_t p, const uint8_t* level_list, uint32_t n_lvl, float bynode,
+                                 uint8_t* out);
+// Whether f is one of them, as a split kernel finds it: the features of the level's list that lie below f by (key, f) are
+// counted, and f is in where they are fewer than n_node.  n_node >= n_lvl counts nothing.  f must be in the list.
+inline bool grow_node_has_feature(uint64_t seed, uint64_t i, uint32_t p, const uint8_t* level_list, uint32_t n_lvl, uint32_t n_node,
+                                  uint32_t f) {
+  if (n_node >= n_lvl) return true;
+  const uint64_t key = grow_node_key(grow_col_key(seed, i), p);
+  const uint64_t mine = grow_mix(key + f);
+  uint32_t below = 0;
+  for (uint32_t k = 0; k < n_lvl; ++k) below += grow_draw_below(grow_mix(key + level_list[k]), level_list[k], mine, f) ? 1u : 0u;
+  return below < n_node;
+}
 // A Tree of the forest from n node records (at most max_nodes: the stride of the call's node table); throws on a record
 // that is not a tree in allocation order.
 Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature, uint32_t max_nodes = kGrowMaxNodes);
@@ -777,7 +822,12 @@ int launch_grow_tree_deep(const GrowDeepArgs& a, const GrowDeepPlan& plan, uint3
 // deep levels (they read histograms alone) and the widen, partition and leaf kernels are launch_grow_tree_deep's own.
 struct GrowDeepLaunches {
   std::function<int(const GrowArgs& top, const GrowPlan& lds, void* stream)> top;
-  std::function<void(const GrowDeepArgs& d, uint32_t round, uint32_t batch0, uint32_t nslots, uint32_t hist_blocks, void* stream)> hist;
+  std::function<void(const GrowDeepArgs& d, uint32_t level, uint32_t round, uint32_t batch0, uint32_t nslots, uint32_t hist_blocks,
+                     void* stream)>
+      hist;
+  // The histogram columns of the deep levels where they are not the tree's (0: they are): a column-sampled call's n_lvl.
+  // The memsets, the waves of phase 0 and the plan's scratch are over them.
+  uint32_t ncols = 0;
   // The split phases of a deep level, where they are not grow_deep.hip's own (empty: they are): phase 0 over `blocks`
   // blocks of four waves for the batch from batch0 on, and phase 1, one block.
   std::function<void(const GrowDeepArgs& d, uint32_t level, uint32_t round, uint32_t batch0, uint32_t blocks, void* stream)> split0;
@@ -810,6 +860,14 @@ struct GrowPairSplits {
   std::function<void(const GrowArgs& a, const uint8_t* list, uint32_t ncols, int root, uint32_t level, uint32_t round, void* stream)> split1;
   std::function<void(const GrowDeepArgs& d, uint32_t level, uint32_t round, uint32_t batch0, uint32_t blocks, void* stream)> deep_split0;
   std::function<void(const GrowDeepArgs& d, uint32_t level, uint32_t round, void* stream)> deep_split1;
+  // Column sampling by level (grow_colsample.hip): with levels.lists the histogram kernels of level d of the call's round
+  // r add the columns levels.list(r, d), levels.n_lvl of them, in place of the tree's list, and so do the memsets and the
+  // split launches; the call's plan is over n_lvl columns.  `list` and `ncols` of split0 / split1 are then the level's, and
+  // level_split0 / level_split1 stand in their place: they take the call's round too, which `round` is not where the
+  // tree is round 0 of its own table (the Deep call's levels 0 - 7).
+  GrowColsampleArgs levels;
+  std::function<void(const GrowArgs& a, uint32_t tree, uint32_t blocks, uint32_t level, uint32_t round, void* stream)> level_split0;
+  std::function<void(const GrowArgs& a, uint32_t tree, int root, uint32_t level, uint32_t round, void* stream)> level_split1;
 };
 // launch_grow_tree_weighted (a.features == nullptr) or launch_grow_tree_sampled (a.features != nullptr) on pairs: the
 // pair kernel over every row, then the levels with the histogram kernel that reads the planes, then the leaf kernel.
@@ -837,6 +895,14 @@ int launch_grow_walk_sse_deep_metric(const GrowEvalArgs& a, const GrowDeepArgs& 
 // The constrained split launches of a call: grow_split_mono_kernel for levels 0 - 7 and grow_deep_split_mono_kernel below.
 // m.bounds holds two doubles a node of the call's node stride, m.constraints num_feature entries; both on the device.
 GrowPairSplits grow_mono_splits(const GrowMonoArgs& m);
+// ---- column sampling by level and by node on the GPU (grow_colsample.hip; design in docs/29_colsample_level_node.md) ----
+
+// The split launches of a column-sampled call under each hessian policy of the pair path: grow_split_colsample_kernel
+// for levels 0 - 7 and grow_deep_split_colsample_kernel below, over the level's list, with a (node, column) outside the
+// node's features left an invalid candidate.  c.lists is on the device.  Empty launches where c is unsound.
+GrowPairSplits grow_colsample_splits(const GrowColsampleArgs& c, const GrowFixedHess& hess);
+GrowPairSplits grow_colsample_splits(const GrowColsampleArgs& c, const GrowRegHess& hess);
+GrowPairSplits grow_colsample_splits(const GrowColsampleArgs& c, const GrowMonoArgs& m);
 // Enqueues grow_deep_stage_kernel and grow_deep_walk_sse_kernel: eval_nodes from the records of tree `round`, then
 // launch_grow_walk_sse_weighted's walk and sums over the rows of `a`, its nodes read from HBM.  Returns a hipError_t.
 int launch_grow_walk_sse_deep(const GrowEvalArgs& a, const GrowDeepArgs& d, uint32_t blocks, uint32_t round, uint32_t set,

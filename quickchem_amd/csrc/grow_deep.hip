@@ -326,9 +326,10 @@ __global__ __launch_bounds__(kBlock) void grow_deep_walk_sse_kernel(GrowEvalArgs
 // the histogram columns of a tree: the tree's feature list where the call has one, else every feature
 uint32_t deep_columns(const GrowArgs& a) { return a.features != nullptr ? a.n_sel : a.num_feature; }
 
-bool deep_args_sound(const GrowDeepArgs& d, const GrowDeepPlan& plan) {
+// ncols: the histogram columns of the deep levels, the tree's or fewer (GrowDeepLaunches::ncols)
+bool deep_args_sound(const GrowDeepArgs& d, const GrowDeepPlan& plan, uint32_t ncols) {
   const GrowArgs& a = d.g;
-  const uint32_t ncols = deep_columns(a);
+  if (ncols > deep_columns(a)) return false;
   return a.nrow != 0 && a.nrow <= kRefitMaxRows && a.num_feature != 0 && a.num_feature <= kGrowMaxFeatures && ncols != 0 &&
          ncols <= a.num_feature && (a.features != nullptr || a.bag == nullptr) &&
          a.max_depth > kGrowMaxDepth && a.max_depth <= kGrowDeepMaxDepth && a.min_child_weight >= 0.0 && d.pos != nullptr &&
@@ -347,7 +348,7 @@ int launch_grow_tree_deep(const GrowDeepArgs& d, const GrowDeepPlan& plan, uint3
   l.top = [](const GrowArgs& top, const GrowPlan& lds, void* s) {
     return top.features != nullptr ? launch_grow_levels_sampled(top, lds, lds, 0, s) : launch_grow_levels_weighted(top, lds, lds, 0, s);
   };
-  l.hist = [](const GrowDeepArgs& a, uint32_t r, uint32_t batch0, uint32_t nslots, uint32_t hist_blocks, void* s) {
+  l.hist = [](const GrowDeepArgs& a, uint32_t, uint32_t r, uint32_t batch0, uint32_t nslots, uint32_t hist_blocks, void* s) {
     hipStream_t stream = static_cast<hipStream_t>(s);
     if (a.g.features != nullptr)
       hipLaunchKernelGGL(grow_deep_hist_sampled_kernel, dim3(hist_blocks, (a.g.n_sel + kDeepPackFeatures - 1) / kDeepPackFeatures),
@@ -360,14 +361,14 @@ int launch_grow_tree_deep(const GrowDeepArgs& d, const GrowDeepPlan& plan, uint3
 int launch_grow_tree_deep_with(const GrowDeepArgs& d, const GrowDeepPlan& plan, uint32_t round, GrowLevelState* h_state,
                                void* stream_, const GrowDeepLaunches& launches) {
   hipStream_t stream = static_cast<hipStream_t>(stream_);
-  if (!deep_args_sound(d, plan) || h_state == nullptr || !launches.top || !launches.hist) return hipErrorInvalidValue;
+  const uint32_t ncols = launches.ncols != 0 ? launches.ncols : deep_columns(d.g);
+  if (!deep_args_sound(d, plan, ncols) || h_state == nullptr || !launches.top || !launches.hist) return hipErrorInvalidValue;
   // levels 0 - 7 on the tree's own records (a tree of 8 levels has at most 511 of them, and no more than 2 * nrow - 1:
   // within the stride either way)
   const bool sampled = d.g.features != nullptr;
-  const uint32_t ncols = deep_columns(d.g);
   GrowArgs top = tree_args(d, round);
   top.max_depth = kGrowMaxDepth;
-  if (sampled) top.features += (uint64_t)round * ncols;   // round 0 of its own list, as of its own records
+  if (sampled) top.features += (uint64_t)round * deep_columns(d.g);   // round 0 of its own list, as of its own records
   hipError_t e = (hipError_t)launches.top(top, plan.lds, stream);
   if (e != hipSuccess) return e;
   // the level word after phase 1 of level d - 1: the open nodes of level d
@@ -389,7 +390,7 @@ int launch_grow_tree_deep_with(const GrowDeepArgs& d, const GrowDeepPlan& plan, 
       const size_t bytes = (size_t)nslots * ncols * kGrowBins * sizeof(unsigned long long);
       if ((e = hipMemsetAsync(d.g.Ghist, 0, bytes, stream)) != hipSuccess) return e;
       if ((e = hipMemsetAsync(d.g.Hhist, 0, bytes, stream)) != hipSuccess) return e;
-      launches.hist(d, round, batch0, nslots, plan.hist_blocks, stream);
+      launches.hist(d, level, round, batch0, nslots, plan.hist_blocks, stream);
       if ((e = hipGetLastError()) != hipSuccess) return e;
       const dim3 waves((nslots * ncols + kWaves - 1) / kWaves);
       if (launches.split0) launches.split0(d, level, round, batch0, waves.x, stream);

@@ -297,6 +297,42 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_features(uint64_t
   }
 }
 
+// ---- column sampling by level and by node (docs/29_colsample_level_node.md) ----
+
+// keys[0] = K_lvl(tree, level) and keys[1] = K_node(tree, node) of the draws (grow_col_key, grow_level_key, grow_node_key)
+extern "C" __attribute__((visibility("default"))) void ohx_grow_colsample_keys(uint64_t seed, uint64_t tree, uint32_t level, uint32_t node,
+                                                                              uint64_t keys[2]) {
+  const uint64_t col = grow_col_key(seed, tree);
+  keys[0] = grow_level_key(col, level);
+  keys[1] = grow_node_key(col, node);
+}
+
+// out[0 .. *n_out): what level `level` (which == 0: grow_pick_level_features) or node `at` (which == 1:
+// grow_pick_node_features) of tree `tree` keeps of list[0 .. n) at `fraction`; out holds n entries
+extern "C" __attribute__((visibility("default"))) int ohx_grow_colsample_pick(int which, uint64_t seed, uint64_t tree, uint32_t at,
+                                                                             const uint8_t* list, uint32_t n, float fraction,
+                                                                             uint8_t* out, uint32_t* n_out) {
+  try {
+    if (n == 0 || n > kGrowMaxFeatures) throw OhxError("ohx_grow_colsample_pick: a list of 1 to 128 features");
+    const uint32_t k = which == 0 ? grow_pick_level_features(seed, tree, at, list, n, fraction, out)
+                                  : grow_pick_node_features(seed, tree, at, list, n, fraction, out);
+    if (k == 0) throw OhxError("ohx_grow_colsample_pick: the fraction must be finite, > 0 and <= 1");
+    *n_out = k;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
+// grow_node_has_feature: 1 where f is one of node `node`'s n_node features of list[0 .. n_lvl), by the rank a split kernel
+// computes; f must be in the list
+extern "C" __attribute__((visibility("default"))) int ohx_grow_colsample_has(uint64_t seed, uint64_t tree, uint32_t node,
+                                                                            const uint8_t* list, uint32_t n_lvl, uint32_t n_node,
+                                                                            uint32_t f) {
+  return grow_node_has_feature(seed, tree, node, list, n_lvl, n_node, f) ? 1 : 0;
+}
+
 // the level plan of a sampled call: plan_grow_weighted over n_sel = grow_num_selected(num_feature, colsample) features;
 // info as ohx_grow_plan_weighted's with info[3] the bin planes of all num_feature features, and info[8] = n_sel
 extern "C" __attribute__((visibility("default"))) int ohx_grow_plan_sampled(uint64_t nrow, uint32_t num_feature, float colsample,

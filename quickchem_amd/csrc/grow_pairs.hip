@@ -236,25 +236,42 @@ hipError_t launch_pair_kernel(const GrowArgs& a, const GrowPairArgs& p, const Gr
 }
 
 // The pair kernel, then grow_device.hpp's level loop with this file's launches.  `list`: the tree's own list or nullptr.
+// `tree`: the call's round, which `round` is not where the tree is round 0 of its own table; it picks the lists of a
+// column-sampled call (splits->levels), whose level d adds and splits the columns of its own list.
 hipError_t pairs_levels(const GrowArgs& a, const GrowPairArgs& p, const uint8_t* list, const GrowPlan& plan, const GrowPlan& levels,
-                        uint32_t round, hipStream_t stream, bool leaf, const GrowPairSplits* splits) {
+                        uint32_t round, uint32_t tree, hipStream_t stream, bool leaf, const GrowPairSplits* splits) {
   if (!pairs_args_sound(a, p)) return hipErrorInvalidValue;
-  if (splits != nullptr && (!splits->split0 || !splits->split1)) return hipErrorInvalidValue;
+  const bool by_level = splits != nullptr && splits->levels.lists != nullptr;
+  if (by_level ? !splits->level_split0 || !splits->level_split1 || splits->levels.depth < (uint32_t)a.max_depth ||
+                     splits->levels.n_lvl == 0 || splits->levels.n_lvl > (list != nullptr ? a.n_sel : a.num_feature)
+               : splits != nullptr && (!splits->split0 || !splits->split1))
+    return hipErrorInvalidValue;
   const GrowPairPlanes k = planes_of(a, p, list);
+  // the planes and the columns of level d
+  auto planes_at = [&](uint32_t d) {
+    GrowPairPlanes kd = k;
+    if (by_level) {
+      kd.list = splits->levels.list(tree, d);
+      kd.ncols = splits->levels.n_lvl;
+    }
+    return kd;
+  };
   hipError_t e = launch_pair_kernel(a, p, k, plan, stream);
   if (e != hipSuccess) return e;
   const int root = p.objective == kGrowObjPseudoHuber ? kRootHess : list != nullptr ? kRootBag : kRootNone;
   return grow_launch_tree(
-      a, plan, levels, round, stream, k.ncols, kGrowWeightedPairBytes, 0,
+      a, plan, levels, round, stream, planes_at(0).ncols, kGrowWeightedPairBytes, 0,
       [&](const GrowLevelPlan& l, uint32_t d) {
         hipLaunchKernelGGL(grow_hist_pairs_kernel, dim3(l.hist_blocks, l.node_groups * l.feat_groups), dim3(kHistBlock), l.lds_bytes,
-                           stream, a, k, d, l.node_group, l.feat_group, l.feat_groups);
+                           stream, a, planes_at(d), d, l.node_group, l.feat_group, l.feat_groups);
       },
       [&](uint32_t blocks, uint32_t d) {
+        if (by_level) return splits->level_split0(a, tree, blocks, d, round, stream);
         if (splits != nullptr) return splits->split0(a, k.list, k.ncols, blocks, d, round, stream);
         hipLaunchKernelGGL((grow_split_pairs_kernel<0, kRootNone>), dim3(blocks), dim3(kBlock), 0, stream, a, k, d, round);
       },
       [&](uint32_t d) {
+        if (by_level) return splits->level_split1(a, tree, root, d, round, stream);
         if (splits != nullptr) return splits->split1(a, k.list, k.ncols, root, d, round, stream);
         if (root == kRootHess) hipLaunchKernelGGL((grow_split_pairs_kernel<1, kRootHess>), dim3(1), dim3(kBlock), 0, stream, a, k, d, round);
         else if (root == kRootBag) hipLaunchKernelGGL((grow_split_pairs_kernel<1, kRootBag>), dim3(1), dim3(kBlock), 0, stream, a, k, d, round);
@@ -270,7 +287,7 @@ int grow_lds_limits_pairs() { return raise_lds_limit(grow_hist_pairs_kernel, kGr
 int launch_grow_tree_pairs(const GrowArgs& a, const GrowPairArgs& p, const GrowPlan& plan, const GrowPlan& levels, uint32_t round,
                            void* stream, const GrowPairSplits* splits) {
   const uint8_t* list = a.features != nullptr ? a.features + (uint64_t)round * a.n_sel : nullptr;
-  return pairs_levels(a, p, list, plan, levels, round, static_cast<hipStream_t>(stream), true, splits);
+  return pairs_levels(a, p, list, plan, levels, round, round, static_cast<hipStream_t>(stream), true, splits);
 }
 
 int launch_grow_tree_deep_pairs(const GrowDeepArgs& d, const GrowPairArgs& p, const GrowDeepPlan& plan, uint32_t round,
@@ -283,11 +300,21 @@ int launch_grow_tree_deep_pairs(const GrowDeepArgs& d, const GrowPairArgs& p, co
     l.split1 = splits->deep_split1;
   }
   // (top.features is the tree's own list already: round 0 of its own list, as of its own records)
-  l.top = [&p, splits](const GrowArgs& top, const GrowPlan& lds, void* s) {
-    return (int)pairs_levels(top, p, top.features, lds, lds, 0, static_cast<hipStream_t>(s), false, splits);
+  const bool by_level = splits != nullptr && splits->levels.lists != nullptr;
+  if (by_level && (splits->levels.depth < (uint32_t)d.g.max_depth || splits->levels.n_lvl == 0 ||
+                   splits->levels.n_lvl > (d.g.features != nullptr ? d.g.n_sel : d.g.num_feature)))
+    return hipErrorInvalidValue;
+  if (by_level) l.ncols = splits->levels.n_lvl;
+  l.top = [&p, splits, round](const GrowArgs& top, const GrowPlan& lds, void* s) {
+    return (int)pairs_levels(top, p, top.features, lds, lds, 0, round, static_cast<hipStream_t>(s), false, splits);
   };
-  l.hist = [&p](const GrowDeepArgs& a, uint32_t r, uint32_t batch0, uint32_t nslots, uint32_t hist_blocks, void* s) {
-    const GrowPairPlanes k = planes_of(a.g, p, a.g.features != nullptr ? a.g.features + (uint64_t)r * a.g.n_sel : nullptr);
+  l.hist = [&p, splits, by_level](const GrowDeepArgs& a, uint32_t level, uint32_t r, uint32_t batch0, uint32_t nslots, uint32_t hist_blocks,
+                                  void* s) {
+    GrowPairPlanes k = planes_of(a.g, p, a.g.features != nullptr ? a.g.features + (uint64_t)r * a.g.n_sel : nullptr);
+    if (by_level) {   // the level's own list
+      k.list = splits->levels.list(r, level);
+      k.ncols = splits->levels.n_lvl;
+    }
     hipLaunchKernelGGL(grow_deep_hist_pairs_kernel, dim3(hist_blocks, (k.ncols + kDeepPackFeatures - 1) / kDeepPackFeatures),
                        dim3(kBlock), 0, static_cast<hipStream_t>(s), a, k, batch0, nslots);
   };

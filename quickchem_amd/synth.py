@@ -115,6 +115,11 @@ def _load():
         lib.ohx_grow_weighted_stop.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p]
         lib.ohx_grow_bag.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p]
         lib.ohx_grow_features.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p, C.c_void_p]
+        lib.ohx_grow_colsample_keys.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.ohx_grow_colsample_keys.restype = None
+        lib.ohx_grow_colsample_pick.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float,
+                                                C.c_void_p, C.c_void_p]
+        lib.ohx_grow_colsample_has.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
         lib.ohx_grow_plan_sampled.argtypes = [C.c_uint64, C.c_uint32, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
                                               C.c_void_p]
         lib.ohx_grow_deep_batch.argtypes = []
@@ -784,6 +789,41 @@ def boost_features(seed: int, tree: int, F: int, colsample: float):
     _check(_load().ohx_grow_features(int(seed) & 0xFFFFFFFFFFFFFFFF, int(tree) & 0xFFFFFFFFFFFFFFFF, F, colsample, out.ctypes.data,
                                      C.addressof(n)))
     return out[:int(n.value)].copy()
+
+
+_U64 = 0xFFFFFFFFFFFFFFFF
+
+
+def colsample_keys(seed: int, tree: int, level: int, node: int):
+    """csrc/grow.hpp grow_level_key and grow_node_key over grow_col_key -> (K_lvl(tree, level), K_node(tree, node))."""
+    keys = np.zeros(2, dtype=np.uint64)
+    _load().ohx_grow_colsample_keys(int(seed) & _U64, int(tree) & _U64, level, node, keys.ctypes.data)
+    return int(keys[0]), int(keys[1])
+
+
+def _colsample_pick(which: int, seed: int, tree: int, at: int, features, fraction: float):
+    lst = np.ascontiguousarray(features, dtype=np.uint8)
+    out = np.zeros(max(len(lst), 1), dtype=np.uint8)
+    n = C.c_uint32()
+    _check(_load().ohx_grow_colsample_pick(which, int(seed) & _U64, int(tree) & _U64, at, lst.ctypes.data, len(lst), fraction,
+                                           out.ctypes.data, C.addressof(n)))
+    return out[:int(n.value)].copy()
+
+
+def boost_level_features(seed: int, tree: int, level: int, tree_list, bylevel: float):
+    """csrc/grow.cpp grow_pick_level_features: what level `level` of tree `tree` keeps of the tree's list (uint8 [n_lvl])."""
+    return _colsample_pick(0, seed, tree, level, tree_list, bylevel)
+
+
+def boost_node_features(seed: int, tree: int, node: int, level_list, bynode: float):
+    """csrc/grow.cpp grow_pick_node_features: what node `node` of tree `tree` keeps of its level's list (uint8 [n_node])."""
+    return _colsample_pick(1, seed, tree, node, level_list, bynode)
+
+
+def boost_node_has_feature(seed: int, tree: int, node: int, level_list, n_node: int, f: int) -> bool:
+    """csrc/grow.hpp grow_node_has_feature: the rank the split kernels compute; f must be in the level's list."""
+    lst = np.ascontiguousarray(level_list, dtype=np.uint8)
+    return bool(_load().ohx_grow_colsample_has(int(seed) & _U64, int(tree) & _U64, node, lst.ctypes.data, len(lst), n_node, f))
 
 
 def grow_plan_sampled(nrow: int, num_feature: int = NFEAT, colsample: float = 1.0, ncuts: int = 0, max_depth: int = 6,

@@ -46,7 +46,13 @@ under pseudohuber.
 `--monotone "(1,0,-1)"` sets "ohx_monotone_constraints" on every booster that is timed (docs/28_monotone_constraints.md): the
 calls with row weights then take the constrained split kernels over the pair path.  Against a run with `--pairs on
 --max-delta-step 0.5` - the same pair and histogram kernels and the same gain form - the difference is the split kernels
-and the trees they choose; the node counts stand beside the times."""
+and the trees they choose; the node counts stand beside the times.
+
+`--colsample-bylevel L` and `--colsample-bynode N` set "ohx_colsample_bylevel" and "ohx_colsample_bynode" on every booster
+that is timed (docs/29_colsample_level_node.md), with `--subsample` / `--colsample`: the sampled calls then add the columns
+of a level's own list and take the column-sampled split kernels over the pair path.  Against a run with `--pairs on` and
+the same `--subsample` / `--colsample` the difference is the columns the histogram kernels add, the split kernels and the
+trees they choose.  Left out, neither parameter is set."""
 from __future__ import annotations
 
 import argparse
@@ -160,6 +166,8 @@ def main():
     ap.add_argument("--max-delta-step", type=float, default=0.0, help="ohx_max_delta_step of the timed boosters")
     ap.add_argument("--eval-metric", choices=("rmse", "mae", "pseudohuber"), default="rmse", help="ohx_eval_metric of the timed boosters")
     ap.add_argument("--monotone", default=None, help="ohx_monotone_constraints of the timed boosters, as the parameter is written: \"(1,0,-1)\"")
+    ap.add_argument("--colsample-bylevel", type=float, default=None, help="ohx_colsample_bylevel of the timed boosters (with --subsample / --colsample)")
+    ap.add_argument("--colsample-bynode", type=float, default=None, help="ohx_colsample_bynode of the timed boosters (with --subsample / --colsample)")
     args = ap.parse_args()
     sampled = args.subsample is not None or args.colsample is not None
     if sampled:
@@ -171,6 +179,8 @@ def main():
         ap.error("--deep times the call without a held-out set: leave --holdout out")
     if args.weights != "none" and args.holdout:
         ap.error("--weights times the call without a held-out set: leave --holdout out")
+    if (args.colsample_bylevel is not None or args.colsample_bynode is not None) and not sampled:
+        ap.error("--colsample-bylevel / --colsample-bynode act on the calls that carry a seed: give --subsample / --colsample")
     regularised = args.reg_alpha != 0.0 or args.max_delta_step != 0.0 or args.eval_metric != "rmse"
     if (args.objective != "squarederror" or args.pairs != "auto" or regularised or args.monotone is not None) and (args.holdout or not (sampled or args.deep or args.weights != "none")):
         ap.error("--objective / --pairs / --reg-alpha / --max-delta-step / --eval-metric / --monotone time a call with row weights: give --weights, --subsample / --colsample or --deep, and no --holdout")
@@ -264,6 +274,7 @@ def main():
     res["objective"] = {"ohx_objective": args.objective, "ohx_huber_slope": args.huber_slope, "ohx_grow_pairs": args.pairs}
     res["regularisation"] = {"ohx_reg_alpha": args.reg_alpha, "ohx_max_delta_step": args.max_delta_step, "ohx_eval_metric": args.eval_metric}
     res["monotone_constraints"] = args.monotone
+    res["colsample"] = {"ohx_colsample_bylevel": args.colsample_bylevel, "ohx_colsample_bynode": args.colsample_bynode}
     res["pair_planes"] = synth.grow_pairs_plan(n, F, ncuts, args.max_depth, cus)
 
     def timed_booster():
@@ -277,6 +288,10 @@ def main():
             b.set_param("ohx_eval_metric", args.eval_metric)
         if args.monotone is not None:
             b.set_param("ohx_monotone_constraints", args.monotone)
+        if args.colsample_bylevel is not None:
+            b.set_param("ohx_colsample_bylevel", repr(args.colsample_bylevel))
+        if args.colsample_bynode is not None:
+            b.set_param("ohx_colsample_bynode", repr(args.colsample_bynode))
         return b
 
     last = {}                              # what the weighted call returned last
