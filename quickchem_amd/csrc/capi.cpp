@@ -1245,17 +1245,12 @@ PeriodColumns level_columns(const DMatrixObj& d) { return PeriodColumns{{0u, (ui
 // verdict[c * (kmax - 1) + x]: 0 = column c repeats with period nrow / (kmax - x)
 void adopt_level_size(DMatrixObj& d, const uint32_t* verdict, uint32_t kmax) {
   d.grid_looked = true;
-  for (uint32_t c = 0; c < 4; ++c)
-    for (uint32_t x = 0; x + 1 < kmax; ++x) {                    // ascending periods: the smallest that holds
-      const uint64_t period = d.nrow / (kmax - x);
-      if (verdict[(size_t)c * (kmax - 1) + x] == 0 && period <= 0x7FFFFFFFull) {
-        d.grid_im = (int)period;
-        d.grid_jm = 1;
-        d.grid_row0 = 0;
-        d.grid_inferred = true;
-        return;
-      }
-    }
+  const uint64_t period = pick_level_period(verdict, kmax, d.nrow);      // kernels.hpp: column order, then the smallest
+  if (period == 0) return;
+  d.grid_im = (int)period;
+  d.grid_jm = 1;
+  d.grid_row0 = 0;
+  d.grid_inferred = true;
 }
 
 // What the search found for matrices of a shape seen before.  The reference creates and frees its DMatrix on every
@@ -1371,13 +1366,10 @@ const uint32_t* cluster_rows(BoosterObj& b, DMatrixObj& d, const PredictArgs& a,
     HIP_CHECK(hipStreamSynchronize(stream));
     // observed agreement between neighbours in row order against what rows in random order would show
     // (sum of squared shares of the eight outcomes): 0 = as good as shuffled, 1 = every row like the one before
-    const uint32_t* h = b.h_cluster_small.p;
-    const double n = (double)d.nrow, observed = (double)h[0] / n;
-    double by_chance = 0.0;
-    for (int v = 1; v <= 8; ++v) by_chance += ((double)h[v] / n) * ((double)h[v] / n);
-    const double order = by_chance < 0.999 ? (observed - by_chance) / (1.0 - by_chance) : 0.0;
+    double observed = 0.0, by_chance = 0.0;
+    const double order = cluster_order(b.h_cluster_small.p, d.nrow, &observed, &by_chance);      // kernels.hpp
     d.cluster_decided = true;
-    d.cluster_on = order < 0.33;
+    d.cluster_on = order < kClusterOrderBelow;
     if (getenv("OHX_DEBUG"))
       fprintf(stderr, "[libohxgb] cluster verdict: %.1f %% of the rows take the first three decisions of the row before them, "
               "%.1f %% would by chance: order %.2f -> %s\n", 100.0 * observed, 100.0 * by_chance, order,

@@ -1512,7 +1512,7 @@ __global__ __launch_bounds__(kBlock) void detect_period_kernel(const float* __re
 // One lane = one row.  The wave's rows go through the same LDS tile as in the walk (coalesced row loads, missing ->
 // NaN), the key walk reads its features from there.  Key = for each of `ntrees` trees the root decision (trees
 // whose super-nodes start below the root) and two decisions per super-node step, most significant first; a row
-// that reaches a leaf early keeps walking on fixed decisions.  zorder: the trees' decisions interleaved step by
+// that reaches a leaf early adds 00 for every step from there on.  zorder: the trees' decisions interleaved step by
 // step instead of tree after tree.  Also counts how many rows agree with the row before them on the first three
 // decisions of the first tree - rows in grid order mostly do (74 % on the C360 batch), shuffled rows mostly do
 // not (21 %) - and how often each of the eight outcomes occurs, so that the host can tell "ordered" from "a
@@ -1570,11 +1570,13 @@ __global__ __launch_bounds__(kBlock) void cluster_keys_kernel(DeviceForest fr, C
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     uint32_t key = 0, lead = 0;
     uint32_t rel[NT], part[NT];
+    bool on_leaf[NT];                       // the walk has its leaf: 00 from here on, whatever the row holds
     u32x4 nd[NT];
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       rel[t] = 4u;
       part[t] = 0;
+      on_leaf[t] = false;
       if (h[t].root_meta & 0x100u) {        // phase 1: the root is evaluated from the head
         const float x = tile[(h[t].root_meta & 31u) * kKeyTileStride];
         const bool l = (x != x) ? (h[t].root_meta & 32u) != 0u : x < h[t].root_thr;
@@ -1587,9 +1589,12 @@ __global__ __launch_bounds__(kBlock) void cluster_keys_kernel(DeviceForest fr, C
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         uint32_t bits = 0;
-        if (s < h[t].steps) {
+        // (past its leaf a walk stands on fillers, which compare feature 0 with +inf: a row that holds +inf there as a
+        // value - the marker being -inf - would go right at them, and its key would say 11 where it means "leaf")
+        if (s < h[t].steps && !on_leaf[t]) {
           const uint32_t w = nd[t].w;
           const uint32_t f0 = (w >> 8) & 31u;
+          on_leaf[t] = f0 == kSuperLeaf;
           if (f0 != kSuperLeaf) {
             const float x0 = tile[f0 * kKeyTileStride];
             const bool l0 = (x0 != x0) ? (w & 32u) != 0u : x0 < __uint_as_float(nd[t].x);
@@ -1598,6 +1603,8 @@ __global__ __launch_bounds__(kBlock) void cluster_keys_kernel(DeviceForest fr, C
             if (f1 != kSuperLeaf) {
               const float x1 = tile[f1 * kKeyTileStride];
               l1 = (x1 != x1) ? (w & (l0 ? 64u : 128u)) != 0u : x1 < __uint_as_float(l0 ? nd[t].y : nd[t].z);
+            } else {
+              on_leaf[t] = true;
             }
             bits = (l0 ? 0u : 2u) | (l1 ? 0u : 1u);
             rel[t] = ((w >> 18) << 2) + bits;

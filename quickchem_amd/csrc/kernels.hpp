@@ -310,6 +310,20 @@ struct ClusterArgs {
                                      // previous row's, [1..8] rows per outcome of those three decisions
 };
 uint32_t cluster_key_bits(const ClusterArgs& a);
+// What the host makes of the nine `agree` words of a pass over `nrow` rows (capi.cpp cluster_rows): the observed
+// agreement between neighbours in row order against what rows in random order would show (the sum of the squared
+// shares of the eight outcomes).  0 = as good as shuffled, 1 = every row like the one before; 0 as well where nearly
+// every row takes one outcome (by chance >= 0.999: a tree top that tells nothing).  Rows are clustered while the
+// order is below kClusterOrderBelow.
+constexpr double kClusterOrderBelow = 0.33;
+inline double cluster_order(const uint32_t agree[9], uint64_t nrow, double* observed, double* by_chance) {
+  const double n = (double)nrow, seen = (double)agree[0] / n;
+  double chance = 0.0;
+  for (int v = 1; v <= 8; ++v) chance += ((double)agree[v] / n) * ((double)agree[v] / n);
+  if (observed) *observed = seen;
+  if (by_chance) *by_chance = chance;
+  return chance < 0.999 ? (seen - chance) / (1.0 - chance) : 0.0;
+}
 hipError_t launch_cluster_keys(const DeviceForest& forest, const ClusterArgs& a, int num_cus, hipStream_t stream);
 // (key, value) pairs sorted by the low `key_bits` bits of the key.  Called with temp == nullptr it only reports
 // the scratch bytes needed in *temp_bytes.  *sorted_vals = whichever of vals_a / vals_b holds the result.
@@ -398,5 +412,16 @@ struct PeriodColumns {
 };
 hipError_t launch_detect_period(const float* data, uint64_t nrow, uint32_t ncol, const PeriodColumns& cols,
                                 uint32_t ncols, uint32_t kmax, uint32_t* d_verdict, hipStream_t stream);
+// The level size the host adopts from the verdict words of four columns (capi.cpp adopt_level_size): the columns in
+// the order they were given, and within a column the smallest period that holds (x ascending); a period that does not
+// fit an int is passed over.  0 = none.
+inline uint64_t pick_level_period(const uint32_t* verdict, uint32_t kmax, uint64_t nrow) {
+  for (uint32_t c = 0; c < 4; ++c)
+    for (uint32_t x = 0; x + 1 < kmax; ++x) {                    // ascending periods: the smallest that holds
+      const uint64_t period = nrow / (kmax - x);
+      if (verdict[(size_t)c * (kmax - 1) + x] == 0 && period <= 0x7FFFFFFFull) return period;
+    }
+  return 0;
+}
 
 }  // namespace ohx

@@ -84,6 +84,10 @@ int launched(const char* what) {
 
 }  // namespace
 
+namespace ohx {
+void synth_gpu_set_error(const std::string& m) { g_err = m; }   // for probe_gpu.hip
+}
+
 #pragma GCC visibility push(default)
 extern "C" {
 

@@ -156,6 +156,9 @@ def _load():
                                         C.c_uint32, C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]
         lib.ohx_cuts_keys.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.ohx_cuts_plan.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+        lib.ohx_cluster_order.argtypes = [C.c_void_p, C.c_uint64, C.POINTER(C.c_double)]
+        lib.ohx_pick_level_period.argtypes = [C.c_void_p, C.c_uint32, C.c_uint64]
+        lib.ohx_pick_level_period.restype = C.c_uint64
         _lib = lib
     return _lib
 
@@ -339,6 +342,24 @@ def super_heads_cpu(image):
     out = np.zeros((n.value, 2), dtype=np.uint32)
     _check(lib.ohx_super_heads_cpu(src.ctypes.data, src.nbytes, out.ctypes.data, n.value, C.byref(n)))
     return out
+
+
+def cluster_order(agree, nrow: int):
+    """What the product makes of the clustering pass's nine `agree` words over `nrow` rows (csrc/kernels.hpp
+    cluster_order): (order, observed, by_chance, clustered) - rows of an order below kClusterOrderBelow are clustered."""
+    words = np.ascontiguousarray(agree, dtype=np.uint32)
+    assert words.shape == (9,)
+    out = (C.c_double * 3)()
+    on = _load().ohx_cluster_order(words.ctypes.data, int(nrow), out)
+    return float(out[0]), float(out[1]), float(out[2]), bool(on)
+
+
+def pick_level_period(verdict, kmax: int, nrow: int) -> int:
+    """The level size the product adopts from the level search's verdict words (csrc/kernels.hpp pick_level_period):
+    verdict[c][x] of four columns, x = 0 .. kmax - 2 for the periods nrow / (kmax - x).  0 = none."""
+    words = np.ascontiguousarray(verdict, dtype=np.uint32).reshape(-1)
+    assert kmax >= 2 and words.size == 4 * (kmax - 1)
+    return int(_load().ohx_pick_level_period(words.ctypes.data, int(kmax), int(nrow)))
 
 
 def contribs_cpu(image, rows: np.ndarray, num_feature: int, missing: float = XX_MISS, approximate: bool = False,
@@ -934,6 +955,10 @@ def _load_gpu():
         lib.ohx_synth_rows_device.argtypes = [u32, i32, i32, i32, u64, u64, vp, vp]
         lib.ohx_synth_field_device.argtypes = [u32, i32, i32, i32, i32, vp, vp]
         lib.ohx_inject_missing_device.argtypes = [vp, u64, u32, u32, C.c_float, vp]
+        lib.ohx_probe_cluster_keys.argtypes = [vp, u64, vp, u32, u32, vp, u64, u32, C.c_float, u32, u32, u32, vp, vp, vp,
+                                               i32, vp]
+        lib.ohx_probe_sort_pairs.argtypes = [vp, vp, vp, vp, u64, u32, vp, C.POINTER(i32), C.POINTER(u64)]
+        lib.ohx_probe_detect_period.argtypes = [vp, u64, u32, vp, u32, u32, vp, vp]
         _gpu_lib = lib
     return _gpu_lib
 
@@ -959,6 +984,44 @@ def field_device(grid: Tuple[int, int, int], feature: int, out, seed: int = FEAT
 def inject_missing_device(rows, rate_per_million: int, missing: float = XX_MISS, seed: int = 7, stream: int = 0) -> None:
     _check_gpu(_load_gpu().ohx_inject_missing_device(rows.data_ptr(), rows.numel(), seed, rate_per_million, missing,
                                                      stream or None))
+
+
+# ---- probes of the clustering pass and the level search (csrc/probe_gpu.hip): the product's kernels on the test's buffers ----
+
+def probe_cluster_keys(nodes, heads, num_feature: int, rows, ncol: int, missing: float, ntrees: int, nsteps: int,
+                       zorder: int, keys, vals, agree, num_cus: int, stream: int = 0, nrow=None) -> None:
+    """launch_cluster_keys (csrc/kernels.hip) on torch tensors in HBM: `nodes` ([records][4] uint32-sized words) and
+    `heads` ([trees][4]) are super_records_cpu's arrays uploaded as they are, `rows` holds nrow x ncol float32, `keys`
+    and `vals` take nrow words each, `agree` is nine words that must be zero before.  Raises OhxError where the
+    launcher refuses."""
+    nrow = rows.numel() // max(ncol, 1) if nrow is None else nrow
+    assert rows.numel() >= nrow * ncol and keys.numel() >= nrow and vals.numel() >= nrow and agree.numel() >= 9
+    assert all(t.is_contiguous() and t.element_size() == 4 for t in (nodes, heads, rows, keys, vals, agree))
+    assert nodes.numel() % 4 == 0 and heads.numel() % 4 == 0
+    _check_gpu(_load_gpu().ohx_probe_cluster_keys(nodes.data_ptr(), nodes.numel() * 4, heads.data_ptr(), heads.numel() // 4,
+                                                  num_feature, rows.data_ptr(), nrow, ncol, missing, ntrees, nsteps,
+                                                  zorder, keys.data_ptr(), vals.data_ptr(), agree.data_ptr(), num_cus,
+                                                  stream or None))
+
+
+def probe_sort_pairs(keys_a, keys_b, vals_a, vals_b, n: int, key_bits: int, stream: int = 0):
+    """sort_pairs_u32 (csrc/sort_pairs.hip) called the way the clustering pass calls it, on torch tensors of n 32-bit
+    words each; the stream has run on return.  -> (which, temp_bytes): vals_a (0) or vals_b (1) holds the result."""
+    assert all(t.is_contiguous() and t.element_size() == 4 and t.numel() >= n for t in (keys_a, keys_b, vals_a, vals_b))
+    which, temp = C.c_int(-1), C.c_uint64(0)
+    _check_gpu(_load_gpu().ohx_probe_sort_pairs(keys_a.data_ptr(), keys_b.data_ptr(), vals_a.data_ptr(), vals_b.data_ptr(),
+                                                n, key_bits, stream or None, C.byref(which), C.byref(temp)))
+    return which.value, temp.value
+
+
+def probe_detect_period(data, nrow: int, ncol: int, cols, kmax: int, verdict, stream: int = 0) -> None:
+    """launch_detect_period (csrc/kernels.hip) on torch tensors: `data` nrow x ncol float32, `verdict` len(cols) x
+    (kmax - 1) words that must be zero before; verdict[c][x] is then 0, 1 or 2 for the period nrow / (kmax - x)."""
+    cols = np.ascontiguousarray(cols, dtype=np.uint32)
+    assert 1 <= cols.size <= 4 and data.numel() >= nrow * ncol and verdict.numel() >= cols.size * max(kmax - 1, 0)
+    assert data.is_contiguous() and verdict.is_contiguous() and data.element_size() == 4 and verdict.element_size() == 4
+    _check_gpu(_load_gpu().ohx_probe_detect_period(data.data_ptr(), nrow, ncol, cols.ctypes.data, cols.size, kmax,
+                                                   verdict.data_ptr(), stream or None))
 
 
 def run1_state(grid, seed=17):
