@@ -1,4 +1,5 @@
-"""An exact audit of one grown tree, and the cases of tests/test_grow_hyper_cpu.py and tests/test_gpu_grow_hyper.py.
+"""An exact audit of one grown tree, and the cases of tests/test_grow_hyper_cpu.py and tests/test_gpu_grow_hyper.py (CASES,
+AUDITED) and of tests/test_grow_audit_cpu.py and tests/test_gpu_grow_audit.py (INLINE_CASES, COLSAMPLE_CASES, AUDITED_MORE).
 
 The audit shares no operation order with include/ohxgb.h.  It is written from the regularised objective itself,
 
@@ -38,15 +39,21 @@ Hd < 2 min_child_weight, or no candidate is admitted, or none has loss_k - e_k >
 as admitted where its exact child weights stand in the order c_f asks for; two weights closer than their bounds could stand
 the other way in doubles, and the audit would then ask more than the header does (no tree here meets that).
 
-On the restated trees of every case below the bounds pin 11217 of the 11219 float32 records looked at to a single value, and
-the restatements' own doubles err by at most 0.09 of the bound for the loss_chg of a split and 0.31 for a constrained split's
-child weights (tests/test_grow_hyper_cpu.py asserts that both stay below 1 and prints them)."""
+On the restated trees of every case of CASES the bounds pin 11217 of the 11219 float32 records looked at to a single value,
+and the restatements' own doubles err by at most 0.09 of the bound for the loss_chg of a split and 0.31 for a constrained
+split's child weights (tests/test_grow_hyper_cpu.py asserts that both stay below 1 and prints them).  On those of the later
+tables: 17217 of 17396, 0.09 and 0.17 (tests/test_grow_audit_cpu.py, which asserts 95 % a case, and prints).
+
+Under "ohx_colsample_bylevel" and "ohx_colsample_bynode" a node has features of its own: `kept` is then a callable, and the
+structure, the histograms and the candidates of a node are those of S_node(p).  The calls that count rows
+(OHXBoosterBoostTrees, ..Eval) are audited as unit weights: hq = 2^24 a row, min_child_weight = min_child_rows."""
 import functools
 import math
 from fractions import Fraction
 
 import numpy as np
 
+from tests import grow_colsample_support as K
 from tests import grow_deep_support as D
 from tests import grow_eval_support as E
 from tests import grow_mono_support as M
@@ -95,9 +102,10 @@ class Audit:
     """One tree against the rows it was grown on.
 
     bins uint8 [F][n] (grow_support.bin_rows); q int64 [n], hq uint64 [n]: the round's pairs of every row; in_bag bool [n] or
-    None; kept: the features the tree may split on, or None for all; cuts = (cut_ptr, cut_values); tree: the nine arrays, as
-    a restatement or as test_gpu_grow.held returns them; the hyper-parameters as the call takes them (float32);
-    constraints: an entry a feature, or fewer, or ()."""
+    None; kept: the features the tree may split on, or None for all, or a callable (p, depth) -> the features node p may
+    split on (S_node(p) under "ohx_colsample_bylevel" / "ohx_colsample_bynode"; `node_sets` makes one); cuts = (cut_ptr,
+    cut_values); tree: the nine arrays, as a restatement or as test_gpu_grow.held returns them; the hyper-parameters as the
+    call takes them (float32); constraints: an entry a feature, or fewer, or ()."""
 
     def __init__(self, bins, q, hq, in_bag, kept, cuts, tree, max_depth, eta, lam, gamma, mcw, alpha=0.0, m=0.0, constraints=()):
         self.bins = np.asarray(bins)
@@ -107,7 +115,8 @@ class Audit:
         self.hq = np.where(keep, np.asarray(hq, np.uint64), 0).astype(np.int64)       # (a row's hq < 2^32, a sum < 2^63)
         self.cut_ptr = [int(v) for v in cuts[0]]
         self.cut_values = np.asarray(cuts[1], F32)
-        self.kept = list(range(F)) if kept is None else [int(f) for f in kept]
+        self.kept = None if callable(kept) else (list(range(F)) if kept is None else [int(f) for f in kept])
+        self._kept_of, self._kept_at = kept if callable(kept) else None, {}
         self.t = {k: np.asarray(tree[k]).copy() for k in G.ARRAYS}
         self.size = len(self.t["left"])
         self.max_depth, self.eta = int(max_depth), F32(eta)
@@ -129,6 +138,14 @@ class Audit:
         self._intervals()
 
     # -- membership --
+
+    def kept_at(self, p):
+        """The features node p may split on, ascending: the tree's list, or the node's own set."""
+        if self._kept_of is None:
+            return self.kept
+        if p not in self._kept_at:
+            self._kept_at[p] = sorted(int(f) for f in self._kept_of(p, self.depth[p]))
+        return self._kept_at[p]
 
     def _structure(self):
         """rows, G, H, depth, j (the cut index of a split) of every node, by walking the binned rows through the tree."""
@@ -157,9 +174,9 @@ class Audit:
                     self.found.append((c, "structure", f"parent {int(t['parent'][c])} under {p}"))
             f = int(t["feature"][p])
             cuts = self.cut_values[self.cut_ptr[f]:self.cut_ptr[f + 1]] if f < len(self.cut_ptr) - 1 else self.cut_values[:0]
-            at = np.flatnonzero(cuts.view(np.uint32) == np.asarray(t["value"][p], F32).view(np.uint32)) if f in self.kept else []
+            at = np.flatnonzero(cuts.view(np.uint32) == np.asarray(t["value"][p], F32).view(np.uint32)) if f in self.kept_at(p) else []
             if len(at) != 1:
-                self.found.append((p, "structure", f"{t['value'][p]!r} is no cut of feature {f}, or the tree may not split on it"))
+                self.found.append((p, "structure", f"{t['value'][p]!r} is no cut of feature {f}, or the node may not split on it"))
                 self.broken.add(p)
                 continue
             self.j[p] = int(at[0])
@@ -248,7 +265,7 @@ class Audit:
         rows = self.rows[p]
         F = self.bins.shape[0]
         Gh, Hh = np.zeros((F, 256), np.int64), np.zeros((F, 256), np.int64)
-        for f in self.kept:
+        for f in self.kept_at(p):
             if self.cut_ptr[f + 1] > self.cut_ptr[f]:
                 np.add.at(Gh[f], self.bins[f, rows], self.q[rows])
                 np.add.at(Hh[f], self.bins[f, rows], self.hq[rows])
@@ -262,7 +279,7 @@ class Audit:
         Gp, Hp, lo, hi = self.G[p], self.H[p], self.lo[p], self.hi[p]
         Gh, Hh = self.histograms(p)
         out = []
-        for f in self.kept:
+        for f in self.kept_at(p):
             c = self.cons[f]
             GLb = HLb = 0
             Gm, Hm = Gh[f][G.MISSING_BIN], Hh[f][G.MISSING_BIN]
@@ -318,7 +335,7 @@ class Audit:
 
     def violations(self):
         """-> a list of (node, check, text), empty for a sound tree.  The checks:
-        structure    the children, the parents, and a split value that is a cut of a feature the tree may split on
+        structure    the children, the parents, and a split value that is a cut of a feature the node may split on
         sum_hess     == float32(H * 2^-24), H the sum over the rows that reach the node
         base_weight  the float32 of a double within the bound of the exact minimiser of obj over the node's admissible set
         leaf         value == base_weight * eta, one float32 multiply
@@ -439,24 +456,65 @@ def restated(kind, policy, setting, seed=SEED, n=None):
     return _restated(kind, policy, tuple(sorted(hyper(kind, setting).items())), seed, n or ROWS[kind])
 
 
-def round_inputs(kind, policy, setting, x, y, w, cuts, trees, r):
-    """What tree r of a call was grown on -> the keyword arguments of Audit without the tree: the pairs from the margins
-    after the trees before r (walked on the host), the bag and the list of the round, the hyper-parameters."""
-    kw = hyper(kind, setting)
+def node_sets(seed, i, tree_list, bylevel, bynode):
+    """-> the callable (p, depth) -> S_node(p) of tree i, for Audit(kept=...): grow_colsample_support's level and node lists
+    over the tree's list (a level's list is drawn once)."""
+    levels = {}
+
+    def kept(p, d):
+        if d not in levels:
+            levels[d] = K.level_features(seed, i, d, tree_list, bylevel)
+        return K.node_features(seed, i, p, levels[d], bynode)
+
+    return kept
+
+
+def round_inputs(kind, policy, setting, x, y, w, cuts, trees, r, objective="pseudohuber", bylevel=1.0, bynode=1.0, tree0=0,
+                 count_hess=False):
+    """What tree r of a call was grown on -> the keyword arguments of Audit without the tree: the pairs of `objective` from
+    the margins after the trees before r (walked on the host), the bag and the list of round i = tree0 + r, the node sets
+    where a fraction is below 1, the hyper-parameters.  count_hess: the plain and the Eval call, which count rows: unit
+    weights (hq = 2^24 a row), no bag, every feature, and min_child_rows where the others take min_child_weight."""
+    kw = hyper_more(kind, setting)
     alpha, m, cons = POLICIES[policy]
+    nfeat, i = np.asarray(x).shape[1], tree0 + r
     pred = np.full(len(y), O.BASE, F32)
     for t in trees[:r]:
         pred = pred + E.walk(t, x, float("nan"))
         assert pred.dtype == F32
-    q, hq = O.pairs("pseudohuber", SLOPE, pred, y, w)
-    return dict(bins=G.bin_rows(x, float("nan"), cuts, NFEAT), q=q, hq=hq, in_bag=P.bag(kw.get("seed", 0), r, len(y), kw.get("subsample", 1.0)),
-                kept=P.features(kw.get("seed", 0), r, NFEAT, kw.get("colsample_bytree", 1.0)), cuts=cuts, max_depth=kw["max_depth"],
-                eta=kw["eta"], lam=kw["reg_lambda"], gamma=kw["gamma"], mcw=kw["min_child_weight"], alpha=alpha, m=m, constraints=cons)
+    q, hq = O.pairs(objective, SLOPE, pred, y, None if count_hess else w)
+    mcw = float(kw["min_child_rows"]) if count_hess else kw["min_child_weight"]
+    kept = P.features(kw.get("seed", 0), i, nfeat, kw.get("colsample_bytree", 1.0))
+    if bylevel != 1.0 or bynode != 1.0:
+        kept = node_sets(kw.get("seed", 0), i, kept, bylevel, bynode)
+    return dict(bins=G.bin_rows(x, float("nan"), cuts, nfeat), q=q, hq=hq, in_bag=P.bag(kw.get("seed", 0), i, len(y), kw.get("subsample", 1.0)),
+                kept=kept, cuts=cuts, max_depth=kw["max_depth"], eta=kw["eta"], lam=kw["reg_lambda"], gamma=kw["gamma"], mcw=mcw,
+                alpha=alpha, m=m, constraints=cons)
 
 
-def audits(kind, policy, setting, x, y, w, cuts, trees):
-    """An Audit a tree of a call's new trees (restated, or read back from the library)."""
-    return [Audit(tree=t, **round_inputs(kind, policy, setting, x, y, w, cuts, trees, r)) for r, t in enumerate(trees)]
+def audits(kind, policy, setting, x, y, w, cuts, trees, **more):
+    """An Audit a tree of a call's new trees (restated, or read back from the library).  more: round_inputs' own."""
+    return [Audit(tree=t, **round_inputs(kind, policy, setting, x, y, w, cuts, trees, r, **more)) for r, t in enumerate(trees)]
+
+
+def decided(a):
+    """How many split nodes of the Audit `a` chose a candidate whose exact loss_chg exceeds that of the best candidate with
+    another (f, j, dl) by more than the sum of the two bounds: the nodes at which a wrong choice would be reported.  At the
+    others the best two tie within the bounds (mostly exactly: two cuts with no row between them), and their order is the
+    restatement's business."""
+    n = 0
+    for p in a.order:
+        if a.t["left"][p] < 0 or p in a.broken or not a.evaluated(p):
+            continue
+        key, cands = a.split_of(p), a.candidates(p)
+        mine = [c for c in cands if c[1:4] == key]
+        others = [c for c in cands if c[1:4] != key]
+        if mine and others:
+            best = max(others, key=functools.cmp_to_key(lambda u, v: _cmp(u[0], v[0])))
+            parent = a.parent_gain(p)
+            (loss, e), (other, eo) = a.loss(p, mine[0], parent), a.loss(p, best, parent)
+            n += int(loss - other > Fraction(e + eo))
+    return n
 
 
 # ---- what a case reaches, from the restatement's own policy ----
@@ -584,3 +642,226 @@ def refusal_case(kind):
                         seed=sampling["draw_seed"], tree0=1)
 
     return x, y, w, cuts, ev, first, again
+
+
+# ---- squared error, the bag and the list, and the node sets: the cases of tests/test_grow_audit_cpu.py and
+# ---- tests/test_gpu_grow_audit.py (as above, what follows is the restatements' business) ----
+
+COUNT_KINDS = ("plain", "eval")                       # OHXBoosterBoostTrees and ..Eval count rows: GrowCountHess
+INLINE_KINDS = COUNT_KINDS + tuple(ROWS)
+ROWS_MORE = dict(ROWS, plain=1300, eval=1300)
+SETTINGS_MORE = dict(SETTINGS, **{"lambda0.5": dict(reg_lambda=0.5)})
+COL_NFEAT, COL_FRACTIONS = 8, (0.75, 0.67)            # of a tree's four features a level keeps three, and a node two of those
+NO_FRACTIONS = (1.0, 1.0)
+COL_SEED = 29                                         # (tests/test_gpu_grow_colsample.py draws with it: check_c2)
+
+
+def hyper_more(kind, setting):
+    """`hyper` for the six kinds and SETTINGS_MORE.  The plain and the Eval call take min_child_rows, 1 unless the setting
+    says otherwise, where the others take min_child_weight."""
+    change = dict(SETTINGS_MORE[setting] if isinstance(setting, str) else setting)
+    if kind not in COUNT_KINDS:
+        return hyper(kind, change)
+    kw = dict(eta=0.125, reg_lambda=1.0, min_child_rows=1, max_depth=6, gamma=0.0, rounds=ROUNDS)
+    if "min_child_weight" in change:
+        change["min_child_rows"] = int(change.pop("min_child_weight"))
+    kw.update(change)
+    return kw
+
+
+# A case: (kind, form, objective, policy, setting, seed, (bylevel, bynode)).
+def nfeat_of(case):
+    """8 features under the fractions, so that n_lvl and n_node shrink; 4 under constraints, CONSTRAINTS' own."""
+    return COL_NFEAT if case[6] != NO_FRACTIONS and not POLICIES[case[3]][2] else NFEAT
+
+
+def case_hyper(case):
+    """The keyword arguments of the binding for a case.  Under the fractions the draws take COL_SEED, and under constraints
+    the tree keeps all four features."""
+    kw = hyper_more(case[0], case[4])
+    if case[6] != NO_FRACTIONS:
+        kw["seed"] = COL_SEED
+        if POLICIES[case[3]][2]:
+            kw["colsample_bytree"] = 1.0
+    return kw
+
+
+def more_inputs(case):
+    """The keyword arguments of round_inputs / audits that a case adds."""
+    return dict(objective=case[2], bylevel=case[6][0], bynode=case[6][1], count_hess=case[0] in COUNT_KINDS)
+
+
+@functools.lru_cache(maxsize=None)
+def _restated_more(kind, objective, policy, items, seed, n, nfeat, fractions):
+    kw = dict(items)
+    alpha, m, cons = POLICIES[policy]
+    if kind in COUNT_KINDS:
+        assert objective == "squarederror" and policy == "pairs" and fractions == NO_FRACTIONS
+        x, y, _, cuts, ev = O.inputs(n, seed, nfeat, BINS, HELD)
+        pk = dict(rounds=kw["rounds"], max_depth=kw["max_depth"], eta=kw["eta"], lam=kw["reg_lambda"], gamma=kw["gamma"],
+                  min_child_rows=kw["min_child_rows"])
+        if kind == "plain":
+            want = G.boost(np.full(n, O.BASE, F32), x, float("nan"), y, cuts, nfeat, **pk)
+            return x, y, None, cuts, None, dict(want, all_trees=want["trees"])
+        ev = ev[:3]
+        return x, y, None, cuts, ev, E.boost_eval(np.full(n, O.BASE, F32), x, float("nan"), y, cuts, nfeat, eval_set=ev,
+                                                  eval_pred=np.full(HELD, O.BASE, F32), **pk)
+    common = dict(bins=BINS, nfeat=nfeat, rounds=kw["rounds"], held_out=HELD, subsample=kw.get("subsample", 1.0),
+                  colsample=kw.get("colsample_bytree", 1.0), draw_seed=kw.get("seed", 0), lam=kw["reg_lambda"],
+                  mcw=kw["min_child_weight"], eta=kw["eta"], gamma=kw["gamma"])
+    if fractions != NO_FRACTIONS:
+        return K.restated(fractions[0], fractions[1], tuple(cons), objective, SLOPE, alpha, m, "rmse", n, seed, kw["max_depth"], **common)
+    if policy == "pairs":
+        return O.restated(objective, SLOPE, n, seed, kw["max_depth"], **common)
+    if policy == "regularised":
+        return RG.restated(objective, SLOPE, alpha, m, "rmse", n, seed, kw["max_depth"], **common)
+    return M.restated(cons, objective, SLOPE, alpha, m, "rmse", n, seed, kw["max_depth"], **common)
+
+
+def restated_more(case, setting=None):
+    """-> (x, y, w, cuts, ev, the dict of the boost call) of the case's own restatement - grow_support.boost,
+    grow_eval_support.boost_eval, grow_objective_support.restated (which is boost_weighted, boost_sampled, boost_deep and
+    boost_deep_sampled under squared error), grow_reg_support's, grow_mono_support's or grow_colsample_support's - computed
+    once (not to be changed).  w is None and ev has three entries, or is None, for the calls that count rows.
+    setting: another one than the case's."""
+    kind, _, objective, policy, _, seed, fractions = case
+    if setting is not None:
+        case = case[:4] + (setting,) + case[5:]
+    return _restated_more(kind, objective, policy, tuple(sorted(case_hyper(case).items())), seed, ROWS_MORE[kind], nfeat_of(case), fractions)
+
+
+def audits_more(case, x, y, w, cuts, trees):
+    """An Audit a tree of the case's call (restated trees, or the library's)."""
+    return audits(case[0], case[3], case_hyper(case), x, y, w, cuts, trees, **more_inputs(case))
+
+
+def best_split_more(case):
+    """As restated_best_split; for the calls that count rows grow_support.best_split over the histograms of rows."""
+    if case[0] not in COUNT_KINDS:
+        return restated_best_split(case[3])
+
+    def best(Gh, Hh, nc, Gp, Hp, lam, mcr, lo, hi):
+        assert Hp % ONE == 0 and not np.any(Hh % np.uint64(ONE))
+        found = G.best_split(Gh, (Hh // np.uint64(ONE)).astype(np.int64), nc, Gp, Hp // ONE, lam, mcr)
+        return None if found is None else found[:5] + (found[5] * ONE,)
+
+    return best
+
+
+@functools.lru_cache(maxsize=None)
+def profile_more(case):
+    """`profile` for a case of the tables below; a node's candidates are those of its own features."""
+    kind = case[0]
+    x, y, w, cuts, ev, want = restated_more(case)
+    kw = case_hyper(case)
+    count = kind in COUNT_KINDS
+    mcw = kw["min_child_rows"] if count else kw["min_child_weight"]
+    floor = 1 if count else 0.0            # (the least a setting can ask: a child of a row, or of any hessian at all)
+    best_of = best_split_more(case)
+    out = []
+    for a in audits_more(case, x, y, w, cuts, want["all_trees"]):
+        t = want["all_trees"][len(out)]
+        intervals = t.get("intervals", [(-math.inf, math.inf)] * a.size)
+        nodes = []
+        for p in range(a.size):
+            lo, hi = intervals[p]
+            nd = dict(level=a.depth[p], split=bool(t["left"][p] >= 0), best=None, free_best=None, narrowed=lo > -math.inf or hi < math.inf,
+                      evaluates=W.hess(a.H[p]) >= 2.0 * float(F32(mcw)))
+            if a.depth[p] < kw["max_depth"] and (nd["evaluates"] or not count):
+                ncuts = [(a.cut_ptr[f + 1] - a.cut_ptr[f]) if f in a.kept_at(p) else 0 for f in range(a.bins.shape[0])]
+                Gh, Hh = (np.asarray(h, dtype) for h, dtype in zip(a.histograms(p), (np.int64, np.uint64)))
+                nd["best"] = best_of(Gh, Hh, ncuts, a.G[p], a.H[p], kw["reg_lambda"], mcw, lo, hi)
+                if mcw > floor:
+                    nd["free_best"] = best_of(Gh, Hh, ncuts, a.G[p], a.H[p], kw["reg_lambda"], floor, lo, hi)
+            nodes.append(nd)
+        out.append(nodes)
+    return out
+
+
+def reaches_more(case):
+    """`reaches` for a case of the tables below, from the restatement alone; under the fractions also that a node's best
+    candidate over the tree's features is not its own and, with gamma > 0, that such a node is closed for it."""
+    kind, _, objective, policy, setting, seed, fractions = case
+    kw = case_hyper(case)
+    count = kind in COUNT_KINDS
+    *_, want = restated_more(case)
+    *_, plain = restated_more(case, dict(max_depth=kw["max_depth"]))
+    assert len(want["all_trees"]) == kw["rounds"] and not M.same_trees(want["all_trees"], plain["all_trees"]), "the setting changes a tree"
+    trees = profile_more(case)
+    gamma = float(F32(kw["gamma"]))
+    mcw, floor = (kw["min_child_rows"], 1) if count else (kw["min_child_weight"], 0.0)
+    levels = [[[nd for nd in nodes if nd["level"] == d] for d in range(kw["max_depth"])] for nodes in trees]
+
+    def closed_by_gamma(nd):
+        return not nd["split"] and nd["best"] is not None
+
+    def mixed(level):
+        return any(nd["split"] for nd in level) and any(closed_by_gamma(nd) for nd in level)
+
+    if gamma > 0:
+        assert any(mixed(level) for tree in levels for level in tree), "a level with a split beside a node that gamma closes"
+        for nodes in trees:
+            assert all(not nd["best"][0] > gamma for nd in nodes if closed_by_gamma(nd))
+        if POLICIES[policy][2]:
+            assert any(closed_by_gamma(nd) and nd["narrowed"] for nodes in trees for nd in nodes), "gamma closes a node with an interval"
+    if mcw > floor:
+        inner = [nd for nodes in trees for nd in nodes if nd["level"] < kw["max_depth"]]
+        assert any(not nd["evaluates"] for nd in inner), "a node with Hd < 2 min_child_weight (or fewer rows than 2 min_child_rows)"
+        assert any(nd["split"] and nd["best"][1:4] != nd["free_best"][1:4] for nd in inner), "the child minimum moves a split"
+    if "deep" in kind:
+        assert any(D.depth_of(t) > 8 and D.levels(t)[8][1] > 0 for t in want["all_trees"]), "level 8 splits"
+        if gamma > 0 or mcw > floor:
+            assert any(any(nd["split"] for nd in level) and any(not nd["split"] for nd in level) for tree in levels for level in tree[8:]), \
+                "a deep level with closed nodes beside splits"
+    if fractions != NO_FRACTIONS:
+        assert K.narrowed(want["draws"]) >= 1, "a node whose best candidate over the tree's features is not its own"
+        if gamma > 0:
+            assert any(e["free"] is not None and e["feature"] is None for log in want["draws"] for e in log), \
+                "a node whose free best candidate would split, closed because none of its own columns' passes gamma"
+    return want
+
+
+def _inline(kind, form, setting, seed=SEED):
+    return (kind, form, "squarederror", "pairs", setting, seed, NO_FRACTIONS)
+
+
+def _cols(kind, form, objective, policy, setting, seed=SEED):
+    return (kind, form, objective, policy, setting, seed, COL_FRACTIONS)
+
+
+# Seeds other than SEED were chosen as 284 was above: at 283 and 284 gamma = 0.25 closes no node of the row-counting trees
+# beside a split, at 285 it does; under the fractions the sampled cases reach theirs at 284 and 286, and the deep constrained
+# one a split that min_child_weight moves at 284.
+# Squared error with no handle parameter set: the inline kernels.  Every (kind, form) pair occurs, and every setting on a
+# kind that counts rows and on one with fixed-point hessians; deep_combination on both deep kinds.
+INLINE_CASES = (
+    _inline("plain", "host", "gamma0.5"), _inline("eval", "device", "gamma2"), _inline("plain", "device", "mcw8"),
+    _inline("eval", "host", "mcw40"), _inline("plain", "host", "lambda0"), _inline("eval", "device", "lambda0.5"),
+    _inline("plain", "device", "eta1"), _inline("eval", "host", "eta1/32"), _inline("plain", "host", "combination", 285),
+    _inline("eval", "device", "combination", 285),
+    _inline("weighted", "host", "gamma0.5"), _inline("sampled", "device", "gamma2"), _inline("weighted", "device", "mcw8"),
+    _inline("deep", "host", "mcw40"), _inline("sampled", "host", "lambda0"), _inline("weighted", "host", "lambda0.5"),
+    _inline("sampled", "device", "eta1"), _inline("deep_sampled", "device", "eta1/32"), _inline("weighted", "device", "combination"),
+    _inline("sampled", "host", "combination"), _inline("deep", "device", "deep_combination"),
+    _inline("deep_sampled", "host", "deep_combination"))
+# The level and the node lists off kind_kw's point: each policy under pseudo-Huber at a combination, squared error on either
+# kind, and gamma2 and mcw8 once each.
+COLSAMPLE_CASES = (
+    _cols("sampled", "host", "pseudohuber", "pairs", "combination", 286),
+    _cols("deep_sampled", "device", "pseudohuber", "regularised", "deep_combination"),
+    _cols("sampled", "device", "pseudohuber", "constrained", "combination"),
+    _cols("deep_sampled", "host", "pseudohuber", "constrained_regularised", "deep_combination", 284),
+    _cols("sampled", "device", "squarederror", "pairs", "combination", 284),
+    _cols("deep_sampled", "host", "squarederror", "pairs", "deep_combination"),
+    _cols("sampled", "host", "pseudohuber", "pairs", "gamma2"),
+    _cols("deep_sampled", "device", "pseudohuber", "pairs", "mcw8"))
+# What the GPU tests audit beyond AUDITED: every inline kind at its combination; the bag and the tree's list under
+# pseudo-Huber, free and constrained (the cases of CASES, which the audit did not reach); every node-set case at a combination.
+AUDITED_MORE = tuple(c for c in INLINE_CASES if "combination" in c[4]) \
+    + tuple((k, f, "pseudohuber", p, s, seed, NO_FRACTIONS) for k, f, p, s, seed in CASES
+            if "sampled" in k and "combination" in s and p in ("pairs", "constrained_regularised")) \
+    + tuple(c for c in COLSAMPLE_CASES if "combination" in c[4])
+
+
+def more_id(case):
+    return "-".join(str(v) for v in case[:6]) + ("" if case[6] == NO_FRACTIONS else "-%gx%g" % case[6])

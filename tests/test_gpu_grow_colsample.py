@@ -9,7 +9,10 @@ says so, so the margin a restatement starts from is the model's base.  What a ca
 restatement before the GPU is asked: above all a node whose best candidate over the tree's features lies outside the node's
 own (grow_colsample_support.narrowed) - without one the case would pass on the code path of a call without the two parameters.  A row
 alone and a feature alone can have no such node (nothing splits; nothing is drawn): those two cases say so.  C2 is computed
-from the trees the library returns and the restated draws alone, for every case."""
+from the trees the library returns and the restated draws alone, for every case.  Every tree here grows at one point of
+eta, lambda, min_child_weight and gamma (call_kw), and C2 asks only that a split's feature is the node's own: gamma > 0,
+min_child_weight > 0 and lambda 0 under the fractions, and whether a split is the best of the node's own columns, asked
+of the library's tree by the exact audit, are tests/test_gpu_grow_audit.py's."""
 import ctypes as C
 
 import numpy as np

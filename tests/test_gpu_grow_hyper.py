@@ -10,7 +10,9 @@ The expected values are the restatements' (tests/grow_objective_support.py, grow
 a case is meant to reach - a level where gamma closes a node beside one that splits, a node closed by Hd < 2 min_child_weight,
 a split that min_child_weight moves, level 8 - is asserted from the restatement before the GPU is asked.  A second check does
 not share the restatements' origin: the exact audit of tests/grow_audit_support.py over the trees the library grew, with the
-pairs of a round made from the margins of the library's own earlier trees."""
+pairs of a round made from the margins of the library's own earlier trees.  Left out here and found in
+tests/test_gpu_grow_audit.py: squared error off the defaults (the inline kernels, the plain and the Eval call among them),
+and the audit of the bagged kinds and of the node sets of column sampling by level and by node."""
 import ctypes as C
 
 import numpy as np
