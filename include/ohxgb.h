@@ -202,16 +202,25 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *   "ohx_cat_kernel"  auto | direct : boosters with categorical splits: direct = margins by the kernel without LDS
  *                     too (auto: the tile kernel where a block's tiles fit a CU's LDS, up to 160 features)
  *   "ohx_device"      HIP device ordinal for this booster
- *   "ohx_objective"   squarederror (default) | pseudohuber : the loss the OHXBoosterBoostTrees* calls fit, as the
+ *   "ohx_objective"   squarederror (default) | pseudohuber | quantile : the loss the OHXBoosterBoostTrees* calls fit, as the
  *                     (gradient, hessian) pair of a row (defined bit for bit with OHXBoosterBoostTreesWeighted below;
  *                     docs/26_objectives.md).  Any other value returns -1 and the message names "ohx_objective".  Kept on
  *                     the handle, written into no model file; the forest's own objective name is not changed.  The name
  *                     "objective" without the prefix is an xgboost parameter and is ignored.  With pseudohuber the calls
  *                     that keep row counts, not hessian sums - OHXBoosterBoostTrees[Device], OHXBoosterBoostTreesEval[Device]
  *                     - and OHXBoosterRefitLeaves[Device] return -1 before anything is enqueued; the message names
- *                     OHXBoosterBoostTreesWeighted
+ *                     OHXBoosterBoostTreesWeighted.  With quantile (the pinball loss at "ohx_quantile_alpha", with leaves that
+ *                     are weighted quantiles of residuals; docs/32_quantile_objective.md) the same calls are refused the same
+ *                     way, and so are OHXBoosterBoostTreesDeep[Device] and ...DeepSampled[Device] at any depth and every
+ *                     setting that replaces the split kernels - ohx_reg_alpha or ohx_max_delta_step not 0, a non-zero
+ *                     ohx_monotone_constraints entry, ohx_colsample_bylevel or ohx_colsample_bynode below 1; each message
+ *                     names what to call or unset.  It acts on OHXBoosterBoostTreesWeighted[Device] and ...Sampled[Device]
  *   "ohx_huber_slope" the slope delta of pseudohuber: a decimal number, finite, 2^-10 <= delta <= 256 (default 1).
  *                     Anything else returns -1 and the message names "ohx_huber_slope"
+ *   "ohx_quantile_alpha" alpha of the quantile objective and of the quantile metric: a decimal number, finite,
+ *                     2^-10 <= alpha <= 1 - 2^-10 (default 0.5), parsed as "ohx_huber_slope" is.  Anything else ("", "0",
+ *                     "1", "nan", "1x", "0.5 ", "-0.1") returns -1 and the message names "ohx_quantile_alpha".  Kept on the
+ *                     handle, written into no model file
  *   "ohx_grow_pairs"  auto (default) | on : for tests and measurement.  on = squared error goes through the pair kernels
  *                     too (a pass that writes every row's pair once a round, and histogram kernels that read it); auto =
  *                     only an objective that needs them does.  The same bits either way.  With none of the three set
@@ -221,9 +230,9 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *                     gain and the leaf of OHXBoosterBoostTreesWeighted, ...Sampled, ...Deep and ...DeepSampled as defined
  *                     with the Weighted call below (docs/27_regularisation_and_metrics.md).  Anything else ("", "1x",
  *                     "1 ", nan, inf, a negative number) returns -1 and the message names the parameter
- *   "ohx_eval_metric" rmse (default) | mae | pseudohuber : what train_rmse[] and eval_rmse[] of those four calls hold and
+ *   "ohx_eval_metric" rmse (default) | mae | pseudohuber | quantile : what train_rmse[] and eval_rmse[] of those four calls hold and
  *                     what their stop rule compares (defined with the Weighted call below; delta is "ohx_huber_slope"
- *                     whatever the objective).  Any other value returns -1 and the message names "ohx_eval_metric".
+ *                     and alpha "ohx_quantile_alpha" whatever the objective).  Any other value returns -1 and the message names "ohx_eval_metric".
  *                     All three are kept on the handle and written into no model file; the names without the prefix are
  *                     xgboost's and stay ignored.  While ohx_reg_alpha or ohx_max_delta_step is not 0 or the metric is
  *                     not rmse, OHXBoosterBoostTrees[Device] and OHXBoosterBoostTreesEval[Device] (row counts and
@@ -763,6 +772,27 @@ int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, con
  * (every in-bag hq rounds to 0: a leaf would divide by lambda alone) is refused, the message says "hessian", and the
  * forest and every output are untouched, as for "bag".  The same holds for OHXBoosterBoostTreesSampled, ...Deep and
  * ...DeepSampled.
+ * The quantile objective ("ohx_objective" = quantile, alpha = "ohx_quantile_alpha" as a float32).
+ *   alpha_q = (uint32) rint(alpha * 2^24), so 2^14 <= alpha_q <= 2^24 - 2^14; everything below is defined on alpha_q.
+ * Pair: z, w and their refusals as above;
+ *   quantile:      g = (z >= 0) ? 1.0f - alpha : -alpha; h = 1.0f
+ * in float32; gw, hw, q and hq as above, so hq = rint(w * 2^24) and a leaf's H is the weight it holds.  A row out of the
+ * bag, or one that raised a flag, has the pair (0, 0) as above.  Structure: the tree is grown from these pairs exactly as
+ * above - histograms, candidates, their order, lambda, gamma, min_child_weight, the bag and colsample_bytree.  Leaf: after
+ * the last level every leaf node p of the new tree is set as follows.  The rows that count are those with pos == p and
+ * hq_i > 0 (in the bag, unflagged and of non-zero weight).  For each, r_i = y_i - pred_i in float32 with pred as at the
+ * start of the round (this is -z bit for bit), and k_i = key(bits(r_i)), where key maps a float's bits to an unsigned
+ * integer in the order of the floats: -0.0f counts as +0.0f, u = bits; key = u ^ ((u >> 31) ? 0xFFFFFFFF : 0x80000000).
+ *   W_p = sum hq_i;   C_p(k) = sum of hq_i over k_i <= k
+ *   k*  = the smallest key with alpha_q * W_p <= 2^24 * C_p(k*)      exact integers (unsigned __int128; both sides < 2^88)
+ *   q_p = the float whose key is k*;   value = q_p * eta  (one float32 multiply)
+ * The leaf is the lower weighted alpha-quantile of the leaf's residuals, with no interpolation; it depends on neither the
+ * order of the rows nor the launch shape.  base_weight, sum_hess, G and H of the record stay as the split left them (the
+ * Newton values, as xgboost's adaptive leaf leaves them).  A leaf with W_p == 0 keeps its record; only a weightless root
+ * of the Weighted call is one.  The held-out walk, the assembled tree, the saved model, pred and both metric arrays carry
+ * the quantile leaves.  This is xgboost's adaptive leaf (reg:quantileerror since 2.0) without its interpolation; parity
+ * with libxgboost is not pinned, the text above is the definition.  Refused under the quantile objective, before anything
+ * is enqueued and with the forest and every output untouched: the calls named with "ohx_objective" above.
  * Regularisation ("ohx_reg_alpha" = alpha, "ohx_max_delta_step" = m of XGBoosterSetParam).  What is stated above is
  * alpha = 0 and m = 0.  In general, with Gd = (double)G * 2^-24, Hd = (double)H * 2^-24, D = Hd + (double)lambda and alpha
  * and m widened to double; every operation is a double operation and rounds once, nothing is fused:
@@ -810,11 +840,13 @@ int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, con
  *   mae          sq = |e|
  *   pseudohuber  d2 = delta * delta; z2 = z * z; s = sqrtf(1.0f + z2 / d2); mf = z2 / (1.0f + s);   float32, IEEE, not fused
  *                sq = (uint64) rint(mf * 2^24)
+ *   quantile     sq = |e| * (z < 0 ? alpha_q : 2^24 - alpha_q),  alpha_q of "ohx_quantile_alpha" as above;  sq < 2^56
  * mf is delta^2 (s - 1) written without a cancellation at small z; mf <= delta |z| < 2^16, so sq < 2^40, and a denormal z2
  * or mf gives sq = 0 whether or not denormals are flushed.  S = sum hq * sq is exact and W is as above.  train_rmse[t] and
  * eval_rmse[t] - the arrays keep their names - then hold, for mae and pseudohuber, ((double)S_t * 2^-48) / ((double)W *
  * 2^-24), both conversions from unsigned __int128 and no square root: the weighted mean absolute error, and the weighted
- * mean of delta^2 (sqrt(1 + z^2 / delta^2) - 1).  The stop rule compares the exact S_eval[t] of the metric, strictly, as
+ * mean of delta^2 (sqrt(1 + z^2 / delta^2) - 1).  For quantile they hold ((double)S_t * 2^-72) / ((double)W * 2^-24), the
+ * weighted mean pinball loss at alpha, likewise without a square root.  The stop rule compares the exact S_eval[t] of the metric, strictly, as
  * above.  The same holds for OHXBoosterBoostTreesSampled, ...Deep and ...DeepSampled.
  * Everything else is OHXBoosterBoostTreesEval's: all or nothing; what a success drops; patience == 0 waits once, at the
  * end, and patience >= 1 waits once a round; eval_dmat == NULL works as there, and eval_weights must then be NULL.  Not

@@ -567,11 +567,13 @@ class Booster:
             patience, train.ctypes.data, held.ctypes.data, C.byref(run), C.byref(best), C.byref(n), stream or None))
         return self._eval_result(train, held, run, best, n, ed is not None)
 
-    def _set_objective(self, objective, huber_slope, reg_alpha=None, max_delta_step=None, eval_metric=None,
+    def _set_objective(self, objective, huber_slope, quantile_alpha=None, reg_alpha=None, max_delta_step=None, eval_metric=None,
                        monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> None:
-        """objective= and huber_slope= of the boost_trees_* methods: "squarederror" or "pseudohuber" and its slope, set on
-        the handle by set_param("ohx_objective") and set_param("ohx_huber_slope") and kept for later calls (they go into
-        no model file).  reg_alpha=, max_delta_step= and eval_metric= ("rmse", "mae" or "pseudohuber": what the two
+        """objective= and huber_slope= of the boost_trees_* methods: "squarederror", "pseudohuber" and its slope, or
+        "quantile", set on the handle by set_param("ohx_objective") and set_param("ohx_huber_slope") and kept for later
+        calls (they go into no model file).  quantile_alpha= is alpha of the quantile objective and metric, set by
+        "ohx_quantile_alpha"; the calls that refuse the quantile objective surface the refusal.
+        reg_alpha=, max_delta_step= and eval_metric= ("rmse", "mae", "pseudohuber" or "quantile": what the two
         metric arrays hold and the stop rule compares) likewise, by "ohx_reg_alpha", "ohx_max_delta_step" and
         "ohx_eval_metric".  monotone_constraints= is a sequence of ints in {-1, 0, 1}, one a feature from feature 0 on, or
         the string itself ("(1,0,-1)"), set by "ohx_monotone_constraints"; () is none.  colsample_bylevel= and
@@ -595,16 +597,18 @@ class Booster:
             self.set_param("ohx_objective", objective)
         if huber_slope is not None:
             self.set_param("ohx_huber_slope", repr(float(huber_slope)))
+        if quantile_alpha is not None:
+            self.set_param("ohx_quantile_alpha", repr(float(quantile_alpha)))
 
     def boost_trees_weighted(self, dmat: DMatrix, labels, cuts, weights=None, eval_set=None, rounds: int = 1,
                              max_depth: int = 6, eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
                              min_child_weight: float = 1.0, patience: int = 0,
-                             *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
+                             *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
                              eval_metric=None, monotone_constraints=None) -> dict:
         """OHXBoosterBoostTreesWeighted: boost_trees_eval with a weight per row (0 <= w < 256; None: all 1) in the
         histograms, the leaves and both RMSEs.  eval_set = (DMatrix, labels[, weights]).  min_child_weight stands where
         min_child_rows stood.  -> the dict of boost_trees_eval."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
         return self._boost_weighted("OHXBoosterBoostTreesWeighted", dmat, labels, cuts, weights, eval_set, rounds, max_depth,
                                     eta, reg_lambda, gamma, min_child_weight, patience)
 
@@ -638,12 +642,12 @@ class Booster:
                                     eval_set=None, rounds: int = 1, max_depth: int = 6, eta: float = 0.3,
                                     reg_lambda: float = 1.0, gamma: float = 0.0, min_child_weight: float = 1.0,
                                     patience: int = 0, stream: int = 0,
-                                    *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
+                                    *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
                              eval_metric=None, monotone_constraints=None) -> dict:
         """The same with labels and weights in device memory: labels_ptr, weights_ptr (0: all 1) and
         eval_set = (DMatrix, eval_labels_ptr, eval_nlabel[, eval_weights_ptr]) are torch data_ptr()s of float32 ready
         on `stream`; the cuts stay host arrays.  Enqueues on `stream`; waits as boost_trees_eval_device (not capturable)."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
         return self._boost_weighted_device("OHXBoosterBoostTreesWeightedDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
                                            eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, patience,
                                            stream)
@@ -666,12 +670,12 @@ class Booster:
     def boost_trees_deep(self, dmat: DMatrix, labels, cuts, weights=None, eval_set=None, rounds: int = 1,
                          max_depth: int = 12, eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
                          min_child_weight: float = 1.0, patience: int = 0,
-                         *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
+                         *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
                              eval_metric=None, monotone_constraints=None) -> dict:
         """OHXBoosterBoostTreesDeep: boost_trees_weighted with max_depth up to 18.  From level 8 on a level's histograms
         are kept in HBM for a batch of nodes at a time, and the call waits once a level for the ids of the open nodes.
         Up to depth 8 it is boost_trees_weighted itself.  -> the dict of boost_trees_eval."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
         return self._boost_weighted("OHXBoosterBoostTreesDeep", dmat, labels, cuts, weights, eval_set, rounds, max_depth, eta,
                                     reg_lambda, gamma, min_child_weight, patience)
 
@@ -679,11 +683,11 @@ class Booster:
                                 eval_set=None, rounds: int = 1, max_depth: int = 12, eta: float = 0.3,
                                 reg_lambda: float = 1.0, gamma: float = 0.0, min_child_weight: float = 1.0,
                                 patience: int = 0, stream: int = 0,
-                                *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
+                                *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
                              eval_metric=None, monotone_constraints=None) -> dict:
         """The same with labels and weights in device memory, as boost_trees_weighted_device takes them.  With
         max_depth > 8 the call waits for `stream` once a level from level 7 on."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
         return self._boost_weighted_device("OHXBoosterBoostTreesDeepDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
                                            eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, patience,
                                            stream)
@@ -692,13 +696,13 @@ class Booster:
                             max_depth: int = 6, eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
                             min_child_weight: float = 1.0, subsample: float = 1.0, colsample_bytree: float = 1.0,
                             seed: int = 0, patience: int = 0,
-                            *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
+                            *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
                              eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
         """OHXBoosterBoostTreesSampled: boost_trees_weighted where every tree is fitted to a fresh bag of the rows
         (a fraction `subsample`) and may split on a fresh set of the features (a fraction `colsample_bytree`), both
         drawn on the GPU from `seed` (a uint64) and the tree's index in the forest.  colsample_bylevel= and
         colsample_bynode= narrow the tree's features again for every level and every node.  -> the dict of boost_trees_eval."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
                             colsample_bylevel, colsample_bynode)
         return self._boost_sampled("OHXBoosterBoostTreesSampled", dmat, labels, cuts, weights, eval_set, rounds, max_depth, eta,
                                    reg_lambda, gamma, min_child_weight, subsample, colsample_bytree, seed, patience)
@@ -735,10 +739,10 @@ class Booster:
                                    reg_lambda: float = 1.0, gamma: float = 0.0, min_child_weight: float = 1.0,
                                    subsample: float = 1.0, colsample_bytree: float = 1.0, seed: int = 0,
                                    patience: int = 0, stream: int = 0,
-                                   *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
+                                   *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
                              eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
         """The same with labels and weights in device memory, as boost_trees_weighted_device takes them."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
                             colsample_bylevel, colsample_bynode)
         return self._boost_sampled_device("OHXBoosterBoostTreesSampledDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
                                           eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, subsample,
@@ -763,13 +767,13 @@ class Booster:
                                  max_depth: int = 12, eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
                                  min_child_weight: float = 1.0, subsample: float = 1.0, colsample_bytree: float = 1.0,
                                  seed: int = 0, patience: int = 0,
-                                 *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
+                                 *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
                              eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
         """OHXBoosterBoostTreesDeepSampled: boost_trees_sampled with max_depth up to 18.  From level 8 on a level's
         histograms are kept in HBM for a batch of nodes at a time, over the bag's rows and the tree's features only, and
         the call waits once a level for the ids of the open nodes.  Up to depth 8 it is boost_trees_sampled itself; with
         both fractions 1 it is boost_trees_deep.  -> the dict of boost_trees_eval."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
                             colsample_bylevel, colsample_bynode)
         return self._boost_sampled("OHXBoosterBoostTreesDeepSampled", dmat, labels, cuts, weights, eval_set, rounds, max_depth,
                                    eta, reg_lambda, gamma, min_child_weight, subsample, colsample_bytree, seed, patience)
@@ -779,11 +783,11 @@ class Booster:
                                         reg_lambda: float = 1.0, gamma: float = 0.0, min_child_weight: float = 1.0,
                                         subsample: float = 1.0, colsample_bytree: float = 1.0, seed: int = 0,
                                         patience: int = 0, stream: int = 0,
-                                        *, objective=None, huber_slope=None, reg_alpha=None, max_delta_step=None,
+                                        *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
                              eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
         """The same with labels and weights in device memory, as boost_trees_weighted_device takes them.  With
         max_depth > 8 the call waits for `stream` once a level from level 7 on."""
-        self._set_objective(objective, huber_slope, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
                             colsample_bylevel, colsample_bynode)
         return self._boost_sampled_device("OHXBoosterBoostTreesDeepSampledDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
                                           eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, subsample,

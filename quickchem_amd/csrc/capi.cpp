@@ -35,6 +35,7 @@
 #include "visits.hpp"
 #include "refit.hpp"
 #include "grow.hpp"
+#include "grow_quantile.hpp"
 #include "cuts.hpp"
 
 using namespace ohx;
@@ -653,6 +654,7 @@ struct GrowState {
   int device = -1;
   bool prepared = false;               // prepare_grow has raised the LDS limits on `device`
   bool pairs_prepared = false;         // grow_lds_limits_pairs has: at the first call that takes the pair path
+  bool quantile_prepared = false;      // grow_lds_limits_quantile has: at the first call under the quantile objective
   DevBuf<uint8_t> d_bins;
   DevBuf<uint16_t> d_pos;
   DevBuf<float> d_pred, d_labels, d_cuts;
@@ -698,7 +700,11 @@ struct GrowState {
   // allocated only where a fraction takes a feature away
   DevBuf<uint8_t> d_level_lists;
   PinnedBuf<uint8_t> h_level_lists;
+  // the quantile objective (grow_quantile.hip): the bins of the select's pass at hand, 256 leaves x 256 digits x 8 bytes,
+  // and its leaf table; allocated only where the objective runs
+  DevBuf<uint8_t> d_quantile;
   void release_device() {
+    d_quantile.release();
     d_level_lists.release();
     d_mono_bounds.release();
     d_mono_constraints.release();
@@ -722,6 +728,7 @@ struct GrowState {
     d_state.release();
     prepared = false;
     pairs_prepared = false;
+    quantile_prepared = false;
   }
 };
 
@@ -866,7 +873,8 @@ struct BoosterObj {
                                         // (auto and global: every tree the global way - the faster at C360; same integers)
   uint32_t visits_lds_leaves = 0;       // "ohx_visits_lds_leaves": leaves a block's LDS histogram may hold (0 = what fits)
   // boosting (docs/26_objectives.md): kept on the handle, never written into a model file
-  uint32_t grow_objective = kGrowObjSquared;   // "ohx_objective": squarederror or pseudohuber
+  uint32_t grow_objective = kGrowObjSquared;   // "ohx_objective": squarederror, pseudohuber or quantile
+  float grow_quantile_alpha = 0.5f;            // "ohx_quantile_alpha": alpha of the quantile objective and metric
   float grow_slope = 1.0f;                     // "ohx_huber_slope": delta of pseudohuber
   bool grow_pairs_on = false;                  // "ohx_grow_pairs" = on: squared error goes through the pair kernels too (same bits)
   // (docs/27_regularisation_and_metrics.md): likewise on the handle alone
@@ -2158,7 +2166,8 @@ void refit_leaves(BoosterObj& b, DMatrixHandle dmat, const float* labels, bst_ul
     throw OhxError(std::string(what) + " refits squared-error leaves (gradient pred - label, hessian 1): the objective " +
                    b.forest.objective + " is not reg:squarederror");
   if (b.grow_objective != kGrowObjSquared)
-    throw OhxError(std::string(what) + " refits squared-error leaves (hessian 1 a row): it is refused while ohx_objective=pseudohuber "
+    throw OhxError(std::string(what) + " refits squared-error leaves (hessian 1 a row): it is refused while ohx_objective=" +
+                   grow_objective_name(b.grow_objective) + " "
                    "is set; grow with OHXBoosterBoostTreesWeighted, or set ohx_objective=squarederror; nothing was enqueued");
   if (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f)
     throw OhxError(std::string(what) + " refits unregularised leaves: it is refused while ohx_reg_alpha or ohx_max_delta_step is set; "
@@ -2405,7 +2414,12 @@ struct BoostKind {
   bool regularised = false, constrained = false, colsampled = false;
   GrowPairSplits reg_splits;
   uint32_t metric = kGrowMetricRmse;
-  float slope = 1.0f;
+  float slope = 1.0f;                  // delta of the pseudohuber metric, alpha of the quantile one
+  // quantile (ohx_objective = quantile; then `pairs` holds too, the kind is Weighted or Sampled and splits() is null): the
+  // pair path with grow_quantile.hip's pair kernel, the levels without the leaf kernel, the select that sets the leaves,
+  // then the leaf kernel.  Without it, and without the quantile metric, nothing of grow_quantile.hip is touched.
+  bool quantile = false;
+  GrowQuantileArgs quantile_args;
   const GrowPairSplits* splits() const { return constrained || regularised || colsampled ? &reg_splits : nullptr; }
   bool wide() const { return which != Plain; }
   // The call's one plan, asked for once: the level loop over `cols` histogram columns - F itself, or the n_sel features
@@ -2437,19 +2451,25 @@ struct BoostKind {
                                   : launch_grow_tree_deep(d, deep, round, h_state, stream));
       }
       case Sampled:
+        if (quantile) return (hipError_t)launch_grow_tree_quantile(a, pair_args, quantile_args, plan, levels, round, stream);
         return (hipError_t)(pairs ? launch_grow_tree_pairs(a, pair_args, plan, levels, round, stream, splits())
                                   : launch_grow_tree_sampled(a, plan, levels, round, stream));
       case Weighted:
+        if (quantile) return (hipError_t)launch_grow_tree_quantile(a, pair_args, quantile_args, plan, levels, round, stream);
         return (hipError_t)(pairs ? launch_grow_tree_pairs(a, pair_args, plan, levels, round, stream, splits())
                                   : launch_grow_tree_weighted(a, plan, levels, round, stream));
       default: return (hipError_t)launch_grow_tree(a, plan, levels, round, stream);
     }
   }
   hipError_t sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t t, uint32_t set, void* stream) const {
+    if (metric == kGrowMetricQuantile) return (hipError_t)launch_grow_sse_quantile(a, slope, blocks, t, set, stream);
     if (metric != kGrowMetricRmse) return (hipError_t)launch_grow_sse_metric(a, metric, slope, blocks, t, set, stream);
     return (hipError_t)(wide() ? launch_grow_sse_weighted(a, blocks, t, set, stream) : launch_grow_sse(a, blocks, t, set, stream));
   }
   hipError_t walk_sse(const GrowEvalArgs& a, uint32_t blocks, uint32_t round, uint32_t set, void* stream) const {
+    if (metric == kGrowMetricQuantile)
+      return (hipError_t)(which == Deep ? launch_grow_walk_sse_deep_quantile(a, deep_args, slope, blocks, round, set, stream)
+                                        : launch_grow_walk_sse_quantile(a, slope, blocks, round, set, stream));
     if (metric != kGrowMetricRmse)
       return (hipError_t)(which == Deep ? launch_grow_walk_sse_deep_metric(a, deep_args, metric, slope, blocks, round, set, stream)
                                         : launch_grow_walk_sse_metric(a, metric, slope, blocks, round, set, stream));
@@ -2485,8 +2505,26 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     throw OhxError(w0 + " fits squared-error trees (gradient pred - label, hessian 1): the objective " + b.forest.objective +
                    " is not reg:squarederror");
   if (b.grow_objective != kGrowObjSquared && !weighted)
-    throw OhxError(w0 + " keeps row counts, not hessian sums: with ohx_objective=pseudohuber call OHXBoosterBoostTreesWeighted "
+    throw OhxError(w0 + " keeps row counts, not hessian sums: with ohx_objective=" + grow_objective_name(b.grow_objective) +
+                   " call OHXBoosterBoostTreesWeighted "
                    "(weights may be NULL) or a later form; nothing was enqueued and the forest is unchanged");
+  if (b.grow_objective == kGrowObjQuantile) {
+    // the leaves of a quantile tree are set by a select over per-leaf tables of 256 leaves, after the pair path's own splits
+    const std::string tail = "; nothing was enqueued and the forest is unchanged";
+    if (c.deep)
+      throw OhxError(w0 + " keeps no per-leaf tables for the quantile leaves at any depth: with ohx_objective=quantile call "
+                     "OHXBoosterBoostTreesWeighted or OHXBoosterBoostTreesSampled (max_depth <= 8), or set ohx_objective=squarederror" + tail);
+    if (b.grow_alpha != 0.0f)
+      throw OhxError(w0 + ": a quantile leaf honours no ohx_reg_alpha: set ohx_reg_alpha=0 or ohx_objective=squarederror" + tail);
+    if (b.grow_max_delta_step != 0.0f)
+      throw OhxError(w0 + ": a quantile leaf honours no ohx_max_delta_step: set ohx_max_delta_step=0 or ohx_objective=squarederror" + tail);
+    if (!b.grow_mono.empty())
+      throw OhxError(w0 + ": a quantile leaf honours no ohx_monotone_constraints: unset them (every entry 0) or set "
+                     "ohx_objective=squarederror" + tail);
+    if (b.grow_bylevel != 1.0f || b.grow_bynode != 1.0f)
+      throw OhxError(w0 + ": ohx_objective=quantile grows with the pair path's own split kernels: set ohx_colsample_bylevel and "
+                     "ohx_colsample_bynode to 1, or ohx_objective=squarederror" + tail);
+  }
   if (!weighted && (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f || b.grow_metric != kGrowMetricRmse))
     throw OhxError(w0 + " keeps row counts and two-word sums: with ohx_reg_alpha, ohx_max_delta_step or ohx_eval_metric set call "
                    "OHXBoosterBoostTreesWeighted (weights may be NULL) or a later form; nothing was enqueued and the forest is unchanged");
@@ -2577,10 +2615,11 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   kind.pairs = weighted && (b.grow_objective != kGrowObjSquared || b.grow_pairs_on || kind.regularised || kind.constrained || colsampled);
   if (kind.regularised && !colsampled)
     kind.reg_splits = grow_reg_splits(GrowRegHess{(double)wt.min_child_weight, b.grow_alpha, b.grow_max_delta_step});
+  kind.quantile = weighted && b.grow_objective == kGrowObjQuantile;
   kind.metric = weighted ? b.grow_metric : kGrowMetricRmse;
-  kind.slope = b.grow_slope;
+  kind.slope = kind.metric == kGrowMetricQuantile ? b.grow_quantile_alpha : b.grow_slope;
   kind.pair_args.objective = b.grow_objective;
-  kind.pair_args.slope = b.grow_slope;
+  kind.pair_args.slope = kind.quantile ? b.grow_quantile_alpha : b.grow_slope;
   // before anything is built or enqueued: building the state waits for the library's stream
   if (!host_form && stream_capturing(c.caller))
     refuse_in_capture("grow trees", (w0 + " is not capturable; call it outside the capture").c_str());
@@ -2601,6 +2640,10 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (kind.pairs && !g.pairs_prepared) {
     HIP_CHECK((hipError_t)grow_lds_limits_pairs());
     g.pairs_prepared = true;
+  }
+  if (kind.quantile && !g.quantile_prepared) {
+    HIP_CHECK((hipError_t)grow_lds_limits_quantile());
+    g.quantile_prepared = true;
   }
   const uint64_t n = d.nrow, ncuts = c.cut_ptr[F];
   const size_t R = (size_t)c.rounds;
@@ -2647,6 +2690,7 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     g.h_identity.ensure(F);
     for (uint32_t f = 0; f < F; ++f) g.h_identity.p[f] = (uint8_t)f;
   }
+  if (kind.quantile) room(g.d_quantile, (size_t)kGrowQuantileBytes, 1, "the bins and the leaf table of the quantile select");
   if (kind.constrained) {
     room(g.d_mono_bounds, 2 * stride, 8, "the weight intervals of the monotone constraints");
     room(g.d_mono_constraints, F, 1, "the monotone constraints of every feature");
@@ -2774,6 +2818,12 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     kind.pair_args.q = g.d_pair_q.p;
     kind.pair_args.hq = g.d_pair_hq.p;
     kind.pair_args.identity = g.d_identity.p;
+  }
+  if (kind.quantile) {
+    kind.quantile_args.hist = reinterpret_cast<unsigned long long*>(g.d_quantile.p);
+    kind.quantile_args.state = reinterpret_cast<GrowQuantileState*>(g.d_quantile.p + kGrowQuantileHistBytes);
+    kind.quantile_args.hq = g.d_pair_hq.p;
+    kind.quantile_args.alpha = b.grow_quantile_alpha;
   }
   if (colsampled) {
     GrowColsampleArgs cs;
@@ -2984,7 +3034,9 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
         x.p2 = s[0];
         x.p1 = s[1];
         x.p0 = s[2];
-        return kind.metric == kGrowMetricRmse ? grow_wide_rmse(x, g.h_sums.p[set]) : grow_wide_mean(x, g.h_sums.p[set]);
+        return kind.metric == kGrowMetricRmse       ? grow_wide_rmse(x, g.h_sums.p[set])
+               : kind.metric == kGrowMetricQuantile ? grow_wide_quantile(x, g.h_sums.p[set])
+                                                    : grow_wide_mean(x, g.h_sums.p[set]);
       }
       GrowSum x;
       x.hi = s[0];
@@ -3462,14 +3514,22 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
     b->visits_lds_leaves = (uint32_t)k;
   } else if (n == "ohx_objective") {
     // boosting: what a row's (gradient, hessian) pair is made from (docs/26_objectives.md); on the handle, in no file
-    if (v != "squarederror" && v != "pseudohuber") throw OhxError("ohx_objective must be squarederror or pseudohuber");
-    b->grow_objective = v == "pseudohuber" ? kGrowObjPseudoHuber : kGrowObjSquared;
+    if (v != "squarederror" && v != "pseudohuber" && v != "quantile")
+      throw OhxError("ohx_objective must be squarederror, pseudohuber or quantile");
+    b->grow_objective = v == "pseudohuber" ? kGrowObjPseudoHuber : v == "quantile" ? kGrowObjQuantile : kGrowObjSquared;
   } else if (n == "ohx_huber_slope") {
     char* end = nullptr;
     const float k = strtof(value, &end);
     if (v.empty() || end == value || *end != '\0' || !grow_slope_sound(k))
       throw OhxError("ohx_huber_slope must be a decimal number with 2^-10 <= slope <= 256");
     b->grow_slope = k;
+  } else if (n == "ohx_quantile_alpha") {
+    // boosting: alpha of the quantile objective and metric (docs/32_quantile_objective.md); on the handle, in no file
+    char* end = nullptr;
+    const float k = strtof(value, &end);
+    if (v.empty() || end == value || *end != '\0' || !grow_alpha_sound(k))
+      throw OhxError("ohx_quantile_alpha must be a decimal number with 2^-10 <= alpha <= 1 - 2^-10");
+    b->grow_quantile_alpha = k;
   } else if (n == "ohx_reg_alpha" || n == "ohx_max_delta_step") {
     // boosting: CalcWeight / CalcGain's other two parameters (docs/27_regularisation_and_metrics.md); on the handle, in no file
     char* end = nullptr;
@@ -3478,8 +3538,12 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
       throw OhxError(n + " must be a finite decimal number >= 0");
     (n == "ohx_reg_alpha" ? b->grow_alpha : b->grow_max_delta_step) = k;
   } else if (n == "ohx_eval_metric") {
-    if (v != "rmse" && v != "mae" && v != "pseudohuber") throw OhxError("ohx_eval_metric must be rmse, mae or pseudohuber");
-    b->grow_metric = v == "mae" ? kGrowMetricMae : v == "pseudohuber" ? kGrowMetricPseudoHuber : kGrowMetricRmse;
+    if (v != "rmse" && v != "mae" && v != "pseudohuber" && v != "quantile")
+      throw OhxError("ohx_eval_metric must be rmse, mae, pseudohuber or quantile");
+    b->grow_metric = v == "mae"           ? kGrowMetricMae
+                     : v == "pseudohuber" ? kGrowMetricPseudoHuber
+                     : v == "quantile"    ? kGrowMetricQuantile
+                                          : kGrowMetricRmse;
   } else if (n == "ohx_monotone_constraints") {
     // boosting: c_f of every feature (docs/28_monotone_constraints.md); on the handle, in no file
     b->grow_mono = parse_monotone_constraints(value);

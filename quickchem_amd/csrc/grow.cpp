@@ -240,4 +240,9 @@ double grow_wide_mean(GrowWideSum s, uint64_t W) {
   return ((double)S * (1.0 / 281474976710656.0)) / ((double)(unsigned __int128)W * (1.0 / 16777216.0));
 }
 
+double grow_wide_quantile(GrowWideSum s, uint64_t W) {
+  const unsigned __int128 S = grow_wide_value(s);
+  return ((double)S * (1.0 / 4722366482869645213696.0)) / ((double)(unsigned __int128)W * (1.0 / 16777216.0));
+}
+
 }  // namespace ohx

@@ -91,7 +91,13 @@ OHX_GROW_HD inline void grow_solve_leaf_weighted(int64_t G, uint64_t H, float et
 
 // "ohx_objective": what a row's pair is made from.  squarederror is g = z, h = 1; pseudohuber is xgboost 1.6.0's
 // PseudoHuberRegression::GetGradient with slope delta ("ohx_huber_slope").
-constexpr uint32_t kGrowObjSquared = 0, kGrowObjPseudoHuber = 1;
+// quantile (design in docs/32_quantile_objective.md) is the pinball loss at alpha ("ohx_quantile_alpha"), which rides in
+// the slope's place: g = 1 - alpha where z >= 0, else -alpha; h = 1.  Its leaves are not Newton steps: grow_quantile.hpp.
+constexpr uint32_t kGrowObjSquared = 0, kGrowObjPseudoHuber = 1, kGrowObjQuantile = 2;
+// the value of "ohx_objective" that names it
+inline const char* grow_objective_name(uint32_t objective) {
+  return objective == kGrowObjPseudoHuber ? "pseudohuber" : objective == kGrowObjQuantile ? "quantile" : "squarederror";
+}
 constexpr float kGrowMinSlope = 0.0009765625f;   // 2^-10
 constexpr float kGrowMaxSlope = 256.0f;
 // (NaN fails both comparisons)
@@ -122,6 +128,7 @@ OHX_GROW_HD inline uint32_t grow_pair(float slope, float pred, float label, floa
     const float c = d2 + z2;
     h = d2 / (c * s);
   }
+  if (OBJ == kGrowObjQuantile) g = z >= 0.0f ? 1.0f - slope : -slope;   // slope is alpha here; no division, no square root
   const float gw = g * w;
   if (!(__builtin_fabsf(gw) < kRefitMaxAbsGrad)) return kGrowFlagLabel;
   const float hw = h * w;
@@ -132,6 +139,7 @@ OHX_GROW_HD inline uint32_t grow_pair(float slope, float pred, float label, floa
 // the same with the objective as a value (the host's callers)
 inline uint32_t grow_pair_of(uint32_t objective, float slope, float pred, float label, float w, int64_t* q, uint32_t* hq) {
   return objective == kGrowObjPseudoHuber ? grow_pair<kGrowObjPseudoHuber>(slope, pred, label, w, q, hq)
+         : objective == kGrowObjQuantile  ? grow_pair<kGrowObjQuantile>(slope, pred, label, w, q, hq)
                                           : grow_pair<kGrowObjSquared>(slope, pred, label, w, q, hq);
 }
 
@@ -570,7 +578,14 @@ double grow_wide_rmse(GrowWideSum s, uint64_t W);
 // "ohx_eval_metric": what one row adds to S beside its hq (design in docs/27_regularisation_and_metrics.md).  rmse is the
 // square of the fixed-point residual, as ever; mae its size; pseudohuber delta^2 (sqrt(1 + z^2 / delta^2) - 1) in the
 // form that cancels nothing, every operation float32 and rounding once, the division and the square root IEEE.
-constexpr uint32_t kGrowMetricRmse = 0, kGrowMetricMae = 1, kGrowMetricPseudoHuber = 2;
+// quantile is the pinball loss at alpha (in the slope's place): the size of the fixed-point residual times alpha_q where
+// z < 0 and 2^24 - alpha_q where not, below 2^56; its sums stand 2^24 above mae's (grow_wide_quantile).
+constexpr uint32_t kGrowMetricRmse = 0, kGrowMetricMae = 1, kGrowMetricPseudoHuber = 2, kGrowMetricQuantile = 3;
+// "ohx_quantile_alpha": 2^-10 <= alpha <= 1 - 2^-10 (NaN fails both comparisons), and alpha_q = rint(alpha * 2^24): the
+// scaling of a float32 by 2^24 is exact, so 2^14 <= alpha_q <= 2^24 - 2^14
+constexpr float kGrowMinAlpha = 0.0009765625f, kGrowMaxAlpha = 0.9990234375f;
+inline bool grow_alpha_sound(float alpha) { return alpha >= kGrowMinAlpha && alpha <= kGrowMaxAlpha; }
+OHX_GROW_HD inline uint32_t grow_alpha_q(float alpha) { return (uint32_t)__builtin_rintf(alpha * kRefitGradScale); }
 // sq of the header for z = pred - label; false (and sq = 0) where z is not finite or |z| >= 256.  sq < 2^64 for rmse,
 // < 2^32 for mae and < 2^40 for pseudohuber (mf <= delta |z| < 2^16).  A denormal z2 or mf gives 0 whether or not
 // denormals are flushed: 1 + z2 / d2 absorbs the one and rint(mf * 2^24) the other.
@@ -590,6 +605,11 @@ OHX_GROW_HD inline bool grow_metric_row(float slope, float pred, float label, ui
   }
   const long long e = (long long)__builtin_rintf(z * kRefitGradScale);
   const uint64_t m = (uint64_t)(e < 0 ? -e : e);   // <= 2^32 - 256
+  if (METRIC == kGrowMetricQuantile) {
+    const uint32_t alpha_q = grow_alpha_q(slope);   // slope is alpha here
+    *sq = m * (uint64_t)(z < 0.0f ? alpha_q : kGrowSampleOne - alpha_q);
+    return true;
+  }
   *sq = METRIC == kGrowMetricMae ? m : m * m;
   return true;
 }
@@ -597,11 +617,14 @@ OHX_GROW_HD inline bool grow_metric_row(float slope, float pred, float label, ui
 inline bool grow_metric_row_of(uint32_t metric, float slope, float pred, float label, uint64_t* sq) {
   return metric == kGrowMetricPseudoHuber ? grow_metric_row<kGrowMetricPseudoHuber>(slope, pred, label, sq)
          : metric == kGrowMetricMae       ? grow_metric_row<kGrowMetricMae>(slope, pred, label, sq)
+         : metric == kGrowMetricQuantile  ? grow_metric_row<kGrowMetricQuantile>(slope, pred, label, sq)
                                           : grow_metric_row<kGrowMetricRmse>(slope, pred, label, sq);
 }
 // What mae and pseudohuber report: ((double)S * 2^-48) / ((double)W * 2^-24), both exact integers rounded to nearest
 // even as they become doubles, exact scalings, then an IEEE division.  No square root.
 double grow_wide_mean(GrowWideSum s, uint64_t W);
+// What quantile reports: ((double)S * 2^-72) / ((double)W * 2^-24), likewise.  No square root.
+double grow_wide_quantile(GrowWideSum s, uint64_t W);
 
 // ---- the launch plan ----
 
@@ -875,6 +898,10 @@ struct GrowPairSplits {
 // use in place of this file's.  Returns a hipError_t.
 int launch_grow_tree_pairs(const GrowArgs& a, const GrowPairArgs& p, const GrowPlan& plan, const GrowPlan& levels, uint32_t round,
                            void* stream, const GrowPairSplits* splits = nullptr);
+// The levels of launch_grow_tree_pairs alone, over planes that hold the round's pairs already: no pair kernel before them
+// and no leaf kernel after, so the rows stay on their leaves (grow_quantile.hip, which makes the pairs and sets the leaves).
+int launch_grow_levels_pairs(const GrowArgs& a, const GrowPairArgs& p, const GrowPlan& plan, const GrowPlan& levels, uint32_t round,
+                             void* stream);
 // launch_grow_tree_deep on pairs, with or without a bag and a list.  Returns a hipError_t.
 int launch_grow_tree_deep_pairs(const GrowDeepArgs& a, const GrowPairArgs& p, const GrowDeepPlan& plan, uint32_t round,
                                 GrowLevelState* h_state, void* stream, const GrowPairSplits* splits = nullptr);

@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "grow.hpp"
+#include "grow_quantile.hpp"
 
 namespace ohx {
 void synth_set_error(const std::string& m);   // synth_host.cpp
@@ -421,14 +422,15 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_deep_children(con
 
 // ---- the objective's pair (docs/26_objectives.md) ----
 
-// grow.hpp grow_pair over n rows: objective 0 squarederror, 1 pseudohuber with `slope`.  w may be NULL (every weight
+// grow.hpp grow_pair over n rows: objective 0 squarederror, 1 pseudohuber with `slope`, 2 quantile with alpha in its place.  w may be NULL (every weight
 // 1.0f).  q int64 [n], hq uint32 [n]; *flags: the kGrowFlag* bits the rows raise together (a row that raises one has the
 // pair (0, 0)).  An objective or a slope the library refuses is an error.
 extern "C" __attribute__((visibility("default"))) int ohx_grow_pairs(uint32_t objective, float slope, const float* pred,
                                                                     const float* y, const float* w, uint64_t n, int64_t* q,
                                                                     uint32_t* hq, uint32_t* flags) {
   try {
-    if (objective != kGrowObjSquared && objective != kGrowObjPseudoHuber) throw OhxError("ohx_grow_pairs: objective must be 0 or 1");
+    if (objective > kGrowObjQuantile) throw OhxError("ohx_grow_pairs: objective must be 0, 1 or 2");
+    if (objective == kGrowObjQuantile && !grow_alpha_sound(slope)) throw OhxError("ohx_grow_pairs: 2^-10 <= alpha <= 1 - 2^-10");
     if (objective == kGrowObjPseudoHuber && !grow_slope_sound(slope)) throw OhxError("ohx_grow_pairs: 2^-10 <= slope <= 256");
     uint32_t raised = 0;
     for (uint64_t r = 0; r < n; ++r) raised |= grow_pair_of(objective, slope, pred[r], y[r], w != nullptr ? w[r] : 1.0f, &q[r], &hq[r]);
@@ -525,11 +527,12 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_mono_node_split(c
   return 0;
 }
 
-// sq of every row by `metric` (0 rmse, 1 mae, 2 pseudohuber with `slope`); sound[r] = 0 where the residual is refused
+// sq of every row by `metric` (0 rmse, 1 mae, 2 pseudohuber with `slope`, 3 quantile with alpha in its place); sound[r] = 0 where the residual is refused
 extern "C" __attribute__((visibility("default"))) int ohx_grow_metric_row(uint32_t metric, float slope, const float* pred, const float* y,
                                                                          uint64_t n, uint64_t* sq, uint8_t* sound) {
   try {
-    if (metric > kGrowMetricPseudoHuber) throw OhxError("ohx_grow_metric_row: metric must be 0, 1 or 2");
+    if (metric > kGrowMetricQuantile) throw OhxError("ohx_grow_metric_row: metric must be 0, 1, 2 or 3");
+    if (metric == kGrowMetricQuantile && !grow_alpha_sound(slope)) throw OhxError("ohx_grow_metric_row: 2^-10 <= alpha <= 1 - 2^-10");
     if (metric == kGrowMetricPseudoHuber && !grow_slope_sound(slope)) throw OhxError("ohx_grow_metric_row: 2^-10 <= slope <= 256");
     for (uint64_t r = 0; r < n; ++r) sound[r] = grow_metric_row_of(metric, slope, pred[r], y[r], &sq[r]) ? 1 : 0;
     return 0;
@@ -546,4 +549,76 @@ extern "C" __attribute__((visibility("default"))) double ohx_grow_weighted_mean(
   x.p1 = s[1];
   x.p0 = s[2];
   return grow_wide_mean(x, W);
+}
+
+// ---- the quantile objective (docs/32_quantile_objective.md) ----
+
+// s: (p2, p1, p0); W: the sum of hq
+extern "C" __attribute__((visibility("default"))) double ohx_grow_weighted_quantile(const uint64_t s[3], uint64_t W) {
+  GrowWideSum x;
+  x.p2 = s[0];
+  x.p1 = s[1];
+  x.p0 = s[2];
+  return grow_wide_quantile(x, W);
+}
+
+// grow_quantile.hpp grow_quantile_pick on one leaf's bins of pass `pass`; st = (prefix, below, W) in and out.  Returns 1
+// where a digit was picked, 0 where the leaf holds no weight.
+extern "C" __attribute__((visibility("default"))) int ohx_grow_quantile_pick(const uint64_t bins[256], uint32_t pass, float alpha,
+                                                                            uint64_t st[3]) {
+  GrowQuantileLeaf leaf;
+  leaf.prefix = (uint32_t)st[0];
+  leaf.below = st[1];
+  leaf.W = st[2];
+  const bool found = pass < kGrowQuantilePasses && grow_alpha_sound(alpha) && grow_quantile_pick(bins, pass, grow_alpha_q(alpha), &leaf);
+  st[0] = leaf.prefix;
+  st[1] = leaf.below;
+  st[2] = leaf.W;
+  return found ? 1 : 0;
+}
+
+// The whole select as the device runs it, with host counting: rows at node pos[r] with hessian hq[r] (0: the row does
+// not count) and residual y[r] - pred[r]; leaves[s] is the node of slot s.  Four passes of bins[slot][digit] over the rows
+// whose key carries their leaf's prefix, each followed by the picks.  found[s] = 0 where slot s holds no weight; else
+// key[s] = k*, value[s] = float(cuts_unkey(k*)) * eta and W[s] the leaf's weight.
+extern "C" __attribute__((visibility("default"))) int ohx_grow_quantile_leaves(const uint16_t* pos, const uint32_t* hq, const float* pred,
+                                                                              const float* y, uint64_t n, const uint16_t* leaves,
+                                                                              uint32_t nleaves, float alpha, float eta, uint8_t* found,
+                                                                              uint32_t* key, float* value, uint64_t* W) {
+  try {
+    if (nleaves > kGrowQuantileMaxLeaves) throw OhxError("ohx_grow_quantile_leaves: at most 256 leaves");
+    if (!grow_alpha_sound(alpha)) throw OhxError("ohx_grow_quantile_leaves: 2^-10 <= alpha <= 1 - 2^-10");
+    std::vector<uint16_t> slot_of(kGrowMaxNodes, (uint16_t)kGrowQuantileNoSlot);
+    for (uint32_t s = 0; s < nleaves; ++s) {
+      if (leaves[s] >= kGrowMaxNodes || slot_of[leaves[s]] != kGrowQuantileNoSlot) throw OhxError("ohx_grow_quantile_leaves: a leaf's node id");
+      slot_of[leaves[s]] = (uint16_t)s;
+    }
+    const uint32_t alpha_q = grow_alpha_q(alpha);
+    std::vector<GrowQuantileLeaf> leaf(nleaves);
+    std::vector<uint8_t> live(nleaves, 1);
+    std::vector<uint64_t> bins((size_t)nleaves * kGrowQuantileDigits);
+    for (uint32_t pass = 0; pass < kGrowQuantilePasses; ++pass) {
+      std::fill(bins.begin(), bins.end(), 0);
+      for (uint64_t r = 0; r < n; ++r) {
+        if (hq[r] == 0 || pos[r] >= kGrowMaxNodes) continue;
+        const uint32_t s = slot_of[pos[r]];
+        if (s >= nleaves) continue;
+        const uint32_t k = grow_quantile_key(pred[r], y[r]);
+        if (!grow_quantile_matches(k, leaf[s].prefix, pass)) continue;
+        bins[(size_t)s * kGrowQuantileDigits + grow_quantile_digit(k, pass)] += hq[r];
+      }
+      for (uint32_t s = 0; s < nleaves; ++s)
+        if (live[s]) live[s] = grow_quantile_pick(bins.data() + (size_t)s * kGrowQuantileDigits, pass, alpha_q, &leaf[s]) ? 1 : 0;
+    }
+    for (uint32_t s = 0; s < nleaves; ++s) {
+      found[s] = live[s];
+      key[s] = live[s] ? leaf[s].prefix : 0;
+      value[s] = live[s] ? grow_quantile_value(leaf[s].prefix, eta) : 0.0f;
+      W[s] = leaf[s].W;
+    }
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
 }

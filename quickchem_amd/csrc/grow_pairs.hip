@@ -210,7 +210,8 @@ __global__ __launch_bounds__(kBlock) void grow_split_pairs_kernel(GrowArgs a, Gr
 bool pairs_args_sound(const GrowArgs& a, const GrowPairArgs& p) {
   return a.nrow != 0 && a.nrow <= kRefitMaxRows && a.num_feature != 0 && a.num_feature <= kGrowMaxFeatures && p.q != nullptr &&
          p.hq != nullptr && p.identity != nullptr && a.pred != nullptr && a.labels != nullptr && a.state != nullptr &&
-         (p.objective == kGrowObjSquared || (p.objective == kGrowObjPseudoHuber && grow_slope_sound(p.slope))) &&
+         (p.objective == kGrowObjSquared || (p.objective == kGrowObjPseudoHuber && grow_slope_sound(p.slope)) ||
+          (p.objective == kGrowObjQuantile && grow_alpha_sound(p.slope))) &&
          (a.features != nullptr ? a.n_sel != 0 && a.n_sel <= a.num_feature && a.k_s != 0 && a.k_s <= kGrowSampleOne
                                 : a.bag == nullptr) &&
          a.min_child_weight >= 0.0;
@@ -235,12 +236,14 @@ hipError_t launch_pair_kernel(const GrowArgs& a, const GrowPairArgs& p, const Gr
   return hipGetLastError();
 }
 
-// The pair kernel, then grow_device.hpp's level loop with this file's launches.  `list`: the tree's own list or nullptr.
+// The pair kernel (make_pairs; without, the planes hold the round's pairs already: grow_quantile.hip makes its own), then
+// grow_device.hpp's level loop with this file's launches.  `list`: the tree's own list or nullptr.
 // `tree`: the call's round, which `round` is not where the tree is round 0 of its own table; it picks the lists of a
 // column-sampled call (splits->levels), whose level d adds and splits the columns of its own list.
 hipError_t pairs_levels(const GrowArgs& a, const GrowPairArgs& p, const uint8_t* list, const GrowPlan& plan, const GrowPlan& levels,
-                        uint32_t round, uint32_t tree, hipStream_t stream, bool leaf, const GrowPairSplits* splits) {
-  if (!pairs_args_sound(a, p)) return hipErrorInvalidValue;
+                        uint32_t round, uint32_t tree, hipStream_t stream, bool leaf, const GrowPairSplits* splits,
+                        bool make_pairs = true) {
+  if (!pairs_args_sound(a, p) || (make_pairs && p.objective == kGrowObjQuantile)) return hipErrorInvalidValue;
   const bool by_level = splits != nullptr && splits->levels.lists != nullptr;
   if (by_level ? !splits->level_split0 || !splits->level_split1 || splits->levels.depth < (uint32_t)a.max_depth ||
                      splits->levels.n_lvl == 0 || splits->levels.n_lvl > (list != nullptr ? a.n_sel : a.num_feature)
@@ -256,8 +259,10 @@ hipError_t pairs_levels(const GrowArgs& a, const GrowPairArgs& p, const uint8_t*
     }
     return kd;
   };
-  hipError_t e = launch_pair_kernel(a, p, k, plan, stream);
-  if (e != hipSuccess) return e;
+  if (make_pairs) {
+    const hipError_t e = launch_pair_kernel(a, p, k, plan, stream);
+    if (e != hipSuccess) return e;
+  }
   const int root = p.objective == kGrowObjPseudoHuber ? kRootHess : list != nullptr ? kRootBag : kRootNone;
   return grow_launch_tree(
       a, plan, levels, round, stream, planes_at(0).ncols, kGrowWeightedPairBytes, 0,
@@ -288,6 +293,12 @@ int launch_grow_tree_pairs(const GrowArgs& a, const GrowPairArgs& p, const GrowP
                            void* stream, const GrowPairSplits* splits) {
   const uint8_t* list = a.features != nullptr ? a.features + (uint64_t)round * a.n_sel : nullptr;
   return pairs_levels(a, p, list, plan, levels, round, round, static_cast<hipStream_t>(stream), true, splits);
+}
+
+int launch_grow_levels_pairs(const GrowArgs& a, const GrowPairArgs& p, const GrowPlan& plan, const GrowPlan& levels, uint32_t round,
+                             void* stream) {
+  const uint8_t* list = a.features != nullptr ? a.features + (uint64_t)round * a.n_sel : nullptr;
+  return pairs_levels(a, p, list, plan, levels, round, round, static_cast<hipStream_t>(stream), false, nullptr, false);
 }
 
 int launch_grow_tree_deep_pairs(const GrowDeepArgs& d, const GrowPairArgs& p, const GrowDeepPlan& plan, uint32_t round,

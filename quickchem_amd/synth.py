@@ -149,6 +149,11 @@ def _load():
         lib.ohx_grow_mono_node_split.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_uint64, C.c_float,
                                                  C.c_float, C.c_float, C.c_float, C.c_double, C.c_double, C.c_void_p, C.c_void_p,
                                                  C.POINTER(C.c_double), C.c_void_p]
+        lib.ohx_grow_weighted_quantile.argtypes = [C.c_void_p, C.c_uint64]
+        lib.ohx_grow_weighted_quantile.restype = C.c_double
+        lib.ohx_grow_quantile_pick.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]
+        lib.ohx_grow_quantile_leaves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
+                                                 C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         lib.ohx_grow_metric_row.argtypes = [C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.ohx_grow_weighted_mean.argtypes = [C.c_void_p, C.c_uint64]
         lib.ohx_grow_weighted_mean.restype = C.c_double
@@ -653,13 +658,13 @@ def grow_deep_children(flags, width: int, next_id: int):
     return left[:f.size], int(n.value)
 
 
-GROW_OBJECTIVES = {"squarederror": 0, "pseudohuber": 1}
+GROW_OBJECTIVES = {"squarederror": 0, "pseudohuber": 1, "quantile": 2}
 GROW_FLAG_LABEL, GROW_FLAG_WEIGHT = 1, 8   # csrc/grow.hpp kGrowFlagLabel, kGrowFlagWeight
 
 
 def ohx_grow_pairs(objective: str, slope: float, pred, y, w=None):
     """csrc/grow.hpp grow_pair over the rows: the fixed-point (gradient, hessian) pair of every row by `objective`
-    ("squarederror" or "pseudohuber" with `slope`) -> (q int64 [n], hq uint32 [n], flags).  A row that raises a flag
+    ("squarederror", "pseudohuber" with `slope`, or "quantile" with alpha in the slope's place) -> (q int64 [n], hq uint32 [n], flags).  A row that raises a flag
     (GROW_FLAG_LABEL, GROW_FLAG_WEIGHT) has the pair (0, 0).  w None: every weight is 1."""
     pred = np.ascontiguousarray(pred, dtype=np.float32)
     y = np.ascontiguousarray(y, dtype=np.float32)
@@ -681,7 +686,7 @@ def grow_pairs_plan(nrow: int, num_feature: int, ncuts: int, max_depth: int, num
     return {"pairs_bytes": int(info[0]), "row_bytes": int(info[1])}
 
 
-GROW_METRICS = {"rmse": 0, "mae": 1, "pseudohuber": 2}
+GROW_METRICS = {"rmse": 0, "mae": 1, "pseudohuber": 2, "quantile": 3}
 
 
 def ohx_grow_reg_gain(G: int, H: int, reg_lambda: float, reg_alpha: float, max_delta_step: float) -> float:
@@ -755,7 +760,8 @@ def grow_mono_node_split(Gh, Hh, cut_ptr, Gp: int, Hp: int, reg_lambda: float, m
 
 def ohx_grow_metric_row(metric: str, slope: float, pred, y):
     """csrc/grow.hpp grow_metric_row over the rows: what a row adds to S beside its hq by `metric` ("rmse", "mae" or
-    "pseudohuber" with `slope`) -> (sq uint64 [n], sound bool [n]); a refused residual has sq = 0."""
+    "pseudohuber" with `slope`, or "quantile" with alpha in the slope's place) -> (sq uint64 [n], sound bool [n]); a refused
+    residual has sq = 0."""
     pred = np.ascontiguousarray(pred, dtype=np.float32)
     y = np.ascontiguousarray(y, dtype=np.float32)
     assert pred.shape == y.shape and pred.ndim == 1
@@ -770,6 +776,44 @@ def boost_weighted_mean(p2: int, p1: int, p0: int, W: int) -> float:
     """csrc/grow.cpp grow_wide_mean: ((double)(p2 * 2^64 + p1 * 2^32 + p0) * 2^-48) / ((double)W * 2^-24)."""
     s = np.ascontiguousarray([p2, p1, p0], dtype=np.uint64)
     return float(_load().ohx_grow_weighted_mean(s.ctypes.data, W))
+
+
+def boost_weighted_quantile(p2: int, p1: int, p0: int, W: int) -> float:
+    """csrc/grow.cpp grow_wide_quantile: ((double)(p2 * 2^64 + p1 * 2^32 + p0) * 2^-72) / ((double)W * 2^-24)."""
+    s = np.ascontiguousarray([p2, p1, p0], dtype=np.uint64)
+    return float(_load().ohx_grow_weighted_quantile(s.ctypes.data, W))
+
+
+def grow_quantile_pick(bins, pass_: int, alpha: float, prefix: int = 0, below: int = 0, W: int = 0):
+    """csrc/grow_quantile.hpp grow_quantile_pick: one pass's pick over a leaf's 256 bins (uint64) from the leaf's state
+    (prefix, below, W; pass 0 makes W from the bins) -> None where the leaf holds no weight, else (prefix, below, W)."""
+    b = np.ascontiguousarray(bins, dtype=np.uint64)
+    assert b.shape == (256,)
+    st = np.array([prefix, below, W], dtype=np.uint64)
+    rc = _load().ohx_grow_quantile_pick(b.ctypes.data, int(pass_), float(alpha), st.ctypes.data)
+    return None if rc == 0 else (int(st[0]), int(st[1]), int(st[2]))
+
+
+def grow_quantile_leaves(pos, hq, pred, y, leaves, alpha: float, eta: float = 1.0):
+    """The whole per-leaf select on the host, pass by pass as the device runs it (csrc/grow_host.cpp over
+    grow_quantile.hpp): rows at node pos[r] (uint16) with hessian hq[r] (uint32) and residual y[r] - pred[r]; `leaves` the
+    node ids in slot order -> (found bool [L], key uint32 [L], value float32 [L], W uint64 [L]); a leaf without weight is
+    not found."""
+    pos = np.ascontiguousarray(pos, dtype=np.uint16)
+    hq = np.ascontiguousarray(hq, dtype=np.uint32)
+    pred = np.ascontiguousarray(pred, dtype=np.float32)
+    y = np.ascontiguousarray(y, dtype=np.float32)
+    lv = np.ascontiguousarray(leaves, dtype=np.uint16)
+    assert pos.shape == hq.shape == pred.shape == y.shape and pos.ndim == 1 and lv.ndim == 1
+    L = max(lv.size, 1)
+    found = np.zeros(L, dtype=np.uint8)
+    key = np.zeros(L, dtype=np.uint32)
+    value = np.zeros(L, dtype=np.float32)
+    W = np.zeros(L, dtype=np.uint64)
+    _check(_load().ohx_grow_quantile_leaves(pos.ctypes.data, hq.ctypes.data, pred.ctypes.data, y.ctypes.data, y.size, lv.ctypes.data,
+                                            lv.size, float(alpha), float(eta), found.ctypes.data, key.ctypes.data, value.ctypes.data,
+                                            W.ctypes.data))
+    return found[:lv.size].astype(bool), key[:lv.size], value[:lv.size], W[:lv.size]
 
 
 def boost_weighted_rmse(p2: int, p1: int, p0: int, W: int) -> float:

@@ -41,7 +41,9 @@ features a tree sees.  Without the two fractions `--deep` does what it did.
 "ohx_grow_pairs" on every booster that is timed (docs/26_objectives.md): the calls with row weights, `--weights`,
 `--subsample` / `--colsample` or `--deep`, then go through the pair kernels.  Three runs that differ in these alone compare
 the inline path, squared error on pairs and pseudo-Huber.  The refit at the end is a squared-error step and is left out
-under pseudohuber.
+under pseudohuber.  `--objective quantile` (with `--quantile-alpha`) sets "ohx_objective" and "ohx_quantile_alpha"
+(docs/32_quantile_objective.md): the calls with row weights at depth <= 8, never `--deep`; `--eval-metric quantile` reads the
+same alpha.
 
 `--monotone "(1,0,-1)"` sets "ohx_monotone_constraints" on every booster that is timed (docs/28_monotone_constraints.md): the
 calls with row weights then take the constrained split kernels over the pair path.  Against a run with `--pairs on
@@ -159,12 +161,13 @@ def main():
     ap.add_argument("--seed", type=int, default=0, help="the seed of the sampled call's draws")
     ap.add_argument("--deep", action="store_true", help="time OHXBoosterBoostTreesDeepDevice (with --subsample / --colsample: ...DeepSampledDevice): --max-depth up to 18")
     ap.add_argument("--deep-only", action="store_true", help="with --deep: one call a round count on a fresh booster, no refit")
-    ap.add_argument("--objective", choices=("squarederror", "pseudohuber"), default="squarederror", help="ohx_objective of the timed boosters")
+    ap.add_argument("--objective", choices=("squarederror", "pseudohuber", "quantile"), default="squarederror", help="ohx_objective of the timed boosters")
     ap.add_argument("--huber-slope", type=float, default=1.0, help="ohx_huber_slope of the timed boosters")
+    ap.add_argument("--quantile-alpha", type=float, default=0.5, help="ohx_quantile_alpha of the timed boosters")
     ap.add_argument("--pairs", choices=("auto", "on"), default="auto", help="ohx_grow_pairs of the timed boosters")
     ap.add_argument("--reg-alpha", type=float, default=0.0, help="ohx_reg_alpha of the timed boosters")
     ap.add_argument("--max-delta-step", type=float, default=0.0, help="ohx_max_delta_step of the timed boosters")
-    ap.add_argument("--eval-metric", choices=("rmse", "mae", "pseudohuber"), default="rmse", help="ohx_eval_metric of the timed boosters")
+    ap.add_argument("--eval-metric", choices=("rmse", "mae", "pseudohuber", "quantile"), default="rmse", help="ohx_eval_metric of the timed boosters")
     ap.add_argument("--monotone", default=None, help="ohx_monotone_constraints of the timed boosters, as the parameter is written: \"(1,0,-1)\"")
     ap.add_argument("--colsample-bylevel", type=float, default=None, help="ohx_colsample_bylevel of the timed boosters (with --subsample / --colsample)")
     ap.add_argument("--colsample-bynode", type=float, default=None, help="ohx_colsample_bynode of the timed boosters (with --subsample / --colsample)")
@@ -271,7 +274,8 @@ def main():
     elif args.weights == "random":
         weights = torch.rand(n, dtype=torch.float32, device="cuda", generator=torch.Generator(device="cuda").manual_seed(1)) * 4.0
     res["weights"] = args.weights
-    res["objective"] = {"ohx_objective": args.objective, "ohx_huber_slope": args.huber_slope, "ohx_grow_pairs": args.pairs}
+    res["objective"] = {"ohx_objective": args.objective, "ohx_huber_slope": args.huber_slope, "ohx_quantile_alpha": args.quantile_alpha,
+                        "ohx_grow_pairs": args.pairs}
     res["regularisation"] = {"ohx_reg_alpha": args.reg_alpha, "ohx_max_delta_step": args.max_delta_step, "ohx_eval_metric": args.eval_metric}
     res["monotone_constraints"] = args.monotone
     res["colsample"] = {"ohx_colsample_bylevel": args.colsample_bylevel, "ohx_colsample_bynode": args.colsample_bynode}
@@ -281,6 +285,7 @@ def main():
         b = capi.Booster(model_buffer=model.image)
         b.set_param("ohx_objective", args.objective)
         b.set_param("ohx_huber_slope", repr(args.huber_slope))
+        b.set_param("ohx_quantile_alpha", repr(args.quantile_alpha))
         b.set_param("ohx_grow_pairs", args.pairs)
         if regularised:        # (left unset otherwise: the tool then also runs against a library from before the parameters)
             b.set_param("ohx_reg_alpha", repr(args.reg_alpha))
