@@ -577,6 +577,27 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_quantile_pick(con
   return found ? 1 : 0;
 }
 
+// grow_quantile.hpp plan_grow_quantile over the row_blocks of plan_grow_weighted, which does not depend on the columns: the
+// grid launch_grow_tree_quantile gives grow_quantile_pass_kernel.  info: [0] blocks of the pass kernel over the rows
+// (gridDim.x), [1] rows such a block takes per trip, [2] leaves a block holds, [3] leaf groups (gridDim.y), [4] row_blocks
+extern "C" __attribute__((visibility("default"))) int ohx_grow_quantile_plan(uint64_t nrow, int max_depth, int num_cus, uint64_t info[5]) {
+  try {
+    if (max_depth < 1 || max_depth > kGrowMaxDepth) throw OhxError("ohx_grow_quantile_plan: max_depth must be in 1..8");
+    if (nrow == 0) throw OhxError("ohx_grow_quantile_plan: no rows");
+    const uint32_t row_blocks = plan_grow_weighted(nrow, 1, 0, max_depth, num_cus).row_blocks;
+    const GrowQuantilePlan p = plan_grow_quantile(nrow, max_depth, row_blocks);
+    info[0] = p.blocks;
+    info[1] = kGrowHistBlock;
+    info[2] = p.group;
+    info[3] = p.groups;
+    info[4] = row_blocks;
+    return 0;
+  } catch (const std::exception& e) {
+    synth_set_error(e.what());
+    return -1;
+  }
+}
+
 // The whole select as the device runs it, with host counting: rows at node pos[r] with hessian hq[r] (0: the row does
 // not count) and residual y[r] - pred[r]; leaves[s] is the node of slot s.  Four passes of bins[slot][digit] over the rows
 // whose key carries their leaf's prefix, each followed by the picks.  found[s] = 0 where slot s holds no weight; else

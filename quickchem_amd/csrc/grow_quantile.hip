@@ -272,10 +272,6 @@ bool metric_args_sound(const GrowEvalArgs& a, float alpha, uint32_t blocks, uint
           (a.label_flag == kGrowFlagEvalLabel && a.weight_flag == kGrowFlagEvalWeight));
 }
 
-// leaves a block of the pass kernel holds, and the groups of a tree of this depth
-uint32_t pass_group(int max_depth) { return std::min<uint32_t>(kGrowQuantileGroup, 1u << max_depth); }
-uint32_t pass_groups(int max_depth) { return ((1u << max_depth) + pass_group(max_depth) - 1) / pass_group(max_depth); }
-
 }  // namespace
 
 int grow_lds_limits_quantile() { return raise_lds_limit(grow_quantile_pass_kernel, kGrowQuantileGroup * kLeafBins * 8); }
@@ -299,10 +295,8 @@ int launch_grow_tree_quantile(const GrowArgs& a, const GrowPairArgs& p, const Gr
   // the rows stand on their leaves; pred is the margin at the start of the round until the leaf kernel
   hipLaunchKernelGGL(grow_quantile_slots_kernel, dim3(1), dim3(kGrowMaxNodes), 0, stream, a, q, round);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  const uint32_t group = pass_group(a.max_depth), groups = pass_groups(a.max_depth);
-  // a block holds a CU's LDS: about a block a CU over all of gridDim.y (plan.row_blocks is kGrowRowBlocksPerCu a CU at most)
-  const uint64_t want = (a.nrow + kPassBlock - 1) / kPassBlock;
-  const uint32_t blocks = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(want, plan.row_blocks / (kGrowRowBlocksPerCu * groups)));
+  const GrowQuantilePlan shape = plan_grow_quantile(a.nrow, a.max_depth, plan.row_blocks);
+  const uint32_t group = shape.group, groups = shape.groups, blocks = shape.blocks;
   for (uint32_t pass = 0; pass < kGrowQuantilePasses; ++pass) {
     if ((e = hipMemsetAsync(q.hist, 0, (size_t)kGrowQuantileHistBytes, stream)) != hipSuccess) return e;
     hipLaunchKernelGGL(grow_quantile_pass_kernel, dim3(blocks, groups), dim3(kPassBlock), group * kLeafBins * 8, stream, a, q, pass, group);

@@ -72,6 +72,26 @@ OHX_GROW_HD inline float grow_quantile_value(uint32_t key, float eta) {
   return __builtin_bit_cast(float, cuts_unkey(key)) * eta;
 }
 
+// The launch shape of grow_quantile_pass_kernel for a tree of `max_depth` levels over `nrow` rows, where the streaming
+// kernels of the call take `row_blocks` blocks (GrowPlan::row_blocks: kGrowRowBlocksPerCu a CU at most).  A block holds
+// the bins of `group` leaves and a CU's LDS, so the grid is about a block a CU over all of its `groups`; a block takes
+// kGrowHistBlock rows a trip.
+struct GrowQuantilePlan {
+  uint32_t group = 0;    // leaves a block holds
+  uint32_t groups = 0;   // gridDim.y: group * groups >= 2^max_depth
+  uint32_t blocks = 0;   // gridDim.x, at least 1
+};
+inline GrowQuantilePlan plan_grow_quantile(uint64_t nrow, int max_depth, uint32_t row_blocks) {
+  GrowQuantilePlan p;
+  const uint32_t leaves = 1u << max_depth;
+  p.group = leaves < kGrowQuantileGroup ? leaves : kGrowQuantileGroup;
+  p.groups = (leaves + p.group - 1) / p.group;
+  const uint64_t want = (nrow + kGrowHistBlock - 1) / kGrowHistBlock, cap = row_blocks / (kGrowRowBlocksPerCu * p.groups);
+  const uint64_t blocks = want < cap ? want : cap;
+  p.blocks = (uint32_t)(blocks < 1 ? 1 : blocks);
+  return p;
+}
+
 #ifdef __HIPCC__
 // What the select keeps on the device between its kernels, one per call
 struct GrowQuantileState {

@@ -154,6 +154,7 @@ def _load():
         lib.ohx_grow_quantile_pick.argtypes = [C.c_void_p, C.c_uint32, C.c_float, C.c_void_p]
         lib.ohx_grow_quantile_leaves.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32,
                                                  C.c_float, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ohx_grow_quantile_plan.argtypes = [C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
         lib.ohx_grow_metric_row.argtypes = [C.c_uint32, C.c_float, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
         lib.ohx_grow_weighted_mean.argtypes = [C.c_void_p, C.c_uint64]
         lib.ohx_grow_weighted_mean.restype = C.c_double
@@ -814,6 +815,16 @@ def grow_quantile_leaves(pos, hq, pred, y, leaves, alpha: float, eta: float = 1.
                                             lv.size, float(alpha), float(eta), found.ctypes.data, key.ctypes.data, value.ctypes.data,
                                             W.ctypes.data))
     return found[:lv.size].astype(bool), key[:lv.size], value[:lv.size], W[:lv.size]
+
+
+def grow_quantile_plan(nrow: int, max_depth: int = 6, num_cus: int = 256):
+    """csrc/grow_quantile.hpp plan_grow_quantile, the grid launch_grow_tree_quantile gives grow_quantile_pass_kernel -> dict:
+    pass_blocks (over the rows) and pass_block_rows (rows such a block takes per trip), group (leaves a block holds), groups
+    (leaf groups, the grid's second dimension) and row_blocks (grow_plan_weighted's, which the blocks are cut from)."""
+    info = (C.c_uint64 * 5)()
+    _check(_load().ohx_grow_quantile_plan(nrow, max_depth, num_cus, info))
+    return {"pass_blocks": int(info[0]), "pass_block_rows": int(info[1]), "group": int(info[2]), "groups": int(info[3]),
+            "row_blocks": int(info[4])}
 
 
 def boost_weighted_rmse(p2: int, p1: int, p0: int, W: int) -> float:

@@ -1,5 +1,7 @@
 """An exact audit of one grown tree, and the cases of tests/test_grow_hyper_cpu.py and tests/test_gpu_grow_hyper.py (CASES,
-AUDITED) and of tests/test_grow_audit_cpu.py and tests/test_gpu_grow_audit.py (INLINE_CASES, COLSAMPLE_CASES, AUDITED_MORE).
+AUDITED) and of tests/test_grow_audit_cpu.py and tests/test_gpu_grow_audit.py (INLINE_CASES, COLSAMPLE_CASES, AUDITED_MORE),
+and for quantile trees, whose leaves are no Newton steps, a leaf check of its own and the cases of
+tests/test_grow_quantile_audit_cpu.py and tests/test_gpu_grow_quantile.py (Q_CASES), at the end of the module.
 
 The audit shares no operation order with include/ohxgb.h.  It is written from the regularised objective itself,
 
@@ -58,6 +60,7 @@ from tests import grow_deep_support as D
 from tests import grow_eval_support as E
 from tests import grow_mono_support as M
 from tests import grow_objective_support as O
+from tests import grow_quantile_support as Q
 from tests import grow_reg_support as RG
 from tests import grow_sampled_support as P
 from tests import grow_support as G
@@ -105,9 +108,13 @@ class Audit:
     None; kept: the features the tree may split on, or None for all, or a callable (p, depth) -> the features node p may
     split on (S_node(p) under "ohx_colsample_bylevel" / "ohx_colsample_bynode"; `node_sets` makes one); cuts = (cut_ptr,
     cut_values); tree: the nine arrays, as a restatement or as test_gpu_grow.held returns them; the hyper-parameters as the
-    call takes them (float32); constraints: an entry a feature, or fewer, or ()."""
+    call takes them (float32); constraints: an entry a feature, or fewer, or (); leaf: "newton", or None for a tree whose
+    leaves are not base_weight * eta (the `leaf` check is then left out, and every other check stays)."""
 
-    def __init__(self, bins, q, hq, in_bag, kept, cuts, tree, max_depth, eta, lam, gamma, mcw, alpha=0.0, m=0.0, constraints=()):
+    def __init__(self, bins, q, hq, in_bag, kept, cuts, tree, max_depth, eta, lam, gamma, mcw, alpha=0.0, m=0.0, constraints=(),
+                 leaf="newton"):
+        assert leaf in ("newton", None)
+        self.leaf_rule = leaf
         self.bins = np.asarray(bins)
         F, n = self.bins.shape
         keep = np.ones(n, bool) if in_bag is None else np.asarray(in_bag, bool)
@@ -338,7 +345,8 @@ class Audit:
         structure    the children, the parents, and a split value that is a cut of a feature the node may split on
         sum_hess     == float32(H * 2^-24), H the sum over the rows that reach the node
         base_weight  the float32 of a double within the bound of the exact minimiser of obj over the node's admissible set
-        leaf         value == base_weight * eta, one float32 multiply
+        leaf         value == base_weight * eta, one float32 multiply (left out at leaf=None: a quantile tree's leaves are
+                     no Newton steps, and quantile_leaf_violations below asks of them what the header does)
         admission    a split node is not at max_depth, has Hd >= 2 min_child_weight and chose an admitted candidate
         loss_chg     the float32 of a double within the bound of gain(L) + gain(R) - gain(P) at the exact minimisers
         gamma        a split's loss_chg, at the top of its bound, is above gamma
@@ -360,7 +368,7 @@ class Audit:
                 continue
             if t["left"][p] < 0:
                 leaf = t["base_weight"][p] * self.eta
-                if t["value"][p].view(np.uint32) != F32(leaf).view(np.uint32):
+                if self.leaf_rule == "newton" and t["value"][p].view(np.uint32) != F32(leaf).view(np.uint32):
                     out.append((p, "leaf", f"{t['value'][p]!r} is not {t['base_weight'][p]!r} * {self.eta!r}"))
                 if self.evaluated(p):
                     out += self._closure(p)
@@ -469,27 +477,42 @@ def node_sets(seed, i, tree_list, bylevel, bynode):
     return kept
 
 
-def round_inputs(kind, policy, setting, x, y, w, cuts, trees, r, objective="pseudohuber", bylevel=1.0, bynode=1.0, tree0=0,
-                 count_hess=False):
-    """What tree r of a call was grown on -> the keyword arguments of Audit without the tree: the pairs of `objective` from
-    the margins after the trees before r (walked on the host), the bag and the list of round i = tree0 + r, the node sets
-    where a fraction is below 1, the hyper-parameters.  count_hess: the plain and the Eval call, which count rows: unit
-    weights (hq = 2^24 a row), no bag, every feature, and min_child_rows where the others take min_child_weight."""
-    kw = hyper_more(kind, setting)
-    alpha, m, cons = POLICIES[policy]
-    nfeat, i = np.asarray(x).shape[1], tree0 + r
-    pred = np.full(len(y), O.BASE, F32)
+def margin_before(x, trees, r, start=None):
+    """The margin of every row at the start of round r of a call: `start` (the model's base where None) and the trees
+    before r, walked on the host, one float32 add a tree."""
+    pred = np.full(len(x), O.BASE, F32) if start is None else np.asarray(start, F32).copy()
     for t in trees[:r]:
         pred = pred + E.walk(t, x, float("nan"))
         assert pred.dtype == F32
-    q, hq = O.pairs(objective, SLOPE, pred, y, None if count_hess else w)
+    return pred
+
+
+def round_inputs(kind, policy, setting, x, y, w, cuts, trees, r, objective="pseudohuber", bylevel=1.0, bynode=1.0, tree0=0,
+                 count_hess=False, quantile_alpha=None, start=None):
+    """What tree r of a call was grown on -> the keyword arguments of Audit without the tree: the pairs of `objective` from
+    the margins after the trees before r (walked on the host), the bag and the list of round i = tree0 + r, the node sets
+    where a fraction is below 1, the hyper-parameters.  count_hess: the plain and the Eval call, which count rows: unit
+    weights (hq = 2^24 a row), no bag, every feature, and min_child_rows where the others take min_child_weight.
+    objective "quantile": the pinball pairs at quantile_alpha (grow_quantile_support.pairs), and leaf=None for the Audit.
+    start: the margins the call began from, where the model had trees (the base otherwise)."""
+    kw = hyper_more(kind, setting)
+    alpha, m, cons = POLICIES[policy]
+    nfeat, i = np.asarray(x).shape[1], tree0 + r
+    pred = margin_before(x, trees, r, start)
+    more = {}
+    if objective == "quantile":
+        assert policy == "pairs" and not count_hess and quantile_alpha is not None
+        q, hq = Q.pairs(quantile_alpha, pred, y, w)
+        more["leaf"] = None
+    else:
+        q, hq = O.pairs(objective, SLOPE, pred, y, None if count_hess else w)
     mcw = float(kw["min_child_rows"]) if count_hess else kw["min_child_weight"]
     kept = P.features(kw.get("seed", 0), i, nfeat, kw.get("colsample_bytree", 1.0))
     if bylevel != 1.0 or bynode != 1.0:
         kept = node_sets(kw.get("seed", 0), i, kept, bylevel, bynode)
     return dict(bins=G.bin_rows(x, float("nan"), cuts, nfeat), q=q, hq=hq, in_bag=P.bag(kw.get("seed", 0), i, len(y), kw.get("subsample", 1.0)),
                 kept=kept, cuts=cuts, max_depth=kw["max_depth"], eta=kw["eta"], lam=kw["reg_lambda"], gamma=kw["gamma"], mcw=mcw,
-                alpha=alpha, m=m, constraints=cons)
+                alpha=alpha, m=m, constraints=cons, **more)
 
 
 def audits(kind, policy, setting, x, y, w, cuts, trees, **more):
@@ -865,3 +888,146 @@ AUDITED_MORE = tuple(c for c in INLINE_CASES if "combination" in c[4]) \
 
 def more_id(case):
     return "-".join(str(v) for v in case[:6]) + ("" if case[6] == NO_FRACTIONS else "-%gx%g" % case[6])
+
+
+# ---- quantile trees: the leaf check, and the cases of tests/test_grow_quantile_audit_cpu.py and of the audited tests of
+# ---- tests/test_gpu_grow_quantile.py ----
+
+def quantile_leaf_verdict(value, base_weight, eta, r, hq, aq):
+    """One leaf of a quantile tree against the header, from the rows that count alone: r float32 their residuals
+    label - pred, hq their hessians (all > 0), aq = alpha_q.  -> None, or what is wrong.  eta is a power of two, so
+    value / eta is exact unless value is denormal, which is refused.  Python integers and comparisons: no sort, no radix
+    and no cumulated array (grow_quantile_support.covers sums the weights at or below a key, and below it)."""
+    eta = F32(eta)
+    mant, _ = math.frexp(float(eta))
+    assert mant == 0.5 and eta > 0, "an audited eta is a power of two"
+    value = F32(value)
+    if value != 0 and abs(float(value)) < 2.0 ** -126:
+        return f"{value!r} is denormal"
+    if len(hq) == 0:                                   # no weight: the split kernel's leaf stays
+        newton = F32(base_weight) * eta
+        return None if value.view(np.uint32) == F32(newton).view(np.uint32) else f"{value!r} is not {base_weight!r} * {eta!r} on a leaf without weight"
+    assert all(int(h) > 0 for h in hq)
+    resid = F32(float(value) / float(eta))             # exact: a power of two and no denormal
+    assert F32(resid * eta).view(np.uint32) == value.view(np.uint32) or value == 0
+    k = Q.keys(np.asarray(r, F32))
+    kstar = int(Q.keys(np.asarray([resid], F32))[0])
+    if kstar not in set(int(v) for v in k):
+        return f"{value!r} / {eta!r} is the residual of no row that counts"
+    if Q.leaf_value(kstar, eta).view(np.uint32) != value.view(np.uint32):
+        return f"{value!r} is not {Q.unkey(kstar)!r} * {eta!r}"             # (-0.0 where the header says +0.0)
+    if not Q.covers(k, np.asarray(hq, np.uint64), aq, kstar):
+        return f"{resid!r} is not the lower {aq} / 2^24 quantile of the leaf's residuals"
+    return None
+
+
+def quantile_leaf_violations(a, pred, y, alpha):
+    """The leaves of the quantile tree under the Audit `a` -> a list of (node, "quantile_leaf", text), empty for a sound
+    tree.  pos is the audit's own walk of the tree over the binned rows (a.rows), the rows that count those of a.hq > 0
+    (a.hq is 0 out of the bag), the residuals label - pred in float32 at the margins `pred` of the start of the round."""
+    r = np.asarray(y, F32) - np.asarray(pred, F32)
+    assert r.dtype == F32
+    aq, out = Q.alpha_q(alpha), []
+    for p in a.order:
+        if a.t["left"][p] >= 0 or a.rows[p] is None:
+            continue
+        rows = a.rows[p][a.hq[a.rows[p]] > 0]
+        what = quantile_leaf_verdict(a.t["value"][p], a.t["base_weight"][p], a.eta, r[rows], a.hq[rows], aq)
+        if what is not None:
+            out.append((p, "quantile_leaf", what))
+    return out
+
+
+Q_ROWS, Q_HELD, Q_SEED, Q_DEPTH = 4097, 700, 3310, 6
+Q_SETTINGS = {"g0.5-l0.5-mcw8-eta1/32": dict(gamma=0.5, reg_lambda=0.5, min_child_weight=8.0, eta=0.03125),
+              "g2-l0-mcw40-eta1": dict(gamma=2.0, reg_lambda=0.0, min_child_weight=40.0, eta=1.0),
+              "lambda0.5": dict(reg_lambda=0.5)}
+
+
+def q_hyper(case):
+    """The keyword arguments of the binding for a quantile case (kind, form, alpha, setting, seed): kind_kw's (for the
+    sampled kind subsample = colsample_bytree = 0.5 and seed 11), gamma 0, two rounds, and what the setting changes."""
+    return hyper(case[0], Q_SETTINGS[case[3]])
+
+
+def q_restated(case, setting=None):
+    """-> (x, y, w, cuts, ev, the dict of grow_quantile_support.boost), computed once (not to be changed)."""
+    kind, _, alpha, _, seed = case
+    kw = hyper(kind, Q_SETTINGS[case[3]] if setting is None else setting)
+    return Q.restated("quantile", alpha, Q_ROWS, seed, kw["max_depth"], bins=BINS, nfeat=NFEAT, rounds=kw["rounds"], held_out=Q_HELD,
+                      subsample=kw.get("subsample", 1.0), colsample=kw.get("colsample_bytree", 1.0), draw_seed=kw.get("seed", 0),
+                      lam=kw["reg_lambda"], mcw=kw["min_child_weight"], eta=kw["eta"], gamma=kw["gamma"])
+
+
+def q_audits(case, x, y, w, cuts, trees):
+    """-> per tree (the Audit, the margins at the start of its round): restated trees, or the library's."""
+    return [(Audit(tree=t, **round_inputs(case[0], "pairs", q_hyper(case), x, y, w, cuts, trees, r, objective="quantile",
+                                          quantile_alpha=case[2])), margin_before(x, trees, r)) for r, t in enumerate(trees)]
+
+
+@functools.lru_cache(maxsize=None)
+def q_profile(case):
+    """`profile` for a quantile case, and per tree what its leaves hold -> (per tree the list of node dicts, per tree
+    (leaves with a row out of the bag, leaves with a row of weight 0 in the bag))."""
+    x, y, w, cuts, ev, want = q_restated(case)
+    kw = q_hyper(case)
+    out, held = [], []
+    for (a, _), t in zip(q_audits(case, x, y, w, cuts, want["all_trees"]), want["all_trees"]):
+        ncuts = [(a.cut_ptr[f + 1] - a.cut_ptr[f]) if f in a.kept else 0 for f in range(NFEAT)]
+        nodes = []
+        for p in range(a.size):
+            nd = dict(level=a.depth[p], split=bool(t["left"][p] >= 0), best=None, free_best=None,
+                      evaluates=W.hess(a.H[p]) >= 2.0 * float(F32(kw["min_child_weight"])))
+            if a.depth[p] < kw["max_depth"]:
+                Gh, Hh = (np.asarray(h, dtype) for h, dtype in zip(a.histograms(p), (np.int64, np.uint64)))
+                nd["best"] = W.best_split(Gh, Hh, ncuts, a.G[p], a.H[p], kw["reg_lambda"], kw["min_child_weight"])
+                if kw["min_child_weight"] > 0:
+                    nd["free_best"] = W.best_split(Gh, Hh, ncuts, a.G[p], a.H[p], kw["reg_lambda"], 0.0)
+            nodes.append(nd)
+        out.append(nodes)
+        in_bag = P.bag(kw.get("seed", 0), len(held), len(y), kw.get("subsample", 1.0))
+        leaves = [p for p in a.order if t["left"][p] < 0]
+        held.append((sum(1 for p in leaves if not np.all(in_bag[a.rows[p]])),
+                     sum(1 for p in leaves if np.any(in_bag[a.rows[p]] & (np.asarray(w)[a.rows[p]] == 0)))))
+    return out, held
+
+
+def q_reaches(case):
+    """What a quantile case reaches, from the restatement alone -> dict(mixed: a level with a split beside a node that
+    gamma closed, moved: a split that min_child_weight moved, out_of_bag, weightless: leaves per tree that hold such rows)."""
+    kw = q_hyper(case)
+    trees, held = q_profile(case)
+    gamma = float(F32(kw["gamma"]))
+    levels = [[[nd for nd in nodes if nd["level"] == d] for d in range(kw["max_depth"])] for nodes in trees]
+
+    def closed_by_gamma(nd):
+        return not nd["split"] and nd["evaluates"] and nd["best"] is not None
+
+    for nodes in trees:
+        assert all(not nd["best"][0] > gamma for nd in nodes if closed_by_gamma(nd))
+    inner = [nd for nodes in trees for nd in nodes if nd["level"] < kw["max_depth"]]
+    return dict(mixed=gamma > 0 and any(any(nd["split"] for nd in level) and any(closed_by_gamma(nd) for nd in level)
+                                        for tree in levels for level in tree),
+                moved=kw["min_child_weight"] > 0 and any(nd["split"] and nd["best"][1:4] != nd["free_best"][1:4] for nd in inner),
+                out_of_bag=[h[0] for h in held], weightless=[h[1] for h in held])
+
+
+def q_id(case):
+    return "-".join(("%g" % v) if isinstance(v, float) else str(v) for v in case)
+
+
+# (kind, form, alpha, setting, seed).  The form is the one the bit-for-bit comparison takes; the audit of the library's own
+# trees takes the other.  Both kinds at the three alphas under the first setting.  Under the second eta is 1 and lambda 0: at
+# lambda 0 the gain of a split does not depend on alpha (G = W+ - alpha H, and the terms in alpha cancel between the children
+# and the parent), and after one round at eta 1 every leaf stands on its own quantile, so that at alpha 0.05 and 0.95 the
+# second tree is a single leaf.  The call then has the first tree's splits alone: at seed 3310 the weighted call has 7 decided
+# split nodes and the sampled one 3; at 3381 the weighted call has 10, and no seed from 3310 to 3599 brings the sampled call
+# at alpha 0.05 or 0.95 to 10 (its first tree has about ten leaves), so the sampled kind stands under that setting at alpha
+# 0.5, at seed 3341, where min_child_weight moves a split of it (at 3310 it moves none and 6 are decided).
+_Q_FIRST, _Q_SECOND = "g0.5-l0.5-mcw8-eta1/32", "g2-l0-mcw40-eta1"
+Q_CASES = (
+    ("weighted", "host", 0.05, _Q_FIRST, Q_SEED), ("weighted", "device", 0.5, _Q_FIRST, Q_SEED), ("weighted", "host", 0.95, _Q_FIRST, Q_SEED),
+    ("sampled", "device", 0.05, _Q_FIRST, Q_SEED), ("sampled", "host", 0.5, _Q_FIRST, Q_SEED), ("sampled", "device", 0.95, _Q_FIRST, Q_SEED),
+    ("weighted", "device", 0.05, _Q_SECOND, 3381), ("weighted", "host", 0.5, _Q_SECOND, 3341), ("weighted", "device", 0.95, _Q_SECOND, 3381),
+    ("sampled", "host", 0.5, _Q_SECOND, 3341),
+    ("sampled", "device", 0.5, "lambda0.5", Q_SEED), ("weighted", "host", 0.05, "lambda0.5", Q_SEED))

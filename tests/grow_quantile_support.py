@@ -278,6 +278,20 @@ def restated(objective, alpha, n, seed, max_depth, bins=32, nfeat=3, rounds=2, h
     return x, y, w, cuts, ev, want
 
 
+@functools.lru_cache(maxsize=None)
+def tie_case(n=1300, held_out=400, seed=3330, alpha=0.5, rounds=3):
+    """A call whose held-out pinball sum does not move: four labels in five equal the base, so the root's quantile is the
+    residual +0.0, and gamma is large enough that no round splits.  Every tree is one leaf of value +0.0, the margins stay
+    where they were, and the sum after round 1 ties with the sum before it: under patience = 1 that is no improvement.
+    -> (x, y, w, cuts, ev, the dict of boost; not to be changed)."""
+    x, y, w, cuts, ev = inputs(n, seed, 3, 32, held_out)
+    at_base = np.random.default_rng(seed + 1).random(n) < 0.8
+    y = np.where(at_base, F32(BASE), y).astype(F32)
+    want = boost("quantile", alpha, np.full(n, BASE, F32), x, float("nan"), y, w, cuts, 3, eval_set=ev, eval_pred=np.full(held_out, BASE, F32),
+                 rounds=rounds, patience=1, max_depth=6, eta=0.125, lam=1.0, gamma=1e6, min_child_weight=0.0, metric="quantile")
+    return x, y, w, cuts, ev, want
+
+
 # ---- crafted leaves: the edges of the select ----
 
 BELOW_256 = np.nextafter(F32(256.0), F32(0.0))

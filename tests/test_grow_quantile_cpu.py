@@ -219,6 +219,38 @@ def test_one_pick_over_a_leafs_bins():
     assert synth.grow_quantile_pick(bins, 0, 0.5)[0] == 2, "one unit short of half, at sums near 2^63"
 
 
+# ---- the launch shape of the pass kernel ----
+
+def test_the_plan_of_the_pass_kernel():
+    """synth.grow_quantile_plan is the function launch_grow_tree_quantile calls (csrc/grow_quantile.hpp plan_grow_quantile).
+    The figures below are worked out by hand from its text: a block holds min(64, 2^depth) leaves, and the blocks over the
+    rows are row_blocks / (8 * groups), at least one and no more than the rows need at 1024 a block."""
+    for depth in range(1, 9):
+        assert synth.grow_quantile_plan(1, depth, 256) == dict(pass_blocks=1, pass_block_rows=1024, group=min(64, 1 << depth),
+                                                               groups=(1, 1, 1, 1, 1, 1, 2, 4)[depth - 1], row_blocks=1), depth
+    # 4097 rows are 17 blocks of 256 and 5 of 1024: 17 // 8 = 2 of them with one group, 17 // 16 = 1 with two, 17 // 32 = 0 -> 1
+    for depth, group, groups, blocks in ((1, 2, 1, 2), (6, 64, 1, 2), (7, 64, 2, 1), (8, 64, 4, 1)):
+        assert synth.grow_quantile_plan(4097, depth, 256) == dict(pass_blocks=blocks, pass_block_rows=1024, group=group, groups=groups,
+                                                                  row_blocks=17), depth
+    # 2^31 rows on 256 CUs: 2048 row blocks, a block a CU over all groups
+    for depth, blocks in ((1, 256), (6, 256), (7, 128), (8, 64)):
+        p = synth.grow_quantile_plan(1 << 31, depth, 256)
+        assert (p["pass_blocks"], p["row_blocks"]) == (blocks, 2048) and p["pass_blocks"] * p["groups"] == 256, depth
+    for cus in (1, 2, 7, 8, 64, 104, 256, 304):
+        for nrow in (1, 63, 1024, 1025, 4097, 262144, 262145, 528450, 55987200, 1 << 31):
+            rows = synth.grow_plan_weighted(nrow, 3, 0, 6, cus)["row_blocks"]
+            assert rows == synth.grow_plan(nrow, 3, 0, 6, cus)["row_blocks"], "the row blocks do not depend on the histograms' bins"
+            for depth in range(1, 9):
+                p = synth.grow_quantile_plan(nrow, depth, cus)
+                assert p["pass_blocks"] >= 1 and p["groups"] * p["group"] >= 1 << depth, (cus, nrow, depth)
+                assert p["group"] <= 64 and p["groups"] * p["group"] < (1 << depth) + p["group"], "no empty group"
+                assert p["row_blocks"] == rows and p["pass_block_rows"] == 1024
+                assert p["pass_blocks"] == max(1, min((nrow + 1023) // 1024, rows // (8 * p["groups"]))), (cus, nrow, depth)
+    for bad in (dict(nrow=0, max_depth=6), dict(nrow=4097, max_depth=0), dict(nrow=4097, max_depth=9)):
+        with pytest.raises(Exception, match="ohx_grow_quantile_plan"):
+            synth.grow_quantile_plan(num_cus=256, **bad)
+
+
 # ---- the metric ----
 
 def test_the_pinball_term_the_sums_and_the_reported_value():
