@@ -66,7 +66,7 @@ def call(torch, b, kind, x, y, w, cuts, ev, device=False, grid=False, **kw):
                 tew = torch.from_numpy(ev[3]).to("cuda") if ev[3] is not None else None
         s.synchronize()
         d = capi.DMatrix(device_ptr=tx.data_ptr(), nrow=x.shape[0], ncol=x.shape[1], missing=NAN)
-        ed = capi.DMatrix(device_ptr=tex.data_ptr(), nrow=ev[0].shape[0], ncol=ev[0].shape[1], missing=NAN) if ev is not None else None
+        ed = capi.DMatrix(device_ptr=tex.data_ptr(), nrow=ev[0].shape[0], ncol=ev[0].shape[1], missing=ev[1]) if ev is not None else None
         es = (ed, tey.data_ptr(), len(ev[2]), tew.data_ptr() if tew is not None else 0) if ev is not None else None
         got = getattr(b, "boost_trees_" + kind + "_device")(d, ty.data_ptr(), len(y), cuts, weights_ptr=tw.data_ptr() if tw is not None else 0,
                                                           eval_set=es, stream=s.cuda_stream, **kw)
