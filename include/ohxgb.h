@@ -267,6 +267,25 @@ int XGBoosterPredict(BoosterHandle handle, DMatrixHandle dmat, int option_mask, 
  *                     ...Deep[Device] return -1 before anything is enqueued; the message names
  *                     OHXBoosterBoostTreesSampled, and the forest and every output are untouched.
  *                     OHXBoosterRefitLeaves chooses no split and is unaffected
+ *   "ohx_interaction_constraints" the interaction constraints of boosting: which features may act together in one
+ *                     tree.  The value is a list of groups, `[` groups `]` with the groups separated by `,`; each group
+ *                     is `[` ids `]` with the ids separated by `,`; each id is a decimal integer without sign.  Spaces
+ *                     and tabs between tokens are ignored, so Python's str([[0, 2], [1, 3, 4]]) is valid; [] is the
+ *                     default, none.  At most 64 groups; every group is non-empty and its ids are distinct; every id is
+ *                     below 128; a feature may appear in several groups.  Anything else ("", [[]], [0, 1], [[0, 0]],
+ *                     [[1.0]], [[-1]], a trailing comma, 65 groups, an id of 128) returns -1, the message names
+ *                     "ohx_interaction_constraints", and the handle keeps its previous value.  Kept on the handle and
+ *                     written into no model file; the name without the prefix is xgboost's and stays ignored.  It acts
+ *                     on OHXBoosterBoostTreesWeighted, ...Sampled, ...Deep and ...DeepSampled as defined with the
+ *                     Weighted call below (docs/35_interaction_constraints.md).  An id >= num_feature makes every boost
+ *                     call return -1 before anything is enqueued.  The constraints are inactive when the list is empty
+ *                     or when some group holds every feature 0 .. num_feature - 1: such a call launches nothing new and
+ *                     produces the default's bytes.  While they are active, OHXBoosterBoostTrees[Device] and
+ *                     OHXBoosterBoostTreesEval[Device] (row counts; their split kernels keep no feature sets; the
+ *                     message names OHXBoosterBoostTreesWeighted), ohx_objective=quantile, and ohx_colsample_bylevel or
+ *                     ohx_colsample_bynode where they take a feature away (n_lvl != n_sel or n_node != n_lvl) return -1
+ *                     before anything is enqueued; every message names the parameter, and the forest and every output
+ *                     are untouched.  OHXBoosterRefitLeaves chooses no split and is unaffected
  * None of them changes a prediction.
  * xgboost's own parameter names ("nthread", "predictor", ...) are accepted and
  * ignored. */
@@ -834,6 +853,35 @@ int OHXBoosterBoostTreesEvalDevice(BoosterHandle handle, DMatrixHandle dmat, con
  * non-decreasing (c_f = 1) or non-increasing (c_f = -1) in x_f over non-missing values, with every other feature fixed;
  * a row whose x_f is missing goes where default_left sends it and is outside the claim.  Parity with libxgboost is not
  * pinned; the text above is the definition.  The same holds for OHXBoosterBoostTreesSampled, ...Deep and ...DeepSampled.
+ * Interaction constraints ("ohx_interaction_constraints": a list of groups of feature ids).  What is stated above is no
+ * group.  The constraints are active unless the list is empty or some group holds every feature 0 .. F - 1, F the
+ * booster's num_feature.  While they are active every node carries two 128-bit sets of the booster's feature ids:
+ *   P(root) = {}            A(root) = every feature 0 .. F - 1
+ *   p splits on f, children c:   P(c) = P(p) + {f}
+ *                                A(c) = P(c) + the union of every group g with P(c) a subset of g
+ *   candidates of node p:  the (f, j, dl) the call has without the constraints, with f additionally in A(p)
+ * Under a tree's feature list the candidates are the list's intersection with A(p).  Everything else is unchanged: the
+ * bag and the integer histograms; the total order (f, j, dl) with the original f, and the ties; which splits are
+ * admitted, which nodes are evaluated, and min_child_weight; the gain form of whichever of the objective, the
+ * regularisation and the monotone constraints is active; the node's sums, sum_hess and base_weight; the node numbering
+ * and the records; the refusals of a root with H == 0; the metrics, the stop rule and all or nothing; both forms, and
+ * "not capturable".  A node with no candidate in A(p) is a leaf.  A feature in no group, once split on, admits only the
+ * path's own features below it.  Parity with libxgboost is not pinned; the text above is the definition.
+ *   C1.  With inactive constraints the forest, XGBoosterSaveModel's bytes in all three formats and both metric arrays
+ *     equal those of the same call with the parameter never set, and nothing of the kernels of interaction constraints is
+ *     launched, set or loaded.
+ *   C2.  In every new tree, every split node p has its feature in A(p), with A derived from the features on p's path by
+ *     the text above.  In particular the features on any root-to-leaf path lie together in one group, or are a single
+ *     feature.
+ *   C3.  With every feature in a group of its own, every tree splits on one feature only.
+ *   C4.  The result depends on neither the row order, the launch shape, the batch size of the deep levels, the form nor
+ *     the stream.
+ * They compose with squared error and pseudo-Huber, ohx_reg_alpha, ohx_max_delta_step, ohx_monotone_constraints, all
+ * metrics, weights, a held-out set and patience, and with any subsample and colsample_bytree.  Refused while active, at
+ * the top and with nothing enqueued: ohx_colsample_bylevel or ohx_colsample_bynode taking a feature away,
+ * ohx_objective=quantile, and the two calls that keep row counts.  The sets of the tree at hand, 32 bytes a node of the
+ * call's node stride, and the groups are part of the grow state; where they cannot be allocated the call returns -1 and
+ * the message names the bytes.  The same holds for OHXBoosterBoostTreesSampled, ...Deep and ...DeepSampled.
  * The metric ("ohx_eval_metric").  What is stated above is rmse.  For one row z = pred - y in float32 (refused as above if
  * not finite or |z| >= 256), hq = rint(w * 2^24), delta = "ohx_huber_slope" whatever the objective, and
  *   rmse         sq = e * e,  e = (int64) rint(z * 2^24)

@@ -568,7 +568,7 @@ class Booster:
         return self._eval_result(train, held, run, best, n, ed is not None)
 
     def _set_objective(self, objective, huber_slope, quantile_alpha=None, reg_alpha=None, max_delta_step=None, eval_metric=None,
-                       monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> None:
+                       monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None, interaction_constraints=None) -> None:
         """objective= and huber_slope= of the boost_trees_* methods: "squarederror", "pseudohuber" and its slope, or
         "quantile", set on the handle by set_param("ohx_objective") and set_param("ohx_huber_slope") and kept for later
         calls (they go into no model file).  quantile_alpha= is alpha of the quantile objective and metric, set by
@@ -578,7 +578,13 @@ class Booster:
         "ohx_eval_metric".  monotone_constraints= is a sequence of ints in {-1, 0, 1}, one a feature from feature 0 on, or
         the string itself ("(1,0,-1)"), set by "ohx_monotone_constraints"; () is none.  colsample_bylevel= and
         colsample_bynode= (the calls that carry a seed take them) are fractions in (0, 1], set by "ohx_colsample_bylevel" and
-        "ohx_colsample_bynode".  None leaves the handle's setting."""
+        "ohx_colsample_bynode".  interaction_constraints= is a list of lists of feature ids, the groups of features that may
+        act together in one tree, or the string itself ("[[0, 2], [1, 3, 4]]"), set by "ohx_interaction_constraints"; [] is
+        none.  None leaves the handle's setting."""
+        if interaction_constraints is not None:
+            if not isinstance(interaction_constraints, str):
+                interaction_constraints = "[" + ",".join("[" + ",".join(str(int(f)) for f in g) + "]" for g in interaction_constraints) + "]"
+            self.set_param("ohx_interaction_constraints", interaction_constraints)
         if colsample_bylevel is not None:
             self.set_param("ohx_colsample_bylevel", repr(float(colsample_bylevel)))
         if colsample_bynode is not None:
@@ -604,11 +610,12 @@ class Booster:
                              max_depth: int = 6, eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
                              min_child_weight: float = 1.0, patience: int = 0,
                              *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, interaction_constraints=None) -> dict:
         """OHXBoosterBoostTreesWeighted: boost_trees_eval with a weight per row (0 <= w < 256; None: all 1) in the
         histograms, the leaves and both RMSEs.  eval_set = (DMatrix, labels[, weights]).  min_child_weight stands where
         min_child_rows stood.  -> the dict of boost_trees_eval."""
-        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+                            interaction_constraints=interaction_constraints)
         return self._boost_weighted("OHXBoosterBoostTreesWeighted", dmat, labels, cuts, weights, eval_set, rounds, max_depth,
                                     eta, reg_lambda, gamma, min_child_weight, patience)
 
@@ -643,11 +650,12 @@ class Booster:
                                     reg_lambda: float = 1.0, gamma: float = 0.0, min_child_weight: float = 1.0,
                                     patience: int = 0, stream: int = 0,
                                     *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, interaction_constraints=None) -> dict:
         """The same with labels and weights in device memory: labels_ptr, weights_ptr (0: all 1) and
         eval_set = (DMatrix, eval_labels_ptr, eval_nlabel[, eval_weights_ptr]) are torch data_ptr()s of float32 ready
         on `stream`; the cuts stay host arrays.  Enqueues on `stream`; waits as boost_trees_eval_device (not capturable)."""
-        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+                            interaction_constraints=interaction_constraints)
         return self._boost_weighted_device("OHXBoosterBoostTreesWeightedDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
                                            eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, patience,
                                            stream)
@@ -671,11 +679,12 @@ class Booster:
                          max_depth: int = 12, eta: float = 0.3, reg_lambda: float = 1.0, gamma: float = 0.0,
                          min_child_weight: float = 1.0, patience: int = 0,
                          *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, interaction_constraints=None) -> dict:
         """OHXBoosterBoostTreesDeep: boost_trees_weighted with max_depth up to 18.  From level 8 on a level's histograms
         are kept in HBM for a batch of nodes at a time, and the call waits once a level for the ids of the open nodes.
         Up to depth 8 it is boost_trees_weighted itself.  -> the dict of boost_trees_eval."""
-        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+                            interaction_constraints=interaction_constraints)
         return self._boost_weighted("OHXBoosterBoostTreesDeep", dmat, labels, cuts, weights, eval_set, rounds, max_depth, eta,
                                     reg_lambda, gamma, min_child_weight, patience)
 
@@ -684,10 +693,11 @@ class Booster:
                                 reg_lambda: float = 1.0, gamma: float = 0.0, min_child_weight: float = 1.0,
                                 patience: int = 0, stream: int = 0,
                                 *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, interaction_constraints=None) -> dict:
         """The same with labels and weights in device memory, as boost_trees_weighted_device takes them.  With
         max_depth > 8 the call waits for `stream` once a level from level 7 on."""
-        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints)
+        self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
+                            interaction_constraints=interaction_constraints)
         return self._boost_weighted_device("OHXBoosterBoostTreesDeepDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
                                            eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, patience,
                                            stream)
@@ -697,13 +707,14 @@ class Booster:
                             min_child_weight: float = 1.0, subsample: float = 1.0, colsample_bytree: float = 1.0,
                             seed: int = 0, patience: int = 0,
                             *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None,
+                             interaction_constraints=None) -> dict:
         """OHXBoosterBoostTreesSampled: boost_trees_weighted where every tree is fitted to a fresh bag of the rows
         (a fraction `subsample`) and may split on a fresh set of the features (a fraction `colsample_bytree`), both
         drawn on the GPU from `seed` (a uint64) and the tree's index in the forest.  colsample_bylevel= and
         colsample_bynode= narrow the tree's features again for every level and every node.  -> the dict of boost_trees_eval."""
         self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
-                            colsample_bylevel, colsample_bynode)
+                            colsample_bylevel, colsample_bynode, interaction_constraints=interaction_constraints)
         return self._boost_sampled("OHXBoosterBoostTreesSampled", dmat, labels, cuts, weights, eval_set, rounds, max_depth, eta,
                                    reg_lambda, gamma, min_child_weight, subsample, colsample_bytree, seed, patience)
 
@@ -740,10 +751,11 @@ class Booster:
                                    subsample: float = 1.0, colsample_bytree: float = 1.0, seed: int = 0,
                                    patience: int = 0, stream: int = 0,
                                    *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None,
+                             interaction_constraints=None) -> dict:
         """The same with labels and weights in device memory, as boost_trees_weighted_device takes them."""
         self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
-                            colsample_bylevel, colsample_bynode)
+                            colsample_bylevel, colsample_bynode, interaction_constraints=interaction_constraints)
         return self._boost_sampled_device("OHXBoosterBoostTreesSampledDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
                                           eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, subsample,
                                           colsample_bytree, seed, patience, stream)
@@ -768,13 +780,14 @@ class Booster:
                                  min_child_weight: float = 1.0, subsample: float = 1.0, colsample_bytree: float = 1.0,
                                  seed: int = 0, patience: int = 0,
                                  *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None,
+                             interaction_constraints=None) -> dict:
         """OHXBoosterBoostTreesDeepSampled: boost_trees_sampled with max_depth up to 18.  From level 8 on a level's
         histograms are kept in HBM for a batch of nodes at a time, over the bag's rows and the tree's features only, and
         the call waits once a level for the ids of the open nodes.  Up to depth 8 it is boost_trees_sampled itself; with
         both fractions 1 it is boost_trees_deep.  -> the dict of boost_trees_eval."""
         self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
-                            colsample_bylevel, colsample_bynode)
+                            colsample_bylevel, colsample_bynode, interaction_constraints=interaction_constraints)
         return self._boost_sampled("OHXBoosterBoostTreesDeepSampled", dmat, labels, cuts, weights, eval_set, rounds, max_depth,
                                    eta, reg_lambda, gamma, min_child_weight, subsample, colsample_bytree, seed, patience)
 
@@ -784,11 +797,12 @@ class Booster:
                                         subsample: float = 1.0, colsample_bytree: float = 1.0, seed: int = 0,
                                         patience: int = 0, stream: int = 0,
                                         *, objective=None, huber_slope=None, quantile_alpha=None, reg_alpha=None, max_delta_step=None,
-                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None) -> dict:
+                             eval_metric=None, monotone_constraints=None, colsample_bylevel=None, colsample_bynode=None,
+                             interaction_constraints=None) -> dict:
         """The same with labels and weights in device memory, as boost_trees_weighted_device takes them.  With
         max_depth > 8 the call waits for `stream` once a level from level 7 on."""
         self._set_objective(objective, huber_slope, quantile_alpha, reg_alpha, max_delta_step, eval_metric, monotone_constraints,
-                            colsample_bylevel, colsample_bynode)
+                            colsample_bylevel, colsample_bynode, interaction_constraints=interaction_constraints)
         return self._boost_sampled_device("OHXBoosterBoostTreesDeepSampledDevice", dmat, labels_ptr, nlabel, cuts, weights_ptr,
                                           eval_set, rounds, max_depth, eta, reg_lambda, gamma, min_child_weight, subsample,
                                           colsample_bytree, seed, patience, stream)

@@ -700,12 +700,20 @@ struct GrowState {
   // allocated only where a fraction takes a feature away
   DevBuf<uint8_t> d_level_lists;
   PinnedBuf<uint8_t> h_level_lists;
+  // interaction constraints (grow_interact.hip): the sets of the tree at hand, four words a node of the call's node stride
+  // (the features on its path, then those it may split on), and the groups, two words each; allocated only where the
+  // constraints are active
+  DevBuf<uint64_t> d_interact_sets;
+  DevBuf<uint64_t> d_interact_groups;
+  PinnedBuf<uint64_t> h_interact_groups;
   // the quantile objective (grow_quantile.hip): the bins of the select's pass at hand, 256 leaves x 256 digits x 8 bytes,
   // and its leaf table; allocated only where the objective runs
   DevBuf<uint8_t> d_quantile;
   void release_device() {
     d_quantile.release();
     d_level_lists.release();
+    d_interact_sets.release();
+    d_interact_groups.release();
     d_mono_bounds.release();
     d_mono_constraints.release();
     d_pair_q.release();
@@ -887,6 +895,9 @@ struct BoosterObj {
   // (docs/29_colsample_level_node.md): "ohx_colsample_bylevel" and "ohx_colsample_bynode", the fraction of a tree's features a
   // level sees and of a level's a node does; 1 is the default
   float grow_bylevel = 1.0f, grow_bynode = 1.0f;
+  // (docs/35_interaction_constraints.md): "ohx_interaction_constraints", the groups as two words of feature bits each; empty
+  // is the default
+  std::vector<uint64_t> grow_interact;
   std::unique_ptr<RefitState> refit;
   std::unique_ptr<GrowState> grow;
 };
@@ -2153,6 +2164,15 @@ std::vector<int8_t> parse_monotone_constraints(const char* value) {
   return c;
 }
 
+// "ohx_interaction_constraints": grow.cpp's grow_interact_parse; a refused value throws and leaves the caller's as it was.
+std::vector<uint64_t> parse_interaction_constraints(const char* value) {
+  std::vector<uint64_t> groups;
+  if (!grow_interact_parse(value, &groups))
+    throw OhxError("ohx_interaction_constraints must be a list of groups such as [[0,2],[1,3,4]]: at most 64 groups in brackets, "
+                   "separated by commas, each a non-empty list of distinct feature ids below 128 in brackets; [] sets none");
+  return groups;
+}
+
 // ---- leaf refit (refit.hpp) ----
 
 // Both forms of OHXBoosterRefitLeaves.  The refusals that need neither a matrix nor a device come first, in the
@@ -2411,7 +2431,10 @@ struct BoostKind {
   // column-sampled (ohx_colsample_bylevel or ohx_colsample_bynode takes a feature away from a level or a node; then
   // `pairs` holds too): the pair path over the level's list with grow_colsample.hip's split launches, under the policy
   // `regularised` / `constrained` name or the fixed-point one.  Without it nothing of grow_colsample.hip is touched.
-  bool regularised = false, constrained = false, colsampled = false;
+  // interacting (ohx_interaction_constraints takes a candidate away from some node; then `pairs` holds too, and
+  // `colsampled` and `quantile` do not): the pair path with grow_interact.hip's split launches, under the policy
+  // `regularised` / `constrained` name or the fixed-point one.  Without it nothing of grow_interact.hip is touched.
+  bool regularised = false, constrained = false, colsampled = false, interacting = false;
   GrowPairSplits reg_splits;
   uint32_t metric = kGrowMetricRmse;
   float slope = 1.0f;                  // delta of the pseudohuber metric, alpha of the quantile one
@@ -2420,7 +2443,7 @@ struct BoostKind {
   // then the leaf kernel.  Without it, and without the quantile metric, nothing of grow_quantile.hip is touched.
   bool quantile = false;
   GrowQuantileArgs quantile_args;
-  const GrowPairSplits* splits() const { return constrained || regularised || colsampled ? &reg_splits : nullptr; }
+  const GrowPairSplits* splits() const { return constrained || regularised || colsampled || interacting ? &reg_splits : nullptr; }
   bool wide() const { return which != Plain; }
   // The call's one plan, asked for once: the level loop over `cols` histogram columns - F itself, or the n_sel features
   // a tree of a sampled call sees (compact histograms and candidates) - the streaming kernels, which do not depend on
@@ -2538,6 +2561,25 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (b.grow_mono.size() > (size_t)b.forest.num_feature)
     throw OhxError(w0 + ": ohx_monotone_constraints has " + std::to_string(b.grow_mono.size()) + " entries but the booster " +
                    std::to_string(b.forest.num_feature) + " features; nothing was enqueued and the forest is unchanged");
+  // interaction constraints: the ids' range, then - while the groups take a candidate away from some node - what they do
+  // not compose with (docs/35_interaction_constraints.md)
+  const uint32_t ngroups = (uint32_t)(b.grow_interact.size() / 2);
+  for (uint32_t f = b.forest.num_feature; f < kGrowMaxFeatures; ++f)
+    for (uint32_t k = 0; k < ngroups; ++k)
+      if (grow_interact_has(b.grow_interact.data() + 2 * k, f))
+        throw OhxError(w0 + ": ohx_interaction_constraints names feature " + std::to_string(f) + " but the booster has " +
+                       std::to_string(b.forest.num_feature) + " features; nothing was enqueued and the forest is unchanged");
+  const bool interacting = b.forest.num_feature >= 1 && b.forest.num_feature <= kGrowMaxFeatures &&
+                           grow_interact_active(b.grow_interact.data(), ngroups, b.forest.num_feature);
+  if (interacting) {
+    const std::string tail = "; nothing was enqueued and the forest is unchanged";
+    if (!weighted)
+      throw OhxError(w0 + " keeps row counts, and its split kernels no feature sets: with ohx_interaction_constraints active call "
+                     "OHXBoosterBoostTreesWeighted (weights may be NULL) or a later form, or set it to []" + tail);
+    if (b.grow_objective == kGrowObjQuantile)
+      throw OhxError(w0 + ": ohx_objective=quantile grows with the pair path's own split kernels, which read no feature sets: set "
+                     "ohx_interaction_constraints to [], or ohx_objective=squarederror" + tail);
+  }
   if (!b.margin_error.empty()) throw OhxError(b.margin_error);
   if (c.labels == nullptr) throw OhxError(w0 + ": labels is NULL");
   if (c.cut_ptr == nullptr || c.cut_values == nullptr) throw OhxError(w0 + ": the cuts are NULL");
@@ -2568,6 +2610,9 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     n_node = grow_num_selected(n_lvl, b.grow_bynode);
     if (n_lvl == 0 || n_node == 0) throw OhxError(w0 + ": ohx_colsample_bylevel and ohx_colsample_bynode must be finite, > 0 and <= 1");
   }
+  if (interacting && (n_lvl != n_sel || n_node != n_lvl))
+    throw OhxError(w0 + ": ohx_interaction_constraints is not crossed with the draws of ohx_colsample_bylevel and ohx_colsample_bynode: "
+                   "set both to 1, or ohx_interaction_constraints to []; nothing was enqueued and the forest is unchanged");
   grow_check_cuts(c.cut_ptr, c.cut_values, F, what);
   if (ev.present) {
     if (ev.patience < 0) throw OhxError(w0 + ": patience must be >= 0");
@@ -2612,8 +2657,10 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   kind.constrained = weighted && !b.grow_mono.empty();
   kind.regularised = weighted && !kind.constrained && (b.grow_alpha != 0.0f || b.grow_max_delta_step != 0.0f);
   kind.colsampled = colsampled;
-  kind.pairs = weighted && (b.grow_objective != kGrowObjSquared || b.grow_pairs_on || kind.regularised || kind.constrained || colsampled);
-  if (kind.regularised && !colsampled)
+  kind.interacting = interacting;
+  kind.pairs = weighted && (b.grow_objective != kGrowObjSquared || b.grow_pairs_on || kind.regularised || kind.constrained || colsampled ||
+                            interacting);
+  if (kind.regularised && !colsampled && !interacting)
     kind.reg_splits = grow_reg_splits(GrowRegHess{(double)wt.min_child_weight, b.grow_alpha, b.grow_max_delta_step});
   kind.quantile = weighted && b.grow_objective == kGrowObjQuantile;
   kind.metric = weighted ? b.grow_metric : kGrowMetricRmse;
@@ -2697,6 +2744,12 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     g.h_mono_constraints.ensure(F);
     for (uint32_t f = 0; f < F; ++f) g.h_mono_constraints.p[f] = f < b.grow_mono.size() ? b.grow_mono[f] : (int8_t)0;
   }
+  if (kind.interacting) {
+    room(g.d_interact_sets, 4 * stride, 8, "the feature sets of the interaction constraints");
+    room(g.d_interact_groups, 2 * (size_t)ngroups, 8, "the groups of the interaction constraints");
+    g.h_interact_groups.ensure(2 * (size_t)ngroups);
+    std::copy(b.grow_interact.begin(), b.grow_interact.end(), g.h_interact_groups.p);
+  }
   const size_t bag_words = (size_t)((n + 63) / 64);
   if (sampled) {
     if (k_s != kGrowSampleOne) room(g.d_bag, bag_words, 8, "the bag's bit plane");
@@ -2766,6 +2819,9 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
   if (colsampled) HIP_CHECK(hipMemcpyAsync(g.d_level_lists.p, g.h_level_lists.p, level_bytes, hipMemcpyHostToDevice, stream));
   if (kind.pairs) HIP_CHECK(hipMemcpyAsync(g.d_identity.p, g.h_identity.p, F, hipMemcpyHostToDevice, stream));
   if (kind.constrained) HIP_CHECK(hipMemcpyAsync(g.d_mono_constraints.p, g.h_mono_constraints.p, F, hipMemcpyHostToDevice, stream));
+  if (kind.interacting)
+    HIP_CHECK(hipMemcpyAsync(g.d_interact_groups.p, g.h_interact_groups.p, 2 * (size_t)ngroups * sizeof(uint64_t), hipMemcpyHostToDevice,
+                             stream));
   if (host_form) HIP_CHECK(hipMemcpyAsync(g.d_labels.p, c.labels, n * sizeof(float), hipMemcpyHostToDevice, stream));
   initial_margin(d, g.d_pred.p, n);
   if (ev.present) HIP_CHECK(hipMemsetAsync(g.d_sums.p, 0, nsums * sizeof(unsigned long long), stream));
@@ -2837,6 +2893,16 @@ void boost_trees(BoosterObj& b, const BoostCall& c) {
     kind.reg_splits = kind.constrained    ? grow_colsample_splits(cs, GrowMonoArgs{reg, g.d_mono_bounds.p, g.d_mono_constraints.p})
                       : kind.regularised ? grow_colsample_splits(cs, reg)
                                          : grow_colsample_splits(cs, GrowFixedHess{(double)wt.min_child_weight});
+  } else if (kind.interacting) {
+    const GrowRegHess reg{(double)wt.min_child_weight, b.grow_alpha, b.grow_max_delta_step};
+    const uint64_t* groups = g.d_interact_groups.p;
+    uint64_t* sets = g.d_interact_sets.p;
+    kind.reg_splits =
+        kind.constrained ? grow_interact_splits(GrowInteractArgs<GrowMonoArgs>{groups, sets, ngroups,
+                                                                               GrowMonoArgs{reg, g.d_mono_bounds.p, g.d_mono_constraints.p}})
+        : kind.regularised ? grow_interact_splits(GrowInteractArgs<GrowRegHess>{groups, sets, ngroups, reg})
+                           : grow_interact_splits(GrowInteractArgs<GrowFixedHess>{groups, sets, ngroups,
+                                                                                 GrowFixedHess{(double)wt.min_child_weight}});
   } else if (kind.constrained) {
     kind.reg_splits = grow_mono_splits(GrowMonoArgs{GrowRegHess{(double)wt.min_child_weight, b.grow_alpha, b.grow_max_delta_step},
                                                     g.d_mono_bounds.p, g.d_mono_constraints.p});
@@ -3547,6 +3613,10 @@ int XGBoosterSetParam(BoosterHandle handle, const char* name, const char* value)
   } else if (n == "ohx_monotone_constraints") {
     // boosting: c_f of every feature (docs/28_monotone_constraints.md); on the handle, in no file
     b->grow_mono = parse_monotone_constraints(value);
+  } else if (n == "ohx_interaction_constraints") {
+    // boosting: the groups of features that may act together in a tree (docs/35_interaction_constraints.md); on the
+    // handle, in no file
+    b->grow_interact = parse_interaction_constraints(value);
   } else if (n == "ohx_colsample_bylevel" || n == "ohx_colsample_bynode") {
     // boosting: the fraction of a tree's features a level sees, and of a level's a node does
     // (docs/29_colsample_level_node.md); on the handle, in no file

@@ -117,6 +117,59 @@ uint32_t grow_pick_node_features(uint64_t seed, uint64_t i, uint32_t p, const ui
   return n_node;
 }
 
+bool grow_interact_parse(const char* value, std::vector<uint64_t>* words) {
+  if (value == nullptr || words == nullptr) return false;
+  std::vector<uint64_t> w;
+  const char* p = value;
+  auto blanks = [&]() {
+    while (*p == ' ' || *p == '\t') ++p;
+  };
+  blanks();
+  if (*p++ != '[') return false;
+  blanks();
+  if (*p != ']') {
+    for (;;) {   // a group
+      if (*p++ != '[') return false;
+      if (w.size() == 2 * (size_t)kGrowMaxGroups) return false;
+      uint64_t g[2] = {0, 0};
+      for (;;) {   // an id
+        blanks();
+        if (*p < '0' || *p > '9') return false;
+        uint32_t f = 0;
+        while (*p >= '0' && *p <= '9') {
+          f = f * 10 + (uint32_t)(*p++ - '0');
+          if (f >= kGrowMaxFeatures) return false;
+        }
+        if (grow_interact_has(g, f)) return false;
+        g[f >> 6] |= 1ull << (f & 63u);
+        blanks();
+        if (*p == ']') break;
+        if (*p++ != ',') return false;
+      }
+      ++p;
+      w.push_back(g[0]);
+      w.push_back(g[1]);
+      blanks();
+      if (*p == ']') break;
+      if (*p++ != ',') return false;
+      blanks();
+    }
+  }
+  ++p;
+  blanks();
+  if (*p != '\0') return false;
+  words->swap(w);
+  return true;
+}
+
+bool grow_interact_active(const uint64_t* groups, uint32_t ngroups, uint32_t F) {
+  uint64_t all[2];
+  grow_interact_all(F < kGrowMaxFeatures ? F : kGrowMaxFeatures, all);
+  for (uint32_t g = 0; g < ngroups; ++g)
+    if ((all[0] & ~groups[2 * g]) == 0 && (all[1] & ~groups[2 * g + 1]) == 0) return false;
+  return ngroups != 0;
+}
+
 Tree grow_assemble_tree(const GrowNode* nodes, uint32_t n, uint32_t num_feature, uint32_t max_nodes) {
   if (n == 0 || n > max_nodes || n % 2 == 0) throw OhxError("grown tree: " + std::to_string(n) + " nodes is not a tree");
   Tree t;

@@ -414,6 +414,55 @@ struct GrowColsampleArgs {
   OHX_GROW_HD uint64_t col_key(uint32_t round) const { return grow_col_key(seed, tree0 + round); }
 };
 
+// ---- interaction constraints ("ohx_interaction_constraints"; design in docs/35_interaction_constraints.md) ----
+
+// A set of feature ids is two uint64 words, bit f % 64 of word f / 64.  The groups are ngroups x 2 words.
+constexpr uint32_t kGrowMaxGroups = 64;
+static_assert(kGrowMaxFeatures == 128, "a set of features is two 64-bit words");
+OHX_GROW_HD inline bool grow_interact_has(const uint64_t set[2], uint32_t f) {
+  return f < kGrowMaxFeatures && (((f < 64 ? set[0] : set[1]) >> (f & 63u)) & 1ull) != 0;
+}
+// every feature 0 .. F - 1 (F <= 128)
+OHX_GROW_HD inline void grow_interact_all(uint32_t F, uint64_t out[2]) {
+  out[0] = F >= 64 ? ~0ull : (1ull << F) - 1ull;
+  out[1] = F >= 128 ? ~0ull : (F > 64 ? (1ull << (F - 64)) - 1ull : 0ull);
+}
+// The header's A of a node whose path has split on the features P: every feature 0 .. F - 1 where P is empty (the root),
+// else P and every group that holds all of P.  The one function the host and the split kernels use.
+OHX_GROW_HD inline void grow_interact_allowed(const uint64_t P[2], const uint64_t* groups, uint32_t ngroups, uint32_t F, uint64_t out[2]) {
+  if ((P[0] | P[1]) == 0) {
+    grow_interact_all(F, out);
+    return;
+  }
+  uint64_t a0 = P[0], a1 = P[1];
+  for (uint32_t g = 0; g < ngroups; ++g) {
+    const uint64_t g0 = groups[2 * g], g1 = groups[2 * g + 1];
+    if ((P[0] & ~g0) == 0 && (P[1] & ~g1) == 0) {
+      a0 |= g0;
+      a1 |= g1;
+    }
+  }
+  out[0] = a0;
+  out[1] = a1;
+}
+// The value of "ohx_interaction_constraints" by the header's grammar: the groups' words into `words` (ngroups x 2) and
+// true, or false, and `words` as it was.
+bool grow_interact_parse(const char* value, std::vector<uint64_t>* words);
+// Whether the groups take a candidate away from some node of a booster with F features: false for no group, and where a
+// group holds every feature 0 .. F - 1.
+bool grow_interact_active(const uint64_t* groups, uint32_t ngroups, uint32_t F);
+// What a split kernel of a call under interaction constraints takes: the groups, the sets of the tree at hand - four words
+// a node id, P then A; the root's are ({}, every feature) and are never read, so nothing is reset between trees: every
+// other node has its sets written when its parent splits - and the policy the call has underneath (GrowFixedHess,
+// GrowRegHess or GrowMonoArgs), whose gain, leaf solve and records are unchanged.
+template <class Policy>
+struct GrowInteractArgs {
+  const uint64_t* groups;
+  uint64_t* sets;
+  uint32_t ngroups;
+  Policy inner;
+};
+
 // A node as the device leaves it.  Children are written as leaves when their parent splits and overwritten if they
 // split in turn, so every record is complete whenever the level loop stops.
 struct GrowNode {
@@ -930,6 +979,15 @@ GrowPairSplits grow_mono_splits(const GrowMonoArgs& m);
 GrowPairSplits grow_colsample_splits(const GrowColsampleArgs& c, const GrowFixedHess& hess);
 GrowPairSplits grow_colsample_splits(const GrowColsampleArgs& c, const GrowRegHess& hess);
 GrowPairSplits grow_colsample_splits(const GrowColsampleArgs& c, const GrowMonoArgs& m);
+// ---- interaction constraints on the GPU (grow_interact.hip; design in docs/35_interaction_constraints.md) ----
+
+// The split launches of a call under interaction constraints, under each hessian policy of the pair path:
+// grow_split_interact_kernel for levels 0 - 7 and grow_deep_split_interact_kernel below, over the tree's list, with a
+// (node, column) outside the node's allowed set left an invalid candidate.  x.groups (x.ngroups x 2 words) and x.sets
+// (four words a node of the call's node stride) are on the device.  Empty launches where x is unsound.
+GrowPairSplits grow_interact_splits(const GrowInteractArgs<GrowFixedHess>& x);
+GrowPairSplits grow_interact_splits(const GrowInteractArgs<GrowRegHess>& x);
+GrowPairSplits grow_interact_splits(const GrowInteractArgs<GrowMonoArgs>& x);
 // Enqueues grow_deep_stage_kernel and grow_deep_walk_sse_kernel: eval_nodes from the records of tree `round`, then
 // launch_grow_walk_sse_weighted's walk and sums over the rows of `a`, its nodes read from HBM.  Returns a hipError_t.
 int launch_grow_walk_sse_deep(const GrowEvalArgs& a, const GrowDeepArgs& d, uint32_t blocks, uint32_t round, uint32_t set,

@@ -334,6 +334,29 @@ extern "C" __attribute__((visibility("default"))) int ohx_grow_colsample_has(uin
   return grow_node_has_feature(seed, tree, node, list, n_lvl, n_node, f) ? 1 : 0;
 }
 
+// ---- interaction constraints (docs/35_interaction_constraints.md) ----
+
+// grow_interact_parse: the groups of `value` as words[0 .. 2 * *ngroups) (words holds 128), and *active =
+// grow_interact_active for a booster of F features; -1 where the grammar refuses the value
+extern "C" __attribute__((visibility("default"))) int ohx_grow_interact_parse(const char* value, uint32_t F, uint64_t* words,
+                                                                             uint32_t* ngroups, int* active) {
+  std::vector<uint64_t> w;
+  if (!grow_interact_parse(value, &w)) {
+    synth_set_error("ohx_grow_interact_parse: ohx_interaction_constraints is not a list of groups such as [[0,2],[1,3,4]]");
+    return -1;
+  }
+  for (size_t k = 0; k < w.size(); ++k) words[k] = w[k];
+  *ngroups = (uint32_t)(w.size() / 2);
+  *active = grow_interact_active(w.data(), *ngroups, F) ? 1 : 0;
+  return 0;
+}
+
+// grow_interact_allowed: out = A of a node whose path has split on the features P
+extern "C" __attribute__((visibility("default"))) void ohx_grow_interact_allowed(const uint64_t P[2], const uint64_t* groups,
+                                                                                uint32_t ngroups, uint32_t F, uint64_t out[2]) {
+  grow_interact_allowed(P, groups, ngroups, F, out);
+}
+
 // the level plan of a sampled call: plan_grow_weighted over n_sel = grow_num_selected(num_feature, colsample) features;
 // info as ohx_grow_plan_weighted's with info[3] the bin planes of all num_feature features, and info[8] = n_sel
 extern "C" __attribute__((visibility("default"))) int ohx_grow_plan_sampled(uint64_t nrow, uint32_t num_feature, float colsample,

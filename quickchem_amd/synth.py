@@ -120,6 +120,9 @@ def _load():
         lib.ohx_grow_colsample_pick.argtypes = [C.c_int, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float,
                                                 C.c_void_p, C.c_void_p]
         lib.ohx_grow_colsample_has.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32]
+        lib.ohx_grow_interact_parse.argtypes = [C.c_char_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
+        lib.ohx_grow_interact_allowed.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p]
+        lib.ohx_grow_interact_allowed.restype = None
         lib.ohx_grow_plan_sampled.argtypes = [C.c_uint64, C.c_uint32, C.c_float, C.c_uint64, C.c_int, C.c_int, C.c_void_p,
                                               C.c_void_p]
         lib.ohx_grow_deep_batch.argtypes = []
@@ -900,6 +903,35 @@ def boost_node_has_feature(seed: int, tree: int, node: int, level_list, n_node: 
     """csrc/grow.hpp grow_node_has_feature: the rank the split kernels compute; f must be in the level's list."""
     lst = np.ascontiguousarray(level_list, dtype=np.uint8)
     return bool(_load().ohx_grow_colsample_has(int(seed) & _U64, int(tree) & _U64, node, lst.ctypes.data, len(lst), n_node, f))
+
+
+def _feature_set(words) -> set:
+    return {64 * k + b for k in (0, 1) for b in range(64) if (int(words[k]) >> b) & 1}
+
+
+def _feature_words(features):
+    w = [0, 0]
+    for f in features:
+        w[int(f) >> 6] |= 1 << (int(f) & 63)
+    return w
+
+
+def interact_parse(value: str, num_feature: int):
+    """csrc/grow.cpp grow_interact_parse and grow_interact_active -> (the groups as sorted lists of feature ids, whether
+    they are active for a booster of num_feature features); raises RuntimeError where the grammar refuses the value."""
+    words = np.zeros(128, dtype=np.uint64)
+    n, active = C.c_uint32(), C.c_int()
+    _check(_load().ohx_grow_interact_parse(value.encode(), num_feature, words.ctypes.data, C.addressof(n), C.addressof(active)))
+    return [sorted(_feature_set(words[2 * g:2 * g + 2])) for g in range(int(n.value))], bool(active.value)
+
+
+def interact_allowed(path, groups, num_feature: int) -> set:
+    """csrc/grow.hpp grow_interact_allowed: the features a node may split on whose path has split on `path`."""
+    P = np.array(_feature_words(path), dtype=np.uint64)
+    gw = np.array([w for g in groups for w in _feature_words(g)] or [0, 0], dtype=np.uint64)
+    out = np.zeros(2, dtype=np.uint64)
+    _load().ohx_grow_interact_allowed(P.ctypes.data, gw.ctypes.data, len(groups), num_feature, out.ctypes.data)
+    return _feature_set(out)
 
 
 def grow_plan_sampled(nrow: int, num_feature: int = NFEAT, colsample: float = 1.0, ncuts: int = 0, max_depth: int = 6,

@@ -50,6 +50,11 @@ calls with row weights then take the constrained split kernels over the pair pat
 --max-delta-step 0.5` - the same pair and histogram kernels and the same gain form - the difference is the split kernels
 and the trees they choose; the node counts stand beside the times.
 
+`--interaction-constraints "[[0,1,2],[3,4]]"` sets "ohx_interaction_constraints" on every booster that is timed
+(docs/35_interaction_constraints.md): the calls with row weights then take the split kernels of grow_interact.hip over the
+pair path.  Against a run with `--pairs on` - the same pair and histogram kernels - the difference is the split kernels and
+the trees they choose; the node counts stand beside the times.
+
 `--colsample-bylevel L` and `--colsample-bynode N` set "ohx_colsample_bylevel" and "ohx_colsample_bynode" on every booster
 that is timed (docs/29_colsample_level_node.md), with `--subsample` / `--colsample`: the sampled calls then add the columns
 of a level's own list and take the column-sampled split kernels over the pair path.  Against a run with `--pairs on` and
@@ -169,6 +174,8 @@ def main():
     ap.add_argument("--max-delta-step", type=float, default=0.0, help="ohx_max_delta_step of the timed boosters")
     ap.add_argument("--eval-metric", choices=("rmse", "mae", "pseudohuber", "quantile"), default="rmse", help="ohx_eval_metric of the timed boosters")
     ap.add_argument("--monotone", default=None, help="ohx_monotone_constraints of the timed boosters, as the parameter is written: \"(1,0,-1)\"")
+    ap.add_argument("--interaction-constraints", default=None,
+                    help="ohx_interaction_constraints of the timed boosters, as the parameter is written: \"[[0,1,2],[3,4]]\"")
     ap.add_argument("--colsample-bylevel", type=float, default=None, help="ohx_colsample_bylevel of the timed boosters (with --subsample / --colsample)")
     ap.add_argument("--colsample-bynode", type=float, default=None, help="ohx_colsample_bynode of the timed boosters (with --subsample / --colsample)")
     args = ap.parse_args()
@@ -185,8 +192,9 @@ def main():
     if (args.colsample_bylevel is not None or args.colsample_bynode is not None) and not sampled:
         ap.error("--colsample-bylevel / --colsample-bynode act on the calls that carry a seed: give --subsample / --colsample")
     regularised = args.reg_alpha != 0.0 or args.max_delta_step != 0.0 or args.eval_metric != "rmse"
-    if (args.objective != "squarederror" or args.pairs != "auto" or regularised or args.monotone is not None) and (args.holdout or not (sampled or args.deep or args.weights != "none")):
-        ap.error("--objective / --pairs / --reg-alpha / --max-delta-step / --eval-metric / --monotone time a call with row weights: give --weights, --subsample / --colsample or --deep, and no --holdout")
+    if (args.objective != "squarederror" or args.pairs != "auto" or regularised or args.monotone is not None or
+            args.interaction_constraints is not None) and (args.holdout or not (sampled or args.deep or args.weights != "none")):
+        ap.error("--objective / --pairs / --reg-alpha / --max-delta-step / --eval-metric / --monotone / --interaction-constraints time a call with row weights: give --weights, --subsample / --colsample or --deep, and no --holdout")
     assert torch.cuda.is_available(), "boost_timing needs the MI355X"
     torch.cuda.set_device(0)
     model = synth.make_model()
@@ -278,6 +286,7 @@ def main():
                         "ohx_grow_pairs": args.pairs}
     res["regularisation"] = {"ohx_reg_alpha": args.reg_alpha, "ohx_max_delta_step": args.max_delta_step, "ohx_eval_metric": args.eval_metric}
     res["monotone_constraints"] = args.monotone
+    res["interaction_constraints"] = args.interaction_constraints
     res["colsample"] = {"ohx_colsample_bylevel": args.colsample_bylevel, "ohx_colsample_bynode": args.colsample_bynode}
     res["pair_planes"] = synth.grow_pairs_plan(n, F, ncuts, args.max_depth, cus)
 
@@ -293,6 +302,8 @@ def main():
             b.set_param("ohx_eval_metric", args.eval_metric)
         if args.monotone is not None:
             b.set_param("ohx_monotone_constraints", args.monotone)
+        if args.interaction_constraints is not None:
+            b.set_param("ohx_interaction_constraints", args.interaction_constraints)
         if args.colsample_bylevel is not None:
             b.set_param("ohx_colsample_bylevel", repr(args.colsample_bylevel))
         if args.colsample_bynode is not None:
@@ -356,7 +367,8 @@ def main():
         per_round = (res[f"rounds_{args.rounds}"]["median_s"] - res["rounds_1"]["median_s"]) / (args.rounds - 1)
         res["per_round_s"] = per_round
         res["one_off_s"] = res["rounds_1"]["median_s"] - per_round
-    if not args.skip_rmse and not args.holdout and not args.deep_only and args.objective == "squarederror" and not regularised and args.monotone is None:
+    if not args.skip_rmse and not args.holdout and not args.deep_only and args.objective == "squarederror" and not regularised and args.monotone is None and \
+            args.interaction_constraints is None:
         b = capi.Booster(model_buffer=model.image)
         res["rmse_before"] = rmse(b)
         b.refit_leaves_device(d, labels.data_ptr(), n, eta=1.0, reg_lambda=1.0, stream=stream)
